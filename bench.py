@@ -10,12 +10,20 @@ whole-job crops/s.  Rank 0 prints ONE JSON line.
 The K timed steps are taken in turn by TWO classifier lanes per GPU (two handles of the
 library = two streams and workspaces, `rtdfd_amd._lib.ClassifierLanes`): two forwards are
 in flight, every forward is still one whole 256-crop batch with the same kernels and the
-same result bits.  One step in 20 carries the per-launch HIP events and is ordered ALONE on
-the device (`dfd_wait_for`), so the roofline durations are those of isolated kernels; the
-overlap that step gives up is inside the timed region.  `DFD_BENCH_LANES=1` = one forward
-in flight (the loop of rounds 1-3; reported as `one_forward_in_flight` either way).
+same result bits.  `DFD_BENCH_LANES=1` = one forward in flight (the loop of rounds 1-3).
 
-Extra objects on that line:
+A plain run sets up, warms up, times the K steps and prints the headline line (metric,
+value, unit, ms_per_step, dtype, config) - nothing else.  `--dump-outputs DIR` writes what
+the last timed step computed, its batch x 1 fp32 logits, to DIR/logits.npy (inputs and
+weights are seeded: two builds compare output for output).
+
+`--full` adds everything else.  One timed step in 20 then carries the per-launch HIP events
+and is ordered ALONE on the device (`dfd_wait_for`), so the roofline durations are those of
+isolated kernels; the overlap that step gives up is inside the timed region.  After the
+timed loop: lane-equality and oracle-parity checks, and the extra objects below
+(`--no-e2e`, `--no-streams`, `--no-cpu-baseline` leave single ones out).
+
+Extra objects on a --full line:
   roofline      depthwise-conv kernel family against the HBM roofline: algorithmic bytes
                 (25.11 MB per crop) x crops per launch-set / the 16 depthwise
                 launches' duration, measured with HIP events on the library's stream
@@ -832,11 +840,19 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=BATCH)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--layers", action="store_true", help="print the per-launch table to stderr")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the 1080p end-to-end extra (configs[2]/[3])")
-    ap.add_argument("--no-streams", action="store_true", help="skip the frame-sharded 8-stream extra (configs[4])")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: instrumented steps (roofline, per-launch times), lane and oracle "
+                         "checks, the other classifier loops and precisions, the 1080p end-to-end and stream extras, the "
+                         "CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the logits of the last timed step to DIR/logits.npy (float32, batch x 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--layers", action="store_true", help="with --full: print the per-launch table to stderr")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the 1080p end-to-end extra (configs[2]/[3])")
+    ap.add_argument("--no-streams", action="store_true", help="with --full: skip the frame-sharded 8-stream extra (configs[4])")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout carries exactly ONE line (the JSON): libraries that print there (RCCL's version banner at communicator
     # creation) are sent to stderr for the whole run; the JSON goes to the saved descriptor.
@@ -890,7 +906,7 @@ def main():
 
     # dfd_warmup sizes the workspace, splits the weights and measures the GEMM tile of every layer shape at this batch
     # (classifier) and at the e2e extra's 64 frames (detector): the only place the library synchronises for tuning.
-    h.warmup(args.batch, 0 if args.no_e2e else E2E_FRAMES)
+    h.warmup(args.batch, E2E_FRAMES if args.full and not args.no_e2e else 0)
     # TWO forwards in flight (rtdfd_amd._lib.ClassifierLanes: a second handle = its own stream and workspace, the same
     # weights and tile table) take the K steps in turn.  A step is still one batch-256 forward; the second forward's
     # kernels fill the launch gaps and under-filled late layers of the first.  DFD_BENCH_LANES=1 is
@@ -917,11 +933,14 @@ def main():
     # step, the other lane's next step starts when it has finished; no host wait, so the host stays ahead of the GPU and
     # the gaps between its events are kernel time).  Its events then time isolated kernels, which is what the roofline
     # object must describe; the time the other lane idles beside it is inside the timed region and `value` pays for it.
+    # Only a --full run instruments steps: a plain run times the two lanes and nothing else.
     nl = len(lanes)
-    every = PROFILE_EVERY if args.steps >= PROFILE_EVERY else max(nl, args.steps // nl * nl)
-    every = (every + nl - 1) // nl * nl                          # instrumented steps fall on lane 0 ...
-    first = every // 2 // nl * nl                                # ... in the middle of each window of `every` steps
-    h.set_option("profile_stride", every // nl)
+    every, first = 0, args.steps
+    if args.full:
+        every = PROFILE_EVERY if args.steps >= PROFILE_EVERY else max(nl, args.steps // nl * nl)
+        every = (every + nl - 1) // nl * nl                      # instrumented steps fall on lane 0 ...
+        first = every // 2 // nl * nl                            # ... in the middle of each window of `every` steps
+        h.set_option("profile_stride", every // nl)
     t0 = time.perf_counter()
     for i in range(args.steps):
         if i == first:
@@ -933,11 +952,48 @@ def main():
     lanes.sync()
     barrier()
     dt = time.perf_counter() - t0
-    steps_seen, layers = h.profile_end()
+    if args.full:
+        steps_seen, layers = h.profile_end()
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device=_red_dev(local_rank))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+
+    crops = args.batch * args.steps * world
+    value = crops / dt
+    out = {
+        "metric": "face-crops/sec (224x224 crops through EfficientNet-B0 classify)",
+        "value": round(value, 1), "unit": "crops/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic (torch.manual_seed(1) randn crops, seeded random-init weights)",
+        "config": {"workload": "configs[1]: batch=256 random 224x224 crops, EfficientNet-B0 fp32 inference",
+                   "batch_per_gpu": args.batch, "parallelism": f"frame-shard x{world}, no data-path collective",
+                   "forwards_in_flight": nl, "lanes_overlap_check_untimed": overlap,
+                   "arithmetic": "fp32 storage and accumulation; 1x1-conv products are fp32-exact (each operand = exact sum "
+                                 "of three bf16 terms, six cross terms on the bf16 MFMA; the dropped terms are < 2^-24 "
+                                 "relative); DFD_SPLIT_GEMM=0 runs the same GEMMs on the fp32 MFMA instead"},
+    }
+    # what a caller of the timed path receives from its last step: that step's logits (lane (steps - 1) % lanes); the
+    # inputs and weights are seeded, so two builds can be compared output for output
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last = ys[(args.steps - 1) % nl].download((args.batch, 1)).astype(np.float32)
+        name = "logits.npy" if rank == 0 else f"logits_rank{rank}.npy"
+        np.save(os.path.join(args.dump_outputs, name), last)
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), file=json_out, flush=True)
+        for b in ys[1:]:
+            b.free()
+        lanes.close()
+        xd.free()
+        yd.free()
+        h.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     for k in range(1, min(nl, args.steps)):                      # every lane computed the same batch: the same bits
         if not np.array_equal(ys[k].download((args.batch, 1)), yd.download((args.batch, 1))):
@@ -964,9 +1020,6 @@ def main():
         parity = float(np.abs(logits[:8] - want).max())
         if not parity <= 1e-3:
             sys.exit(f"timed-run logits differ from the oracle: max|d| = {parity:.3e} > 1e-3")
-
-    crops = args.batch * args.steps * world
-    value = crops / dt
 
     dw_ms = sum(ms for name, ms in layers if name.endswith(".dw")) / max(steps_seen, 1)
     all_ms = sum(ms for _, ms in layers) / max(steps_seen, 1)
@@ -1003,21 +1056,10 @@ def main():
                               "us": round(ms * 1e3, 1), "GBps": round(nbytes / (ms * 1e-3) / 1e9, 1),
                               "frac": round(nbytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 3)})
 
-    out = {
-        "metric": "face-crops/sec (224x224 crops through EfficientNet-B0 classify)",
-        "value": round(value, 1), "unit": "crops/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic (torch.manual_seed(1) randn crops, seeded random-init weights)",
-        "config": {"workload": "configs[1]: batch=256 random 224x224 crops, EfficientNet-B0 fp32 inference",
-                   "batch_per_gpu": args.batch, "parallelism": f"frame-shard x{world}, no data-path collective",
-                   "forwards_in_flight": nl, "lanes_overlap_check_untimed": overlap,
-                   "instrumented_steps": f"every {every}th step (from step {first}) carries per-launch HIP events and runs "
-                                         "alone (the other lane waits for it on the device, inside the timed region): "
-                                         "roofline durations are those of isolated kernels",
-                   "arithmetic": "fp32 storage and accumulation; 1x1-conv products are fp32-exact (each operand = exact sum "
-                                 "of three bf16 terms, six cross terms on the bf16 MFMA; the dropped terms are < 2^-24 "
-                                 "relative); DFD_SPLIT_GEMM=0 runs the same GEMMs on the fp32 MFMA instead"},
+    out["config"]["instrumented_steps"] = (f"every {every}th step (from step {first}) carries per-launch HIP events and runs "
+                                           "alone (the other lane waits for it on the device, inside the timed region): "
+                                           "roofline durations are those of isolated kernels")
+    out.update({
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                      # the contract's fraction prices ALGORITHMIC depthwise bytes (25.11 MB per crop) against the 16 launches'
@@ -1038,7 +1080,7 @@ def main():
                      "per_layer": per_layer},
         "kernel_ms_per_step": round(all_ms, 3),
         "parity": {"rows": 8, "max_abs_logit_err_vs_oracle": parity, "tol": 1e-3},
-    }
+    })
     if rank == 0 and world == 1:
         out["ms_by_kind"] = {k: round(sum(ms for n_, ms in layers if n_.split(".")[-1] == k) / max(steps_seen, 1), 3)
                              for k in ("dw", "se", "proj", "exp", "head", "avgpool", "mlp")}

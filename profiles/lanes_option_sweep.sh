@@ -1,5 +1,5 @@
 # Probe (GPU box, repo root): the classifier step of bench.py with two forwards in flight under the library option switches.
-run() { python bench.py --steps 40 --warmup 5 --no-e2e --no-streams --no-cpu-baseline 2>/dev/null | python -c "
+run() { python bench.py --steps 40 --warmup 5 --full --no-e2e --no-streams --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('$1', j['value'], j['ms_per_step'], j['roofline']['frac'], j['one_forward_in_flight']['crops_per_s'])"; }
 run base

@@ -15,7 +15,7 @@ export DFD_TILE_CACHE=$OUT/tiles.txt
 export TMPDIR=/tmp
 python3 profiles/b0_profile_driver.py > "$OUT/warm_fp32.log" 2>&1 || exit 1
 B0_BF16=1 python3 profiles/b0_profile_driver.py > "$OUT/warm_bf16.log" 2>&1 || exit 1
-python3 bench.py --steps 20 --warmup 5 --no-e2e --no-streams --no-cpu-baseline > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.err" || exit 1
+python3 bench.py --full --steps 20 --warmup 5 --no-e2e --no-streams --no-cpu-baseline > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.err" || exit 1
 # the MTCNN / e2e drivers once un-profiled too: their handles warm up other batch shapes, and a shape missing from the
 # tile cache is measured inside the profiled process (round 2's MTCNN table was dominated by those tuning launches)
 MT_FRAMES=64 python3 profiles/mtcnn_profile_driver.py > "$OUT/warm_mtcnn64.log" 2>&1 || exit 1
@@ -26,9 +26,9 @@ run() { name=$1; shift; rocprofv3 "$@" > "$OUT/$name.log" 2>&1 || { echo "rocpro
 # bench.py keeps two forwards in flight (its instrumented step runs alone): the trace of the default command averages
 # kernels that overlap another forward's; DFD_BENCH_LANES=1 is the same loop with one forward in flight - the isolated
 # durations bench.py's events (and its roofline object) report.  Both summaries are kept.
-run stats_bench_lanes2 --kernel-trace --stats -d "$OUT/stats_bench_lanes2" -o s --output-format csv -- python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-e2e --no-streams --no-cpu-baseline
+run stats_bench_lanes2 --kernel-trace --stats -d "$OUT/stats_bench_lanes2" -o s --output-format csv -- python3 "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-e2e --no-streams --no-cpu-baseline
 export DFD_BENCH_LANES=1
-run stats_bench --kernel-trace --stats -d "$OUT/stats_bench" -o s --output-format csv -- python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-e2e --no-streams --no-cpu-baseline
+run stats_bench --kernel-trace --stats -d "$OUT/stats_bench" -o s --output-format csv -- python3 "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-e2e --no-streams --no-cpu-baseline
 unset DFD_BENCH_LANES
 if [ "$MODE" = "bench" ]; then cd "$ROOT"; find "$OUT" -name "*.csv" | sort; exit 0; fi
 export MT_FRAMES=64
