@@ -193,6 +193,35 @@ int dfd_preprocess_crops(dfd_handle* h, const uint8_t* bgr, int height, int widt
 int dfd_classify_crops(dfd_handle* h, const uint8_t* bgr, int height, int width, int stride,
                        const int32_t* xywh, int n, int apply_clahe, float* logits_out);
 
+/* ---- Grad-CAM of the classifier ------------------------------------------------------------
+ * pytorch_grad_cam 1.3.x GradCAM(model, target_layers=[net._conv_head]) with targets None (category 0 = the logit),
+ * reference deepfake_detection.py:5-7 / :300-311 and model.py:100-102, computed without autograd (closed form of the
+ * gradient through the MLP head and the head conv's swish + pool):
+ *   cam7    (n,7,7)       float32: relu(sum_k alpha_k A_k) at the head conv's 7 x 7 grid, before any normalisation
+ *   heat    (n,224,224)   float32: scale_cam_image (min-max, cv2 INTER_LINEAR 7 -> 224), then the one-layer
+ *                                  aggregation's second min-max: the library's returned grayscale_cam
+ *   overlay (n,224,224,3) uint8:   show_cam_on_image(img, heat, use_rgb=True) in BGR order, img = the de-normalised
+ *                                  classifier input clamped to [0,1]; JET table: luts.JET_BGR (OpenCV parity unpinned)
+ * cam7 / heat / overlay may each be NULL.  The logits are bit-identical to dfd_classify_nchw(_device) /
+ * dfd_classify_crops on the same input and handle (the same forward runs).  n > max_batch: DFD_ERR_CAPACITY, the
+ * handle stays usable.  Cost over a classify call: one more launch of the head GEMM without swish (z = BN(conv_head)
+ * into the handle's dead expand buffer, handle activation type), an MLP backward (~0.34 GFLOP at n = 256) and one
+ * map kernel per call that reads z once (250 KB fp32 per crop) - measured in DESIGN sections 4 / 5.  No HBM is
+ * allocated: host-call outputs are staged in dead classifier workspace.
+ *
+ * dfd_gradcam_nchw_device: all pointers in HBM, enqueued on the handle's stream (no host wait), as
+ * dfd_classify_nchw_device; the input must stay untouched until the stream has passed the call (the overlay reads it). */
+int dfd_gradcam_nchw_device(dfd_handle* h, const float* nchw_dev, int n, float* logits_dev, float* cam7_dev,
+                            float* heat_dev, uint8_t* overlay_dev);
+/* the same from / to host memory (synchronises) */
+int dfd_gradcam_nchw(dfd_handle* h, const float* nchw_host, int n, float* logits_host, float* cam7_host,
+                     float* heat_host, uint8_t* overlay_host);
+/* dfd_classify_crops followed by Grad-CAM (reference analyze_face with a heat map, deepfake_detection.py:517-546): a crop
+ * the MTCNN stage rejects gets a NaN logit and all-zero cam7 / heat / overlay rows; the others run at the batch of the
+ * crops kept.  Outputs are host arrays of n rows. */
+int dfd_gradcam_crops(dfd_handle* h, const uint8_t* bgr, int height, int width, int stride, const int32_t* xywh, int n,
+                      int apply_clahe, float* logits_out, float* cam7_out, float* heat_out, uint8_t* overlay_out);
+
 /* compute_frequency_features, reference model.py:105-149: BGR (channels = 3) or gray (1) 8-bit
  * image -> gray -> cv2.resize 224x224 -> channel 0 = min-max-normalised log1p|fftshift(fft2)|,
  * channel 1 = min-max-normalised log1p|cv2.dct(gray/255)|.  out: (2,224,224) float32.  The model

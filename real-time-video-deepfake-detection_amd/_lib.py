@@ -61,6 +61,11 @@ SIGNATURES = {
                                        C.c_int, C.c_void_p]),
     "dfd_classify_crops": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                      C.c_int, C.c_void_p]),
+    "dfd_gradcam_nchw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dfd_gradcam_nchw_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "dfd_gradcam_crops": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dfd_frequency_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dfd_detect_faces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                    C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
@@ -368,6 +373,40 @@ class Handle:
         self._check(self._lib.dfd_classify_crops(self._p, _ptr(a), a.shape[0], a.shape[1], a.strides[0], _ptr(b),
                                                  b.shape[0], int(apply_clahe), _ptr(out)))
         return out
+
+    # -- Grad-CAM (include/dfd_hip.h, "Grad-CAM of the classifier")
+    @staticmethod
+    def _gradcam_outputs(n: int, overlay: bool, raw: bool):
+        return (np.empty((n, 1), np.float32), np.empty((n, 224, 224), np.float32),
+                np.empty((n, 224, 224, 3), np.uint8) if overlay else None,
+                np.empty((n, 7, 7), np.float32) if raw else None)
+
+    @staticmethod
+    def _gradcam_result(logits, heat, ov, cam7):
+        return (logits, heat) + ((ov,) if ov is not None else ()) + ((cam7,) if cam7 is not None else ())
+
+    def gradcam(self, x, overlay: bool = False, raw: bool = False):
+        """Grad-CAM of the head conv on (n,3,224,224) normalised input -> (logits (n,1), heat (n,224,224) float32
+        [, overlay (n,224,224,3) BGR uint8 if `overlay`] [, cam7 (n,7,7) if `raw`]).  The logits are `classify`'s bits."""
+        a = self._as_nchw(x)
+        lg, heat, ov, c7 = self._gradcam_outputs(a.shape[0], overlay, raw)
+        self._check(self._lib.dfd_gradcam_nchw(self._p, _ptr(a), a.shape[0], _ptr(lg), None if c7 is None else _ptr(c7),
+                                               _ptr(heat), None if ov is None else _ptr(ov)))
+        return self._gradcam_result(lg, heat, ov, c7)
+
+    def gradcam_device(self, x_dev: int, n: int, logits_dev: int, cam7_dev: Optional[int] = None,
+                       heat_dev: Optional[int] = None, overlay_dev: Optional[int] = None):
+        """Enqueue Grad-CAM on device buffers (no host wait); any of the three map outputs may be None."""
+        self._check(self._lib.dfd_gradcam_nchw_device(self._p, x_dev, int(n), logits_dev, cam7_dev, heat_dev, overlay_dev))
+
+    def gradcam_crops(self, frame, boxes, apply_clahe: bool = True, overlay: bool = False, raw: bool = False):
+        """`classify_crops` + Grad-CAM: as `gradcam`; a crop the MTCNN stage rejects has a NaN logit and zero maps."""
+        a, b = self._as_bgr(frame), self._as_boxes(boxes)
+        lg, heat, ov, c7 = self._gradcam_outputs(b.shape[0], overlay, raw)
+        self._check(self._lib.dfd_gradcam_crops(self._p, _ptr(a), a.shape[0], a.shape[1], a.strides[0], _ptr(b), b.shape[0],
+                                                int(apply_clahe), _ptr(lg), None if c7 is None else _ptr(c7), _ptr(heat),
+                                                None if ov is None else _ptr(ov)))
+        return self._gradcam_result(lg, heat, ov, c7)
 
     # -- frame forensics
     FORENSIC_KEYS = ("frequency", "noise", "ela", "edge", "color", "temporal")

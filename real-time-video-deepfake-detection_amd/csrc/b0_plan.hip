@@ -328,6 +328,25 @@ static int b0_forward_t(dfd_handle* h, const float* x, int n, float* logits_dev,
     return DFD_OK;
 }
 
+// The block loop above swaps io0 / io1 once per block: after b0_forward the last block's output is in io0 for an even
+// block count (16), in io1 otherwise.
+float* b0_last_block_out(const dfd_handle* h) { return h->b0.blocks.size() % 2 == 0 ? h->io0 : h->io1; }
+
+// Grad-CAM's z (gradcam.hip): after b0_forward on n crops, the head conv of the last block's output once more with
+// ACT_NONE - BN(conv_head(x15)) with BN folded into head.w / head.b, the pre-swish values of the head GEMM - into
+// z_out [n][49][1280] in the handle's activation type.  One extra launch of the same GEMM (same tile-table entry: the
+// table's key has no activation); the classify path itself is not touched.
+int b0_head_preact(dfd_handle* h, int n, void* z_out) {
+    const B0Plan& P = h->b0;
+    const B0Block& last = P.blocks.back();
+    const int hw = last.h_out * last.h_out;
+    if (h->act_bf16)
+        return pointwise_t<bf16_t>(h, reinterpret_cast<const bf16_t*>(b0_last_block_out(h)), P.head_w, P.head_b, nullptr, nullptr,
+                                   static_cast<bf16_t*>(z_out), n * hw, last.c_out, 1280, hw, ACT_NONE);
+    return pointwise_t<float>(h, b0_last_block_out(h), P.head_w, P.head_b, nullptr, nullptr, static_cast<float*>(z_out),
+                              n * hw, last.c_out, 1280, hw, ACT_NONE);
+}
+
 // fp32 activation storage, or - dfd_set_option(h, "bf16_activations", 1) - bf16 storage of every activation tensor
 // that reaches HBM (depthwise / block / expand / head outputs) with fp32 arithmetic and accumulation throughout:
 // BASELINE.json configs[3].  Squeeze-excite pools, gates, the pooled feature vector and the MLP head stay fp32.

@@ -198,8 +198,9 @@ int detect_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stri
 int haar_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride, float scale_factor, int min_neighbors,
              int min_size, int32_t* xywh_out, int max_out, int* n_out, int* n_candidates, int* n_total = nullptr);
 // frame_offs: per-crop byte offset of its frame inside frame_dev (null = single frame)
+// compact: in_nchw receives only the crops the MTCNN stage kept (h->n_compact rows, flags in h->crop_valid)
 int preprocess_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride, const int32_t* xywh, int n,
-                   int apply_clahe, const size_t* frame_offs = nullptr);
+                   int apply_clahe, const size_t* frame_offs = nullptr, bool compact = false);
 // boxes of resident frame(s) -> logits on the host, m <= max_batch: crop / CLAHE / MTCNN / 224 x 224, then the classifier
 // at the batch of the crops the cascade KEPT (reference deepfake_detection.py:377-380: `mtcnn()` -> None returns before
 // the model runs) - a rejected crop costs no classifier work and gets NaN.  Ends with a stream wait.
@@ -254,5 +255,9 @@ int b0_build_plan(dfd_handle* h);
 // Runs the classifier on h->stream.  `stop_at_features`: leave after the pooled 1280-vector.
 int b0_forward(dfd_handle* h, const float* nchw_dev, int n, float* logits_dev, B0Tap* tap,
                B0Prof* prof);
+// the buffer (io0 or io1) that holds the last block's output after b0_forward
+float* b0_last_block_out(const dfd_handle* h);
+// after b0_forward on n crops: the head conv WITHOUT its swish into z_out [n][49][1280] (activation type of the handle)
+int b0_head_preact(dfd_handle* h, int n, void* z_out);
 
 }  // namespace dfd

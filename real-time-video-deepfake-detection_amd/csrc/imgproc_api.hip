@@ -261,8 +261,8 @@ int preprocess_on_device(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww
 
 namespace dfd {
 int preprocess_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride, const int32_t* xywh, int n,
-                   int apply_clahe, const size_t* frame_offs) {
-    return preprocess_on_device(h, frame_dev, hh, ww, stride, xywh, n, apply_clahe, frame_offs);
+                   int apply_clahe, const size_t* frame_offs, bool compact) {
+    return preprocess_on_device(h, frame_dev, hh, ww, stride, xywh, n, apply_clahe, frame_offs, compact);
 }
 
 int classify_boxes(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride, const int32_t* xywh, int m,

@@ -7,9 +7,13 @@ does forensics, face detection, crop -> CLAHE -> 224x224 -> EfficientNet-B0 in O
 (`dfd_analyze_frame`); calibration, the small-face heuristic and the vote stay on the host as in
 the reference.  The MTCNN align/crop of reference :376-380 runs inside the same library call when the handle's
 weights carry the cascade (`mtcnn` below is its module-level mirror); a crop in which it finds no face yields no
-prediction, exactly as the reference's `None` (:378-380, :616-617, backend_server.py:166).  Deliberate differences
-(DESIGN.md section 8): GradCAM is not implemented (disabled in the reference's shipped configurations, :730-736 and
-backend_server.py:57), frames are returned un-annotated, nothing is printed per frame.  TTA (:408-443) is
+prediction, exactly as the reference's `None` (:378-380, :616-617, backend_server.py:166).  GradCAM (:5-7 imports
+`GradCAM`, `ClassifierOutputTarget`, `show_cam_on_image`, re-exported here from `gradcam`) runs on the GPU for the
+head conv the reference hooks (`dfd_gradcam_crops`); `DeepfakeDetector.explain_face` returns a face's probability with
+its heat map and BGR overlay, while `analyze_face` keeps returning None in its third slot whatever `enable_gradcam` is,
+as the reference does (:543-546; GradCAM is disabled in its shipped configurations, :730-736 and
+backend_server.py:57).  Deliberate differences: frames are returned un-annotated, nothing is
+printed per frame.  TTA (:408-443) is
 `analyze_face_with_tta` over `dfd_tta_augment`.  Face detection inside the fused call follows the reference's
 `detect_bounding_box` (face_detection.py:58-66): the SSD when the handle carries one, else - and after an SSD failure -
 the Haar cascade, else no faces ('frame_only').
@@ -28,6 +32,7 @@ from . import runtime
 from ._lib import DfdError, Handle
 from .face_detection import detect_bounding_box
 from .frame_analysis import FrameForensicAnalyzer
+from .gradcam import ClassifierOutputTarget, GradCAM, show_cam_on_image  # noqa: F401  (reference :5-7)
 from .tracker import TemporalTracker
 
 log = logging.getLogger(__name__)
@@ -205,6 +210,22 @@ class DeepfakeDetector:
         except (DfdError, ValueError) as e:
             log.warning("face analysis error: %s", e)
             return None, None, None
+
+    def explain_face(self, face_region):
+        """Where in the face the classifier saw a fake: {'fake_probability' (as `analyze_face` without TTA: same
+        calibration and small-face heuristic), 'heatmap' (224,224) float32 Grad-CAM map of the head conv in [0,1],
+        'overlay' (224,224,3) BGR uint8 (show_cam_on_image on the classifier input)}, or None when the MTCNN stage
+        finds no face.  The maps are in the 224x224 classifier frame of the (MTCNN-aligned) face."""
+        face = np.ascontiguousarray(face_region)
+        if face.ndim != 3 or face.shape[2] != 3 or face.shape[0] < 1 or face.shape[1] < 1:
+            return None
+        h, w = face.shape[:2]
+        with self._lock:
+            logits, heat, overlay = self.handle.gradcam_crops(face, [(0, 0, w, h)], apply_clahe=True, overlay=True)
+        p = self._finish_face(logits[0, 0], h, w)
+        if p is None:
+            return None
+        return {'fake_probability': p, 'heatmap': heat[0], 'overlay': overlay[0]}
 
     def _frame_on_gpu(self, frame, max_faces, jpeg: Optional[bytes] = None):
         """forensics + detection + per-face logits in one library call.  With `jpeg` the frame is decoded on the
