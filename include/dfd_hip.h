@@ -64,11 +64,6 @@ int dfd_max_batch(const dfd_handle* h);
  *   GEMM and depthwise kernel as separate launches.
  *   "fuse_late_skip" (default blocks 8 and 9: bit b set = block b keeps separate launches although "fuse_late" is on; chosen
  *   per block by measurement at batch 256).
- *   "se_in_proj" (default 0, env DFD_SE_IN_PROJ; measured slower, kept for the measurement): where a depthwise launch leaves final per-image pool sums (the
- *   whole-image launches of "fuse_late") the projection GEMM's blocks evaluate the squeeze-excite gate themselves
- *   (se_kernel's arithmetic, identical gate bits) instead of a separate launch per block.
- *   "se_thin" (default 0; measured slower, kept for the measurement): blocks 0-4 - the blocks of the narrow projection
- *   kernel (pw8_kernel) evaluate the squeeze-excite gate of the images they meet in a prologue, no se_kernel launch.
  *   "fuse_stem" (default 1, env DFD_FUSE_STEM): the stem conv is computed inside block 0's depthwise
  *   kernel (the 112x112x32 stem activation stays in LDS).
  *   "split_gemm" (default 1, env DFD_SPLIT_GEMM): 1x1 convs (N >= 16) and the detector's k x k convs run on
@@ -84,9 +79,7 @@ int dfd_max_batch(const dfd_handle* h);
  *   runtime maps streams of ONE priority onto a small pool of hardware queues and two main streams that land on the same
  *   queue run in line; streams of different priorities come from different pools. */
 int dfd_set_option(dfd_handle* h, const char* name, int value);
-/*   "fuse_se" (default 0): the squeeze-excite gate is computed by the last-arriving block of each image inside the
- *   depthwise launch (measured slower than the separate launch: DESIGN.md section 5; kept for the measurement).
- *   "bf16_activations" (default 0): every classifier activation that reaches HBM is stored as bf16 (arithmetic,
+/*   "bf16_activations" (default 0): every classifier activation that reaches HBM is stored as bf16 (arithmetic,
  *   accumulators, SE pools / gates and the MLP head stay fp32): BASELINE.json configs[3], DESIGN.md section 4a.
  *   "bf16_weight_planes" (3 or 1, default 3): with bf16 activations, the 1x1 convs multiply against the three exact
  *   bf16 planes of the fp32 weights (3) or against bf16-rounded weights (1).

@@ -7,7 +7,5 @@ DFD_FUSE_LATE=0 run fuse_late0
 DFD_FUSE_LATE_SKIP=0 run skip0
 DFD_FUSE_LATE_SKIP=1792 run skip8_9_10
 DFD_FUSE_LATE_SKIP=256 run skip8
-DFD_SE_IN_PROJ=1 run se_in_proj
-DFD_FUSE_SE=1 run fuse_se
 DFD_BENCH_LANES=4 run lanes4
 run base

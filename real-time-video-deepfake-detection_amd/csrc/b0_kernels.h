@@ -11,21 +11,6 @@ typedef __bf16 bf16_t;
 
 enum Act { ACT_NONE = 0, ACT_SWISH = 1, ACT_RELU = 2, ACT_PRELU = 3 };   // PRELU: bias points at [N bias][N slope]
 
-// Squeeze-excite finished inside the depthwise-family launch: the block that completes an image's pool partials last
-// (an agent-scope counter per image) computes mean -> FC(c_se) + swish -> FC(C) + sigmoid and writes gate[n][C] - the
-// separate se_kernel launch (16 per forward, ~9 us each plus a launch gap on either side) goes away.
-// counter == null: off (launch_se does it) - the default: measured at batch 256 the fused form is SLOWER (3.59 vs 3.04 ms
-// per step).  The gate is three dependent L2 round trips (pool partials -> FC1 -> FC2) wherever it runs; inside the
-// depthwise launch it adds the agent-scope acquire (~2-7 us on a CU that holds several blocks) in front of them and runs
-// on 4-8 waves instead of 16, and the launch cannot end before the last image's tail has.  Option "fuse_se" keeps it testable.
-struct SeTail {
-    const float *w1 = nullptr, *b1 = nullptr, *w2t = nullptr, *b2 = nullptr;
-    float* gate = nullptr;
-    unsigned* counter = nullptr;     // [n images], zero between launches (the last block of an image resets its entry)
-    float inv_hw = 0.f;
-    int c_se = 0;
-};
-
 // stem: 3x3 stride-2 conv, NCHW (n,3,224,224) -> NHWC (n,112,112,32), folded BN + swish.
 template <typename XT>
 void launch_stem(const float* x_nchw, const float* w /*[3][3][3][32]*/, const float* b,
@@ -38,7 +23,7 @@ void launch_stem(const float* x_nchw, const float* w /*[3][3][3][32]*/, const fl
 // runs on the bf16 MFMA with split-precision operands, K = 27 padded to 32)
 template <typename XT>
 void launch_stem_dw(const float* x_nchw, const unsigned short* ws3, int plane, int Kp, const float* bs, const float* Wd,
-                    const float* bd, XT* Y, float* P, XT* stem_out, int n, int* tiles, hipStream_t s, const SeTail& se = SeTail());
+                    const float* bd, XT* Y, float* P, XT* stem_out, int n, int* tiles, hipStream_t s);
 
 // pointwise conv as GEMM: Y[m][o] = act( sum_k X[m][k]*gate[m/HW][k] * W[o][k] + b[o] ) + R[m][o]
 // gate / R may be null.  X rows have stride K, Y/R rows stride N.
@@ -56,27 +41,6 @@ struct ConvGeom {
 // otherwise): Y[n][oy][ox][o] = act( conv(X, W[o][ky][kx][ci]) + b[o] (+ R before act if res_first) )
 bool launch_conv_gemm(const float* X, const float* W, const float* bias, const float* R, float* Y,
                       int n_img, const ConvGeom& g, int Cout, int act, bool res_first, hipStream_t s);
-
-// Squeeze-excite computed by the projection GEMM itself (option "se_in_proj", round 4): every block of the gated 1x1
-// conv first evaluates mean -> FC(c_se) + swish -> FC(C) + sigmoid for the (at most four) images its rows belong to -
-// the arithmetic of se_kernel operation by operation, so the gate bits do not depend on who computes them - writes the
-// gate rows to `gate` and goes on as before.  The 10-12 us se_kernel launch between the depthwise launch and the
-// projection (pure latency: three dependent L2 round trips on an otherwise idle chip, plus a launch gap on either
-// side) disappears for every layer whose pool sums are final per image (tiles == 1: the whole-image launches of
-// blocks 6-10 / 12-15).  P == nullptr: off (`gate` was written by launch_se).
-struct SeFuse {
-    const float* P = nullptr;        // [n][C] final per-image channel sums of the depthwise output
-    const float *w1 = nullptr, *b1 = nullptr, *w2t = nullptr, *b2 = nullptr;
-    float inv_hw = 0.f;
-    int c_se = 0;
-    int tiles = 1;                   // pool partials per image: P is [n][tiles][C]
-    bool thin = false;               // no se_kernel ran: the call must go to pw8_kernel, whose blocks evaluate the gate of the
-                                     // (at most two) images they meet in a light prologue (C <= 256, c_se <= 16; any `tiles`)
-};
-constexpr int SE_THIN_MAX_C = 256, SE_THIN_MAX_SE = 16;
-inline bool se_thin_supported(int C, int c_se) { return C <= SE_THIN_MAX_C && c_se >= 1 && c_se <= SE_THIN_MAX_SE; }
-constexpr int SE_FUSE_MAX_IMG = 4;   // images one GEMM block (<= 128 rows) can touch when an image has >= 49 rows
-constexpr int SE_FUSE_MAX_SE = 48;
 
 // Split-precision variants (gemm_split.hip): same contracts, the weight operand is the three-plane bf16 split
 // of W [N][K] written by launch_split_weights (out: 3 * split_weights_count(N, K) bf16, zero-padded planes).
@@ -105,10 +69,7 @@ int s6_table_import(S6Table* t, const char* text, size_t len);       // -> entri
 // XT = bf16_t: bf16 activation storage in and out, `planes` = 3 (fp32-exact weights) or 1 (bf16 weights).
 template <typename XT>
 bool launch_pointwise_split(S6Table* tab, const XT* X, const unsigned short* W3, const float* bias, const float* gate,
-                            const XT* R, XT* Y, int M, int K, int N, int HW, int act, int planes, hipStream_t s,
-                            const SeFuse* se = nullptr);
-// se usable with this shape: an image is at least 49 rows, so a block of <= 128 rows touches <= SE_FUSE_MAX_IMG images
-inline bool se_fuse_supported(int HW, int c_se) { return HW >= 49 && c_se >= 1 && c_se <= SE_FUSE_MAX_SE; }
+                            const XT* R, XT* Y, int M, int K, int N, int HW, int act, int planes, hipStream_t s);
 template <typename XT>
 bool launch_conv_gemm_split(S6Table* tab, const XT* X, const unsigned short* W3, const float* bias, const XT* R,
                             XT* Y, int n_img, const ConvGeom& g, int Cout, int act, bool res_first, int planes, hipStream_t s);
@@ -119,7 +80,7 @@ bool launch_conv_gemm_split(S6Table* tab, const XT* X, const unsigned short* W3,
 template <typename XT>
 bool launch_depthwise(const XT* X, const float* W /*[k][k][C]*/, const float* bias, XT* Y,
                       float* P, int n, int H, int C, int k, int stride, int pad_lo,
-                      int* tiles, hipStream_t s, const SeTail& se = SeTail());
+                      int* tiles, hipStream_t s);
 int depthwise_tiles(int H, int C, int k, int stride);
 // MBConv front half in one kernel: 1x1 expand (+BN+swish) computed per LDS halo tile on the bf16 MFMA with
 // split-precision operands (We3 = the three bf16 planes of We [C][Cin] from launch_split_weights, `plane`
@@ -128,7 +89,7 @@ int depthwise_tiles(int H, int C, int k, int stride);
 template <typename XT>
 bool launch_mbconv_front(const XT* Xin, int Cin, const unsigned short* We3, int plane, int Kp, const float* Wef, const float* be,
                          const float* Wd, const float* bd, XT* Y, float* P, int n, int H, int C, int k, int stride,
-                         int pad_lo, int* tiles, hipStream_t s, const SeTail& se = SeTail(), bool late = false);
+                         int pad_lo, int* tiles, hipStream_t s, bool late = false);
 // largest pool-tile count of the fused variants, -1: none.  late: also the whole-image launches of blocks 6-15
 // (mbconv_late_kernel, option "fuse_late")
 int mbconv_tiles(int H, int C, int k, int stride, int Cin, bool late = false);

@@ -126,20 +126,14 @@ const unsigned short* split_weights(dfd_handle* h, const float* W, int N, int K,
 
 // 1x1 conv.  XT = float: split path when enabled and the shape allows, else the fp32 MFMA kernel.
 // XT = bf16_t ("bf16_activations"): always the split GEMM's bf16-activation instances.
-// does this 1x1 conv run on the split GEMM (the only kernels that can evaluate the squeeze-excite gate themselves)?
-template <typename XT>
-static bool pointwise_on_split(const dfd_handle* h, int K, int N) {
-    return (sizeof(XT) == 2 || h->split_gemm) && N >= 16 && split_gemm_supports(K, N);
-}
-
 template <typename XT>
 int pointwise_t(dfd_handle* h, const XT* X, const float* W, const float* bias, const float* gate, const XT* R,
-                XT* Y, int M, int K, int N, int HW, int act, const SeFuse* se = nullptr) {
+                XT* Y, int M, int K, int N, int HW, int act) {
     constexpr bool BF = sizeof(XT) == 2;
     if ((BF || h->split_gemm) && N >= 16 && split_gemm_supports(K, N)) {       // never on M: batch-invariant results
         const unsigned short* w3 = split_weights(h, W, N, K);
         if (!w3) return DFD_ERR_HIP;
-        if (!launch_pointwise_split<XT>(h->gemm, X, w3, bias, gate, R, Y, M, K, N, HW, act, BF ? h->bf16_planes : 3, h->stream, se))
+        if (!launch_pointwise_split<XT>(h->gemm, X, w3, bias, gate, R, Y, M, K, N, HW, act, BF ? h->bf16_planes : 3, h->stream))
             return fail(h, DFD_ERR_CAPACITY, "1x1 conv M=%d K=%d: one image exceeds the 2^31-byte addressing of the split GEMM", M, K);
     } else {
         if constexpr (BF) return fail(h, DFD_ERR_STATE, "1x1 conv K=%d N=%d has no bf16-activation kernel", K, N);
@@ -212,18 +206,6 @@ static int b0_forward_t(dfd_handle* h, const float* x, int n, float* logits_dev,
     XT* const expbuf = reinterpret_cast<XT*>(h->expbuf);
     XT* const dwbuf = reinterpret_cast<XT*>(h->dwbuf);
     XT* const headbuf = reinterpret_cast<XT*>(h->headbuf);
-    // squeeze-excite inside the depthwise-family launch (option "fuse_se"): the last block of an image writes the gate
-    auto se_of = [&](const B0Block& b) {
-        SeTail t;
-        if (h->fuse_se && h->se_counter) {
-            t.w1 = b.se_w1; t.b1 = b.se_b1; t.w2t = b.se_w2; t.b2 = b.se_b2;
-            t.gate = h->gate; t.counter = h->se_counter;
-            t.inv_hw = 1.0f / (float)(b.h_out * b.h_out);
-            t.c_se = b.c_se;
-        }
-        return t;
-    };
-    const bool se_fused = h->fuse_se && h->se_counter;
     mk.mark("start");
     // block 0 has no expand conv: its depthwise input IS the stem output, so the two fuse (option "fuse_stem")
     const bool stem_fused = h->fuse_stem && P.blocks[0].expand == 1;
@@ -233,7 +215,7 @@ static int b0_forward_t(dfd_handle* h, const float* x, int n, float* logits_dev,
         const unsigned short* ws3 = split_weights(h, P.stem_w, 32, 27, true);          // [ky][kx][ci][co] = [27][32], transposed
         if (!ws3) return DFD_ERR_HIP;
         launch_stem_dw<XT>(x, ws3, (int)split_weights_count(32, 27), 64, P.stem_b, P.blocks[0].dw_w, P.blocks[0].dw_b, dwbuf,
-                           h->pool, want_stem ? io0 : (XT*)nullptr, n, &stem_tiles, s, se_of(P.blocks[0]));
+                           h->pool, want_stem ? io0 : (XT*)nullptr, n, &stem_tiles, s);
         mk.mark("b0.dw");                               // stem + depthwise of block 0 in one launch
     } else {
         launch_stem<XT>(x, P.stem_w, P.stem_b, io0, n, s);
@@ -257,7 +239,7 @@ static int b0_forward_t(dfd_handle* h, const float* x, int n, float* logits_dev,
             !(we3 = split_weights(h, b.exp_w, b.c_exp, b.c_in))) return DFD_ERR_HIP;
         if (we3 && launch_mbconv_front<XT>(cur, b.c_in, we3, (int)split_weights_count(b.c_exp, b.c_in), (b.c_in + 63) / 64 * 64,
                                            b.exp_w, b.exp_b, b.dw_w, b.dw_b, dwbuf, h->pool, n, b.h_in, b.c_exp,
-                                           b.kernel, b.stride, b.pad_lo, &tiles, s, se_of(b), late_here)) {
+                                           b.kernel, b.stride, b.pad_lo, &tiles, s, late_here)) {
             fused = true;
             mk.mark(layer_name(bi, "dw"));            // expand + depthwise in one launch
             if (tap && tap->name && q + ".exp" == tap->name)
@@ -275,36 +257,18 @@ static int b0_forward_t(dfd_handle* h, const float* x, int n, float* logits_dev,
             tiles = stem_tiles;
         } else if (!fused) {
             if (!launch_depthwise<XT>(dw_in, b.dw_w, b.dw_b, dwbuf, h->pool, n, b.h_in, b.c_exp, b.kernel,
-                                      b.stride, b.pad_lo, &tiles, s, se_of(b)))
+                                      b.stride, b.pad_lo, &tiles, s))
                 return fail(h, DFD_ERR_STATE, "no depthwise kernel for block %d", bi);
             mk.mark(layer_name(bi, "dw"));
         }
         if ((rc = tap_out(h, tap, q + ".dw", dwbuf, (size_t)m_out * b.c_exp))) return rc;
-        // option "se_in_proj": where the depthwise launch left FINAL per-image pool sums (tiles == 1: the whole-image
-        // launches of blocks 6-10 / 12-15) the projection GEMM evaluates the gate itself - no se_kernel launch
-        SeFuse sef;
-        // option "se_thin" (round 4; measured slower, off by default): the narrow projections of blocks 0-4 run on pw8_kernel,
-        // whose blocks evaluate the gate of the images they meet themselves - no se_kernel launch in front of them
-        const bool se_thin = !se_fused && h->se_thin && pointwise_on_split<XT>(h, b.c_exp, b.c_out) && !h->se_in_proj &&
-                             split_gemm_thin_supports(b.c_exp, b.c_out, b.h_out * b.h_out) && se_thin_supported(b.c_exp, b.c_se);
-        const bool se_in_proj = se_thin || (!se_fused && h->se_in_proj && tiles == 1 && se_fuse_supported(b.h_out * b.h_out, b.c_se) &&
-                                            pointwise_on_split<XT>(h, b.c_exp, b.c_out));
-        if (se_thin) {
-            sef.P = h->pool; sef.w1 = b.se_w1; sef.b1 = b.se_b1; sef.w2t = b.se_w2; sef.b2 = b.se_b2;
-            sef.inv_hw = 1.0f / (float)(b.h_out * b.h_out); sef.c_se = b.c_se; sef.tiles = tiles; sef.thin = true;
-        } else if (se_in_proj) {
-            sef.P = h->pool; sef.w1 = b.se_w1; sef.b1 = b.se_b1; sef.w2t = b.se_w2; sef.b2 = b.se_b2;
-            sef.inv_hw = 1.0f / (float)(b.h_out * b.h_out); sef.c_se = b.c_se;
-        } else if (!se_fused) {
-            launch_se(h->pool, tiles, 1.0f / (float)(b.h_out * b.h_out), b.se_w1, b.se_b1, b.se_w2, b.se_b2,
-                      h->gate, n, b.c_exp, b.c_se, s);
-            mk.mark(layer_name(bi, "se"));
-        }
-        if (!se_in_proj && (rc = tap_out(h, tap, q + ".gate", h->gate, (size_t)n * b.c_exp))) return rc;
+        launch_se(h->pool, tiles, 1.0f / (float)(b.h_out * b.h_out), b.se_w1, b.se_b1, b.se_w2, b.se_b2,
+                  h->gate, n, b.c_exp, b.c_se, s);
+        mk.mark(layer_name(bi, "se"));
+        if ((rc = tap_out(h, tap, q + ".gate", h->gate, (size_t)n * b.c_exp))) return rc;
         if ((rc = pointwise_t<XT>(h, dwbuf, b.proj_w, b.proj_b, h->gate, b.skip ? cur : (const XT*)nullptr, nxt, m_out,
-                                  b.c_exp, b.c_out, b.h_out * b.h_out, ACT_NONE, se_in_proj ? &sef : nullptr))) return rc;
+                                  b.c_exp, b.c_out, b.h_out * b.h_out, ACT_NONE))) return rc;
         mk.mark(layer_name(bi, "proj"));
-        if (se_in_proj && (rc = tap_out(h, tap, q + ".gate", h->gate, (size_t)n * b.c_exp))) return rc;   // written by the GEMM's blocks
         if ((rc = tap_out(h, tap, q + ".out", nxt, (size_t)m_out * b.c_out))) return rc;
         XT* t = cur; cur = nxt; nxt = t;
         ++bi;

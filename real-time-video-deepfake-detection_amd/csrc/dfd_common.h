@@ -125,15 +125,6 @@ struct dfd_handle {
     unsigned fuse_late_skip = (1u << 8) | (1u << 9);   // blocks that keep expand GEMM + depthwise kernel although fuse_late is on:
                                          // measured per block at batch 256 (fused - separate, us): b6 -17.8, b7 -5.5, b8 +2.1, b9 +3.6,
                                          // b10 -1.4, b12 -9.8, b13 -4.9, b14 -4.7, b15 -2.3 (option "fuse_late_skip", a bit per block)
-    bool fuse_se = false;                // squeeze-excite gate computed by the last block of each image inside the depthwise launch
-                                         // (measured slower than the separate launch: DESIGN.md section 5, round 3; kept as an option)
-    bool se_in_proj = false;             // squeeze-excite gate evaluated by the projection GEMM's blocks where the pool sums are final
-                                         // per image (blocks 6-10 / 12-15 with fuse_late): no se_kernel launch there.  Built and
-                                         // measured in round 4: gates bit-identical, step SLOWER - off
-    bool se_thin = false;                // blocks 0-4: the gate evaluated by the narrow projection's own blocks (pw8_kernel prologue),
-                                         // no se_kernel launch there.  Built and measured in round 4: the five projections +85 us
-                                         // against 54 us of se_kernel launches saved (3.08 vs 2.99 ms per step) - off (option "se_thin")
-    unsigned* se_counter = nullptr;      // [max_batch] arrival counters of that hand-off (zero between launches)
     bool split_gemm = true;              // 1x1 / k x k convs on the bf16x3-split MFMA path (gemm_split.hip)
     bool act_bf16 = false;               // classifier activations stored as bf16 (fp32 arithmetic): configs[3]
     int bf16_planes = 3;                 // weight planes the bf16-activation GEMMs use: 3 = fp32-exact weights, 1 = bf16 weights

@@ -195,19 +195,19 @@ long long s6_chunk_rows(long long M, long long row_bytes, long long HW) {
 template <typename XT, int NP>
 static void s6_measure(bool conv, bool gated, const std::vector<S6Tile>& cands, S6Tile* tile, const S6Key& key, const XT* X,
                        const unsigned short* W3, const float* bias, const float* gate, const XT* R, XT* Y, int M,
-                       int K, int N, int HW, int act, const ConvGeom& g, int res_first, hipStream_t s, const SeFuse& se) {
+                       int K, int N, int HW, int act, const ConvGeom& g, int res_first, hipStream_t s) {
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess) return;
     if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); return; }
     float best_ms = 1e30f;
     for (const S6Tile& t : cands) {
-        s6_dispatch_any<XT, NP>(conv, gated, t, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s, se);
+        s6_dispatch_any<XT, NP>(conv, gated, t, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s);
         float ms = 1e30f;
         bool ok = true;
         for (int rep = 0; rep < 2 && ok; ++rep) {          // best of two groups of three: robust to a stray hiccup
             hipEventRecord(e0, s);
             for (int r = 0; r < 3; ++r)
-                s6_dispatch_any<XT, NP>(conv, gated, t, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s, se);
+                s6_dispatch_any<XT, NP>(conv, gated, t, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s);
             hipEventRecord(e1, s);
             float m1 = 0.f;
             ok = hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&m1, e0, e1) == hipSuccess;
@@ -228,21 +228,16 @@ static void s6_measure(bool conv, bool gated, const std::vector<S6Tile>& cands, 
 template <typename XT, int NP>
 static void s6_run_one(S6Table* tab, bool conv, bool gated, const XT* X, const unsigned short* W3, const float* bias,
                        const float* gate, const XT* R, XT* Y, int M, int K, int N, int HW, int act, const ConvGeom& g,
-                       int res_first, hipStream_t s, const SeFuse& se) {
+                       int res_first, hipStream_t s) {
     static const bool tune_env = !(getenv("DFD_S6_TUNE") && atoi(getenv("DFD_S6_TUNE")) == 0);
     static const bool thin_env = !(getenv("DFD_S6_THIN") && atoi(getenv("DFD_S6_THIN")) == 0);
     // pw8 takes the call when the whole weight matrix fits its LDS image, a 16-row tile never straddles two images (the
     // gate row is block-uniform) and nothing but bias / activation / residual happens in the epilogue
     const bool thin = thin_env && !conv && s8_supports(K, N) && (!gated || (HW % 16 == 0 && M % HW == 0)) && act != ACT_PRELU &&
-                      !(R && res_first) && (!se.P || (se.thin && se_thin_supported(K, se.c_se)));
-    // se.thin: nobody launched se_kernel - only pw8 can take the call (the plan asked split_gemm_thin_supports first)
+                      !(R && res_first);
     static const bool wide_env = !(getenv("DFD_S6_WIDE") && atoi(getenv("DFD_S6_WIDE")) == 0);
-    const bool wide = wide_env && !conv && !gated && sizeof(XT) == 4 && NP == 3 && s9_supports(K, N) && act != ACT_PRELU && !se.P && !R;
-    auto candidates = [&]() {
-        std::vector<S6Tile> c = s6_candidates(M, K, N, thin, wide);
-        if (se.P && se.thin) c.erase(std::remove_if(c.begin(), c.end(), [](const S6Tile& t) { return t.kind != 2; }), c.end());
-        return c;
-    };
+    const bool wide = wide_env && !conv && !gated && sizeof(XT) == 4 && NP == 3 && s9_supports(K, N) && act != ACT_PRELU && !R;
+    auto candidates = [&]() { return s6_candidates(M, K, N, thin, wide); };
     S6Tile tile;
     if (tab && tab->force >= 0) {
         const std::vector<S6Tile> cands = candidates();
@@ -255,8 +250,10 @@ static void s6_run_one(S6Table* tab, bool conv, bool gated, const XT* X, const u
             while ((M >> sh) > 15) ++sh;
             mkey = ((M + (1 << sh) - 1) >> sh) << sh;
         }
+        // mode bits are what dfd_tiles_export saves: keep their values (16 is free outside conv since the removed
+        // squeeze-excite-in-GEMM path; renumbering would orphan saved tables)
         const S6Key key{mkey, K, N, (conv ? 1 : 0) | (gated ? 2 : 0) | (sizeof(XT) == 2 ? 4 : 0) | (NP == 1 ? 8 : 0) |
-                                        (se.P ? 16 : 0) | (thin ? 128 : 0) | (wide ? 64 : 0) | (conv ? (g.ksize << 8) | (g.stride << 4) : 0)};
+                                        (thin ? 128 : 0) | (wide ? 64 : 0) | (conv ? (g.ksize << 8) | (g.stride << 4) : 0)};
         const bool tuning = tab && tab->tuning && tune_env;
         auto it = tab ? tab->tiles.find(key) : std::map<S6Key, S6Tile>::iterator();
         if (tab && it != tab->tiles.end() && (it->second.measured || !tuning)) {
@@ -266,58 +263,49 @@ static void s6_run_one(S6Table* tab, bool conv, bool gated, const XT* X, const u
             // pw6 heuristic: pw8 / pw9 are picked by MEASUREMENT only - un-warmed at small batches they lose (batch 71 / 16 / 4 / 1:
             // 1.34 / 0.73 / 0.59 / 0.56 ms per forward against 1.31 / 0.66 / 0.50 / 0.47 with pw6; profiles/unwarmed_batch_probe.py):
             // their blocks amortise a prologue over many tiles, and a short matrix has few.
-            tile = se.P && se.thin ? candidates()[2] : pick_tile6(M, N);      // (thin-only list: 2, 3, 4 ... blocks per CU)
-            if (tuning) s6_measure<XT, NP>(conv, gated, candidates(), &tile, key, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s, se);
+            tile = pick_tile6(M, N);
+            if (tuning) s6_measure<XT, NP>(conv, gated, candidates(), &tile, key, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s);
             if (tab) tab->tiles[key] = tile;
         }
         tile = make_tile(M, N, tile.kind, tile.wm, tile.wn, tile.mt, tile.nt, tile.ks);      // block counts for this call's M
     }
-    s6_dispatch_any<XT, NP>(conv, gated, tile, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s, se);
+    s6_dispatch_any<XT, NP>(conv, gated, tile, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s);
 }
 
 template <typename XT>
 static void s6_run_np(int planes, S6Table* tab, bool conv, bool gated, const XT* X, const unsigned short* W3, const float* bias,
                       const float* gate, const XT* R, XT* Y, int M, int K, int N, int HW, int act, const ConvGeom& g,
-                      int res_first, hipStream_t s, const SeFuse& se = SeFuse()) {
+                      int res_first, hipStream_t s) {
     if constexpr (sizeof(XT) == 2) {
         if (planes == 1) {
-            s6_run_one<XT, 1>(tab, conv, gated, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s, se);
+            s6_run_one<XT, 1>(tab, conv, gated, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s);
             return;
         }
     }
-    s6_run_one<XT, 3>(tab, conv, gated, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s, se);
+    s6_run_one<XT, 3>(tab, conv, gated, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s);
 }
 
 bool split_gemm_supports(int K, int N) { return K % 8 == 0 && K >= 16 && split_weights_count(N, K) * 6 < (1ull << 31); }
-bool split_gemm_thin_supports(int K, int N, int HW) {
-    static const bool thin_env = !(getenv("DFD_S6_THIN") && atoi(getenv("DFD_S6_THIN")) == 0);
-    return thin_env && split_gemm_supports(K, N) && s8_supports(K, N) && HW > 0 && HW % 16 == 0;
-}
 
 template <typename XT>
 bool launch_pointwise_split(S6Table* tab, const XT* X, const unsigned short* W3, const float* bias, const float* gate,
-                            const XT* R, XT* Y, int M, int K, int N, int HW, int act, int planes, hipStream_t s,
-                            const SeFuse* se) {
+                            const XT* R, XT* Y, int M, int K, int N, int HW, int act, int planes, hipStream_t s) {
     const ConvGeom none{};
     if (HW <= 0) HW = 1;
-    if (se && se->P && (!gate || !se_fuse_supported(HW, se->c_se))) return false;
-    if (se && se->P && se->thin && !(split_gemm_thin_supports(K, N, HW) && se_thin_supported(K, se->c_se) && M % HW == 0)) return false;
     const long long chunk = s6_chunk_rows(M, (long long)K * (long long)sizeof(XT), gate ? HW : 1);
     if (chunk <= 0) return false;
     for (long long m0 = 0; m0 < M; m0 += chunk) {
         const int mc = (int)std::min<long long>(chunk, M - m0);
-        SeFuse sec = se ? *se : SeFuse();
-        if (sec.P) sec.P += (size_t)(m0 / HW) * K * (size_t)sec.tiles;      // chunks are whole images
         s6_run_np<XT>(planes, tab, false, gate != nullptr, X + (size_t)m0 * K, W3, bias,
                       gate ? gate + (size_t)(m0 / HW) * K : nullptr, R ? R + (size_t)m0 * N : nullptr, Y + (size_t)m0 * N,
-                      mc, K, N, HW, act, none, 0, s, sec);
+                      mc, K, N, HW, act, none, 0, s);
     }
     return true;
 }
 template bool launch_pointwise_split<float>(S6Table*, const float*, const unsigned short*, const float*, const float*,
-                                            const float*, float*, int, int, int, int, int, int, hipStream_t, const SeFuse*);
+                                            const float*, float*, int, int, int, int, int, int, hipStream_t);
 template bool launch_pointwise_split<bf16_t>(S6Table*, const bf16_t*, const unsigned short*, const float*, const float*,
-                                             const bf16_t*, bf16_t*, int, int, int, int, int, int, hipStream_t, const SeFuse*);
+                                             const bf16_t*, bf16_t*, int, int, int, int, int, int, hipStream_t);
 
 template <typename XT>
 bool launch_conv_gemm_split(S6Table* tab, const XT* X, const unsigned short* W3, const float* bias, const XT* R,

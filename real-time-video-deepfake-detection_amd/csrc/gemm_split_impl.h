@@ -79,88 +79,6 @@ __device__ __forceinline__ bf8 bf16x8_gate(const v4f raw, const v4f g0, const v4
     return x;
 }
 
-// Squeeze-excite gate of the images a block's rows belong to (SeFuse, b0_kernels.h), before the K loop.  se_kernel's
-// arithmetic operation by operation: mean = P * inv_hw; FC1 output o by ONE wave (lane l takes channels l, l + 64, ...
-// as a chain of fmas, then the xor-shuffle tree 32 .. 1), + bias, swish; FC2 channel c by one thread, the c_se terms in
-// order as fmas from the bias; sigmoid.  Which wave or thread takes an output never enters the arithmetic, so every
-// tile and both kernels produce the same gate bits, equal to se_kernel's.  zbuf: 4 x 48 floats of LDS that the K loop
-// overwrites afterwards.  The closing barrier is a workgroup release / acquire: the block's own gate rows (global, L2)
-// are visible to its buffer loads below; other blocks that share an image write the same values.
-template <int NTHR>
-__device__ __forceinline__ void s6_se_gate(const SeFuse& se, float* __restrict__ gate, int C, int HW, int M, int m_first,
-                                           int BM, float* __restrict__ zbuf) {
-    // Everything here is latency: the loops have compile-time trip counts and their loads are issued in batches before
-    // the first use (clamped index, masked VALUE - a load under a runtime condition is issued alone behind its own wait).
-    constexpr int NW = NTHR / 64, NI = SE_FUSE_MAX_IMG, STEPS = 1152 / 64, OG = 6;      // C <= 1152; OG outputs per batch
-    constexpr int OPW = (SE_FUSE_MAX_SE + NW - 1) / NW;                               // FC1 outputs per wave
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int m_last = m_first + BM - 1 < M - 1 ? m_first + BM - 1 : M - 1;
-    const int img0 = m_first / HW, nimg = m_last / HW - img0 + 1;          // <= NI (host: se_fuse_supported, BM <= 128)
-    const float* pimg[NI];
-#pragma unroll
-    for (int im = 0; im < NI; ++im) pimg[im] = se.P + (size_t)(img0 + (im < nimg ? im : nimg - 1)) * C;
-    // means of the lane's channels (lane, lane + 64, ...) for every image of the block
-    float mean[NI][STEPS];
-#pragma unroll
-    for (int i = 0; i < STEPS; ++i) {
-        const int c = lane + 64 * i, cc = c < C ? c : 0;
-#pragma unroll
-        for (int im = 0; im < NI; ++im) mean[im][i] = pimg[im][cc];
-    }
-#pragma unroll
-    for (int i = 0; i < STEPS; ++i)
-#pragma unroll
-        for (int im = 0; im < NI; ++im) mean[im][i] = lane + 64 * i < C ? mean[im][i] * se.inv_hw : 0.f;
-    // FC1: wave w owns outputs w, w + NW, ...; OG of them per batch of loads
-#pragma unroll
-    for (int g0 = 0; g0 < OPW; g0 += OG) {
-        float wv[OG][STEPS];
-#pragma unroll
-        for (int k = 0; k < OG; ++k) {
-            const int o = wave + NW * (g0 + k), oo = o < se.c_se ? o : se.c_se - 1;
-#pragma unroll
-            for (int i = 0; i < STEPS; ++i) {
-                const int c = lane + 64 * i;
-                wv[k][i] = se.w1[(size_t)oo * C + (c < C ? c : 0)];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < OG; ++k) {
-            if (g0 + k >= OPW) continue;
-            const int o = wave + NW * (g0 + k);
-            const float bo = se.b1[o < se.c_se ? o : 0];
-#pragma unroll
-            for (int im = 0; im < NI; ++im) {
-                float v = 0.f;
-#pragma unroll
-                for (int i = 0; i < STEPS; ++i) v = __builtin_fmaf(mean[im][i], wv[k][i], v);
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-                if (lane == 0 && o < se.c_se) zbuf[im * SE_FUSE_MAX_SE + o] = swish1(v + bo);
-            }
-        }
-    }
-    __syncthreads();
-    // FC2: channel c by one thread, all c_se weights of a channel requested before the first use
-    constexpr int CPT = (1152 + NTHR - 1) / NTHR;
-#pragma unroll
-    for (int r = 0; r < CPT; ++r) {
-        const int c = tid + NTHR * r, cc = c < C ? c : 0;
-        float wv[SE_FUSE_MAX_SE];
-#pragma unroll
-        for (int o = 0; o < SE_FUSE_MAX_SE; ++o) wv[o] = se.w2t[(size_t)(o < se.c_se ? o : 0) * C + cc];
-        const float bc = se.b2[cc];
-#pragma unroll
-        for (int im = 0; im < NI; ++im) {
-            float sacc = bc;
-#pragma unroll
-            for (int o = 0; o < SE_FUSE_MAX_SE; ++o) sacc = __builtin_fmaf(o < se.c_se ? zbuf[im * SE_FUSE_MAX_SE + (o < se.c_se ? o : 0)] : 0.f, wv[o], sacc);
-            if (im < nimg && c < C) gate[(size_t)(img0 + im) * C + c] = sigmoid1(sacc);
-        }
-    }
-    __syncthreads();
-}
-
 // The products of one 16x16x32 block, smallest terms first; ONE definition shared by pw6 and pw7 so that every
 // tile of either kernel accumulates each output in the same order (bit-identical results across tiles).
 //   fp32 activations (NXS = 3 terms) x 3 weight planes: the six products with i + j <= 2
@@ -347,7 +265,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && 2 * KS * NT * 16 * S6_ROWB <= 
                                                      const XT* __restrict__ R,
                                                      XT* __restrict__ Y, int M, int K, int N,
                                                      int HW, int act, int mblocks, int nblocks,
-                                                     ConvGeom cg, int res_first, unsigned xbytes, unsigned gbytes, SeFuse se) {
+                                                     ConvGeom cg, int res_first, unsigned xbytes, unsigned gbytes) {
     constexpr int BK = S6_BK;
     constexpr int BN = NT * 16, BM = NW * MT * 16, NTHR = NW * 64;
     constexpr bool PIPE = false;
@@ -371,9 +289,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && 2 * KS * NT * 16 * S6_ROWB <= 
 #ifdef S6_TRACE
     int tp = 0;
 #endif
-    if constexpr (GATE && !CONV) {
-        if (se.P) s6_se_gate<NTHR>(se, const_cast<float*>(gate), K, HW, M, mblk * BM, BM, reinterpret_cast<float*>(&ws[0][0][0]));
-    }
 
     int m[MT];
     size_t gbase[MT];
@@ -641,7 +556,7 @@ __global__ __launch_bounds__(256, (2 * (WM * MT + WN * NT) * 16 * S6_ROWB <= 80 
                                                      const XT* __restrict__ R,
                                                      XT* __restrict__ Y, int M, int K, int N,
                                                      int HW, int act, int mblocks, int nblocks,
-                                                     ConvGeom cg, int res_first, unsigned xbytes, unsigned gbytes, SeFuse se) {
+                                                     ConvGeom cg, int res_first, unsigned xbytes, unsigned gbytes) {
     static_assert(WM * WN == 4, "four waves per block");
     constexpr int BK = S6_BK;
     constexpr int BM = WM * MT * 16, BN = WN * NT * 16;
@@ -660,9 +575,6 @@ __global__ __launch_bounds__(256, (2 * (WM * MT + WN * NT) * 16 * S6_ROWB <= 80 
     const int j = lane & 15, q = lane >> 4;
     const int wm = wave / WN, wn = wave % WN;
     const int m0 = mblk * BM, n0 = nblk * BN;
-    if constexpr (GATE && !CONV) {
-        if (se.P) s6_se_gate<256>(se, const_cast<float*>(gate), K, HW, M, m0, BM, reinterpret_cast<float*>(&ws[0][0]));
-    }
 
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(W3), 0, 6 * plane, 0x00020000);
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<XT*>(X), 0, xbytes, 0x00020000);
@@ -881,7 +793,7 @@ template <int NT, int NK, bool GATE, int NW, typename XT, int NP>
 __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : NT * NK <= 10 ? 3 : 2)) void pw8_kernel(const XT* __restrict__ X, const unsigned short* __restrict__ W3, int plane,
                                                       int Kp, const float* __restrict__ bias, const float* __restrict__ gate,
                                                       const XT* __restrict__ R, XT* __restrict__ Y, int M, int K, int N,
-                                                      int tpg, int tpb, int act, int res_first, unsigned xbytes, SeFuse se) {
+                                                      int tpg, int tpb, int act, int res_first, unsigned xbytes) {
     constexpr int BK = S6_BK, BN = NT * 16, NTHR = NW * 64;
     constexpr int ESZ = (int)sizeof(XT), XL = ESZ == 4 ? 2 : 1, NXS = ESZ == 4 ? 3 : 1;
     static_assert(NP == 3 || (NP == 1 && ESZ == 2), "weight planes: 3 (fp32-exact), or 1 with bf16 activations");
@@ -944,13 +856,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : NT * NK <= 10 ? 3 : 2)) voi
         }
         constexpr int GL = (2 * NK * BK + NTHR - 1) / NTHR;
         const int img_last = GATE ? (M - 1) / (tpg * 16) : 0;
-        const bool own_gate = GATE && se.P != nullptr;               // this block evaluates its images' gates itself (below)
         float gv[GL];
 #pragma unroll
         for (int t = 0; t < GL; ++t) {
             const int e = tid + t * NTHR, im = e >= NK * BK ? 1 : 0, k = e - im * NK * BK;
             const int img = img0 + im < img_last ? img0 + im : img_last;
-            gv[t] = GATE && !own_gate ? gate[(size_t)img * K + (k < K ? k : 0)] : 1.f;
+            gv[t] = GATE ? gate[(size_t)img * K + (k < K ? k : 0)] : 1.f;
         }
 #pragma unroll
         for (int t = 0; t < WLOADS; ++t) {
@@ -963,60 +874,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : NT * NK <= 10 ? 3 : 2)) voi
         for (int t = 0; t < GL; ++t) {
             const int e = tid + t * NTHR, im = e >= NK * BK ? 1 : 0, k = e - im * NK * BK;
             if (e < 2 * NK * BK) gs[im][k] = k < K ? gv[t] : 0.f;
-        }
-    }
-    if constexpr (GATE) {
-        // Squeeze-excite of the block's (at most two) images by the block itself: on these layers (C <= 256, c_se <= 16) the
-        // gate is ~5 k MACs per image and the separate se_kernel launch 10-13 us of launch + three dependent round trips on an
-        // otherwise idle chip.  MEASURED (option "se_thin", batch 256): the five projections 105 / 69 / 134 / 34 / 58 -> 130 / 82 /
-        // 159 / 41 / 73 us - +85 us for 54 us of se_kernel launches: every block re-reads its images' pool partials (98 x 32
-        // floats per image in block 0) behind two barriers before its first tile, and the tuner answers with fewer, longer
-        // blocks.  Third form of "squeeze-excite inside a neighbouring launch" that loses (fuse_se, se_in_proj): off.  Fixed
-        // summation orders (tile sums as four strided chains folded pairwise, FC1 in 8 lanes per output + xor tree, FC2 as a
-        // chain from the bias): every block that meets an image writes the same gate bits.
-        if (se.P != nullptr) {
-            float* mean_s = reinterpret_cast<float*>(&os[0][0]);     // [2][SE_THIN_MAX_C] (the output image is not in use yet)
-            float* z_s = mean_s + 2 * SE_THIN_MAX_C;                 // [2][SE_THIN_MAX_SE]
-            const int img_last = (M - 1) / (tpg * 16), C = K;
-            for (int e = tid; e < 2 * C; e += NTHR) {
-                const int im = e >= C ? 1 : 0, c = e - im * C;
-                const int img = img0 + im < img_last ? img0 + im : img_last;
-                const float* p = se.P + (size_t)img * se.tiles * C + c;
-                float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-                int t = 0;
-                for (; t + 3 < se.tiles; t += 4) {
-                    s0 += p[(size_t)t * C];
-                    s1 += p[(size_t)(t + 1) * C];
-                    s2 += p[(size_t)(t + 2) * C];
-                    s3 += p[(size_t)(t + 3) * C];
-                }
-                for (; t < se.tiles; ++t) s0 += p[(size_t)t * C];
-                mean_s[im * SE_THIN_MAX_C + c] = ((s0 + s1) + (s2 + s3)) * se.inv_hw;
-            }
-            __syncthreads();
-            for (int e = tid; e < 2 * SE_THIN_MAX_SE * 8; e += NTHR) {      // (image, output, part of 8): 256 work items
-                const int im = e >> 7, o = (e >> 3) & (SE_THIN_MAX_SE - 1), part = e & 7;
-                const int oo = o < se.c_se ? o : se.c_se - 1;
-                float v = 0.f;
-                for (int c = part; c < C; c += 8) v = __builtin_fmaf(mean_s[im * SE_THIN_MAX_C + c], se.w1[(size_t)oo * C + c], v);
-                v += __shfl_xor(v, 4);
-                v += __shfl_xor(v, 2);
-                v += __shfl_xor(v, 1);
-                if (part == 0 && o < se.c_se) z_s[im * SE_THIN_MAX_SE + o] = swish1(v + se.b1[o]);
-            }
-            __syncthreads();
-            for (int e = tid; e < 2 * NK * BK; e += NTHR) {
-                const int im = e >= NK * BK ? 1 : 0, c = e - im * NK * BK;
-                float g = 0.f;
-                if (c < C) {
-                    float sacc = se.b2[c];
-                    for (int o = 0; o < se.c_se; ++o) sacc = __builtin_fmaf(z_s[im * SE_THIN_MAX_SE + o], se.w2t[(size_t)o * C + c], sacc);
-                    g = sigmoid1(sacc);
-                    const int img = img0 + im < img_last ? img0 + im : img_last;
-                    if (img0 + im <= img_last) const_cast<float*>(gate)[(size_t)img * C + c] = g;      // for taps; every writer agrees
-                }
-                gs[im][c] = g;
-            }
         }
     }
     __syncthreads();
@@ -1350,7 +1207,7 @@ inline S6Tile make_tile6(int M, int N, int mt, int nt, int ks = 1) { return make
 template <bool CONV, bool GATE, typename XT, int NP>
 void s6_dispatch(const S6Tile& t, const XT* X, const unsigned short* W3, const float* bias,
                  const float* gate, const XT* R, XT* Y, int M, int K, int N, int HW, int act,
-                 const ConvGeom& g, int res_first, hipStream_t s, const SeFuse& se) {
+                 const ConvGeom& g, int res_first, hipStream_t s) {
     const int grid = ((t.mblocks + 7) / 8) * 8 * t.nblocks;
     const int Kp = (K + S6_KPAD - 1) / S6_KPAD * S6_KPAD, plane = s6_np(N) * Kp;
     const unsigned xbytes = CONV ? (unsigned)((size_t)(M / (g.Ho * g.Wo)) * g.H * g.W * g.Cin * sizeof(XT))
@@ -1383,7 +1240,7 @@ void s6_dispatch(const S6Tile& t, const XT* X, const unsigned short* W3, const f
             const int nblk = (ttot + tpb - 1) / tpb;
 #define DFD_S8_LAUNCH(NTV, NKV, NWV)                                                                                 \
     hipLaunchKernelGGL((pw8_kernel<NTV, NKV, GATE, NWV, XT, NP>), dim3(nblk), dim3(NWV * 64), 0, s, X, W3, plane, Kp, bias, \
-                       gate, R, Y, M, K, N, tpg, tpb, act, res_first, xbytes, se)
+                       gate, R, Y, M, K, N, tpg, tpb, act, res_first, xbytes)
 #define DFD_S8_CASE(NKV, NWV)                            \
     if (nk == NKV) {                                     \
         if (t.nt == 1) DFD_S8_LAUNCH(1, NKV, NWV);       \
@@ -1400,7 +1257,7 @@ void s6_dispatch(const S6Tile& t, const XT* X, const unsigned short* W3, const f
 #define DFD_S7_CASE(WMV, WNV, MTV, NTV)                                                                              \
     if (t.wm == WMV && t.wn == WNV && t.mt == MTV && t.nt == NTV) {                                                  \
         hipLaunchKernelGGL((pw7_kernel<WMV, WNV, MTV, NTV, CONV, GATE, XT, NP>), dim3(grid), dim3(256), 0, s, X, W3, plane,  \
-                           Kp, bias, gate, R, Y, M, K, N, HW, act, t.mblocks, t.nblocks, g, res_first, xbytes, gbytes, se); \
+                           Kp, bias, gate, R, Y, M, K, N, HW, act, t.mblocks, t.nblocks, g, res_first, xbytes, gbytes); \
         return;                                                                                                      \
     }
         DFD_S7_CONFIGS(DFD_S7_CASE)
@@ -1409,10 +1266,10 @@ void s6_dispatch(const S6Tile& t, const XT* X, const unsigned short* W3, const f
     }
 #define DFD_S6_LAUNCH(NTV, MTV, KSV)                                                                                 \
     hipLaunchKernelGGL((pw6_kernel<NTV, CONV, MTV, GATE, KSV, 4, XT, NP>), dim3(grid), dim3(256), 0, s, X, W3, plane, Kp, bias, gate, \
-                       R, Y, M, K, N, HW, act, t.mblocks, t.nblocks, g, res_first, xbytes, gbytes, se)
+                       R, Y, M, K, N, HW, act, t.mblocks, t.nblocks, g, res_first, xbytes, gbytes)
 #define DFD_S6_LAUNCH8(NTV, KSV)                                                                                     \
     hipLaunchKernelGGL((pw6_kernel<NTV, CONV, 1, GATE, KSV, 8, XT, NP>), dim3(grid), dim3(512), 0, s, X, W3, plane, Kp, bias, \
-                       gate, R, Y, M, K, N, HW, act, t.mblocks, t.nblocks, g, res_first, xbytes, gbytes, se)
+                       gate, R, Y, M, K, N, HW, act, t.mblocks, t.nblocks, g, res_first, xbytes, gbytes)
 #define DFD_S6_CASE(NTV)                                        \
     case NTV:                                                   \
         if (t.wm == 8 && t.ks == 2) DFD_S6_LAUNCH8(NTV, 2);     \
@@ -1434,16 +1291,16 @@ void s6_dispatch(const S6Tile& t, const XT* X, const unsigned short* W3, const f
 template <typename XT, int NP>
 void s6_dispatch_any(bool conv, bool gated, const S6Tile& t, const XT* X, const unsigned short* W3, const float* bias,
                      const float* gate, const XT* R, XT* Y, int M, int K, int N, int HW, int act, const ConvGeom& g,
-                     int res_first, hipStream_t s, const SeFuse& se);
+                     int res_first, hipStream_t s);
 
 #define DFD_S6_INSTANTIATE(XT, NP)                                                                                      \
     template <>                                                                                                         \
     void s6_dispatch_any<XT, NP>(bool conv, bool gated, const S6Tile& t, const XT* X, const unsigned short* W3,         \
                                  const float* bias, const float* gate, const XT* R, XT* Y, int M, int K, int N, int HW, \
-                                 int act, const ConvGeom& g, int res_first, hipStream_t s, const SeFuse& se) {          \
-        if (conv) s6_dispatch<true, false, XT, NP>(t, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s, se);  \
-        else if (gated) s6_dispatch<false, true, XT, NP>(t, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s, se); \
-        else s6_dispatch<false, false, XT, NP>(t, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s, se);      \
+                                 int act, const ConvGeom& g, int res_first, hipStream_t s) {                            \
+        if (conv) s6_dispatch<true, false, XT, NP>(t, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s);      \
+        else if (gated) s6_dispatch<false, true, XT, NP>(t, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s); \
+        else s6_dispatch<false, false, XT, NP>(t, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s);          \
     }
 
 }  // namespace dfd
