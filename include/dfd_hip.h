@@ -297,6 +297,10 @@ int dfd_forensics(dfd_handle* h, int stream_id, const uint8_t* bgr, int height, 
                   int full, double* scores_out, double* prob_out, double* stats_out);
 /* FrameForensicAnalyzer.reset, reference frame_analysis.py:391-395. */
 int dfd_forensics_reset(dfd_handle* h, int stream_id);
+/* Drops a stream's state (reset keeps its 64 KB device plane and its entry): the plane goes to a free list inside the
+ * handle and is reused by the next new stream, so short-lived streams cost no HBM and no device allocation.  The stream
+ * id may be used again afterwards; it then starts as a new stream.  Unknown ids are a no-op. */
+int dfd_forensics_release(dfd_handle* h, int stream_id);
 /* Mirrors the analyzer's attributes frame_count, len(temporal_diffs), prev_frame_gray is not None. */
 int dfd_forensics_state(dfd_handle* h, int stream_id, int* frame_count, int* n_diffs, int* has_prev);
 
@@ -369,6 +373,23 @@ int dfd_analyze_stream_batch(dfd_handle* h, int stream_id, int n, const uint8_t*
                              int width, const int* full_forensics, float conf_thr, int max_faces, int apply_clahe,
                              double* scores_out, double* forensic_prob_out, int32_t* xywh_out, int* n_faces_out,
                              int* n_detected_out, float* logits_out, int* height_out, int* width_out);
+
+/* ---- one device pass over frames of MANY streams (the session pool; no reference counterpart) ----------------------
+ * dfd_analyze_stream_batch for n frames of any streams and sizes: frame i belongs to stream stream_ids[i] (the frames of
+ * one stream in stream order) and is a JPEG of len[i] bytes or, with len[i] = 0, a packed BGR frame of heights[i] x
+ * widths[i] (heights / widths may be NULL when every part is a JPEG).  JPEG parts of one size are decoded as one batch;
+ * frames under 30 px a side get forensics but no detection.  Outputs as dfd_analyze_stream_batch, per frame: scores
+ * [n][6], forensic_prob [n], xywh [n][max_faces][4], n_faces [n], n_detected [n] or NULL, logits [n][max_faces],
+ * height [n] / width [n] or NULL.  Per frame, bit for bit, the results (and every stream's state afterwards) equal those
+ * of running each stream's frames alone, in order, through dfd_analyze_stream_batch / dfd_analyze_frame /
+ * dfd_analyze_jpeg.  Every header is parsed and every check runs before anything moves: a part the device path does
+ * not take fails the call (DFD_ERR_UNSUPPORTED for JPEG flavours, DFD_ERR_ARG for unreadable parts, among them scans
+ * that are corrupt or cut off, found while decoding) with its index in *bad_index_out (NULL allowed); no stream state
+ * has moved then.  More than 2^27 pixels in one call are refused with DFD_ERR_UNSUPPORTED and index -1. */
+int dfd_analyze_streams_batch(dfd_handle* h, int n, const uint8_t* const* data, const size_t* len, const int* heights,
+                              const int* widths, const int* stream_ids, const int* full_forensics, float conf_thr, int max_faces,
+                              int apply_clahe, double* scores_out, double* forensic_prob_out, int32_t* xywh_out, int* n_faces_out,
+                              int* n_detected_out, float* logits_out, int* height_out, int* width_out, int* bad_index_out);
 
 /* ---- many frames, resident in HBM (throughput path; BASELINE.json configs[2]/[3]) ----------
  * frames_dev: n packed 8-bit BGR frames of height x width on the handle's device (row stride

@@ -102,7 +102,11 @@ SIGNATURES = {
                                            C.c_void_p]),
     "dfd_forensics": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dfd_analyze_streams_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "dfd_forensics_reset": (C.c_int, [C.c_void_p, C.c_int]),
+    "dfd_forensics_release": (C.c_int, [C.c_void_p, C.c_int]),
     "dfd_forensics_state": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                       C.POINTER(C.c_int)]),
     "dfd_host_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -428,6 +432,10 @@ class Handle:
     def forensics_reset(self, stream_id: int = 0):
         self._check(self._lib.dfd_forensics_reset(self._p, int(stream_id)))
 
+    def forensics_release(self, stream_id: int):
+        """drop the stream's state; its device plane is reused by the next new stream (dfd_forensics_release)"""
+        self._check(self._lib.dfd_forensics_release(self._p, int(stream_id)))
+
     def forensics_state(self, stream_id: int = 0):
         fc, nd, hp = C.c_int(), C.c_int(), C.c_int()
         self._check(self._lib.dfd_forensics_state(self._p, int(stream_id), C.byref(fc), C.byref(nd), C.byref(hp)))
@@ -582,6 +590,55 @@ class Handle:
             out.append((scores, float(prob[i]), [tuple(int(v) for v in boxes[i, j]) for j in range(nf[i])],
                         logits[i, : nf[i]].copy(), int(nd[i])))
         return out, (oh.value, ow.value)
+
+    def analyze_streams_batch(self, items, stream_ids, full_flags, confidence_threshold: float = 0.5, max_faces: int = 1,
+                              apply_clahe: bool = True):
+        """frames of MANY streams and sizes in ONE call (dfd_analyze_streams_batch).  items: JPEG `bytes` and / or BGR
+        uint8 arrays; stream_ids / full_flags: one per item (a stream's frames in stream order).  -> list of (scores dict,
+        forensic prob, boxes, logits, n_detected, (H, W)) per frame.  A refused part raises DfdError with
+        `.bad_index` = its index (-1: the call as a whole), before anything has moved."""
+        n = len(items)
+        if n == 0 or len(full_flags) != n or len(stream_ids) != n:
+            raise ValueError("analyze_streams_batch: one stream id and one full / fast flag per frame")
+        keep, ptrs, lens = [], (C.c_void_p * n)(), (C.c_size_t * n)()
+        hs, ws = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        for i, it in enumerate(items):
+            if isinstance(it, (bytes, bytearray, memoryview)):
+                b = (C.c_char * len(it)).from_buffer_copy(it)
+                keep.append(b)
+                ptrs[i], lens[i] = C.addressof(b), len(it)
+            else:
+                a = np.ascontiguousarray(it, dtype=np.uint8)
+                if a.ndim != 3 or a.shape[2] != 3:
+                    raise ValueError("analyze_streams_batch: raw frames are (H, W, 3) uint8")
+                hs[i], ws[i] = a.shape[:2]
+                keep.append(a)
+                ptrs[i], lens[i] = a.ctypes.data, 0
+        max_faces = max(1, int(max_faces))
+        ids = np.ascontiguousarray(stream_ids, dtype=np.int32)
+        full = np.ascontiguousarray([int(bool(f)) for f in full_flags], dtype=np.int32)
+        sc = np.empty((n, 6), np.float64)
+        prob = np.empty(n, np.float64)
+        boxes = np.zeros((n, max_faces, 4), np.int32)
+        nf = np.zeros(n, np.int32)
+        nd = np.zeros(n, np.int32)
+        logits = np.zeros((n, max_faces), np.float32)
+        oh, ow = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        bad = C.c_int(-1)
+        rc = self._lib.dfd_analyze_streams_batch(self._p, n, ptrs, lens, _ptr(hs), _ptr(ws), _ptr(ids), _ptr(full),
+                                                 float(confidence_threshold), max_faces, int(bool(apply_clahe)), _ptr(sc),
+                                                 _ptr(prob), _ptr(boxes), _ptr(nf), _ptr(nd), _ptr(logits), _ptr(oh), _ptr(ow),
+                                                 C.byref(bad))
+        if rc != 0:
+            err = DfdError(rc, (self._lib.dfd_last_error(self._p) or b"").decode())
+            err.bad_index = bad.value
+            raise err
+        out = []
+        for i in range(n):
+            scores = {k: float(v) for k, v in zip(self.FORENSIC_KEYS, sc[i]) if not np.isnan(v)}
+            out.append((scores, float(prob[i]), [tuple(int(v) for v in boxes[i, j]) for j in range(nf[i])],
+                        logits[i, : nf[i]].copy(), int(nd[i]), (int(oh[i]), int(ow[i]))))
+        return out
 
     def host_alloc(self, shape, dtype=np.uint8) -> np.ndarray:
         """A numpy array over pinned host memory (hipHostMalloc); release with host_free(arr)."""

@@ -11,11 +11,17 @@ Pillow (cv2 is not a dependency here); ``POST /analyze_batch`` takes several ``f
 request; CORS headers are added by hand (no
 flask_cors), and the rate limiter and detector are guarded by locks (the reference shares them
 unsynchronised across Flask's worker threads, :57,62-80,275).
+
+Sessions (not in the reference): an optional ``?session=<id>`` on ``/analyze``, ``/analyze_batch``, ``/stats`` and
+``/reset`` gives each client its own detector and its own 100 ms limiter, and the frames of all sessions are served in
+shared batched device passes (`sessions.SessionPool`).  Session ids are chosen by the client and are NOT a security
+boundary: whoever knows an id can post to, read or reset that session.  Without the parameter nothing changes.
 """
 from __future__ import annotations
 
 import io
 import logging
+import re
 import threading
 import time
 import traceback
@@ -27,6 +33,7 @@ from flask import Flask, jsonify, request
 from . import runtime
 from .deepfake_detection import DEVICE, DeepfakeDetector, model, mtcnn  # noqa: F401  (reference :39)
 from .face_detection import detect_bounding_box  # noqa: F401                      (reference :40)
+from .sessions import InvalidFrame, SessionClosed, SessionPool, SessionPoolFull
 
 logging.basicConfig(level=logging.INFO, format='%(asctime)s [%(levelname)s] %(message)s', datefmt='%H:%M:%S')
 logger = logging.getLogger(__name__)
@@ -58,12 +65,59 @@ _min_request_interval = 0.1                                                 # re
 _rate_lock = threading.Lock()
 _detector_lock = threading.Lock()
 
+# Sessions (optional `?session=<id>` on /analyze, /analyze_batch, /stats, /reset; no reference counterpart): each id gets
+# its own DeepfakeDetector in the pool (own vote window, frame counter, forensic stream) and its own 100 ms limiter, and
+# the frames of all sessions share batched device passes (sessions.SessionPool).  Ids are chosen by the client and are
+# not a security boundary: anyone who knows an id can read or reset that session.  Without the parameter every route
+# takes the session-less path above (global detector, global limiter) exactly as before.
+_SESSION_ID = re.compile(r'[A-Za-z0-9_-]{1,64}')
+_session_pool = None                      # built on first use; tests may install their own
+_session_last: dict = {}                  # session id -> time of its last admitted request (under _rate_lock)
+
+
+def _pool():
+    global _session_pool
+    with _rate_lock:
+        if _session_pool is None:
+            _session_pool = SessionPool(lock=_detector_lock, detection_threshold=0.55)
+        return _session_pool
+
+
+def _session_arg():
+    """(session id or None, error response or None)"""
+    sid = request.args.get('session')
+    if sid is None:
+        return None, None
+    if not _SESSION_ID.fullmatch(sid):
+        return None, (jsonify({'error': 'Invalid session id (1-64 characters of A-Z a-z 0-9 _ -)'}), 400)
+    return sid, None
+
+
+def _session_rate_limited(sid):
+    """the per-session form of the reference's limiter (:66-80): a 429 response, or None"""
+    with _rate_lock:
+        now = time.time()
+        elapsed = now - _session_last.get(sid, 0.0)
+        if elapsed < _min_request_interval:
+            return jsonify({'error': 'Rate limited', 'retry_after_ms': int((_min_request_interval - elapsed) * 1000)}), 429
+        if len(_session_last) > 4096:                               # forget sessions that are past their interval
+            for k in [k for k, t in _session_last.items() if now - t >= _min_request_interval]:
+                del _session_last[k]
+        _session_last[sid] = now
+    return None
+
 
 def rate_limit(f):
-    """reference :66-80"""
+    """reference :66-80; with ?session= the session's own limiter instead (the session id is checked first)"""
     @wraps(f)
     def decorated(*args, **kwargs):
         global _last_request_time
+        sid, bad = _session_arg()
+        if bad is not None:
+            return bad
+        if sid is not None:
+            limited = _session_rate_limited(sid)
+            return limited if limited is not None else f(*args, **kwargs)
         with _rate_lock:
             now = time.time()
             elapsed = now - _last_request_time
@@ -73,6 +127,19 @@ def rate_limit(f):
             _last_request_time = now
         return f(*args, **kwargs)
     return decorated
+
+
+def _session_results(sid, items, single=False):
+    """the pool's responses for one request of session `sid` (list of dicts), or an error response: a part that does not
+    decode gets the 400 of the session-less route (`single`: /analyze's body), and no other session notices it"""
+    try:
+        return _pool().submit(sid, items).result(), None
+    except SessionPoolFull as e:
+        return None, (jsonify({'error': 'Too many active sessions', 'retry_after_ms': e.retry_after_ms}), 503)
+    except InvalidFrame as e:
+        return None, (jsonify({'error': 'Invalid image format' if single else str(e)}), 400)
+    except SessionClosed:
+        return None, (jsonify({'error': f'Session {sid} was closed'}), 410)
 
 
 def image_size(image_bytes: bytes):
@@ -128,8 +195,14 @@ def health_check():
 
 @app.route('/reset', methods=['POST'])
 def reset_detector():
-    """reference :101-115"""
+    """reference :101-115; ?session= resets only that session"""
+    sid, bad = _session_arg()
+    if bad is not None:
+        return bad
     try:
+        if sid is not None:
+            _pool().reset(sid)                                      # an unknown session has nothing to reset
+            return jsonify({'success': True, 'message': 'Detector reset successfully'}), 200
         with _detector_lock:
             detector.reset()
         return jsonify({'success': True, 'message': 'Detector reset successfully'}), 200
@@ -148,7 +221,19 @@ def analyze_frame():
             return jsonify({'error': 'No frame provided'}), 400
         image_bytes = request.files['frame'].read()
         response = None
-        if image_bytes[:2] == b'\xff\xd8':                        # JPEG: decode on the device, no raw upload
+        sid = request.args.get('session')
+        if sid is not None:                                         # the session's detector, in the pool's next pass
+            if image_bytes[:2] == b'\xff\xd8' and image_size(image_bytes) is not None:
+                item = image_bytes                                  # decoded on the device (Pillow if the library refuses it)
+            else:
+                item = decode_image(image_bytes)
+                if item is None:
+                    return jsonify({'error': 'Invalid image format'}), 400
+            results, err = _session_results(sid, [item], single=True)
+            if err is not None:
+                return err
+            response = results[0]
+        elif image_bytes[:2] == b'\xff\xd8':                      # JPEG: decode on the device, no raw upload
             try:
                 with _detector_lock:
                     response = detector.analyze_request(jpeg=image_bytes)
@@ -211,6 +296,13 @@ def analyze_batch():
                 if frame is None:
                     return jsonify({'error': f'Invalid image format (frame {k})'}), 400
                 items.append(frame)
+        sid = request.args.get('session')
+        if sid is not None:                                         # the session's detector; sizes may differ
+            results, err = _session_results(sid, items)
+            if err is not None:
+                return err
+            ms = (time.time() - start_time) * 1000
+            return jsonify({'success': True, 'frames': len(results), 'processing_time_ms': round(ms, 1), 'results': results}), 200
         results = None
         with _detector_lock:
             try:
@@ -241,8 +333,17 @@ def analyze_batch():
 
 @app.route('/stats', methods=['GET'])
 def get_stats():
-    """reference :240-255"""
+    """reference :240-255; ?session= reports that session (404 when there is none)"""
+    sid, bad = _session_arg()
+    if bad is not None:
+        return bad
     try:
+        if sid is not None:
+            s = _pool().stats(sid)
+            if s is None:
+                return jsonify({'error': f'Unknown session {sid}'}), 404
+            s['device'] = DEVICE
+            return jsonify(s), 200
         t = detector.temporal_tracker
         return jsonify({'frame_count': detector.frame_count, 'temporal_average': float(t.get_temporal_average()),
                         'stability_score': float(t.get_stability_score()), 'confidence_level': t.get_confidence_level(),

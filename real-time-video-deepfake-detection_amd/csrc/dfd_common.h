@@ -107,6 +107,7 @@ struct dfd_handle {
     dfd::ColorTables color{};
     bool has_color = false;
     dfd::DevBuf frame_buf, lab_buf, crop_buf, lut_buf, desc_buf, u8_out, face_batch;
+    dfd::DevBuf det_desc;                // detect_frames_run: FrameDesc table of the detector's ragged resize
     int last_detections = 0;             // detections of the last single-frame detector run, before the max_out cut
     std::vector<char> crop_valid;        // per crop of the last preprocess: 0 = the MTCNN stage found no face
     int n_compact = 0;                   // rows of in_nchw the last preprocess filled (= crops with a face, in crop order, when it compacts)
@@ -195,15 +196,22 @@ int preprocess_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int 
 // boxes of resident frame(s) -> logits on the host, m <= max_batch: crop / CLAHE / MTCNN / 224 x 224, then the classifier
 // at the batch of the crops the cascade KEPT (reference deepfake_detection.py:377-380: `mtcnn()` -> None returns before
 // the model runs) - a rejected crop costs no classifier work and gets NaN.  Ends with a stream wait.
+// crop_frames (or null): per-crop frame of a ragged batch (offset in frame_dev, size, stride) instead of hh / ww / stride /
+// frame_offs
 int classify_boxes(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride, const int32_t* xywh, int m,
-                   int apply_clahe, const size_t* frame_offs, float* logits_out);
+                   int apply_clahe, const size_t* frame_offs, float* logits_out, const FrameDesc* crop_frames = nullptr);
 // DetectionOutput of `n` frames already resized to 300x300 -> rows/count on the host
 int detect_batch_run(dfd_handle* h, const uint8_t* frames_dev, int n, int hh, int ww, int stride, size_t frame_bytes,
                      float conf_thr, int max_faces, int32_t* xywh_out, int* n_out, int* n_total_out = nullptr);
-// the analyzer over n consecutive frames of ONE stream (its temporal state advances n frames): frame i scored in full
-// or fast mode as full[i] says - results identical to n forensics_run calls in order
-int forensics_stream_batch_run(dfd_handle* h, int stream_id, const uint8_t* frames_dev, int n, int hh, int ww, int stride,
-                               size_t frame_bytes, const int* full, double* scores_out, double* prob_out);
+// the same for m frames of their own sizes: frame fd[idx[j]] of the arena at frames_dev (every one >= 30 px a side); its
+// boxes go to xywh_out + idx[j] * max_faces * 4, its counts to n_out[idx[j]] / n_total_out[idx[j]]
+int detect_frames_run(dfd_handle* h, const uint8_t* frames_dev, const FrameDesc* fd, const int* idx, int m, float conf_thr,
+                      int max_faces, int32_t* xywh_out, int* n_out, int* n_total_out);
+// the analyzer over n frames of any streams and sizes (frame f of stream stream_ids[f], descriptor fd[f] into the arena
+// at frames_dev; the frames of one stream in stream order): one launch set, every stream's temporal state advances by its
+// frames - results identical to forensics_run on each stream's frames in order
+int forensics_streams_run(dfd_handle* h, const uint8_t* frames_dev, const FrameDesc* fd, int n, const int* stream_ids,
+                          const int* full, double* scores_out, double* prob_out);
 // jpeg_decode.hip: n JPEGs of one size -> packed BGR frames [n][hh][ww][3] at frames_dev (entropy decoding of the files
 // in parallel on the host pool, one coefficient upload, IDCT / colour per frame).  *hh / *ww: in = expected size or 0
 int jpeg_decode_batch_to(dfd_handle* h, const uint8_t* const* jpegs, const size_t* lens, int n, uint8_t* frames_dev_or_null,

@@ -27,6 +27,8 @@ struct ForensicState {
     DevBuf pair_idx, pair_part;    // dfd_forensic_signals_device: predecessor indices, [n][256] partial sums
     double* host_res = nullptr;    // pinned: statistics of a batch that ran on the second stream (forensics_batch_begin)
     size_t host_res_cap = 0;
+    DevBuf frame_desc, prev_tab, copy_tab;   // forensics_streams_run: FrameDesc [n], predecessor planes [n], write-backs
+    std::vector<void*> free_planes;          // stored planes of released streams, reused by the next new stream
 };
 
 void forensic_destroy(dfd_handle* h) {
@@ -122,6 +124,63 @@ void static_scores(const double* st, const double* noise, const double* ela, boo
     for (int i = 0; i < 10; ++i) ex[i] = e[i];
 }
 
+// the host half of one frame of a stream, in the stream's frame order: frame counter, temporal deque and signal
+// (frame_analysis.py:358-389; dpart = the frame's 256 partial sums against its predecessor, read only when the stream
+// has one), then the weighted sum in the reference's dict order (:49-56,88 / :118-119).  sc[6] / ex[10] as static_scores;
+// *mean_diff / *temporal_cv: -1 / NaN when not computed.
+double score_frame(ForensicStream& S, const double* st, const double* noise, const double* ela, bool full, const double* dpart,
+                   double* sc, double* ex, double* mean_diff, double* temporal_cv) {
+    S.frame_count += 1;                                              // frame_analysis.py:68,110
+    static_scores(st, noise, ela, full, sc, ex);
+    *mean_diff = -1.0;
+    *temporal_cv = std::nan("");
+    if (!S.has_prev) {
+        S.has_prev = true;
+    } else {
+        double sum = 0;
+        for (int i = 0; i < 256; ++i) sum += dpart[i];
+        const double md = sum / 65536.0;
+        *mean_diff = md;
+        S.diffs.push_back(md);
+        if (S.diffs.size() > 30) S.diffs.pop_front();
+        if (S.diffs.size() >= 5) {
+            std::vector<double> d(S.diffs.begin(), S.diffs.end());
+            double dm;
+            const double tcv = pop_std(d.data(), (int)d.size(), &dm) / (dm + 1e-10);
+            *temporal_cv = tcv;
+            double s = 0.0;
+            if (tcv > 1.5) s += 0.4; else if (tcv > 1.0) s += 0.2;
+            if (md < 0.3 && S.frame_count > 10) s += 0.3;
+            else if (md < 0.8 && S.frame_count > 10) s += 0.1;
+            sc[5] = clip01(s);
+        }
+    }
+    double comb = 0.0;
+    if (full) {
+        const double w[6] = {0.25, 0.20, 0.20, 0.15, 0.10, 0.10};
+        for (int i = 0; i < 6; ++i) comb += sc[i] * w[i];
+    } else {
+        comb += sc[0] * 0.45;
+        comb += sc[5] * 0.25;
+        comb += sc[3] * 0.30;
+    }
+    return clip01(comb);
+}
+
+// the stream's stored gray plane: a released stream's plane when there is one (no hipMalloc on the serving path)
+int stream_plane(dfd_handle* h, ForensicStream& S) {
+    if (S.prev_gray) return DFD_OK;
+    ForensicState& F = *h->forensic;
+    if (!F.free_planes.empty()) {
+        S.prev_gray = F.free_planes.back();
+        F.free_planes.pop_back();
+        return DFD_OK;
+    }
+    DFD_HIP_TRY(h, hipMalloc(&S.prev_gray, 65536));
+    h->owned.push_back(S.prev_gray);
+    return DFD_OK;
+}
+
 }  // namespace
 
 namespace dfd {
@@ -134,15 +193,10 @@ int forensics_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh
     if (rc) return rc;
     ForensicState& F = *h->forensic;
     ForensicStream& S = F.streams[stream_id];
-    if (!S.prev_gray) {
-        DFD_HIP_TRY(h, hipMalloc(&S.prev_gray, 65536));
-        h->owned.push_back(S.prev_gray);
-    }
-    S.frame_count += 1;                                              // frame_analysis.py:68,110
+    if ((rc = stream_plane(h, S))) return rc;
 
     launch_resize_bgr(frame_dev, 1, hh, ww, stride, 0, F.buf.rs, 256, 256, h->stream);
     launch_forensics(F.buf, 1, full != 0, h->color, F.twiddle, h->stream);
-    double mean_diff = -1.0;
     if (S.has_prev) launch_absdiff(F.buf.gray, (const uint8_t*)S.prev_gray, F.diff_part, h->stream);
     double st[FORENSIC_STATS], noise[64], ela[64], dpart[256];
     DFD_HIP_TRY(h, hipMemcpyAsync(st, F.buf.stats, sizeof st, hipMemcpyDeviceToHost, h->stream));
@@ -156,45 +210,12 @@ int forensics_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh
     DFD_HIP_TRY(h, hipGetLastError());
 
     const double nan = std::nan("");
-    double sc[6], ex[10];
-    static_scores(st, noise, ela, full != 0, sc, ex);
+    double sc[6], ex[10], mean_diff, temporal_cv;
+    *prob_out = score_frame(S, st, noise, ela, full != 0, dpart, sc, ex, &mean_diff, &temporal_cv);
     const double lo = ex[0], mi = ex[1], hi = ex[2], hr = ex[3], mr = ex[4], mid_cv = ex[5];
     const double noise_mean = ex[6], noise_cv = ex[7], ela_mean = ex[8], ela_cv = ex[9];
     const double density = st[ST_EDGE_COUNT] / 65536.0, lap_var = st[ST_LAP_VAR];
-    double s = 0.0;
-    // ---- temporal (:358-389)
-    double temporal_cv = nan;
-    if (!S.has_prev) {
-        S.has_prev = true;
-    } else {
-        double sum = 0;
-        for (int i = 0; i < 256; ++i) sum += dpart[i];
-        mean_diff = sum / 65536.0;
-        S.diffs.push_back(mean_diff);
-        if (S.diffs.size() > 30) S.diffs.pop_front();
-        if (S.diffs.size() >= 5) {
-            std::vector<double> d(S.diffs.begin(), S.diffs.end());
-            double dm;
-            temporal_cv = pop_std(d.data(), (int)d.size(), &dm) / (dm + 1e-10);
-            s = 0.0;
-            if (temporal_cv > 1.5) s += 0.4; else if (temporal_cv > 1.0) s += 0.2;
-            if (mean_diff < 0.3 && S.frame_count > 10) s += 0.3;
-            else if (mean_diff < 0.8 && S.frame_count > 10) s += 0.1;
-            sc[5] = clip01(s);
-        }
-    }
-    // ---- weighted sum in the reference's dict order (:49-56,88 / :118-119)
-    double comb = 0.0;
-    if (full) {
-        const double w[6] = {0.25, 0.20, 0.20, 0.15, 0.10, 0.10};
-        for (int i = 0; i < 6; ++i) comb += sc[i] * w[i];
-    } else {
-        comb += sc[0] * 0.45;
-        comb += sc[5] * 0.25;
-        comb += sc[3] * 0.30;
-    }
     for (int i = 0; i < 6; ++i) scores_out[i] = sc[i];
-    *prob_out = clip01(comb);
     if (stats_out) {
         const double out[DFD_FORENSIC_NSTATS] = {lo, mi, hi, hr, mr, mid_cv, noise_mean, noise_cv, ela_mean, ela_cv,
                                                  density, lap_var, full ? st[ST_SAT_STD] : nan, full ? st[ST_VAL_STD] : nan,
@@ -204,78 +225,53 @@ int forensics_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh
     return DFD_OK;
 }
 
-// n consecutive frames of one stream in one launch set (POST /analyze_batch): the device statistics of all frames at
-// once (full mode kernels when any frame is full), frame 0 differenced against the stream's stored gray plane and
-// frame i against frame i - 1, then the host half of forensics_run replayed frame by frame in order - the temporal
-// deque, the frame counter and the stored plane end exactly where n single calls would leave them.
-int forensics_stream_batch_run(dfd_handle* h, int stream_id, const uint8_t* frames_dev, int n, int hh, int ww, int stride,
-                               size_t frame_bytes, const int* full, double* scores_out, double* prob_out) {
+// n frames of any streams and sizes in one launch set (POST /analyze_batch, the session pool): the device statistics of
+// all frames at once (full mode kernels when any frame is full), every frame differenced against its predecessor - the
+// previous frame of its stream in this call, else the stream's stored plane - in one launch, each stream's last gray
+// plane written back to its stored slot in one launch, then the host half replayed frame by frame in order: every
+// stream's temporal deque, frame counter and stored plane end exactly where single calls in order would leave them.
+int forensics_streams_run(dfd_handle* h, const uint8_t* frames_dev, const FrameDesc* fd, int n, const int* stream_ids,
+                          const int* full, double* scores_out, double* prob_out) {
     if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
     int rc = state_init(h, n);
     if (rc) return rc;
     ForensicState& F = *h->forensic;
-    ForensicStream& S = F.streams[stream_id];
-    if (!S.prev_gray) {
-        DFD_HIP_TRY(h, hipMalloc(&S.prev_gray, 65536));
-        h->owned.push_back(S.prev_gray);
-    }
     bool any_full = false;
-    for (int f = 0; f < n; ++f) any_full = any_full || full[f] != 0;
-    if ((rc = ensure(h, &F.pair_idx, (size_t)n * 4))) return rc;
+    std::vector<const uint8_t*> prev(n);
+    std::map<int, int> last;                                         // stream -> its latest frame so far in this call
+    for (int f = 0; f < n; ++f) {
+        any_full = any_full || full[f] != 0;
+        ForensicStream& S = F.streams[stream_ids[f]];
+        if ((rc = stream_plane(h, S))) return rc;
+        auto it = last.find(stream_ids[f]);
+        prev[f] = it != last.end() ? F.buf.gray + (size_t)it->second * 65536 : S.has_prev ? (const uint8_t*)S.prev_gray : nullptr;
+        last[stream_ids[f]] = f;
+    }
+    std::vector<PlaneCopy> back;
+    for (const auto& kv : last) back.push_back(PlaneCopy{F.buf.gray + (size_t)kv.second * 65536, (uint8_t*)F.streams[kv.first].prev_gray});
+    if ((rc = ensure(h, &F.frame_desc, (size_t)n * sizeof(FrameDesc)))) return rc;
+    if ((rc = ensure(h, &F.prev_tab, (size_t)n * sizeof(void*)))) return rc;
+    if ((rc = ensure(h, &F.copy_tab, back.size() * sizeof(PlaneCopy)))) return rc;
     if ((rc = ensure(h, &F.pair_part, (size_t)n * 256 * 8))) return rc;
-    std::vector<int32_t> prev(n);
-    for (int f = 0; f < n; ++f) prev[f] = f - 1;                   // frame 0: the stored plane (below)
-    if ((rc = mailbox_h2d(h, F.pair_idx.p, prev.data(), (size_t)n * 4))) return rc;
-    launch_resize_bgr(frames_dev, n, hh, ww, stride, frame_bytes, F.buf.rs, 256, 256, h->stream);
+    if ((rc = mailbox_h2d(h, F.frame_desc.p, fd, (size_t)n * sizeof(FrameDesc)))) return rc;
+    if ((rc = mailbox_h2d(h, F.prev_tab.p, prev.data(), (size_t)n * sizeof(void*)))) return rc;
+    if ((rc = mailbox_h2d(h, F.copy_tab.p, back.data(), back.size() * sizeof(PlaneCopy)))) return rc;
+    launch_resize_bgr_ragged(frames_dev, (const FrameDesc*)F.frame_desc.p, n, F.buf.rs, 256, 256, h->stream);
     launch_forensics(F.buf, n, any_full, h->color, F.twiddle, h->stream);
-    const bool had_prev = S.has_prev;
-    if (had_prev) launch_absdiff(F.buf.gray, (const uint8_t*)S.prev_gray, F.diff_part, h->stream);
-    if (n > 1) launch_absdiff_pairs(F.buf.gray, (const int*)F.pair_idx.p, (double*)F.pair_part.p, n, h->stream);
+    launch_absdiff_prev(F.buf.gray, (const uint8_t* const*)F.prev_tab.p, (double*)F.pair_part.p, n, h->stream);
+    launch_copy_planes((const PlaneCopy*)F.copy_tab.p, (int)back.size(), h->stream);
     const double* st = (const double*)mailbox_d2h(h, F.buf.stats, (size_t)n * FORENSIC_STATS * 8);
     const double* noise = (const double*)mailbox_d2h(h, F.buf.stats_noise, (size_t)n * 64 * 8);
     const double* ela = (const double*)mailbox_d2h(h, F.buf.stats_ela, (size_t)n * 64 * 8);
     const double* part = (const double*)mailbox_d2h(h, F.pair_part.p, (size_t)n * 256 * 8);
-    const double* part0 = (const double*)mailbox_d2h(h, F.diff_part, 256 * 8);
-    if (!st || !noise || !ela || !part || !part0) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
-    DFD_HIP_TRY(h, hipMemcpyAsync(S.prev_gray, F.buf.gray + (size_t)(n - 1) * 65536, 65536, hipMemcpyDeviceToDevice, h->stream));
+    if (!st || !noise || !ela || !part) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
     DFD_HIP_TRY(h, stream_sync(h));
     DFD_HIP_TRY(h, hipGetLastError());
     for (int f = 0; f < n; ++f) {
-        S.frame_count += 1;
-        const bool fl = full[f] != 0;
-        double sc[6], ex[10];
-        static_scores(&st[(size_t)f * FORENSIC_STATS], &noise[(size_t)f * 64], &ela[(size_t)f * 64], fl, sc, ex);
-        if (!S.has_prev) {
-            S.has_prev = true;
-        } else {
-            const double* dp = f == 0 ? part0 : part + (size_t)f * 256;
-            double sum = 0;
-            for (int i = 0; i < 256; ++i) sum += dp[i];
-            const double mean_diff = sum / 65536.0;
-            S.diffs.push_back(mean_diff);
-            if (S.diffs.size() > 30) S.diffs.pop_front();
-            if (S.diffs.size() >= 5) {
-                std::vector<double> d(S.diffs.begin(), S.diffs.end());
-                double dm;
-                const double temporal_cv = pop_std(d.data(), (int)d.size(), &dm) / (dm + 1e-10);
-                double s = 0.0;
-                if (temporal_cv > 1.5) s += 0.4; else if (temporal_cv > 1.0) s += 0.2;
-                if (mean_diff < 0.3 && S.frame_count > 10) s += 0.3;
-                else if (mean_diff < 0.8 && S.frame_count > 10) s += 0.1;
-                sc[5] = clip01(s);
-            }
-        }
-        double comb = 0.0;
-        if (fl) {
-            const double w[6] = {0.25, 0.20, 0.20, 0.15, 0.10, 0.10};
-            for (int i = 0; i < 6; ++i) comb += sc[i] * w[i];
-        } else {
-            comb += sc[0] * 0.45;
-            comb += sc[5] * 0.25;
-            comb += sc[3] * 0.30;
-        }
+        double sc[6], ex[10], md, tcv;
+        prob_out[f] = score_frame(F.streams[stream_ids[f]], &st[(size_t)f * FORENSIC_STATS], &noise[(size_t)f * 64],
+                                  &ela[(size_t)f * 64], full[f] != 0, part + (size_t)f * 256, sc, ex, &md, &tcv);
         for (int i = 0; i < 6; ++i) scores_out[(size_t)f * 6 + i] = sc[i];
-        prob_out[f] = clip01(comb);
     }
     return DFD_OK;
 }
@@ -443,6 +439,17 @@ int dfd_forensics_reset(dfd_handle* h, int stream_id) {
     it->second.has_prev = false;                 // frame_analysis.py:391-395
     it->second.diffs.clear();
     it->second.frame_count = 0;
+    return DFD_OK;
+}
+
+int dfd_forensics_release(dfd_handle* h, int stream_id) {
+    if (!h) return DFD_ERR_ARG;
+    if (!h->forensic) return DFD_OK;
+    ForensicState& F = *h->forensic;
+    auto it = F.streams.find(stream_id);
+    if (it == F.streams.end()) return DFD_OK;
+    if (it->second.prev_gray) F.free_planes.push_back(it->second.prev_gray);   // every call that used it has synchronised
+    F.streams.erase(it);
     return DFD_OK;
 }
 

@@ -36,5 +36,10 @@ void launch_forensics(const ForensicBuffers& B, int n, bool full, const ColorTab
                       int gray_only = 0);
 void launch_absdiff(const uint8_t* gray, const uint8_t* prev, double* part256, hipStream_t s);
 void launch_absdiff_pairs(const uint8_t* gray, const int* prev_index, double* part /*[n][256]*/, int n, hipStream_t s);
+// frame f of gray [n][65536] against the plane prev_dev[f] (device pointer table; null = no predecessor, sums 0)
+void launch_absdiff_prev(const uint8_t* gray, const uint8_t* const* prev_dev, double* part /*[n][256]*/, int n, hipStream_t s);
+// n 65536-byte gray planes src -> dst (16-byte aligned), one launch
+struct PlaneCopy { const uint8_t* src; uint8_t* dst; };
+void launch_copy_planes(const PlaneCopy* pairs_dev, int n, hipStream_t s);
 
 }  // namespace dfd

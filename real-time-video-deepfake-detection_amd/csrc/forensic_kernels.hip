@@ -537,6 +537,34 @@ void launch_absdiff(const uint8_t* gray, const uint8_t* prev, double* part, hipS
     hipLaunchKernelGGL(absdiff_kernel, dim3(256), dim3(256), 0, s, gray, prev, part);
 }
 
+// frames of many streams: frame f against the gray plane prev[f] - an earlier frame of its stream in this batch or the
+// stream's stored plane - or, prev[f] = null, nothing (partial sums 0).  The same sums as absdiff_kernel.  part: [n][256].
+__global__ __launch_bounds__(256) void absdiff_prev_kernel(const uint8_t* __restrict__ gray, const uint8_t* const* __restrict__ prev,
+                                                           double* __restrict__ part) {
+    __shared__ double red[4];
+    const int f = blockIdx.y;
+    const uint8_t* p = prev[f];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int d = p ? abs((int)gray[(size_t)f * FPIX + i] - (int)p[i]) : 0;
+    const double t = block_sum<256>((double)d, red);
+    if (threadIdx.x == 0) part[(size_t)f * 256 + blockIdx.x] = t;
+}
+
+void launch_absdiff_prev(const uint8_t* gray, const uint8_t* const* prev_dev, double* part, int n, hipStream_t s) {
+    hipLaunchKernelGGL(absdiff_prev_kernel, dim3(256, n), dim3(256), 0, s, gray, prev_dev, part);
+}
+
+// one 65536-byte plane per table entry, 16 bytes per thread (4096 per plane: 16 blocks of 256)
+__global__ __launch_bounds__(256) void copy_planes_kernel(const PlaneCopy* __restrict__ pairs) {
+    const PlaneCopy pc = pairs[blockIdx.y];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    reinterpret_cast<uint4*>(pc.dst)[i] = reinterpret_cast<const uint4*>(pc.src)[i];
+}
+
+void launch_copy_planes(const PlaneCopy* pairs_dev, int n, hipStream_t s) {
+    hipLaunchKernelGGL(copy_planes_kernel, dim3(FPIX / 16 / 256, n), dim3(256), 0, s, pairs_dev);
+}
+
 }  // namespace dfd
 
 namespace dfd {

@@ -178,8 +178,9 @@ int upload_frame(dfd_handle* h, const uint8_t* bgr, int hh, int ww, int stride) 
 }
 
 // validates the boxes, lays the packed crops out in the scratch buffers, uploads descriptors
-int stage_crops(dfd_handle* h, int hh, int ww, const int32_t* xywh, int n, size_t* total, int* max_pixels,
-                const size_t* frame_offs = nullptr) {
+// crop_frames: per-crop frame (offset, size, stride) of a ragged batch; it replaces hh / ww / stride / frame_offs
+int stage_crops(dfd_handle* h, int hh, int ww, int stride, const int32_t* xywh, int n, size_t* total, int* max_pixels,
+                const size_t* frame_offs = nullptr, const FrameDesc* crop_frames = nullptr) {
     if (!xywh || n <= 0) return fail(h, DFD_ERR_ARG, "crops: null boxes or n <= 0");
     if (n > h->max_batch) return fail(h, DFD_ERR_CAPACITY, "crops: %d boxes exceed handle capacity %d", n, h->max_batch);
     std::vector<CropDesc> d(n);
@@ -187,9 +188,10 @@ int stage_crops(dfd_handle* h, int hh, int ww, const int32_t* xywh, int n, size_
     int mp = 0;
     for (int i = 0; i < n; ++i) {
         const int x = xywh[4 * i], y = xywh[4 * i + 1], w = xywh[4 * i + 2], hgt = xywh[4 * i + 3];
-        if (w <= 0 || hgt <= 0 || x < 0 || y < 0 || x + w > ww || y + hgt > hh)
-            return fail(h, DFD_ERR_ARG, "crops: box %d (%d,%d,%d,%d) outside the %dx%d frame", i, x, y, w, hgt, ww, hh);
-        d[i] = CropDesc{x, y, w, hgt, off, frame_offs ? frame_offs[i] : 0};
+        const FrameDesc f = crop_frames ? crop_frames[i] : FrameDesc{frame_offs ? frame_offs[i] : 0, hh, ww, stride};
+        if (w <= 0 || hgt <= 0 || x < 0 || y < 0 || x + w > f.w || y + hgt > f.h)
+            return fail(h, DFD_ERR_ARG, "crops: box %d (%d,%d,%d,%d) outside the %dx%d frame", i, x, y, w, hgt, f.w, f.h);
+        d[i] = CropDesc{x, y, w, hgt, off, f.offset, (size_t)f.stride};
         off += ((size_t)w * hgt * 3 + 255) & ~(size_t)255;
         if (w * hgt > mp) mp = w * hgt;
     }
@@ -205,17 +207,18 @@ int stage_crops(dfd_handle* h, int hh, int ww, const int32_t* xywh, int n, size_
 // compact: in_nchw receives only the crops the MTCNN stage kept (h->n_compact rows, crop order); without the stage, or
 // with compact = false, all n rows (a rejected crop's row is then the zero-filled face, as facenet-pytorch never returns)
 int preprocess_on_device(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride,
-                         const int32_t* xywh, int n, int apply_clahe, const size_t* frame_offs = nullptr, bool compact = false) {
+                         const int32_t* xywh, int n, int apply_clahe, const size_t* frame_offs = nullptr, bool compact = false,
+                         const FrameDesc* crop_frames = nullptr) {
     size_t total = 0;
     int mp = 0, rc;
-    if ((rc = stage_crops(h, hh, ww, xywh, n, &total, &mp, frame_offs))) return rc;
+    if ((rc = stage_crops(h, hh, ww, stride, xywh, n, &total, &mp, frame_offs, crop_frames))) return rc;
     const CropDesc* dd = static_cast<const CropDesc*>(h->desc_buf.p);
     if (apply_clahe) {
         if (!h->has_color) return fail(h, DFD_ERR_STATE, "CLAHE needs the colour tables (blob packed without luts)");
         if ((rc = ensure(h, &h->lab_buf, total))) return rc;
         if ((rc = ensure(h, &h->crop_buf, total))) return rc;
         if ((rc = ensure(h, &h->lut_buf, (size_t)n * 64 * 256))) return rc;
-        launch_clahe(frame_dev, stride, dd, n, (uint8_t*)h->lab_buf.p, (uint8_t*)h->lut_buf.p,
+        launch_clahe(frame_dev, dd, n, (uint8_t*)h->lab_buf.p, (uint8_t*)h->lut_buf.p,
                      (uint8_t*)h->crop_buf.p, h->color, mp, h->stream);
     }
     h->crop_valid.assign(n, 1);
@@ -230,9 +233,10 @@ int preprocess_on_device(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww
         size_t off = 0;
         for (int i = 0; i < n; ++i) {
             const int x = xywh[4 * i], y = xywh[4 * i + 1], w = xywh[4 * i + 2], hgt = xywh[4 * i + 3];
-            const uint8_t* img = apply_clahe ? (const uint8_t*)h->crop_buf.p + off
-                                             : frame_dev + (frame_offs ? frame_offs[i] : 0) + (size_t)y * stride + (size_t)x * 3;
-            imgs[i] = MtImage{img, hgt, w, apply_clahe ? (size_t)w * 3 : (size_t)stride};
+            const size_t fo = crop_frames ? crop_frames[i].offset : frame_offs ? frame_offs[i] : 0;
+            const size_t fs = crop_frames ? (size_t)crop_frames[i].stride : (size_t)stride;
+            const uint8_t* img = apply_clahe ? (const uint8_t*)h->crop_buf.p + off : frame_dev + fo + (size_t)y * fs + (size_t)x * 3;
+            imgs[i] = MtImage{img, hgt, w, apply_clahe ? (size_t)w * 3 : fs};
             off += ((size_t)w * hgt * 3 + 255) & ~(size_t)255;        // as stage_crops lays the packed crops out
         }
         // the cascade returns after its last stream wait with the per-crop flags (one 32-byte row per crop): what the
@@ -244,15 +248,15 @@ int preprocess_on_device(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww
         std::vector<CropDesc> fd;
         fd.reserve(n);
         for (int i = 0; i < n; ++i)
-            if (!compact || h->crop_valid[i]) fd.push_back(CropDesc{0, 0, 160, 160, 0, (size_t)i * 160 * 160 * 3});
+            if (!compact || h->crop_valid[i]) fd.push_back(CropDesc{0, 0, 160, 160, 0, (size_t)i * 160 * 160 * 3, 160 * 3});
         h->n_compact = (int)fd.size();
         if (fd.empty()) return DFD_OK;
         if ((rc = mailbox_h2d(h, h->desc_buf.p, fd.data(), fd.size() * sizeof(CropDesc)))) return rc;
-        launch_crop_norm((const uint8_t*)h->face_batch.p, 160 * 3, nullptr, dd, (int)fd.size(), h->in_nchw, false, h->stream);
+        launch_crop_norm((const uint8_t*)h->face_batch.p, nullptr, dd, (int)fd.size(), h->in_nchw, false, h->stream);
         DFD_HIP_TRY(h, hipGetLastError());
         return DFD_OK;
     }
-    launch_crop_norm(frame_dev, stride, (const uint8_t*)h->crop_buf.p, dd, n, h->in_nchw, apply_clahe != 0, h->stream);
+    launch_crop_norm(frame_dev, (const uint8_t*)h->crop_buf.p, dd, n, h->in_nchw, apply_clahe != 0, h->stream);
     DFD_HIP_TRY(h, hipGetLastError());
     return DFD_OK;
 }
@@ -266,9 +270,9 @@ int preprocess_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int 
 }
 
 int classify_boxes(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride, const int32_t* xywh, int m,
-                   int apply_clahe, const size_t* frame_offs, float* logits_out) {
+                   int apply_clahe, const size_t* frame_offs, float* logits_out, const FrameDesc* crop_frames) {
     int rc;
-    if ((rc = preprocess_on_device(h, frame_dev, hh, ww, stride, xywh, m, apply_clahe, frame_offs, true))) return rc;
+    if ((rc = preprocess_on_device(h, frame_dev, hh, ww, stride, xywh, m, apply_clahe, frame_offs, true, crop_frames))) return rc;
     const int k = h->n_compact;
     const float* lg = nullptr;
     if (k > 0) {
@@ -403,12 +407,12 @@ int dfd_preprocess_face_quality(dfd_handle* h, const uint8_t* bgr, int hh, int w
     size_t total = 0;
     int mp = 0;
     const int saved = h->max_batch;
-    if ((rc = stage_crops(h, hh, ww, box, 1, &total, &mp))) return rc;
+    if ((rc = stage_crops(h, hh, ww, stride, box, 1, &total, &mp))) return rc;
     (void)saved;
     if ((rc = ensure(h, &h->lab_buf, total))) return rc;
     if ((rc = ensure(h, &h->crop_buf, total))) return rc;
     if ((rc = ensure(h, &h->lut_buf, 64 * 256))) return rc;
-    launch_clahe((const uint8_t*)h->frame_buf.p, stride, (const CropDesc*)h->desc_buf.p, 1, (uint8_t*)h->lab_buf.p,
+    launch_clahe((const uint8_t*)h->frame_buf.p, (const CropDesc*)h->desc_buf.p, 1, (uint8_t*)h->lab_buf.p,
                  (uint8_t*)h->lut_buf.p, (uint8_t*)h->crop_buf.p, h->color, mp, h->stream);
     DFD_HIP_TRY(h, hipMemcpyAsync(out, h->crop_buf.p, (size_t)hh * ww * 3, hipMemcpyDeviceToHost, h->stream));
     DFD_HIP_TRY(h, stream_sync(h));

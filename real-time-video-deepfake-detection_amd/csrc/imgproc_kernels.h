@@ -16,10 +16,20 @@ struct CropDesc {
     int x, y, w, h;        // box in the frame
     size_t offset;         // byte offset of this crop's packed w*h*3 region in the scratch buffers
     size_t src_off;        // byte offset of the crop's frame inside the frame buffer (batched frames)
+    size_t stride;         // row stride of that frame (frames of different widths share one batch)
+};
+
+// one frame of a ragged batch: byte offset in the frame arena, size, row stride
+struct FrameDesc {
+    size_t offset;
+    int h, w, stride;
 };
 
 void launch_resize_bgr(const uint8_t* src, int n, int sh, int sw, size_t sstride, size_t simg,
                        uint8_t* dst, int dh, int dw, hipStream_t s);
+// the same for n frames of their own sizes (frames_dev: n descriptors on the device) -> [n][dh][dw][3]
+void launch_resize_bgr_ragged(const uint8_t* src, const FrameDesc* frames_dev, int n, uint8_t* dst, int dh, int dw,
+                              hipStream_t s);
 // single-channel cv2.resize(INTER_LINEAR) and u8 -> float (x scale)
 // test-time augmentation of a face crop (flip, brightness, small rotation) as the reference builds it with cv2;
 // mi = the inverted 2x3 affine matrix (warpAffine's internal form)
@@ -27,9 +37,10 @@ void launch_tta_augment(const uint8_t* src, int h, int w, int stride, int flip, 
                         hipStream_t s);
 void launch_resize_gray(const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw, hipStream_t s);
 void u8_to_float(const uint8_t* src, float* dst, int n, float scale, hipStream_t s);
-void launch_clahe(const uint8_t* frame, size_t fstride, const CropDesc* crops_dev, int n, uint8_t* lab,
+// both read a crop's source rows with the row stride of its descriptor
+void launch_clahe(const uint8_t* frame, const CropDesc* crops_dev, int n, uint8_t* lab,
                   uint8_t* luts, uint8_t* bgr_out, const ColorTables& T, int max_pixels, hipStream_t s);
-void launch_crop_norm(const uint8_t* frame, size_t fstride, const uint8_t* scratch, const CropDesc* crops_dev,
+void launch_crop_norm(const uint8_t* frame, const uint8_t* scratch, const CropDesc* crops_dev,
                       int n, float* out_nchw, bool from_scratch, hipStream_t s);
 
 }  // namespace dfd

@@ -44,15 +44,10 @@ __device__ __forceinline__ Tap linear_tap(int d, int src_n, int dst_n, bool is_x
     return t;
 }
 
+// destination pixel (dy, dx) of one image: the per-pixel body of both resize kernels below
 template <int C>
-__global__ __launch_bounds__(256) void resize_linear_u8_kernel(const uint8_t* __restrict__ src, int sh,
-                                                               int sw, size_t sstride, size_t simg,
-                                                               uint8_t* __restrict__ dst, int dh, int dw) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= dh * dw) return;
-    const int dy = idx / dw, dx = idx % dw;
-    const uint8_t* s = src + (size_t)blockIdx.y * simg;
-    uint8_t* d = dst + ((size_t)blockIdx.y * dh * dw + idx) * C;
+__device__ __forceinline__ void resize_linear_px(const uint8_t* __restrict__ s, int sh, int sw, size_t sstride,
+                                                 uint8_t* __restrict__ d, int dy, int dx, int dh, int dw) {
     if (sh == dh && sw == dw) {
 #pragma unroll
         for (int c = 0; c < C; ++c) d[c] = s[(size_t)dy * sstride + dx * C + c];
@@ -70,10 +65,37 @@ __global__ __launch_bounds__(256) void resize_linear_u8_kernel(const uint8_t* __
     }
 }
 
+template <int C>
+__global__ __launch_bounds__(256) void resize_linear_u8_kernel(const uint8_t* __restrict__ src, int sh,
+                                                               int sw, size_t sstride, size_t simg,
+                                                               uint8_t* __restrict__ dst, int dh, int dw) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= dh * dw) return;
+    resize_linear_px<C>(src + (size_t)blockIdx.y * simg, sh, sw, sstride, dst + ((size_t)blockIdx.y * dh * dw + idx) * C,
+                        idx / dw, idx % dw, dh, dw);
+}
+
+// frames of different sizes in one launch: image blockIdx.y is read through its descriptor
+__global__ __launch_bounds__(256) void resize_linear_u8_ragged_kernel(const uint8_t* __restrict__ src,
+                                                                      const FrameDesc* __restrict__ frames,
+                                                                      uint8_t* __restrict__ dst, int dh, int dw) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= dh * dw) return;
+    const FrameDesc fd = frames[blockIdx.y];
+    resize_linear_px<3>(src + fd.offset, fd.h, fd.w, (size_t)fd.stride, dst + ((size_t)blockIdx.y * dh * dw + idx) * 3,
+                        idx / dw, idx % dw, dh, dw);
+}
+
 void launch_resize_bgr(const uint8_t* src, int n, int sh, int sw, size_t sstride, size_t simg,
                        uint8_t* dst, int dh, int dw, hipStream_t s) {
     hipLaunchKernelGGL(resize_linear_u8_kernel<3>, dim3((dh * dw + 255) / 256, n), dim3(256), 0, s, src, sh,
                        sw, sstride, simg, dst, dh, dw);
+}
+
+void launch_resize_bgr_ragged(const uint8_t* src, const FrameDesc* frames_dev, int n, uint8_t* dst, int dh, int dw,
+                              hipStream_t s) {
+    hipLaunchKernelGGL(resize_linear_u8_ragged_kernel, dim3((dh * dw + 255) / 256, n), dim3(256), 0, s, src, frames_dev,
+                       dst, dh, dw);
 }
 
 void launch_resize_gray(const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw, hipStream_t s) {
@@ -125,7 +147,7 @@ __device__ __forceinline__ void bgr2lab_lds(const ColorTables& T, const LabLds& 
     B = clampi((200 * (fY - fZ) + 128 * (1 << 15) + (1 << 14)) >> 15, 0, 255);
 }
 
-__global__ __launch_bounds__(256) void clahe_hist_kernel(const uint8_t* __restrict__ frame, size_t fstride,
+__global__ __launch_bounds__(256) void clahe_hist_kernel(const uint8_t* __restrict__ frame,
                                                          const CropDesc* __restrict__ crops,
                                                          uint8_t* __restrict__ lab_out,
                                                          uint8_t* __restrict__ luts, ColorTables T,
@@ -136,6 +158,7 @@ __global__ __launch_bounds__(256) void clahe_hist_kernel(const uint8_t* __restri
     __shared__ int clipped_total;
     const int tid = threadIdx.x;
     const CropDesc cd = crops[blockIdx.y];
+    const size_t fstride = cd.stride;
     int ew, eh;
     clahe_geometry(cd, ew, eh);
     const int tw = ew / 8, th = eh / 8;
@@ -298,7 +321,7 @@ __global__ __launch_bounds__(256) void clahe_apply_kernel(const CropDesc* __rest
 // ------------------------------------------------------------------ crop -> network input
 // torch F.interpolate(bilinear, align_corners=False) on the RGB float crop, /255, normalise.
 // from_scratch: read the CLAHE'd packed crop; else read the box straight from the frame.
-__global__ __launch_bounds__(256) void crop_norm_kernel(const uint8_t* __restrict__ frame, size_t fstride,
+__global__ __launch_bounds__(256) void crop_norm_kernel(const uint8_t* __restrict__ frame,
                                                         const uint8_t* __restrict__ scratch,
                                                         const CropDesc* __restrict__ crops,
                                                         float* __restrict__ out_nchw, int from_scratch) {
@@ -320,6 +343,7 @@ __global__ __launch_bounds__(256) void crop_norm_kernel(const uint8_t* __restric
         p00 = b + ((size_t)y0 * cd.w + x0) * 3; p01 = b + ((size_t)y0 * cd.w + x1) * 3;
         p10 = b + ((size_t)y1 * cd.w + x0) * 3; p11 = b + ((size_t)y1 * cd.w + x1) * 3;
     } else {
+        const size_t fstride = cd.stride;
         const uint8_t* b = frame + cd.src_off + (size_t)cd.y * fstride + (size_t)cd.x * 3;
         p00 = b + (size_t)y0 * fstride + x0 * 3; p01 = b + (size_t)y0 * fstride + x1 * 3;
         p10 = b + (size_t)y1 * fstride + x0 * 3; p11 = b + (size_t)y1 * fstride + x1 * 3;
@@ -334,9 +358,9 @@ __global__ __launch_bounds__(256) void crop_norm_kernel(const uint8_t* __restric
     }
 }
 
-void launch_clahe(const uint8_t* frame, size_t fstride, const CropDesc* crops_dev, int n, uint8_t* lab,
+void launch_clahe(const uint8_t* frame, const CropDesc* crops_dev, int n, uint8_t* lab,
                   uint8_t* luts, uint8_t* bgr_out, const ColorTables& T, int max_pixels, hipStream_t s) {
-    hipLaunchKernelGGL(clahe_hist_kernel, dim3(64, n), dim3(256), 0, s, frame, fstride, crops_dev, lab, luts, T, 2.0f);
+    hipLaunchKernelGGL(clahe_hist_kernel, dim3(64, n), dim3(256), 0, s, frame, crops_dev, lab, luts, T, 2.0f);
     // blocks per crop: each stages 22 KB of tables, so a block gets >= 1024 pixel groups (one crop alone still fills
     // the chip's eighth: the request path) and a large batch 8 blocks per crop
     int gx = (max_pixels / 4 + 1023) / 1024;
@@ -346,9 +370,9 @@ void launch_clahe(const uint8_t* frame, size_t fstride, const CropDesc* crops_de
     hipLaunchKernelGGL(clahe_apply_kernel, dim3(gx, n), dim3(256), 0, s, crops_dev, lab, luts, bgr_out, T);
 }
 
-void launch_crop_norm(const uint8_t* frame, size_t fstride, const uint8_t* scratch, const CropDesc* crops_dev,
+void launch_crop_norm(const uint8_t* frame, const uint8_t* scratch, const CropDesc* crops_dev,
                       int n, float* out_nchw, bool from_scratch, hipStream_t s) {
-    hipLaunchKernelGGL(crop_norm_kernel, dim3((224 * 224 + 255) / 256, n), dim3(256), 0, s, frame, fstride,
+    hipLaunchKernelGGL(crop_norm_kernel, dim3((224 * 224 + 255) / 256, n), dim3(256), 0, s, frame,
                        scratch, crops_dev, out_nchw, from_scratch ? 1 : 0);
 }
 

@@ -84,6 +84,141 @@ int dfd_analyze_batch_device(dfd_handle* h, const uint8_t* frames_dev, int n, in
 // entropy-decoded in parallel on the host pool and turned into frames on the device (raw BGR parts are uploaded),
 // then ONE forensic launch set, ONE detector pass, ONE classifier batch.  Results equal n single calls in order.
 // data[i] / len[i]: the bytes of a JPEG (len[i] > 0) or a packed BGR frame of hh x ww (len[i] = 0).
+}  // extern "C"
+
+namespace {
+
+// n frames of any streams and sizes: every header parsed and every check run before anything is uploaded or any stream
+// state moves (bad_index_out: the refused part, -1 for the call as a whole), the JPEG parts decoded in runs of one size
+// into the frame arena and the raw parts uploaded into their own slots, then ONE forensic launch set, ONE detector pass
+// over the frames of at least 30 px a side, ONE classifier batch per max_batch crops.
+int analyze_streams(dfd_handle* h, int n, const uint8_t* const* data, const size_t* len, const int* heights, const int* widths,
+                    const int* stream_ids, const int* full_forensics, float conf_thr, int max_faces, int apply_clahe,
+                    double* scores_out, double* forensic_prob_out, int32_t* xywh_out, int* n_faces_out, int* n_detected_out,
+                    float* logits_out, int* height_out, int* width_out, int* bad_index_out) {
+    int rc;
+    if (bad_index_out) *bad_index_out = -1;
+    std::vector<int> fh(n), fw(n);
+    size_t pixels = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!data[i]) {
+            if (bad_index_out) *bad_index_out = i;
+            return fail(h, DFD_ERR_ARG, "analyze_streams_batch: frame %d is null", i);
+        }
+        fh[i] = fw[i] = 0;
+        if (len[i]) {
+            rc = jpeg_decode_batch_to(h, &data[i], &len[i], 1, nullptr, &fh[i], &fw[i]);   // headers only
+        } else if (heights[i] <= 0 || widths[i] <= 0) {
+            rc = fail(h, DFD_ERR_ARG, "analyze_streams_batch: raw frame %d needs its height and width", i);
+        } else {
+            fh[i] = heights[i];
+            fw[i] = widths[i];
+            rc = DFD_OK;
+        }
+        if (rc) {
+            if (bad_index_out) *bad_index_out = i;
+            return rc;
+        }
+        pixels += (size_t)fh[i] * (size_t)fw[i];
+    }
+    if (pixels > kMaxBatchPixels)                                    // before any allocation or upload (raw parts too)
+        return fail(h, DFD_ERR_UNSUPPORTED, "analyze_streams_batch: %d frames of %zu pixels exceed the %zu-pixel budget of one request",
+                    n, pixels, kMaxBatchPixels);
+    // arena: the JPEG parts of one size as one contiguous run (one batch decode each), then every raw part in its slot
+    std::vector<FrameDesc> fd(n);
+    std::map<std::pair<int, int>, std::vector<int>> runs;
+    for (int i = 0; i < n; ++i)
+        if (len[i]) runs[{fh[i], fw[i]}].push_back(i);
+    size_t off = 0;
+    auto al256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    for (const auto& r : runs) {
+        const size_t fb = (size_t)r.first.first * r.first.second * 3;
+        for (size_t k = 0; k < r.second.size(); ++k) fd[r.second[k]] = FrameDesc{off + k * fb, r.first.first, r.first.second, r.first.second * 3};
+        off += al256(fb * r.second.size());
+    }
+    for (int i = 0; i < n; ++i)
+        if (!len[i]) {
+            fd[i] = FrameDesc{off, fh[i], fw[i], fw[i] * 3};
+            off += al256((size_t)fh[i] * fw[i] * 3);
+        }
+    if ((rc = ensure(h, &h->stage[0], off))) return rc;
+    uint8_t* frames = static_cast<uint8_t*>(h->stage[0].p);
+    for (int i = 0; i < n; ++i)
+        if (!len[i]) DFD_HIP_TRY(h, hipMemcpyAsync(frames + fd[i].offset, data[i], (size_t)fh[i] * fw[i] * 3, hipMemcpyHostToDevice, h->stream));
+    for (const auto& r : runs) {
+        std::vector<const uint8_t*> jp;
+        std::vector<size_t> jl;
+        for (int i : r.second) { jp.push_back(data[i]); jl.push_back(len[i]); }
+        int rh = r.first.first, rw = r.first.second;
+        rc = jpeg_decode_batch_to(h, jp.data(), jl.data(), (int)jp.size(), frames + fd[r.second[0]].offset, &rh, &rw);
+        if (rc == DFD_ERR_ARG || rc == DFD_ERR_UNSUPPORTED) {
+            // a scan that is corrupt or cut off fails only here, after its headers passed: find the part (each one of the
+            // run decoded on its own) so the caller learns its index.  No stream state has moved yet.
+            for (int i : r.second) {
+                int ih = rh, iw = rw;
+                const int rc1 = jpeg_decode_batch_to(h, &data[i], &len[i], 1, frames + fd[i].offset, &ih, &iw);
+                if (rc1) {
+                    if (bad_index_out && (rc1 == DFD_ERR_ARG || rc1 == DFD_ERR_UNSUPPORTED)) *bad_index_out = i;
+                    return rc1;
+                }
+            }
+            rc = DFD_OK;                                             // every part decodes on its own: the run is in place
+        }
+        if (rc) return rc;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (height_out) height_out[i] = fh[i];
+        if (width_out) width_out[i] = fw[i];
+    }
+    if ((rc = forensics_streams_run(h, frames, fd.data(), n, stream_ids, full_forensics, scores_out, forensic_prob_out))) return rc;
+    for (int f = 0; f < n; ++f) n_faces_out[f] = 0;
+    if (n_detected_out) for (int f = 0; f < n; ++f) n_detected_out[f] = 0;
+    h->last_detections = 0;
+    if (!h->ssd && !h->haar) return DFD_OK;
+    std::vector<int> det;                                            // face_detection.py:55-56: no detection under 30 px
+    for (int f = 0; f < n; ++f)
+        if (fh[f] >= 30 && fw[f] >= 30) det.push_back(f);
+    if (det.empty()) return DFD_OK;
+    std::vector<int> total(n, 0);
+    rc = h->ssd ? detect_frames_run(h, frames, fd.data(), det.data(), (int)det.size(), conf_thr, max_faces, xywh_out, n_faces_out,
+                                    total.data())
+                : DFD_ERR_STATE;
+    if (rc) {                                                        // reference face_detection.py:58-66
+        if (!h->haar) return rc;
+        for (int f : det)
+            if ((rc = haar_run(h, frames + fd[f].offset, fh[f], fw[f], fd[f].stride, 1.1f, 5, 30, xywh_out + (size_t)f * max_faces * 4,
+                               max_faces, &n_faces_out[f], nullptr, &total[f])))
+                return rc;
+    }
+    if (n_detected_out) for (int f = 0; f < n; ++f) n_detected_out[f] = total[f];
+    h->last_detections = total[n - 1];
+    std::vector<int32_t> boxes;
+    std::vector<FrameDesc> crop_frames;
+    for (int f = 0; f < n; ++f)
+        for (int i = 0; i < n_faces_out[f]; ++i) {
+            for (int c = 0; c < 4; ++c) boxes.push_back(xywh_out[((size_t)f * max_faces + i) * 4 + c]);
+            crop_frames.push_back(fd[f]);
+        }
+    const int ncrops = (int)crop_frames.size();
+    std::vector<float> logits(ncrops);
+    for (int start = 0; start < ncrops; start += h->max_batch) {
+        const int m = std::min(h->max_batch, ncrops - start);
+        if ((rc = classify_boxes(h, frames, 0, 0, 0, boxes.data() + (size_t)start * 4, m, apply_clahe, nullptr, logits.data() + start,
+                                 crop_frames.data() + start)))
+            return rc;
+    }
+    int k = 0;
+    for (int f = 0; f < n; ++f)
+        for (int i = 0; i < n_faces_out[f]; ++i) logits_out[(size_t)f * max_faces + i] = logits[k++];
+    return DFD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// one stream: its size rules (one size for all parts, the caller's for raw parts) are checked here, the work is
+// analyze_streams with every frame on stream_id
 int dfd_analyze_stream_batch(dfd_handle* h, int stream_id, int n, const uint8_t* const* data, const size_t* len, int hh, int ww,
                              const int* full_forensics, float conf_thr, int max_faces, int apply_clahe, double* scores_out,
                              double* forensic_prob_out, int32_t* xywh_out, int* n_faces_out, int* n_detected_out,
@@ -97,10 +232,9 @@ int dfd_analyze_stream_batch(dfd_handle* h, int stream_id, int n, const uint8_t*
     // frame size: from the JPEG headers when there is a JPEG part, else the caller's
     std::vector<const uint8_t*> jp;
     std::vector<size_t> jl;
-    std::vector<int> jidx;
     for (int i = 0; i < n; ++i) {
         if (!data[i]) return fail(h, DFD_ERR_ARG, "analyze_stream_batch: frame %d is null", i);
-        if (len[i]) { jp.push_back(data[i]); jl.push_back(len[i]); jidx.push_back(i); }
+        if (len[i]) { jp.push_back(data[i]); jl.push_back(len[i]); }
     }
     if (jp.size() != (size_t)n && (hh <= 0 || ww <= 0)) return fail(h, DFD_ERR_ARG, "analyze_stream_batch: raw frames need hh and ww");
     if (!jp.empty() && (rc = jpeg_decode_batch_to(h, jp.data(), jl.data(), (int)jp.size(), nullptr, &hh, &ww))) return rc;
@@ -109,58 +243,26 @@ int dfd_analyze_stream_batch(dfd_handle* h, int stream_id, int n, const uint8_t*
     if ((size_t)n * (size_t)hh * (size_t)ww > kMaxBatchPixels)         // before any allocation or upload (raw parts too)
         return fail(h, DFD_ERR_UNSUPPORTED, "analyze_stream_batch: %d frames of %d x %d exceed the %zu-pixel budget of one request", n,
                     ww, hh, kMaxBatchPixels);
-    const int stride = ww * 3;
-    const size_t frame_bytes = (size_t)hh * stride;
-    if ((rc = ensure(h, &h->stage[0], (size_t)n * frame_bytes))) return rc;
-    uint8_t* frames = static_cast<uint8_t*>(h->stage[0].p);
+    const std::vector<int> hs(n, hh), ws(n, ww), ids(n, stream_id);
+    return analyze_streams(h, n, data, len, hs.data(), ws.data(), ids.data(), full_forensics, conf_thr, max_faces, apply_clahe,
+                           scores_out, forensic_prob_out, xywh_out, n_faces_out, n_detected_out, logits_out, nullptr, nullptr, nullptr);
+}
+
+int dfd_analyze_streams_batch(dfd_handle* h, int n, const uint8_t* const* data, const size_t* len, const int* heights,
+                              const int* widths, const int* stream_ids, const int* full_forensics, float conf_thr, int max_faces,
+                              int apply_clahe, double* scores_out, double* forensic_prob_out, int32_t* xywh_out, int* n_faces_out,
+                              int* n_detected_out, float* logits_out, int* height_out, int* width_out, int* bad_index_out) {
+    if (!h) return DFD_ERR_ARG;
+    if (bad_index_out) *bad_index_out = -1;
+    if (n <= 0 || !data || !len || !stream_ids || !full_forensics || max_faces <= 0 || !scores_out || !forensic_prob_out ||
+        !xywh_out || !n_faces_out || !logits_out)
+        return fail(h, DFD_ERR_ARG, "analyze_streams_batch: bad pointer or count");
     for (int i = 0; i < n; ++i)
-        if (!len[i]) DFD_HIP_TRY(h, hipMemcpyAsync(frames + (size_t)i * frame_bytes, data[i], frame_bytes, hipMemcpyHostToDevice, h->stream));
-    if (!jp.empty()) {
-        if (jp.size() == (size_t)n) {
-            if ((rc = jpeg_decode_batch_to(h, jp.data(), jl.data(), n, frames, &hh, &ww))) return rc;
-        } else {                                                     // mixed request: the JPEG parts one by one into their slots
-            for (size_t k = 0; k < jp.size(); ++k)
-                if ((rc = jpeg_decode_batch_to(h, &jp[k], &jl[k], 1, frames + (size_t)jidx[k] * frame_bytes, &hh, &ww))) return rc;
-        }
-    }
-    if ((rc = forensics_stream_batch_run(h, stream_id, frames, n, hh, ww, stride, frame_bytes, full_forensics, scores_out,
-                                         forensic_prob_out)))
-        return rc;
-    for (int f = 0; f < n; ++f) n_faces_out[f] = 0;
-    if (n_detected_out) for (int f = 0; f < n; ++f) n_detected_out[f] = 0;
-    h->last_detections = 0;
-    if ((!h->ssd && !h->haar) || hh < 30 || ww < 30) return DFD_OK;
-    std::vector<int> total(n, 0);
-    rc = h->ssd ? detect_batch_run(h, frames, n, hh, ww, stride, frame_bytes, conf_thr, max_faces, xywh_out, n_faces_out, total.data())
-                : DFD_ERR_STATE;
-    if (rc) {                                                        // reference face_detection.py:58-66
-        if (!h->haar) return rc;
-        for (int f = 0; f < n; ++f)
-            if ((rc = haar_run(h, frames + (size_t)f * frame_bytes, hh, ww, stride, 1.1f, 5, 30, xywh_out + (size_t)f * max_faces * 4,
-                               max_faces, &n_faces_out[f], nullptr, &total[f])))
-                return rc;
-    }
-    if (n_detected_out) for (int f = 0; f < n; ++f) n_detected_out[f] = total[f];
-    h->last_detections = total[n - 1];
-    std::vector<int32_t> boxes;
-    std::vector<size_t> offs;
-    for (int f = 0; f < n; ++f)
-        for (int i = 0; i < n_faces_out[f]; ++i) {
-            for (int c = 0; c < 4; ++c) boxes.push_back(xywh_out[((size_t)f * max_faces + i) * 4 + c]);
-            offs.push_back((size_t)f * frame_bytes);
-        }
-    const int ncrops = (int)offs.size();
-    std::vector<float> logits(ncrops);
-    for (int start = 0; start < ncrops; start += h->max_batch) {
-        const int m = std::min(h->max_batch, ncrops - start);
-        if ((rc = classify_boxes(h, frames, hh, ww, stride, boxes.data() + (size_t)start * 4, m, apply_clahe, offs.data() + start,
-                                 logits.data() + start)))
-            return rc;
-    }
-    int k = 0;
-    for (int f = 0; f < n; ++f)
-        for (int i = 0; i < n_faces_out[f]; ++i) logits_out[(size_t)f * max_faces + i] = logits[k++];
-    return DFD_OK;
+        if (!len[i] && (!heights || !widths))
+            return fail(h, DFD_ERR_ARG, "analyze_streams_batch: raw frames need heights and widths");
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    return analyze_streams(h, n, data, len, heights, widths, stream_ids, full_forensics, conf_thr, max_faces, apply_clahe, scores_out,
+                           forensic_prob_out, xywh_out, n_faces_out, n_detected_out, logits_out, height_out, width_out, bad_index_out);
 }
 
 

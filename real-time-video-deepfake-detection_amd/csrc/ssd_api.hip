@@ -454,6 +454,33 @@ int detect_batch_run(dfd_handle* h, const uint8_t* frames_dev, int n, int hh, in
     return DFD_OK;
 }
 
+int detect_frames_run(dfd_handle* h, const uint8_t* frames_dev, const FrameDesc* fd, const int* idx, int m, float conf_thr,
+                      int max_faces, int32_t* xywh_out, int* n_out, int* n_total_out) {
+    if (!h->ssd || !h->ssd->ready) return fail(h, DFD_ERR_STATE, "detector weights were not packed into the blob (weights.pack_all)");
+    int rc;
+    std::vector<FrameDesc> sub(m);
+    for (int j = 0; j < m; ++j) sub[j] = fd[idx[j]];
+    if ((rc = ensure(h, &h->ssd->in_u8, (size_t)m * SSD_IN * SSD_IN * 3))) return rc;
+    if ((rc = ensure(h, &h->det_desc, (size_t)m * sizeof(FrameDesc)))) return rc;
+    if ((rc = mailbox_h2d(h, h->det_desc.p, sub.data(), (size_t)m * sizeof(FrameDesc)))) return rc;
+    launch_resize_bgr_ragged(frames_dev, (const FrameDesc*)h->det_desc.p, m, (uint8_t*)h->ssd->in_u8.p, SSD_IN, SSD_IN, h->stream);
+    if ((rc = ssd_forward(h, (const uint8_t*)h->ssd->in_u8.p, m, nullptr, nullptr, 0, nullptr))) return rc;
+    const int* cnt = (const int*)mailbox_d2h(h, h->ssd->count.p, (size_t)m * 4);
+    const float* rows = (const float*)mailbox_d2h(h, h->ssd->rows.p, (size_t)m * SSD_KEEP * 5 * 4);
+    if (!cnt || !rows) return fail(h, DFD_ERR_HIP, "detect_frames: mailbox allocation failed");
+    DFD_HIP_TRY(h, hipGetLastError());
+    DFD_HIP_TRY(h, stream_sync(h));
+    for (int j = 0; j < m; ++j)
+        if (cnt[j] < 0)
+            return fail(h, DFD_ERR_HIP, "detector: DetectionOutput of frame %d gave up waiting for its overlap rows (ssd_nms_kernel); no boxes returned", idx[j]);
+    for (int j = 0; j < m; ++j) {                                    // each frame's boxes in its own size
+        const int f = idx[j];
+        n_out[f] = ssd_postprocess(rows + (size_t)j * SSD_KEEP * 5, cnt[j], sub[j].h, sub[j].w, conf_thr,
+                                   xywh_out + (size_t)f * max_faces * 4, nullptr, max_faces, &n_total_out[f]);
+    }
+    return DFD_OK;
+}
+
 }  // namespace dfd
 
 extern "C" {

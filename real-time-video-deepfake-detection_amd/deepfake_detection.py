@@ -315,11 +315,17 @@ class DeepfakeDetector:
             small = frame.shape[0] < 30 or frame.shape[1] < 30
             frame_forensic, faces, logits = self._frame_on_gpu(frame, max_faces=1)
         n_detected = 0 if small else self._last_face_count(frame, faces)
+        return self._request_response(frame_forensic['fake_probability'], [] if small else faces, logits, n_detected)
+
+    def _request_response(self, fprob, faces, logits, n_detected):
+        """One frame of the /analyze flow once its GPU work is done (reference backend_server.py:166-233): the frame
+        counter moves, faces[0] (if any) or the forensic probability votes, and the response dict without timing is
+        returned.  `faces` is empty for frames under 30 px.  Shared by analyze_request, analyze_request_batch and the
+        session pool (sessions.SessionPool)."""
         self.frame_count += 1
         tr = self.temporal_tracker
-        fprob = frame_forensic['fake_probability']
         fake_prob = None
-        if len(faces) > 0 and not small:
+        if len(faces) > 0:
             x, y, w, h = faces[0]
             fake_prob = self._finish_face(logits[0], h, w)
         if fake_prob is not None:                                            # backend_server.py:166
@@ -336,6 +342,13 @@ class DeepfakeDetector:
                 'real_probability': float(1 - fprob), 'confidence_level': tr.get_confidence_level(),
                 'temporal_average': float(tr.get_temporal_average()), 'stability_score': float(tr.get_stability_score()),
                 'frame_count': self.frame_count}
+
+    def release(self):
+        """Frees this detector's forensic stream on the device (dfd_forensics_release): its 64 KB plane goes back to the
+        handle for the next new stream.  Used again afterwards, the detector's forensic stream starts fresh."""
+        h = self.frame_analyzer._existing_handle()
+        if h is not None:
+            h.forensics_release(self.frame_analyzer.stream_id)
 
     def analyze_request_batch(self, items):
         """`analyze_request` for several consecutive frames of this stream in ONE library call (POST /analyze_batch):
@@ -360,31 +373,11 @@ class DeepfakeDetector:
             first_number = self.frame_analyzer.frame_count - n + 1
         out = []
         small = shape[0] < 30 or shape[1] < 30
-        tr = self.temporal_tracker
         for i, (scores, fprob, faces, logits, n_detected) in enumerate(res):
             self.last_frame_forensic_result = {'scores': scores, 'fake_probability': fprob,
                                                'analysis_type': 'frame_forensic' if full[i] else 'frame_forensic_fast',
                                                'frame_number': first_number + i}
-            self.frame_count += 1
-            fake_prob = None
-            if len(faces) > 0 and not small:
-                x, y, w, h = faces[0]
-                fake_prob = self._finish_face(logits[0], h, w)
-            if fake_prob is not None:
-                tr.update(fake_prob)
-                out.append({'success': True, 'analysis_mode': 'face+frame', 'faces_detected': 0 if small else n_detected,
-                            'fake_probability': float(fake_prob), 'face_probability': float(fake_prob),
-                            'frame_forensic_probability': float(fprob), 'real_probability': float(1 - fake_prob),
-                            'confidence_level': tr.get_confidence_level(), 'temporal_average': float(tr.get_temporal_average()),
-                            'stability_score': float(tr.get_stability_score()), 'frame_count': self.frame_count,
-                            'face_bbox': {'x': int(x), 'y': int(y), 'width': int(w), 'height': int(h)}})
-                continue
-            tr.update(fprob)
-            out.append({'success': True, 'analysis_mode': 'frame_only', 'faces_detected': 0 if small else n_detected,
-                        'fake_probability': float(fprob), 'frame_forensic_probability': float(fprob),
-                        'real_probability': float(1 - fprob), 'confidence_level': tr.get_confidence_level(),
-                        'temporal_average': float(tr.get_temporal_average()), 'stability_score': float(tr.get_stability_score()),
-                        'frame_count': self.frame_count})
+            out.append(self._request_response(fprob, [] if small else faces, logits, 0 if small else n_detected))
         return out
 
     def _last_face_count(self, frame, faces):
