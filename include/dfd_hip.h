@@ -304,6 +304,23 @@ int dfd_forensics_release(dfd_handle* h, int stream_id);
 /* Mirrors the analyzer's attributes frame_count, len(temporal_diffs), prev_frame_gray is not None. */
 int dfd_forensics_state(dfd_handle* h, int stream_id, int* frame_count, int* n_diffs, int* has_prev);
 
+/* One named buffer of the forensic kernel chain, for parity tests (as dfd_ssd_tap / dfd_mtcnn_tap).  The chain runs on n
+ * (1..64) frames that are already 256x256 (no resize), in full or fast mode, touching no stream's temporal state, and
+ * `name` of frame `frame` (-1: of all n frames, frame-major) is copied to `out` as raw bytes; *bytes receives their count.
+ *   start = "rs": from bgr256, n x 256 x 256 x 3 BGR bytes (start_data unused).
+ *   start = "gray" | "grad" | "map": teacher forcing - start_data (n planes: uint8 gray, int16 (dx, dy) pairs, uint8
+ *           labels 0 candidate / 1 none / 2 strong) replaces that buffer and only the kernels downstream of it run
+ *           (bgr256 unused); a buffer that is not downstream, or that needs `rs`, is refused.
+ * Per frame: "rs" u8[256][256][3]; "gray", "map", "jy" u8[256][256]; "jcb", "jcr" u8[128][128]; "grad" i16[256][256][2];
+ * "fft_tmp" (row pass) and "spectrum" (both passes) complex64 [kx][ky] (transposed); "logmag" f32 [kx][ky], the
+ * log1pf(hypotf()) values the band sums add; "edges" u8[256][256] 0 / 1, the final hysteresis set; f64 "fft_part"
+ * [256][7] (low sum, count | mid sum, sum of squares, count | high sum, count), "lap_part" [256][2], "hsv_part" [256][4],
+ * "stats_noise" [64], "stats_ela" [64], "edge_count" [1], "stats" [9] (band means low, mid, high, mid std, Laplacian
+ * variance, edge count, S std, V std, hues; only the first 6 unless full and start = "rs"); "hue_bits" u32[6]; and
+ * "twiddle", complex64 [128], the FFT's table (not per frame). */
+int dfd_forensic_tap(dfd_handle* h, const uint8_t* bgr256, int n, int full, const char* start, const void* start_data,
+                     const char* name, int frame, void* out, size_t capacity, size_t* bytes);
+
 /* ---- one frame, end to end ---------------------------------------------------------------
  * The per-frame work of DeepfakeDetector.predict (reference deepfake_detection.py:597-626)
  * and of the /analyze handler (reference backend_server.py:147-164) with ONE upload of the

@@ -63,7 +63,7 @@ class ForensicsRef:
 
     # ------------------------------------------------------------------ signals
     def frequency(self, frame):                                         # :128-180
-        gray = I.bgr2gray_u8(frame).astype(np.float32)
+        gray = I.bgr2gray_u8(frame).astype(np.float64)                 # float64: fft2 of a float32 array is complex64
         mag = np.log1p(np.abs(np.fft.fftshift(np.fft.fft2(gray))))
         d = self._dist
         low, mid, high = d <= self._inner, (d > self._inner) & (d <= self._mid), (d > self._mid) & (d <= self._outer)

@@ -342,17 +342,20 @@ def sobel3_i32(gray: np.ndarray):
     return dx, dy
 
 
-def canny_u8(gray: np.ndarray, low: int = 50, high: int = 150) -> np.ndarray:
-    """cv2.Canny(gray, low, high): aperture 3, L1 magnitude, fixed-point non-maximum suppression
-    (tan 22.5 deg = 13573/2^15), 8-connected hysteresis.  Returns 0/255."""
-    dx, dy = sobel3_i32(gray)
+def canny_labels(dx: np.ndarray, dy: np.ndarray, low: int = 50, high: int = 150, branches: dict = None,
+                 ties_pass: bool = False) -> np.ndarray:
+    """cv2.Canny's non-maximum suppression on Sobel dx, dy: L1 magnitude, fixed-point direction classes
+    (tan 22.5 deg = 13573/2^15), zero magnitude outside the image.  Labels as OpenCV's map: 1 = not an edge,
+    0 = candidate (a local maximum above `low`), 2 = strong (above `high`).  `branches`, when given, receives how
+    many pixels above `low` fell into each direction class and onto each class boundary.  `ties_pass` is a deliberately
+    wrong variant for tests of tests (>= towards both neighbours in the horizontal and vertical classes)."""
+    dx, dy = np.asarray(dx).astype(np.int64), np.asarray(dy).astype(np.int64)
     mag = np.abs(dx) + np.abs(dy)
-    h, w = mag.shape
     mp = np.pad(mag, 1)                                        # zero border like OpenCV's mag buffer
     m = mp[1:-1, 1:-1]
     TG22 = 13573
-    x = np.abs(dx).astype(np.int64)
-    y = np.abs(dy).astype(np.int64) << 15
+    x = np.abs(dx)
+    y = np.abs(dy) << 15
     tg22x = x * TG22
     tg67x = tg22x + (x << 16)
     left, right = mp[1:-1, :-2], mp[1:-1, 2:]
@@ -361,14 +364,36 @@ def canny_u8(gray: np.ndarray, low: int = 50, high: int = 150) -> np.ndarray:
     # s = -1: compare prev[j+1], next[j-1] ; s = +1: prev[j-1], next[j+1]
     diag_prev = np.where(s_neg, mp[:-2, 2:], mp[:-2, :-2])
     diag_next = np.where(s_neg, mp[2:, :-2], mp[2:, 2:])
-    horiz = (y < tg22x) & (m > left) & (m >= right)
-    vert = (y > tg67x) & (m > up) & (m >= down)
-    diag = (y >= tg22x) & (y <= tg67x) & (m > diag_prev) & (m > diag_next)
-    cand = (m > low) & (horiz | vert | diag)
-    strong = cand & (m > high)
-    # hysteresis: grow `strong` through 8-connected candidates
-    edge = strong.copy()
-    stack = list(zip(*np.nonzero(strong)))
+    is_h, is_v = y < tg22x, y > tg67x
+    is_d = ~is_h & ~is_v
+    horiz = is_h & ((m >= left) if ties_pass else (m > left)) & (m >= right)
+    vert = is_v & ((m >= up) if ties_pass else (m > up)) & (m >= down)
+    diag = is_d & (m > diag_prev) & (m > diag_next)
+    above = m > low
+    cand = above & (horiz | vert | diag)
+    if branches is not None:
+        n = lambda mask: int(np.count_nonzero(above & mask))
+        one = 1 << 15                                           # one step of |dy|
+        edge = np.zeros(m.shape, bool)
+        edge[0, :] = edge[-1, :] = edge[:, 0] = edge[:, -1] = True
+        branches.update(horizontal=n(is_h), vertical=n(is_v), diagonal=n(is_d & ~s_neg), antidiagonal=n(is_d & s_neg),
+                        at_tg22=n(y == tg22x), at_tg67=n(y == tg67x),
+                        below_tg22=n(is_h & (y + one >= tg22x)), above_tg22=n(is_d & (y - one < tg22x)),
+                        below_tg67=n(is_d & (y + one > tg67x)), above_tg67=n(is_v & (y - one <= tg67x)),
+                        tie_left=n(is_h & (m == left)), tie_right=n(is_h & (m == right)),
+                        tie_up=n(is_v & (m == up)), tie_down=n(is_v & (m == down)),
+                        tie_diag_prev=n(is_d & (m == diag_prev)), tie_diag_next=n(is_d & (m == diag_next)),
+                        border=n(edge))
+    return np.where(cand, np.where(m > high, 2, 0), 1).astype(np.uint8)
+
+
+def hysteresis(labels: np.ndarray) -> np.ndarray:
+    """cv2.Canny's hysteresis on a label map (canny_labels): the strong pixels and every candidate 8-connected to
+    one, by a plain stack flood fill.  Returns a bool array."""
+    cand = labels != 1
+    h, w = labels.shape
+    edge = labels == 2
+    stack = list(zip(*np.nonzero(edge)))
     while stack:
         i, j = stack.pop()
         for di in (-1, 0, 1):
@@ -377,7 +402,14 @@ def canny_u8(gray: np.ndarray, low: int = 50, high: int = 150) -> np.ndarray:
                 if 0 <= a < h and 0 <= b < w and cand[a, b] and not edge[a, b]:
                     edge[a, b] = True
                     stack.append((a, b))
-    return (edge * 255).astype(np.uint8)
+    return edge
+
+
+def canny_u8(gray: np.ndarray, low: int = 50, high: int = 150) -> np.ndarray:
+    """cv2.Canny(gray, low, high): aperture 3, L1 magnitude, fixed-point non-maximum suppression
+    (tan 22.5 deg = 13573/2^15), 8-connected hysteresis.  Returns 0/255."""
+    dx, dy = sobel3_i32(gray)
+    return (hysteresis(canny_labels(dx, dy, low, high)) * 255).astype(np.uint8)
 
 
 # --------------------------------------------------------------------------- crop -> network input

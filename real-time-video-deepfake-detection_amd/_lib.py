@@ -117,6 +117,8 @@ SIGNATURES = {
     "dfd_analyze_jpegs_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float,
                                          C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dfd_forensic_tap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_void_p, C.c_char_p, C.c_int,
+                                   C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "dfd_forensic_signals_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
     "dfd_comm_unique_id": (C.c_int, [C.c_void_p]),
@@ -440,6 +442,37 @@ class Handle:
         fc, nd, hp = C.c_int(), C.c_int(), C.c_int()
         self._check(self._lib.dfd_forensics_state(self._p, int(stream_id), C.byref(fc), C.byref(nd), C.byref(hp)))
         return fc.value, nd.value, bool(hp.value)
+
+    # per-frame dtype and shape of every dfd_forensic_tap buffer ("stats": 6 entries unless full and start = "rs")
+    FORENSIC_TAPS = {"rs": (np.uint8, (256, 256, 3)), "gray": (np.uint8, (256, 256)), "fft_tmp": (np.complex64, (256, 256)),
+                     "spectrum": (np.complex64, (256, 256)), "logmag": (np.float32, (256, 256)),
+                     "fft_part": (np.float64, (256, 7)), "grad": (np.int16, (256, 256, 2)), "lap_part": (np.float64, (256, 2)),
+                     "map": (np.uint8, (256, 256)), "edges": (np.uint8, (256, 256)), "edge_count": (np.float64, (1,)),
+                     "jy": (np.uint8, (256, 256)), "jcb": (np.uint8, (128, 128)), "jcr": (np.uint8, (128, 128)),
+                     "stats_ela": (np.float64, (64,)), "stats_noise": (np.float64, (64,)), "hsv_part": (np.float64, (256, 4)),
+                     "hue_bits": (np.uint32, (6,)), "stats": (np.float64, (9,)), "twiddle": (np.complex64, (128,))}
+    FORENSIC_STARTS = {"rs": (np.uint8, (256, 256, 3)), "gray": (np.uint8, (256, 256)), "grad": (np.int16, (256, 256, 2)),
+                       "map": (np.uint8, (256, 256))}
+
+    def forensic_tap(self, data, name: str, full: bool = True, start: str = "rs", frame: int = -1) -> np.ndarray:
+        """Test entry: the forensic kernel chain on `data` = n frames of the `start` buffer ("rs": 256x256 BGR; "gray",
+        "grad", "map": that buffer injected, only the kernels downstream of it run) -> buffer `name` of all frames
+        (n, ...) or of one `frame` (...).  "twiddle" is the FFT table, (128,) complex64."""
+        dt, shp = self.FORENSIC_STARTS[start]
+        a = np.ascontiguousarray(np.asarray(data))
+        if a.dtype != dt or a.shape[1:] != shp:
+            raise ValueError(f"start '{start}' takes (n,) + {shp} {np.dtype(dt).name}, got {a.shape} {a.dtype}")
+        odt, oshp = self.FORENSIC_TAPS[name]
+        if name == "stats" and not (full and start == "rs"):
+            oshp = (6,)
+        nout = 1 if (frame >= 0 or name == "twiddle") else a.shape[0]
+        out = np.empty((nout,) + oshp, odt)
+        cnt = C.c_size_t()
+        self._check(self._lib.dfd_forensic_tap(self._p, _ptr(a) if start == "rs" else None, a.shape[0], int(bool(full)),
+                                               start.encode(), None if start == "rs" else _ptr(a), name.encode(), int(frame),
+                                               _ptr(out), out.nbytes, C.byref(cnt)))
+        assert cnt.value == out.nbytes, (name, cnt.value, out.nbytes)
+        return out[0] if (frame >= 0 or name == "twiddle") else out
 
     def frequency_features(self, image) -> np.ndarray:
         a = np.ascontiguousarray(np.asarray(image))

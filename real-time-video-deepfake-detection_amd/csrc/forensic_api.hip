@@ -1,6 +1,7 @@
 // C ABI of the forensic analyzer: device statistics -> the reference's threshold scoring
 // (reference frame_analysis.py:58-389), with the per-stream temporal state kept here.
 #include <cmath>
+#include <cstring>
 #include <deque>
 
 #include "dfd_common.h"
@@ -29,6 +30,7 @@ struct ForensicState {
     size_t host_res_cap = 0;
     DevBuf frame_desc, prev_tab, copy_tab;   // forensics_streams_run: FrameDesc [n], predecessor planes [n], write-backs
     std::vector<void*> free_planes;          // stored planes of released streams, reused by the next new stream
+    DevBuf tap_store;                        // dfd_forensic_tap: spectrum, logmag, edges; allocated on its first call
 };
 
 void forensic_destroy(dfd_handle* h) {
@@ -428,6 +430,81 @@ int dfd_forensic_signals_device(dfd_handle* h, const uint8_t* frames_dev, int n,
             mean_diff_out[f] = sum / 65536.0;
         }
     }
+    return DFD_OK;
+}
+
+int dfd_forensic_tap(dfd_handle* h, const uint8_t* bgr256, int n, int full, const char* start, const void* start_data,
+                     const char* name, int frame, void* out, size_t capacity, size_t* bytes) {
+    if (!h) return DFD_ERR_ARG;
+    if (!start || !name || !out || !bytes || n <= 0 || n > 64 || frame < -1 || frame >= n)
+        return fail(h, DFD_ERR_ARG, "forensic_tap: bad pointer, frame index or frame count (1..64)");
+    constexpr size_t PIX = 65536;
+    static const char* const starts[4] = {"rs", "gray", "grad", "map"};
+    int st = -1;
+    for (int i = 0; i < 4; ++i)
+        if (!std::strcmp(start, starts[i])) st = i;
+    if (st < 0) return fail(h, DFD_ERR_ARG, "forensic_tap: start '%s' is none of rs, gray, grad, map", start);
+    if (st == FROM_RS ? !bgr256 : !start_data) return fail(h, DFD_ERR_ARG, "forensic_tap: no data for start '%s'", start);
+    if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    int rc = state_init(h, n);
+    if (rc) return rc;
+    ForensicState& F = *h->forensic;
+    if ((rc = ensure(h, &F.tap_store, (size_t)n * PIX * (sizeof(float2) + sizeof(float) + 1)))) return rc;
+    ForensicTaps T;
+    T.spectrum = static_cast<float2*>(F.tap_store.p);
+    T.logmag = reinterpret_cast<float*>(T.spectrum + (size_t)n * PIX);
+    T.edges = reinterpret_cast<uint8_t*>(T.logmag + (size_t)n * PIX);
+    const ForensicBuffers& B = F.buf;
+    // which buffer, bytes per frame, the last start that still computes it, and whether only full mode does
+    struct Tap { const char* name; const void* p; size_t per; int last_start; bool full_only; };
+    const bool stats_full = full && st == FROM_RS;
+    const Tap taps[] = {
+        {"rs", B.rs, PIX * 3, FROM_RS, false}, {"gray", B.gray, PIX, FROM_GRAY, false},
+        {"fft_tmp", B.fft_tmp, PIX * sizeof(float2), FROM_GRAY, false}, {"spectrum", T.spectrum, PIX * sizeof(float2), FROM_GRAY, false},
+        {"logmag", T.logmag, PIX * sizeof(float), FROM_GRAY, false}, {"fft_part", B.fft_part, 256 * 7 * 8, FROM_GRAY, false},
+        {"grad", B.grad, PIX * sizeof(short2), FROM_GRAD, false}, {"lap_part", B.lap_part, 256 * 2 * 8, FROM_GRAY, false},
+        {"map", B.map, PIX, FROM_MAP, false}, {"edges", T.edges, PIX, FROM_MAP, false}, {"edge_count", B.edge_count, 8, FROM_MAP, false},
+        {"jy", B.jy, PIX, FROM_RS, true}, {"jcb", B.jcb, PIX / 4, FROM_RS, true}, {"jcr", B.jcr, PIX / 4, FROM_RS, true},
+        {"stats_ela", B.stats_ela, 64 * 8, FROM_RS, true}, {"stats_noise", B.stats_noise, 64 * 8, FROM_GRAY, true},
+        {"hsv_part", B.hsv_part, 256 * 4 * 8, FROM_RS, true}, {"hue_bits", B.hue_bits, 6 * 4, FROM_RS, true},
+        {"stats", B.stats, (size_t)(stats_full ? FORENSIC_STATS : ST_SAT_STD) * 8, FROM_GRAY, false},
+    };
+    const char* src = nullptr;
+    size_t per = 0, stride = 0;
+    if (!std::strcmp(name, "twiddle")) {                        // the table every FFT launch reads; not per frame
+        src = reinterpret_cast<const char*>(F.twiddle);
+        per = 128 * sizeof(float2);
+        frame = 0;
+    }
+    for (const Tap& t : taps)
+        if (!src && !std::strcmp(name, t.name)) {
+            if (st > t.last_start || (t.full_only && !full))
+                return fail(h, DFD_ERR_ARG, "forensic_tap: '%s' is not computed from start '%s' with full = %d", name, start, full);
+            src = static_cast<const char*>(t.p);
+            per = t.per;
+            stride = !std::strcmp(name, "stats") ? FORENSIC_STATS * 8 : t.per;
+        }
+    if (!src) return fail(h, DFD_ERR_ARG, "forensic_tap: no buffer named '%s'", name);
+    const size_t nout = frame < 0 ? (size_t)n : 1, total = nout * per;
+    *bytes = total;
+    if (total > capacity) return fail(h, DFD_ERR_ARG, "forensic_tap '%s' needs %zu bytes, capacity %zu", name, total, capacity);
+    if (st == FROM_RS) {
+        DFD_HIP_TRY(h, hipMemcpyAsync(B.rs, bgr256, (size_t)n * PIX * 3, hipMemcpyHostToDevice, h->stream));
+    } else {
+        void* dst = st == FROM_GRAY ? (void*)B.gray : st == FROM_GRAD ? (void*)B.grad : (void*)B.map;
+        DFD_HIP_TRY(h, hipMemcpyAsync(dst, start_data, (size_t)n * PIX * (st == FROM_GRAD ? sizeof(short2) : 1), hipMemcpyHostToDevice, h->stream));
+    }
+    launch_forensics(B, n, full != 0, h->color, F.twiddle, h->stream, 0, (ForensicStart)st, &T);
+    DFD_HIP_TRY(h, hipGetLastError());
+    const size_t first = frame < 0 ? 0 : (size_t)frame;
+    if (stride == per || nout == 1) {
+        DFD_HIP_TRY(h, hipMemcpyAsync(out, src + first * stride, total, hipMemcpyDeviceToHost, h->stream));
+    } else {
+        for (size_t f = 0; f < nout; ++f)
+            DFD_HIP_TRY(h, hipMemcpyAsync((char*)out + f * per, src + f * stride, per, hipMemcpyDeviceToHost, h->stream));
+    }
+    DFD_HIP_TRY(h, stream_sync(h));
     return DFD_OK;
 }
 

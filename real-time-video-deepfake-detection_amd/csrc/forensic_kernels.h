@@ -30,10 +30,18 @@ struct ForensicBuffers {
     double* stats_ela;   // [n][64] block means of the ELA difference
 };
 
+// test entry (dfd_forensic_tap) only: where the chain starts, and storage for what the kernels otherwise keep in LDS
+enum ForensicStart { FROM_RS = 0, FROM_GRAY, FROM_GRAD, FROM_MAP };
+struct ForensicTaps {
+    float2* spectrum;    // [n][256][256] second FFT pass, [k1][k2] like fft_tmp
+    float* logmag;       // [n][256][256] log1pf(hypotf()) of it: the values the band sums add
+    uint8_t* edges;      // [n][65536] final hysteresis set, 0 / 1
+};
+
 size_t forensic_bytes_per_frame();
 void forensic_carve(void* base, int n, ForensicBuffers* out);
 void launch_forensics(const ForensicBuffers& B, int n, bool full, const ColorTables& T, const float2* tw, hipStream_t s,
-                      int gray_only = 0);
+                      int gray_only = 0, ForensicStart start = FROM_RS, const ForensicTaps* taps = nullptr);
 void launch_absdiff(const uint8_t* gray, const uint8_t* prev, double* part256, hipStream_t s);
 void launch_absdiff_pairs(const uint8_t* gray, const int* prev_index, double* part /*[n][256]*/, int n, hipStream_t s);
 // frame f of gray [n][65536] against the plane prev_dev[f] (device pointer table; null = no predecessor, sums 0)

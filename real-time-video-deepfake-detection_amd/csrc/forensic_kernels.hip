@@ -103,8 +103,10 @@ __global__ __launch_bounds__(128) void fft256_kernel(const uint8_t* __restrict__
 
 // pass 2: FFT along the other axis, then log1p|X| accumulated into the three radial bands.
 // The band masks depend on k1^2+k2^2 only, so working on the transposed array changes nothing.
+// spec_out / logmag_out: test taps ([frame][k1][k2], the layout of `in`), null on every production launch.
 __global__ __launch_bounds__(128) void fft_band_kernel(const float2* __restrict__ in, double* __restrict__ part,
-                                                       const float2* __restrict__ tw) {
+                                                       const float2* __restrict__ tw, float2* __restrict__ spec_out,
+                                                       float* __restrict__ logmag_out) {
     __shared__ float2 x[256];
     __shared__ double red[2 * 7];
     const int tid = threadIdx.x, k1 = blockIdx.x;
@@ -118,6 +120,11 @@ __global__ __launch_bounds__(128) void fft_band_kernel(const float2* __restrict_
         const int s2 = k2 < 128 ? k2 : k2 - 256;
         const int d2 = s1 * s1 + s2 * s2;
         const float m = log1pf(hypotf(x[k2].x, x[k2].y));
+        if (spec_out) {                                       // (wave-uniform)
+            const size_t o = (size_t)blockIdx.y * FPIX + (size_t)k1 * FS + k2;
+            spec_out[o] = x[k2];
+            logmag_out[o] = m;
+        }
         if (d2 <= 32 * 32) { acc[0] += m; acc[1] += 1.0; }
         else if (d2 <= 64 * 64) { acc[2] += m; acc[3] += (double)m * m; acc[4] += 1.0; }
         else if (d2 <= 128 * 128) { acc[5] += m; acc[6] += 1.0; }
@@ -363,7 +370,12 @@ __device__ __forceinline__ unsigned long long fill_row(unsigned long long gen, u
     return g | h;
 }
 
-__global__ __launch_bounds__(1024) void canny_hyst_kernel(const uint8_t* __restrict__ map, double* __restrict__ count) {
+// edges_out: test tap, the final edge set as one byte (0 / 1) per pixel; null on every production launch, which runs the
+// TAP = false instantiation (with the store compiled in behind a run-time test of the pointer alone, the kernel measured
+// 36 -> 40 us per 64 frames with the branch never taken).
+template <bool TAP>
+__global__ __launch_bounds__(1024) void canny_hyst_kernel(const uint8_t* __restrict__ map, double* __restrict__ count,
+                                                          uint8_t* __restrict__ edges_out) {
     __shared__ unsigned long long S[FS * 4 + 8];            // [row][word], one guard word each side
     __shared__ double red[16];
     const int tid = threadIdx.x, row = tid >> 2, wd = tid & 3;
@@ -401,6 +413,19 @@ __global__ __launch_bounds__(1024) void canny_hyst_kernel(const uint8_t* __restr
         Sw[tid] = s;
         __syncthreads();
         if (!any) break;
+    }
+    if (TAP && edges_out) {                                 // (wave-uniform)
+        uint4* dst = reinterpret_cast<uint4*>(edges_out + (size_t)blockIdx.x * FPIX + row * FS + wd * 64);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            unsigned wv[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const unsigned nib = (unsigned)(s >> (k * 16 + q * 4)) & 0xFu;
+                wv[q] = (nib & 1u) | ((nib & 2u) << 7) | ((nib & 4u) << 14) | ((nib & 8u) << 21);
+            }
+            dst[k] = make_uint4(wv[0], wv[1], wv[2], wv[3]);
+        }
     }
     const double tot = block_sum<1024>((double)__popcll(s), red);
     if (tid == 0) count[blockIdx.x] = tot;
@@ -497,18 +522,26 @@ __global__ __launch_bounds__(64) void stats_finalize_kernel(ForensicBuffers B, i
 }
 
 // ------------------------------------------------------------------------------- launchers
-// n frames get every signal; `gray_only` further frames (behind them in the buffers) only their gray plane
+// n frames get every signal; `gray_only` further frames (behind them in the buffers) only their gray plane.
+// `start` / `taps` are the test entry's (dfd_forensic_tap): production callers pass neither.  From FROM_GRAY on, only the
+// kernels downstream of that buffer run: nothing that reads `rs` (JPEG, ELA, HSV), and no statistics from FROM_GRAD on.
 void launch_forensics(const ForensicBuffers& B, int n, bool full, const ColorTables& T, const float2* tw, hipStream_t s,
-                      int gray_only) {
-    hipLaunchKernelGGL(gray_kernel, dim3(256, n + gray_only), dim3(256), 0, s, B.rs, B.gray);
+                      int gray_only, ForensicStart start, const ForensicTaps* taps) {
+    if (start == FROM_RS) hipLaunchKernelGGL(gray_kernel, dim3(256, n + gray_only), dim3(256), 0, s, B.rs, B.gray);
     if (n <= 0) return;
-    hipLaunchKernelGGL(fft256_kernel, dim3(256, n), dim3(128), 0, s, B.gray, B.fft_tmp, tw);
-    hipLaunchKernelGGL(fft_band_kernel, dim3(256, n), dim3(128), 0, s, B.fft_tmp, B.fft_part, tw);
-    hipLaunchKernelGGL(sobel_lap_kernel, dim3(256, n), dim3(256), 0, s, B.gray, B.grad, B.lap_part);
-    hipLaunchKernelGGL(canny_nms_kernel, dim3(256, n), dim3(256), 0, s, B.grad, B.map, 50, 150);
-    hipLaunchKernelGGL(canny_hyst_kernel, dim3(n), dim3(1024), 0, s, B.map, B.edge_count);
+    if (start <= FROM_GRAY) {
+        hipLaunchKernelGGL(fft256_kernel, dim3(256, n), dim3(128), 0, s, B.gray, B.fft_tmp, tw);
+        hipLaunchKernelGGL(fft_band_kernel, dim3(256, n), dim3(128), 0, s, B.fft_tmp, B.fft_part, tw,
+                           taps ? taps->spectrum : nullptr, taps ? taps->logmag : nullptr);
+        hipLaunchKernelGGL(sobel_lap_kernel, dim3(256, n), dim3(256), 0, s, B.gray, B.grad, B.lap_part);
+    }
+    if (start <= FROM_GRAD) hipLaunchKernelGGL(canny_nms_kernel, dim3(256, n), dim3(256), 0, s, B.grad, B.map, 50, 150);
+    if (taps && taps->edges) hipLaunchKernelGGL(canny_hyst_kernel<true>, dim3(n), dim3(1024), 0, s, B.map, B.edge_count, taps->edges);
+    else hipLaunchKernelGGL(canny_hyst_kernel<false>, dim3(n), dim3(1024), 0, s, B.map, B.edge_count, (uint8_t*)nullptr);
+    if (start >= FROM_GRAD) return;
+    if (full) hipLaunchKernelGGL(noise_block_kernel, dim3(64, n), dim3(256), 0, s, B.gray, B.stats_noise);
+    if (start != FROM_RS) full = false;
     if (full) {
-        hipLaunchKernelGGL(noise_block_kernel, dim3(64, n), dim3(256), 0, s, B.gray, B.stats_noise);
         hipLaunchKernelGGL(jpeg_block_kernel, dim3(24, n), dim3(64), 0, s, B.rs, B.jy, B.jcb, B.jcr);
         hipLaunchKernelGGL(ela_block_kernel, dim3(64, n), dim3(256), 0, s, B.rs, B.jy, B.jcb, B.jcr, B.stats_ela);
         hipMemsetAsync(B.hue_bits, 0, (size_t)n * 6 * sizeof(unsigned), s);
