@@ -279,6 +279,53 @@ int dfd_mtcnn_align(dfd_handle* h, const uint8_t* bgr, int height, int width, in
 int dfd_mtcnn_tap(dfd_handle* h, const uint8_t* bgr, int height, int width, int stride,
                   const char* name, float* out, size_t capacity, size_t* count, int* dims);
 
+/* ---- MTCNN with every constructor argument of the package: all faces, landmarks, any crop size ----------
+ * facenet_pytorch.MTCNN(image_size, margin, min_face_size, thresholds, factor, post_process, select_largest,
+ * selection_method, keep_all) on a list of images in ONE device pass.  dfd_mtcnn_params_default fills the package's
+ * defaults (160, 0, 20, .6/.7/.7, .709, post_process, select_largest).
+ *   selection : order of the returned rows.  NONE: as stage 3 yields them (descending probability - MTCNN.detect with
+ *               select_largest=False); PROBABILITY; LARGEST: box area; CENTER_WEIGHTED_SIZE: area - 2 x squared offset of
+ *               the box centre from the image centre; LARGEST_OVER_THRESHOLD: area among the rows above 0.9 probability.
+ *               Descending key; of equal keys the LATER stage-3 row comes first (np.argsort(..)[::-1], stable sort).
+ *   keep_all  : 0: only row 0 of that order is returned (n_faces_out <= 1); 1: every row.
+ *   factor    : double, as the package multiplies Python floats. */
+enum {
+    DFD_MT_SELECT_NONE = 0,
+    DFD_MT_SELECT_PROBABILITY = 1,
+    DFD_MT_SELECT_LARGEST = 2,
+    DFD_MT_SELECT_CENTER_WEIGHTED_SIZE = 3,
+    DFD_MT_SELECT_LARGEST_OVER_THRESHOLD = 4
+};
+typedef struct dfd_mtcnn_params {
+    int image_size;        /* edge of the returned crops                                   */
+    int margin;            /* extract_face margin, in pixels of the returned crop          */
+    int min_face_size;     /* >= 12                                                        */
+    float thresholds[3];   /* P-Net (>=), R-Net, O-Net (>) face probability                */
+    double factor;         /* pyramid scale step, in (0, 1)                                */
+    int selection;         /* DFD_MT_SELECT_*                                              */
+    int keep_all;
+    int post_process;      /* crops as (x - 127.5) / 128 instead of 0..255                 */
+} dfd_mtcnn_params;
+void dfd_mtcnn_params_default(dfd_mtcnn_params* params);
+/* MTCNN.detect(landmarks=True) for n_images packed BGR images (bgr[i], heights[i] x widths[i], row stride strides[i] bytes).
+ *   boxes_out     : [n_images][max_faces][5] (x1, y1, x2, y2, probability)
+ *   landmarks_out : NULL (the landmark head is then not run) or [n_images][max_faces][5][2] (x, y) in image coordinates
+ *   n_faces_out   : [n_images] rows of the order (may exceed max_faces: call again with more room); only
+ *                   min(n_faces, max_faces) rows of an image are written, the rest of the arrays is left alone
+ * DFD_ERR_ARG for parameters that make no sense (image_size <= margin, factor outside (0,1), min_face_size < 12, thresholds
+ * outside [0,1], n_images x max_faces > 65535), DFD_ERR_CAPACITY beyond 64 pyramid levels per image, DFD_ERR_STATE when the
+ * blob holds no cascade.  Results do not depend on DFD_MT_DEVICE_BOXES. */
+int dfd_mtcnn_detect(dfd_handle* h, int n_images, const uint8_t* const* bgr, const int* heights, const int* widths,
+                     const int* strides, const dfd_mtcnn_params* params, int max_faces, float* boxes_out,
+                     float* landmarks_out, int* n_faces_out);
+/* MTCNN.forward: the same, plus extract_face of every returned row (margin scaled to the box, corners clipped to the image,
+ * PIL crop + 8-bit BILINEAR resize to image_size^2):
+ *   faces_out : [n_images][max_faces][3][image_size][image_size] floats, RGB planes 0..255 or standardised; a row whose
+ *               clipped box is empty (the package raises there) gets a zero face. */
+int dfd_mtcnn_extract(dfd_handle* h, int n_images, const uint8_t* const* bgr, const int* heights, const int* widths,
+                      const int* strides, const dfd_mtcnn_params* params, int max_faces, float* boxes_out,
+                      float* landmarks_out, int* n_faces_out, float* faces_out);
+
 /* ---- frame forensics ------------------------------------------------------------------
  * FrameForensicAnalyzer.analyze (full != 0) / analyze_fast (full == 0), reference
  * frame_analysis.py:58-126: cv2.resize to 256x256, then the six signals (:128-389), weighted

@@ -82,6 +82,11 @@ SIGNATURES = {
                                   C.POINTER(C.c_int)]),
     "dfd_mtcnn_tap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_void_p,
                                 C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "dfd_mtcnn_params_default": (None, [C.c_void_p]),
+    "dfd_mtcnn_detect": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dfd_mtcnn_extract": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dfd_analyze_frame": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "dfd_jpeg_coefficients": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_size_t,
@@ -131,6 +136,30 @@ SIGNATURES = {
     "dfd_b0_profile_end": (C.c_int, [C.c_void_p, c_float_p, C.POINTER(C.c_char_p), C.c_int,
                                       C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
+
+
+class MtcnnParams(C.Structure):
+    """`dfd_mtcnn_params` (include/dfd_hip.h): the constructor arguments of facenet_pytorch.MTCNN."""
+    _fields_ = [("image_size", C.c_int), ("margin", C.c_int), ("min_face_size", C.c_int), ("thresholds", C.c_float * 3),
+                ("factor", C.c_double), ("selection", C.c_int), ("keep_all", C.c_int), ("post_process", C.c_int)]
+
+
+MT_SELECT = {None: 0, "none": 0, "probability": 1, "largest": 2, "center_weighted_size": 3, "largest_over_threshold": 4}
+
+
+def mtcnn_params(image_size=160, margin=0, min_face_size=20, thresholds=(0.6, 0.7, 0.7), factor=0.709, selection="largest",
+                 keep_all=False, post_process=True) -> MtcnnParams:
+    """The package's defaults from the library (dfd_mtcnn_params_default), then the given values."""
+    p = MtcnnParams()
+    load().dfd_mtcnn_params_default(C.byref(p))
+    if selection not in MT_SELECT:
+        raise ValueError(f"unknown selection {selection!r}")
+    p.image_size, p.margin, p.min_face_size = int(image_size), int(margin), int(min_face_size)
+    p.thresholds = (C.c_float * 3)(*[float(t) for t in thresholds])
+    p.factor = float(factor)
+    p.selection, p.keep_all, p.post_process = MT_SELECT[selection], int(bool(keep_all)), int(bool(post_process))
+    return p
+
 
 _lib: Optional[C.CDLL] = None
 _lock = threading.Lock()
@@ -866,6 +895,47 @@ class Handle:
         if dims[1] == 5 and dims[2] == 1:
             shape = (int(dims[0]), 5)
         return out[: cnt.value].reshape(shape) if cnt.value else out[:0].reshape((0,) + shape[1:])
+
+    def _mtcnn_call(self, images, params: MtcnnParams, max_faces: int, landmarks: bool, faces: bool):
+        imgs = [self._as_bgr(a) for a in images]
+        n = len(imgs)
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in imgs])
+        hs = np.array([a.shape[0] for a in imgs], np.int32)
+        ws = np.array([a.shape[1] for a in imgs], np.int32)
+        st = np.array([a.strides[0] for a in imgs], np.int32)
+        size = int(params.image_size)
+        while True:
+            boxes = np.zeros((n, max_faces, 5), np.float32)
+            lm = np.zeros((n, max_faces, 5, 2), np.float32) if landmarks else None
+            nf = np.zeros(n, np.int32)
+            lmp = _ptr(lm) if landmarks else None
+            if faces:
+                out = np.empty((n, max_faces, 3, size, size), np.float32)
+                rc = self._lib.dfd_mtcnn_extract(self._p, n, ptrs, _ptr(hs), _ptr(ws), _ptr(st), C.byref(params), max_faces,
+                                                 _ptr(boxes), lmp, _ptr(nf), _ptr(out))
+            else:
+                out = None
+                rc = self._lib.dfd_mtcnn_detect(self._p, n, ptrs, _ptr(hs), _ptr(ws), _ptr(st), C.byref(params), max_faces,
+                                                _ptr(boxes), lmp, _ptr(nf))
+            self._check(rc)
+            most = int(nf.max()) if n else 0
+            if most <= max_faces:
+                break
+            max_faces = most                      # an image holds more faces than there was room for: once more, with room
+        res = []
+        for i in range(n):
+            k = int(nf[i])
+            res.append((boxes[i, :k].copy(), lm[i, :k].copy() if landmarks else None, out[i, :k].copy() if faces else None))
+        return res
+
+    def mtcnn_detect(self, images, params: Optional[MtcnnParams] = None, landmarks: bool = True, max_faces: int = 16):
+        """MTCNN.detect on a list of (H, W, 3) uint8 BGR images in one device pass (dfd_mtcnn_detect): per image
+        (rows (k, 5) = x1, y1, x2, y2, probability, landmarks (k, 5, 2) or None, None), k = 0 when no face passes."""
+        return self._mtcnn_call(images, params or mtcnn_params(), max_faces, landmarks, False)
+
+    def mtcnn_extract(self, images, params: Optional[MtcnnParams] = None, landmarks: bool = False, max_faces: int = 16):
+        """MTCNN.forward on a list of images (dfd_mtcnn_extract): as mtcnn_detect, plus the crops (k, 3, S, S) float32."""
+        return self._mtcnn_call(images, params or mtcnn_params(), max_faces, landmarks, True)
 
     def ssd_tap(self, frame, name: str, capacity: int) -> np.ndarray:
         a = self._as_bgr(frame)

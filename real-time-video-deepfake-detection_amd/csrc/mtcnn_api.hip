@@ -40,6 +40,9 @@ struct MtcnnState {
     // box bookkeeping on the device (mtcnn_boxes.hip): crop / level tables, counts + prefix arrays + meta words, segmented and
     // compact row / window arenas, per-crop result rows, rows of crop 0 for the parity taps
     DevBuf cnt, rows_a, wins_a, rows_b, wins_b, res, taprows;
+    // every face of an image (dfd_mtcnn_detect / dfd_mtcnn_extract): landmark fractions of the O-Net windows, the rows stage 3
+    // keeps, [first n + 1][counts n] of the host path, ordered boxes / landmarks / face counts, the float face slots
+    DevBuf pts, det_rows, det_idx, det_box, det_lm, det_nf, det_faces;
 };
 
 void mtcnn_destroy(dfd_handle* h) {
@@ -128,7 +131,7 @@ void parallel_for(int count, size_t work, F fn) {
     for (auto& th : pool) th.join();
 }
 
-struct Box { float x1, y1, x2, y2, score, r[4]; };
+struct Box { float x1, y1, x2, y2, score, r[4]; int win; };      // win: the box's O-Net window (stage 3 of a detect call)
 
 // Greedy NMS over boxes already in processing order (structure of arrays: the inner loop is branch-free and
 // vectorises).  PLUS1 = false: torchvision.ops.nms - suppress IoU > thr, areas without the +1;
@@ -296,6 +299,17 @@ struct Cascade {
     std::vector<float>* tap;
     int* tap_dims;
 
+    // the package's constructor arguments that shape the cascade (defaults: what the reference constructs)
+    float thr[3] = {0.6f, 0.7f, 0.7f};
+    double min_face = 20.0, factor = 0.709;
+    // dfd_mtcnn_detect / dfd_mtcnn_extract: every row stage 3 keeps instead of the selected face; out_size / slots size the
+    // resize tables and intermediates of the faces a crop may return
+    bool det = false, want_points = false;
+    int out_size = 160, slots = 1;
+    std::vector<MtDetRow> det_in;          // host path: input box + landmark fractions of every O-Net window
+    const int* det_first = nullptr;        // device: first row / row count of each image in S->det_rows
+    const int* det_counts = nullptr;
+
     bool want(const std::string& nm) const { return tap_name && nm == tap_name; }
 
     std::chrono::steady_clock::time_point t_mark = std::chrono::steady_clock::now();
@@ -347,9 +361,9 @@ struct Cascade {
     const MtCropGeo* dcg = nullptr;
     const MtLevelGeo* dlg = nullptr;
 
-    // Pillow's kernel size for a 160-wide axis read from in_size pixels (pil_coeffs)
-    static int pil_ksize(int in_size) {
-        const double scale = (double)in_size / 160;
+    // Pillow's kernel size for an out_size-wide axis read from in_size pixels (pil_coeffs)
+    static int pil_ksize(int in_size, int out_size = 160) {
+        const double scale = (double)in_size / out_size;
         return (int)std::ceil(scale < 1.0 ? 1.0 : scale) * 2 + 1;
     }
 
@@ -366,7 +380,7 @@ struct Cascade {
         cells = 0;
         for (int c = 0; c < n; ++c) {
             const int hh = imgs[c].h, ww = imgs[c].w;
-            const double m = 12.0 / 20.0;                         // scale pyramid in double, as the package's Python floats
+            const double m = 12.0 / min_face;                     // scale pyramid in double, as the package's Python floats
             double minl = std::min(hh, ww) * m, scale_i = m;
             while (minl >= 12) {
                 const int sh = (int)(hh * scale_i + 1), sw = (int)(ww * scale_i + 1);
@@ -382,8 +396,8 @@ struct Cascade {
                 pre_c2.push_back(pre_c2.back() + (long long)c2h * c2w * 16);
                 pre_c3.push_back(pre_c3.back() + (long long)c3h * c3w * 32);
                 cells += (long long)c3h * c3w;
-                scale_i *= 0.709;
-                minl *= 0.709;
+                scale_i *= factor;
+                minl *= factor;
             }
         }
         // crop / level tables of the device box path (mtcnn_boxes.hip); geo_ok = false: a field would overflow - host path
@@ -408,11 +422,12 @@ struct Cascade {
                 }
                 if (g.nlevels > 31) geo_ok = false;
                 seg += std::min<long long>(crop_cells, kMtCap2);
-                tmp_bytes += ((long long)imgs[c].h * 160 * 3 + 255) & ~255ll;
-                tab += 160ll * pil_ksize(imgs[c].w) + 320 + 160ll * pil_ksize(imgs[c].h) + 320;
+                tmp_bytes += slots * (((long long)imgs[c].h * out_size * 3 + 255) & ~255ll);
+                tab += slots * ((long long)out_size * (pil_ksize(imgs[c].w, out_size) + pil_ksize(imgs[c].h, out_size)) + 4ll * out_size);
                 if (tab > (1ll << 30) || seg > (1ll << 30)) geo_ok = false;
             }
         }
+        if (det && tab > (1ll << 30)) return fail(h, DFD_ERR_CAPACITY, "mtcnn: max_faces x image_size too large for these images");
         mark("s1 host: pyramid tables");
         const int nl = (int)levels.size();
         // counters of the step in ONE zeroed block: [candidate count (4 words)][counts n][first_a n + 1][first_b n + 1][meta 4]
@@ -466,7 +481,7 @@ struct Cascade {
             unsigned* d_count = (unsigned*)S->cnt.p;                 // zeroed above
             MtCand* d_cand = (MtCand*)((char*)S->cand.p + 16);
             const MtPnetHeads heads{S->p41.w, S->p41.b, S->p42.w, S->p42.b, (float*)S->prob.p, (float*)S->reg.p,
-                                    d_cand, d_count, (unsigned)cells, 0.6f};                  // thresholds[0], >=, float32
+                                    d_cand, d_count, (unsigned)cells, thr[0]};                // thresholds[0], >=, float32
             // conv1 + PReLU + pool in one launch (the 10-channel conv map is never stored), conv2, then conv3 with both
             // 1x1 heads and the softmax evaluated from its registers (prob [cell], reg [cell][4], candidates; the
             // 32-channel map is never stored either)
@@ -601,6 +616,7 @@ struct Cascade {
         if ((rc = ensure(h, &S->a1, big))) return rc;
         if ((rc = ensure(h, &S->prob, (size_t)total * 4))) return rc;
         if ((rc = ensure(h, &S->reg, (size_t)total * 4 * 4))) return rc;
+        if (onet && want_points && (rc = ensure(h, &S->pts, (size_t)total * 10 * 4))) return rc;
         for (int start = 0; start < total; start += kChunk) {
             const int m = std::min(kChunk, total - start);
             const MtSrcWindow* wd = wd_all + start;                  // (the ensure calls above never move the window list)
@@ -625,7 +641,8 @@ struct Cascade {
                 if ((rc = gemm_conv_prelu(h, S->o4g, a1, a0, m, 4, 4))) return rc;                  // 3 -> [m][3][3][128]
                 if ((rc = gemm_dense_prelu(h, S->o5, a0, a1, m))) return rc;                        // 1152 -> 256
                 launch_mt_heads(a1, S->o61.w, S->o61.b, S->o62.w, S->o62.b, pr, rg, m, 256, s);
-                // dense6_3 (landmarks) does not influence the selected crop: not evaluated
+                // dense6_3 (landmarks) does not influence the boxes: evaluated only for callers that return landmarks
+                if (want_points) launch_mt_points(a1, S->o63.w, S->o63.b, (float*)S->pts.p + (size_t)start * 10, m, 256, s);
             }
             DFD_HIP_TRY(h, hipGetLastError());
         }
@@ -642,11 +659,14 @@ struct Cascade {
         if ((rc = refine_gpu(onet, (const MtSrcWindow*)S->win.p, total))) return rc;
         const float* pp = (const float*)mailbox_d2h(h, S->prob.p, (size_t)total * 4);
         const float* rr = (const float*)mailbox_d2h(h, S->reg.p, (size_t)total * 16);
-        if (!pp || !rr) return fail(h, DFD_ERR_HIP, "mtcnn: mailbox allocation failed");
+        const float* qq = onet && want_points ? (const float*)mailbox_d2h(h, S->pts.p, (size_t)total * 40) : nullptr;
+        if (!pp || !rr || (onet && want_points && !qq)) return fail(h, DFD_ERR_HIP, "mtcnn: mailbox allocation failed");
         DFD_HIP_TRY(h, hipGetLastError());
         DFD_HIP_TRY(h, stream_sync(h));
         prob->assign(pp, pp + total);
         reg->assign(rr, rr + (size_t)total * 4);
+        if (qq)
+            for (int k = 0; k < total; ++k) memcpy(det_in[k].p, qq + (size_t)k * 10, 40);
         return DFD_OK;
     }
 
@@ -675,6 +695,15 @@ struct Cascade {
                     live[c].push_back(b);
                 }
             std::vector<float> prob, reg;
+            if (det && stage == 3) {                             // the landmarks' frame: the O-Net input box, before bbreg
+                det_in.assign(wins.size(), MtDetRow{});
+                size_t k = 0;
+                for (int c = 0; c < n; ++c)
+                    for (const Box& b : live[c]) {
+                        float* in = det_in[k++].in;
+                        in[0] = b.x1; in[1] = b.y1; in[2] = b.x2; in[3] = b.y2;
+                    }
+            }
             mark("host: windows");
             if (!wins.empty() && (rc = refine(stage == 3, wins, &prob, &reg))) return rc;
             mark("gpu: refine + download");
@@ -698,9 +727,10 @@ struct Cascade {
                 size_t k = first[c];
                 std::vector<Box> pass;
                 for (const Box& lb : live[c]) {
-                    if (prob[k] > 0.7f) {                        // thresholds[1] = thresholds[2] = 0.7, strict
+                    if (prob[k] > thr[stage - 1]) {              // thresholds[1], thresholds[2]: strict
                         Box b = lb;
                         b.score = prob[k];
+                        b.win = (int)k;
                         for (int r = 0; r < 4; ++r) b.r[r] = reg[k * 4 + r];
                         pass.push_back(b);
                     }
@@ -791,7 +821,7 @@ struct Cascade {
         int mh[4] = {0, 0, 0, 0};
         int m2 = 0, m3 = 0;
         if (!levels.empty()) {
-            launch_mt_stage1_boxes(dcg, dlg, n, (const float*)S->prob.p, (const float*)S->reg.p, 0.6f,
+            launch_mt_stage1_boxes(dcg, dlg, n, (const float*)S->prob.p, (const float*)S->reg.p, thr[0],
                                    rows_a, wins_a, counts, meta, taprows, s);
             launch_mt_compact(counts, n, dcg, nullptr, rows_a, wins_a, rows_b, wins_b, first_a, meta, s);
             if ((rc = read_meta(mh))) return rc;
@@ -811,7 +841,7 @@ struct Cascade {
         if (m2 > 0) {
             if ((rc = refine_gpu(false, wins_b, m2))) return rc;
             if ((rc = tap_net("rnet.prob", "rnet.reg", mh[3]))) return rc;
-            launch_mt_refine_boxes(2, dcg, first_a, n, rows_b, (const float*)S->prob.p, (const float*)S->reg.p, 0.7f, 0.7f, rows_a, wins_a,
+            launch_mt_refine_boxes(2, dcg, first_a, n, rows_b, (const float*)S->prob.p, (const float*)S->reg.p, thr[1], 0.7f, rows_a, wins_a,
                                    counts, nullptr, nullptr, nullptr, taprows, meta, s);
             launch_mt_compact(counts, n, dcg, first_a, rows_a, wins_a, rows_b, wins_b, first_b, meta, s);
             if ((rc = read_meta(mh))) return rc;
@@ -827,8 +857,22 @@ struct Cascade {
             if ((rc = refine_gpu(true, wins_b, m3))) return rc;
             if ((rc = tap_net("onet.prob", "onet.reg", mh[3]))) return rc;
         }
+        if (det) {
+            // every row stage 3 keeps, at the crop's run of O-Net windows; with no window left the counts are all zero
+            // (stage 2 wrote them, or the step's memset)
+            if ((rc = ensure(h, &S->det_rows, (size_t)std::max(m3, 1) * sizeof(MtDetRow)))) return rc;
+            if (m3 > 0)
+                launch_mt_stage3_rows(dcg, first_b, n, rows_b, (const float*)S->prob.p, (const float*)S->reg.p,
+                                      want_points ? (const float*)S->pts.p : nullptr, thr[2], 0.7f, (MtDetRow*)S->det_rows.p, counts,
+                                      taprows, meta, s);
+            DFD_HIP_TRY(h, hipGetLastError());
+            det_first = first_b;
+            det_counts = counts;
+            *done = true;
+            return DFD_OK;
+        }
         // (with no window left first_b is all zero: every crop gets a zero-filled face and found = 0)
-        launch_mt_refine_boxes(3, dcg, first_b, n, rows_b, (const float*)S->prob.p, (const float*)S->reg.p, 0.7f, 0.7f, nullptr, nullptr,
+        launch_mt_refine_boxes(3, dcg, first_b, n, rows_b, (const float*)S->prob.p, (const float*)S->reg.p, thr[2], 0.7f, nullptr, nullptr,
                                nullptr, (MtFaceJob*)S->bnd.p, (float*)S->res.p, (int*)S->coef.p, taprows, meta, s);
         launch_mt_extract_faces((const MtFaceJob*)S->bnd.p, n, (const int*)S->coef.p, faces_out, (uint8_t*)S->tmp.p, s);
         DFD_HIP_TRY(h, hipGetLastError());
@@ -1002,6 +1046,84 @@ int mtcnn_align_device(dfd_handle* h, const uint8_t* img_dev, int hh, int ww, si
     return DFD_OK;
 }
 
+// MTCNN.detect (+ MTCNN.extract with faces_out) on `n` BGR images already in HBM, one device pass for all of them: the
+// cascade with the caller's pyramid and thresholds, every row stage 3 keeps (device box path, or the host path beyond its
+// capacity - the same rows either way), then ONE ordering / landmark / extract_face-geometry kernel and the resize
+// launches whatever path produced the rows.  Host outputs as dfd_mtcnn_detect documents them.
+int mtcnn_detect_batch(dfd_handle* h, const MtImage* imgs, int n, const dfd_mtcnn_params& P, int max_faces, float* boxes_out,
+                       float* landmarks_out, int* n_faces_out, float* faces_out) {
+    MtcnnState* S = h->mtcnn;
+    hipStream_t s = h->stream;
+    const int size = P.image_size;
+    Cascade c{h, S, imgs, n, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 3; ++k) c.thr[k] = P.thresholds[k];
+    c.min_face = (double)P.min_face_size;
+    c.factor = P.factor;
+    c.det = true;
+    c.want_points = landmarks_out != nullptr;
+    c.out_size = size;
+    c.slots = max_faces;
+    int rc;
+    bool done = false;
+    const char* dv = getenv("DFD_MT_DEVICE_BOXES");
+    if (!(dv && atoi(dv) == 0) && (rc = c.run_device(nullptr, nullptr, nullptr, &done))) return rc;
+    if (!done) {
+        std::vector<std::vector<Box>> boxes;
+        if ((rc = c.run(&boxes))) return rc;
+        std::vector<int> idx(2 * (size_t)n + 1, 0);                  // [first n + 1][counts n]
+        std::vector<MtDetRow> rows;
+        for (int i = 0; i < n; ++i) {
+            if (boxes[i].size() > (size_t)kMtCap2) return fail(h, DFD_ERR_CAPACITY, "mtcnn: more than %d faces in one image", kMtCap2);
+            idx[i] = (int)rows.size();
+            idx[n + 1 + i] = (int)boxes[i].size();
+            for (const Box& b : boxes[i]) {
+                MtDetRow d = c.det_in[b.win];                        // input box + landmark fractions of the row's window
+                d.x1 = b.x1; d.y1 = b.y1; d.x2 = b.x2; d.y2 = b.y2; d.score = b.score;
+                rows.push_back(d);
+            }
+        }
+        idx[n] = (int)rows.size();
+        if ((rc = c.upload(&S->det_rows, rows))) return rc;
+        if ((rc = c.upload(&S->det_idx, idx))) return rc;
+        c.det_first = (const int*)S->det_idx.p;
+        c.det_counts = c.det_first + n + 1;
+    }
+    const size_t slots = (size_t)n * max_faces, face = (size_t)3 * size * size;
+    if ((rc = ensure(h, &S->det_box, slots * 5 * 4))) return rc;
+    if (landmarks_out && (rc = ensure(h, &S->det_lm, slots * 10 * 4))) return rc;
+    if ((rc = ensure(h, &S->det_nf, (size_t)n * 4))) return rc;
+    MtFaceJob* jobs = nullptr;
+    if (faces_out) {
+        if ((rc = ensure(h, &S->bnd, slots * sizeof(MtFaceJob)))) return rc;
+        if ((rc = ensure(h, &S->coef, (size_t)std::max<long long>(c.tab, 4) * 4))) return rc;
+        if ((rc = ensure(h, &S->tmp, (size_t)std::max<long long>(c.tmp_bytes, 16)))) return rc;
+        if ((rc = ensure(h, &S->det_faces, slots * face * 4))) return rc;
+        jobs = (MtFaceJob*)S->bnd.p;
+        DFD_HIP_TRY(h, hipMemsetAsync(jobs, 0, slots * sizeof(MtFaceJob), s));                 // found = 0: slot unused
+    }
+    const MtSelect sel{P.selection, P.keep_all ? 1 : 0, size, P.margin, max_faces};
+    launch_mt_select(c.dcg, c.det_first, c.det_counts, n, (const MtDetRow*)S->det_rows.p, sel, (float*)S->det_box.p,
+                     landmarks_out ? (float*)S->det_lm.p : nullptr, (int*)S->det_nf.p, jobs, (int*)S->coef.p, s);
+    if (faces_out)
+        launch_mt_extract_faces_multi(jobs, (int)slots, size, (const int*)S->coef.p, (float*)S->det_faces.p, (uint8_t*)S->tmp.p,
+                                      P.post_process != 0, s);
+    DFD_HIP_TRY(h, hipGetLastError());
+    // the caller's arrays are written whole only where rows exist: first the counts, then per image its rows
+    DFD_HIP_TRY(h, hipMemcpyAsync(n_faces_out, S->det_nf.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    DFD_HIP_TRY(h, stream_sync(h));
+    for (int i = 0; i < n; ++i) {
+        const size_t k = (size_t)std::min(n_faces_out[i], max_faces), at = (size_t)i * max_faces;
+        if (!k) continue;
+        DFD_HIP_TRY(h, hipMemcpyAsync(boxes_out + at * 5, (const float*)S->det_box.p + at * 5, k * 5 * 4, hipMemcpyDeviceToHost, s));
+        if (landmarks_out)
+            DFD_HIP_TRY(h, hipMemcpyAsync(landmarks_out + at * 10, (const float*)S->det_lm.p + at * 10, k * 10 * 4, hipMemcpyDeviceToHost, s));
+        if (faces_out)
+            DFD_HIP_TRY(h, hipMemcpyAsync(faces_out + at * face, (const float*)S->det_faces.p + at * face, k * face * 4, hipMemcpyDeviceToHost, s));
+    }
+    DFD_HIP_TRY(h, stream_sync(h));
+    return DFD_OK;
+}
+
 const uint8_t* mtcnn_face_dev(dfd_handle* h) { return h->mtcnn ? (const uint8_t*)h->mtcnn->face.p : nullptr; }
 
 }  // namespace dfd
@@ -1036,6 +1158,72 @@ int dfd_mtcnn_align(dfd_handle* h, const uint8_t* bgr, int hh, int ww, int strid
         DFD_HIP_TRY(h, stream_sync(h));
     }
     return DFD_OK;
+}
+
+void dfd_mtcnn_params_default(dfd_mtcnn_params* p) {
+    if (!p) return;
+    *p = dfd_mtcnn_params{};
+    p->image_size = 160;
+    p->margin = 0;
+    p->min_face_size = 20;
+    p->thresholds[0] = 0.6f; p->thresholds[1] = 0.7f; p->thresholds[2] = 0.7f;
+    p->factor = 0.709;
+    p->selection = DFD_MT_SELECT_LARGEST;          // the package's select_largest=True
+    p->keep_all = 0;
+    p->post_process = 1;
+}
+
+// arguments of dfd_mtcnn_detect / dfd_mtcnn_extract, the images into one device buffer, the batch call
+static int mt_detect_call(dfd_handle* h, int n, const uint8_t* const* bgr, const int* hs, const int* ws, const int* strides,
+                          const dfd_mtcnn_params* P, int max_faces, float* boxes_out, float* landmarks_out, int* n_faces_out,
+                          float* faces_out, bool extract) {
+    if (!h) return DFD_ERR_ARG;
+    if (n <= 0 || !bgr || !hs || !ws || !strides || !P || !boxes_out || !n_faces_out || (extract && !faces_out))
+        return fail(h, DFD_ERR_ARG, "mtcnn_detect: null argument or no image");
+    if (!h->mtcnn || !h->mtcnn->ready) return fail(h, DFD_ERR_STATE, "the weights blob holds no MTCNN cascade");
+    if (P->image_size <= 0 || P->image_size > 1024 || P->margin < 0 || P->image_size <= P->margin)
+        return fail(h, DFD_ERR_ARG, "mtcnn: image_size %d / margin %d (need 0 <= margin < image_size <= 1024)", P->image_size, P->margin);
+    if (!(P->factor > 0.0 && P->factor < 1.0)) return fail(h, DFD_ERR_ARG, "mtcnn: factor %g outside (0, 1)", P->factor);
+    if (P->min_face_size < 12) return fail(h, DFD_ERR_ARG, "mtcnn: min_face_size %d below the P-Net cell (12)", P->min_face_size);
+    for (int k = 0; k < 3; ++k)
+        if (!(P->thresholds[k] >= 0.f && P->thresholds[k] <= 1.f))
+            return fail(h, DFD_ERR_ARG, "mtcnn: thresholds[%d] = %g outside [0, 1]", k, (double)P->thresholds[k]);
+    if (P->selection < DFD_MT_SELECT_NONE || P->selection > DFD_MT_SELECT_LARGEST_OVER_THRESHOLD)
+        return fail(h, DFD_ERR_ARG, "mtcnn: unknown selection %d", P->selection);
+    if (max_faces < 1 || (long long)n * max_faces > 65535) return fail(h, DFD_ERR_ARG, "mtcnn: max_faces %d (need 1 <= n_images x max_faces <= 65535)", max_faces);
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!bgr[i] || hs[i] <= 0 || ws[i] <= 0 || strides[i] < ws[i] * 3 || hs[i] >= 32768 || ws[i] >= 32768)
+            return fail(h, DFD_ERR_ARG, "mtcnn: image %d: bad pointer or geometry", i);
+        int levels = 0;                                              // a factor close to 1 asks for an unbounded pyramid
+        for (double minl = std::min(hs[i], ws[i]) * (12.0 / P->min_face_size); minl >= 12; minl *= P->factor)
+            if (++levels > 64) return fail(h, DFD_ERR_CAPACITY, "mtcnn: image %d needs more than 64 pyramid levels", i);
+        total += ((size_t)hs[i] * strides[i] + 255) & ~(size_t)255;
+    }
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    int rc = ensure(h, &h->frame_buf, total + 16);
+    if (rc) return rc;
+    std::vector<MtImage> imgs(n);
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        uint8_t* dst = (uint8_t*)h->frame_buf.p + off;
+        DFD_HIP_TRY(h, hipMemcpyAsync(dst, bgr[i], (size_t)hs[i] * strides[i], hipMemcpyHostToDevice, h->stream));
+        imgs[i] = MtImage{dst, hs[i], ws[i], (size_t)strides[i]};
+        off += ((size_t)hs[i] * strides[i] + 255) & ~(size_t)255;
+    }
+    return mtcnn_detect_batch(h, imgs.data(), n, *P, max_faces, boxes_out, landmarks_out, n_faces_out, faces_out);
+}
+
+int dfd_mtcnn_detect(dfd_handle* h, int n_images, const uint8_t* const* bgr, const int* heights, const int* widths,
+                     const int* strides, const dfd_mtcnn_params* params, int max_faces, float* boxes_out, float* landmarks_out,
+                     int* n_faces_out) {
+    return mt_detect_call(h, n_images, bgr, heights, widths, strides, params, max_faces, boxes_out, landmarks_out, n_faces_out, nullptr, false);
+}
+
+int dfd_mtcnn_extract(dfd_handle* h, int n_images, const uint8_t* const* bgr, const int* heights, const int* widths,
+                      const int* strides, const dfd_mtcnn_params* params, int max_faces, float* boxes_out, float* landmarks_out,
+                      int* n_faces_out, float* faces_out) {
+    return mt_detect_call(h, n_images, bgr, heights, widths, strides, params, max_faces, boxes_out, landmarks_out, n_faces_out, faces_out, true);
 }
 
 int dfd_mtcnn_tap(dfd_handle* h, const uint8_t* bgr, int hh, int ww, int stride, const char* name, float* out,

@@ -318,9 +318,9 @@ __global__ __launch_bounds__(256) void mt_compact_kernel(const int* __restrict__
 }
 
 // Pillow's precompute_coeffs + normalize_coeffs_8bpc for the bilinear filter (src/libImaging/Resample.c), output index
-// xx of a 160-wide axis read from `in_size` pixels; coeff [160][ksize], bounds [160][2]
-__device__ void pil_axis(int in_size, int xx, int ksize, int* __restrict__ coeff, int* __restrict__ bounds) {
-    const double scale = (double)in_size / 160;
+// xx of an `out_size`-wide axis read from `in_size` pixels; coeff [out_size][ksize], bounds [out_size][2]
+__device__ void pil_axis(int in_size, int out_size, int xx, int ksize, int* __restrict__ coeff, int* __restrict__ bounds) {
+    const double scale = (double)in_size / out_size;
     const double fs = scale < 1.0 ? 1.0 : scale;
     const double support = 1.0 * fs;
     const double center = (xx + 0.5) * scale, ss = 1.0 / fs;
@@ -351,14 +351,15 @@ __device__ void pil_axis(int in_size, int xx, int ksize, int* __restrict__ coeff
     bounds[2 * xx + 1] = xmax;
 }
 
-__device__ __forceinline__ int pil_ksize(int in_size) {
-    const double scale = (double)in_size / 160;
+__device__ __forceinline__ int pil_ksize(int in_size, int out_size = 160) {
+    const double scale = (double)in_size / out_size;
     const double fs = scale < 1.0 ? 1.0 : scale;
     return (int)ceil(1.0 * fs) * 2 + 1;
 }
 
 // ---- stages 2 / 3: network outputs of the crop's windows -> boxes for O-Net (2) / the selected face and its
-// extract_face job (3)
+// extract_face job (3); STAGE 4 is stage 3 for callers that want every face: all rows the NMS keeps, with their O-Net input
+// boxes and landmark fractions, and no selection
 template <int STAGE>
 __global__ __launch_bounds__(kNT) void mt_refine_boxes_kernel(const MtCropGeo* __restrict__ crops, const int* __restrict__ first,
                                                               const MtRow* __restrict__ rows_in, const float* __restrict__ prob,
@@ -366,7 +367,8 @@ __global__ __launch_bounds__(kNT) void mt_refine_boxes_kernel(const MtCropGeo* _
                                                               MtRow* __restrict__ rows_seg, MtSrcWindow* __restrict__ wins_seg,
                                                               int* __restrict__ counts, MtFaceJob* __restrict__ jobs,
                                                               float* __restrict__ results, int* __restrict__ tables,
-                                                              MtRow* __restrict__ tap_rows, int* __restrict__ meta) {
+                                                              MtRow* __restrict__ tap_rows, int* __restrict__ meta,
+                                                              const float* __restrict__ pts, MtDetRow* __restrict__ det_rows) {
     __shared__ u64 keys[kMtCap2];
     __shared__ float4 bx[kMtCap2];
     __shared__ unsigned short kept[kMtCap2];
@@ -395,7 +397,7 @@ __global__ __launch_bounds__(kNT) void mt_refine_boxes_kernel(const MtCropGeo* _
         const int k = src_of(i);
         const MtRow r = rows_in[lo + k];
         float x1 = r.x1, y1 = r.y1, x2 = r.x2, y2 = r.y2;
-        if (STAGE == 3) bbreg(x1, y1, x2, y2, *reinterpret_cast<const float4*>(reg + (size_t)(lo + k) * 4));     // before the NMS
+        if (STAGE >= 3) bbreg(x1, y1, x2, y2, *reinterpret_cast<const float4*>(reg + (size_t)(lo + k) * 4));     // before the NMS
         bx[i] = make_float4(x1, y1, x2, y2);
     }
     __syncthreads();
@@ -430,6 +432,26 @@ __global__ __launch_bounds__(kNT) void mt_refine_boxes_kernel(const MtCropGeo* _
         }
         if (tid == 0) {
             counts[c] = nlive;
+            if (c == 0) meta[2] = nk;
+        }
+        return;
+    }
+    if (STAGE == 4) {
+        for (int idx = tid; idx < nk; idx += kNT) {
+            const int i = kept[idx], k = src_of(i);
+            const float4 b = bx[i];
+            const MtRow in = rows_in[lo + k];                        // the O-Net input box (before bbreg): the landmarks' frame
+            MtDetRow d{};
+            d.x1 = b.x; d.y1 = b.y; d.x2 = b.z; d.y2 = b.w;
+            d.score = __uint_as_float(~(unsigned)(keys[i] >> 32));
+            d.in[0] = in.x1; d.in[1] = in.y1; d.in[2] = in.x2; d.in[3] = in.y2;
+            if (pts)
+                for (int q = 0; q < 10; ++q) d.p[q] = pts[(size_t)(lo + k) * 10 + q];
+            det_rows[lo + idx] = d;                                  // nk <= m: inside the crop's run of windows
+            if (tap_rows && c == 0) tap_rows[idx] = MtRow{b.x, b.y, b.z, b.w, d.score};
+        }
+        if (tid == 0) {
+            counts[c] = nk;
             if (c == 0) meta[2] = nk;
         }
         return;
@@ -474,9 +496,108 @@ __global__ __launch_bounds__(kNT) void mt_refine_boxes_kernel(const MtCropGeo* _
     const MtFaceJob j = s_job;
     if (!j.found) return;
     if (tid < 160) {
-        if (j.cw != 160) pil_axis(j.cw, tid, j.kx, tables + j.cx, tables + j.bx);
+        if (j.cw != 160) pil_axis(j.cw, 160, tid, j.kx, tables + j.cx, tables + j.bx);
     } else if (tid < 320) {
-        if (j.ch != 160) pil_axis(j.ch, tid - 160, j.ky, tables + j.cy, tables + j.by);
+        if (j.ch != 160) pil_axis(j.ch, 160, tid - 160, j.ky, tables + j.cy, tables + j.by);
+    }
+}
+
+// ---- every face of an image: order of the rows (MTCNN.detect's select_largest, MTCNN.select_boxes), landmarks in image
+// coordinates, extract_face geometry with margin for any image_size.  The keys are the package's numpy expressions: box
+// area and box centre in float32, the centre-weighted key in float64 (float32 array minus a tuple of Python floats).
+// Order: descending key; of equal keys the LATER stage-3 row first (np.argsort(...)[::-1] with a stable sort - the rule
+// the single-face path already applies to equal probabilities).
+__global__ __launch_bounds__(256) void mt_select_kernel(const MtCropGeo* __restrict__ crops, const int* __restrict__ first,
+                                                        const int* __restrict__ counts, const MtDetRow* __restrict__ rows, MtSelect P,
+                                                        float* __restrict__ boxes, float* __restrict__ landmarks,
+                                                        int* __restrict__ nfaces, MtFaceJob* jobs, int* __restrict__ tables) {
+    __shared__ double keys[kMtCap2];
+    __shared__ unsigned short order[kMtCap2];
+    __shared__ int s_nsel;
+    const int tid = threadIdx.x, c = blockIdx.x;
+    const MtCropGeo cg = crops[c];
+    const int lo = first[c];
+    const int nk = counts[c] < kMtCap2 ? counts[c] : kMtCap2;        // (the caller refuses more rows than that)
+    if (tid == 0) s_nsel = 0;
+    for (int i = tid; i < nk; i += 256) {
+        const MtDetRow r = rows[lo + i];
+        const float area = (r.x2 - r.x1) * (r.y2 - r.y1);
+        double key = -(double)i;                                     // 0: stage-3 order
+        bool valid = true;
+        if (P.selection == 1) key = (double)r.score;
+        else if (P.selection == 2) key = (double)area;
+        else if (P.selection == 3) {
+            const float cx = (r.x1 + r.x2) / 2.f, cy = (r.y1 + r.y2) / 2.f;
+            const double ox = (double)cx - (double)cg.w / 2.0, oy = (double)cy - (double)cg.h / 2.0;
+            key = (double)area - (ox * ox + oy * oy) * 2.0;
+        } else if (P.selection == 4) {
+            valid = r.score > 0.9f;
+            key = (double)area;
+        }
+        keys[i] = valid && key == key ? key : __longlong_as_double(0x7FF8000000000000ll);      // NaN: not in the order
+    }
+    __syncthreads();
+    for (int i = tid; i < nk; i += 256) {
+        const double ki = keys[i];
+        if (!(ki == ki)) continue;
+        int rank = 0;
+        for (int j = 0; j < nk; ++j) {
+            const double kj = keys[j];
+            rank += (kj > ki || (kj == ki && j > i)) ? 1 : 0;
+        }
+        order[rank] = (unsigned short)i;
+        atomicAdd(&s_nsel, 1);
+    }
+    __syncthreads();
+    const int nsel = s_nsel;
+    const int nret = P.keep_all ? nsel : (nsel < 1 ? nsel : 1);
+    const int nout = nret < P.max_faces ? nret : P.max_faces;
+    if (tid == 0) nfaces[c] = nret;
+    const int S = P.image_size;
+    const int kmx = pil_ksize(cg.w, S), kmy = pil_ksize(cg.h, S);                   // table capacities (cw <= w, ch <= h)
+    const int slot_tab = S * (kmx + kmy) + 4 * S;
+    const long long slot_tmp = ((long long)cg.h * S * 3 + 255) & ~255ll;
+    for (int r = tid; r < nout; r += 256) {
+        const MtDetRow d = rows[lo + order[r]];
+        const size_t slot = (size_t)c * P.max_faces + r;
+        float* bo = boxes + slot * 5;
+        bo[0] = d.x1; bo[1] = d.y1; bo[2] = d.x2; bo[3] = d.y2; bo[4] = d.score;
+        if (landmarks) {
+            // detect_face: points_x = w * p[0:5] + x1 - 1, points_y = h * p[5:10] + y1 - 1 on the O-Net input box
+            const float w = d.in[2] - d.in[0] + 1.f, hgt = d.in[3] - d.in[1] + 1.f;
+            float* lm = landmarks + slot * 10;
+            for (int q = 0; q < 5; ++q) {
+                lm[2 * q] = w * d.p[q] + d.in[0] - 1.f;
+                lm[2 * q + 1] = hgt * d.p[5 + q] + d.in[1] - 1.f;
+            }
+        }
+        if (jobs) {
+            // extract_face: margin scaled to the box per axis, corners clipped to the image, int() of the floats
+            MtFaceJob j{cg.src, cg.stride, 0, 0, S, S, 0, 0, 0, 0, 0, 0, cg.tmp_off + r * slot_tmp, 2};
+            const float den = (float)(S - P.margin);
+            const float mx = (float)P.margin * (d.x2 - d.x1) / den, my = (float)P.margin * (d.y2 - d.y1) / den;
+            const int x1 = f2i(smax(d.x1 - mx / 2.f, 0.f)), y1 = f2i(smax(d.y1 - my / 2.f, 0.f));
+            const int x2 = f2i(smin(d.x2 + mx / 2.f, (float)cg.w)), y2 = f2i(smin(d.y2 + my / 2.f, (float)cg.h));
+            if (!(x2 <= x1 || y2 <= y1)) {
+                j.x1 = x1; j.y1 = y1; j.cw = x2 - x1; j.ch = y2 - y1;
+                j.cx = cg.tab_off + r * slot_tab; j.bx = j.cx + S * kmx; j.cy = j.bx + 2 * S; j.by = j.cy + S * kmy;
+                j.kx = j.cw != S ? pil_ksize(j.cw, S) : 0;
+                j.ky = j.ch != S ? pil_ksize(j.ch, S) : 0;
+                j.found = 1;
+            }
+            jobs[slot] = j;
+        }
+    }
+    if (!jobs) return;
+    __syncthreads();
+    for (int r = 0; r < nout; ++r) {
+        const MtFaceJob j = jobs[(size_t)c * P.max_faces + r];
+        if (j.found != 1) continue;
+        for (int t = tid; t < 2 * S; t += 256) {
+            if (t < S) {
+                if (j.cw != S) pil_axis(j.cw, S, t, j.kx, tables + j.cx, tables + j.bx);
+            } else if (j.ch != S) pil_axis(j.ch, S, t - S, j.ky, tables + j.cy, tables + j.by);
+        }
     }
 }
 
@@ -502,10 +623,24 @@ void launch_mt_refine_boxes(int stage, const MtCropGeo* crops, const int* first,
     if (n <= 0) return;
     if (stage == 2)
         hipLaunchKernelGGL(mt_refine_boxes_kernel<2>, dim3(n), dim3(kNT), 0, s, crops, first, rows_in, prob, reg, thr_p, thr_nms, rows_seg,
-                           wins_seg, counts, jobs, results, tables, tap_rows, meta);
+                           wins_seg, counts, jobs, results, tables, tap_rows, meta, nullptr, nullptr);
     else
         hipLaunchKernelGGL(mt_refine_boxes_kernel<3>, dim3(n), dim3(kNT), 0, s, crops, first, rows_in, prob, reg, thr_p, thr_nms, rows_seg,
-                           wins_seg, counts, jobs, results, tables, tap_rows, meta);
+                           wins_seg, counts, jobs, results, tables, tap_rows, meta, nullptr, nullptr);
+}
+
+void launch_mt_stage3_rows(const MtCropGeo* crops, const int* first, int n, const MtRow* rows_in, const float* prob, const float* reg,
+                           const float* pts, float thr_p, float thr_nms, MtDetRow* det_rows, int* counts, MtRow* tap_rows, int* meta,
+                           hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(mt_refine_boxes_kernel<4>, dim3(n), dim3(kNT), 0, s, crops, first, rows_in, prob, reg, thr_p, thr_nms, nullptr,
+                       nullptr, counts, nullptr, nullptr, nullptr, tap_rows, meta, pts, det_rows);
+}
+
+void launch_mt_select(const MtCropGeo* crops, const int* first, const int* counts, int n, const MtDetRow* rows, MtSelect sel,
+                      float* boxes, float* landmarks, int* nfaces, MtFaceJob* jobs, int* tables, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(mt_select_kernel, dim3(n), dim3(256), 0, s, crops, first, counts, rows, sel, boxes, landmarks, nfaces, jobs, tables);
 }
 
 }  // namespace dfd

@@ -57,6 +57,13 @@ void launch_mt_area_resize_multi(const MtSrcWindow* win_dev, int n, int oh, int 
 struct MtFaceJob { const uint8_t* src; long long stride; int x1, y1, cw, ch, kx, ky, cx, bx, cy, by; long long tmp_off; int found; };
 void launch_mt_extract_faces(const MtFaceJob* jobs_dev, int n, const int* tables_dev, uint8_t* faces, uint8_t* tmp, hipStream_t s);
 void launch_mt_face_chw(const uint8_t* bgr, float* out, int hw, hipStream_t s);
+// O-Net landmark head: pts [n][10] = f [n][in] . w [in][10] + b (dense6_3; the five x fractions, then the five y fractions)
+void launch_mt_points(const float* f, const float* w, const float* b, float* pts, int n, int in, hipStream_t s);
+// extract_face of every face slot of a call (dfd_mtcnn_extract): jobs [slots] as above with found = 0: slot unused, not
+// written; 1: window -> size x size (Pillow bilinear, one launch per pass, tmp [ch][size][3] per slot); 2: degenerate box,
+// zero-filled.  faces [slots][3][size][size] float RGB planes, 0..255 or (x - 127.5) / 128 with `standardize`.
+void launch_mt_extract_faces_multi(const MtFaceJob* jobs_dev, int slots, int size, const int* tables_dev, float* faces, uint8_t* tmp,
+                                   bool standardize, hipStream_t s);
 
 // ---- box bookkeeping on the device (mtcnn_boxes.hip): one block per crop and stage
 constexpr int kMtCap1 = 8192;    // P-Net candidates of one crop the stage-1 block holds
@@ -77,5 +84,22 @@ void launch_mt_compact(const int* counts, int n, const MtCropGeo* crops, const i
 void launch_mt_refine_boxes(int stage, const MtCropGeo* crops, const int* first, int n, const MtRow* rows_in, const float* prob,
                             const float* reg, float thr_p, float thr_nms, MtRow* rows_seg, MtSrcWindow* wins_seg, int* counts,
                             MtFaceJob* jobs, float* results, int* tables, MtRow* tap_rows, int* meta, hipStream_t s);
+
+// ---- every face of an image (dfd_mtcnn_detect / dfd_mtcnn_extract)
+// a row that survived stage 3: regressed box + probability, the O-Net input box it came from, the raw landmark fractions
+struct MtDetRow { float x1, y1, x2, y2, score; float in[4]; float p[10]; float pad; };
+// stage 3 for all rows: O-Net prob / reg (and pts [window][10] or null) of the windows first[c] .. first[c + 1] -> the rows
+// kept by the "Min" NMS in its order at det_rows[first[c] ..], counts[c] of them
+void launch_mt_stage3_rows(const MtCropGeo* crops, const int* first, int n, const MtRow* rows_in, const float* prob, const float* reg,
+                           const float* pts, float thr_p, float thr_nms, MtDetRow* det_rows, int* counts, MtRow* tap_rows, int* meta,
+                           hipStream_t s);
+// order of the returned rows: 0 = as stage 3 yields them, 1 = probability, 2 = box area, 3 = area - 2 x squared offset from
+// the image centre, 4 = area among the rows above 0.9 probability; all descending, of equal keys the later stage-3 row first
+struct MtSelect { int selection, keep_all, image_size, margin, max_faces; };
+// one block per image: ordered rows -> boxes [n][max_faces][5], landmarks [n][max_faces][5][2] (or null) in image
+// coordinates, nfaces [n] (all rows of the order, also beyond max_faces; at most 1 without keep_all), and with `jobs`
+// [n][max_faces] the extract_face geometry (margin, clipping) and resize tables of the returned rows
+void launch_mt_select(const MtCropGeo* crops, const int* first, const int* counts, int n, const MtDetRow* rows, MtSelect sel,
+                      float* boxes, float* landmarks, int* nfaces, MtFaceJob* jobs, int* tables, hipStream_t s);
 
 }  // namespace dfd

@@ -183,6 +183,100 @@ void launch_mt_face_chw(const uint8_t* bgr, float* out, int hw, hipStream_t s) {
     hipLaunchKernelGGL(mt_face_chw_kernel, dim3((3 * hw + 255) / 256), dim3(256), 0, s, bgr, out, hw);
 }
 
+// O-Net landmark head (dense6_3): ten dot products per feature row, sixteen lanes per row as in mt_heads_kernel.  A launch
+// of its own so that callers that want no landmarks (the classify path) do not run it at all.
+__global__ __launch_bounds__(256) void mt_points_kernel(const float* __restrict__ f, const float* __restrict__ w,
+                                                        const float* __restrict__ b, float* __restrict__ pts, int n, int in) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    constexpr int LANES = 16;
+    const int l = (int)(t & (LANES - 1));
+    const long long row = t / LANES;
+    const long long rc = row < n ? row : (long long)n - 1;     // surplus groups redo the last row (uniform shuffles)
+    const float* fp = f + (size_t)rc * in;
+    float acc[10];
+#pragma unroll
+    for (int q = 0; q < 10; ++q) acc[q] = 0.f;
+    for (int c = l; c < in; c += LANES) {
+        const float v = fp[c];
+        const float2* wp = reinterpret_cast<const float2*>(w + (size_t)c * 10);
+#pragma unroll
+        for (int q = 0; q < 5; ++q) {
+            const float2 a = wp[q];
+            acc[2 * q] = fmaf(v, a.x, acc[2 * q]);
+            acc[2 * q + 1] = fmaf(v, a.y, acc[2 * q + 1]);
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < LANES; off <<= 1)
+#pragma unroll
+        for (int q = 0; q < 10; ++q) acc[q] += __shfl_xor(acc[q], off);
+    if (l == 0 && row < n) {
+#pragma unroll
+        for (int q = 0; q < 10; ++q) pts[(size_t)row * 10 + q] = acc[q] + b[q];
+    }
+}
+
+void launch_mt_points(const float* f, const float* w, const float* b, float* pts, int n, int in, hipStream_t s) {
+    if (n <= 0) return;
+    const long long threads = (long long)n * 16;
+    hipLaunchKernelGGL(mt_points_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, f, w, b, pts, n, in);
+}
+
+// extract_face for every face slot of a call (blockIdx.y = slot), any output size: the horizontal pass of every slot whose
+// window is not `size` wide into the slot's [ch][size][3] intermediate, then the vertical pass / plain copy that writes
+// the slot's float RGB planes.  Per element the arithmetic is the 160 x 160 kernels' above.
+__global__ __launch_bounds__(256) void mt_extract_multi_h_kernel(const MtFaceJob* __restrict__ jobs, int size,
+                                                                 const int* __restrict__ tables, uint8_t* __restrict__ tmp) {
+    const MtFaceJob j = jobs[blockIdx.y];
+    if (j.found != 1 || j.cw == size) return;
+    uint8_t* dst = tmp + j.tmp_off;
+    const int total = j.ch * size * 3;
+    const int* coeff = tables + j.cx;
+    const int* bounds = tables + j.bx;
+    for (int t = blockIdx.x * 256 + threadIdx.x; t < total; t += gridDim.x * 256) {
+        const int c = t % 3, col = (t / 3) % size, row = t / 3 / size;
+        const int xmin = bounds[2 * col], cnt = bounds[2 * col + 1];
+        dst[t] = pil_tap_sum(j.src + (size_t)(j.y1 + row) * j.stride + (size_t)(j.x1 + xmin) * 3 + c, 3, coeff + (size_t)col * j.kx, cnt);
+    }
+}
+
+__global__ __launch_bounds__(256) void mt_extract_multi_v_kernel(const MtFaceJob* __restrict__ jobs, int size,
+                                                                 const int* __restrict__ tables, float* __restrict__ faces,
+                                                                 const uint8_t* __restrict__ tmp, int standardize) {
+    const MtFaceJob j = jobs[blockIdx.y];
+    if (j.found == 0) return;                                               // unused slot: not written
+    const int plane = size * size, total = 3 * plane;
+    float* dst = faces + (size_t)blockIdx.y * total;
+    const bool resized = j.cw != size;                                      // the vertical pass reads tmp [ch][size][3]
+    const uint8_t* src = resized ? tmp + j.tmp_off : j.src + (size_t)j.y1 * j.stride + (size_t)j.x1 * 3;
+    const size_t sstride = resized ? (size_t)size * 3 : (size_t)j.stride;
+    const int* coeff = tables + j.cy;
+    const int* bounds = tables + j.by;
+    for (int t = blockIdx.x * 256 + threadIdx.x; t < total; t += gridDim.x * 256) {
+        const int p = t / plane, rem = t - p * plane, row = rem / size, col = rem - row * size;
+        const int c = 2 - p;                                                // RGB plane p <- BGR channel
+        float v = 0.f;
+        if (j.found == 1) {
+            uint8_t u;
+            if (j.ch == size) u = src[(size_t)row * sstride + (size_t)col * 3 + c];
+            else {
+                const int ymin = bounds[2 * row], cnt = bounds[2 * row + 1];
+                u = pil_tap_sum(src + (size_t)ymin * sstride + (size_t)col * 3 + c, sstride, coeff + (size_t)row * j.ky, cnt);
+            }
+            v = standardize ? ((float)u - 127.5f) / 128.f : (float)u;       // fixed_image_standardization (exact in fp32)
+        }
+        dst[t] = v;
+    }
+}
+
+void launch_mt_extract_faces_multi(const MtFaceJob* jobs_dev, int slots, int size, const int* tables_dev, float* faces, uint8_t* tmp,
+                                   bool standardize, hipStream_t s) {
+    if (slots <= 0) return;
+    hipLaunchKernelGGL(mt_extract_multi_h_kernel, dim3(64, slots), dim3(256), 0, s, jobs_dev, size, tables_dev, tmp);
+    hipLaunchKernelGGL(mt_extract_multi_v_kernel, dim3(64, slots), dim3(256), 0, s, jobs_dev, size, tables_dev, faces, tmp,
+                       standardize ? 1 : 0);
+}
+
 // ------------------------------------------------------------------------------------------------ ragged
 // Stage 1 runs P-Net over every pyramid level of every crop of a step: a few hundred small images of different
 // sizes.  One launch per layer covers them all: `items` describes each image (offsets into the layer's input and
