@@ -273,11 +273,38 @@ int dfd_detect_faces_haar(dfd_handle* h, const uint8_t* bgr, int height, int wid
 int dfd_has_mtcnn(const dfd_handle* h);
 int dfd_mtcnn_align(dfd_handle* h, const uint8_t* bgr, int height, int width, int stride,
                     float* face_chw_out, float* box_out, int* found);
-/* One named cascade intermediate for parity tests: "pnet.prob.<level>" [H][W], "pnet.reg.<level>"
- * [H][W][4], "rnet.prob" / "onet.prob" [n] and "rnet.reg" / "onet.reg" [n][4] of the candidate windows in
- * order, "stage1" / "stage2" / "stage3" rows (x1,y1,x2,y2,score); dims[3] receives the shape. */
+/* One named cascade intermediate for parity tests; dims[3] receives the shape.  Every buffer the cascade
+ * materialises has a name (activations NHWC, fp32):
+ *   "pnet.in.<level>" [sh][sw][3] the area-resized, normalised RGB level; "pnet.pool1.<level>" [ph][pw][10] conv1 + PReLU
+ *   + ceil-mode pool of ONE launch (the conv1 map is never stored); "pnet.conv2.<level>" [ph-2][pw-2][16];
+ *   "pnet.prob.<level>" [H][W], "pnet.reg.<level>" [H][W][4] (conv3 + both heads + softmax of one launch: the 32-channel
+ *   conv3 map is never stored either);
+ *   "pnet.cand": the raw candidate records of ALL images of the call in the order the conv3 launch appended them,
+ *   [k][6] 32-bit words {cell (uint32, index into the concatenated maps of all levels of all images), p, r[4]}: dims =
+ *   {records, 6, the launch's counter};
+ *   "rnet.in" [n][24*24][3], "rnet.pool1" [n][11*11][32] (conv1 + PReLU + pool, one launch; channels 28..31 are zero
+ *   padding), "rnet.conv2" [n][9*9][64] (48..63 zero padding), "rnet.pool2" [n][4*4][64], "rnet.conv3" [n][3*3][64],
+ *   "rnet.dense4" [n][1][128], "rnet.prob" [n], "rnet.reg" [n][4] of the image's candidate windows in order;
+ *   "onet.in" [n][48*48][3], "onet.pool1" [n][23*23][32], "onet.conv2" [n][21*21][64], "onet.pool2" [n][10*10][64],
+ *   "onet.conv3" [n][8*8][64], "onet.pool3" [n][4*4][64], "onet.conv4" [n][3*3][128], "onet.dense5" [n][1][256],
+ *   "onet.prob", "onet.reg", "onet.pts" [n][10] (the landmark head, evaluated for this tap only);
+ *   "stage1" / "stage2" / "stage3" rows (x1,y1,x2,y2,score); "boxes.overflow" [1]: 1 when an image exceeded the device
+ *   box blocks' capacity and the call ran on the host path (device box path only).
+ * dfd_mtcnn_tap runs one image.  dfd_mtcnn_tap_batch runs n images in ONE cascade call - the ragged launches of
+ * dfd_classify_crops / dfd_analyze_batch_device - and reads the buffer of image `crop`; a network that no window of that
+ * image reached yields an empty tap.  dfd_mtcnn_net_tap runs the R-Net (onet = 0, 24 x 24) or O-Net (48 x 48) trunk alone,
+ * on m windows, in chunks as in production, and reads rows [row0, row0 + rows) of an "rnet.*" / "onet.*" buffer.  Its
+ * input is either `windows` [m][sz][sz][3], which takes the place of the window resize (values and counts no image
+ * produces), or - windows = NULL - the source windows xywh [m][4] (x, y, w, h inside the image) of the BGR image given.
+ * P-Net has no injected input: its ragged launches take their geometry from the image sizes.
+ * A call that names no tap (every production entry point) downloads none of these. */
 int dfd_mtcnn_tap(dfd_handle* h, const uint8_t* bgr, int height, int width, int stride,
                   const char* name, float* out, size_t capacity, size_t* count, int* dims);
+int dfd_mtcnn_tap_batch(dfd_handle* h, int n_images, const uint8_t* const* bgr, const int* heights, const int* widths,
+                        const int* strides, int crop, const char* name, float* out, size_t capacity, size_t* count, int* dims);
+int dfd_mtcnn_net_tap(dfd_handle* h, int onet, const float* windows, const uint8_t* bgr, int height, int width, int stride,
+                      const int* xywh, int m, int row0, int rows, const char* name, float* out, size_t capacity,
+                      size_t* count, int* dims);
 
 /* ---- MTCNN with every constructor argument of the package: all faces, landmarks, any crop size ----------
  * facenet_pytorch.MTCNN(image_size, margin, min_face_size, thresholds, factor, post_process, select_largest,

@@ -82,6 +82,10 @@ SIGNATURES = {
                                   C.POINTER(C.c_int)]),
     "dfd_mtcnn_tap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_void_p,
                                 C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "dfd_mtcnn_tap_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_char_p,
+                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "dfd_mtcnn_net_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                    C.c_int, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "dfd_mtcnn_params_default": (None, [C.c_void_p]),
     "dfd_mtcnn_detect": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -895,6 +899,53 @@ class Handle:
         if dims[1] == 5 and dims[2] == 1:
             shape = (int(dims[0]), 5)
         return out[: cnt.value].reshape(shape) if cnt.value else out[:0].reshape((0,) + shape[1:])
+
+    @staticmethod
+    def _mtcnn_tap_result(out, cnt, dims, name):
+        d = tuple(int(v) for v in dims)
+        if name == "pnet.cand":                              # raw 32-bit words, the launch's counter
+            return out[:cnt].reshape(-1, 6), d[2]
+        if d[2] == 1 and d[1] in (1, 4, 5):
+            return out[:cnt].reshape(d[0]) if d[1] == 1 else out[:cnt].reshape(d[0], d[1])
+        return out[:cnt].reshape(d)
+
+    def mtcnn_tap_batch(self, images, crop: int, name: str, capacity: int = 1 << 24):
+        """One named buffer (dfd_mtcnn_tap in include/dfd_hip.h lists them) of image `crop` of one batched cascade call
+        over `images`, shaped as the header documents; "pnet.cand" -> (records (k, 6) float32 bit patterns, counter)."""
+        imgs = [self._as_bgr(a) for a in images]
+        n = len(imgs)
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in imgs])
+        hs = np.array([a.shape[0] for a in imgs], np.int32)
+        ws = np.array([a.shape[1] for a in imgs], np.int32)
+        st = np.array([a.strides[0] for a in imgs], np.int32)
+        out = np.empty(int(capacity), np.float32)
+        cnt = C.c_size_t()
+        dims = np.zeros(3, np.int32)
+        self._check(self._lib.dfd_mtcnn_tap_batch(self._p, n, ptrs, _ptr(hs), _ptr(ws), _ptr(st), int(crop), name.encode(),
+                                                  _ptr(out), out.size, C.byref(cnt), _ptr(dims)))
+        return self._mtcnn_tap_result(out, cnt.value, dims, name)
+
+    def mtcnn_net_tap(self, net: str, windows, name: str, row0: int = 0, rows: Optional[int] = None, image=None):
+        """Rows [row0, row0 + rows) of buffer `name` of the R-Net ("rnet") or O-Net ("onet") trunk run alone
+        (dfd_mtcnn_net_tap): on the input windows (m, sz, sz, 3) float32 in place of the window resize, or - with
+        `image` (H, W, 3) uint8 BGR - on its source windows (m, 4) int32 (x, y, w, h)."""
+        sz = 48 if net == "onet" else 24
+        if image is None:
+            x = np.ascontiguousarray(windows, np.float32)
+            assert x.ndim == 4 and x.shape[1:] == (sz, sz, 3), x.shape
+            src = (_ptr(x), None, 0, 0, 0, None)
+        else:
+            a = self._as_bgr(image)
+            x = np.ascontiguousarray(windows, np.int32)
+            assert x.ndim == 2 and x.shape[1] == 4, x.shape
+            src = (None, _ptr(a), a.shape[0], a.shape[1], a.strides[0], _ptr(x))
+        rows = x.shape[0] - row0 if rows is None else rows
+        out = np.empty(rows * sz * sz * 16, np.float32)        # (the widest buffer: conv2)
+        cnt = C.c_size_t()
+        dims = np.zeros(3, np.int32)
+        self._check(self._lib.dfd_mtcnn_net_tap(self._p, int(net == "onet"), *src, x.shape[0], int(row0), int(rows), name.encode(),
+                                                _ptr(out), out.size, C.byref(cnt), _ptr(dims)))
+        return self._mtcnn_tap_result(out, cnt.value, dims, name)
 
     def _mtcnn_call(self, images, params: MtcnnParams, max_faces: int, landmarks: bool, faces: bool):
         imgs = [self._as_bgr(a) for a in images]

@@ -226,12 +226,12 @@ int forensics_batch_begin(dfd_handle* h, const uint8_t* frames_dev, int n, int h
 int forensics_batch_end(dfd_handle* h, int n, double* prob_out, double* scores_out);
 
 // mtcnn_api.hip: MTCNN.forward on a BGR image in HBM -> selected box (x1,y1,x2,y2,prob), *found, and the
-// 160x160 BGR u8 crop at mtcnn_face_dev(h).  tap_* are for parity tests (null otherwise).
+// 160x160 BGR u8 crop at mtcnn_face_dev(h).  tap_* are for parity tests (null otherwise; tap_crop: the image they read).
 struct MtImage { const uint8_t* src; int h, w; size_t stride; };
 // the same for `n` images of a step at once: faces_out [n][160*160*3] (device), boxes_out [n][5] or null, found [n]
 // returns after the step's last stream wait: `found` is final (the classifier is then sized by the faces that are left)
 int mtcnn_align_batch_device(dfd_handle* h, const MtImage* imgs, int n, uint8_t* faces_out, float* boxes_out, char* found,
-                             const char* tap_name, std::vector<float>* tap, int* tap_dims);
+                             const char* tap_name, std::vector<float>* tap, int* tap_dims, int tap_crop = 0);
 int mtcnn_align_device(dfd_handle* h, const uint8_t* img_dev, int hh, int ww, size_t stride, float* box_out, int* found,
                        const char* tap_name, std::vector<float>* tap, int* tap_dims);
 const uint8_t* mtcnn_face_dev(dfd_handle* h);

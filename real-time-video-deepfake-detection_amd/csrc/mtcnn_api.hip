@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstring>
 #include <atomic>
 #include <numeric>
 #include <thread>
@@ -38,11 +39,12 @@ struct MtcnnState {
     MtGemmConv r2g, r3g, o2g, o3g, o4g;
     DevBuf in, a0, a1, prob, reg, win, coef, bnd, tmp, face, d_lv, bs, cand;       // d_lv: every descriptor table of a step
     // box bookkeeping on the device (mtcnn_boxes.hip): crop / level tables, counts + prefix arrays + meta words, segmented and
-    // compact row / window arenas, per-crop result rows, rows of crop 0 for the parity taps
+    // compact row / window arenas, per-crop result rows, rows of the tap crop for the parity taps
     DevBuf cnt, rows_a, wins_a, rows_b, wins_b, res, taprows;
     // every face of an image (dfd_mtcnn_detect / dfd_mtcnn_extract): landmark fractions of the O-Net windows, the rows stage 3
     // keeps, [first n + 1][counts n] of the host path, ordered boxes / landmarks / face counts, the float face slots
     DevBuf pts, det_rows, det_idx, det_box, det_lm, det_nf, det_faces;
+    DevBuf inject;                        // dfd_mtcnn_net_tap: the caller's R-/O-Net input windows
 };
 
 void mtcnn_destroy(dfd_handle* h) {
@@ -295,7 +297,7 @@ struct Cascade {
     MtcnnState* S;
     const MtImage* imgs;
     int n;
-    const char* tap_name;          // parity taps (crop 0 only)
+    const char* tap_name;          // parity taps (of crop `tap_crop`); null in production: no tap costs anything then
     std::vector<float>* tap;
     int* tap_dims;
 
@@ -310,7 +312,48 @@ struct Cascade {
     const int* det_first = nullptr;        // device: first row / row count of each image in S->det_rows
     const int* det_counts = nullptr;
 
+    // parity taps: the crop they read; the window rows [tap_lo, tap_lo + tap_n) of that crop in the running refine_gpu call;
+    // `inject` (dfd_mtcnn_net_tap): device array [total][sz][sz][3] that takes the place of the window resize
+    int tap_crop = 0, tap_lo = 0, tap_n = 0;
+    const float* inject = nullptr;
+
     bool want(const std::string& nm) const { return tap_name && nm == tap_name; }
+    // (taps can be tens of MB: a plain copy, not the mailbox)
+    int fetch(const void* dev, size_t floats, float* out) {
+        if (!floats) return DFD_OK;
+        DFD_HIP_TRY(h, hipMemcpyAsync(out, dev, floats * 4, hipMemcpyDeviceToHost, h->stream));
+        DFD_HIP_TRY(h, stream_sync(h));
+        return DFD_OK;
+    }
+    int tap_map(const std::string& nm, const float* dev, int d0, int d1, int d2) {
+        if (!want(nm)) return DFD_OK;
+        tap->resize((size_t)d0 * d1 * d2);
+        tap_dims[0] = d0; tap_dims[1] = d1; tap_dims[2] = d2;
+        return fetch(dev, tap->size(), tap->data());
+    }
+    // rows of the tap crop in a per-window buffer of the chunk [start, start + m): `per` = d1 * d2 floats a window
+    int tap_windows(const std::string& nm, const float* chunk, int start, int m, int d1, int d2) {
+        if (!want(nm)) return DFD_OK;
+        const size_t per = (size_t)d1 * d2;
+        if (start == 0) {
+            tap->assign((size_t)tap_n * per, 0.f);
+            tap_dims[0] = tap_n; tap_dims[1] = d1; tap_dims[2] = d2;
+        }
+        const int lo = std::max(tap_lo, start), hi = std::min(tap_lo + tap_n, start + m);
+        if (hi <= lo) return DFD_OK;
+        return fetch(chunk + (size_t)(lo - start) * per, (size_t)(hi - lo) * per, tap->data() + (size_t)(lo - tap_lo) * per);
+    }
+    // device box path: the tap crop's run of windows, from the compact kernel's prefix array
+    int tap_range(const int* first_dev) {
+        tap_lo = tap_n = 0;
+        if (!tap_name) return DFD_OK;
+        const int* pf = (const int*)mailbox_d2h(h, first_dev + tap_crop, 8);
+        if (!pf) return fail(h, DFD_ERR_HIP, "mtcnn: mailbox allocation failed");
+        DFD_HIP_TRY(h, stream_sync(h));
+        tap_lo = pf[0];
+        tap_n = pf[1] - pf[0];
+        return DFD_OK;
+    }
 
     std::chrono::steady_clock::time_point t_mark = std::chrono::steady_clock::now();
     void mark(const char* what) {                          // DFD_MT_VERBOSE=2: wall time of each phase
@@ -345,7 +388,7 @@ struct Cascade {
         tap_dims[0] = (int)b.size(); tap_dims[1] = 5; tap_dims[2] = 1;
     }
 
-    struct Level { int crop; double scale; int sh, sw, oh, ow; long long cell_off; };
+    struct Level { int crop; double scale; int sh, sw, oh, ow; long long cell_off; long long in_off, p_off, c2_off; };
 
     bool stage1_done = false;              // the P-Net launches of this step are already queued (device path fell back)
     std::vector<Level> levels;             // pyramid levels of all crops (stage1_gpu)
@@ -386,7 +429,7 @@ struct Cascade {
                 const int sh = (int)(hh * scale_i + 1), sw = (int)(ww * scale_i + 1);
                 const int c1h = sh - 2, c1w = sw - 2, ph = mt_pool_out(c1h, 2, 2), pw = mt_pool_out(c1w, 2, 2);
                 const int c2h = ph - 2, c2w = pw - 2, c3h = c2h - 2, c3w = c2w - 2;
-                levels.push_back(Level{c, scale_i, sh, sw, c3h, c3w, cells});
+                levels.push_back(Level{c, scale_i, sh, sw, c3h, c3w, cells, pre_in.back(), pre_p.back(), pre_c2.back()});
                 lv.push_back(MtLevel{imgs[c].src, (long long)imgs[c].stride, hh, ww, sh, sw, pre_in.back()});
                 it_f.push_back(MtItem{pre_in.back(), pre_p.back(), sh, sw});            // conv1 + pool: pyramid -> pooled map
                 it_c2.push_back(MtItem{pre_p.back(), pre_c2.back(), ph, pw});
@@ -507,13 +550,29 @@ struct Cascade {
                 tap_prob.resize(cells);
                 DFD_HIP_TRY(h, hipMemcpyAsync(tap_prob.data(), S->prob.p, cells * 4, hipMemcpyDeviceToHost, s));
                 if ((rc = download(S->reg.p, (size_t)cells * 4, &tap_reg))) return rc;
+                if (want("pnet.cand")) {                      // the raw records of ALL crops, append order: [k][cell, p, r[4]]
+                    unsigned count = 0;
+                    if ((rc = fetch(d_count, 1, (float*)&count))) return rc;
+                    const size_t nrec = std::min<size_t>(count, (size_t)cells);
+                    tap->resize(nrec * 6);
+                    static_assert(sizeof(MtCand) == 24, "tap layout");
+                    if ((rc = fetch(d_cand, nrec * 6, tap->data()))) return rc;
+                    tap_dims[0] = (int)nrec; tap_dims[1] = 6; tap_dims[2] = (int)count;       // count: what the kernels counted
+                }
             }
         }
         int level_in_crop = 0, prev_crop = -1;
-        for (const Level& L : levels) {                      // parity taps (crop 0 only)
+        for (const Level& L : levels) {                      // parity taps
             level_in_crop = L.crop == prev_crop ? level_in_crop + 1 : 0;
             prev_crop = L.crop;
-            if (L.crop != 0 || !tap_name) continue;
+            if (L.crop != tap_crop || !tap_name) continue;
+            {
+                const int ph = mt_pool_out(L.sh - 2, 2, 2), pw = mt_pool_out(L.sw - 2, 2, 2);
+                const std::string k = std::to_string(level_in_crop);
+                if ((rc = tap_map("pnet.in." + k, (const float*)S->in.p + L.in_off, L.sh, L.sw, 3))) return rc;
+                if ((rc = tap_map("pnet.pool1." + k, (const float*)S->a1.p + L.p_off, ph, pw, 10))) return rc;
+                if ((rc = tap_map("pnet.conv2." + k, (const float*)S->a0.p + L.c2_off, ph - 2, pw - 2, 16))) return rc;
+            }
             const float* P = tap_prob.data() + L.cell_off;
             const float* R = tap_reg.data() + L.cell_off * 4;
             if (want("pnet.prob." + std::to_string(level_in_crop))) {
@@ -598,7 +657,7 @@ struct Cascade {
             }
         });
         mark("s1 host: cross-level NMS");
-        tap_boxes("stage1", (*out)[0]);
+        tap_boxes("stage1", (*out)[tap_crop]);
         return DFD_OK;
     }
 
@@ -619,32 +678,60 @@ struct Cascade {
         if (onet && want_points && (rc = ensure(h, &S->pts, (size_t)total * 10 * 4))) return rc;
         for (int start = 0; start < total; start += kChunk) {
             const int m = std::min(kChunk, total - start);
-            const MtSrcWindow* wd = wd_all + start;                  // (the ensure calls above never move the window list)
+            const MtSrcWindow* wd = inject ? nullptr : wd_all + start;     // (the ensure calls above never move the window list)
             float *in = (float*)S->in.p, *a0 = (float*)S->a0.p, *a1 = (float*)S->a1.p;
             float *pr = (float*)S->prob.p + start, *rg = (float*)S->reg.p + (size_t)start * 4;
-            launch_mt_area_resize_multi(wd, m, sz, sz, in, s);
+            if (inject)
+                DFD_HIP_TRY(h, hipMemcpyAsync(in, inject + (size_t)start * sz * sz * 3, (size_t)m * sz * sz * 3 * 4, hipMemcpyDeviceToDevice, s));
+            else
+                launch_mt_area_resize_multi(wd, m, sz, sz, in, s);
+            // parity taps: every buffer right after the launch that wrote it (a0 / a1 are reused down the trunk)
+            auto T = [&](const char* nm, const float* buf, int d1, int d2) {
+                return tap_name ? tap_windows(std::string(onet ? "onet." : "rnet.") + nm, buf, start, m, d1, d2) : DFD_OK;
+            };
+            if ((rc = T("in", in, sz * sz, 3))) return rc;
             if (!onet) {
                 // conv1 (22, 32 ch = 28 + 4 zero) + PReLU + pool (11) in one launch
                 if (!launch_mt_conv1_pool(in, S->r1p.w, S->r1p.b, S->r1p.a, a1, m, 24, 24, 32, s)) return fail(h, DFD_ERR_STATE, "mtcnn: conv1+pool shape");
+                if ((rc = T("pool1", a1, 11 * 11, 32))) return rc;
                 if ((rc = gemm_conv_prelu(h, S->r2g, a1, a0, m, 11, 11))) return rc;                // 9, 64 ch (48 + 16 zero)
+                if ((rc = T("conv2", a0, 9 * 9, 64))) return rc;
                 launch_mt_maxpool(a0, a1, m, 9, 9, 64, 3, 2, s);                                    // 4
+                if ((rc = T("pool2", a1, 4 * 4, 64))) return rc;
                 if ((rc = gemm_conv_prelu(h, S->r3g, a1, a0, m, 4, 4))) return rc;                  // 3 -> [m][3][3][64]
+                if ((rc = T("conv3", a0, 3 * 3, 64))) return rc;
                 if ((rc = gemm_dense_prelu(h, S->r4, a0, a1, m))) return rc;                        // 576 -> 128
+                if ((rc = T("dense4", a1, 1, 128))) return rc;
                 launch_mt_heads(a1, S->r51.w, S->r51.b, S->r52.w, S->r52.b, pr, rg, m, 128, s);
             } else {
                 // conv1 (46) + PReLU + pool (23) in one launch
                 if (!launch_mt_conv1_pool(in, S->o1.w, S->o1.b, S->o1.a, a1, m, 48, 48, 32, s)) return fail(h, DFD_ERR_STATE, "mtcnn: conv1+pool shape");
+                if ((rc = T("pool1", a1, 23 * 23, 32))) return rc;
                 if ((rc = gemm_conv_prelu(h, S->o2g, a1, a0, m, 23, 23))) return rc;                // 21
+                if ((rc = T("conv2", a0, 21 * 21, 64))) return rc;
                 launch_mt_maxpool(a0, a1, m, 21, 21, 64, 3, 2, s);                                  // 10
+                if ((rc = T("pool2", a1, 10 * 10, 64))) return rc;
                 if ((rc = gemm_conv_prelu(h, S->o3g, a1, a0, m, 10, 10))) return rc;                // 8
+                if ((rc = T("conv3", a0, 8 * 8, 64))) return rc;
                 launch_mt_maxpool(a0, a1, m, 8, 8, 64, 2, 2, s);                                    // 4
+                if ((rc = T("pool3", a1, 4 * 4, 64))) return rc;
                 if ((rc = gemm_conv_prelu(h, S->o4g, a1, a0, m, 4, 4))) return rc;                  // 3 -> [m][3][3][128]
+                if ((rc = T("conv4", a0, 3 * 3, 128))) return rc;
                 if ((rc = gemm_dense_prelu(h, S->o5, a0, a1, m))) return rc;                        // 1152 -> 256
+                if ((rc = T("dense5", a1, 1, 256))) return rc;
                 launch_mt_heads(a1, S->o61.w, S->o61.b, S->o62.w, S->o62.b, pr, rg, m, 256, s);
                 // dense6_3 (landmarks) does not influence the boxes: evaluated only for callers that return landmarks
                 if (want_points) launch_mt_points(a1, S->o63.w, S->o63.b, (float*)S->pts.p + (size_t)start * 10, m, 256, s);
             }
             DFD_HIP_TRY(h, hipGetLastError());
+        }
+        if (tap_name) {
+            // parity taps of the outputs: the tap crop's rows of the FINAL arrays, after every chunk has run - what the
+            // box kernels and the host path read
+            const std::string net = onet ? "onet." : "rnet.";
+            if ((rc = tap_windows(net + "prob", (const float*)S->prob.p, 0, total, 1, 1))) return rc;
+            if ((rc = tap_windows(net + "reg", (const float*)S->reg.p, 0, total, 4, 1))) return rc;
+            if (onet && want_points && (rc = tap_windows(net + "pts", (const float*)S->pts.p, 0, total, 10, 1))) return rc;
         }
         return DFD_OK;
     }
@@ -659,8 +746,9 @@ struct Cascade {
         if ((rc = refine_gpu(onet, (const MtSrcWindow*)S->win.p, total))) return rc;
         const float* pp = (const float*)mailbox_d2h(h, S->prob.p, (size_t)total * 4);
         const float* rr = (const float*)mailbox_d2h(h, S->reg.p, (size_t)total * 16);
-        const float* qq = onet && want_points ? (const float*)mailbox_d2h(h, S->pts.p, (size_t)total * 40) : nullptr;
-        if (!pp || !rr || (onet && want_points && !qq)) return fail(h, DFD_ERR_HIP, "mtcnn: mailbox allocation failed");
+        const bool lm = onet && want_points && det;
+        const float* qq = lm ? (const float*)mailbox_d2h(h, S->pts.p, (size_t)total * 40) : nullptr;
+        if (!pp || !rr || (lm && !qq)) return fail(h, DFD_ERR_HIP, "mtcnn: mailbox allocation failed");
         DFD_HIP_TRY(h, hipGetLastError());
         DFD_HIP_TRY(h, stream_sync(h));
         prob->assign(pp, pp + total);
@@ -705,24 +793,16 @@ struct Cascade {
                     }
             }
             mark("host: windows");
-            if (!wins.empty() && (rc = refine(stage == 3, wins, &prob, &reg))) return rc;
-            mark("gpu: refine + download");
             std::vector<size_t> first(n + 1, 0);
             size_t pairs = 0;
             for (int c = 0; c < n; ++c) {
                 first[c + 1] = first[c] + live[c].size();
                 pairs += live[c].size() * live[c].size();
             }
-            if (!live[0].empty()) {
-                if (want(stage == 2 ? "rnet.prob" : "onet.prob")) {
-                    tap->assign(prob.begin(), prob.begin() + first[1]);
-                    tap_dims[0] = (int)first[1]; tap_dims[1] = 1; tap_dims[2] = 1;
-                }
-                if (want(stage == 2 ? "rnet.reg" : "onet.reg")) {
-                    tap->assign(reg.begin(), reg.begin() + first[1] * 4);
-                    tap_dims[0] = (int)first[1]; tap_dims[1] = 4; tap_dims[2] = 1;
-                }
-            }
+            tap_lo = (int)first[tap_crop];                       // parity taps: the tap crop's windows (refine_gpu)
+            tap_n = (int)live[tap_crop].size();
+            if (!wins.empty() && (rc = refine(stage == 3, wins, &prob, &reg))) return rc;
+            mark("gpu: refine + download");
             parallel_for(n, pairs, [&](int c) {
                 size_t k = first[c];
                 std::vector<Box> pass;
@@ -745,7 +825,7 @@ struct Cascade {
                 }
             });
             mark("host: threshold + NMS");
-            tap_boxes(stage == 2 ? "stage2" : "stage3", boxes[0]);
+            tap_boxes(stage == 2 ? "stage2" : "stage3", boxes[tap_crop]);
             if (verbose) {
                 size_t tot = 0;
                 for (auto& b : boxes) tot += b.size();
@@ -783,7 +863,7 @@ struct Cascade {
         int *first_a = counts + n, *first_b = first_a + n + 1, *meta = first_b + n + 1;
         MtRow *rows_a = (MtRow*)S->rows_a.p, *rows_b = (MtRow*)S->rows_b.p, *taprows = tap_name ? (MtRow*)S->taprows.p : nullptr;
         MtSrcWindow *wins_a = (MtSrcWindow*)S->wins_a.p, *wins_b = (MtSrcWindow*)S->wins_b.p;
-        // rows of crop 0 after a stage (parity taps): meta[2] of them at taprows
+        // rows of the tap crop after a stage (parity taps): meta[2] of them at taprows
         auto tap_stage = [&](const char* name, const int* meta_host) -> int {
             if (!want(name)) return DFD_OK;
             const int k = std::min(meta_host[2], kMtCap1);
@@ -794,22 +874,7 @@ struct Cascade {
             tap_dims[0] = k; tap_dims[1] = 5; tap_dims[2] = 1;
             return DFD_OK;
         };
-        // first_x[0 .. cnt) of crop 0: the network's outputs of its windows (parity taps)
-        auto tap_net = [&](const char* pname, const char* rname, int cnt0) -> int {
-            if (cnt0 <= 0) return DFD_OK;
-            if (want(pname)) {
-                int rc2 = download(S->prob.p, (size_t)cnt0, tap);
-                if (rc2) return rc2;
-                tap_dims[0] = cnt0; tap_dims[1] = 1; tap_dims[2] = 1;
-            }
-            if (want(rname)) {
-                int rc2 = download(S->reg.p, (size_t)cnt0 * 4, tap);
-                if (rc2) return rc2;
-                tap_dims[0] = cnt0; tap_dims[1] = 4; tap_dims[2] = 1;
-            }
-            return DFD_OK;
-        };
-        // the count words after a stage: {windows of all crops, overflow, rows of crop 0, windows of crop 0}
+        // the count words after a stage: {windows of all crops, overflow, rows of the tap crop, unused}
         auto read_meta = [&](int out[4]) -> int {
             const int* pm = (const int*)mailbox_d2h(h, meta, 16);
             if (!pm) return fail(h, DFD_ERR_HIP, "mtcnn: mailbox allocation failed");
@@ -822,10 +887,14 @@ struct Cascade {
         int m2 = 0, m3 = 0;
         if (!levels.empty()) {
             launch_mt_stage1_boxes(dcg, dlg, n, (const float*)S->prob.p, (const float*)S->reg.p, thr[0],
-                                   rows_a, wins_a, counts, meta, taprows, s);
+                                   rows_a, wins_a, counts, meta, taprows, tap_crop, s);
             launch_mt_compact(counts, n, dcg, nullptr, rows_a, wins_a, rows_b, wins_b, first_a, meta, s);
             if ((rc = read_meta(mh))) return rc;
             mark("s1 gpu: boxes + count");
+            if (want("boxes.overflow")) {                        // 1: a crop exceeds the device blocks - the host path takes over
+                tap->assign(1, mh[1] ? 1.f : 0.f);
+                tap_dims[0] = tap_dims[1] = tap_dims[2] = 1;
+            }
             if (mh[1]) {
                 if (verbose) fprintf(stderr, "[dfd] mtcnn: a crop exceeds the device box capacity - host path\n");
                 return DFD_OK;
@@ -839,10 +908,10 @@ struct Cascade {
         }
         if (verbose) fprintf(stderr, "[dfd] mtcnn %d crops (device boxes): stage 1 -> %d windows\n", n, m2);
         if (m2 > 0) {
+            if ((rc = tap_range(first_a))) return rc;
             if ((rc = refine_gpu(false, wins_b, m2))) return rc;
-            if ((rc = tap_net("rnet.prob", "rnet.reg", mh[3]))) return rc;
             launch_mt_refine_boxes(2, dcg, first_a, n, rows_b, (const float*)S->prob.p, (const float*)S->reg.p, thr[1], 0.7f, rows_a, wins_a,
-                                   counts, nullptr, nullptr, nullptr, taprows, meta, s);
+                                   counts, nullptr, nullptr, nullptr, taprows, tap_crop, meta, s);
             launch_mt_compact(counts, n, dcg, first_a, rows_a, wins_a, rows_b, wins_b, first_b, meta, s);
             if ((rc = read_meta(mh))) return rc;
             mark("s2 gpu: R-Net + boxes + count");
@@ -854,8 +923,8 @@ struct Cascade {
             tap_dims[0] = 0; tap_dims[1] = 5; tap_dims[2] = 1;
         }
         if (m3 > 0) {
+            if ((rc = tap_range(first_b))) return rc;
             if ((rc = refine_gpu(true, wins_b, m3))) return rc;
-            if ((rc = tap_net("onet.prob", "onet.reg", mh[3]))) return rc;
         }
         if (det) {
             // every row stage 3 keeps, at the crop's run of O-Net windows; with no window left the counts are all zero
@@ -864,7 +933,7 @@ struct Cascade {
             if (m3 > 0)
                 launch_mt_stage3_rows(dcg, first_b, n, rows_b, (const float*)S->prob.p, (const float*)S->reg.p,
                                       want_points ? (const float*)S->pts.p : nullptr, thr[2], 0.7f, (MtDetRow*)S->det_rows.p, counts,
-                                      taprows, meta, s);
+                                      taprows, tap_crop, meta, s);
             DFD_HIP_TRY(h, hipGetLastError());
             det_first = first_b;
             det_counts = counts;
@@ -873,7 +942,7 @@ struct Cascade {
         }
         // (with no window left first_b is all zero: every crop gets a zero-filled face and found = 0)
         launch_mt_refine_boxes(3, dcg, first_b, n, rows_b, (const float*)S->prob.p, (const float*)S->reg.p, thr[2], 0.7f, nullptr, nullptr,
-                               nullptr, (MtFaceJob*)S->bnd.p, (float*)S->res.p, (int*)S->coef.p, taprows, meta, s);
+                               nullptr, (MtFaceJob*)S->bnd.p, (float*)S->res.p, (int*)S->coef.p, taprows, tap_crop, meta, s);
         launch_mt_extract_faces((const MtFaceJob*)S->bnd.p, n, (const int*)S->coef.p, faces_out, (uint8_t*)S->tmp.p, s);
         DFD_HIP_TRY(h, hipGetLastError());
         const float* pr = (const float*)mailbox_d2h(h, S->res.p, (size_t)n * 8 * 4);
@@ -967,12 +1036,16 @@ int mtcnn_init(dfd_handle* h) {
 // crop written to faces_out + i * 160*160*3 (zero-filled when not found).  found = 0: no face passed the cascade,
 // or the selected box is degenerate (the package raises there and the reference call site returns None).
 int mtcnn_align_batch_device(dfd_handle* h, const MtImage* imgs, int n, uint8_t* faces_out, float* boxes_out, char* found,
-                             const char* tap_name, std::vector<float>* tap, int* tap_dims) {
+                             const char* tap_name, std::vector<float>* tap, int* tap_dims, int tap_crop) {
     MtcnnState* S = h->mtcnn;
     if (!S || !S->ready) return fail(h, DFD_ERR_STATE, "the weights blob holds no MTCNN cascade");
     for (int i = 0; i < n; ++i)
         if (imgs[i].h <= 0 || imgs[i].w <= 0) return fail(h, DFD_ERR_ARG, "mtcnn: empty image");
     Cascade c{h, S, imgs, n, tap_name, tap, tap_dims};
+    if (tap_name) {
+        c.tap_crop = tap_crop;
+        c.want_points = !strcmp(tap_name, "onet.pts");          // the landmark head runs only for callers that read it
+    }
     std::vector<std::vector<Box>> boxes;
     int rc;
     // box bookkeeping on the device unless DFD_MT_DEVICE_BOXES=0 (read per call: the tests switch it); a step that does
@@ -1226,20 +1299,94 @@ int dfd_mtcnn_extract(dfd_handle* h, int n_images, const uint8_t* const* bgr, co
     return mt_detect_call(h, n_images, bgr, heights, widths, strides, params, max_faces, boxes_out, landmarks_out, n_faces_out, faces_out, true);
 }
 
-int dfd_mtcnn_tap(dfd_handle* h, const uint8_t* bgr, int hh, int ww, int stride, const char* name, float* out,
-                  size_t capacity, size_t* count, int* dims) {
+// the named buffer of image `crop` of ONE batched cascade call over n images (the launches of the classify entry points)
+static int mt_tap_call(dfd_handle* h, int n, const uint8_t* const* bgr, const int* hs, const int* ws, const int* strides, int crop,
+                       const char* name, float* out, size_t capacity, size_t* count, int* dims, bool lenient) {
     if (!h) return DFD_ERR_ARG;
-    if (!name || !out || !count || !dims) return fail(h, DFD_ERR_ARG, "mtcnn_tap: null argument");
+    if (!name || !out || !count || !dims || !bgr || !hs || !ws || !strides) return fail(h, DFD_ERR_ARG, "mtcnn_tap: null argument");
+    if (n <= 0 || crop < 0 || crop >= n) return fail(h, DFD_ERR_ARG, "mtcnn_tap: crop %d of %d images", crop, n);
+    if (!h->mtcnn || !h->mtcnn->ready) return fail(h, DFD_ERR_STATE, "the weights blob holds no MTCNN cascade");
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!bgr[i] || hs[i] <= 0 || ws[i] <= 0 || strides[i] < ws[i] * 3) return fail(h, DFD_ERR_ARG, "mtcnn: bad pointer or geometry");
+        total += ((size_t)hs[i] * strides[i] + 255) & ~(size_t)255;
+    }
     DFD_HIP_TRY(h, hipSetDevice(h->device));
-    int rc = mt_upload(h, bgr, hh, ww, stride);
+    int rc = ensure(h, &h->frame_buf, total + 16);
     if (rc) return rc;
+    if ((rc = ensure(h, &h->mtcnn->face, (size_t)n * 160 * 160 * 3))) return rc;               // (u8 face slots of this call)
+    std::vector<MtImage> imgs(n);
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        uint8_t* dst = (uint8_t*)h->frame_buf.p + off;
+        DFD_HIP_TRY(h, hipMemcpyAsync(dst, bgr[i], (size_t)hs[i] * strides[i], hipMemcpyHostToDevice, h->stream));
+        imgs[i] = MtImage{dst, hs[i], ws[i], (size_t)strides[i]};
+        off += ((size_t)hs[i] * strides[i] + 255) & ~(size_t)255;
+    }
     std::vector<float> tap;
-    int found = 0;
+    std::vector<char> found(n, 0);
     dims[0] = dims[1] = dims[2] = -1;
-    float box[5];
-    if ((rc = mtcnn_align_device(h, (const uint8_t*)h->frame_buf.p, hh, ww, stride, box, &found, name, &tap, dims))) return rc;
+    if ((rc = mtcnn_align_batch_device(h, imgs.data(), n, (uint8_t*)h->mtcnn->face.p, nullptr, found.data(), name, &tap, dims, crop)))
+        return rc;
+    if (dims[0] < 0 && lenient && (!strncmp(name, "rnet.", 5) || !strncmp(name, "onet.", 5))) {
+        dims[0] = 0; dims[1] = dims[2] = 1;                      // no window reached that network
+        tap.clear();
+    }
     if (dims[0] < 0) return fail(h, DFD_ERR_ARG, "mtcnn_tap: no stage named '%s' for this image", name);
     if (tap.size() > capacity) return fail(h, DFD_ERR_ARG, "mtcnn_tap '%s' needs %zu floats, capacity %zu", name, tap.size(), capacity);
+    if (!tap.empty()) memcpy(out, tap.data(), tap.size() * 4);
+    *count = tap.size();
+    return DFD_OK;
+}
+
+int dfd_mtcnn_tap(dfd_handle* h, const uint8_t* bgr, int hh, int ww, int stride, const char* name, float* out,
+                  size_t capacity, size_t* count, int* dims) {
+    return mt_tap_call(h, 1, &bgr, &hh, &ww, &stride, 0, name, out, capacity, count, dims, false);
+}
+
+int dfd_mtcnn_tap_batch(dfd_handle* h, int n_images, const uint8_t* const* bgr, const int* heights, const int* widths,
+                        const int* strides, int crop, const char* name, float* out, size_t capacity, size_t* count, int* dims) {
+    return mt_tap_call(h, n_images, bgr, heights, widths, strides, crop, name, out, capacity, count, dims, true);
+}
+
+int dfd_mtcnn_net_tap(dfd_handle* h, int onet, const float* windows, const uint8_t* bgr, int hh, int ww, int stride, const int* xywh,
+                      int m, int row0, int rows, const char* name, float* out, size_t capacity, size_t* count, int* dims) {
+    if (!h) return DFD_ERR_ARG;
+    if ((!windows && !(bgr && xywh)) || !name || !out || !count || !dims) return fail(h, DFD_ERR_ARG, "mtcnn_net_tap: null argument");
+    if (m <= 0 || row0 < 0 || rows <= 0 || row0 > m - rows) return fail(h, DFD_ERR_ARG, "mtcnn_net_tap: rows [%d, +%d) of %d windows", row0, rows, m);
+    MtcnnState* S = h->mtcnn;
+    if (!S || !S->ready) return fail(h, DFD_ERR_STATE, "the weights blob holds no MTCNN cascade");
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    const int sz = onet ? 48 : 24;
+    std::vector<float> tap;
+    dims[0] = dims[1] = dims[2] = -1;
+    Cascade c{h, S, nullptr, 0, name, &tap, dims};
+    int rc;
+    const MtSrcWindow* wd = nullptr;
+    if (!windows) {                                              // source windows of an image, through the window resize
+        if ((rc = mt_upload(h, bgr, hh, ww, stride))) return rc;
+        std::vector<MtSrcWindow> wins(m);
+        for (int k = 0; k < m; ++k) {
+            const int* q = xywh + 4 * k;
+            if (q[0] < 0 || q[1] < 0 || q[2] <= 0 || q[3] <= 0 || q[0] > ww - q[2] || q[1] > hh - q[3])
+                return fail(h, DFD_ERR_ARG, "mtcnn_net_tap: window %d lies outside the image", k);
+            wins[k] = MtSrcWindow{(const uint8_t*)h->frame_buf.p, (long long)stride, q[0], q[1], q[2], q[3]};
+        }
+        if ((rc = c.upload(&S->win, wins))) return rc;
+        wd = (const MtSrcWindow*)S->win.p;
+    } else {
+        const size_t bytes = (size_t)m * sz * sz * 3 * 4;
+        if ((rc = ensure(h, &S->inject, bytes))) return rc;
+        DFD_HIP_TRY(h, hipMemcpyAsync(S->inject.p, windows, bytes, hipMemcpyHostToDevice, h->stream));
+        c.inject = (const float*)S->inject.p;
+    }
+    c.tap_lo = row0;
+    c.tap_n = rows;
+    c.want_points = onet != 0;
+    if ((rc = c.refine_gpu(onet != 0, wd, m))) return rc;
+    DFD_HIP_TRY(h, stream_sync(h));
+    if (dims[0] < 0) return fail(h, DFD_ERR_ARG, "mtcnn_net_tap: no buffer named '%s' in that network", name);
+    if (tap.size() > capacity) return fail(h, DFD_ERR_ARG, "mtcnn_net_tap '%s' needs %zu floats, capacity %zu", name, tap.size(), capacity);
     memcpy(out, tap.data(), tap.size() * 4);
     *count = tap.size();
     return DFD_OK;

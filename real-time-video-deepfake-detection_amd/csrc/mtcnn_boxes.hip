@@ -190,7 +190,7 @@ __device__ __forceinline__ bool window_of(float bx1, float by1, float bx2, float
 __global__ __launch_bounds__(kNT) void mt_stage1_boxes_kernel(const MtCropGeo* __restrict__ crops, const MtLevelGeo* __restrict__ levels,
                                                               const float* __restrict__ prob, const float* __restrict__ reg, float thr,
                                                               MtRow* __restrict__ rows_seg, MtSrcWindow* __restrict__ wins_seg,
-                                                              int* __restrict__ counts, int* __restrict__ meta, MtRow* __restrict__ tap_rows) {
+                                                              int* __restrict__ counts, int* __restrict__ meta, MtRow* __restrict__ tap_rows, int tap_c) {
     __shared__ u64 keys[kMtCap1];
     __shared__ ushort4 bx[kMtCap1];
     __shared__ unsigned short kept[kMtCap1];
@@ -266,7 +266,7 @@ __global__ __launch_bounds__(kNT) void mt_stage1_boxes_kernel(const MtCropGeo* _
             float nx1 = b.x + r.x * regw, ny1 = b.y + r.y * regh, nx2 = b.z + r.z * regw, ny2 = b.w + r.w * regh;
             rerec(nx1, ny1, nx2, ny2);
             row = MtRow{nx1, ny1, nx2, ny2, __uint_as_float(~(unsigned)(key >> 32))};
-            if (tap_rows && c == 0) tap_rows[idx] = row;
+            if (tap_rows && c == tap_c) tap_rows[idx] = row;
             win.src = cg.src; win.stride = cg.stride;
             valid = window_of(nx1, ny1, nx2, ny2, cg.w, cg.h, &win);
         }
@@ -281,7 +281,7 @@ __global__ __launch_bounds__(kNT) void mt_stage1_boxes_kernel(const MtCropGeo* _
     if (tid == 0) {
         if (nlive > kMtCap2) { atomicOr(&meta[1], 1); nlive = 0; }
         counts[c] = nlive;
-        if (c == 0) meta[2] = nk;
+        if (c == tap_c) meta[2] = nk;
     }
 }
 
@@ -309,7 +309,6 @@ __global__ __launch_bounds__(256) void mt_compact_kernel(const int* __restrict__
     }
     if (tid == 0) {
         first_out[c] = off;
-        if (c == 0) meta[3] = m;
         if (c == n - 1) {
             first_out[n] = off + m;
             meta[0] = off + m;
@@ -368,7 +367,7 @@ __global__ __launch_bounds__(kNT) void mt_refine_boxes_kernel(const MtCropGeo* _
                                                               int* __restrict__ counts, MtFaceJob* __restrict__ jobs,
                                                               float* __restrict__ results, int* __restrict__ tables,
                                                               MtRow* __restrict__ tap_rows, int* __restrict__ meta,
-                                                              const float* __restrict__ pts, MtDetRow* __restrict__ det_rows) {
+                                                              const float* __restrict__ pts, MtDetRow* __restrict__ det_rows, int tap_c) {
     __shared__ u64 keys[kMtCap2];
     __shared__ float4 bx[kMtCap2];
     __shared__ unsigned short kept[kMtCap2];
@@ -418,7 +417,7 @@ __global__ __launch_bounds__(kNT) void mt_refine_boxes_kernel(const MtCropGeo* _
                 bbreg(x1, y1, x2, y2, *reinterpret_cast<const float4*>(reg + (size_t)(lo + k) * 4));
                 rerec(x1, y1, x2, y2);
                 row = MtRow{x1, y1, x2, y2, __uint_as_float(~(unsigned)(keys[i] >> 32))};
-                if (tap_rows && c == 0) tap_rows[idx] = row;
+                if (tap_rows && c == tap_c) tap_rows[idx] = row;
                 win.src = cg.src; win.stride = cg.stride;
                 valid = window_of(x1, y1, x2, y2, cg.w, cg.h, &win);
             }
@@ -432,7 +431,7 @@ __global__ __launch_bounds__(kNT) void mt_refine_boxes_kernel(const MtCropGeo* _
         }
         if (tid == 0) {
             counts[c] = nlive;
-            if (c == 0) meta[2] = nk;
+            if (c == tap_c) meta[2] = nk;
         }
         return;
     }
@@ -448,24 +447,24 @@ __global__ __launch_bounds__(kNT) void mt_refine_boxes_kernel(const MtCropGeo* _
             if (pts)
                 for (int q = 0; q < 10; ++q) d.p[q] = pts[(size_t)(lo + k) * 10 + q];
             det_rows[lo + idx] = d;                                  // nk <= m: inside the crop's run of windows
-            if (tap_rows && c == 0) tap_rows[idx] = MtRow{b.x, b.y, b.z, b.w, d.score};
+            if (tap_rows && c == tap_c) tap_rows[idx] = MtRow{b.x, b.y, b.z, b.w, d.score};
         }
         if (tid == 0) {
             counts[c] = nk;
-            if (c == 0) meta[2] = nk;
+            if (c == tap_c) meta[2] = nk;
         }
         return;
     }
     // stage 3: rows in kept order; select_boxes(method="probability"): np.argsort(probs)[::-1][0] = the LAST row of the
     // highest probability; extract_face(margin 0) geometry; resize tables
-    if (tap_rows && c == 0)
+    if (tap_rows && c == tap_c)
         for (int idx = tid; idx < nk; idx += kNT) {
             const int i = kept[idx];
             const float4 b = bx[i];
             tap_rows[idx] = MtRow{b.x, b.y, b.z, b.w, __uint_as_float(~(unsigned)(keys[i] >> 32))};
         }
     if (tid == 0) {
-        if (c == 0) meta[2] = nk;
+        if (c == tap_c) meta[2] = nk;
         MtFaceJob j{cg.src, cg.stride, 0, 0, 160, 160, 0, 0, 0, 0, 0, 0, cg.tmp_off, 0};
         float* res = results + (size_t)c * 8;
         for (int k = 0; k < 8; ++k) res[k] = 0.f;
@@ -604,10 +603,10 @@ __global__ __launch_bounds__(256) void mt_select_kernel(const MtCropGeo* __restr
 }  // namespace
 
 void launch_mt_stage1_boxes(const MtCropGeo* crops, const MtLevelGeo* levels, int n, const float* prob, const float* reg, float thr,
-                            MtRow* rows_seg, MtSrcWindow* wins_seg, int* counts, int* meta, MtRow* tap_rows, hipStream_t s) {
+                            MtRow* rows_seg, MtSrcWindow* wins_seg, int* counts, int* meta, MtRow* tap_rows, int tap_crop, hipStream_t s) {
     if (n <= 0) return;
     hipLaunchKernelGGL(mt_stage1_boxes_kernel, dim3(n), dim3(kNT), 0, s, crops, levels, prob, reg, thr, rows_seg, wins_seg, counts, meta,
-                       tap_rows);
+                       tap_rows, tap_crop);
 }
 
 void launch_mt_compact(const int* counts, int n, const MtCropGeo* crops, const int* seg_first, const MtRow* rows_seg,
@@ -619,22 +618,22 @@ void launch_mt_compact(const int* counts, int n, const MtCropGeo* crops, const i
 
 void launch_mt_refine_boxes(int stage, const MtCropGeo* crops, const int* first, int n, const MtRow* rows_in, const float* prob,
                             const float* reg, float thr_p, float thr_nms, MtRow* rows_seg, MtSrcWindow* wins_seg, int* counts,
-                            MtFaceJob* jobs, float* results, int* tables, MtRow* tap_rows, int* meta, hipStream_t s) {
+                            MtFaceJob* jobs, float* results, int* tables, MtRow* tap_rows, int tap_crop, int* meta, hipStream_t s) {
     if (n <= 0) return;
     if (stage == 2)
         hipLaunchKernelGGL(mt_refine_boxes_kernel<2>, dim3(n), dim3(kNT), 0, s, crops, first, rows_in, prob, reg, thr_p, thr_nms, rows_seg,
-                           wins_seg, counts, jobs, results, tables, tap_rows, meta, nullptr, nullptr);
+                           wins_seg, counts, jobs, results, tables, tap_rows, meta, nullptr, nullptr, tap_crop);
     else
         hipLaunchKernelGGL(mt_refine_boxes_kernel<3>, dim3(n), dim3(kNT), 0, s, crops, first, rows_in, prob, reg, thr_p, thr_nms, rows_seg,
-                           wins_seg, counts, jobs, results, tables, tap_rows, meta, nullptr, nullptr);
+                           wins_seg, counts, jobs, results, tables, tap_rows, meta, nullptr, nullptr, tap_crop);
 }
 
 void launch_mt_stage3_rows(const MtCropGeo* crops, const int* first, int n, const MtRow* rows_in, const float* prob, const float* reg,
-                           const float* pts, float thr_p, float thr_nms, MtDetRow* det_rows, int* counts, MtRow* tap_rows, int* meta,
+                           const float* pts, float thr_p, float thr_nms, MtDetRow* det_rows, int* counts, MtRow* tap_rows, int tap_crop, int* meta,
                            hipStream_t s) {
     if (n <= 0) return;
     hipLaunchKernelGGL(mt_refine_boxes_kernel<4>, dim3(n), dim3(kNT), 0, s, crops, first, rows_in, prob, reg, thr_p, thr_nms, nullptr,
-                       nullptr, counts, nullptr, nullptr, nullptr, tap_rows, meta, pts, det_rows);
+                       nullptr, counts, nullptr, nullptr, nullptr, tap_rows, meta, pts, det_rows, tap_crop);
 }
 
 void launch_mt_select(const MtCropGeo* crops, const int* first, const int* counts, int n, const MtDetRow* rows, MtSelect sel,

@@ -73,17 +73,17 @@ constexpr int kMtCap2 = 4096;    // windows of one crop the stage-2 / stage-3 bl
 struct MtCropGeo { const uint8_t* src; long long stride; int h, w, level0, nlevels; long long seg_off; long long tmp_off; int tab_off, pad; };
 struct MtLevelGeo { long long cell_off; int oh, ow; float scale; int pad; };      // P-Net output grid of a level, first cell, (float) scale
 struct MtRow { float x1, y1, x2, y2, score; };
-// meta[0] = windows of all crops, meta[3] = windows of crop 0 (compact kernel), meta[1] = overflow flag (zeroed by the
-// caller), meta[2] = rows of crop 0
+// meta[0] = windows of all crops (compact kernel), meta[3] unused, meta[1] = overflow flag (zeroed by the
+// caller), meta[2] = rows of crop `tap_crop`, the crop whose rows go to tap_rows (parity taps; null in production)
 void launch_mt_stage1_boxes(const MtCropGeo* crops, const MtLevelGeo* levels, int n, const float* prob, const float* reg, float thr,
-                            MtRow* rows_seg, MtSrcWindow* wins_seg, int* counts, int* meta, MtRow* tap_rows, hipStream_t s);
+                            MtRow* rows_seg, MtSrcWindow* wins_seg, int* counts, int* meta, MtRow* tap_rows, int tap_crop, hipStream_t s);
 void launch_mt_compact(const int* counts, int n, const MtCropGeo* crops, const int* seg_first, const MtRow* rows_seg,
                        const MtSrcWindow* wins_seg, MtRow* rows_out, MtSrcWindow* wins_out, int* first_out, int* meta, hipStream_t s);
 // stage 2: R-Net prob / reg of the windows first[c] .. first[c + 1] -> rows / windows at first[c] of the segment arenas, counts;
 // stage 3: O-Net prob / reg -> jobs[c], results[c][8] = {found, has box, x1, y1, x2, y2, prob, 0}, resize tables
 void launch_mt_refine_boxes(int stage, const MtCropGeo* crops, const int* first, int n, const MtRow* rows_in, const float* prob,
                             const float* reg, float thr_p, float thr_nms, MtRow* rows_seg, MtSrcWindow* wins_seg, int* counts,
-                            MtFaceJob* jobs, float* results, int* tables, MtRow* tap_rows, int* meta, hipStream_t s);
+                            MtFaceJob* jobs, float* results, int* tables, MtRow* tap_rows, int tap_crop, int* meta, hipStream_t s);
 
 // ---- every face of an image (dfd_mtcnn_detect / dfd_mtcnn_extract)
 // a row that survived stage 3: regressed box + probability, the O-Net input box it came from, the raw landmark fractions
@@ -91,7 +91,7 @@ struct MtDetRow { float x1, y1, x2, y2, score; float in[4]; float p[10]; float p
 // stage 3 for all rows: O-Net prob / reg (and pts [window][10] or null) of the windows first[c] .. first[c + 1] -> the rows
 // kept by the "Min" NMS in its order at det_rows[first[c] ..], counts[c] of them
 void launch_mt_stage3_rows(const MtCropGeo* crops, const int* first, int n, const MtRow* rows_in, const float* prob, const float* reg,
-                           const float* pts, float thr_p, float thr_nms, MtDetRow* det_rows, int* counts, MtRow* tap_rows, int* meta,
+                           const float* pts, float thr_p, float thr_nms, MtDetRow* det_rows, int* counts, MtRow* tap_rows, int tap_crop, int* meta,
                            hipStream_t s);
 // order of the returned rows: 0 = as stage 3 yields them, 1 = probability, 2 = box area, 3 = area - 2 x squared offset from
 // the image centre, 4 = area among the rows above 0.9 probability; all descending, of equal keys the later stage-3 row first

@@ -180,10 +180,11 @@ def test_device_box_logic_equals_host_path(pkg, mt_handle, monkeypatch):
     assert not np.isnan(dev).all()
 
 
-def test_box_capacity_overflow_falls_back_to_the_host_path(pkg, mt_handle, monkeypatch):
-    """A crop with more P-Net candidates than a device block holds (the random-init cascade on a 700 x 900 crop: ~20 %
-    of ~100k cells) raises the overflow flag; the step then runs on the host path - same result as with the device
-    path switched off."""
+def test_largest_dense_crop_device_boxes_equal_host_path(pkg, mt_handle, monkeypatch):
+    """The largest dense crop of this file (the random-init cascade on a 700 x 900 crop, ~107k cells) gives the same
+    result with the device box path on and off.  Its 1,451 candidates stay below the device block's capacity: the case
+    that does raise the overflow flag and runs on the host path is
+    tests/test_mtcnn_stages_gpu.py::test_candidates_beyond_the_device_block_report_overflow."""
     bgr = _bgr(mt_images.textured(700, 900, 3))
     monkeypatch.setenv("DFD_MT_DEVICE_BOXES", "1")
     fd, bd = mt_handle.mtcnn_align(bgr)
