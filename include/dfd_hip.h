@@ -427,11 +427,17 @@ int dfd_decode_jpeg(dfd_handle* h, const uint8_t* jpeg, size_t len, uint8_t* bgr
 /* n JPEGs of ONE size -> n packed BGR frames [n][H][W][3] (bgr_out may be NULL: the frames stay on the device).  Round 4:
  * in a batch the scans of restart-less files are entropy-decoded ON THE DEVICE (csrc/jpeg_gpu_entropy.h: a lane per
  * 512-byte chunk of the de-stuffed scan, the host decoder's speculative-chunk scheme as a fixed-point iteration) - the
- * JPEG bytes cross PCIe instead of 6.2 MB of coefficients per 1080p frame.  Restart-interval files, files of differing
- * sampling, and any frame the device decoder's own checks do not vouch for go through the host decoder; the result is
- * the same bits either way (tests pin both to libjpeg).  Options: "jpeg_device_entropy" (default 2: from 1 MiB of scan data
- * per call - a small batch is quicker on the host pool; 1 = always; 0 = never), "jpeg_chunk_bytes" (default 512), "jpeg_rounds".  dfd_jpeg_decode_counts: frames of batch calls decoded
- * on the device / by the host decoder since dfd_create. */
+ * JPEG bytes cross PCIe instead of 6.2 MB of coefficients per 1080p frame.  Restart-interval files (unless option
+ * "jpeg_device_restart" is on), files of differing sampling, and any frame the device decoder's own checks do not vouch for
+ * go through the host decoder; the result is the same bits either way (tests pin both to libjpeg).  Options:
+ * "jpeg_device_entropy" (default 2: from 1 MiB of scan data per call - a small batch is quicker on the host pool; 1 =
+ * always; 0 = never), "jpeg_device_restart" (default 0: files with a restart interval (DRI) take the host decoder; 1: they
+ * are eligible for the device decoder under the "jpeg_device_entropy" rule like any other file, alone or mixed with
+ * restart-less files of the same size and sampling - every RSTn marker is a certain start state for the lanes; a file whose
+ * restart structure is malformed (marker missing, misnumbered or surplus) is still decoded by the host decoder, as are
+ * single-file calls; the environment variable DFD_JPEG_DEVICE_RESTART sets the value a new handle starts with),
+ * "jpeg_chunk_bytes" (default 512), "jpeg_rounds".  dfd_jpeg_decode_counts: frames of batch calls decoded on the device /
+ * by the host decoder since dfd_create (restart-interval frames decoded on the device count as device decodes). */
 int dfd_decode_jpeg_batch(dfd_handle* h, int n, const uint8_t* const* jpegs, const size_t* lens, uint8_t* bgr_out, size_t capacity,
                           int* height, int* width);
 int dfd_jpeg_decode_counts(const dfd_handle* h, unsigned long long* on_device, unsigned long long* on_host);
@@ -439,7 +445,8 @@ int dfd_jpeg_decode_counts(const dfd_handle* h, unsigned long long* on_device, u
  * memory, from dfd_host_alloc for full speed) are analysed `batch` at a time - the scans of chunk k + 1 cross PCIe on the
  * copy stream while chunk k is entropy-decoded on the device, turned into frames (IDCT, upsampling, colour) and run
  * through dfd_analyze_batch_device.  0.3 - 1.2 MB per 1080p frame over the link instead of 6.2 MB: the path that is not
- * bound by the raw upload.  DFD_ERR_UNSUPPORTED for files only the host decoder takes (restart intervals, mixed layouts).
+ * bound by the raw upload.  DFD_ERR_UNSUPPORTED for files only the host decoder takes (mixed layouts; restart intervals
+ * unless option "jpeg_device_restart" is 1).
  * Results as dfd_analyze_batch_device; height_out / width_out (may be NULL) receive the frame size. */
 int dfd_analyze_jpegs_host(dfd_handle* h, const uint8_t* const* jpegs, const size_t* lens, int n_total, int batch,
                            const int32_t* forced_xywh, int forced_k, float conf_thr, int max_faces, int apply_clahe, int with_forensics,

@@ -1,5 +1,7 @@
 """Device entropy decoder (csrc/jpeg_gpu_entropy.h): time of dfd_decode_jpeg_batch for 64 x 1080p frames and the lanes
-that decode per round (DFD_JPEG_VERBOSE=1 prints them).  env: JP_N (frames, default 64), JP_KIND (noise | natural)."""
+that decode per round (DFD_JPEG_VERBOSE=1 prints them).  env: JP_N (frames, default 64), JP_KIND (noise | natural),
+JP_RESTART (rows:K | blocks:K: the files carry restart markers every K MCU rows / MCUs),
+JP_DEVICE_RESTART (1: option "jpeg_device_restart" on - such files on the device; 0, the default: on the host pool)."""
 import io, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -12,14 +14,20 @@ n = int(os.environ.get("JP_N", "64"))
 kind = os.environ.get("JP_KIND", "noise")
 W = rtdfd_amd.weights
 h = rtdfd_amd._lib.Handle(W.pack_b0(W.seeded_state_dict(0)), device=0, max_batch=8)
+if "JP_DEVICE_RESTART" in os.environ:
+    h.set_option("jpeg_device_restart", int(os.environ["JP_DEVICE_RESTART"]))
+save_kw = {}
+if os.environ.get("JP_RESTART"):
+    unit, k = os.environ["JP_RESTART"].split(":")
+    save_kw = {"restart_marker_rows" if unit == "rows" else "restart_marker_blocks": int(k)}
 datas = []
 for i in range(min(n, 8)):
     fr = np.random.default_rng(7 + i).integers(50, 200, (1080, 1920, 3), dtype=np.uint8) if kind == "noise" else F.natural_like(1080, 1920, seed=9 + i)
     buf = io.BytesIO()
-    Image.fromarray(np.ascontiguousarray(fr[..., ::-1])).save(buf, format="JPEG", quality=85)
+    Image.fromarray(np.ascontiguousarray(fr[..., ::-1])).save(buf, format="JPEG", quality=85, **save_kw)
     datas.append(buf.getvalue())
 datas = [datas[i % len(datas)] for i in range(n)]
-print(kind, "frames", n, "bytes per frame", [len(d) for d in datas[:4]], flush=True)
+print(kind, save_kw, "frames", n, "bytes per frame", [len(d) for d in datas[:4]], flush=True)
 for chunk in [int(c) for c in os.environ.get("JP_CHUNKS", "512,1024,2048").split(",")]:
     h.set_option("jpeg_chunk_bytes", chunk)
     for rounds in [int(c) for c in os.environ.get("JP_ROUNDS", "16,8").split(",")]:

@@ -4,8 +4,10 @@
 //   host   markers, Huffman tables and the entropy-coded segment -> quantised coefficients, int16, block-major per
 //          component (jpeg_entropy.h: speculative chunks on the host pool).  Round 4: for a BATCH of restart-less files
 //          the scan is decoded on the device instead (jpeg_gpu_entropy.h: a lane per 512-byte chunk) - the JPEG bytes
-//          cross PCIe, not 6.2 MB of coefficients per 1080p frame; the host decoder remains the path of single files,
-//          of restart-interval files and of any frame the device decoder's own checks reject;
+//          cross PCIe, not 6.2 MB of coefficients per 1080p frame; with option "jpeg_device_restart" = 1 files with
+//          restart intervals take that path too (every RSTn marker a certain start state).  The host decoder remains the
+//          path of single files, of restart-interval files while that option is off (the default), and of any frame the
+//          device decoder's own checks reject (a malformed restart structure among them);
 //   device dequantisation + jidctint.c (one thread per 8x8 block), then per output pixel h2v2 / h2v1 "fancy"
 //          (triangle) chroma upsampling + YCbCr -> RGB in libjpeg's 16-bit fixed point - the kernels of the ELA
 //          round trip (forensic_kernels.hip) generalised to any image size - written as packed BGR where
@@ -362,22 +364,25 @@ int jpeg_decode_to_frame(dfd_handle* h, const uint8_t* jpeg, size_t len, int* hh
 static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct JpegGpuLayout {
-    size_t ds, frames, tabs, blkmap, cblkmap, removed, st, en0, en1, cnt, dcs, gfirst, dcb, err, redone, coef, planes, q, total;
-    size_t ds_bytes, nchunks, ndsblk, ncblk, coef_stride, plane_stride;
+    size_t ds, frames, tabs, blkmap, cblkmap, removed, markers, segtab, st, en0, en1, cnt, dcs, gfirst, dcb, err, rs, redone, coef, planes, q, total;
+    size_t ds_bytes, nchunks, ndsblk, ncblk, nsegtab, coef_stride, plane_stride;
+    bool any_restart;                            // a file of the batch has a restart interval: the RST = true kernels
 };
 
 static JpegGpuLayout jpeg_gpu_layout(const std::vector<Parsed>& P, const std::vector<ScanLayout>& L, const uint32_t* raw_len, int n,
                                      int chunk_bytes) {
     JpegGpuLayout W{};
-    size_t ds = 0, chunks = 0, dsblk = 0, cblk = 0;
+    size_t ds = 0, chunks = 0, dsblk = 0, cblk = 0, segs = 0;
     for (int i = 0; i < n; ++i) {
         const size_t nc = ((size_t)raw_len[i] + chunk_bytes - 1) / chunk_bytes;
+        segs += jg_segments(P[i], L[i]) - 1;                        // one table entry per RSTn marker the header promises
+        if (P[i].restart) W.any_restart = true;
         ds += ((nc + JG_CB - 1) / JG_CB * JG_CB + 64) * (size_t)chunk_bytes;      // chunk-interleaved image: whole groups of 64 chunks + one
         cblk += (nc + JG_CB - 1) / JG_CB;
         chunks += (nc + JG_CB - 1) / JG_CB * JG_CB;
         dsblk += ((size_t)raw_len[i] + 15 + JG_DS_BLOCK - 1) / JG_DS_BLOCK;      // (+ up to 15 bytes in front of an unaligned scan)
     }
-    W.ds_bytes = ds; W.nchunks = chunks; W.ndsblk = dsblk; W.ncblk = cblk;
+    W.ds_bytes = ds; W.nchunks = chunks; W.ndsblk = dsblk; W.ncblk = cblk; W.nsegtab = segs;
     size_t plane_total = 0;
     for (int c = 0; c < P[0].ncomp; ++c) plane_total += al256((size_t)P[0].comp[c].bw * 8 * P[0].comp[c].bh * 8);
     W.coef_stride = al256(L[0].total * 64 * 2) / 2;               // int16 elements
@@ -390,8 +395,11 @@ static JpegGpuLayout jpeg_gpu_layout(const std::vector<Parsed>& P, const std::ve
     W.blkmap = take(2 * dsblk);
     W.cblkmap = take(2 * cblk);
     W.removed = take(4 * dsblk);
+    W.markers = take(4 * dsblk);
+    W.segtab = take(4 * segs + 4);
     W.st = take(8 * chunks); W.en0 = take(8 * chunks); W.en1 = take(8 * chunks);
     W.cnt = take(4 * chunks); W.dcs = take(12 * chunks); W.gfirst = take(4 * chunks); W.dcb = take(12 * chunks); W.err = take(chunks);
+    W.rs = take(8 * chunks);
     W.redone = take(4 * JG_MAX_ROUNDS);
     W.coef = take(W.coef_stride * 2 * (size_t)n);
     W.planes = take(plane_total * (size_t)n);
@@ -408,7 +416,7 @@ static bool jpeg_gpu_batch_ok(const dfd_handle* h, const std::vector<Parsed>& P,
     for (int i = 0; i < n; ++i) scan_total += (size_t)(P[i].end - P[i].scan) + 65536 + 64 * (size_t)h->jpeg_chunk_bytes;
     if (scan_total >= ((size_t)1 << 31) || (size_t)n * (L[0].total * 64 + 256) >= ((size_t)1 << 31)) return false;
     for (int i = 0; i < n; ++i) {
-        if (!jg_supported(P[i], L[i])) return false;
+        if (!jg_supported(P[i], L[i], h->jpeg_device_restart != 0)) return false;
         if (P[i].ncomp != P[0].ncomp || P[i].hmax != P[0].hmax || P[i].vmax != P[0].vmax || P[i].width != P[0].width ||
             P[i].height != P[0].height)
             return false;
@@ -513,7 +521,7 @@ struct JpegGpuJob {
         sp += al256((size_t)n * 192 * 2);
         redone_h = reinterpret_cast<uint32_t*>(sp);
         int nsets = 0;
-        size_t ds = 0, dsblk = 0, cblk = 0;
+        size_t ds = 0, dsblk = 0, cblk = 0, segs = 0;
         chunks = 0;
         on_host.assign(n, 0);
         for (int i = 0; i < n; ++i) {
@@ -537,6 +545,8 @@ struct JpegGpuJob {
             for (int c = 0; c < PP[i].ncomp; ++c) {
                 F.comp_h[c] = PP[i].comp[c].h; F.comp_v[c] = PP[i].comp[c].v; F.comp_bw[c] = LL[i].bw[c]; F.comp_off[c] = (uint32_t)LL[i].comp_off[c];
             }
+            F.restart = (uint32_t)PP[i].restart; F.nseg = jg_segments(PP[i], LL[i]); F.seg_off = (uint32_t)segs;
+            segs += F.nseg - 1;
             F.marker_pos = 0xffffffffu;
             // the device image of the tables is built once per run of frames that share them (a stream's frames usually do)
             if (i > 0 && !on_host[i - 1] && jpeg_same_tables(PP[i], LL[i], PP[i - 1], LL[i - 1])) {
@@ -575,20 +585,35 @@ struct JpegGpuJob {
         S.gfirst = reinterpret_cast<uint32_t*>(work + W.gfirst);
         S.dcb = reinterpret_cast<int32_t*>(work + W.dcb);
         S.err = work + W.err;
+        S.rs = reinterpret_cast<uint2*>(work + W.rs);
         S.redone = reinterpret_cast<uint32_t*>(work + W.redone);
         DFD_HIP_TRY(h, hipMemsetAsync(S.redone, 0, 4 * JG_MAX_ROUNDS, s));
         rounds = h->jpeg_rounds < 2 ? 2 : (h->jpeg_rounds > JG_MAX_ROUNDS ? JG_MAX_ROUNDS : h->jpeg_rounds);
         uint8_t* dsd = work + W.ds;
         uint32_t* removed = reinterpret_cast<uint32_t*>(work + W.removed);
+        uint32_t* markers = reinterpret_cast<uint32_t*>(work + W.markers);
+        uint32_t* segtab = reinterpret_cast<uint32_t*>(work + W.segtab);
+        // a batch without restart-interval files runs the RST = false instantiations: the kernels of the restart-less decoder
+        const bool rst = W.any_restart;
         if (dsblk) {
-            hipLaunchKernelGGL(jg_count_kernel, dim3((unsigned)dsblk), dim3(JG_DS_THREADS), 0, s, raw_dev, Fd, bmd, removed);
-            hipLaunchKernelGGL(jg_compact_kernel, dim3((unsigned)dsblk), dim3(JG_DS_THREADS), 0, s, raw_dev, dsd, Fd, bmd, removed);
+            if (rst) {
+                hipLaunchKernelGGL(jg_count_kernel<true>, dim3((unsigned)dsblk), dim3(JG_DS_THREADS), 0, s, raw_dev, Fd, bmd, removed, markers);
+                hipLaunchKernelGGL(jg_compact_kernel<true>, dim3((unsigned)dsblk), dim3(JG_DS_THREADS), 0, s, raw_dev, dsd, Fd, bmd, removed,
+                                   markers, segtab);
+            } else {
+                hipLaunchKernelGGL(jg_count_kernel<false>, dim3((unsigned)dsblk), dim3(JG_DS_THREADS), 0, s, raw_dev, Fd, bmd, removed, markers);
+                hipLaunchKernelGGL(jg_compact_kernel<false>, dim3((unsigned)dsblk), dim3(JG_DS_THREADS), 0, s, raw_dev, dsd, Fd, bmd, removed,
+                                   markers, segtab);
+            }
         }
         if (cblk) {
-            for (int r = 0; r < rounds; ++r)
-                hipLaunchKernelGGL(jg_round_kernel, dim3((unsigned)cblk), dim3(JG_CB), 0, s, dsd, Fd, Td, cmd, S, r);
-            hipLaunchKernelGGL(jg_scan_kernel, dim3(n), dim3(1024), 0, s, Fd, S, rounds - 1);
-            hipLaunchKernelGGL(jg_emit_kernel, dim3((unsigned)cblk), dim3(JG_CB), 0, s, dsd, Fd, Td, cmd, S, coef);
+            for (int r = 0; r < rounds; ++r) {
+                if (rst) hipLaunchKernelGGL(jg_round_kernel<true>, dim3((unsigned)cblk), dim3(JG_CB), 0, s, dsd, Fd, Td, cmd, S, r, segtab);
+                else hipLaunchKernelGGL(jg_round_kernel<false>, dim3((unsigned)cblk), dim3(JG_CB), 0, s, dsd, Fd, Td, cmd, S, r, segtab);
+            }
+            hipLaunchKernelGGL(jg_scan_kernel, dim3(n), dim3(1024), 0, s, Fd, S, rounds - 1, segtab);
+            if (rst) hipLaunchKernelGGL(jg_emit_kernel<true>, dim3((unsigned)cblk), dim3(JG_CB), 0, s, dsd, Fd, Td, cmd, S, coef, segtab);
+            else hipLaunchKernelGGL(jg_emit_kernel<false>, dim3((unsigned)cblk), dim3(JG_CB), 0, s, dsd, Fd, Td, cmd, S, coef, segtab);
         }
         DFD_HIP_TRY(h, hipMemcpyAsync(Fback, Fd, sizeof(JgFrame) * (size_t)n, hipMemcpyDeviceToHost, s));
         DFD_HIP_TRY(h, hipMemcpyAsync(redone_h, S.redone, 4 * JG_MAX_ROUNDS, hipMemcpyDeviceToHost, s));
@@ -600,7 +625,8 @@ struct JpegGpuJob {
         std::vector<Parsed>& PP = *P;
         const std::vector<ScanLayout>& LL = *L;
         if (getenv("DFD_JPEG_VERBOSE")) {
-            fprintf(stderr, "[dfd] jpeg device entropy: %d frames, %zu chunks of %d bytes, lanes decoding per round:", n, chunks, chunk_bytes);
+            fprintf(stderr, "[dfd] jpeg device entropy: %d frames%s, %zu chunks of %d bytes, lanes decoding per round:", n,
+                    W.any_restart ? " (restart intervals)" : "", chunks, chunk_bytes);
             for (int r = 0; r < rounds; ++r) fprintf(stderr, " %u", redone_h[r]);
             fprintf(stderr, "\n");
         }
@@ -608,8 +634,10 @@ struct JpegGpuJob {
         for (int i = 0; i < n; ++i) {
             if (!on_host[i] && Fback[i].status == JG_OK) continue;
             if (getenv("DFD_JPEG_VERBOSE"))
-                fprintf(stderr, "[dfd] jpeg device entropy: frame %d status %d (%u of %d blocks, %u payload bits) -> host decoder\n", i,
-                        on_host[i] ? -1 : Fback[i].status, Fback[i].blocks_found, Fh[i].total_blocks, Fback[i].nbits);
+                fprintf(stderr,
+                        "[dfd] jpeg device entropy: frame %d status %d (%s; %u of %d blocks, %u payload bits, %u of %u restart markers) -> host decoder\n",
+                        i, on_host[i] ? -1 : Fback[i].status, jg_status_name(on_host[i] ? -1 : Fback[i].status), Fback[i].blocks_found,
+                        Fh[i].total_blocks, Fback[i].nbits, Fback[i].nmark, Fh[i].nseg - 1);
             std::vector<int16_t> tmp;
             try {
                 tmp.resize(LL[i].total * 64);
@@ -732,7 +760,8 @@ int dfd_jpeg_coefficients(const uint8_t* jpeg, size_t len, int* info, uint16_t* 
 }
 
 // n JPEGs of one size -> n packed BGR frames (the batch path of dfd_analyze_stream_batch / dfd_analyze_jpegs_host on its
-// own: with the default options the scans of restart-less files are entropy-decoded on the device)
+// own: with the default options the scans of restart-less files are entropy-decoded on the device; option
+// "jpeg_device_restart" = 1 adds files with restart intervals)
 int dfd_decode_jpeg_batch(dfd_handle* h, int n, const uint8_t* const* jpegs, const size_t* lens, uint8_t* bgr_out, size_t capacity,
                           int* height, int* width) {
     if (!h) return DFD_ERR_ARG;
@@ -757,8 +786,9 @@ int dfd_decode_jpeg_batch(dfd_handle* h, int n, const uint8_t* const* jpegs, con
 // the files crossing the link instead of raw frames (dfd_analyze_frames_host moves 6.2 MB per 1080p frame and is bound by
 // the upload: 9.2 k frames/s).  n_total files of ONE size and sampling, `batch` at a time: the scans of chunk k + 1 are
 // copied to the device on the copy stream while chunk k is entropy-decoded (jpeg_gpu_entropy.h), turned into frames and
-// analysed on the compute stream.  Results as dfd_analyze_batch_device.  Files the device decoder cannot take (restart
-// intervals, mixed layouts) make the call fail with DFD_ERR_UNSUPPORTED - decode those with dfd_decode_jpeg_batch.
+// analysed on the compute stream.  Results as dfd_analyze_batch_device.  Files the device decoder cannot take (mixed
+// layouts; restart intervals unless option "jpeg_device_restart" is 1) make the call fail with DFD_ERR_UNSUPPORTED -
+// decode those with dfd_decode_jpeg_batch.
 int dfd_analyze_jpegs_host(dfd_handle* h, const uint8_t* const* jpegs, const size_t* lens, int n_total, int batch,
                            const int32_t* forced_xywh, int forced_k, float conf_thr, int max_faces, int apply_clahe, int with_forensics,
                            int32_t* xywh_out, int* n_faces_out, float* logits_out, double* forensic_prob_out, int* height_out,

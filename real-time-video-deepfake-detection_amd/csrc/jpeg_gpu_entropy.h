@@ -22,8 +22,27 @@
 // Decoding work: three passes over the scan instead of one, on ~2,400 lanes per 1080p frame.  The result does not depend
 // on the chunk size or the number of rounds (tests: equal to the host decoder's coefficients, i.e. pinned to libjpeg
 // through the oracle's IDCT, and the decoded frames equal Pillow's bit for bit).
-// Restart-interval files, more than four distinct Huffman tables and anything the header parser rejects stay on the host
-// path.  Included by jpeg_decode.hip (shares Parsed / ScanLayout / HuffTable with the host decoder).
+//
+// RESTART INTERVALS (option "jpeg_device_restart", kernels instantiated with RST = true; a batch without such a file runs
+// the RST = false instantiations, which are the code above and nothing else).  An RSTn marker is byte aligned, resets the
+// DC predictions and begins at a block index known from the header (segment k: block k * restart * blocks per MCU) - a
+// start state that is CERTAIN where the chunk grid has to guess:
+//   * de-stuffing removes FF D0..D7 like a stuffed zero (two bytes) and records marker k as seg[k] = (de-stuffed byte
+//     offset of the byte behind it) << 3 | n: the bit position of segment k + 1, the marker's number in the low bits.
+//     The table holds nseg - 1 entries (nseg from the header); a marker beyond that is counted, never written;
+//   * a lane knows the next segment start behind its position (binary search at its start).  When a block completes
+//     inside the last byte in front of it - or the decode of a mis-speculated lane has run past it - the lane continues AT
+//     that position with slot 0 and DC predictions 0, and what it decodes from there is the true decode.  Chunk grid and
+//     memory layout are unchanged.  The RST round kernel also iterates INSIDE a launch over the 256 consecutive chunks of
+//     its block (jg_round_kernel): two launches reach the fixed point that took one launch per chunk of propagation.  Per chunk the counting pass also records the first crossing (blocks in front of it,
+//     segment index) and sums the DC differences since the LAST crossing: the DC prefix of jg_scan_kernel is a segmented
+//     scan, the block prefix a plain one (block indices run on across segments);
+//   * checked besides the fixed point: every crossing happens at block k * restart * bpm (first crossing of a chunk:
+//     against its block prefix; later ones: exactly restart * bpm blocks since the one before), nseg - 1 markers, marker
+//     k numbered k mod 8.  A frame that fails is JG_RESTART and goes to the host decoder like any other.
+// More than four distinct Huffman tables, a malformed restart structure and anything the header parser rejects stay on
+// the host path; so do restart-interval files while the option is off (the default).  Included by jpeg_decode.hip
+// (shares Parsed / ScanLayout / HuffTable with the host decoder).
 #pragma once
 
 namespace dfd_jpeg_gpu {
@@ -56,13 +75,19 @@ struct JgFrame {
     uint8_t slot_comp[8], slot_bx[8], slot_by[8], slot_dc[8], slot_ac[8];
     int32_t comp_h[3], comp_v[3], comp_bw[3];
     uint32_t comp_off[3];
+    uint32_t restart, nseg, seg_off;             // restart interval in MCUs (0: none), its segments, the frame's first entry in the segment table
     // written by the device
     uint32_t marker_pos;                         // raw offset of the first marker (0xffffffff before jg_count_kernel)
     uint32_t nbits;                              // payload bits of the de-stuffed scan
     int32_t status;                              // 0 = decoded; else why not (JgStatus)
     uint32_t blocks_found;
+    uint32_t nmark;                              // RSTn markers in front of marker_pos (the table holds the first nseg - 1)
 };
-enum JgStatus { JG_OK = 0, JG_NOT_CONVERGED = 1, JG_BLOCK_COUNT = 2, JG_BAD_CODE = 3, JG_SLOT = 4 };
+enum JgStatus { JG_OK = 0, JG_NOT_CONVERGED = 1, JG_BLOCK_COUNT = 2, JG_BAD_CODE = 3, JG_SLOT = 4, JG_RESTART = 5 };
+inline const char* jg_status_name(int st) {
+    static const char* const names[] = {"ok", "not converged", "block count", "bad code", "slot", "restart structure"};
+    return st < 0 ? "huffman tables" : (st <= JG_RESTART ? names[st] : "?");
+}
 
 struct JgChunks {                                // per chunk, structure of arrays
     uint2* st;                                   // start state (bit position, slot)
@@ -72,6 +97,8 @@ struct JgChunks {                                // per chunk, structure of arra
     uint32_t* gfirst;                            // first block index (scan kernel)
     int32_t* dcb;                                // [3] DC prediction at the chunk's first block
     uint8_t* err;                                // the chunk's decode met an invalid code / coefficient index
+    uint2* rs;                                   // RST: x = blocks in front of the chunk's first segment crossing | crossed << 31 | a whole
+                                                 // segment of another length than restart * bpm << 30, y = index of the segment entered there
     uint32_t* redone;                            // [JG_MAX_ROUNDS] lanes that decoded in round r (diagnostics)
 };
 
@@ -88,9 +115,15 @@ __host__ __device__ __forceinline__ uint32_t jg_dword_at(uint32_t g, int cw_shif
 // ---------------------------------------------------------------------------------------------- de-stuffing
 // piece q of a block = its bytes [16 q, 16 q + 16): thread t takes the pieces t, t + 256, ... (coalesced 16-byte loads)
 // (positions in [lead, raw_len) are the scan; a piece may start in front of it)
+// RST (and the frame has a restart interval, `rst`): FF D0..D7 does not end the data - BOTH bytes are removed, each
+// counted where it lies (the FF needs the byte behind it: `next` = the first byte of the following piece), and the
+// marker is counted where its Dn lies.  A marker may straddle two pieces or two blocks: `prev` / `next` carry it.
+__device__ __forceinline__ bool jg_is_rst(uint8_t v) { return (v & 0xF8u) == 0xD0u; }
+
+template <bool RST>
 __device__ __forceinline__ void jg_piece_scan(uint32_t lead, uint32_t raw_len, uint32_t pos0, const uint8_t (&b)[16], uint8_t prev,
-                                              int* removed, uint32_t* marker) {
-    int rem = 0;
+                                              uint8_t next, bool rst, int* removed, int* markers, uint32_t* marker) {
+    int rem = 0, nmk = 0;
     uint32_t mk = 0xffffffffu;
     uint8_t p = prev;
 #pragma unroll
@@ -100,25 +133,35 @@ __device__ __forceinline__ void jg_piece_scan(uint32_t lead, uint32_t raw_len, u
         if (pos >= lead && pos < raw_len) {
             if (p == 0xFF) {
                 if (b[i] == 0) ++rem;
+                else if (RST && rst && jg_is_rst(b[i])) { ++rem; ++nmk; }
                 else if (mk == 0xffffffffu) mk = pos - 1;
+            }
+            if constexpr (RST) {
+                const uint8_t nb = i < 15 ? b[i < 15 ? i + 1 : 15] : next;
+                if (rst && b[i] == 0xFF && pos + 1 < raw_len && jg_is_rst(nb)) ++rem;   // the FF of a marker
             }
             if (pos + 1 == raw_len && b[i] == 0xFF && mk == 0xffffffffu) mk = pos;   // an FF as the very last byte ends the data too
         }
         p = b[i];
     }
     *removed = rem;
+    *markers = nmk;
     *marker = mk;
 }
 
+template <bool RST>
 __global__ __launch_bounds__(JG_DS_THREADS) void jg_count_kernel(const uint8_t* __restrict__ raw, JgFrame* __restrict__ F,
-                                                                 const uint16_t* __restrict__ blk_frame, uint32_t* __restrict__ blk_removed) {
+                                                                 const uint16_t* __restrict__ blk_frame, uint32_t* __restrict__ blk_removed,
+                                                                 uint32_t* __restrict__ blk_markers) {
     __shared__ int red[JG_DS_THREADS / 64];
+    __shared__ int redm[JG_DS_THREADS / 64];
     const int f = blk_frame[blockIdx.x], tid = threadIdx.x;
     // positions count from the 16-byte boundary in front of the scan: its bytes are [lead, lead + raw_len)
     const uint32_t lead = F[f].raw_off & 15u, raw_len = F[f].raw_len + lead;
     const uint32_t base = (blockIdx.x - F[f].dsblk0) * (uint32_t)JG_DS_BLOCK;
     const uint8_t* scan = raw + (F[f].raw_off - lead);
-    int total = 0;
+    const bool rst = RST && F[f].restart != 0;
+    int total = 0, totalm = 0;
     uint32_t mk = 0xffffffffu;
 #pragma unroll
     for (int i = 0; i < JG_DS_PIECES; ++i) {
@@ -127,69 +170,99 @@ __global__ __launch_bounds__(JG_DS_THREADS) void jg_count_kernel(const uint8_t* 
         const uint4 v = pos0 < raw_len ? *reinterpret_cast<const uint4*>(scan + pos0) : make_uint4(0, 0, 0, 0);   // (capacity is padded)
         memcpy(b, &v, 16);
         const uint8_t prev = pos0 > lead && pos0 <= raw_len ? scan[pos0 - 1] : 0;
-        int rem;
+        uint8_t next = 0;
+        if constexpr (RST) next = pos0 + 16 < raw_len ? scan[pos0 + 16] : 0;
+        int rem, nmk;
         uint32_t m;
-        jg_piece_scan(lead, raw_len, pos0, b, prev, &rem, &m);
+        jg_piece_scan<RST>(lead, raw_len, pos0, b, prev, next, rst, &rem, &nmk, &m);
         total += rem;
+        totalm += nmk;
         mk = m < mk ? m : mk;
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         total += __shfl_xor(total, off);
+        if constexpr (RST) totalm += __shfl_xor(totalm, off);
         const uint32_t o = __shfl_xor(mk, off);
         mk = o < mk ? o : mk;
     }
     if ((tid & 63) == 0) {
         red[tid >> 6] = total;
+        if constexpr (RST) redm[tid >> 6] = totalm;
         if (mk != 0xffffffffu) atomicMin(&F[f].marker_pos, mk);
     }
     __syncthreads();
     if (tid == 0) {
-        int s = 0;
-        for (int w = 0; w < JG_DS_THREADS / 64; ++w) s += red[w];
+        int s = 0, sm = 0;
+        for (int w = 0; w < JG_DS_THREADS / 64; ++w) {
+            s += red[w];
+            if constexpr (RST) sm += redm[w];
+        }
         blk_removed[blockIdx.x] = (uint32_t)s;
+        if constexpr (RST) blk_markers[blockIdx.x] = (uint32_t)sm;
     }
 }
 
+// (RST: the per-piece counts travel through the block's prefix as ONE integer, removed bytes | markers << 16 - at most
+// 16,384 and 8,192 per block)
+template <bool RST>
 __global__ __launch_bounds__(JG_DS_THREADS) void jg_compact_kernel(const uint8_t* __restrict__ raw, uint8_t* __restrict__ ds,
                                                                    JgFrame* __restrict__ F, const uint16_t* __restrict__ blk_frame,
-                                                                   const uint32_t* __restrict__ blk_removed) {
-    __shared__ int cnt[JG_DS_THREADS * JG_DS_PIECES];            // stuffed zeros per piece, then their exclusive prefix
+                                                                   const uint32_t* __restrict__ blk_removed,
+                                                                   const uint32_t* __restrict__ blk_markers, uint32_t* __restrict__ segtab) {
+    __shared__ int cnt[JG_DS_THREADS * JG_DS_PIECES];            // removed bytes per piece, then their exclusive prefix
     __shared__ int wsum[JG_DS_THREADS / 64 + 1];
-    __shared__ int before;
+    __shared__ int wsumm[JG_DS_THREADS / 64 + 1];
+    __shared__ int before, mbefore;
     const int f = blk_frame[blockIdx.x], tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t lead = F[f].raw_off & 15u, raw_len = F[f].raw_len + lead, b0 = F[f].dsblk0;
     const uint32_t base = (blockIdx.x - b0) * (uint32_t)JG_DS_BLOCK;
     const uint8_t* scan = raw + (F[f].raw_off - lead);
     uint8_t* out = ds + F[f].ds_off;
     const int cw_shift = F[f].cw_shift;
-    // stuffed zeros in the frame's blocks before this one
+    const bool rst = RST && F[f].restart != 0;
+    // removed bytes (and markers) in the frame's blocks before this one
     {
-        int s = 0;
-        for (uint32_t b = b0 + tid; b < blockIdx.x; b += JG_DS_THREADS) s += (int)blk_removed[b];
+        int s = 0, sm = 0;
+        for (uint32_t b = b0 + tid; b < blockIdx.x; b += JG_DS_THREADS) {
+            s += (int)blk_removed[b];
+            if constexpr (RST) sm += (int)blk_markers[b];
+        }
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-        if (lane == 0) wsum[wave] = s;
+        for (int off = 32; off > 0; off >>= 1) {
+            s += __shfl_xor(s, off);
+            if constexpr (RST) sm += __shfl_xor(sm, off);
+        }
+        if (lane == 0) {
+            wsum[wave] = s;
+            if constexpr (RST) wsumm[wave] = sm;
+        }
         __syncthreads();
         if (tid == 0) {
-            int t = 0;
-            for (int w = 0; w < JG_DS_THREADS / 64; ++w) t += wsum[w];
+            int t = 0, tm = 0;
+            for (int w = 0; w < JG_DS_THREADS / 64; ++w) {
+                t += wsum[w];
+                if constexpr (RST) tm += wsumm[w];
+            }
             before = t;
+            if constexpr (RST) mbefore = tm;
         }
         __syncthreads();
     }
     uint8_t b[JG_DS_PIECES][16];
-    uint8_t prev[JG_DS_PIECES];
+    uint8_t prev[JG_DS_PIECES], next[JG_DS_PIECES];
 #pragma unroll
     for (int i = 0; i < JG_DS_PIECES; ++i) {
         const uint32_t pos0 = base + (uint32_t)(i * JG_DS_THREADS + tid) * 16;
         const uint4 v = pos0 < raw_len ? *reinterpret_cast<const uint4*>(scan + pos0) : make_uint4(0, 0, 0, 0);
         memcpy(b[i], &v, 16);
         prev[i] = pos0 > lead && pos0 <= raw_len ? scan[pos0 - 1] : 0;
-        int rem;
+        next[i] = 0;
+        if constexpr (RST) next[i] = pos0 + 16 < raw_len ? scan[pos0 + 16] : 0;
+        int rem, nmk;
         uint32_t m;
-        jg_piece_scan(lead, raw_len, pos0, b[i], prev[i], &rem, &m);
-        cnt[i * JG_DS_THREADS + tid] = rem;
+        jg_piece_scan<RST>(lead, raw_len, pos0, b[i], prev[i], next[i], rst, &rem, &nmk, &m);
+        cnt[i * JG_DS_THREADS + tid] = RST ? rem | (nmk << 16) : rem;
     }
     __syncthreads();
     // exclusive prefix over the 1024 pieces in byte order: thread t scans the pieces 4 t .. 4 t + 3, then the block
@@ -211,22 +284,39 @@ __global__ __launch_bounds__(JG_DS_THREADS) void jg_compact_kernel(const uint8_t
     for (int i = 0; i < JG_DS_PIECES; ++i) cnt[JG_DS_PIECES * tid + i] = wbase + incl - tot + mine[i];
     __syncthreads();
     const uint32_t end = F[f].marker_pos < raw_len ? F[f].marker_pos : raw_len;   // one past the last payload byte
+    const uint32_t cap = RST && rst ? F[f].nseg - 1u : 0u;       // entries of the frame's segment table (nseg >= 1)
+    uint32_t* seg = RST ? segtab + F[f].seg_off : nullptr;
 #pragma unroll
     for (int i = 0; i < JG_DS_PIECES; ++i) {
         const int q = i * JG_DS_THREADS + tid;
         const uint32_t pos0 = base + (uint32_t)q * 16;
         if (pos0 >= raw_len) continue;
-        // output index of the piece's first scan byte: scan bytes in front of it minus the stuffed zeros among them
-        uint32_t o = (pos0 > lead ? pos0 - lead : 0u) - (uint32_t)before - (uint32_t)cnt[q];
+        // output index of the piece's first scan byte: scan bytes in front of it minus the removed ones among them
+        uint32_t o = (pos0 > lead ? pos0 - lead : 0u) - (uint32_t)before - (uint32_t)(RST ? cnt[q] & 0xffff : cnt[q]);
+        uint32_t mi = RST ? (uint32_t)mbefore + ((uint32_t)cnt[q] >> 16) : 0u;   // index of the piece's first marker
         uint8_t p = prev[i];
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             const uint32_t pos = pos0 + k;
             if (pos == lead) p = 0;
             if (pos >= lead && pos < raw_len) {
-                const bool stuffed = p == 0xFF && b[i][k] == 0;
-                if (!stuffed) { out[4u * jg_dword_at(o >> 2, cw_shift) + (o & 3u)] = b[i][k]; ++o; }
-                if (pos + 1 == end) F[f].nbits = 8u * o;              // (end == 0: set by the host to 0 beforehand)
+                bool gone = p == 0xFF && b[i][k] == 0;
+                if constexpr (RST) {
+                    if (rst) {
+                        if (p == 0xFF && jg_is_rst(b[i][k])) {   // marker mi: the next segment begins at output byte o
+                            gone = true;
+                            if (pos < end && mi < cap) seg[mi] = (o << 3) | (uint32_t)(b[i][k] & 7u);
+                            ++mi;
+                        }
+                        const uint8_t nb = k < 15 ? b[i][k < 15 ? k + 1 : 15] : next[i];
+                        if (b[i][k] == 0xFF && pos + 1 < raw_len && jg_is_rst(nb)) gone = true;
+                    }
+                }
+                if (!gone) { out[4u * jg_dword_at(o >> 2, cw_shift) + (o & 3u)] = b[i][k]; ++o; }
+                if (pos + 1 == end) {
+                    F[f].nbits = 8u * o;                           // (end == 0: set by the host to 0 beforehand)
+                    if constexpr (RST) F[f].nmark = mi;
+                }
             }
             p = b[i][k];
         }
@@ -250,10 +340,14 @@ __device__ __forceinline__ int jg_extend(uint32_t v, int s) {
 
 // Decodes blocks from bit position p0 (slot z0) of the de-stuffed scan `ds`: !EMIT - up to the first block boundary at
 // or past `pend`; EMIT - exactly `want` blocks, written to coef.  Counts only COMPLETE blocks (every bit inside nbits).
-template <bool EMIT>
+// RST: `seg` = the frame's segment table (nvalid entries written), segblocks = restart * bpm.  The lane carries the bit
+// position of the next segment start behind its own position; the test sits in the block-complete branch, the symbol
+// path is the one of RST = false.  !EMIT: dsum comes back as the sums since the LAST crossing, *rs_out as JgChunks::rs.
+template <bool EMIT, bool RST>
 __device__ __forceinline__ void jg_decode(const JgLds& L, const uint32_t* __restrict__ ds, uint32_t nbits, uint32_t p0, int z0,
                                           uint32_t pend, uint32_t want, uint32_t* p_out, int* z_out, uint32_t* n_out, int (&dsum)[3],
-                                          bool* bad_out, int16_t* __restrict__ coef, uint32_t g0, const int (&pred0)[3]) {
+                                          bool* bad_out, int16_t* __restrict__ coef, uint32_t g0, const int (&pred0)[3],
+                                          const uint32_t* __restrict__ seg, uint32_t nvalid, uint32_t segblocks, uint2* rs_out) {
     const int bpm = L.fr.bpm, cws = L.fr.cw_shift;
     // slot -> DC table / AC table / component as nibbles of three registers: no LDS read on the symbol loop's critical path
     uint32_t dcmap = 0, acmap = 0, cmap = 0;
@@ -275,6 +369,17 @@ __device__ __forceinline__ void jg_decode(const JgLds& L, const uint32_t* __rest
     int z = z0, k = 0;
     bool bad = false;
     int pred[3] = {pred0[0], pred0[1], pred0[2]};
+    // RST: entry sidx of the table is the first segment start behind p0 (0xffffffff: none, p + 7 never reaches it)
+    uint32_t sidx = 0, nextseg = 0xffffffffu, rs_before = 0, rs_seg = 0, nlast = 0;
+    if constexpr (RST) {
+        uint32_t lo = 0, hi = nvalid;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if ((seg[mid] & ~7u) > p0) hi = mid; else lo = mid + 1;
+        }
+        sidx = lo;
+        if (sidx < nvalid) nextseg = seg[sidx] & ~7u;
+    }
     // EMIT: where the current block goes, and - computed while it is decoded, off the loop's critical path - the next one
     uint32_t mx = 0, my = 0, dst = 0, dstn = 0;
     int zn = z0;
@@ -369,6 +474,37 @@ __device__ __forceinline__ void jg_decode(const JgLds& L, const uint32_t* __rest
                 advance();
                 dstn = block_at(zn);
             }
+            if constexpr (RST) {
+                // the block ended inside the last byte in front of the next segment and only padding follows (1-bits: no
+                // Huffman code consists of ones alone, and a block of a flat area can be as short as 4 bits - the segment's
+                // last blocks may all lie in that byte), or, mis-speculated, behind its start: on at that byte with slot 0
+                // and predictions 0.  (EMIT runs on verified frames only: every crossing is at a whole number of MCUs, the
+                // destination pipeline above is already where the segment begins.)
+                bool cross = p + 7u >= nextseg;
+                if (cross && p < nextseg) {
+                    const uint32_t last = (nextseg >> 3) - 1u, pad = (1u << (nextseg - p)) - 1u;
+                    cross = ((ds[jg_dword_at(last >> 2, cws)] >> (8u * (last & 3u))) & pad) == pad;
+                }
+                if (cross) {
+                    if constexpr (!EMIT) {
+                        if (!(rs_before >> 31)) { rs_before = n | 0x80000000u; rs_seg = sidx + 1u; }
+                        else if (n - nlast != segblocks) rs_before |= 0x40000000u;
+                        nlast = n;
+                        dsum[0] = dsum[1] = dsum[2] = 0;
+                    } else {
+                        pred[0] = pred[1] = pred[2] = 0;
+                    }
+                    p = pb = nextseg;
+                    z = 0;
+                    ++sidx;
+                    nextseg = sidx < nvalid ? seg[sidx] & ~7u : 0xffffffffu;
+                    idx = p >> 5;
+                    buf = ((uint64_t)__builtin_bswap32(ds[jg_dword_at(idx, cws)]) << 32 | __builtin_bswap32(ds[jg_dword_at(idx + 1, cws)])) << (p & 31);
+                    have = 64 - (int)(p & 31);
+                    ridx = idx + 2;
+                    wnext = ds[jg_dword_at(ridx, cws)];
+                }
+            }
         }
         return true;
     };
@@ -401,6 +537,13 @@ __device__ __forceinline__ void jg_decode(const JgLds& L, const uint32_t* __rest
     *z_out = z;
     *n_out = n;
     *bad_out = bad;
+    if constexpr (RST && !EMIT) *rs_out = make_uint2(rs_before, rs_seg);
+}
+
+// entries of the frame's segment table that jg_compact_kernel has written (0 for a file without restart interval)
+__device__ __forceinline__ uint32_t jg_seg_valid(const JgFrame& fr) {
+    if (fr.restart == 0) return 0u;
+    return fr.nmark < fr.nseg - 1u ? fr.nmark : fr.nseg - 1u;
 }
 
 __device__ __forceinline__ void jg_load_lds(JgLds& L, const JgFrame* F, const JgTableSet* T, int f) {
@@ -425,86 +568,175 @@ __device__ __forceinline__ void jg_load_lds(JgLds& L, const JgFrame* F, const Jg
     __syncthreads();
 }
 
+// One round.  RST = false: one decode per lane, as described at the top.
+// RST = true: the 256 lanes of a block are 256 CONSECUTIVE chunks, so the iteration also runs INSIDE the launch - after
+// its decode a lane looks at the end state its left neighbour has just written to LDS, and decodes again if that is not
+// the state it started from; up to JG_INNER times, ending as soon as no lane of the block has anything to redo (a
+// converged block: one look, no decode).  Only a block's first lane waits for the next launch.  Round 0 thus settles every
+// block up to its first lane's guess, round 1 hands each first lane the true state: two launches reach the fixed point
+// where lane-per-launch propagation needed one per chunk a guess takes to fall into step.  What is stored per chunk is
+// what the last decode of the lane gave - the scan kernel checks exactly the same relations as before.
+constexpr int JG_INNER = 16;
+
+template <bool RST>
 __global__ __launch_bounds__(JG_CB) void jg_round_kernel(const uint8_t* __restrict__ ds_base, const JgFrame* __restrict__ F,
                                                          const JgTableSet* __restrict__ T, const uint16_t* __restrict__ cblk_frame,
-                                                         JgChunks S, int round) {
+                                                         JgChunks S, int round, const uint32_t* __restrict__ segtab) {
     __shared__ __attribute__((aligned(16))) JgLds L;
     const int f = cblk_frame[blockIdx.x];
     jg_load_lds(L, F, T, f);
     const uint32_t t = (blockIdx.x - L.fr.cblk0) * JG_CB + threadIdx.x, gt = L.fr.chunk0 + t;
     const uint32_t nbits = L.fr.nbits, cbits = (uint32_t)L.fr.chunk_bytes * 8u;
     const uint32_t b0 = t * cbits;
-    if (t >= L.fr.nchunks || b0 >= nbits) return;                 // (chunks past the payload take no part)
-    const uint32_t b1 = b0 + cbits < nbits ? b0 + cbits : nbits;
-    uint2 start;
-    if (t == 0) start = make_uint2(0u, 0u);
-    else if (round == 0) start = make_uint2(b0, 0u);
-    else start = S.en[(round - 1) & 1][gt - 1];
-    if (round > 0) {
-        const uint2 old = S.st[gt];
-        if (old.x == start.x && old.y == start.y) { S.en[round & 1][gt] = S.en[(round - 1) & 1][gt]; return; }
+    if constexpr (!RST) {
+        if (t >= L.fr.nchunks || b0 >= nbits) return;                 // (chunks past the payload take no part)
+        const uint32_t b1 = b0 + cbits < nbits ? b0 + cbits : nbits;
+        uint2 start;
+        if (t == 0) start = make_uint2(0u, 0u);
+        else if (round == 0) start = make_uint2(b0, 0u);
+        else start = S.en[(round - 1) & 1][gt - 1];
+        if (round > 0) {
+            const uint2 old = S.st[gt];
+            if (old.x == start.x && old.y == start.y) { S.en[round & 1][gt] = S.en[(round - 1) & 1][gt]; return; }
+        }
+        S.st[gt] = start;
+        {   // diagnostics: lanes that decode in this round (one atomic per wave)
+            const unsigned long long m = __ballot(1);
+            if ((threadIdx.x & 63) == (unsigned)__ffsll((long long)m) - 1u) atomicAdd(&S.redone[round], (uint32_t)__popcll(m));
+        }
+        uint32_t pe = start.x, n = 0;
+        int ze = (int)start.y, dsum[3] = {0, 0, 0};
+        bool bad = false;
+        const int zero3[3] = {0, 0, 0};
+        if (start.x < b1)
+            jg_decode<false, false>(L, reinterpret_cast<const uint32_t*>(ds_base + L.fr.ds_off), nbits, start.x, (int)start.y, b1, 0u, &pe, &ze,
+                                    &n, dsum, &bad, nullptr, 0u, zero3, nullptr, 0u, 0u, nullptr);
+        S.en[round & 1][gt] = make_uint2(pe, (uint32_t)ze);
+        S.cnt[gt] = n;
+        S.dcs[3 * gt] = dsum[0];
+        S.dcs[3 * gt + 1] = dsum[1];
+        S.dcs[3 * gt + 2] = dsum[2];
+        S.err[gt] = bad ? 1 : 0;
+    } else {
+        __shared__ uint2 ends[JG_CB];                                // the lanes' current end states
+        const bool active = t < L.fr.nchunks && b0 < nbits;          // (the active chunks of a frame are its first ones)
+        const uint32_t b1 = b0 + cbits < nbits ? b0 + cbits : nbits;
+        uint2 start = make_uint2(0u, 0u), end = make_uint2(0u, 0u);
+        bool need = false;
+        if (active) {
+            if (t == 0) start = make_uint2(0u, 0u);
+            else if (round == 0) start = make_uint2(b0, 0u);
+            else start = S.en[(round - 1) & 1][gt - 1];
+            need = true;
+            if (round > 0) {
+                const uint2 old = S.st[gt];
+                if (old.x == start.x && old.y == start.y) { need = false; end = S.en[(round - 1) & 1][gt]; }
+            }
+        }
+        for (int it = 0; it < JG_INNER; ++it) {
+            if (need) {
+                S.st[gt] = start;
+                const unsigned long long m = __ballot(1);              // diagnostics: decodes of this round, inner ones included
+                if ((threadIdx.x & 63) == (unsigned)__ffsll((long long)m) - 1u) atomicAdd(&S.redone[round], (uint32_t)__popcll(m));
+                uint32_t pe = start.x, n = 0;
+                int ze = (int)start.y, dsum[3] = {0, 0, 0};
+                bool bad = false;
+                const int zero3[3] = {0, 0, 0};
+                uint2 rs = make_uint2(0u, 0u);
+                if (start.x < b1)
+                    jg_decode<false, true>(L, reinterpret_cast<const uint32_t*>(ds_base + L.fr.ds_off), nbits, start.x, (int)start.y, b1, 0u, &pe,
+                                           &ze, &n, dsum, &bad, nullptr, 0u, zero3, segtab + L.fr.seg_off, jg_seg_valid(L.fr),
+                                           L.fr.restart * (uint32_t)L.fr.bpm, &rs);
+                end = make_uint2(pe, (uint32_t)ze);
+                S.cnt[gt] = n;
+                S.dcs[3 * gt] = dsum[0];
+                S.dcs[3 * gt + 1] = dsum[1];
+                S.dcs[3 * gt + 2] = dsum[2];
+                S.err[gt] = bad ? 1 : 0;
+                S.rs[gt] = rs;
+            }
+            ends[threadIdx.x] = end;
+            __syncthreads();
+            need = false;
+            if (active && threadIdx.x > 0 && t > 0) {                 // (t > 0 and not the block's first lane: the chunk in front is this block's)
+                const uint2 pred = ends[threadIdx.x - 1];
+                if (pred.x != start.x || pred.y != start.y) { start = pred; need = true; }
+            }
+            if (!__syncthreads_or(need ? 1 : 0)) break;
+        }
+        if (active) S.en[round & 1][gt] = end;
     }
-    S.st[gt] = start;
-    {   // diagnostics: lanes that decode in this round (one atomic per wave)
-        const unsigned long long m = __ballot(1);
-        if ((threadIdx.x & 63) == (unsigned)__ffsll((long long)m) - 1u) atomicAdd(&S.redone[round], (uint32_t)__popcll(m));
-    }
-    uint32_t pe = start.x, n = 0;
-    int ze = (int)start.y, dsum[3] = {0, 0, 0};
-    bool bad = false;
-    const int zero3[3] = {0, 0, 0};
-    if (start.x < b1)
-        jg_decode<false>(L, reinterpret_cast<const uint32_t*>(ds_base + L.fr.ds_off), nbits, start.x, (int)start.y, b1, 0u, &pe, &ze, &n, dsum,
-                         &bad, nullptr, 0u, zero3);
-    S.en[round & 1][gt] = make_uint2(pe, (uint32_t)ze);
-    S.cnt[gt] = n;
-    S.dcs[3 * gt] = dsum[0];
-    S.dcs[3 * gt + 1] = dsum[1];
-    S.dcs[3 * gt + 2] = dsum[2];
-    S.err[gt] = bad ? 1 : 0;
 }
 
-// one 1024-thread block per frame: prefix sums over its chunks + the checks of the fixed point
-__global__ __launch_bounds__(1024) void jg_scan_kernel(JgFrame* __restrict__ F, JgChunks S, int last_round) {
+// one 1024-thread block per frame: prefix sums over its chunks + the checks of the fixed point.
+// A frame with a restart interval: the DC prefix is a SEGMENTED scan - element (crossed, sums since the last crossing),
+// (f1, v1) + (f2, v2) = (f1 | f2, f2 ? v2 : v1 + v2) - so that a chunk's dcb is the sum since the last segment start; the
+// block prefix stays plain.  Then the restart checks (header comment) per chunk and per table entry.
+__global__ __launch_bounds__(1024) void jg_scan_kernel(JgFrame* __restrict__ F, JgChunks S, int last_round, const uint32_t* __restrict__ segtab) {
     __shared__ int wsum[16][4];
+    __shared__ int wflag[16];
     __shared__ int carry[4];
-    __shared__ int status;
+    __shared__ int status, rstatus;                               // (a restart verdict counts only at the fixed point: reported after the others)
     const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const JgFrame fr = F[f];
+    const bool rst = fr.restart != 0;
+    const uint32_t segblocks = fr.restart * (uint32_t)fr.bpm;
     const uint32_t cbits = (uint32_t)fr.chunk_bytes * 8u;
     const uint32_t nvalid = fr.nbits ? (fr.nbits + cbits - 1) / cbits : 0u;
     if (tid < 4) carry[tid] = 0;
-    if (tid == 0) status = JG_OK;
+    if (tid == 0) { status = JG_OK; rstatus = JG_OK; }
     __syncthreads();
     const uint2* en = S.en[last_round & 1];
     for (uint32_t t0 = 0; t0 < nvalid; t0 += 1024) {
         const uint32_t t = t0 + tid, gt = fr.chunk0 + t;
         const bool live = t < nvalid;
         int v[4] = {0, 0, 0, 0};
+        uint2 rs = make_uint2(0u, 0u);
         if (live) {
             v[0] = (int)S.cnt[gt];
             v[1] = S.dcs[3 * gt];
             v[2] = S.dcs[3 * gt + 1];
             v[3] = S.dcs[3 * gt + 2];
+            if (rst) rs = S.rs[gt];
         }
-        int incl[4];
+        const int fl = (int)(rs.x >> 31);                          // the chunk crossed a segment start
+        int incl[4], ifl = fl;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            incl[c] = v[c];
+        for (int c = 0; c < 4; ++c) incl[c] = v[c];
 #pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
+        for (int off = 1; off < 64; off <<= 1) {
+            const int of = __shfl_up(ifl, off);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
                 const int o = __shfl_up(incl[c], off);
-                if (lane >= off) incl[c] += o;
+                if (lane >= off && (c == 0 || !ifl)) incl[c] += o;
             }
-            if (lane == 63) wsum[wave][c] = incl[c];
+            if (lane >= off) ifl |= of;
+        }
+        if (lane == 63) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) wsum[wave][c] = incl[c];
+            wflag[wave] = ifl;
         }
         __syncthreads();
+        // exclusive: (carry + the waves before) + (the lanes before in this wave)
         int excl[4];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            int wb = carry[c];
-            for (int w = 0; w < wave; ++w) wb += wsum[w][c];
-            excl[c] = wb + incl[c] - v[c];
+        for (int c = 0; c < 4; ++c) excl[c] = carry[c];
+        for (int w = 0; w < wave; ++w) {
+            excl[0] += wsum[w][0];
+#pragma unroll
+            for (int c = 1; c < 4; ++c) excl[c] = wflag[w] ? wsum[w][c] : excl[c] + wsum[w][c];
+        }
+        {
+            int ef = __shfl_up(ifl, 1);
+            if (lane == 0) ef = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                int e = __shfl_up(incl[c], 1);
+                if (lane == 0) e = 0;
+                excl[c] = (c > 0 && ef) ? e : excl[c] + e;
+            }
         }
         if (live) {
             S.gfirst[gt] = (uint32_t)excl[0];
@@ -518,26 +750,40 @@ __global__ __launch_bounds__(1024) void jg_scan_kernel(JgFrame* __restrict__ F, 
             if (st.x != want.x || st.y != want.y) bad = JG_NOT_CONVERGED;
             else if ((uint32_t)excl[0] % (uint32_t)fr.bpm != st.y) bad = JG_SLOT;
             else if (S.err[gt] && (uint32_t)excl[0] + (uint32_t)v[0] < (uint32_t)fr.total_blocks) bad = JG_BAD_CODE;   // (the padding bits after the last block decode to anything)
+            // the chunk's first crossing lies at the first block of the segment entered there; its later ones a whole segment on
+            else if (fl && ((rs.x & 0x40000000u) || (uint32_t)excl[0] + (rs.x & 0x3fffffffu) != rs.y * segblocks)) atomicMax(&rstatus, (int)JG_RESTART);
             if (bad) atomicMax(&status, bad);
         }
         __syncthreads();
         if (tid == 1023) {
+            carry[0] = excl[0] + v[0];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) carry[c] = excl[c] + v[c];
+            for (int c = 1; c < 4; ++c) carry[c] = fl ? v[c] : excl[c] + v[c];
         }
+        __syncthreads();
+    }
+    if (rst) {
+        // as many markers as the header says, numbered 0 .. 7 in turn (nmark == nseg - 1: every entry was written)
+        int bad = fr.nmark != fr.nseg - 1u ? JG_RESTART : JG_OK;
+        if (!bad)
+            for (uint32_t k = tid; k < fr.nseg - 1u; k += 1024)
+                if ((segtab[fr.seg_off + k] & 7u) != (k & 7u)) bad = JG_RESTART;
+        if (bad) atomicMax(&rstatus, bad);
         __syncthreads();
     }
     if (tid == 0) {
         int st = status;
+        if (st == JG_OK) st = rstatus;
         if (st == JG_OK && carry[0] != fr.total_blocks) st = JG_BLOCK_COUNT;
         F[f].status = st;
         F[f].blocks_found = (uint32_t)carry[0];
     }
 }
 
+template <bool RST>
 __global__ __launch_bounds__(JG_CB) void jg_emit_kernel(const uint8_t* __restrict__ ds_base, const JgFrame* __restrict__ F,
                                                         const JgTableSet* __restrict__ T, const uint16_t* __restrict__ cblk_frame,
-                                                        JgChunks S, int16_t* __restrict__ coef) {
+                                                        JgChunks S, int16_t* __restrict__ coef, const uint32_t* __restrict__ segtab) {
     __shared__ __attribute__((aligned(16))) JgLds L;
     const int f = cblk_frame[blockIdx.x];
     jg_load_lds(L, F, T, f);
@@ -552,8 +798,9 @@ __global__ __launch_bounds__(JG_CB) void jg_emit_kernel(const uint8_t* __restric
     uint32_t pe, n;
     int ze, dsum[3] = {0, 0, 0};
     bool bad;
-    jg_decode<true>(L, reinterpret_cast<const uint32_t*>(ds_base + L.fr.ds_off), nbits, start.x, (int)start.y, 0u, want, &pe, &ze, &n, dsum, &bad,
-                    coef, S.gfirst[gt], pred0);
+    jg_decode<true, RST>(L, reinterpret_cast<const uint32_t*>(ds_base + L.fr.ds_off), nbits, start.x, (int)start.y, 0u, want, &pe, &ze, &n, dsum,
+                         &bad, coef, S.gfirst[gt], pred0, RST ? segtab + L.fr.seg_off : nullptr, jg_seg_valid(L.fr),
+                         L.fr.restart * (uint32_t)L.fr.bpm, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------- host side
@@ -600,8 +847,12 @@ inline bool jg_build_tables(const Parsed& P, JgTableSet* ts, uint8_t (&slot_dc)[
 }
 
 // can this parsed file take the device path?
-inline bool jg_supported(const Parsed& P, const ScanLayout& L) {
-    return P.restart == 0 && L.bpm <= 8 && (size_t)(P.end - P.scan) < ((size_t)1 << 30);
+// (restart-interval files only when the handle's option "jpeg_device_restart" allows them)
+inline uint32_t jg_segments(const Parsed& P, const ScanLayout& L) {
+    return P.restart ? (uint32_t)(((size_t)L.mcux * L.mcuy + P.restart - 1) / P.restart) : 1u;
+}
+inline bool jg_supported(const Parsed& P, const ScanLayout& L, bool restart_ok) {
+    return (P.restart == 0 || restart_ok) && L.bpm <= 8 && (size_t)(P.end - P.scan) < ((size_t)1 << 30);
 }
 
 }  // namespace dfd_jpeg_gpu
