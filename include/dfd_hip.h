@@ -173,6 +173,37 @@ int dfd_preprocess_face_quality(dfd_handle* h, const uint8_t* bgr, int height, i
 int dfd_tta_augment(dfd_handle* h, const uint8_t* bgr, int height, int width, int stride, int flip, double brightness,
                     double angle_deg, uint8_t* out);
 
+/* Test-time augmentation inside the batched pass.  A draw is one copy's (flip, brightness, angle_deg); a face with
+ * `copies` draws is classified 1 + copies times: column 0 the un-augmented (CLAHE'd) crop, columns 1.. its copies in
+ * draw order.  CLAHE runs once per face, ONE launch makes every copy of every face, all images go through the MTCNN
+ * stage together (when it is on; a rejected image gets NaN and is never classified) and through the classifier in
+ * chunks of max_batch images.  Nothing is averaged on the device: the host takes the mean of the sigmoids.
+ *   dfd_tta_augment_crops : the copies alone, read straight from the frame (no CLAHE); draws [n][copies], face-major;
+ *                           out = the images back to back, tight width*3 rows, face-major then copy
+ *   dfd_classify_crops_tta: dfd_classify_crops with copies; logits_out [n][1 + copies], n <= max_batch faces
+ *   dfd_tta_arm           : one-shot arming of the NEXT dfd_analyze_frame / dfd_analyze_jpeg / dfd_analyze_stream_batch /
+ *                           dfd_analyze_streams_batch call on this handle, which consumes it whether it succeeds or
+ *                           fails.  draws [capacity_faces][copies] are copied now; the faces of the call take rows in
+ *                           the order the call returns them (frame-major, then face order).  That call checks at entry,
+ *                           before any state moves, that capacity_faces >= n_frames x max_faces (else DFD_ERR_ARG).  Its
+ *                           own logits_out keeps its meaning (column 0).  dfd_analyze_batch_device / dfd_analyze_frames_host
+ *                           / dfd_analyze_jpegs_host do not take copies: armed, they return DFD_ERR_STATE.
+ *   dfd_tta_logits        : the [n_faces][1 + copies] block of the last armed call (valid after it succeeded); with too
+ *                           little room DFD_ERR_CAPACITY, *n_faces / *copies still set.
+ * copies < 1 or null draws: DFD_ERR_ARG; copies > 63: DFD_ERR_CAPACITY (the per-face scratch layout). */
+typedef struct dfd_tta_draw {
+    int32_t flip;
+    int32_t reserved;
+    double brightness;
+    double angle_deg;
+} dfd_tta_draw;
+int dfd_tta_augment_crops(dfd_handle* h, const uint8_t* bgr, int height, int width, int stride, const int32_t* xywh, int n,
+                          int copies, const dfd_tta_draw* draws, uint8_t* out);
+int dfd_classify_crops_tta(dfd_handle* h, const uint8_t* bgr, int height, int width, int stride, const int32_t* xywh, int n,
+                           int apply_clahe, int copies, const dfd_tta_draw* draws, float* logits_out);
+int dfd_tta_arm(dfd_handle* h, int copies, const dfd_tta_draw* draws, int capacity_faces);
+int dfd_tta_logits(dfd_handle* h, float* logits_out, size_t capacity_floats, int* n_faces, int* copies);
+
 /* crop (reference backend_server.py:160-161 / deepfake_detection.py:612) -> optional CLAHE ->
  * BGR->RGB, bilinear 224x224 (align_corners=False), /255, ImageNet normalise (reference
  * deepfake_detection.py:376,382-389).  When the blob carries an MTCNN cascade and option "mtcnn" is on, the re-crop at

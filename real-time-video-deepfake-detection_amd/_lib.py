@@ -56,6 +56,12 @@ SIGNATURES = {
     "dfd_resize_bgr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dfd_tta_augment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                   C.c_void_p]),
+    "dfd_tta_augment_crops": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_void_p]),
+    "dfd_classify_crops_tta": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_int, C.c_void_p, C.c_void_p]),
+    "dfd_tta_arm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "dfd_tta_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dfd_preprocess_face_quality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dfd_preprocess_crops": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                        C.c_int, C.c_void_p]),
@@ -146,6 +152,22 @@ class MtcnnParams(C.Structure):
     """`dfd_mtcnn_params` (include/dfd_hip.h): the constructor arguments of facenet_pytorch.MTCNN."""
     _fields_ = [("image_size", C.c_int), ("margin", C.c_int), ("min_face_size", C.c_int), ("thresholds", C.c_float * 3),
                 ("factor", C.c_double), ("selection", C.c_int), ("keep_all", C.c_int), ("post_process", C.c_int)]
+
+
+class TtaDraw(C.Structure):
+    """`dfd_tta_draw` (include/dfd_hip.h): one augmented copy's flip, brightness and rotation angle."""
+    _fields_ = [("flip", C.c_int32), ("reserved", C.c_int32), ("brightness", C.c_double), ("angle_deg", C.c_double)]
+
+
+def tta_draws(draws, rows: int, copies: int):
+    """[(flip, brightness, angle_deg), ...] (face-major, rows x copies of them) -> a `dfd_tta_draw` array"""
+    draws = list(draws)
+    if copies < 1 or len(draws) != rows * copies:
+        raise ValueError(f"expected {rows} x {copies} draws, got {len(draws)}")
+    arr = (TtaDraw * len(draws))()
+    for d, (flip, brightness, angle) in zip(arr, draws):
+        d.flip, d.brightness, d.angle_deg = int(bool(flip)), float(brightness), float(angle)
+    return arr
 
 
 MT_SELECT = {None: 0, "none": 0, "probability": 1, "largest": 2, "center_weighted_size": 3, "largest_over_threshold": 4}
@@ -399,6 +421,60 @@ class Handle:
                                               float(brightness), float(angle_deg), _ptr(out)))
         return out
 
+    def tta_augment_crops(self, frame, boxes, copies: int, draws):
+        """`copies` augmented images of every box in ONE launch (dfd_tta_augment_crops; no CLAHE).  draws: (flip,
+        brightness, angle_deg) per image, face-major.  -> [[image (h, w, 3) per copy] per box]"""
+        a, b = self._as_bgr(frame), self._as_boxes(boxes)
+        d = tta_draws(draws, b.shape[0], int(copies))
+        out = np.empty(int(sum(int(w) * int(h) * 3 * copies for _, _, w, h in b)), np.uint8)
+        self._check(self._lib.dfd_tta_augment_crops(self._p, _ptr(a), a.shape[0], a.shape[1], a.strides[0], _ptr(b), b.shape[0],
+                                                    int(copies), d, _ptr(out)))
+        res, at = [], 0
+        for _, _, w, h in b:
+            n = int(w) * int(h) * 3
+            res.append([out[at + j * n: at + (j + 1) * n].reshape(int(h), int(w), 3) for j in range(copies)])
+            at += n * copies
+        return res
+
+    def classify_crops_tta(self, frame, boxes, copies: int, draws, apply_clahe: bool = True) -> np.ndarray:
+        """`classify_crops` with `copies` augmented images per box in the same pass -> logits (n, 1 + copies): column 0
+        the un-augmented crop, NaN where the MTCNN stage found no face"""
+        a, b = self._as_bgr(frame), self._as_boxes(boxes)
+        d = tta_draws(draws, b.shape[0], int(copies))
+        out = np.empty((b.shape[0], 1 + int(copies)), np.float32)
+        self._check(self._lib.dfd_classify_crops_tta(self._p, _ptr(a), a.shape[0], a.shape[1], a.strides[0], _ptr(b), b.shape[0],
+                                                     int(apply_clahe), int(copies), d, _ptr(out)))
+        return out
+
+    def tta_arm(self, copies: int, draws, capacity_faces: int):
+        """arm the next fused analyze call (dfd_tta_arm): draws for `capacity_faces` faces, face-major"""
+        d = tta_draws(draws, int(capacity_faces), int(copies))
+        self._check(self._lib.dfd_tta_arm(self._p, int(copies), d, int(capacity_faces)))
+
+    def tta_logits(self) -> np.ndarray:
+        """(n_faces, 1 + copies) logits of the last armed call, faces in the order the call returned them"""
+        n, c = C.c_int(), C.c_int()
+        self._lib.dfd_tta_logits(self._p, None, 0, C.byref(n), C.byref(c))
+        out = np.empty((n.value, 1 + c.value), np.float32)
+        self._check(self._lib.dfd_tta_logits(self._p, _ptr(out), out.size, C.byref(n), C.byref(c)))
+        return out
+
+    def _tta_arm_for(self, tta, n_frames: int, max_faces: int):
+        if tta is not None:
+            copies, draws = tta
+            self.tta_arm(copies, draws, n_frames * max_faces)
+
+    def _tta_rows(self, counts):
+        """per frame the (n, 1 + copies) logits of its faces (counts: faces per frame, call order)"""
+        block = self.tta_logits()
+        if block.shape[0] != sum(counts):
+            raise DfdError(-5, f"armed call returned {sum(counts)} faces, dfd_tta_logits holds {block.shape[0]}")
+        out, at = [], 0
+        for k in counts:
+            out.append(block[at:at + k].copy())
+            at += k
+        return out
+
     def preprocess_crops(self, frame, boxes, apply_clahe: bool = True) -> np.ndarray:
         a, b = self._as_bgr(frame), self._as_boxes(boxes)
         out = np.empty((b.shape[0], 3, 224, 224), np.float32)
@@ -548,11 +624,13 @@ class Handle:
         return (out, nc.value) if with_candidates else out
 
     def analyze_frame(self, frame, full_forensics: bool, stream_id: int = 0, confidence_threshold: float = 0.5,
-                      max_faces: int = 16, apply_clahe: bool = True):
+                      max_faces: int = 16, apply_clahe: bool = True, tta=None):
         """One upload: forensics + detect + crop/CLAHE + classify.
-        -> (scores dict, forensic probability, [(x,y,w,h)...], logits (n,))"""
+        -> (scores dict, forensic probability, [(x,y,w,h)...], logits (n,))
+        tta = (copies, draws for max_faces faces): the call is armed (dfd_tta_arm) and logits are (n, 1 + copies)"""
         a = self._as_bgr(frame)
         max_faces = max(1, int(max_faces))
+        self._tta_arm_for(tta, 1, max_faces)
         sc = np.empty(6, np.float64)
         prob = C.c_double()
         boxes = np.zeros((max_faces, 4), np.int32)
@@ -563,7 +641,8 @@ class Handle:
                                                 int(bool(apply_clahe)), _ptr(sc), C.byref(prob), _ptr(boxes), C.byref(n),
                                                 _ptr(logits)))
         scores = {k: float(v) for k, v in zip(self.FORENSIC_KEYS, sc) if not np.isnan(v)}
-        return scores, float(prob.value), [tuple(int(v) for v in boxes[i]) for i in range(n.value)], logits[: n.value].copy()
+        lg = logits[: n.value].copy() if tta is None else self._tta_rows([n.value])[0]
+        return scores, float(prob.value), [tuple(int(v) for v in boxes[i]) for i in range(n.value)], lg
 
     UNSUPPORTED = -7
 
@@ -600,10 +679,11 @@ class Handle:
         return self._lib.dfd_frame_ptr(self._p)
 
     def analyze_jpeg(self, data: bytes, full_forensics: bool, stream_id: int = 0, confidence_threshold: float = 0.5,
-                     max_faces: int = 16, apply_clahe: bool = True):
+                     max_faces: int = 16, apply_clahe: bool = True, tta=None):
         """analyze_frame from JPEG bytes, decoded on the device -> (scores, forensic prob, boxes, logits, (H, W))"""
         buf = (C.c_char * len(data)).from_buffer_copy(data)
         max_faces = max(1, int(max_faces))
+        self._tta_arm_for(tta, 1, max_faces)
         sc = np.empty(6, np.float64)
         prob = C.c_double()
         boxes = np.zeros((max_faces, 4), np.int32)
@@ -613,11 +693,11 @@ class Handle:
                                                float(confidence_threshold), max_faces, int(bool(apply_clahe)), _ptr(sc),
                                                C.byref(prob), _ptr(boxes), C.byref(n), _ptr(logits), C.byref(hh), C.byref(ww)))
         scores = {k: float(v) for k, v in zip(self.FORENSIC_KEYS, sc) if not np.isnan(v)}
-        return (scores, float(prob.value), [tuple(int(v) for v in boxes[i]) for i in range(n.value)], logits[: n.value].copy(),
-                (hh.value, ww.value))
+        lg = logits[: n.value].copy() if tta is None else self._tta_rows([n.value])[0]
+        return (scores, float(prob.value), [tuple(int(v) for v in boxes[i]) for i in range(n.value)], lg, (hh.value, ww.value))
 
     def analyze_stream_batch(self, items, full_flags, stream_id: int = 0, confidence_threshold: float = 0.5,
-                             max_faces: int = 1, apply_clahe: bool = True):
+                             max_faces: int = 1, apply_clahe: bool = True, tta=None):
         """n consecutive frames of one stream in ONE call (dfd_analyze_stream_batch).  items: JPEG `bytes` and / or BGR
         uint8 arrays of one size.  -> list of (scores dict, forensic prob, boxes, logits, n_detected) per frame, (H, W)"""
         n = len(items)
@@ -646,19 +726,21 @@ class Handle:
         nd = np.zeros(n, np.int32)
         logits = np.zeros((n, max_faces), np.float32)
         oh, ow = C.c_int(), C.c_int()
+        self._tta_arm_for(tta, n, max_faces)
         self._check(self._lib.dfd_analyze_stream_batch(self._p, int(stream_id), n, ptrs, lens, int(hh), int(ww), _ptr(full),
                                                        float(confidence_threshold), max_faces, int(bool(apply_clahe)), _ptr(sc),
                                                        _ptr(prob), _ptr(boxes), _ptr(nf), _ptr(nd), _ptr(logits),
                                                        C.byref(oh), C.byref(ow)))
+        rows = None if tta is None else self._tta_rows([int(k) for k in nf])
         out = []
         for i in range(n):
             scores = {k: float(v) for k, v in zip(self.FORENSIC_KEYS, sc[i]) if not np.isnan(v)}
             out.append((scores, float(prob[i]), [tuple(int(v) for v in boxes[i, j]) for j in range(nf[i])],
-                        logits[i, : nf[i]].copy(), int(nd[i])))
+                        logits[i, : nf[i]].copy() if rows is None else rows[i], int(nd[i])))
         return out, (oh.value, ow.value)
 
     def analyze_streams_batch(self, items, stream_ids, full_flags, confidence_threshold: float = 0.5, max_faces: int = 1,
-                              apply_clahe: bool = True):
+                              apply_clahe: bool = True, tta=None):
         """frames of MANY streams and sizes in ONE call (dfd_analyze_streams_batch).  items: JPEG `bytes` and / or BGR
         uint8 arrays; stream_ids / full_flags: one per item (a stream's frames in stream order).  -> list of (scores dict,
         forensic prob, boxes, logits, n_detected, (H, W)) per frame.  A refused part raises DfdError with
@@ -691,6 +773,7 @@ class Handle:
         logits = np.zeros((n, max_faces), np.float32)
         oh, ow = np.zeros(n, np.int32), np.zeros(n, np.int32)
         bad = C.c_int(-1)
+        self._tta_arm_for(tta, n, max_faces)
         rc = self._lib.dfd_analyze_streams_batch(self._p, n, ptrs, lens, _ptr(hs), _ptr(ws), _ptr(ids), _ptr(full),
                                                  float(confidence_threshold), max_faces, int(bool(apply_clahe)), _ptr(sc),
                                                  _ptr(prob), _ptr(boxes), _ptr(nf), _ptr(nd), _ptr(logits), _ptr(oh), _ptr(ow),
@@ -699,11 +782,12 @@ class Handle:
             err = DfdError(rc, (self._lib.dfd_last_error(self._p) or b"").decode())
             err.bad_index = bad.value
             raise err
+        rows = None if tta is None else self._tta_rows([int(k) for k in nf])
         out = []
         for i in range(n):
             scores = {k: float(v) for k, v in zip(self.FORENSIC_KEYS, sc[i]) if not np.isnan(v)}
             out.append((scores, float(prob[i]), [tuple(int(v) for v in boxes[i, j]) for j in range(nf[i])],
-                        logits[i, : nf[i]].copy(), int(nd[i]), (int(oh[i]), int(ow[i]))))
+                        logits[i, : nf[i]].copy() if rows is None else rows[i], int(nd[i]), (int(oh[i]), int(ow[i]))))
         return out
 
     def host_alloc(self, shape, dtype=np.uint8) -> np.ndarray:

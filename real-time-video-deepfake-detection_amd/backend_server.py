@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import io
 import logging
+import os
 import re
 import threading
 import time
@@ -57,8 +58,14 @@ def _cors(resp):                                  # reference :46-53 (CORS(app, 
     return resp
 
 
-detector = DeepfakeDetector(enable_gradcam=False, use_tta=False, num_tta_augmentations=1,
-                            detection_threshold=0.55)                       # reference :57
+# DFD_TTA_AUGMENTATIONS=<K> (K > 1): test-time augmentation with K images per face, inside the one batched device pass of
+# every route.  Unset: off, as the reference ships its server (:57 "Disabled for real-time speed").
+try:
+    TTA_AUGMENTATIONS = max(1, int(os.environ.get("DFD_TTA_AUGMENTATIONS", "1")))
+except ValueError:
+    TTA_AUGMENTATIONS = 1
+detector = DeepfakeDetector(enable_gradcam=False, use_tta=TTA_AUGMENTATIONS > 1, num_tta_augmentations=TTA_AUGMENTATIONS,
+                            detection_threshold=0.55, request_tta=TTA_AUGMENTATIONS > 1)                       # reference :57
 
 _last_request_time = 0.0
 _min_request_interval = 0.1                                                 # reference :63
@@ -79,7 +86,8 @@ def _pool():
     global _session_pool
     with _rate_lock:
         if _session_pool is None:
-            _session_pool = SessionPool(lock=_detector_lock, detection_threshold=0.55)
+            _session_pool = SessionPool(lock=_detector_lock, detection_threshold=0.55, use_tta=TTA_AUGMENTATIONS > 1,
+                                        num_tta_augmentations=TTA_AUGMENTATIONS)
         return _session_pool
 
 

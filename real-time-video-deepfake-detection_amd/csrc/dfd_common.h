@@ -111,6 +111,14 @@ struct dfd_handle {
     int last_detections = 0;             // detections of the last single-frame detector run, before the max_out cut
     std::vector<char> crop_valid;        // per crop of the last preprocess: 0 = the MTCNN stage found no face
     int n_compact = 0;                   // rows of in_nchw the last preprocess filled (= crops with a face, in crop order, when it compacts)
+    // test-time augmentation (imgproc_api.hip): the one-shot arming of the next fused analyze call and the [faces][1 + copies]
+    // logits of the last armed call
+    bool tta_armed = false;
+    int tta_copies = 0, tta_capacity = 0;      // of the arming
+    std::vector<dfd_tta_draw> tta_draws;       // copied at arm time: tta_capacity x tta_copies, face-major
+    std::vector<float> tta_logits;             // last armed call
+    int tta_out_faces = 0, tta_out_copies = 0;
+    dfd::DevBuf tta_desc, tta_logit_buf;       // augment table (rows + tile starts) / device logits of all images of a call
     unsigned long long classifier_crops = 0;   // crops b0_forward has been asked for since dfd_create (dfd_classifier_crop_count)
     dfd::ForensicState* forensic = nullptr;   // per-stream temporal state + work buffers
     dfd::FreqState* freq = nullptr;           // compute_frequency_features tables + scratch
@@ -200,8 +208,24 @@ int preprocess_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int 
 // the model runs) - a rejected crop costs no classifier work and gets NaN.  Ends with a stream wait.
 // crop_frames (or null): per-crop frame of a ragged batch (offset in frame_dev, size, stride) instead of hh / ww / stride /
 // frame_offs
+// tta (or null): `copies` augmented images of every box ride in the same pass (CLAHE once per face, one augment launch, all
+// m x (1 + copies) images through the cascade together, the classifier in chunks of max_batch images); draws: m x copies,
+// face-major; logits_out still receives the un-augmented column, all_out [m][1 + copies] the whole block
+struct TtaCall { int copies; const dfd_tta_draw* draws; float* all_out; };
 int classify_boxes(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride, const int32_t* xywh, int m,
-                   int apply_clahe, const size_t* frame_offs, float* logits_out, const FrameDesc* crop_frames = nullptr);
+                   int apply_clahe, const size_t* frame_offs, float* logits_out, const FrameDesc* crop_frames = nullptr,
+                   const TtaCall* tta = nullptr);
+// The arming of dfd_tta_arm as the fused entry points use it.  tta_take: called first thing by an entry point - consumes
+// the arming (whatever becomes of the call) and checks its capacity against n_frames x max_faces; *armed tells whether the
+// call carries copies.
+constexpr int kMaxTtaCopies = 63;
+int tta_take(dfd_handle* h, long long n_frames, int max_faces, bool* armed);
+int tta_refuse(dfd_handle* h, const char* entry);       // entry points without the feature: DFD_ERR_STATE when armed
+// classify_boxes on m <= max_batch faces of the running fused call; tta: with the arming's next m x copies draws, the
+// [m][1 + copies] block appended to h->tta_logits
+int classify_faces(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride, const int32_t* xywh, int m, int apply_clahe,
+                   float* logits_out, const FrameDesc* crop_frames, bool tta);
+
 // DetectionOutput of `n` frames already resized to 300x300 -> rows/count on the host
 int detect_batch_run(dfd_handle* h, const uint8_t* frames_dev, int n, int hh, int ww, int stride, size_t frame_bytes,
                      float conf_thr, int max_faces, int32_t* xywh_out, int* n_out, int* n_total_out = nullptr);
@@ -241,7 +265,7 @@ const uint8_t* mtcnn_face_dev(dfd_handle* h);
 // imgproc_api.hip: the per-frame work on a frame that is already in h->frame_buf
 int analyze_frame_resident(dfd_handle* h, int stream_id, int hh, int ww, int stride, int full_forensics, float conf_thr,
                            int max_faces, int apply_clahe, double* scores_out, double* forensic_prob_out, int32_t* xywh_out,
-                           int* n_faces_out, float* logits_out);
+                           int* n_faces_out, float* logits_out, bool tta = false);
 
 // jpeg_decode.hip: baseline JPEG bytes -> packed BGR frame in h->frame_buf (stride width * 3)
 int jpeg_decode_to_frame(dfd_handle* h, const uint8_t* jpeg, size_t len, int* hh, int* ww);

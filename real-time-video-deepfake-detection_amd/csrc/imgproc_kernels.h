@@ -31,10 +31,20 @@ void launch_resize_bgr(const uint8_t* src, int n, int sh, int sw, size_t sstride
 void launch_resize_bgr_ragged(const uint8_t* src, const FrameDesc* frames_dev, int n, uint8_t* dst, int dh, int dw,
                               hipStream_t s);
 // single-channel cv2.resize(INTER_LINEAR) and u8 -> float (x scale)
-// test-time augmentation of a face crop (flip, brightness, small rotation) as the reference builds it with cv2;
-// mi = the inverted 2x3 affine matrix (warpAffine's internal form)
-void launch_tta_augment(const uint8_t* src, int h, int w, int stride, int flip, float alpha, const double mi[6], uint8_t* dst,
-                        hipStream_t s);
+// test-time augmentation of face crops (flip, brightness, small rotation) as the reference builds it with cv2: one row per
+// output image.  src_off / dst_off: bytes from the launch's source / destination base; stride: source row stride;
+// m = the inverted 2x3 affine matrix (warpAffine's internal form); tw_log2: tile width of this image (tta_tile_count)
+struct TtaRow {
+    size_t src_off, stride, dst_off;
+    int h, w, flip, tw_log2;
+    float alpha;
+    double m[6];
+};
+// tiles (= blocks) an h x w image takes and the tile width chosen for it
+int tta_tile_count(int h, int w, int* tw_log2);
+// n images, `tiles` blocks in all; tile_start_dev: n + 1 running tile counts
+void launch_tta_augment_batch(const uint8_t* src_base, uint8_t* dst_base, const TtaRow* rows_dev, const int* tile_start_dev, int n,
+                              int tiles, hipStream_t s);
 void launch_resize_gray(const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw, hipStream_t s);
 void u8_to_float(const uint8_t* src, float* dst, int n, float scale, hipStream_t s);
 // both read a crop's source rows with the row stride of its descriptor

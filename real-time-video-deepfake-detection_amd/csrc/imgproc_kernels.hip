@@ -5,6 +5,7 @@
 //   clahe_hist_kernel   BGR->Lab + per-tile histogram/clip/LUT            deepfake_detection.py:363-366
 //   clahe_apply_kernel  4-LUT bilinear blend + Lab->BGR                   deepfake_detection.py:366-368
 //   crop_norm_kernel    bilinear 224x224 + /255 + ImageNet normalise      deepfake_detection.py:382-389
+//   tta_augment_batch_kernel  flip / convertScaleAbs / warpAffine copies  deepfake_detection.py:419-433
 //
 // Compiled with -ffp-contract=off: the float expressions below are written in the exact
 // operation order of the algorithms they restate and must not be fused.
@@ -377,46 +378,96 @@ void launch_crop_norm(const uint8_t* frame, const uint8_t* scratch, const CropDe
 }
 
 // ------------------------------------------------------------------- test-time augmentation
-// One augmented copy of a face crop as reference deepfake_detection.py:419-433 builds it with cv2:
+// An augmented copy of a face crop as reference deepfake_detection.py:419-433 builds it with cv2:
 //   cv2.flip(img, 1) (optional) -> cv2.convertScaleAbs(img, alpha=brightness, beta=0) -> cv2.warpAffine(img,
 //   getRotationMatrix2D((w/2, h/2), angle, 1.0), (w, h))   [INTER_LINEAR, BORDER_CONSTANT 0]
 // composed per destination pixel.  warpAffine as OpenCV computes it: the INVERSE matrix Mi in double, fixed-point
 // source coordinates (10 fractional bits, 5 kept for interpolation: X = (round((Mi[1]*y + Mi[2]) * 1024) + 16 +
 // round(Mi[0]*x * 1024)) >> 5), bilinear weights (32 - fx)(32 - fy) * 32 of 32768, result (sum + 16384) >> 15,
 // samples outside the image = 0.  convertScaleAbs on 8-bit data: saturate(rint(|v * (float)alpha|)).
-__global__ __launch_bounds__(256) void tta_augment_kernel(const uint8_t* __restrict__ src, int h, int w, int stride, int flip, float alpha,
-                                                          double m0, double m1, double m2, double m3, double m4, double m5,
-                                                          uint8_t* __restrict__ dst) {
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (x >= w) return;
-    const int X0 = (int)rint((m1 * y + m2) * 1024.0) + 16, Y0 = (int)rint((m4 * y + m5) * 1024.0) + 16;
-    const int X = (X0 + (int)rint(m0 * x * 1024.0)) >> 5, Y = (Y0 + (int)rint(m3 * x * 1024.0)) >> 5;
-    const int sx = X >> 5, sy = Y >> 5, fx = X & 31, fy = Y & 31;
-    const int wgt[4] = {(32 - fx) * (32 - fy) * 32, fx * (32 - fy) * 32, (32 - fx) * fy * 32, fx * fy * 32};
-    int acc[3] = {0, 0, 0};
+//
+// One launch for every copy of every crop of a call: image r of the table is one (crop, draw) pair.  Source and
+// destination may be one buffer (the packed crops): an image's source and destination regions never overlap.
+// Block = one tile of one image: 1024 destination pixels as tw columns x 1024 / tw rows, tw = 16, 32 or 64 chosen per image
+// by the host (the width that wastes the fewest lanes: a 30 px crop runs 30 of 32 lanes, a 400 px crop 400 of 448), four
+// rows per thread.  Block b finds its image by bisection in `tile_start` (tiles before image r; n + 1 entries), so a launch
+// holds exactly the tiles its images need whatever their sizes.  As OpenCV's warpAffine does, the fp64 terms are computed
+// once and kept as integers: round(Mi[0] * x * 1024) / round(Mi[3] * x * 1024) per column of the tile (adelta / bdelta),
+// X0 / Y0 per row of the tile, both in LDS (1 KB) - a pixel costs two LDS reads and integer arithmetic.
+__global__ __launch_bounds__(256) void tta_augment_batch_kernel(const uint8_t* __restrict__ src_base, uint8_t* __restrict__ dst_base,
+                                                                const TtaRow* __restrict__ rows, const int* __restrict__ tile_start,
+                                                                int n) {
+    __shared__ int adelta[64], bdelta[64], X0s[64], Y0s[64];
+    const int tid = threadIdx.x;
+    int lo = 0, hi = n - 1;                                        // last image whose first tile is <= blockIdx.x
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tile_start[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const TtaRow r = rows[lo];
+    const int tw = 1 << r.tw_log2, th = 1024 >> r.tw_log2;
+    const int tiles_x = (r.w + tw - 1) >> r.tw_log2;
+    const int t = (int)blockIdx.x - tile_start[lo];
+    const int x0 = (t % tiles_x) * tw, y0 = (t / tiles_x) * th;
+    if (tid < tw) {
+        const int x = x0 + tid;
+        adelta[tid] = (int)rint(r.m[0] * x * 1024.0);
+        bdelta[tid] = (int)rint(r.m[3] * x * 1024.0);
+    } else if (tid >= 64 && tid < 64 + th) {                        // th <= 64; another wave than the columns when tw = 64
+        const int y = y0 + tid - 64;
+        X0s[tid - 64] = (int)rint((r.m[1] * y + r.m[2]) * 1024.0) + 16;
+        Y0s[tid - 64] = (int)rint((r.m[4] * y + r.m[5]) * 1024.0) + 16;
+    }
+    __syncthreads();
+    const int col = tid & (tw - 1), x = x0 + col;
+    if (x >= r.w) return;
+    const uint8_t* src = src_base + r.src_off;
+    uint8_t* dst = dst_base + r.dst_off;
+    const int h = r.h, w = r.w, flip = r.flip;
+    const float alpha = r.alpha;
+    const size_t stride = r.stride;
+    const int ad = adelta[col], bd = bdelta[col];
+    for (int ry = tid >> r.tw_log2; ry < th; ry += 256 >> r.tw_log2) {
+        const int y = y0 + ry;
+        if (y >= h) break;
+        const int X = (X0s[ry] + ad) >> 5, Y = (Y0s[ry] + bd) >> 5;
+        const int sx = X >> 5, sy = Y >> 5, fx = X & 31, fy = Y & 31;
+        const int wgt[4] = {(32 - fx) * (32 - fy) * 32, fx * (32 - fy) * 32, (32 - fx) * fy * 32, fx * fy * 32};
+        int acc[3] = {0, 0, 0};
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int yy = sy + (k >> 1), xx = sx + (k & 1);
-        if ((unsigned)yy < (unsigned)h && (unsigned)xx < (unsigned)w) {
-            const uint8_t* p = src + (size_t)yy * stride + 3 * (flip ? w - 1 - xx : xx);
+        for (int k = 0; k < 4; ++k) {
+            const int yy = sy + (k >> 1), xx = sx + (k & 1);
+            if ((unsigned)yy < (unsigned)h && (unsigned)xx < (unsigned)w) {
+                const uint8_t* p = src + (size_t)yy * stride + 3 * (flip ? w - 1 - xx : xx);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float v = fabsf((float)p[c] * alpha);
-                int q = (int)rintf(v);
-                q = q > 255 ? 255 : q;
-                acc[c] += q * wgt[k];
+                for (int c = 0; c < 3; ++c) {
+                    const float v = fabsf((float)p[c] * alpha);
+                    int q = (int)rintf(v);
+                    q = q > 255 ? 255 : q;
+                    acc[c] += q * wgt[k];
+                }
             }
         }
-    }
-    uint8_t* o = dst + ((size_t)y * w + x) * 3;
+        uint8_t* o = dst + ((size_t)y * w + x) * 3;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) o[c] = (uint8_t)((acc[c] + (1 << 14)) >> 15);
+        for (int c = 0; c < 3; ++c) o[c] = (uint8_t)((acc[c] + (1 << 14)) >> 15);
+    }
 }
 
-void launch_tta_augment(const uint8_t* src, int h, int w, int stride, int flip, float alpha, const double mi[6], uint8_t* dst,
-                        hipStream_t s) {
-    hipLaunchKernelGGL(tta_augment_kernel, dim3((w + 255) / 256, h), dim3(256), 0, s, src, h, w, stride, flip, alpha, mi[0], mi[1],
-                       mi[2], mi[3], mi[4], mi[5], dst);
+int tta_tile_count(int h, int w, int* tw_log2) {
+    int best = 6, best_cols = 0;
+    for (int l = 6; l >= 4; --l) {                                  // ties go to the wider tile (fewer blocks)
+        const int cols = ((w + (1 << l) - 1) >> l) << l;
+        if (l == 6 || cols < best_cols) { best = l; best_cols = cols; }
+    }
+    *tw_log2 = best;
+    const int th = 1024 >> best;
+    return (best_cols >> best) * ((h + th - 1) / th);
+}
+
+void launch_tta_augment_batch(const uint8_t* src_base, uint8_t* dst_base, const TtaRow* rows_dev, const int* tile_start_dev, int n,
+                              int tiles, hipStream_t s) {
+    hipLaunchKernelGGL(tta_augment_batch_kernel, dim3(tiles), dim3(256), 0, s, src_base, dst_base, rows_dev, tile_start_dev, n);
 }
 
 }  // namespace dfd

@@ -18,6 +18,7 @@ int dfd_analyze_batch_device(dfd_handle* h, const uint8_t* frames_dev, int n, in
                              int forced_k, float conf_thr, int max_faces, int apply_clahe, int with_forensics,
                              int32_t* xywh_out, int* n_faces_out, float* logits_out, double* forensic_prob_out) {
     if (!h) return DFD_ERR_ARG;
+    if (int rc = tta_refuse(h, "analyze_batch")) return rc;
     if (!frames_dev || n <= 0 || hh <= 0 || ww <= 0 || max_faces <= 0 || !xywh_out || !n_faces_out || !logits_out)
         return fail(h, DFD_ERR_ARG, "analyze_batch: bad pointer or geometry");
     if (forced_xywh && (forced_k <= 0 || forced_k > max_faces))
@@ -95,7 +96,7 @@ namespace {
 int analyze_streams(dfd_handle* h, int n, const uint8_t* const* data, const size_t* len, const int* heights, const int* widths,
                     const int* stream_ids, const int* full_forensics, float conf_thr, int max_faces, int apply_clahe,
                     double* scores_out, double* forensic_prob_out, int32_t* xywh_out, int* n_faces_out, int* n_detected_out,
-                    float* logits_out, int* height_out, int* width_out, int* bad_index_out) {
+                    float* logits_out, int* height_out, int* width_out, int* bad_index_out, bool tta) {
     int rc;
     if (bad_index_out) *bad_index_out = -1;
     std::vector<int> fh(n), fw(n);
@@ -203,8 +204,8 @@ int analyze_streams(dfd_handle* h, int n, const uint8_t* const* data, const size
     std::vector<float> logits(ncrops);
     for (int start = 0; start < ncrops; start += h->max_batch) {
         const int m = std::min(h->max_batch, ncrops - start);
-        if ((rc = classify_boxes(h, frames, 0, 0, 0, boxes.data() + (size_t)start * 4, m, apply_clahe, nullptr, logits.data() + start,
-                                 crop_frames.data() + start)))
+        if ((rc = classify_faces(h, frames, 0, 0, 0, boxes.data() + (size_t)start * 4, m, apply_clahe, logits.data() + start,
+                                 crop_frames.data() + start, tta)))
             return rc;
     }
     int k = 0;
@@ -224,11 +225,13 @@ int dfd_analyze_stream_batch(dfd_handle* h, int stream_id, int n, const uint8_t*
                              double* forensic_prob_out, int32_t* xywh_out, int* n_faces_out, int* n_detected_out,
                              float* logits_out, int* height_out, int* width_out) {
     if (!h) return DFD_ERR_ARG;
+    bool tta = false;
+    int rc = tta_take(h, n, max_faces, &tta);
+    if (rc) return rc;
     if (n <= 0 || !data || !len || !full_forensics || max_faces <= 0 || !scores_out || !forensic_prob_out || !xywh_out ||
         !n_faces_out || !logits_out)
         return fail(h, DFD_ERR_ARG, "analyze_stream_batch: bad pointer or count");
     DFD_HIP_TRY(h, hipSetDevice(h->device));
-    int rc;
     // frame size: from the JPEG headers when there is a JPEG part, else the caller's
     std::vector<const uint8_t*> jp;
     std::vector<size_t> jl;
@@ -245,7 +248,7 @@ int dfd_analyze_stream_batch(dfd_handle* h, int stream_id, int n, const uint8_t*
                     ww, hh, kMaxBatchPixels);
     const std::vector<int> hs(n, hh), ws(n, ww), ids(n, stream_id);
     return analyze_streams(h, n, data, len, hs.data(), ws.data(), ids.data(), full_forensics, conf_thr, max_faces, apply_clahe,
-                           scores_out, forensic_prob_out, xywh_out, n_faces_out, n_detected_out, logits_out, nullptr, nullptr, nullptr);
+                           scores_out, forensic_prob_out, xywh_out, n_faces_out, n_detected_out, logits_out, nullptr, nullptr, nullptr, tta);
 }
 
 int dfd_analyze_streams_batch(dfd_handle* h, int n, const uint8_t* const* data, const size_t* len, const int* heights,
@@ -254,6 +257,8 @@ int dfd_analyze_streams_batch(dfd_handle* h, int n, const uint8_t* const* data, 
                               int* n_detected_out, float* logits_out, int* height_out, int* width_out, int* bad_index_out) {
     if (!h) return DFD_ERR_ARG;
     if (bad_index_out) *bad_index_out = -1;
+    bool tta = false;
+    if (int rc = tta_take(h, n, max_faces, &tta)) return rc;
     if (n <= 0 || !data || !len || !stream_ids || !full_forensics || max_faces <= 0 || !scores_out || !forensic_prob_out ||
         !xywh_out || !n_faces_out || !logits_out)
         return fail(h, DFD_ERR_ARG, "analyze_streams_batch: bad pointer or count");
@@ -262,7 +267,7 @@ int dfd_analyze_streams_batch(dfd_handle* h, int n, const uint8_t* const* data, 
             return fail(h, DFD_ERR_ARG, "analyze_streams_batch: raw frames need heights and widths");
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     return analyze_streams(h, n, data, len, heights, widths, stream_ids, full_forensics, conf_thr, max_faces, apply_clahe, scores_out,
-                           forensic_prob_out, xywh_out, n_faces_out, n_detected_out, logits_out, height_out, width_out, bad_index_out);
+                           forensic_prob_out, xywh_out, n_faces_out, n_detected_out, logits_out, height_out, width_out, bad_index_out, tta);
 }
 
 
@@ -289,6 +294,7 @@ int dfd_analyze_frames_host(dfd_handle* h, const uint8_t* frames_host, int n_tot
                             int with_forensics, int32_t* xywh_out, int* n_faces_out, float* logits_out,
                             double* forensic_prob_out) {
     if (!h) return DFD_ERR_ARG;
+    if (int rc = tta_refuse(h, "analyze_frames_host")) return rc;
     if (!frames_host || n_total <= 0 || batch <= 0 || hh <= 0 || ww <= 0 || max_faces <= 0)
         return fail(h, DFD_ERR_ARG, "analyze_frames_host: bad pointer or geometry");
     DFD_HIP_TRY(h, hipSetDevice(h->device));

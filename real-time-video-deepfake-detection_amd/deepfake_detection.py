@@ -13,8 +13,10 @@ head conv the reference hooks (`dfd_gradcam_crops`); `DeepfakeDetector.explain_f
 its heat map and BGR overlay, while `analyze_face` keeps returning None in its third slot whatever `enable_gradcam` is,
 as the reference does (:543-546; GradCAM is disabled in its shipped configurations, :730-736 and
 backend_server.py:57).  Deliberate differences: frames are returned un-annotated, nothing is
-printed per frame.  TTA (:408-443) is
-`analyze_face_with_tta` over `dfd_tta_augment`.  Face detection inside the fused call follows the reference's
+printed per frame.  TTA (:408-443): `analyze_face`
+keeps the per-face path (`analyze_face_with_tta` over `dfd_tta_augment`); `predict`, `analyze_request` and
+`analyze_request_batch` (these two with `request_tta=True`) carry every face's augmented copies inside their one library call (`dfd_tta_arm`; draws and the
+`random` stream: `tta_draw_table` / `tta_commit_draws`) - the same probabilities, bit for bit.  Face detection inside the fused call follows the reference's
 `detect_bounding_box` (face_detection.py:58-66): the SSD when the handle carries one, else - and after an SSD failure -
 the Haar cascade, else no faces ('frame_only').
 """
@@ -23,6 +25,7 @@ from __future__ import annotations
 import logging
 import os
 import pickle
+import random
 import threading
 from typing import List, Optional
 
@@ -49,6 +52,27 @@ def _sigmoid32(logit) -> float:
     return float(np.float32(1.0) / (np.float32(1.0) + np.exp(-x, dtype=np.float32)))
 
 
+def tta_draw_table(capacity_faces: int, copies: int):
+    """The draws of a call that may return up to `capacity_faces` faces, taken from Python's global `random` in the
+    reference's order (:419-426: per face, per copy `random() > 0.5`, `uniform(0.9, 1.1)`, `uniform(-3, 3)` - all three
+    always) -> (the generator state before the first draw, [(flip, brightness, angle_deg)] face-major).  The number of
+    faces is known only after the call: `tta_commit_draws` then leaves the stream where the used rows end."""
+    state = random.getstate()
+    draws = [(random.random() > 0.5, random.uniform(0.9, 1.1), random.uniform(-3, 3))
+             for _ in range(int(capacity_faces) * int(copies))]
+    return state, draws
+
+
+def tta_commit_draws(state, n_faces: int, copies: int):
+    """Rewind `random` to `state` and draw again exactly the rows `n_faces` faces used: the global stream is then where
+    the reference's per-face loop would have left it (untouched for a call without faces)."""
+    random.setstate(state)
+    for _ in range(int(n_faces) * int(copies)):
+        random.random()
+        random.uniform(0.9, 1.1)
+        random.uniform(-3, 3)
+
+
 class _LazyModel:
     """`model` global of the reference (:32): the classifier bound to the default handle."""
 
@@ -73,9 +97,13 @@ model = _LazyModel()
 
 class DeepfakeDetector:
     def __init__(self, enable_gradcam=False, use_tta=True, num_tta_augmentations=3, detection_threshold=0.5,
-                 face_weight=0.70, forensic_weight=0.30, *, handle: Optional[Handle] = None):
+                 face_weight=0.70, forensic_weight=0.30, *, handle: Optional[Handle] = None, request_tta: bool = False):
         self.enable_gradcam = enable_gradcam
         self.use_tta = use_tta
+        # the /analyze flow (analyze_request, analyze_request_batch, the session pool) carries the copies only when this is
+        # set as well: callers of that flow construct detectors with the reference's constructor defaults (TTA on) and
+        # rely on the single classification it has always made there; `predict` follows use_tta alone, as before
+        self.request_tta = bool(request_tta)
         self.num_tta_augmentations = num_tta_augmentations
         self.detection_threshold = detection_threshold
         self.face_weight = face_weight                  # stored, never used - as in the reference
@@ -132,8 +160,36 @@ class DeepfakeDetector:
         adjustment = 0.10 if (h < 80 or w < 80) else 0.0
         return np.clip(fake_prob + adjustment, 0, 1)
 
+    def _tta_copies(self, request: bool = False) -> int:
+        """augmented copies per face the fused calls carry (0: TTA off; reference :524); request: for the /analyze flow"""
+        if request and not self.request_tta:
+            return 0
+        return self.num_tta_augmentations - 1 if self.use_tta and self.num_tta_augmentations > 1 else 0
+
+    def _armed(self, call, capacity_faces, request, **kw):
+        """`call(**kw)`; with TTA on, armed with the draws of `capacity_faces` faces, and `random` is left after the
+        draws of the faces the call returned (none when it raises)"""
+        copies = self._tta_copies(request)
+        if copies == 0:
+            return call(**kw)
+        state, draws = tta_draw_table(capacity_faces, copies)
+        used = 0
+        try:
+            out = call(tta=(copies, draws), **kw)
+            used = self.handle.tta_logits().shape[0]
+            return out
+        finally:
+            tta_commit_draws(state, used, copies)
+
     def _finish_face(self, logit, h, w):
-        """None when the MTCNN stage found no face in the crop (NaN logit from the library)."""
+        """None when the MTCNN stage found no face in the crop (NaN logit from the library).  `logit` is a scalar, or -
+        from a call that carried augmented copies - the face's row (original, copies): the mean of the sigmoids of
+        the images the cascade kept, in `analyze_face_with_tta`'s arithmetic (reference :436-441)."""
+        if logit is not None and np.ndim(logit) == 1:
+            predictions = [_sigmoid32(v) for v in logit if not np.isnan(v)]
+            if not predictions:
+                return None
+            return self._heuristics_hw(self.apply_calibration(float(np.mean(predictions))), h, w)
         if logit is None or np.isnan(logit):
             return None
         p = self.apply_calibration(_sigmoid32(logit))
@@ -169,8 +225,6 @@ class DeepfakeDetector:
         """reference :408-443: the original plus num_tta_augmentations - 1 randomly augmented copies (horizontal flip
         with probability 1/2, brightness x U(0.9, 1.1), rotation by U(-3, 3) degrees about the centre), each through
         `_single_prediction`, averaged.  The draws come from Python's `random` in the reference's order."""
-        import random
-
         predictions = []
         pred = self._single_prediction(face_region)
         if pred is not None:
@@ -227,14 +281,16 @@ class DeepfakeDetector:
             return None
         return {'fake_probability': p, 'heatmap': heat[0], 'overlay': overlay[0]}
 
-    def _frame_on_gpu(self, frame, max_faces, jpeg: Optional[bytes] = None):
-        """forensics + detection + per-face logits in one library call.  With `jpeg` the frame is decoded on the
+    def _frame_on_gpu(self, frame, max_faces, jpeg: Optional[bytes] = None, request: bool = False):
+        """forensics + detection + per-face logits in one library call (with TTA on: every face's row of logits, original
+        and augmented copies, from the same call).  With `jpeg` the frame is decoded on the
         device from the request's bytes (dfd_analyze_jpeg) instead of uploaded raw; returns its (H, W) as 4th item."""
         full = self._forensic_is_full()
         with self._lock:
             if jpeg is not None:
-                scores, prob, boxes, logits, shape = self.handle.analyze_jpeg(
-                    jpeg, full, stream_id=self.frame_analyzer.stream_id, confidence_threshold=0.5, max_faces=max_faces)
+                scores, prob, boxes, logits, shape = self._armed(
+                    self.handle.analyze_jpeg, max_faces, request, data=jpeg, full_forensics=full,
+                    stream_id=self.frame_analyzer.stream_id, confidence_threshold=0.5, max_faces=max_faces)
                 number = self.frame_analyzer.frame_count
                 forensic = {'scores': scores, 'fake_probability': prob,
                             'analysis_type': 'frame_forensic' if full else 'frame_forensic_fast', 'frame_number': number}
@@ -242,8 +298,9 @@ class DeepfakeDetector:
                 return forensic, boxes, logits, shape
             if self.handle.has_detector or self.handle.has_haar:
                 # SSD, or the reference's Haar fallback (face_detection.py:58-61), inside the same library call
-                scores, prob, boxes, logits = self.handle.analyze_frame(
-                    frame, full, stream_id=self.frame_analyzer.stream_id, confidence_threshold=0.5, max_faces=max_faces)
+                scores, prob, boxes, logits = self._armed(
+                    self.handle.analyze_frame, max_faces, request, frame=frame, full_forensics=full,
+                    stream_id=self.frame_analyzer.stream_id, confidence_threshold=0.5, max_faces=max_faces)
             else:                                   # no detector of either kind: 'frame_only' mode (runtime.py)
                 scores, prob, _ = self.handle.forensics(frame, full=full, stream_id=self.frame_analyzer.stream_id)
                 boxes, logits = [], []
@@ -265,10 +322,10 @@ class DeepfakeDetector:
         face_results: List[dict] = []
         confidence_level = self.temporal_tracker.get_confidence_level()
         if len(faces) > 0:
-            tta = self.use_tta and self.num_tta_augmentations > 1
             for (x, y, w, h), logit in zip(faces, logits):
-                # with TTA every face goes through analyze_face (augmented copies), as the reference does (:614)
-                fake_prob = self.analyze_face(frame[y:y + h, x:x + w])[0] if tta else self._finish_face(logit, h, w)
+                # with TTA `logit` is the face's row from the same call (original + augmented copies): what the
+                # reference's analyze_face computes per face (:614), without a second classification
+                fake_prob = self._finish_face(logit, h, w)
                 if fake_prob is None:                                        # reference :616-617
                     continue
                 self.temporal_tracker.update(fake_prob)
@@ -308,12 +365,12 @@ class DeepfakeDetector:
                 frame = self.handle.decode_jpeg(jpeg)              # frame_only mode has no fused JPEG entry point
                 jpeg = None
             else:
-                frame_forensic, faces, logits, shape = self._frame_on_gpu(None, max_faces=1, jpeg=jpeg)
+                frame_forensic, faces, logits, shape = self._frame_on_gpu(None, max_faces=1, jpeg=jpeg, request=True)
                 small = shape[0] < 30 or shape[1] < 30
         if jpeg is None:
             frame = np.ascontiguousarray(frame)
             small = frame.shape[0] < 30 or frame.shape[1] < 30
-            frame_forensic, faces, logits = self._frame_on_gpu(frame, max_faces=1)
+            frame_forensic, faces, logits = self._frame_on_gpu(frame, max_faces=1, request=True)
         n_detected = 0 if small else self._last_face_count(frame, faces)
         return self._request_response(frame_forensic['fake_probability'], [] if small else faces, logits, n_detected)
 
@@ -361,8 +418,8 @@ class DeepfakeDetector:
         full = [(self.frame_count + i) % self.full_forensic_interval == 0 for i in range(n)]
         with self._lock:
             if self.handle.has_detector or self.handle.has_haar:
-                res, shape = self.handle.analyze_stream_batch(items, full, stream_id=self.frame_analyzer.stream_id,
-                                                              confidence_threshold=0.5, max_faces=1)
+                res, shape = self._armed(self.handle.analyze_stream_batch, n, True, items=items, full_flags=full,
+                                         stream_id=self.frame_analyzer.stream_id, confidence_threshold=0.5, max_faces=1)
             else:                                                   # no detector of either kind: forensics only, frame by frame
                 res, shape = [], None
                 for it, fl in zip(items, full):

@@ -23,7 +23,7 @@ from typing import Optional
 import numpy as np
 
 from ._lib import DfdError, Handle
-from .deepfake_detection import DeepfakeDetector
+from .deepfake_detection import DeepfakeDetector, tta_commit_draws, tta_draw_table
 
 MAX_PASS_FRAMES = 256                     # frames of one device pass (the classifier runs them in max_batch chunks)
 MAX_PASS_PIXELS = 1 << 27                 # the library's per-call budget (dfd_common.h kMaxBatchPixels)
@@ -92,8 +92,13 @@ def _pillow_bgr(data: bytes):
 
 class SessionPool:
     def __init__(self, handle: Optional[Handle] = None, lock=None, detection_threshold: float = 0.55,
-                 max_sessions: int = 1024, idle_seconds: float = 300):
+                 max_sessions: int = 1024, idle_seconds: float = 300, use_tta: bool = False, num_tta_augmentations: int = 1):
         self._handle = handle
+        # test-time augmentation for every session: the pass's one library call is armed with the draws of all its frames.
+        # Draw order = the order results are applied to sessions: submissions in queue order, a submission's frames in
+        # stream order (Python's global `random`, left where that many per-face calls would have left it)
+        self.use_tta = bool(use_tta)
+        self.num_tta_augmentations = int(num_tta_augmentations)
         self.lock = lock if lock is not None else threading.Lock()
         self.detection_threshold = detection_threshold
         self.max_sessions = int(max_sessions)
@@ -127,7 +132,9 @@ class SessionPool:
             return None
         if len(self._sessions) >= self.max_sessions:
             evicted.append(self._evict_one())
-        s = _Session(sid, DeepfakeDetector(enable_gradcam=False, use_tta=False, num_tta_augmentations=1,
+        s = _Session(sid, DeepfakeDetector(enable_gradcam=False, use_tta=self.use_tta,
+                                           num_tta_augmentations=self.num_tta_augmentations,
+                                           request_tta=self.use_tta,
                                            detection_threshold=self.detection_threshold, handle=self.handle))
         self._sessions[sid] = s
         return s
@@ -264,8 +271,18 @@ class SessionPool:
                     ids.append(d.frame_analyzer.stream_id)
                     full.append((d.frame_count + k + i) % d.full_forensic_interval == 0)
                 offset[s] = k + len(items)
+            copies = self.num_tta_augmentations - 1 if self.use_tta and self.num_tta_augmentations > 1 else 0
             try:
-                res = self.handle.analyze_streams_batch(flat, ids, full, confidence_threshold=0.5, max_faces=1)
+                if copies > 0:
+                    state, draws = tta_draw_table(len(flat), copies)     # max_faces = 1: at most one face per frame
+                    res = None
+                    try:
+                        res = self.handle.analyze_streams_batch(flat, ids, full, confidence_threshold=0.5, max_faces=1,
+                                                                tta=(copies, draws))
+                    finally:                                             # a refused call used no draw
+                        tta_commit_draws(state, 0 if res is None else sum(len(r[2]) for r in res), copies)
+                else:
+                    res = self.handle.analyze_streams_batch(flat, ids, full, confidence_threshold=0.5, max_faces=1)
             except DfdError as e:
                 # a refusal of one part (its headers, or its scan while decoding), raised before any stream state has
                 # moved: that part is decoded with Pillow (as the server does for /analyze) or its submission alone fails,
