@@ -426,6 +426,27 @@ int dfd_forensics_state(dfd_handle* h, int stream_id, int* frame_count, int* n_d
 int dfd_forensic_tap(dfd_handle* h, const uint8_t* bgr256, int n, int full, const char* start, const void* start_data,
                      const char* name, int frame, void* out, size_t capacity, size_t* bytes);
 
+/* ---- frame forensics at any square analysis size ---------------------------------------------
+ * FrameForensicAnalyzer(analysis_size=(size, size)) of the reference (frame_analysis.py:28-46): dfd_forensics with the
+ * resize target, the band radii size/8, size/4, size/2 around (size/2, size/2), the 32x32 blocks at i, j in
+ * range(0, size - 31, 32) and every divisor derived from `size`, a multiple of 16 in 32..1024 (anything else:
+ * DFD_ERR_ARG).  With fewer than 4 blocks (size < 64) the noise and ELA scores are 0.0 and their statistics NaN.
+ * Outputs as dfd_forensics.  size = 256 is accepted and runs this general chain, not the 256x256 kernels.
+ * A stream's analysis size is fixed by its first frame: this entry at another size, or dfd_forensics / dfd_analyze_* /
+ * the batched stream entries (all 256x256) on a stream of another size, return DFD_ERR_STATE and change nothing.
+ * dfd_forensics_reset keeps size and plane; dfd_forensics_release returns the size x size plane to a free list keyed
+ * by plane size, after which the id may start again at any size. */
+int dfd_forensics_sized(dfd_handle* h, int stream_id, const uint8_t* bgr, int height, int width, int stride, int size,
+                        int full, double* scores_out, double* prob_out, double* stats_out);
+/* dfd_forensic_tap for the general chain: n (1..16) frames that are already size x size.  Same buffer names and
+ * teacher-forcing starts; per frame, with S = size: "rs" u8[S][S][3]; "gray", "map", "jy", "edges" u8[S][S]; "jcb",
+ * "jcr" u8[S/2][S/2]; "grad" i16[S][S][2]; "fft_tmp" (row pass), "spectrum" (both passes)
+ * complex64 [S][S] and "logmag" f32 [S][S] ([kx][ky]);
+ * f64 "fft_part" [S][7], "lap_part" [S][2], "hsv_part" [S][4] (one partial per row), "stats_noise", "stats_ela"
+ * [(S/32)^2], "edge_count" [1], "stats" [9] / [6]; "hue_bits" u32[6]; "twiddle" complex64 [S], exp(-2 pi i j / S). */
+int dfd_forensic_tap_sized(dfd_handle* h, const uint8_t* frames, int n, int size, int full, const char* start,
+                           const void* start_data, const char* name, int frame, void* out, size_t capacity, size_t* bytes);
+
 /* ---- one frame, end to end ---------------------------------------------------------------
  * The per-frame work of DeepfakeDetector.predict (reference deepfake_detection.py:597-626)
  * and of the /analyze handler (reference backend_server.py:147-164) with ONE upload of the

@@ -134,6 +134,10 @@ SIGNATURES = {
                                          C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dfd_forensic_tap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_void_p, C.c_char_p, C.c_int,
                                    C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "dfd_forensics_sized": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dfd_forensic_tap_sized": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_void_p, C.c_char_p,
+                                         C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "dfd_forensic_signals_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
     "dfd_comm_unique_id": (C.c_int, [C.c_void_p]),
@@ -580,6 +584,52 @@ class Handle:
         self._check(self._lib.dfd_forensic_tap(self._p, _ptr(a) if start == "rs" else None, a.shape[0], int(bool(full)),
                                                start.encode(), None if start == "rs" else _ptr(a), name.encode(), int(frame),
                                                _ptr(out), out.nbytes, C.byref(cnt)))
+        assert cnt.value == out.nbytes, (name, cnt.value, out.nbytes)
+        return out[0] if (frame >= 0 or name == "twiddle") else out
+
+    # ---- any square analysis size (dfd_forensics_sized / dfd_forensic_tap_sized)
+    def forensics_sized(self, frame, size: int, full: bool = True, stream_id: int = 0):
+        """`forensics` at analysis size (size, size), a multiple of 16 in 32..1024 -> (scores dict, fake_probability,
+        stats dict).  A stream keeps the size of its first frame until it is released."""
+        a = self._as_bgr(frame)
+        sc = np.empty(6, np.float64)
+        st = np.empty(len(self.FORENSIC_STAT_KEYS), np.float64)
+        prob = C.c_double()
+        self._check(self._lib.dfd_forensics_sized(self._p, int(stream_id), _ptr(a), a.shape[0], a.shape[1], a.strides[0],
+                                                  int(size), int(bool(full)), _ptr(sc), C.byref(prob), _ptr(st)))
+        scores = {k: float(v) for k, v in zip(self.FORENSIC_KEYS, sc) if not np.isnan(v)}
+        return scores, float(prob.value), dict(zip(self.FORENSIC_STAT_KEYS, (float(v) for v in st)))
+
+    @staticmethod
+    def forensic_taps_sized(size: int):
+        """per-frame dtype and shape of every dfd_forensic_tap_sized buffer, and of its four starts"""
+        s, c, nb = int(size), int(size) // 2, (int(size) // 32) ** 2
+        taps = {"rs": (np.uint8, (s, s, 3)), "gray": (np.uint8, (s, s)), "fft_tmp": (np.complex64, (s, s)),
+                "spectrum": (np.complex64, (s, s)), "logmag": (np.float32, (s, s)), "fft_part": (np.float64, (s, 7)),
+                "grad": (np.int16, (s, s, 2)), "lap_part": (np.float64, (s, 2)), "map": (np.uint8, (s, s)),
+                "edges": (np.uint8, (s, s)), "edge_count": (np.float64, (1,)), "jy": (np.uint8, (s, s)),
+                "jcb": (np.uint8, (c, c)), "jcr": (np.uint8, (c, c)), "stats_ela": (np.float64, (nb,)),
+                "stats_noise": (np.float64, (nb,)), "hsv_part": (np.float64, (s, 4)), "hue_bits": (np.uint32, (6,)),
+                "stats": (np.float64, (9,)), "twiddle": (np.complex64, (s,))}
+        return taps, {k: taps[k] for k in ("rs", "gray", "grad", "map")}
+
+    def forensic_tap_sized(self, data, size: int, name: str, full: bool = True, start: str = "rs", frame: int = -1) -> np.ndarray:
+        """Test entry: `forensic_tap` for the general chain at analysis size (size, size); `data` = n <= 16 frames of the
+        `start` buffer at that size."""
+        taps, starts = self.forensic_taps_sized(size)
+        dt, shp = starts[start]
+        a = np.ascontiguousarray(np.asarray(data))
+        if a.dtype != dt or a.shape[1:] != shp:
+            raise ValueError(f"start '{start}' takes (n,) + {shp} {np.dtype(dt).name}, got {a.shape} {a.dtype}")
+        odt, oshp = taps[name]
+        if name == "stats" and not (full and start == "rs"):
+            oshp = (6,)
+        nout = 1 if (frame >= 0 or name == "twiddle") else a.shape[0]
+        out = np.empty((nout,) + oshp, odt)
+        cnt = C.c_size_t()
+        self._check(self._lib.dfd_forensic_tap_sized(self._p, _ptr(a) if start == "rs" else None, a.shape[0], int(size),
+                                                     int(bool(full)), start.encode(), None if start == "rs" else _ptr(a),
+                                                     name.encode(), int(frame), _ptr(out), out.nbytes, C.byref(cnt)))
         assert cnt.value == out.nbytes, (name, cnt.value, out.nbytes)
         return out[0] if (frame >= 0 or name == "twiddle") else out
 

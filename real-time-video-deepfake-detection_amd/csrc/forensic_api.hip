@@ -6,13 +6,15 @@
 
 #include "dfd_common.h"
 #include "forensic_kernels.h"
+#include "forensic_sized_kernels.h"
 
 using namespace dfd;
 
 namespace dfd {
 
 struct ForensicStream {
-    void* prev_gray = nullptr;     // 65536 bytes on the device
+    void* prev_gray = nullptr;     // size * size bytes on the device
+    int size = 0;                  // analysis edge, fixed by the stream's first frame (0: no frame yet)
     bool has_prev = false;
     std::deque<double> diffs;      // last 30 mean absolute differences
     int frame_count = 0;
@@ -29,7 +31,16 @@ struct ForensicState {
     double* host_res = nullptr;    // pinned: statistics of a batch that ran on the second stream (forensics_batch_begin)
     size_t host_res_cap = 0;
     DevBuf frame_desc, prev_tab, copy_tab;   // forensics_streams_run: FrameDesc [n], predecessor planes [n], write-backs
-    std::vector<void*> free_planes;          // stored planes of released streams, reused by the next new stream
+    std::map<int, std::vector<void*>> free_planes;   // stored planes of released streams by analysis edge, reused by the
+                                                     // next new stream of that edge
+    struct Sized {                           // dfd_forensics_sized / dfd_forensic_tap_sized: per analysis edge
+        DevBuf work, tap_store;
+        int cap = 0;
+        ForensicBuffers buf{};
+        float2* table = nullptr;             // exp(-2 pi i j / S), S entries
+        double* diff_part = nullptr;         // S partial sums
+    };
+    std::map<int, Sized> sized;
     DevBuf tap_store;                        // dfd_forensic_tap: spectrum, logmag, edges; allocated on its first call
 };
 
@@ -83,7 +94,9 @@ double pop_std(const double* v, int n, double* mean_out) {
 double clip01(double v) { return v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v); }
 
 // the five stateless signals from the device statistics (frame_analysis.py:150-347); sc[5] (temporal) = 0
-void static_scores(const double* st, const double* noise, const double* ela, bool full, double* sc, double* ex) {
+// npix: pixels of the analysis image; nblk: its 32x32 blocks (fewer than 4: noise and ELA score 0.0, reference :204,:255)
+void static_scores(const double* st, const double* noise, const double* ela, bool full, double* sc, double* ex,
+                   double npix = 65536.0, int nblk = 64, bool f32_means = false) {
     const double nan = std::nan("");
     sc[0] = 0; sc[1] = nan; sc[2] = nan; sc[3] = 0; sc[4] = nan; sc[5] = 0;
     // ---- frequency (:150-180)
@@ -96,25 +109,31 @@ void static_scores(const double* st, const double* noise, const double* ela, boo
     if (mr > 0.45 && hr < 0.2) s += 0.15;
     sc[0] = clip01(s);
     // ---- edges (:296-309)
-    const double density = st[ST_EDGE_COUNT] / 65536.0, lap_var = st[ST_LAP_VAR];
+    const double density = st[ST_EDGE_COUNT] / npix, lap_var = st[ST_LAP_VAR];
     s = 0.0;
     if (density < 0.02) s += 0.35; else if (density < 0.04) s += 0.15;
     if (lap_var < 50) s += 0.3; else if (lap_var < 100) s += 0.1;
     sc[3] = clip01(s);
     double noise_mean = nan, noise_cv = nan, ela_mean = nan, ela_cv = nan;
-    if (full) {
+    if (full && nblk < 4) sc[1] = sc[2] = 0.0;
+    if (full && nblk >= 4) {
         // ---- noise (:207-225)
-        noise_cv = pop_std(noise, 64, &noise_mean) / (noise_mean + 1e-10);
+        noise_cv = pop_std(noise, nblk, &noise_mean) / (noise_mean + 1e-10);
         s = 0.0;
         if (noise_cv > 0.7) s += 0.5; else if (noise_cv > 0.5) s += 0.25;
         if (noise_mean < 1.0) s += 0.3; else if (noise_mean < 2.0) s += 0.1;
         sc[1] = clip01(s);
         // ---- ELA (:258-276)
-        ela_cv = pop_std(ela, 64, &ela_mean) / (ela_mean + 1e-10);
+        ela_cv = pop_std(ela, nblk, &ela_mean);
+        // the reference's block means are float32 and so is their mean (:250-256); at 256x256 the quotient by 64 is exact
+        if (f32_means) ela_mean = (double)(float)ela_mean;
+        ela_cv = ela_cv / (ela_mean + 1e-10);
         s = 0.0;
         if (ela_cv > 0.9) s += 0.5; else if (ela_cv > 0.6) s += 0.2;
         if (ela_mean > 15) s += 0.2; else if (ela_mean > 10) s += 0.1;
         sc[2] = clip01(s);
+    }
+    if (full) {
         // ---- colour (:326-347)
         s = 0.0;
         if (st[ST_SAT_STD] < 15) s += 0.3; else if (st[ST_SAT_STD] < 25) s += 0.1;
@@ -131,17 +150,19 @@ void static_scores(const double* st, const double* noise, const double* ela, boo
 // has one), then the weighted sum in the reference's dict order (:49-56,88 / :118-119).  sc[6] / ex[10] as static_scores;
 // *mean_diff / *temporal_cv: -1 / NaN when not computed.
 double score_frame(ForensicStream& S, const double* st, const double* noise, const double* ela, bool full, const double* dpart,
-                   double* sc, double* ex, double* mean_diff, double* temporal_cv) {
+                   double* sc, double* ex, double* mean_diff, double* temporal_cv, int npart = 256, double npix = 65536.0,
+                   int nblk = 64, bool f32_means = false) {
     S.frame_count += 1;                                              // frame_analysis.py:68,110
-    static_scores(st, noise, ela, full, sc, ex);
+    static_scores(st, noise, ela, full, sc, ex, npix, nblk, f32_means);
     *mean_diff = -1.0;
     *temporal_cv = std::nan("");
     if (!S.has_prev) {
         S.has_prev = true;
     } else {
         double sum = 0;
-        for (int i = 0; i < 256; ++i) sum += dpart[i];
-        const double md = sum / 65536.0;
+        for (int i = 0; i < npart; ++i) sum += dpart[i];
+        // np.mean of a float32 plane (:364): the integer sum (exact in float32 below 2^24) divided in float32
+        const double md = f32_means ? (double)((float)sum / (float)npix) : sum / npix;
         *mean_diff = md;
         S.diffs.push_back(md);
         if (S.diffs.size() > 30) S.diffs.pop_front();
@@ -170,16 +191,54 @@ double score_frame(ForensicStream& S, const double* st, const double* noise, con
 }
 
 // the stream's stored gray plane: a released stream's plane when there is one (no hipMalloc on the serving path)
-int stream_plane(dfd_handle* h, ForensicStream& S) {
+int stream_plane(dfd_handle* h, ForensicStream& S, int size = 256) {
     if (S.prev_gray) return DFD_OK;
     ForensicState& F = *h->forensic;
-    if (!F.free_planes.empty()) {
-        S.prev_gray = F.free_planes.back();
-        F.free_planes.pop_back();
+    std::vector<void*>& fl = F.free_planes[size];
+    if (!fl.empty()) {
+        S.prev_gray = fl.back();
+        fl.pop_back();
+        S.size = size;
         return DFD_OK;
     }
-    DFD_HIP_TRY(h, hipMalloc(&S.prev_gray, 65536));
+    DFD_HIP_TRY(h, hipMalloc(&S.prev_gray, (size_t)size * size));
     h->owned.push_back(S.prev_gray);
+    S.size = size;
+    return DFD_OK;
+}
+
+// a stream's analysis edge is fixed by its first frame: any entry at another edge is refused before it touches anything
+int stream_size_check(dfd_handle* h, int stream_id, int size) {
+    if (!h->forensic) return DFD_OK;
+    auto it = h->forensic->streams.find(stream_id);
+    if (it != h->forensic->streams.end() && it->second.size && it->second.size != size)
+        return fail(h, DFD_ERR_STATE, "forensics: stream %d runs at analysis size %d, this call at %d (dfd_forensics_release frees it)",
+                    stream_id, it->second.size, size);
+    return DFD_OK;
+}
+
+int sized_init(dfd_handle* h, int S, int frames, ForensicState::Sized** out) {
+    ForensicState& F = *h->forensic;
+    ForensicState::Sized& Z = F.sized[S];
+    if (!Z.table) {
+        std::vector<float2> tw(S);
+        forensic_sized_table(S, tw.data());
+        void* d = nullptr;
+        DFD_HIP_TRY(h, hipMalloc(&d, (size_t)S * sizeof(float2)));
+        h->owned.push_back(d);
+        DFD_HIP_TRY(h, hipMemcpy(d, tw.data(), (size_t)S * sizeof(float2), hipMemcpyHostToDevice));
+        Z.table = static_cast<float2*>(d);
+        DFD_HIP_TRY(h, hipMalloc(&d, (size_t)S * 8));
+        h->owned.push_back(d);
+        Z.diff_part = static_cast<double*>(d);
+    }
+    if (frames > Z.cap) {
+        const int rc = ensure(h, &Z.work, forensic_sized_bytes_per_frame(S) * frames + 65536);
+        if (rc) return rc;
+        forensic_sized_carve(Z.work.p, S, frames, &Z.buf);
+        Z.cap = frames;
+    }
+    *out = &Z;
     return DFD_OK;
 }
 
@@ -191,8 +250,9 @@ namespace dfd {
 int forensics_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh, int ww, int stride, int full,
                   double* scores_out, double* prob_out, double* stats_out) {
     if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
-    int rc = state_init(h, 1);
+    int rc = stream_size_check(h, stream_id, 256);
     if (rc) return rc;
+    if ((rc = state_init(h, 1))) return rc;
     ForensicState& F = *h->forensic;
     ForensicStream& S = F.streams[stream_id];
     if ((rc = stream_plane(h, S))) return rc;
@@ -235,8 +295,10 @@ int forensics_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh
 int forensics_streams_run(dfd_handle* h, const uint8_t* frames_dev, const FrameDesc* fd, int n, const int* stream_ids,
                           const int* full, double* scores_out, double* prob_out) {
     if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
-    int rc = state_init(h, n);
-    if (rc) return rc;
+    int rc = DFD_OK;
+    for (int f = 0; f < n; ++f)
+        if ((rc = stream_size_check(h, stream_ids[f], 256))) return rc;
+    if ((rc = state_init(h, n))) return rc;
     ForensicState& F = *h->forensic;
     bool any_full = false;
     std::vector<const uint8_t*> prev(n);
@@ -525,7 +587,7 @@ int dfd_forensics_release(dfd_handle* h, int stream_id) {
     ForensicState& F = *h->forensic;
     auto it = F.streams.find(stream_id);
     if (it == F.streams.end()) return DFD_OK;
-    if (it->second.prev_gray) F.free_planes.push_back(it->second.prev_gray);   // every call that used it has synchronised
+    if (it->second.prev_gray) F.free_planes[it->second.size].push_back(it->second.prev_gray);   // every call that used it has synchronised
     F.streams.erase(it);
     return DFD_OK;
 }
@@ -544,6 +606,136 @@ int dfd_forensics_state(dfd_handle* h, int stream_id, int* frame_count, int* n_d
     if (frame_count) *frame_count = fc;
     if (n_diffs) *n_diffs = nd;
     if (has_prev) *has_prev = hp;
+    return DFD_OK;
+}
+
+// ---- any square analysis size (forensic_sized_kernels.hip): the same host half, S in place of 256
+int dfd_forensics_sized(dfd_handle* h, int stream_id, const uint8_t* bgr, int hh, int ww, int stride, int size, int full,
+                        double* scores_out, double* prob_out, double* stats_out) {
+    if (!h) return DFD_ERR_ARG;
+    if (!bgr || !scores_out || !prob_out || hh <= 0 || ww <= 0 || stride < ww * 3)
+        return fail(h, DFD_ERR_ARG, "forensics_sized: bad pointer or geometry");
+    if (!sized_ok(size))
+        return fail(h, DFD_ERR_ARG, "forensics_sized: analysis size %d is not a multiple of 16 in %d..%d", size, SIZED_MIN, SIZED_MAX);
+    if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    int rc = stream_size_check(h, stream_id, size);
+    if (rc) return rc;
+    if ((rc = ensure(h, &h->frame_buf, (size_t)hh * stride))) return rc;
+    DFD_HIP_TRY(h, hipMemcpyAsync(h->frame_buf.p, bgr, (size_t)hh * stride, hipMemcpyHostToDevice, h->stream));
+    if ((rc = state_init(h, 1))) return rc;
+    ForensicState& F = *h->forensic;
+    ForensicState::Sized* Z = nullptr;
+    if ((rc = sized_init(h, size, 1, &Z))) return rc;
+    ForensicStream& S = F.streams[stream_id];
+    if ((rc = stream_plane(h, S, size))) return rc;
+    const size_t pix = (size_t)size * size;
+    const int nblk = sized_blocks(size);
+    const ForensicBuffers& B = Z->buf;
+
+    launch_resize_bgr((const uint8_t*)h->frame_buf.p, 1, hh, ww, stride, 0, B.rs, size, size, h->stream);
+    DFD_HIP_TRY(h, launch_forensics_sized(B, size, 1, full != 0, h->color, Z->table, h->stream));
+    if (S.has_prev) launch_absdiff_sized(B.gray, (const uint8_t*)S.prev_gray, Z->diff_part, size, h->stream);
+    double st[FORENSIC_STATS];
+    std::vector<double> blk((size_t)2 * nblk + size);
+    double *noise = blk.data(), *ela = noise + nblk, *dpart = ela + nblk;
+    DFD_HIP_TRY(h, hipMemcpyAsync(st, B.stats, sizeof st, hipMemcpyDeviceToHost, h->stream));
+    if (full) {
+        DFD_HIP_TRY(h, hipMemcpyAsync(noise, B.stats_noise, (size_t)nblk * 8, hipMemcpyDeviceToHost, h->stream));
+        DFD_HIP_TRY(h, hipMemcpyAsync(ela, B.stats_ela, (size_t)nblk * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (S.has_prev) DFD_HIP_TRY(h, hipMemcpyAsync(dpart, Z->diff_part, (size_t)size * 8, hipMemcpyDeviceToHost, h->stream));
+    DFD_HIP_TRY(h, hipMemcpyAsync(S.prev_gray, B.gray, pix, hipMemcpyDeviceToDevice, h->stream));
+    DFD_HIP_TRY(h, stream_sync(h));
+    DFD_HIP_TRY(h, hipGetLastError());
+
+    const double nan = std::nan("");
+    double sc[6], ex[10], mean_diff, temporal_cv;
+    *prob_out = score_frame(S, st, noise, ela, full != 0, dpart, sc, ex, &mean_diff, &temporal_cv, size, (double)pix, nblk, true);
+    for (int i = 0; i < 6; ++i) scores_out[i] = sc[i];
+    if (stats_out) {
+        const double out[DFD_FORENSIC_NSTATS] = {ex[0], ex[1], ex[2], ex[3], ex[4], ex[5], ex[6], ex[7], ex[8], ex[9],
+                                                 st[ST_EDGE_COUNT] / (double)pix, st[ST_LAP_VAR], full ? st[ST_SAT_STD] : nan,
+                                                 full ? st[ST_VAL_STD] : nan, full ? st[ST_HUES] : nan, mean_diff, temporal_cv,
+                                                 (double)S.frame_count};
+        for (int i = 0; i < DFD_FORENSIC_NSTATS; ++i) stats_out[i] = out[i];
+    }
+    return DFD_OK;
+}
+
+int dfd_forensic_tap_sized(dfd_handle* h, const uint8_t* frames, int n, int size, int full, const char* start, const void* start_data,
+                           const char* name, int frame, void* out, size_t capacity, size_t* bytes) {
+    if (!h) return DFD_ERR_ARG;
+    if (!start || !name || !out || !bytes || n <= 0 || n > 16 || frame < -1 || frame >= n)
+        return fail(h, DFD_ERR_ARG, "forensic_tap_sized: bad pointer, frame index or frame count (1..16)");
+    if (!sized_ok(size))
+        return fail(h, DFD_ERR_ARG, "forensic_tap_sized: analysis size %d is not a multiple of 16 in %d..%d", size, SIZED_MIN, SIZED_MAX);
+    const size_t PIX = (size_t)size * size, NB = (size_t)sized_blocks(size), SS = (size_t)size;
+    static const char* const starts[4] = {"rs", "gray", "grad", "map"};
+    int st = -1;
+    for (int i = 0; i < 4; ++i)
+        if (!std::strcmp(start, starts[i])) st = i;
+    if (st < 0) return fail(h, DFD_ERR_ARG, "forensic_tap_sized: start '%s' is none of rs, gray, grad, map", start);
+    if (st == FROM_RS ? !frames : !start_data) return fail(h, DFD_ERR_ARG, "forensic_tap_sized: no data for start '%s'", start);
+    if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    int rc = state_init(h, 1);
+    if (rc) return rc;
+    ForensicState::Sized* Z = nullptr;
+    if ((rc = sized_init(h, size, n, &Z))) return rc;
+    if ((rc = ensure(h, &Z->tap_store, (size_t)n * PIX * (sizeof(float2) + sizeof(float) + 1)))) return rc;
+    ForensicTaps T;
+    T.spectrum = static_cast<float2*>(Z->tap_store.p);
+    T.logmag = reinterpret_cast<float*>(T.spectrum + (size_t)n * PIX);
+    T.edges = reinterpret_cast<uint8_t*>(T.logmag + (size_t)n * PIX);
+    const ForensicBuffers& B = Z->buf;
+    struct Tap { const char* name; const void* p; size_t per; int last_start; bool full_only; };
+    const bool stats_full = full && st == FROM_RS;
+    const Tap taps[] = {
+        {"rs", B.rs, PIX * 3, FROM_RS, false}, {"gray", B.gray, PIX, FROM_GRAY, false},
+        {"fft_tmp", B.fft_tmp, PIX * sizeof(float2), FROM_GRAY, false}, {"spectrum", T.spectrum, PIX * sizeof(float2), FROM_GRAY, false},
+        {"logmag", T.logmag, PIX * sizeof(float), FROM_GRAY, false}, {"fft_part", B.fft_part, SS * 7 * 8, FROM_GRAY, false},
+        {"grad", B.grad, PIX * sizeof(short2), FROM_GRAD, false}, {"lap_part", B.lap_part, SS * 2 * 8, FROM_GRAY, false},
+        {"map", B.map, PIX, FROM_MAP, false}, {"edges", T.edges, PIX, FROM_MAP, false}, {"edge_count", B.edge_count, 8, FROM_MAP, false},
+        {"jy", B.jy, PIX, FROM_RS, true}, {"jcb", B.jcb, PIX / 4, FROM_RS, true}, {"jcr", B.jcr, PIX / 4, FROM_RS, true},
+        {"stats_ela", B.stats_ela, NB * 8, FROM_RS, true}, {"stats_noise", B.stats_noise, NB * 8, FROM_GRAY, true},
+        {"hsv_part", B.hsv_part, SS * 4 * 8, FROM_RS, true}, {"hue_bits", B.hue_bits, 6 * 4, FROM_RS, true},
+        {"stats", B.stats, (size_t)(stats_full ? FORENSIC_STATS : ST_SAT_STD) * 8, FROM_GRAY, false},
+    };
+    const char* src = nullptr;
+    size_t per = 0, stride = 0;
+    if (!std::strcmp(name, "twiddle")) {                        // the table both DFT launches read; not per frame
+        src = reinterpret_cast<const char*>(Z->table);
+        per = SS * sizeof(float2);
+        frame = 0;
+    }
+    for (const Tap& t : taps)
+        if (!src && !std::strcmp(name, t.name)) {
+            if (st > t.last_start || (t.full_only && !full))
+                return fail(h, DFD_ERR_ARG, "forensic_tap_sized: '%s' is not computed from start '%s' with full = %d", name, start, full);
+            src = static_cast<const char*>(t.p);
+            per = t.per;
+            stride = !std::strcmp(name, "stats") ? FORENSIC_STATS * 8 : t.per;
+        }
+    if (!src) return fail(h, DFD_ERR_ARG, "forensic_tap_sized: no buffer named '%s'", name);
+    const size_t nout = frame < 0 ? (size_t)n : 1, total = nout * per;
+    *bytes = total;
+    if (total > capacity) return fail(h, DFD_ERR_ARG, "forensic_tap_sized '%s' needs %zu bytes, capacity %zu", name, total, capacity);
+    if (st == FROM_RS) {
+        DFD_HIP_TRY(h, hipMemcpyAsync(B.rs, frames, (size_t)n * PIX * 3, hipMemcpyHostToDevice, h->stream));
+    } else {
+        void* dst = st == FROM_GRAY ? (void*)B.gray : st == FROM_GRAD ? (void*)B.grad : (void*)B.map;
+        DFD_HIP_TRY(h, hipMemcpyAsync(dst, start_data, (size_t)n * PIX * (st == FROM_GRAD ? sizeof(short2) : 1), hipMemcpyHostToDevice, h->stream));
+    }
+    DFD_HIP_TRY(h, launch_forensics_sized(B, size, n, full != 0, h->color, Z->table, h->stream, (ForensicStart)st, &T));
+    const size_t first = frame < 0 ? 0 : (size_t)frame;
+    if (stride == per || nout == 1) {
+        DFD_HIP_TRY(h, hipMemcpyAsync(out, src + first * stride, total, hipMemcpyDeviceToHost, h->stream));
+    } else {
+        for (size_t f = 0; f < nout; ++f)
+            DFD_HIP_TRY(h, hipMemcpyAsync((char*)out + f * per, src + f * stride, per, hipMemcpyDeviceToHost, h->stream));
+    }
+    DFD_HIP_TRY(h, stream_sync(h));
     return DFD_OK;
 }
 

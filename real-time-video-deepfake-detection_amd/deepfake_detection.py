@@ -281,12 +281,54 @@ class DeepfakeDetector:
             return None
         return {'fake_probability': p, 'heatmap': heat[0], 'overlay': overlay[0]}
 
+    def _sized_analyzer(self) -> bool:
+        """a swapped-in analyzer at another analysis size: its stream is not a 256x256 one, so the fused calls (which
+        run the 256x256 forensic kernels on the stream) must not be made on it"""
+        return tuple(self.frame_analyzer.analysis_size) != (256, 256)
+
+    def _frame_sized(self, frame, full, max_faces, request):
+        """the work of the fused call as separate ones, for an analyzer at another analysis size: forensics through
+        the analyzer, detection and classification through the detector and crop entries (with TTA on, the copies of
+        every face in the same classification pass) -> (scores, prob, boxes, logits, n_detected)"""
+        res = self.frame_analyzer.analyze(frame) if full else self.frame_analyzer.analyze_fast(frame)
+        boxes, logits = [], []
+        if self.handle.has_detector:
+            boxes = self.handle.detect_faces(frame, confidence_threshold=0.5)
+        elif self.handle.has_haar:
+            boxes = self.handle.detect_faces_haar(frame)
+        n_detected = len(boxes)
+        boxes = boxes[:max_faces]
+        if boxes:
+            copies = self._tta_copies(request)
+            step = max(1, self.handle.max_batch // (1 + copies))     # images per classification pass
+            if copies == 0:
+                for i in range(0, len(boxes), step):
+                    logits += list(self.handle.classify_crops(frame, boxes[i:i + step], apply_clahe=True)[:, 0])
+            else:
+                state, draws = tta_draw_table(len(boxes), copies)
+                try:
+                    for i in range(0, len(boxes), step):
+                        logits += list(self.handle.classify_crops_tta(frame, boxes[i:i + step], copies,
+                                                                      draws[i * copies:(i + step) * copies], apply_clahe=True))
+                finally:
+                    tta_commit_draws(state, len(logits), copies)
+        return res['scores'], res['fake_probability'], boxes, logits, n_detected
+
     def _frame_on_gpu(self, frame, max_faces, jpeg: Optional[bytes] = None, request: bool = False):
         """forensics + detection + per-face logits in one library call (with TTA on: every face's row of logits, original
         and augmented copies, from the same call).  With `jpeg` the frame is decoded on the
         device from the request's bytes (dfd_analyze_jpeg) instead of uploaded raw; returns its (H, W) as 4th item."""
         full = self._forensic_is_full()
         with self._lock:
+            if self._sized_analyzer():
+                if jpeg is not None:
+                    frame = self.handle.decode_jpeg(jpeg)
+                scores, prob, boxes, logits, _ = self._frame_sized(frame, full, max_faces, request)
+                forensic = {'scores': scores, 'fake_probability': prob,
+                            'analysis_type': 'frame_forensic' if full else 'frame_forensic_fast',
+                            'frame_number': self.frame_analyzer.frame_count}
+                self.last_frame_forensic_result = forensic
+                return (forensic, boxes, logits, frame.shape[:2]) if jpeg is not None else (forensic, boxes, logits)
             if jpeg is not None:
                 scores, prob, boxes, logits, shape = self._armed(
                     self.handle.analyze_jpeg, max_faces, request, data=jpeg, full_forensics=full,
@@ -417,7 +459,13 @@ class DeepfakeDetector:
         n = len(items)
         full = [(self.frame_count + i) % self.full_forensic_interval == 0 for i in range(n)]
         with self._lock:
-            if self.handle.has_detector or self.handle.has_haar:
+            if self._sized_analyzer():                              # the batched stream entry is 256x256 only: frame by frame
+                res, shape = [], None
+                for it, fl in zip(items, full):
+                    fr = self.handle.decode_jpeg(it) if isinstance(it, (bytes, bytearray)) else np.ascontiguousarray(it)
+                    res.append(self._frame_sized(fr, fl, 1, True))
+                    shape = fr.shape[:2]
+            elif self.handle.has_detector or self.handle.has_haar:
                 res, shape = self._armed(self.handle.analyze_stream_batch, n, True, items=items, full_flags=full,
                                          stream_id=self.frame_analyzer.stream_id, confidence_threshold=0.5, max_faces=1)
             else:                                                   # no detector of either kind: forensics only, frame by frame

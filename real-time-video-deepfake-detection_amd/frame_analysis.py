@@ -3,12 +3,14 @@
 `FrameForensicAnalyzer` keeps the reference class's constructor, methods, result dicts and
 visible attributes (reference frame_analysis.py:22-395); each call is one `dfd_forensics`
 through the C ABI, which resizes the frame to 256x256 on the GPU, runs the six signal kernels
-on the library's stream and applies the reference's thresholds.  The temporal state lives in the
+on the library's stream and applies the reference's thresholds (`dfd_forensics_sized` and the
+general kernel chain for any other square size, opted into with `any_size`).  The temporal state lives in the
 library per stream id; the attributes below read it back.
 """
 from __future__ import annotations
 
 import itertools
+import os
 from typing import Optional
 
 import numpy as np
@@ -19,11 +21,25 @@ _stream_ids = itertools.count(1)
 
 
 class FrameForensicAnalyzer:
-    def __init__(self, analysis_size=(256, 256), *, handle: Optional[Handle] = None, stream_id: Optional[int] = None):
-        if tuple(analysis_size) != (256, 256):
-            raise ValueError("the HIP forensic kernels are built for analysis_size=(256, 256) "
-                             "(the only size the reference ever constructs, deepfake_detection.py:327)")
-        self.analysis_size = tuple(analysis_size)
+    def __init__(self, analysis_size=(256, 256), *, handle: Optional[Handle] = None, stream_id: Optional[int] = None,
+                 any_size: Optional[bool] = None):
+        """`any_size` (None: the environment variable DFD_FORENSIC_ANY_SIZE, default off) admits every square
+        analysis_size (S, S) with S a multiple of 16 in 32..1024, run by the general kernel chain
+        (`dfd_forensics_sized`); (256, 256) always runs the 256x256 kernels."""
+        if any_size is None:
+            any_size = os.environ.get("DFD_FORENSIC_ANY_SIZE", "").strip().lower() in ("1", "true", "yes", "on")
+        size = tuple(int(v) for v in analysis_size)
+        if size != (256, 256):
+            if not any_size:
+                raise ValueError("the HIP forensic kernels are built for analysis_size=(256, 256) "
+                                 "(the only size the reference ever constructs, deepfake_detection.py:327); "
+                                 "any_size=True or DFD_FORENSIC_ANY_SIZE=1 admits other square sizes")
+            if len(size) != 2 or size[0] != size[1] or size[0] % 16 or not 32 <= size[0] <= 1024:
+                raise ValueError(f"analysis_size {size}: supported are square sizes (S, S) with S a multiple of 16 "
+                                 "in 32..1024 (the reference itself fails on non-square sizes, and the ELA round "
+                                 "trip needs whole 16x16 JPEG MCUs)")
+        self.analysis_size = size
+        self.any_size = bool(any_size)
         self._handle = handle
         self.stream_id = next(_stream_ids) if stream_id is None else int(stream_id)
         self.weights = {'frequency': 0.25, 'noise': 0.20, 'ela': 0.20, 'edge': 0.15, 'color': 0.10,
@@ -71,7 +87,10 @@ class FrameForensicAnalyzer:
         frame = np.asarray(frame)
         if frame.ndim != 3 or frame.shape[2] != 3 or frame.dtype != np.uint8 or frame.shape[0] < 1 or frame.shape[1] < 1:
             raise ValueError(f"expected a BGR uint8 image, got {frame.dtype} {frame.shape}")
-        scores, prob, stats = self.handle.forensics(frame, full=full, stream_id=self.stream_id)
+        if self.analysis_size == (256, 256):
+            scores, prob, stats = self.handle.forensics(frame, full=full, stream_id=self.stream_id)
+        else:
+            scores, prob, stats = self.handle.forensics_sized(frame, self.analysis_size[0], full=full, stream_id=self.stream_id)
         self.last_stats = stats
         return {'scores': scores, 'fake_probability': prob, 'analysis_type': kind,
                 'frame_number': int(stats['frame_count'])}
