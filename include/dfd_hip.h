@@ -66,6 +66,8 @@ int dfd_max_batch(const dfd_handle* h);
  *   per block by measurement at batch 256).
  *   "fuse_stem" (default 1, env DFD_FUSE_STEM): the stem conv is computed inside block 0's depthwise
  *   kernel (the 112x112x32 stem activation stays in LDS).
+ *   "fuse_proj0" (default 1, env DFD_FUSE_PROJ0; fp32 activations with "fuse_expand" and "split_gemm"): block 0's projection
+ *   is computed inside block 1's expand + depthwise launch, from block 0's depthwise output; same result bits, one launch less.
  *   "split_gemm" (default 1, env DFD_SPLIT_GEMM): 1x1 convs (N >= 16) and the detector's k x k convs run on
  *   the split-precision GEMM (each fp32 operand = exact sum of three bf16 terms, six products on the bf16
  *   MFMA, fp32 accumulate: fp32-dot-product accuracy); 0 = the fp32 MFMA kernel everywhere.

@@ -554,7 +554,25 @@ __global__ __launch_bounds__(256, (RP >= 4 ? 2 : 4)) void dw_kernel(const XT* __
 // for every chunk.  Price: the halo's expand FLOPs are recomputed (1.1-1.65x).
 // (round 3) fp32 only, exactly Cin / 4 MFMAs per pixel tile: lane k-group q supplies the NM = Cin / 4 consecutive
 // channels q * NM .. of its pixel (see mbconv2_kernel); KC = 16-byte registers per tile and lane = ceil(NM / 4).
-template <int K, int S, int CB, int TH, int TW, int RP, int KC, int NSUB, typename XT, int CI>
+// PROJ0 (block 1, option "fuse_proj0"): X is block 0's DEPTHWISE output [n][H][H][32] and the block input is computed
+// here instead of loaded - block 0's projection (squeeze-excite gate, 32 -> 16 channels, bias, no activation, no skip)
+// as gemm_split runs it: gate multiply in fp32, split8, the six products of s6_products in its order on
+// v_mfma_f32_16x16x32_bf16 from a zero accumulator, then s6_epilogue's additions.  With the weights as A (row = output
+// channel) and pixels as columns the accumulator leaves lane (j, q) with channels 4q .. 4q + 3 of pixel j: exactly the
+// expand's B fragment xf[it][0] for CI = 16, bit for bit the value the separate launch stored.  The fragments are
+// computed once per block (the chunk loop reuses them), so the projection's output tensor, its launch and the read of
+// it here disappear; this launch reads 32 instead of 16 channels per halo pixel.
+template <bool PROJ0>
+struct Proj0Args {};
+template <>
+struct Proj0Args<true> {
+    const float* gate;              // block 0's squeeze-excite gate [n][32]
+    const unsigned short* W3;       // its projection weights [16][32]: three bf16 planes, `plane` elements apart, rows Kp long
+    const float* bias;              // [16]
+    int plane, Kp;
+};
+
+template <int K, int S, int CB, int TH, int TW, int RP, int KC, int NSUB, typename XT, int CI, bool PROJ0 = false>
 __global__ __launch_bounds__(256, ((S == 1 && (((TH - 1) * S + K) * ((TW - 1) * S + K) + 63) / 64 * KC > 12) ? 2 : 3)) void mbconv_kernel(const XT* __restrict__ X,
                                                      const float* __restrict__ We,
                                                      const float* __restrict__ be,
@@ -562,7 +580,7 @@ __global__ __launch_bounds__(256, ((S == 1 && (((TH - 1) * S + K) * ((TW - 1) * 
                                                      const float* __restrict__ bias,
                                                      XT* __restrict__ Y, float* __restrict__ P,
                                                      int H, int Ho, int C, int Cin, int pad_lo,
-                                                     int tiles_x, int tiles_sp) {
+                                                     int tiles_x, int tiles_sp, const Proj0Args<PROJ0> pj) {
     using Sh = DwShape<K, S, CB, TH, TW>;
     constexpr int CG = Sh::CG, IH = Sh::IH, IW = Sh::IW;
     constexpr int NTB = CB / 16;                        // 16-channel MFMA row tiles per chunk
@@ -582,24 +600,6 @@ __global__ __launch_bounds__(256, ((S == 1 && (((TH - 1) * S + K) * ((TW - 1) * 
     int mtp = 0;
 #endif
     MB_TP(0);
-
-    // B operand for all of this wave's pixel tiles: lane (pixel j, k-quad q); loaded once
-    const XT* xb = X + (size_t)n * H * H * Cin;
-    v4f xf[NIT][KC];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int p = (wave + 4 * it) * 16 + j;
-        const int iy = iy0 + p / IW, ix = ix0 + p % IW;
-        const bool inside = p < NP && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)H;
-        const float* px = reinterpret_cast<const float*>(xb) + ((size_t)(inside ? iy : 0) * H + (inside ? ix : 0)) * CI + q * NM;
-#pragma unroll
-        for (int kk = 0; kk < KC; ++kk) {
-            v4f v;                                               // unconditional load, masked value
-            if (NM % 4 == 0 || kk < KC - 1) v = ldg4u(px + 4 * kk);
-            else { const v2f t2 = ldg2(px + 4 * kk); v = (v4f){t2.x, t2.y, 0.f, 0.f}; }
-            xf[it][kk] = inside ? v : (v4f){0.f, 0.f, 0.f, 0.f};
-        }
-    }
 
     // Per-chunk weights (depthwise taps, biases, the chunk's expand rows) are requested one chunk ahead into
     // registers: loaded at the top of their own chunk they cost an exposed L2 round trip per chunk (600-1600 of
@@ -623,7 +623,74 @@ __global__ __launch_bounds__(256, ((S == 1 && (((TH - 1) * S + K) * ((TW - 1) * 
         }
     };
     ChunkW cw[2];
-    load_chunk(0, cw[0]);
+
+    // B operand for all of this wave's pixel tiles: lane (pixel j, k-quad q); loaded once
+    v4f xf[NIT][KC];
+    if constexpr (PROJ0) {
+        static_assert(CI == 16 && KC == 1, "block 0's projection: 32 -> 16 channels, one 16-channel row tile");
+        constexpr int C0 = 32;                                   // channels of block 0's depthwise output
+        const float* xb = reinterpret_cast<const float*>(X) + (size_t)n * H * H * C0 + 8 * q;
+        // all of the wave's tiles are requested before the first is used: lane (j, q) = channels 8q .. 8q + 7 of pixel j
+        // (clamped address; a pixel outside the image needs no mask - its expanded value is zeroed by `inside` below)
+        v4f raw[NIT][2];
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int p = (wave + 4 * it) * 16 + j;
+            const int iy = iy0 + p / IW, ix = ix0 + p % IW;
+            const bool inside = p < NP && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)H;
+            const float* px = xb + ((size_t)(inside ? iy : 0) * H + (inside ? ix : 0)) * C0;
+            raw[it][0] = ldg4(px);
+            raw[it][1] = ldg4(px + 4);
+        }
+        // fixed for the whole block: the lane's eight gate values, its weight row (A fragment of each plane), its bias quad
+        const v4f g0 = ldg4(pj.gate + (size_t)n * C0 + 8 * q), g1 = ldg4(pj.gate + (size_t)n * C0 + 8 * q + 4);
+        const unsigned short* wrow = pj.W3 + (size_t)j * pj.Kp + 8 * q;
+        const bf8 w0 = *reinterpret_cast<const bf8*>(wrow), w1 = *reinterpret_cast<const bf8*>(wrow + (size_t)pj.plane),
+                  w2 = *reinterpret_cast<const bf8*>(wrow + 2 * (size_t)pj.plane);
+        const v4f pb = ldg4(pj.bias + 4 * q);
+        load_chunk(0, cw[0]);                                    // in flight behind the tiles, lands during the projection
+        bf8 xs[NIT][3];
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            v4f lo = raw[it][0] * g0, hi = raw[it][1] * g1;
+            // the rounded products are split8's input: the split's first subtraction must not contract with this multiply
+            // into an fma (gemm_split is built without contraction, this file with it)
+            asm("" : "+v"(lo), "+v"(hi));
+            split8(lo, hi, xs[it][0], xs[it][1], xs[it][2]);
+        }
+        // the six products of s6_products (gemm_split_impl.h), smallest terms first; the tiles' chains interleaved
+        v4f pacc[NIT];
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) pacc[it] = (v4f){0.f, 0.f, 0.f, 0.f};
+        const bf8* wsel[6] = {&w2, &w1, &w0, &w1, &w0, &w0};
+        const int xsel[6] = {0, 1, 2, 0, 1, 0};
+#pragma unroll
+        for (int p6 = 0; p6 < 6; ++p6)
+#pragma unroll
+            for (int it = 0; it < NIT; ++it)
+                pacc[it] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*wsel[p6], xs[it][xsel[p6]], pacc[it], 0, 0, 0);
+        // s6_epilogue without activation: + bias, then + the (absent) residual, which it adds as zeros
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) xf[it][0] = (pacc[it] + pb) + (v4f){0.f, 0.f, 0.f, 0.f};
+    } else {
+    const XT* xb = X + (size_t)n * H * H * Cin;
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int p = (wave + 4 * it) * 16 + j;
+        const int iy = iy0 + p / IW, ix = ix0 + p % IW;
+        const bool inside = p < NP && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)H;
+        const float* px = reinterpret_cast<const float*>(xb) + ((size_t)(inside ? iy : 0) * H + (inside ? ix : 0)) * CI + q * NM;
+#pragma unroll
+        for (int kk = 0; kk < KC; ++kk) {
+            v4f v;                                               // unconditional load, masked value
+            if (NM % 4 == 0 || kk < KC - 1) v = ldg4u(px + 4 * kk);
+            else { const v2f t2 = ldg2(px + 4 * kk); v = (v4f){t2.x, t2.y, 0.f, 0.f}; }
+            xf[it][kk] = inside ? v : (v4f){0.f, 0.f, 0.f, 0.f};
+        }
+    }
+    }
+
+    if constexpr (!PROJ0) load_chunk(0, cw[0]);
 #pragma unroll
     for (int sub = 0; sub < NSUB; ++sub) {
         const int c0 = (group * NSUB + sub) * CB;
@@ -1085,15 +1152,16 @@ static void dw_launch(const XT* X, const float* W, const float* b, XT* Y, float*
                        s, X, W, b, Y, P, H, Ho, C, pad_lo, tx, tiles_sp);
 }
 
-template <int K, int S, int CB, int TH, int TW, int RP, int KC, int NSUB, typename XT, int CI>
+template <int K, int S, int CB, int TH, int TW, int RP, int KC, int NSUB, typename XT, int CI, bool PROJ0 = false>
 static void mb_launch(const XT* X, int Cin, const float* We, const float* be, const float* W, const float* b,
-                      XT* Y, float* P, int n, int H, int C, int pad_lo, int* tiles, hipStream_t s) {
+                      XT* Y, float* P, int n, int H, int C, int pad_lo, int* tiles, hipStream_t s,
+                      const Proj0Args<PROJ0> pj = Proj0Args<PROJ0>{}) {
     const int Ho = (H + S - 1) / S;
     const int tx = (Ho + TW - 1) / TW, ty = (Ho + TH - 1) / TH;
     const int tiles_sp = tx * ty;
     *tiles = tiles_sp;
-    hipLaunchKernelGGL((mbconv_kernel<K, S, CB, TH, TW, RP, KC, NSUB, XT, CI>), dim3(tiles_sp * (C / (CB * NSUB)) * n),
-                       dim3(256), 0, s, X, We, be, W, b, Y, P, H, Ho, C, Cin, pad_lo, tx, tiles_sp);
+    hipLaunchKernelGGL((mbconv_kernel<K, S, CB, TH, TW, RP, KC, NSUB, XT, CI, PROJ0>), dim3(tiles_sp * (C / (CB * NSUB)) * n),
+                       dim3(256), 0, s, X, We, be, W, b, Y, P, H, Ho, C, Cin, pad_lo, tx, tiles_sp, pj);
 }
 
 
@@ -1673,6 +1741,20 @@ bool launch_mbconv_front(const XT* Xin, int Cin, const unsigned short* We3, int 
 #endif
     return false;
 }
+// Option "fuse_proj0": block 1's launch with block 0's projection folded in (mbconv_kernel, PROJ0).  Only the default
+// kernel of block 1 has the instance: with a DFD_MB_VARIANT_112_2 experiment selected the plan keeps the two launches.
+bool mbconv_proj0_supported(int H, int C, int k, int stride, int Cin, int C0) {
+    return k == 3 && stride == 2 && H == 112 && C == 96 && Cin == 16 && C0 == 32 && mb_variant(H, stride) == -2;
+}
+bool launch_mbconv_front_proj0(const float* Xdw0, const float* gate0, const unsigned short* Wp3, int plane, int Kp, const float* bp,
+                               const float* Wef, const float* be, const float* Wd, const float* bd, float* Y, float* P, int n,
+                               int H, int C, int k, int stride, int Cin, int pad_lo, int* tiles, hipStream_t s) {
+    if (!mbconv_proj0_supported(H, C, k, stride, Cin, 32)) return false;
+    const Proj0Args<true> pj{gate0, Wp3, bp, plane, Kp};
+    mb_launch<3, 2, 32, 8, 8, 2, 1, 3, float, 16, true>(Xdw0, Cin, Wef, be, Wd, bd, Y, P, n, H, C, pad_lo, tiles, s, pj);   // block 1's row of DFD_MB1_TABLE
+    return true;
+}
+
 template bool launch_mbconv_front<float>(const float*, int, const unsigned short*, int, int, const float*, const float*, const float*, const float*, float*, float*, int, int, int, int, int, int, int*, hipStream_t, bool);
 template bool launch_mbconv_front<bf16_t>(const bf16_t*, int, const unsigned short*, int, int, const float*, const float*, const float*, const float*, bf16_t*, float*, int, int, int, int, int, int, int*, hipStream_t, bool);
 

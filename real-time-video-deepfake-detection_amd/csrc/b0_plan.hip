@@ -222,6 +222,18 @@ static int b0_forward_t(dfd_handle* h, const float* x, int n, float* logits_dev,
         mk.mark("stem");
     }
     if ((rc = tap_out(h, tap, "stem", io0, (size_t)n * 112 * 112 * 32))) return rc;
+    // Option "fuse_proj0": block 0's projection runs inside block 1's expand + depthwise launch (mbconv_kernel, PROJ0), which
+    // reads block 0's depthwise output directly; the 16-channel block output never reaches HBM.  Only where block 1 runs on
+    // that kernel (fp32 storage, split GEMM, "fuse_expand", no kernel experiment); a call that taps b0.out runs the two
+    // launches (the same bits), and so does dfd_warmup, which measures the projection's tile for those calls.
+    bool proj0 = false;
+    if constexpr (sizeof(XT) == 4) {
+        const B0Block &p0 = P.blocks[0], &p1 = P.blocks[1];
+        proj0 = h->fuse_proj0 && h->fuse_expand && h->split_gemm && !h->warming && p0.expand == 1 && !p0.skip &&
+                p0.c_out >= 16 && split_gemm_supports(p0.c_exp, p0.c_out) &&
+                mbconv_proj0_supported(p1.h_in, p1.c_exp, p1.kernel, p1.stride, p1.c_in, p0.c_exp) &&
+                !(tap && tap->name && std::string(tap->name) == "b0.out");
+    }
     XT* cur = io0;
     XT* nxt = io1;
     int bi = 0;
@@ -229,13 +241,33 @@ static int b0_forward_t(dfd_handle* h, const float* x, int n, float* logits_dev,
         const int m_in = n * b.h_in * b.h_in, m_out = n * b.h_out * b.h_out;
         const std::string q = "b" + std::to_string(bi);
         const XT* dw_in = cur;
+        XT* dw_out = dwbuf;
         int tiles = 0;
         bool fused = false;
         const unsigned short* we3 = nullptr;
+        if constexpr (sizeof(XT) == 4) {
+            if (proj0 && bi == 1) {
+                // input: block 0's depthwise output (dwbuf) and gate (h->gate, rewritten only by this block's se launch
+                // below); this block's depthwise output goes to expbuf, which fused blocks leave unused
+                const B0Block& p0 = P.blocks[0];
+                const unsigned short* wp3 = split_weights(h, p0.proj_w, p0.c_out, p0.c_exp);
+                if (!wp3) return DFD_ERR_HIP;
+                dw_out = expbuf;
+                if (!launch_mbconv_front_proj0(dwbuf, h->gate, wp3, (int)split_weights_count(p0.c_out, p0.c_exp),
+                                               (p0.c_exp + 63) / 64 * 64, p0.proj_b, b.exp_w, b.exp_b, b.dw_w, b.dw_b, dw_out,
+                                               h->pool, n, b.h_in, b.c_exp, b.kernel, b.stride, b.c_in, b.pad_lo, &tiles, s))
+                    return fail(h, DFD_ERR_STATE, "no fused projection kernel for block 1");
+                fused = true;
+                mk.mark(layer_name(bi, "dw"));        // block 0's projection + expand + depthwise in one launch
+                if (tap && tap->name && q + ".exp" == tap->name)
+                    return fail(h, DFD_ERR_STATE, "tap '%s': the expanded tensor is not materialised when expand is fused "
+                                                  "(dfd_set_option(h, \"fuse_expand\", 0))", tap->name);
+            }
+        }
         // whole-image launches (blocks 6-15) where they measure faster: per block, batch 256 (section 5, round 4) - blocks 8
         // and 9 (k5, 480 / 672 channels at 14 x 14) are 2-4 us quicker as expand GEMM + depthwise kernel ("fuse_late_skip")
         const bool late_here = h->fuse_late && !((h->fuse_late_skip >> bi) & 1u);
-        if (b.expand != 1 && h->fuse_expand && mbconv_tiles(b.h_in, b.c_exp, b.kernel, b.stride, b.c_in, late_here) > 0 &&
+        if (!fused && b.expand != 1 && h->fuse_expand && mbconv_tiles(b.h_in, b.c_exp, b.kernel, b.stride, b.c_in, late_here) > 0 &&
             !(we3 = split_weights(h, b.exp_w, b.c_exp, b.c_in))) return DFD_ERR_HIP;
         if (we3 && launch_mbconv_front<XT>(cur, b.c_in, we3, (int)split_weights_count(b.c_exp, b.c_in), (b.c_in + 63) / 64 * 64,
                                            b.exp_w, b.exp_b, b.dw_w, b.dw_b, dwbuf, h->pool, n, b.h_in, b.c_exp,
@@ -261,15 +293,17 @@ static int b0_forward_t(dfd_handle* h, const float* x, int n, float* logits_dev,
                 return fail(h, DFD_ERR_STATE, "no depthwise kernel for block %d", bi);
             mk.mark(layer_name(bi, "dw"));
         }
-        if ((rc = tap_out(h, tap, q + ".dw", dwbuf, (size_t)m_out * b.c_exp))) return rc;
+        if ((rc = tap_out(h, tap, q + ".dw", dw_out, (size_t)m_out * b.c_exp))) return rc;
         launch_se(h->pool, tiles, 1.0f / (float)(b.h_out * b.h_out), b.se_w1, b.se_b1, b.se_w2, b.se_b2,
                   h->gate, n, b.c_exp, b.c_se, s);
         mk.mark(layer_name(bi, "se"));
         if ((rc = tap_out(h, tap, q + ".gate", h->gate, (size_t)n * b.c_exp))) return rc;
-        if ((rc = pointwise_t<XT>(h, dwbuf, b.proj_w, b.proj_b, h->gate, b.skip ? cur : (const XT*)nullptr, nxt, m_out,
-                                  b.c_exp, b.c_out, b.h_out * b.h_out, ACT_NONE))) return rc;
-        mk.mark(layer_name(bi, "proj"));
-        if ((rc = tap_out(h, tap, q + ".out", nxt, (size_t)m_out * b.c_out))) return rc;
+        if (!(proj0 && bi == 0)) {                    // (fused: block 1's launch computes this projection, nxt stays unwritten)
+            if ((rc = pointwise_t<XT>(h, dw_out, b.proj_w, b.proj_b, h->gate, b.skip ? cur : (const XT*)nullptr, nxt, m_out,
+                                      b.c_exp, b.c_out, b.h_out * b.h_out, ACT_NONE))) return rc;
+            mk.mark(layer_name(bi, "proj"));
+            if ((rc = tap_out(h, tap, q + ".out", nxt, (size_t)m_out * b.c_out))) return rc;
+        }
         XT* t = cur; cur = nxt; nxt = t;
         ++bi;
     }

@@ -37,6 +37,7 @@ int create_impl(dfd_handle* h, int device, const void* blob, size_t blob_len, in
     h->max_batch = max_batch;
     if (const char* e = getenv("DFD_FUSE_EXPAND")) h->fuse_expand = atoi(e) != 0;
     if (const char* e = getenv("DFD_FUSE_STEM")) h->fuse_stem = atoi(e) != 0;
+    if (const char* e = getenv("DFD_FUSE_PROJ0")) h->fuse_proj0 = atoi(e) != 0;
     if (const char* e = getenv("DFD_FUSE_LATE")) h->fuse_late = atoi(e) != 0;
     if (const char* e = getenv("DFD_FUSE_LATE_SKIP")) h->fuse_late_skip = (unsigned)atoi(e);
     if (const char* e = getenv("DFD_SPLIT_GEMM")) h->split_gemm = atoi(e) != 0;
@@ -164,6 +165,7 @@ int dfd_set_option(dfd_handle* h, const char* name, int value) {
     if (strcmp(name, "fuse_late") == 0) { h->fuse_late = value != 0; return DFD_OK; }
     if (strcmp(name, "fuse_late_skip") == 0) { h->fuse_late_skip = (unsigned)value; return DFD_OK; }
     if (strcmp(name, "fuse_stem") == 0) { h->fuse_stem = value != 0; return DFD_OK; }
+    if (strcmp(name, "fuse_proj0") == 0) { h->fuse_proj0 = value != 0; return DFD_OK; }
     if (strcmp(name, "split_gemm") == 0) { h->split_gemm = value != 0; return DFD_OK; }
     if (strcmp(name, "mtcnn") == 0) { h->use_mtcnn = value != 0; return DFD_OK; }
     if (strcmp(name, "overlap_forensics") == 0) { h->overlap_forensics = value != 0; return DFD_OK; }
@@ -211,6 +213,7 @@ int dfd_warmup(dfd_handle* h, int n_crops, int n_frames) {
         return fail(h, DFD_ERR_ARG, "warmup: n_crops outside 0..%d or n_frames negative", h->max_batch);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     s6_table_set_tuning(h->gemm, true);
+    h->warming = true;
     int rc = DFD_OK;
     if (n_crops > 0) {
         const size_t cnt = (size_t)n_crops * 3 * 224 * 224;
@@ -219,6 +222,7 @@ int dfd_warmup(dfd_handle* h, int n_crops, int n_frames) {
     }
     if (rc == DFD_OK && n_frames > 0) rc = ssd_warmup(h, n_frames);
     s6_table_set_tuning(h->gemm, false);
+    h->warming = false;
     if (rc) return rc;
     DFD_HIP_TRY(h, stream_sync(h));
     return DFD_OK;

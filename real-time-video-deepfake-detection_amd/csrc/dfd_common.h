@@ -129,6 +129,8 @@ struct dfd_handle {
     bool use_mtcnn = true;                    // classify paths align each crop with the cascade when the blob has one
     bool fuse_stem = true;               // stem conv computed inside block 0's depthwise kernel
     bool fuse_expand = true;             // MBConv blocks 1-5: expand conv computed inside the depthwise kernel
+    bool fuse_proj0 = true;              // block 0's projection computed inside block 1's expand + depthwise launch (fp32, with fuse_expand)
+    bool warming = false;                // inside dfd_warmup: every GEMM shape of the unfused plan is launched, so that its tile is measured
     bool fuse_late = true;               // blocks 6-10 / 12-15: expand + depthwise of whole images in one launch (mbconv_late_kernel):
                                          // the faster configuration (round 3: +2.2-2.6 % per step, strictly fewer bytes), default since round 4
     unsigned fuse_late_skip = (1u << 8) | (1u << 9);   // blocks that keep expand GEMM + depthwise kernel although fuse_late is on:
