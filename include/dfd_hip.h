@@ -75,6 +75,9 @@ int dfd_max_batch(const dfd_handle* h);
  *   "overlap_forensics" (default 1): dfd_analyze_batch_device / dfd_analyze_frames_host run the six forensic signals of
  *   a batch on the handle's second stream beside the detector and the classifier and collect them at the end of the call;
  *   0 = in front of the detector on the main stream.  Same results.
+ *   "forensic_chunk_bytes" (default 256 MiB; <= 0 restores it): work memory of one launch set of the general forensic
+ *   chain in dfd_analyze_stream_batch / dfd_analyze_streams_batch - a size group runs in chunks of the frames that fit
+ *   (one at least).  Same results at every value; tests force it small.
  *   "profile_stride" (default 1): between dfd_b0_profile_begin/end only every k-th forward records events.
  *   "stream_priority" (1 high, 0 normal - the default -, -1 low): re-creates the handle's main stream at that priority
  *   (the handle is drained first).  For a process that keeps two handles busy on one device (two batches in flight): the
@@ -434,12 +437,24 @@ int dfd_forensic_tap(dfd_handle* h, const uint8_t* bgr256, int n, int full, cons
  * range(0, size - 31, 32) and every divisor derived from `size`, a multiple of 16 in 32..1024 (anything else:
  * DFD_ERR_ARG).  With fewer than 4 blocks (size < 64) the noise and ELA scores are 0.0 and their statistics NaN.
  * Outputs as dfd_forensics.  size = 256 is accepted and runs this general chain, not the 256x256 kernels.
- * A stream's analysis size is fixed by its first frame: this entry at another size, or dfd_forensics / dfd_analyze_* /
- * the batched stream entries (all 256x256) on a stream of another size, return DFD_ERR_STATE and change nothing.
+ * A stream's analysis size is fixed by dfd_forensics_open or, unopened, by its first frame: this entry at another size,
+ * or dfd_forensics (256x256) on a stream of another size, return DFD_ERR_STATE and change nothing.
  * dfd_forensics_reset keeps size and plane; dfd_forensics_release returns the size x size plane to a free list keyed
  * by plane size, after which the id may start again at any size. */
 int dfd_forensics_sized(dfd_handle* h, int stream_id, const uint8_t* bgr, int height, int width, int stride, int size,
                         int full, double* scores_out, double* prob_out, double* stats_out);
+/* Fixes the analysis size of a stream that has not seen a frame (a new id, or an id after dfd_forensics_release): size as
+ * for dfd_forensics_sized, anything else DFD_ERR_ARG.  On a stream that already holds a size, the same size is a no-op
+ * and another size returns DFD_ERR_STATE and changes nothing.  The stream-carrying entries - dfd_analyze_frame,
+ * dfd_analyze_jpeg, dfd_analyze_stream_batch, dfd_analyze_streams_batch - run a stream at the size it holds: an opened
+ * stream on the general chain of dfd_forensics_sized (size = 256 included), with results, bit for bit, those of
+ * dfd_forensics_sized on the same frames; a stream whose first frame came through dfd_forensics_sized at another size than
+ * 256 likewise; a stream that was never opened on the 256x256 kernels, as dfd_forensics.  dfd_analyze_streams_batch takes
+ * streams of different sizes in one call: the frames are grouped by analysis size, each group gets one ragged resize and
+ * one launch set per chunk of the frames that fit the work-memory budget (dfd_set_option "forensic_chunk_bytes", default
+ * 256 MiB, values <= 0 restore it; one frame at least; the split changes no result), and one launch differences every
+ * frame of the general chain against its predecessor, one more writes every such stream's last gray plane back. */
+int dfd_forensics_open(dfd_handle* h, int stream_id, int size);
 /* dfd_forensic_tap for the general chain: n (1..16) frames that are already size x size.  Same buffer names and
  * teacher-forcing starts; per frame, with S = size: "rs" u8[S][S][3]; "gray", "map", "jy", "edges" u8[S][S]; "jcb",
  * "jcr" u8[S/2][S/2]; "grad" i16[S][S][2]; "fft_tmp" (row pass), "spectrum" (both passes)
@@ -537,7 +552,8 @@ int dfd_analyze_stream_batch(dfd_handle* h, int stream_id, int n, const uint8_t*
  * dfd_analyze_jpeg.  Every header is parsed and every check runs before anything moves: a part the device path does
  * not take fails the call (DFD_ERR_UNSUPPORTED for JPEG flavours, DFD_ERR_ARG for unreadable parts, among them scans
  * that are corrupt or cut off, found while decoding) with its index in *bad_index_out (NULL allowed); no stream state
- * has moved then.  More than 2^27 pixels in one call are refused with DFD_ERR_UNSUPPORTED and index -1. */
+ * has moved then.  More than 2^27 pixels in one call are refused with DFD_ERR_UNSUPPORTED and index -1.  The streams of
+ * a call may hold different analysis sizes (dfd_forensics_open). */
 int dfd_analyze_streams_batch(dfd_handle* h, int n, const uint8_t* const* data, const size_t* len, const int* heights,
                               const int* widths, const int* stream_ids, const int* full_forensics, float conf_thr, int max_faces,
                               int apply_clahe, double* scores_out, double* forensic_prob_out, int32_t* xywh_out, int* n_faces_out,

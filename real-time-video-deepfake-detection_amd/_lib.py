@@ -136,6 +136,7 @@ SIGNATURES = {
                                    C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "dfd_forensics_sized": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dfd_forensics_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "dfd_forensic_tap_sized": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_void_p, C.c_char_p,
                                          C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "dfd_forensic_signals_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -599,6 +600,12 @@ class Handle:
                                                   int(size), int(bool(full)), _ptr(sc), C.byref(prob), _ptr(st)))
         scores = {k: float(v) for k, v in zip(self.FORENSIC_KEYS, sc) if not np.isnan(v)}
         return scores, float(prob.value), dict(zip(self.FORENSIC_STAT_KEYS, (float(v) for v in st)))
+
+    def forensics_open(self, stream_id: int, size: int):
+        """fix the analysis size of a stream that has not seen a frame (dfd_forensics_open): the fused entries
+        (analyze_frame, analyze_jpeg, analyze_stream_batch, analyze_streams_batch) then run it at (size, size) on the
+        general chain.  The same size again is a no-op; another size raises DfdError (-5) and changes nothing."""
+        self._check(self._lib.dfd_forensics_open(self._p, int(stream_id), int(size)))
 
     @staticmethod
     def forensic_taps_sized(size: int):

@@ -32,7 +32,7 @@ import numpy as np
 from flask import Flask, jsonify, request
 
 from . import runtime
-from .deepfake_detection import DEVICE, DeepfakeDetector, model, mtcnn  # noqa: F401  (reference :39)
+from .deepfake_detection import DEVICE, DeepfakeDetector, forensic_size_from_env, model, mtcnn  # noqa: F401  (reference :39)
 from .face_detection import detect_bounding_box  # noqa: F401                      (reference :40)
 from .sessions import InvalidFrame, SessionClosed, SessionPool, SessionPoolFull
 
@@ -64,8 +64,13 @@ try:
     TTA_AUGMENTATIONS = max(1, int(os.environ.get("DFD_TTA_AUGMENTATIONS", "1")))
 except ValueError:
     TTA_AUGMENTATIONS = 1
+# DFD_FORENSIC_SIZE=<S>: the forensic analysis runs at S x S instead of 256 x 256 (S a multiple of 16 in 32..1024, on the
+# general kernel chain; implies DFD_FORENSIC_ANY_SIZE) for the global detector and every session's detector, through the same
+# fused and batched device passes.  An invalid value fails here, at start-up.  Unset: nothing changes.
+FORENSIC_SIZE = forensic_size_from_env()
 detector = DeepfakeDetector(enable_gradcam=False, use_tta=TTA_AUGMENTATIONS > 1, num_tta_augmentations=TTA_AUGMENTATIONS,
-                            detection_threshold=0.55, request_tta=TTA_AUGMENTATIONS > 1)                       # reference :57
+                            detection_threshold=0.55, request_tta=TTA_AUGMENTATIONS > 1,                       # reference :57
+                            forensic_size=FORENSIC_SIZE)
 
 _last_request_time = 0.0
 _min_request_interval = 0.1                                                 # reference :63
@@ -87,7 +92,7 @@ def _pool():
     with _rate_lock:
         if _session_pool is None:
             _session_pool = SessionPool(lock=_detector_lock, detection_threshold=0.55, use_tta=TTA_AUGMENTATIONS > 1,
-                                        num_tta_augmentations=TTA_AUGMENTATIONS)
+                                        num_tta_augmentations=TTA_AUGMENTATIONS, forensic_size=FORENSIC_SIZE)
         return _session_pool
 
 

@@ -169,6 +169,7 @@ int dfd_set_option(dfd_handle* h, const char* name, int value) {
     if (strcmp(name, "split_gemm") == 0) { h->split_gemm = value != 0; return DFD_OK; }
     if (strcmp(name, "mtcnn") == 0) { h->use_mtcnn = value != 0; return DFD_OK; }
     if (strcmp(name, "overlap_forensics") == 0) { h->overlap_forensics = value != 0; return DFD_OK; }
+    if (strcmp(name, "forensic_chunk_bytes") == 0) { h->forensic_chunk_bytes = value > 0 ? (size_t)value : (size_t)256 << 20; return DFD_OK; }
     if (strcmp(name, "bf16_activations") == 0) { h->act_bf16 = value != 0; return DFD_OK; }
     if (strcmp(name, "bf16_weight_planes") == 0) {
         if (value != 1 && value != 3) return fail(h, DFD_ERR_ARG, "bf16_weight_planes must be 1 or 3");

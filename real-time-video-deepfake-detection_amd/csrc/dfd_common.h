@@ -93,6 +93,9 @@ struct dfd_handle {
     hipStream_t aux_stream = nullptr;
     hipEvent_t aux_go = nullptr, aux_done = nullptr;
     bool overlap_forensics = true;
+    size_t forensic_chunk_bytes = (size_t)256 << 20;   // work memory of one launch set of the general forensic chain in the batched
+                                         // stream entries (option "forensic_chunk_bytes"): a size group runs in chunks of the
+                                         // frames that fit, one frame at least
     hipStream_t copy_stream = nullptr;
     hipEvent_t copy_done[2] = {nullptr, nullptr}, slot_free[2] = {nullptr, nullptr};
     dfd::DevBuf stage[2];
@@ -196,6 +199,11 @@ int color_tables_init(dfd_handle* h);
 // stages that work on a frame already resident in HBM (forensic_api / ssd_api / imgproc_api)
 int forensics_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh, int ww, int stride, int full,
                   double* scores_out, double* prob_out, double* stats_out);
+// the same for the fused single-frame entries: the stream at the analysis size it holds - the general chain
+// (forensic_sized_kernels.hip) for a stream that was opened (dfd_forensics_open) or holds another size than 256,
+// forensics_run otherwise
+int forensics_stream_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh, int ww, int stride, int full,
+                         double* scores_out, double* prob_out);
 int detect_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride, float conf_thr, int32_t* xywh_out,
                float* conf_out, int max_out, int* n_out);
 // haar_api.hip: detectMultiScale + groupRectangles on a resident frame; *n_total = groups before the max_out cut
@@ -236,8 +244,8 @@ int detect_batch_run(dfd_handle* h, const uint8_t* frames_dev, int n, int hh, in
 int detect_frames_run(dfd_handle* h, const uint8_t* frames_dev, const FrameDesc* fd, const int* idx, int m, float conf_thr,
                       int max_faces, int32_t* xywh_out, int* n_out, int* n_total_out);
 // the analyzer over n frames of any streams and sizes (frame f of stream stream_ids[f], descriptor fd[f] into the arena
-// at frames_dev; the frames of one stream in stream order): one launch set, every stream's temporal state advances by its
-// frames - results identical to forensics_run on each stream's frames in order
+// at frames_dev; the frames of one stream in stream order): one launch set per analysis size, every stream's temporal
+// state advances by its frames - results identical to forensics_stream_run on each stream's frames in order
 int forensics_streams_run(dfd_handle* h, const uint8_t* frames_dev, const FrameDesc* fd, int n, const int* stream_ids,
                           const int* full, double* scores_out, double* prob_out);
 // jpeg_decode.hip: n JPEGs of one size -> packed BGR frames [n][hh][ww][3] at frames_dev (entropy decoding of the files

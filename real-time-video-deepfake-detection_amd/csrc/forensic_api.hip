@@ -1,5 +1,6 @@
 // C ABI of the forensic analyzer: device statistics -> the reference's threshold scoring
 // (reference frame_analysis.py:58-389), with the per-stream temporal state kept here.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <deque>
@@ -14,7 +15,8 @@ namespace dfd {
 
 struct ForensicStream {
     void* prev_gray = nullptr;     // size * size bytes on the device
-    int size = 0;                  // analysis edge, fixed by the stream's first frame (0: no frame yet)
+    int size = 0;                  // analysis edge, fixed by dfd_forensics_open or the stream's first frame (0: neither yet)
+    bool general = false;          // opened (dfd_forensics_open): the fused entries run it on the general chain, at 256 too
     bool has_prev = false;
     std::deque<double> diffs;      // last 30 mean absolute differences
     int frame_count = 0;
@@ -31,6 +33,9 @@ struct ForensicState {
     double* host_res = nullptr;    // pinned: statistics of a batch that ran on the second stream (forensics_batch_begin)
     size_t host_res_cap = 0;
     DevBuf frame_desc, prev_tab, copy_tab;   // forensics_streams_run: FrameDesc [n], predecessor planes [n], write-backs
+    DevBuf sized_gray, sized_part;           // ... its frames on the general chain: their gray planes, kept for the whole call
+                                             // (a predecessor may sit in an earlier chunk), and their per-row partial sums
+    DevBuf sized_diff_tab, sized_copy_tab;   // ... SizedDiffRow per such frame, SizedPlaneCopy per such stream
     std::map<int, std::vector<void*>> free_planes;   // stored planes of released streams by analysis edge, reused by the
                                                      // next new stream of that edge
     struct Sized {                           // dfd_forensics_sized / dfd_forensic_tap_sized: per analysis edge
@@ -217,6 +222,10 @@ int stream_size_check(dfd_handle* h, int stream_id, int size) {
     return DFD_OK;
 }
 
+// the fused entries (dfd_analyze_*) run a stream at the size it holds: on the general chain when it was opened or holds
+// another size than 256, on the 256x256 kernels otherwise (a stream nobody opened, or one that has no frame yet)
+bool on_general_chain(const ForensicStream& S) { return S.general || (S.size && S.size != 256); }
+
 int sized_init(dfd_handle* h, int S, int frames, ForensicState::Sized** out) {
     ForensicState& F = *h->forensic;
     ForensicState::Sized& Z = F.sized[S];
@@ -287,54 +296,168 @@ int forensics_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh
     return DFD_OK;
 }
 
-// n frames of any streams and sizes in one launch set (POST /analyze_batch, the session pool): the device statistics of
-// all frames at once (full mode kernels when any frame is full), every frame differenced against its predecessor - the
-// previous frame of its stream in this call, else the stream's stored plane - in one launch, each stream's last gray
-// plane written back to its stored slot in one launch, then the host half replayed frame by frame in order: every
-// stream's temporal deque, frame counter and stored plane end exactly where single calls in order would leave them.
+// n frames of any streams and sizes in one pass (POST /analyze_batch, the session pool).  The frames are grouped by the
+// chain and analysis edge of their stream: the frames of 256x256 streams nobody opened run on the 256x256 kernels as one
+// launch set, the frames of every other edge S on the general chain - one ragged resize to S x S and one launch set per
+// chunk of the group, a chunk being as many frames as fit the handle's work-memory budget (forensic_chunk_bytes; the
+// kernels treat every frame on its own, so the split changes no result).  The gray planes of the general chain are kept
+// for the whole call outside the chunk memory, so that ONE launch differences every such frame, whatever its edge and
+// chunk, against its predecessor - the previous frame of its stream in this call, else the stream's stored plane - and
+// ONE launch writes every stream's last gray plane back to its stored slot (the 256x256 group: its own two launches, as
+// before).  Then the host half is replayed frame by frame in call order: every stream's temporal deque, frame counter
+// and stored plane end exactly where single calls in order would leave them.  No stream's state moves before the wait.
 int forensics_streams_run(dfd_handle* h, const uint8_t* frames_dev, const FrameDesc* fd, int n, const int* stream_ids,
                           const int* full, double* scores_out, double* prob_out) {
     if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
     int rc = DFD_OK;
-    for (int f = 0; f < n; ++f)
-        if ((rc = stream_size_check(h, stream_ids[f], 256))) return rc;
-    if ((rc = state_init(h, n))) return rc;
+    if ((rc = state_init(h, 1))) return rc;
     ForensicState& F = *h->forensic;
-    bool any_full = false;
-    std::vector<const uint8_t*> prev(n);
+    std::vector<int> plain;                                          // frames on the 256x256 kernels, in call order
+    std::map<int, std::vector<int>> groups;                          // analysis edge -> frames on the general chain
+    std::vector<int> edge(n);                                        // 0: 256x256 kernels
+    size_t gray_bytes = 0, part_doubles = 0;
+    int n_sized = 0, max_S = 0;
+    for (int f = 0; f < n; ++f) {
+        ForensicStream& S = F.streams[stream_ids[f]];
+        edge[f] = on_general_chain(S) ? S.size : 0;
+        if ((rc = stream_plane(h, S, edge[f] ? edge[f] : 256))) return rc;
+        if (!edge[f]) { plain.push_back(f); continue; }
+        groups[edge[f]].push_back(f);
+        gray_bytes += (size_t)edge[f] * edge[f];
+        part_doubles += (size_t)edge[f];
+        max_S = std::max(max_S, edge[f]);
+        ++n_sized;
+    }
+    const int n_plain = (int)plain.size();
+    if (n_plain && (rc = state_init(h, n_plain))) return rc;
+    if ((rc = ensure(h, &F.sized_gray, gray_bytes))) return rc;
+    if ((rc = ensure(h, &F.sized_part, part_doubles * 8))) return rc;
+    struct Chunk { int S, first, count; ForensicState::Sized* Z; bool full; };   // first: index into the group's frames
+    std::vector<Chunk> chunks;
+    for (const auto& g : groups) {
+        const int S = g.first, cnt = (int)g.second.size();
+        const size_t fit = h->forensic_chunk_bytes / forensic_sized_bytes_per_frame(S);
+        const int per = (int)std::min<size_t>(std::max<size_t>(fit, 1), (size_t)cnt);
+        ForensicState::Sized* Z = nullptr;
+        if ((rc = sized_init(h, S, per, &Z))) return rc;
+        bool any = false;
+        for (int f : g.second) any = any || full[f] != 0;
+        for (int c0 = 0; c0 < cnt; c0 += per) chunks.push_back(Chunk{S, c0, std::min(per, cnt - c0), Z, any});
+    }
+    // where every frame's gray plane and partial sums are, and its slot in the descriptor table (group by group)
+    std::vector<const uint8_t*> gray(n);
+    std::vector<size_t> part_at(n, 0);
+    std::vector<FrameDesc> desc;
+    desc.reserve(n);
+    for (int j = 0; j < n_plain; ++j) {
+        gray[plain[j]] = F.buf.gray + (size_t)j * 65536;
+        desc.push_back(fd[plain[j]]);
+    }
+    {
+        size_t go = 0, po = 0;
+        for (const auto& g : groups)
+            for (int f : g.second) {
+                gray[f] = (const uint8_t*)F.sized_gray.p + go;
+                part_at[f] = po;
+                go += (size_t)g.first * g.first;
+                po += (size_t)g.first;
+                desc.push_back(fd[f]);
+            }
+    }
+    bool any_full = false;                                           // of the 256x256 group
+    std::vector<const uint8_t*> pred(n);                             // every frame's predecessor plane, or null
     std::map<int, int> last;                                         // stream -> its latest frame so far in this call
     for (int f = 0; f < n; ++f) {
-        any_full = any_full || full[f] != 0;
-        ForensicStream& S = F.streams[stream_ids[f]];
-        if ((rc = stream_plane(h, S))) return rc;
+        const ForensicStream& S = F.streams[stream_ids[f]];
         auto it = last.find(stream_ids[f]);
-        prev[f] = it != last.end() ? F.buf.gray + (size_t)it->second * 65536 : S.has_prev ? (const uint8_t*)S.prev_gray : nullptr;
+        pred[f] = it != last.end() ? gray[it->second] : S.has_prev ? (const uint8_t*)S.prev_gray : nullptr;
         last[stream_ids[f]] = f;
+        if (!edge[f]) any_full = any_full || full[f] != 0;
     }
+    std::vector<const uint8_t*> prev(n_plain);
+    for (int j = 0; j < n_plain; ++j) prev[j] = pred[plain[j]];
+    std::vector<SizedDiffRow> rows;
+    for (const auto& g : groups)
+        for (int f : g.second) rows.push_back(SizedDiffRow{gray[f], pred[f], (double*)F.sized_part.p + part_at[f], g.first, 0});
     std::vector<PlaneCopy> back;
-    for (const auto& kv : last) back.push_back(PlaneCopy{F.buf.gray + (size_t)kv.second * 65536, (uint8_t*)F.streams[kv.first].prev_gray});
+    std::vector<SizedPlaneCopy> back_sized;
+    for (const auto& kv : last) {
+        uint8_t* dst = (uint8_t*)F.streams[kv.first].prev_gray;
+        const int S = edge[kv.second];
+        if (S) back_sized.push_back(SizedPlaneCopy{gray[kv.second], dst, (size_t)S * S});
+        else back.push_back(PlaneCopy{gray[kv.second], dst});
+    }
     if ((rc = ensure(h, &F.frame_desc, (size_t)n * sizeof(FrameDesc)))) return rc;
-    if ((rc = ensure(h, &F.prev_tab, (size_t)n * sizeof(void*)))) return rc;
+    if ((rc = ensure(h, &F.prev_tab, (size_t)n_plain * sizeof(void*)))) return rc;
     if ((rc = ensure(h, &F.copy_tab, back.size() * sizeof(PlaneCopy)))) return rc;
-    if ((rc = ensure(h, &F.pair_part, (size_t)n * 256 * 8))) return rc;
-    if ((rc = mailbox_h2d(h, F.frame_desc.p, fd, (size_t)n * sizeof(FrameDesc)))) return rc;
-    if ((rc = mailbox_h2d(h, F.prev_tab.p, prev.data(), (size_t)n * sizeof(void*)))) return rc;
-    if ((rc = mailbox_h2d(h, F.copy_tab.p, back.data(), back.size() * sizeof(PlaneCopy)))) return rc;
-    launch_resize_bgr_ragged(frames_dev, (const FrameDesc*)F.frame_desc.p, n, F.buf.rs, 256, 256, h->stream);
-    launch_forensics(F.buf, n, any_full, h->color, F.twiddle, h->stream);
-    launch_absdiff_prev(F.buf.gray, (const uint8_t* const*)F.prev_tab.p, (double*)F.pair_part.p, n, h->stream);
-    launch_copy_planes((const PlaneCopy*)F.copy_tab.p, (int)back.size(), h->stream);
-    const double* st = (const double*)mailbox_d2h(h, F.buf.stats, (size_t)n * FORENSIC_STATS * 8);
-    const double* noise = (const double*)mailbox_d2h(h, F.buf.stats_noise, (size_t)n * 64 * 8);
-    const double* ela = (const double*)mailbox_d2h(h, F.buf.stats_ela, (size_t)n * 64 * 8);
-    const double* part = (const double*)mailbox_d2h(h, F.pair_part.p, (size_t)n * 256 * 8);
-    if (!st || !noise || !ela || !part) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
+    if ((rc = ensure(h, &F.pair_part, (size_t)n_plain * 256 * 8))) return rc;
+    if ((rc = ensure(h, &F.sized_diff_tab, rows.size() * sizeof(SizedDiffRow)))) return rc;
+    if ((rc = ensure(h, &F.sized_copy_tab, back_sized.size() * sizeof(SizedPlaneCopy)))) return rc;
+    if ((rc = mailbox_h2d(h, F.frame_desc.p, desc.data(), (size_t)n * sizeof(FrameDesc)))) return rc;
+    const FrameDesc* desc_dev = (const FrameDesc*)F.frame_desc.p;
+    // per frame: where the host finds its statistics once the stream has been waited for
+    std::vector<const double*> st(n, nullptr), noise(n, nullptr), ela(n, nullptr), part(n, nullptr);
+    if (n_plain) {
+        if ((rc = mailbox_h2d(h, F.prev_tab.p, prev.data(), (size_t)n_plain * sizeof(void*)))) return rc;
+        if ((rc = mailbox_h2d(h, F.copy_tab.p, back.data(), back.size() * sizeof(PlaneCopy)))) return rc;
+        launch_resize_bgr_ragged(frames_dev, desc_dev, n_plain, F.buf.rs, 256, 256, h->stream);
+        launch_forensics(F.buf, n_plain, any_full, h->color, F.twiddle, h->stream);
+        launch_absdiff_prev(F.buf.gray, (const uint8_t* const*)F.prev_tab.p, (double*)F.pair_part.p, n_plain, h->stream);
+        launch_copy_planes((const PlaneCopy*)F.copy_tab.p, (int)back.size(), h->stream);
+        const double* a = (const double*)mailbox_d2h(h, F.buf.stats, (size_t)n_plain * FORENSIC_STATS * 8);
+        const double* b = (const double*)mailbox_d2h(h, F.buf.stats_noise, (size_t)n_plain * 64 * 8);
+        const double* c = (const double*)mailbox_d2h(h, F.buf.stats_ela, (size_t)n_plain * 64 * 8);
+        const double* d = (const double*)mailbox_d2h(h, F.pair_part.p, (size_t)n_plain * 256 * 8);
+        if (!a || !b || !c || !d) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
+        for (int j = 0; j < n_plain; ++j) {
+            const int f = plain[j];
+            st[f] = a + (size_t)j * FORENSIC_STATS;
+            noise[f] = b + (size_t)j * 64;
+            ela[f] = c + (size_t)j * 64;
+            part[f] = d + (size_t)j * 256;
+        }
+    }
+    if (n_sized) {
+        if ((rc = mailbox_h2d(h, F.sized_diff_tab.p, rows.data(), rows.size() * sizeof(SizedDiffRow)))) return rc;
+        if ((rc = mailbox_h2d(h, F.sized_copy_tab.p, back_sized.data(), back_sized.size() * sizeof(SizedPlaneCopy)))) return rc;
+        int at = n_plain;                                            // the chunk's first slot of the descriptor table
+        for (const Chunk& c : chunks) {
+            const std::vector<int>& frames = groups[c.S];
+            const size_t nblk = (size_t)sized_blocks(c.S);
+            ForensicBuffers B = c.Z->buf;                            // the chunk's work memory, its gray planes in the call's store
+            B.gray = const_cast<uint8_t*>(gray[frames[c.first]]);
+            launch_resize_bgr_ragged(frames_dev, desc_dev + at, c.count, B.rs, c.S, c.S, h->stream);
+            DFD_HIP_TRY(h, launch_forensics_sized(B, c.S, c.count, c.full, h->color, c.Z->table, h->stream));
+            const double* a = (const double*)mailbox_d2h(h, B.stats, (size_t)c.count * FORENSIC_STATS * 8);
+            const double* b = c.full ? (const double*)mailbox_d2h(h, B.stats_noise, (size_t)c.count * nblk * 8) : nullptr;
+            const double* e = c.full ? (const double*)mailbox_d2h(h, B.stats_ela, (size_t)c.count * nblk * 8) : nullptr;
+            if (!a || (c.full && (!b || !e))) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
+            for (int j = 0; j < c.count; ++j) {
+                const int f = frames[c.first + j];
+                st[f] = a + (size_t)j * FORENSIC_STATS;
+                if (c.full) {
+                    noise[f] = b + (size_t)j * nblk;
+                    ela[f] = e + (size_t)j * nblk;
+                }
+            }
+            at += c.count;
+        }
+        launch_absdiff_prev_sized((const SizedDiffRow*)F.sized_diff_tab.p, n_sized, max_S, h->stream);
+        launch_copy_planes_sized((const SizedPlaneCopy*)F.sized_copy_tab.p, (int)back_sized.size(), max_S, h->stream);
+        const double* d = (const double*)mailbox_d2h(h, F.sized_part.p, part_doubles * 8);
+        if (!d) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
+        for (int f = 0; f < n; ++f)
+            if (edge[f]) part[f] = d + part_at[f];
+    }
     DFD_HIP_TRY(h, stream_sync(h));
     DFD_HIP_TRY(h, hipGetLastError());
     for (int f = 0; f < n; ++f) {
         double sc[6], ex[10], md, tcv;
-        prob_out[f] = score_frame(F.streams[stream_ids[f]], &st[(size_t)f * FORENSIC_STATS], &noise[(size_t)f * 64],
-                                  &ela[(size_t)f * 64], full[f] != 0, part + (size_t)f * 256, sc, ex, &md, &tcv);
+        ForensicStream& S = F.streams[stream_ids[f]];
+        const int e = edge[f];
+        prob_out[f] = e ? score_frame(S, st[f], noise[f], ela[f], full[f] != 0, part[f], sc, ex, &md, &tcv, e, (double)e * (double)e,
+                                      sized_blocks(e), true)
+                        : score_frame(S, st[f], noise[f], ela[f], full[f] != 0, part[f], sc, ex, &md, &tcv);
         for (int i = 0; i < 6; ++i) scores_out[(size_t)f * 6 + i] = sc[i];
     }
     return DFD_OK;
@@ -610,19 +733,17 @@ int dfd_forensics_state(dfd_handle* h, int stream_id, int* frame_count, int* n_d
 }
 
 // ---- any square analysis size (forensic_sized_kernels.hip): the same host half, S in place of 256
-int dfd_forensics_sized(dfd_handle* h, int stream_id, const uint8_t* bgr, int hh, int ww, int stride, int size, int full,
+}  // extern "C"
+
+namespace dfd {
+
+// the analyzer at analysis edge `size` on a frame that is already in HBM (shared by dfd_forensics_sized and the fused
+// single-frame entries on a stream of the general chain)
+int forensics_sized_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh, int ww, int stride, int size, int full,
                         double* scores_out, double* prob_out, double* stats_out) {
-    if (!h) return DFD_ERR_ARG;
-    if (!bgr || !scores_out || !prob_out || hh <= 0 || ww <= 0 || stride < ww * 3)
-        return fail(h, DFD_ERR_ARG, "forensics_sized: bad pointer or geometry");
-    if (!sized_ok(size))
-        return fail(h, DFD_ERR_ARG, "forensics_sized: analysis size %d is not a multiple of 16 in %d..%d", size, SIZED_MIN, SIZED_MAX);
     if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
-    DFD_HIP_TRY(h, hipSetDevice(h->device));
     int rc = stream_size_check(h, stream_id, size);
     if (rc) return rc;
-    if ((rc = ensure(h, &h->frame_buf, (size_t)hh * stride))) return rc;
-    DFD_HIP_TRY(h, hipMemcpyAsync(h->frame_buf.p, bgr, (size_t)hh * stride, hipMemcpyHostToDevice, h->stream));
     if ((rc = state_init(h, 1))) return rc;
     ForensicState& F = *h->forensic;
     ForensicState::Sized* Z = nullptr;
@@ -633,7 +754,7 @@ int dfd_forensics_sized(dfd_handle* h, int stream_id, const uint8_t* bgr, int hh
     const int nblk = sized_blocks(size);
     const ForensicBuffers& B = Z->buf;
 
-    launch_resize_bgr((const uint8_t*)h->frame_buf.p, 1, hh, ww, stride, 0, B.rs, size, size, h->stream);
+    launch_resize_bgr(frame_dev, 1, hh, ww, stride, 0, B.rs, size, size, h->stream);
     DFD_HIP_TRY(h, launch_forensics_sized(B, size, 1, full != 0, h->color, Z->table, h->stream));
     if (S.has_prev) launch_absdiff_sized(B.gray, (const uint8_t*)S.prev_gray, Z->diff_part, size, h->stream);
     double st[FORENSIC_STATS];
@@ -660,6 +781,52 @@ int dfd_forensics_sized(dfd_handle* h, int stream_id, const uint8_t* bgr, int hh
                                                  (double)S.frame_count};
         for (int i = 0; i < DFD_FORENSIC_NSTATS; ++i) stats_out[i] = out[i];
     }
+    return DFD_OK;
+}
+
+// the fused single-frame entries: the stream at the size and on the chain it holds
+int forensics_stream_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh, int ww, int stride, int full,
+                         double* scores_out, double* prob_out) {
+    if (h->forensic) {
+        auto it = h->forensic->streams.find(stream_id);
+        if (it != h->forensic->streams.end() && on_general_chain(it->second))
+            return forensics_sized_run(h, stream_id, frame_dev, hh, ww, stride, it->second.size, full, scores_out, prob_out, nullptr);
+    }
+    return forensics_run(h, stream_id, frame_dev, hh, ww, stride, full, scores_out, prob_out, nullptr);
+}
+
+}  // namespace dfd
+
+extern "C" {
+
+int dfd_forensics_sized(dfd_handle* h, int stream_id, const uint8_t* bgr, int hh, int ww, int stride, int size, int full,
+                        double* scores_out, double* prob_out, double* stats_out) {
+    if (!h) return DFD_ERR_ARG;
+    if (!bgr || !scores_out || !prob_out || hh <= 0 || ww <= 0 || stride < ww * 3)
+        return fail(h, DFD_ERR_ARG, "forensics_sized: bad pointer or geometry");
+    if (!sized_ok(size))
+        return fail(h, DFD_ERR_ARG, "forensics_sized: analysis size %d is not a multiple of 16 in %d..%d", size, SIZED_MIN, SIZED_MAX);
+    if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    int rc = stream_size_check(h, stream_id, size);
+    if (rc) return rc;
+    if ((rc = ensure(h, &h->frame_buf, (size_t)hh * stride))) return rc;
+    DFD_HIP_TRY(h, hipMemcpyAsync(h->frame_buf.p, bgr, (size_t)hh * stride, hipMemcpyHostToDevice, h->stream));
+    return forensics_sized_run(h, stream_id, (const uint8_t*)h->frame_buf.p, hh, ww, stride, size, full, scores_out, prob_out, stats_out);
+}
+
+int dfd_forensics_open(dfd_handle* h, int stream_id, int size) {
+    if (!h) return DFD_ERR_ARG;
+    if (!sized_ok(size))
+        return fail(h, DFD_ERR_ARG, "forensics_open: analysis size %d is not a multiple of 16 in %d..%d", size, SIZED_MIN, SIZED_MAX);
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    int rc = stream_size_check(h, stream_id, size);                  // another size already: refused, nothing changes
+    if (rc) return rc;
+    if ((rc = state_init(h, 1))) return rc;
+    ForensicStream& S = h->forensic->streams[stream_id];
+    if (S.size) return DFD_OK;                                       // the same size: as it is
+    S.size = size;
+    S.general = true;
     return DFD_OK;
 }
 

@@ -21,5 +21,13 @@ hipError_t launch_forensics_sized(const ForensicBuffers& B, int S, int n, bool f
                                   hipStream_t s, ForensicStart start = FROM_RS, const ForensicTaps* taps = nullptr);
 // sum |gray - prev| per image row: part [S]
 void launch_absdiff_sized(const uint8_t* gray, const uint8_t* prev, double* part, int S, hipStream_t s);
+// frames of many streams and edges (device table, one row per frame; max_S: the largest edge in it): frame `gray`
+// against `prev` - an earlier frame of its stream in the call, the stream's stored plane, or null (sums 0) - into its S
+// partial sums `part`, the doubles launch_absdiff_sized writes.  One launch.
+struct SizedDiffRow { const uint8_t* gray; const uint8_t* prev; double* part; int S; int pad; };
+void launch_absdiff_prev_sized(const SizedDiffRow* rows_dev, int n, int max_S, hipStream_t s);
+// bytes = S * S of the plane; one launch for every entry
+struct SizedPlaneCopy { const uint8_t* src; uint8_t* dst; size_t bytes; };
+void launch_copy_planes_sized(const SizedPlaneCopy* copies_dev, int n, int max_S, hipStream_t s);
 
 }  // namespace dfd

@@ -14,6 +14,8 @@
 //   sz_canny_hyst_kernel   8-connected hysteresis in LDS + edge count     frame_analysis.py:289-290
 //   sz_hsv_stats_kernel    BGR->HSV integer + S/V moments + hue set       frame_analysis.py:318-338
 //   sz_absdiff_kernel      sum |gray - prev gray|                         frame_analysis.py:363-364
+//   sz_absdiff_prev_kernel the same for frames of many streams and edges, one launch (the batched stream entries)
+//   sz_copy_planes_kernel  every stream's last gray plane to its stored slot, one launch
 //
 // Compiled with -ffp-contract=off (operation orders restate OpenCV's float filters).
 #include "forensic_sized_kernels.h"
@@ -654,6 +656,37 @@ __global__ __launch_bounds__(256) void sz_absdiff_kernel(const uint8_t* __restri
     if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
+// frames of many streams and analysis edges in one launch: table row blockIdx.y is one frame (its gray plane, the plane
+// of its predecessor or null, its edge S and its S partial sums), a wave owns one image row and a lane 16 bytes of it (a
+// row is at most SIZED_MAX = 64 x 16 bytes, and a multiple of 16: whole 16-byte loads, none past the row).  The sums are
+// integers below 2^18, exact in every order - the same doubles sz_absdiff_kernel writes for the frame.  Null predecessor:
+// partial sums 0.
+__global__ __launch_bounds__(256) void sz_absdiff_prev_kernel(const SizedDiffRow* __restrict__ rows) {
+    const SizedDiffRow r = rows[blockIdx.y];
+    const int lane = threadIdx.x & 63, y = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (y >= r.S) return;                                       // (wave-uniform)
+    unsigned d = 0;
+    if (r.prev && 16 * lane < r.S) {
+        const size_t o = (size_t)y * r.S + 16 * lane;
+        const uint4 a = *reinterpret_cast<const uint4*>(r.gray + o);
+        const uint4 b = *reinterpret_cast<const uint4*>(r.prev + o);
+        d = __builtin_amdgcn_sad_u8(a.x, b.x, d);
+        d = __builtin_amdgcn_sad_u8(a.y, b.y, d);
+        d = __builtin_amdgcn_sad_u8(a.z, b.z, d);
+        d = __builtin_amdgcn_sad_u8(a.w, b.w, d);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) d += __shfl_xor(d, off);
+    if (lane == 0) r.part[y] = (double)d;
+}
+
+// one plane of `bytes` (S * S, a multiple of 256) per table entry, 16 bytes per thread
+__global__ __launch_bounds__(256) void sz_copy_planes_kernel(const SizedPlaneCopy* __restrict__ copies) {
+    const SizedPlaneCopy pc = copies[blockIdx.y];
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i * 16 < pc.bytes) reinterpret_cast<uint4*>(pc.dst)[i] = reinterpret_cast<const uint4*>(pc.src)[i];
+}
+
 // ------------------------------------------------------------------------------- finalize
 // One wave per frame: lane l folds partial rows l, l + 64, ... below S (in that order), then a butterfly over the lanes -
 // a fixed order, so the sums are run-to-run and batch-size invariant.  Edge density and the moments divide by S^2.
@@ -748,6 +781,15 @@ hipError_t launch_forensics_sized(const ForensicBuffers& B, int S, int n, bool f
 
 void launch_absdiff_sized(const uint8_t* gray, const uint8_t* prev, double* part, int S, hipStream_t s) {
     hipLaunchKernelGGL(sz_absdiff_kernel, dim3(S), dim3(256), 0, s, gray, prev, part, S);
+}
+
+void launch_absdiff_prev_sized(const SizedDiffRow* rows_dev, int n, int max_S, hipStream_t s) {
+    hipLaunchKernelGGL(sz_absdiff_prev_kernel, dim3((max_S + 3) / 4, n), dim3(256), 0, s, rows_dev);
+}
+
+void launch_copy_planes_sized(const SizedPlaneCopy* copies_dev, int n, int max_S, hipStream_t s) {
+    const size_t vecs = (size_t)max_S * max_S / 16;
+    hipLaunchKernelGGL(sz_copy_planes_kernel, dim3((unsigned)((vecs + 255) / 256), n), dim3(256), 0, s, copies_dev);
 }
 
 void forensic_sized_table(int S, float2* out) {

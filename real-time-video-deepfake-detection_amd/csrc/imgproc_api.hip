@@ -506,7 +506,7 @@ int analyze_frame_resident(dfd_handle* h, int stream_id, int hh, int ww, int str
                            int* n_faces_out, float* logits_out, bool tta) {
     int rc;
     const uint8_t* fd = (const uint8_t*)h->frame_buf.p;
-    if ((rc = forensics_run(h, stream_id, fd, hh, ww, stride, full_forensics, scores_out, forensic_prob_out, nullptr))) return rc;
+    if ((rc = forensics_stream_run(h, stream_id, fd, hh, ww, stride, full_forensics, scores_out, forensic_prob_out))) return rc;
     *n_faces_out = 0;
     h->last_detections = 0;
     if ((!h->ssd && !h->haar) || hh < 30 || ww < 30) return DFD_OK;  // no detector at all / tiny frame: no faces

@@ -73,6 +73,19 @@ def tta_commit_draws(state, n_faces: int, copies: int):
         random.uniform(-3, 3)
 
 
+def forensic_size_from_env() -> Optional[int]:
+    """DFD_FORENSIC_SIZE=<S>: the analysis size the server gives its global detector and every session's detector (it
+    implies any_size).  Unset or empty: None, the reference's 256x256.  Not an integer: ValueError; a size the
+    analyzer does not take fails with the analyzer's ValueError where the detector is built."""
+    v = os.environ.get("DFD_FORENSIC_SIZE", "").strip()
+    if not v:
+        return None
+    try:
+        return int(v)
+    except ValueError:
+        raise ValueError(f"DFD_FORENSIC_SIZE={v!r}: analysis_size must be an integer S, a multiple of 16 in 32..1024") from None
+
+
 class _LazyModel:
     """`model` global of the reference (:32): the classifier bound to the default handle."""
 
@@ -97,7 +110,11 @@ model = _LazyModel()
 
 class DeepfakeDetector:
     def __init__(self, enable_gradcam=False, use_tta=True, num_tta_augmentations=3, detection_threshold=0.5,
-                 face_weight=0.70, forensic_weight=0.30, *, handle: Optional[Handle] = None, request_tta: bool = False):
+                 face_weight=0.70, forensic_weight=0.30, *, handle: Optional[Handle] = None, request_tta: bool = False,
+                 forensic_size: Optional[int] = None):
+        """forensic_size: None = the reference's 256x256 analysis, or S = a (S, S) analysis on the general forensic chain
+        (a multiple of 16 in 32..1024, else the analyzer's ValueError); every fused and batched call runs at that size.
+        Construction makes no library call: the forensic stream is opened by the first call that uses it."""
         self.enable_gradcam = enable_gradcam
         self.use_tta = use_tta
         # the /analyze flow (analyze_request, analyze_request_batch, the session pool) carries the copies only when this is
@@ -112,7 +129,11 @@ class DeepfakeDetector:
                                                 detection_threshold=detection_threshold)
         self.frame_count = 0
         self._handle = handle
-        self.frame_analyzer = FrameForensicAnalyzer(analysis_size=(256, 256), handle=handle)
+        if forensic_size is None:
+            self.frame_analyzer = FrameForensicAnalyzer(analysis_size=(256, 256), handle=handle)
+        else:
+            self.frame_analyzer = FrameForensicAnalyzer(analysis_size=(int(forensic_size), int(forensic_size)), handle=handle,
+                                                        any_size=True, defer_open=True)
         self.full_forensic_interval = 3
         self.last_frame_forensic_result = None
         self.calibrator = None
@@ -281,38 +302,17 @@ class DeepfakeDetector:
             return None
         return {'fake_probability': p, 'heatmap': heat[0], 'overlay': overlay[0]}
 
-    def _sized_analyzer(self) -> bool:
-        """a swapped-in analyzer at another analysis size: its stream is not a 256x256 one, so the fused calls (which
-        run the 256x256 forensic kernels on the stream) must not be made on it"""
-        return tuple(self.frame_analyzer.analysis_size) != (256, 256)
+    def _open_stream(self):
+        """before a fused call: a sized analyzer's stream holds its analysis size on this detector's handle (a no-op
+        in the library when it does already; a released stream is opened again)"""
+        self.frame_analyzer.open(self.handle)
 
-    def _frame_sized(self, frame, full, max_faces, request):
-        """the work of the fused call as separate ones, for an analyzer at another analysis size: forensics through
-        the analyzer, detection and classification through the detector and crop entries (with TTA on, the copies of
-        every face in the same classification pass) -> (scores, prob, boxes, logits, n_detected)"""
-        res = self.frame_analyzer.analyze(frame) if full else self.frame_analyzer.analyze_fast(frame)
-        boxes, logits = [], []
-        if self.handle.has_detector:
-            boxes = self.handle.detect_faces(frame, confidence_threshold=0.5)
-        elif self.handle.has_haar:
-            boxes = self.handle.detect_faces_haar(frame)
-        n_detected = len(boxes)
-        boxes = boxes[:max_faces]
-        if boxes:
-            copies = self._tta_copies(request)
-            step = max(1, self.handle.max_batch // (1 + copies))     # images per classification pass
-            if copies == 0:
-                for i in range(0, len(boxes), step):
-                    logits += list(self.handle.classify_crops(frame, boxes[i:i + step], apply_clahe=True)[:, 0])
-            else:
-                state, draws = tta_draw_table(len(boxes), copies)
-                try:
-                    for i in range(0, len(boxes), step):
-                        logits += list(self.handle.classify_crops_tta(frame, boxes[i:i + step], copies,
-                                                                      draws[i * copies:(i + step) * copies], apply_clahe=True))
-                finally:
-                    tta_commit_draws(state, len(logits), copies)
-        return res['scores'], res['fake_probability'], boxes, logits, n_detected
+    def _forensics_only(self, frame, full):
+        """'frame_only' mode (no detector of either kind): the analyzer's call alone -> (scores, probability)"""
+        a = self.frame_analyzer
+        if a.sized:
+            return self.handle.forensics_sized(frame, a.analysis_size[0], full=full, stream_id=a.stream_id)[:2]
+        return self.handle.forensics(frame, full=full, stream_id=a.stream_id)[:2]
 
     def _frame_on_gpu(self, frame, max_faces, jpeg: Optional[bytes] = None, request: bool = False):
         """forensics + detection + per-face logits in one library call (with TTA on: every face's row of logits, original
@@ -320,15 +320,7 @@ class DeepfakeDetector:
         device from the request's bytes (dfd_analyze_jpeg) instead of uploaded raw; returns its (H, W) as 4th item."""
         full = self._forensic_is_full()
         with self._lock:
-            if self._sized_analyzer():
-                if jpeg is not None:
-                    frame = self.handle.decode_jpeg(jpeg)
-                scores, prob, boxes, logits, _ = self._frame_sized(frame, full, max_faces, request)
-                forensic = {'scores': scores, 'fake_probability': prob,
-                            'analysis_type': 'frame_forensic' if full else 'frame_forensic_fast',
-                            'frame_number': self.frame_analyzer.frame_count}
-                self.last_frame_forensic_result = forensic
-                return (forensic, boxes, logits, frame.shape[:2]) if jpeg is not None else (forensic, boxes, logits)
+            self._open_stream()                     # a sized analyzer: the fused call runs its stream at its own size
             if jpeg is not None:
                 scores, prob, boxes, logits, shape = self._armed(
                     self.handle.analyze_jpeg, max_faces, request, data=jpeg, full_forensics=full,
@@ -344,7 +336,7 @@ class DeepfakeDetector:
                     self.handle.analyze_frame, max_faces, request, frame=frame, full_forensics=full,
                     stream_id=self.frame_analyzer.stream_id, confidence_threshold=0.5, max_faces=max_faces)
             else:                                   # no detector of either kind: 'frame_only' mode (runtime.py)
-                scores, prob, _ = self.handle.forensics(frame, full=full, stream_id=self.frame_analyzer.stream_id)
+                scores, prob = self._forensics_only(frame, full)
                 boxes, logits = [], []
             number = self.frame_analyzer.frame_count
         forensic = {'scores': scores, 'fake_probability': prob,
@@ -443,8 +435,9 @@ class DeepfakeDetector:
                 'frame_count': self.frame_count}
 
     def release(self):
-        """Frees this detector's forensic stream on the device (dfd_forensics_release): its 64 KB plane goes back to the
-        handle for the next new stream.  Used again afterwards, the detector's forensic stream starts fresh."""
+        """Frees this detector's forensic stream on the device (dfd_forensics_release): its gray plane goes back to the
+        handle for the next new stream of its analysis size.  Used again afterwards, the detector's forensic stream
+        starts fresh (at the analyzer's analysis size)."""
         h = self.frame_analyzer._existing_handle()
         if h is not None:
             h.forensics_release(self.frame_analyzer.stream_id)
@@ -459,20 +452,15 @@ class DeepfakeDetector:
         n = len(items)
         full = [(self.frame_count + i) % self.full_forensic_interval == 0 for i in range(n)]
         with self._lock:
-            if self._sized_analyzer():                              # the batched stream entry is 256x256 only: frame by frame
-                res, shape = [], None
-                for it, fl in zip(items, full):
-                    fr = self.handle.decode_jpeg(it) if isinstance(it, (bytes, bytearray)) else np.ascontiguousarray(it)
-                    res.append(self._frame_sized(fr, fl, 1, True))
-                    shape = fr.shape[:2]
-            elif self.handle.has_detector or self.handle.has_haar:
+            self._open_stream()
+            if self.handle.has_detector or self.handle.has_haar:
                 res, shape = self._armed(self.handle.analyze_stream_batch, n, True, items=items, full_flags=full,
                                          stream_id=self.frame_analyzer.stream_id, confidence_threshold=0.5, max_faces=1)
             else:                                                   # no detector of either kind: forensics only, frame by frame
                 res, shape = [], None
                 for it, fl in zip(items, full):
                     fr = self.handle.decode_jpeg(it) if isinstance(it, (bytes, bytearray)) else np.ascontiguousarray(it)
-                    scores, prob, _ = self.handle.forensics(fr, full=fl, stream_id=self.frame_analyzer.stream_id)
+                    scores, prob = self._forensics_only(fr, fl)
                     res.append((scores, prob, [], [], 0))
                     shape = fr.shape[:2]
             first_number = self.frame_analyzer.frame_count - n + 1

@@ -4,8 +4,9 @@
 visible attributes (reference frame_analysis.py:22-395); each call is one `dfd_forensics`
 through the C ABI, which resizes the frame to 256x256 on the GPU, runs the six signal kernels
 on the library's stream and applies the reference's thresholds (`dfd_forensics_sized` and the
-general kernel chain for any other square size, opted into with `any_size`).  The temporal state lives in the
-library per stream id; the attributes below read it back.
+general kernel chain for any other square size, opted into with `any_size`; such an analyzer opens
+its stream at that size, `dfd_forensics_open`, so that the fused and batched entries run it there too).
+The temporal state lives in the library per stream id; the attributes below read it back.
 """
 from __future__ import annotations
 
@@ -20,24 +21,32 @@ from ._lib import Handle
 _stream_ids = itertools.count(1)
 
 
+def check_analysis_size(analysis_size, any_size: bool = True):
+    """-> the size as a tuple of ints, or ValueError: (256, 256) always; with `any_size` every square (S, S) with S a
+    multiple of 16 in 32..1024"""
+    size = tuple(int(v) for v in analysis_size)
+    if size != (256, 256):
+        if not any_size:
+            raise ValueError("the HIP forensic kernels are built for analysis_size=(256, 256) "
+                             "(the only size the reference ever constructs, deepfake_detection.py:327); "
+                             "any_size=True or DFD_FORENSIC_ANY_SIZE=1 admits other square sizes")
+        if len(size) != 2 or size[0] != size[1] or size[0] % 16 or not 32 <= size[0] <= 1024:
+            raise ValueError(f"analysis_size {size}: supported are square sizes (S, S) with S a multiple of 16 "
+                             "in 32..1024 (the reference itself fails on non-square sizes, and the ELA round "
+                             "trip needs whole 16x16 JPEG MCUs)")
+    return size
+
+
 class FrameForensicAnalyzer:
     def __init__(self, analysis_size=(256, 256), *, handle: Optional[Handle] = None, stream_id: Optional[int] = None,
-                 any_size: Optional[bool] = None):
+                 any_size: Optional[bool] = None, defer_open: bool = False):
         """`any_size` (None: the environment variable DFD_FORENSIC_ANY_SIZE, default off) admits every square
         analysis_size (S, S) with S a multiple of 16 in 32..1024, run by the general kernel chain
-        (`dfd_forensics_sized`); (256, 256) always runs the 256x256 kernels."""
+        (`dfd_forensics_sized`); (256, 256) always runs the 256x256 kernels.  `defer_open`: make no library call here
+        (an owner that builds analyzers outside the lock that guards its handle opens the stream later, under it)."""
         if any_size is None:
             any_size = os.environ.get("DFD_FORENSIC_ANY_SIZE", "").strip().lower() in ("1", "true", "yes", "on")
-        size = tuple(int(v) for v in analysis_size)
-        if size != (256, 256):
-            if not any_size:
-                raise ValueError("the HIP forensic kernels are built for analysis_size=(256, 256) "
-                                 "(the only size the reference ever constructs, deepfake_detection.py:327); "
-                                 "any_size=True or DFD_FORENSIC_ANY_SIZE=1 admits other square sizes")
-            if len(size) != 2 or size[0] != size[1] or size[0] % 16 or not 32 <= size[0] <= 1024:
-                raise ValueError(f"analysis_size {size}: supported are square sizes (S, S) with S a multiple of 16 "
-                                 "in 32..1024 (the reference itself fails on non-square sizes, and the ELA round "
-                                 "trip needs whole 16x16 JPEG MCUs)")
+        size = check_analysis_size(analysis_size, any_size)
         self.analysis_size = size
         self.any_size = bool(any_size)
         self._handle = handle
@@ -45,6 +54,21 @@ class FrameForensicAnalyzer:
         self.weights = {'frequency': 0.25, 'noise': 0.20, 'ela': 0.20, 'edge': 0.15, 'color': 0.10,
                         'temporal': 0.10}                       # reference :49-56 (reported; applied in the library)
         self.last_stats = {}
+        if handle is not None and not defer_open:
+            self.open()
+
+    @property
+    def sized(self) -> bool:
+        """another analysis size than 256x256: the stream runs on the general kernel chain"""
+        return self.analysis_size != (256, 256)
+
+    def open(self, handle: Optional[Handle] = None):
+        """A sized analyzer fixes its stream's analysis size in the library (a no-op when the stream holds it already;
+        needed again after the stream was released).  Called on construction with a handle (unless deferred) and by the
+        callers of the fused entries (DeepfakeDetector, sessions.SessionPool) before they pass `stream_id` to one, on
+        the `handle` that call is made on (default: the analyzer's own)."""
+        if self.sized:
+            (self.handle if handle is None else handle).forensics_open(self.stream_id, self.analysis_size[0])
 
     # ---- device
     @property

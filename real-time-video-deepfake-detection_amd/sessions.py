@@ -23,7 +23,8 @@ from typing import Optional
 import numpy as np
 
 from ._lib import DfdError, Handle
-from .deepfake_detection import DeepfakeDetector, tta_commit_draws, tta_draw_table
+from .deepfake_detection import DeepfakeDetector, forensic_size_from_env, tta_commit_draws, tta_draw_table
+from .frame_analysis import check_analysis_size
 
 MAX_PASS_FRAMES = 256                     # frames of one device pass (the classifier runs them in max_batch chunks)
 MAX_PASS_PIXELS = 1 << 27                 # the library's per-call budget (dfd_common.h kMaxBatchPixels)
@@ -92,8 +93,14 @@ def _pillow_bgr(data: bytes):
 
 class SessionPool:
     def __init__(self, handle: Optional[Handle] = None, lock=None, detection_threshold: float = 0.55,
-                 max_sessions: int = 1024, idle_seconds: float = 300, use_tta: bool = False, num_tta_augmentations: int = 1):
+                 max_sessions: int = 1024, idle_seconds: float = 300, use_tta: bool = False, num_tta_augmentations: int = 1,
+                 forensic_size: Optional[int] = None):
         self._handle = handle
+        # analysis size of every session's forensic stream: None = the environment variable DFD_FORENSIC_SIZE (unset:
+        # 256x256).  Streams of any sizes share the pass's one library call; an invalid size fails here.
+        self.forensic_size = forensic_size_from_env() if forensic_size is None else int(forensic_size)
+        if self.forensic_size is not None:
+            check_analysis_size((self.forensic_size, self.forensic_size))                       # ValueError for a bad size
         # test-time augmentation for every session: the pass's one library call is armed with the draws of all its frames.
         # Draw order = the order results are applied to sessions: submissions in queue order, a submission's frames in
         # stream order (Python's global `random`, left where that many per-face calls would have left it)
@@ -135,7 +142,8 @@ class SessionPool:
         s = _Session(sid, DeepfakeDetector(enable_gradcam=False, use_tta=self.use_tta,
                                            num_tta_augmentations=self.num_tta_augmentations,
                                            request_tta=self.use_tta,
-                                           detection_threshold=self.detection_threshold, handle=self.handle))
+                                           detection_threshold=self.detection_threshold, handle=self.handle,
+                                           forensic_size=self.forensic_size))
         self._sessions[sid] = s
         return s
 
@@ -265,6 +273,7 @@ class SessionPool:
             offset = {}                         # session -> frames of it earlier in this pass
             for s, items, _ in live:
                 d = s.detector
+                d._open_stream()                # under self.lock: building the session (submit's thread) made no library call
                 k = offset.get(s, 0)
                 for i, it in enumerate(items):
                     flat.append(it)
