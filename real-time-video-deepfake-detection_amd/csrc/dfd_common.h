@@ -197,11 +197,10 @@ void copy_kernel_async(void* dst, const void* src, size_t bytes, hipStream_t s);
 int color_tables_init(dfd_handle* h);
 
 // stages that work on a frame already resident in HBM (forensic_api / ssd_api / imgproc_api)
-int forensics_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh, int ww, int stride, int full,
-                  double* scores_out, double* prob_out, double* stats_out);
-// the same for the fused single-frame entries: the stream at the analysis size it holds - the general chain
-// (forensic_sized_kernels.hip) for a stream that was opened (dfd_forensics_open) or holds another size than 256,
-// forensics_run otherwise
+// the analyzer for the fused single-frame entries: the stream at the analysis size and on the chain it holds - the general
+// chain (forensic_sized_kernels.hip) for a stream that was opened (dfd_forensics_open) or holds another size than 256,
+// the 256x256 kernels otherwise.  One host path (forensic_api.hip forensics_chain_run) serves both, and dfd_forensics /
+// dfd_forensics_sized with them.
 int forensics_stream_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh, int ww, int stride, int full,
                          double* scores_out, double* prob_out);
 int detect_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride, float conf_thr, int32_t* xywh_out,

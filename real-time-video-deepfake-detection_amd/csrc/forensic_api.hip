@@ -1,9 +1,10 @@
-// C ABI of the forensic analyzer: device statistics -> the reference's threshold scoring
-// (reference frame_analysis.py:58-389), with the per-stream temporal state kept here.
+// C ABI of the forensic analyzer: device statistics -> the reference's threshold scoring (forensic_score.h; reference
+// frame_analysis.py:58-389), with the per-stream temporal state kept here.  The 256x256 kernels and the general chain
+// at any edge S share ONE host path: a ForensicChain says which launcher, carve and table a call uses.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <deque>
+#include <utility>
 
 #include "dfd_common.h"
 #include "forensic_kernels.h"
@@ -13,22 +14,29 @@ using namespace dfd;
 
 namespace dfd {
 
-struct ForensicStream {
+struct ForensicStream : ForensicTemporal {
     void* prev_gray = nullptr;     // size * size bytes on the device
     int size = 0;                  // analysis edge, fixed by dfd_forensics_open or the stream's first frame (0: neither yet)
     bool general = false;          // opened (dfd_forensics_open): the fused entries run it on the general chain, at 256 too
-    bool has_prev = false;
-    std::deque<double> diffs;      // last 30 mean absolute differences
-    int frame_count = 0;
 };
+
+// one chain's device resources: the 256x256 kernels (forensic_kernels.hip, G.general = false) or the general chain at
+// one analysis edge (forensic_sized_kernels.hip)
+struct ForensicChain {
+    ForensicGeometry G;
+    DevBuf work, tap_store;        // work: carved into `buf` for `cap` frames; tap_store: spectrum, logmag, edges of the test tap
+    int cap = 0;
+    ForensicBuffers buf{};
+    float2* table = nullptr;       // exp(-2 pi i j / S): S entries on the general chain, the first S / 2 on the 256x256 kernels
+    double* diff_part = nullptr;   // G.npart partial sums of the single-frame difference
+};
+
+constexpr int FIXED_EDGE = 256;
 
 struct ForensicState {
     std::map<int, ForensicStream> streams;
-    DevBuf work;                   // carved by forensic_carve for `cap` frames
-    int cap = 0;
-    ForensicBuffers buf{};
-    float2* twiddle = nullptr;
-    double* diff_part = nullptr;   // 256 partial sums
+    // keyed by (general, S): the 256x256 kernels and a general chain at 256 differ in table length and in f32_means
+    std::map<std::pair<bool, int>, ForensicChain> chains;
     DevBuf pair_idx, pair_part;    // dfd_forensic_signals_device: predecessor indices, [n][256] partial sums
     double* host_res = nullptr;    // pinned: statistics of a batch that ran on the second stream (forensics_batch_begin)
     size_t host_res_cap = 0;
@@ -38,15 +46,6 @@ struct ForensicState {
     DevBuf sized_diff_tab, sized_copy_tab;   // ... SizedDiffRow per such frame, SizedPlaneCopy per such stream
     std::map<int, std::vector<void*>> free_planes;   // stored planes of released streams by analysis edge, reused by the
                                                      // next new stream of that edge
-    struct Sized {                           // dfd_forensics_sized / dfd_forensic_tap_sized: per analysis edge
-        DevBuf work, tap_store;
-        int cap = 0;
-        ForensicBuffers buf{};
-        float2* table = nullptr;             // exp(-2 pi i j / S), S entries
-        double* diff_part = nullptr;         // S partial sums
-    };
-    std::map<int, Sized> sized;
-    DevBuf tap_store;                        // dfd_forensic_tap: spectrum, logmag, edges; allocated on its first call
 };
 
 void forensic_destroy(dfd_handle* h) {
@@ -59,144 +58,67 @@ void forensic_destroy(dfd_handle* h) {
 
 namespace {
 
-int state_init(dfd_handle* h, int frames) {
-    if (!h->forensic) {
-        h->forensic = new ForensicState();
-        float2 tw[128];
-        for (int k = 0; k < 128; ++k) {
-            const double a = -2.0 * M_PI * k / 256.0;
-            tw[k] = make_float2((float)std::cos(a), (float)std::sin(a));
-        }
-        void* d = nullptr;
-        DFD_HIP_TRY(h, hipMalloc(&d, sizeof tw));
+// ---- what differs between the two chains on the host: table length, bytes per frame + carve, launchers
+size_t chain_table_entries(const ForensicGeometry& G) { return (size_t)(G.general ? G.S : G.S / 2); }
+
+size_t chain_bytes_per_frame(const ForensicGeometry& G) {
+    return G.general ? forensic_sized_bytes_per_frame(G.S) : forensic_bytes_per_frame();
+}
+
+void chain_carve(const ForensicGeometry& G, void* base, int n, ForensicBuffers* out) {
+    if (G.general) forensic_sized_carve(base, G.S, n, out);
+    else forensic_carve(base, n, out);
+}
+
+// B: the chain's own buffers, or a copy with some of them elsewhere (forensics_streams_run)
+hipError_t chain_launch(const ForensicChain& C, const ForensicBuffers& B, int n, bool full, const ColorTables& T, hipStream_t s,
+                        int gray_only = 0, ForensicStart start = FROM_RS, const ForensicTaps* taps = nullptr) {
+    if (C.G.general) return launch_forensics_sized(B, C.G.S, n, full, T, C.table, s, start, taps);
+    launch_forensics(B, n, full, T, C.table, s, gray_only, start, taps);
+    return hipSuccess;
+}
+
+// frame 0 of the chain's buffers against `prev` -> C.diff_part
+void chain_absdiff(const ForensicChain& C, const uint8_t* prev, hipStream_t s) {
+    if (C.G.general) launch_absdiff_sized(C.buf.gray, prev, C.diff_part, C.G.S, s);
+    else launch_absdiff(C.buf.gray, prev, C.diff_part, s);
+}
+
+// the chain (general, S) with work memory for `frames` frames; creates the handle's forensic state and the chain's table
+// on first use
+int chain_reserve(dfd_handle* h, bool general, int S, int frames, ForensicChain** out) {
+    if (!h->forensic) h->forensic = new ForensicState();
+    ForensicChain& C = h->forensic->chains[{general, S}];
+    if (!C.table) {
+        C.G.S = S;
+        C.G.npix = (double)S * (double)S;
+        C.G.nblk = sized_blocks(S);
+        C.G.npart = S;
+        C.G.f32_means = C.G.general = general;
+        std::vector<float2> tw(S);
+        forensic_sized_table(S, tw.data());
+        const size_t bytes = chain_table_entries(C.G) * sizeof(float2);
+        void *t = nullptr, *d = nullptr;
+        DFD_HIP_TRY(h, hipMalloc(&t, bytes));
+        h->owned.push_back(t);
+        DFD_HIP_TRY(h, hipMemcpy(t, tw.data(), bytes, hipMemcpyHostToDevice));
+        DFD_HIP_TRY(h, hipMalloc(&d, (size_t)C.G.npart * 8));
         h->owned.push_back(d);
-        DFD_HIP_TRY(h, hipMemcpy(d, tw, sizeof tw, hipMemcpyHostToDevice));
-        h->forensic->twiddle = static_cast<float2*>(d);
-        DFD_HIP_TRY(h, hipMalloc(&d, 256 * 8));
-        h->owned.push_back(d);
-        h->forensic->diff_part = static_cast<double*>(d);
+        C.diff_part = static_cast<double*>(d);
+        C.table = static_cast<float2*>(t);
     }
-    ForensicState& F = *h->forensic;
-    if (frames > F.cap) {
-        const int rc = ensure(h, &F.work, forensic_bytes_per_frame() * frames + 65536);
+    if (frames > C.cap) {
+        const int rc = ensure(h, &C.work, chain_bytes_per_frame(C.G) * frames + 65536);
         if (rc) return rc;
-        forensic_carve(F.work.p, frames, &F.buf);
-        F.cap = frames;
+        chain_carve(C.G, C.work.p, frames, &C.buf);
+        C.cap = frames;
     }
+    *out = &C;
     return DFD_OK;
 }
 
-double pop_std(const double* v, int n, double* mean_out) {
-    double m = 0;
-    for (int i = 0; i < n; ++i) m += v[i];
-    m /= n;
-    double q = 0;
-    for (int i = 0; i < n; ++i) q += (v[i] - m) * (v[i] - m);
-    *mean_out = m;
-    return std::sqrt(q / n);
-}
-
-double clip01(double v) { return v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v); }
-
-// the five stateless signals from the device statistics (frame_analysis.py:150-347); sc[5] (temporal) = 0
-// npix: pixels of the analysis image; nblk: its 32x32 blocks (fewer than 4: noise and ELA score 0.0, reference :204,:255)
-void static_scores(const double* st, const double* noise, const double* ela, bool full, double* sc, double* ex,
-                   double npix = 65536.0, int nblk = 64, bool f32_means = false) {
-    const double nan = std::nan("");
-    sc[0] = 0; sc[1] = nan; sc[2] = nan; sc[3] = 0; sc[4] = nan; sc[5] = 0;
-    // ---- frequency (:150-180)
-    const double lo = st[ST_FREQ_LOW], mi = st[ST_FREQ_MID], hi = st[ST_FREQ_HIGH];
-    const double total = lo + mi + hi + 1e-10, hr = hi / total, mr = mi / total;
-    const double mid_cv = st[ST_FREQ_MID_STD] / (mi + 1e-10);
-    double s = 0.0;
-    if (hr < 0.18) s += 0.4; else if (hr < 0.22) s += 0.2;
-    if (mid_cv > 0.6) s += 0.25; else if (mid_cv > 0.45) s += 0.1;
-    if (mr > 0.45 && hr < 0.2) s += 0.15;
-    sc[0] = clip01(s);
-    // ---- edges (:296-309)
-    const double density = st[ST_EDGE_COUNT] / npix, lap_var = st[ST_LAP_VAR];
-    s = 0.0;
-    if (density < 0.02) s += 0.35; else if (density < 0.04) s += 0.15;
-    if (lap_var < 50) s += 0.3; else if (lap_var < 100) s += 0.1;
-    sc[3] = clip01(s);
-    double noise_mean = nan, noise_cv = nan, ela_mean = nan, ela_cv = nan;
-    if (full && nblk < 4) sc[1] = sc[2] = 0.0;
-    if (full && nblk >= 4) {
-        // ---- noise (:207-225)
-        noise_cv = pop_std(noise, nblk, &noise_mean) / (noise_mean + 1e-10);
-        s = 0.0;
-        if (noise_cv > 0.7) s += 0.5; else if (noise_cv > 0.5) s += 0.25;
-        if (noise_mean < 1.0) s += 0.3; else if (noise_mean < 2.0) s += 0.1;
-        sc[1] = clip01(s);
-        // ---- ELA (:258-276)
-        ela_cv = pop_std(ela, nblk, &ela_mean);
-        // the reference's block means are float32 and so is their mean (:250-256); at 256x256 the quotient by 64 is exact
-        if (f32_means) ela_mean = (double)(float)ela_mean;
-        ela_cv = ela_cv / (ela_mean + 1e-10);
-        s = 0.0;
-        if (ela_cv > 0.9) s += 0.5; else if (ela_cv > 0.6) s += 0.2;
-        if (ela_mean > 15) s += 0.2; else if (ela_mean > 10) s += 0.1;
-        sc[2] = clip01(s);
-    }
-    if (full) {
-        // ---- colour (:326-347)
-        s = 0.0;
-        if (st[ST_SAT_STD] < 15) s += 0.3; else if (st[ST_SAT_STD] < 25) s += 0.1;
-        if (st[ST_VAL_STD] < 15) s += 0.25; else if (st[ST_VAL_STD] < 25) s += 0.1;
-        if (st[ST_HUES] < 30) s += 0.25; else if (st[ST_HUES] < 50) s += 0.1;
-        sc[4] = clip01(s);
-    }
-    const double e[10] = {lo, mi, hi, hr, mr, mid_cv, noise_mean, noise_cv, ela_mean, ela_cv};
-    for (int i = 0; i < 10; ++i) ex[i] = e[i];
-}
-
-// the host half of one frame of a stream, in the stream's frame order: frame counter, temporal deque and signal
-// (frame_analysis.py:358-389; dpart = the frame's 256 partial sums against its predecessor, read only when the stream
-// has one), then the weighted sum in the reference's dict order (:49-56,88 / :118-119).  sc[6] / ex[10] as static_scores;
-// *mean_diff / *temporal_cv: -1 / NaN when not computed.
-double score_frame(ForensicStream& S, const double* st, const double* noise, const double* ela, bool full, const double* dpart,
-                   double* sc, double* ex, double* mean_diff, double* temporal_cv, int npart = 256, double npix = 65536.0,
-                   int nblk = 64, bool f32_means = false) {
-    S.frame_count += 1;                                              // frame_analysis.py:68,110
-    static_scores(st, noise, ela, full, sc, ex, npix, nblk, f32_means);
-    *mean_diff = -1.0;
-    *temporal_cv = std::nan("");
-    if (!S.has_prev) {
-        S.has_prev = true;
-    } else {
-        double sum = 0;
-        for (int i = 0; i < npart; ++i) sum += dpart[i];
-        // np.mean of a float32 plane (:364): the integer sum (exact in float32 below 2^24) divided in float32
-        const double md = f32_means ? (double)((float)sum / (float)npix) : sum / npix;
-        *mean_diff = md;
-        S.diffs.push_back(md);
-        if (S.diffs.size() > 30) S.diffs.pop_front();
-        if (S.diffs.size() >= 5) {
-            std::vector<double> d(S.diffs.begin(), S.diffs.end());
-            double dm;
-            const double tcv = pop_std(d.data(), (int)d.size(), &dm) / (dm + 1e-10);
-            *temporal_cv = tcv;
-            double s = 0.0;
-            if (tcv > 1.5) s += 0.4; else if (tcv > 1.0) s += 0.2;
-            if (md < 0.3 && S.frame_count > 10) s += 0.3;
-            else if (md < 0.8 && S.frame_count > 10) s += 0.1;
-            sc[5] = clip01(s);
-        }
-    }
-    double comb = 0.0;
-    if (full) {
-        const double w[6] = {0.25, 0.20, 0.20, 0.15, 0.10, 0.10};
-        for (int i = 0; i < 6; ++i) comb += sc[i] * w[i];
-    } else {
-        comb += sc[0] * 0.45;
-        comb += sc[5] * 0.25;
-        comb += sc[3] * 0.30;
-    }
-    return clip01(comb);
-}
-
 // the stream's stored gray plane: a released stream's plane when there is one (no hipMalloc on the serving path)
-int stream_plane(dfd_handle* h, ForensicStream& S, int size = 256) {
+int stream_plane(dfd_handle* h, ForensicStream& S, int size) {
     if (S.prev_gray) return DFD_OK;
     ForensicState& F = *h->forensic;
     std::vector<void*>& fl = F.free_planes[size];
@@ -226,28 +148,120 @@ int stream_size_check(dfd_handle* h, int stream_id, int size) {
 // another size than 256, on the 256x256 kernels otherwise (a stream nobody opened, or one that has no frame yet)
 bool on_general_chain(const ForensicStream& S) { return S.general || (S.size && S.size != 256); }
 
-int sized_init(dfd_handle* h, int S, int frames, ForensicState::Sized** out) {
-    ForensicState& F = *h->forensic;
-    ForensicState::Sized& Z = F.sized[S];
-    if (!Z.table) {
-        std::vector<float2> tw(S);
-        forensic_sized_table(S, tw.data());
-        void* d = nullptr;
-        DFD_HIP_TRY(h, hipMalloc(&d, (size_t)S * sizeof(float2)));
-        h->owned.push_back(d);
-        DFD_HIP_TRY(h, hipMemcpy(d, tw.data(), (size_t)S * sizeof(float2), hipMemcpyHostToDevice));
-        Z.table = static_cast<float2*>(d);
-        DFD_HIP_TRY(h, hipMalloc(&d, (size_t)S * 8));
-        h->owned.push_back(d);
-        Z.diff_part = static_cast<double*>(d);
+// the analyzer on a frame that is already in HBM, on the chain (general, size): shared by dfd_forensics,
+// dfd_forensics_sized and the fused single-frame entries
+int forensics_chain_run(dfd_handle* h, int stream_id, bool general, int size, const uint8_t* frame_dev, int hh, int ww, int stride,
+                        int full, double* scores_out, double* prob_out, double* stats_out) {
+    if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
+    int rc = stream_size_check(h, stream_id, size);
+    if (rc) return rc;
+    ForensicChain* C = nullptr;
+    if ((rc = chain_reserve(h, general, size, 1, &C))) return rc;
+    const ForensicGeometry& G = C->G;
+    const ForensicBuffers& B = C->buf;
+    ForensicStream& S = h->forensic->streams[stream_id];
+    if ((rc = stream_plane(h, S, size))) return rc;
+
+    launch_resize_bgr(frame_dev, 1, hh, ww, stride, 0, B.rs, size, size, h->stream);
+    DFD_HIP_TRY(h, chain_launch(*C, B, 1, full != 0, h->color, h->stream));
+    if (S.has_prev) chain_absdiff(*C, (const uint8_t*)S.prev_gray, h->stream);
+    double st[FORENSIC_STATS];
+    std::vector<double> blk((size_t)2 * G.nblk + G.npart);
+    double *noise = blk.data(), *ela = noise + G.nblk, *dpart = ela + G.nblk;
+    DFD_HIP_TRY(h, hipMemcpyAsync(st, B.stats, sizeof st, hipMemcpyDeviceToHost, h->stream));
+    if (full) {
+        DFD_HIP_TRY(h, hipMemcpyAsync(noise, B.stats_noise, (size_t)G.nblk * 8, hipMemcpyDeviceToHost, h->stream));
+        DFD_HIP_TRY(h, hipMemcpyAsync(ela, B.stats_ela, (size_t)G.nblk * 8, hipMemcpyDeviceToHost, h->stream));
     }
-    if (frames > Z.cap) {
-        const int rc = ensure(h, &Z.work, forensic_sized_bytes_per_frame(S) * frames + 65536);
-        if (rc) return rc;
-        forensic_sized_carve(Z.work.p, S, frames, &Z.buf);
-        Z.cap = frames;
+    if (S.has_prev) DFD_HIP_TRY(h, hipMemcpyAsync(dpart, C->diff_part, (size_t)G.npart * 8, hipMemcpyDeviceToHost, h->stream));
+    DFD_HIP_TRY(h, hipMemcpyAsync(S.prev_gray, B.gray, (size_t)size * size, hipMemcpyDeviceToDevice, h->stream));
+    DFD_HIP_TRY(h, stream_sync(h));
+    DFD_HIP_TRY(h, hipGetLastError());
+
+    const double nan = std::nan("");
+    double sc[6], ex[10], mean_diff, temporal_cv;
+    *prob_out = score_frame(S, G, st, noise, ela, full != 0, dpart, sc, ex, &mean_diff, &temporal_cv);
+    for (int i = 0; i < 6; ++i) scores_out[i] = sc[i];
+    if (stats_out) {
+        const double out[DFD_FORENSIC_NSTATS] = {ex[0], ex[1], ex[2], ex[3], ex[4], ex[5], ex[6], ex[7], ex[8], ex[9],
+                                                 st[ST_EDGE_COUNT] / G.npix, st[ST_LAP_VAR], full ? st[ST_SAT_STD] : nan,
+                                                 full ? st[ST_VAL_STD] : nan, full ? st[ST_HUES] : nan, mean_diff, temporal_cv,
+                                                 (double)S.frame_count};
+        for (int i = 0; i < DFD_FORENSIC_NSTATS; ++i) stats_out[i] = out[i];
     }
-    *out = &Z;
+    return DFD_OK;
+}
+
+// the test taps (dfd_forensic_tap, dfd_forensic_tap_sized) after their own argument checks; who: the entry's message prefix
+int forensic_tap_run(dfd_handle* h, const char* who, bool general, int size, const uint8_t* frames, int n, int full, const char* start,
+                     const void* start_data, const char* name, int frame, void* out, size_t capacity, size_t* bytes) {
+    static const char* const starts[4] = {"rs", "gray", "grad", "map"};
+    int st = -1;
+    for (int i = 0; i < 4; ++i)
+        if (!std::strcmp(start, starts[i])) st = i;
+    if (st < 0) return fail(h, DFD_ERR_ARG, "%s: start '%s' is none of rs, gray, grad, map", who, start);
+    if (st == FROM_RS ? !frames : !start_data) return fail(h, DFD_ERR_ARG, "%s: no data for start '%s'", who, start);
+    if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    ForensicChain* C = nullptr;
+    int rc = chain_reserve(h, general, size, n, &C);
+    if (rc) return rc;
+    const size_t PIX = (size_t)size * size, NB = (size_t)C->G.nblk, SS = (size_t)size;
+    if ((rc = ensure(h, &C->tap_store, (size_t)n * PIX * (sizeof(float2) + sizeof(float) + 1)))) return rc;
+    ForensicTaps T;
+    T.spectrum = static_cast<float2*>(C->tap_store.p);
+    T.logmag = reinterpret_cast<float*>(T.spectrum + (size_t)n * PIX);
+    T.edges = reinterpret_cast<uint8_t*>(T.logmag + (size_t)n * PIX);
+    const ForensicBuffers& B = C->buf;
+    // which buffer, bytes per frame, the last start that still computes it, and whether only full mode does
+    struct Tap { const char* name; const void* p; size_t per; int last_start; bool full_only; };
+    const bool stats_full = full && st == FROM_RS;
+    const Tap taps[] = {
+        {"rs", B.rs, PIX * 3, FROM_RS, false}, {"gray", B.gray, PIX, FROM_GRAY, false},
+        {"fft_tmp", B.fft_tmp, PIX * sizeof(float2), FROM_GRAY, false}, {"spectrum", T.spectrum, PIX * sizeof(float2), FROM_GRAY, false},
+        {"logmag", T.logmag, PIX * sizeof(float), FROM_GRAY, false}, {"fft_part", B.fft_part, SS * 7 * 8, FROM_GRAY, false},
+        {"grad", B.grad, PIX * sizeof(short2), FROM_GRAD, false}, {"lap_part", B.lap_part, SS * 2 * 8, FROM_GRAY, false},
+        {"map", B.map, PIX, FROM_MAP, false}, {"edges", T.edges, PIX, FROM_MAP, false}, {"edge_count", B.edge_count, 8, FROM_MAP, false},
+        {"jy", B.jy, PIX, FROM_RS, true}, {"jcb", B.jcb, PIX / 4, FROM_RS, true}, {"jcr", B.jcr, PIX / 4, FROM_RS, true},
+        {"stats_ela", B.stats_ela, NB * 8, FROM_RS, true}, {"stats_noise", B.stats_noise, NB * 8, FROM_GRAY, true},
+        {"hsv_part", B.hsv_part, SS * 4 * 8, FROM_RS, true}, {"hue_bits", B.hue_bits, 6 * 4, FROM_RS, true},
+        {"stats", B.stats, (size_t)(stats_full ? FORENSIC_STATS : ST_SAT_STD) * 8, FROM_GRAY, false},
+    };
+    const char* src = nullptr;
+    size_t per = 0, stride = 0;
+    if (!std::strcmp(name, "twiddle")) {                        // the table every spectrum launch reads; not per frame
+        src = reinterpret_cast<const char*>(C->table);
+        per = chain_table_entries(C->G) * sizeof(float2);
+        frame = 0;
+    }
+    for (const Tap& t : taps)
+        if (!src && !std::strcmp(name, t.name)) {
+            if (st > t.last_start || (t.full_only && !full))
+                return fail(h, DFD_ERR_ARG, "%s: '%s' is not computed from start '%s' with full = %d", who, name, start, full);
+            src = static_cast<const char*>(t.p);
+            per = t.per;
+            stride = !std::strcmp(name, "stats") ? FORENSIC_STATS * 8 : t.per;
+        }
+    if (!src) return fail(h, DFD_ERR_ARG, "%s: no buffer named '%s'", who, name);
+    const size_t nout = frame < 0 ? (size_t)n : 1, total = nout * per;
+    *bytes = total;
+    if (total > capacity) return fail(h, DFD_ERR_ARG, "%s '%s' needs %zu bytes, capacity %zu", who, name, total, capacity);
+    if (st == FROM_RS) {
+        DFD_HIP_TRY(h, hipMemcpyAsync(B.rs, frames, (size_t)n * PIX * 3, hipMemcpyHostToDevice, h->stream));
+    } else {
+        void* dst = st == FROM_GRAY ? (void*)B.gray : st == FROM_GRAD ? (void*)B.grad : (void*)B.map;
+        DFD_HIP_TRY(h, hipMemcpyAsync(dst, start_data, (size_t)n * PIX * (st == FROM_GRAD ? sizeof(short2) : 1), hipMemcpyHostToDevice, h->stream));
+    }
+    DFD_HIP_TRY(h, chain_launch(*C, B, n, full != 0, h->color, h->stream, 0, (ForensicStart)st, &T));
+    DFD_HIP_TRY(h, hipGetLastError());
+    const size_t first = frame < 0 ? 0 : (size_t)frame;
+    if (stride == per || nout == 1) {
+        DFD_HIP_TRY(h, hipMemcpyAsync(out, src + first * stride, total, hipMemcpyDeviceToHost, h->stream));
+    } else {
+        for (size_t f = 0; f < nout; ++f)
+            DFD_HIP_TRY(h, hipMemcpyAsync((char*)out + f * per, src + f * stride, per, hipMemcpyDeviceToHost, h->stream));
+    }
+    DFD_HIP_TRY(h, stream_sync(h));
     return DFD_OK;
 }
 
@@ -255,45 +269,19 @@ int sized_init(dfd_handle* h, int S, int frames, ForensicState::Sized** out) {
 
 namespace dfd {
 
-// the analyzer on a frame that is already in HBM (shared by dfd_forensics and dfd_analyze_frame)
-int forensics_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh, int ww, int stride, int full,
-                  double* scores_out, double* prob_out, double* stats_out) {
-    if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
-    int rc = stream_size_check(h, stream_id, 256);
-    if (rc) return rc;
-    if ((rc = state_init(h, 1))) return rc;
-    ForensicState& F = *h->forensic;
-    ForensicStream& S = F.streams[stream_id];
-    if ((rc = stream_plane(h, S))) return rc;
-
-    launch_resize_bgr(frame_dev, 1, hh, ww, stride, 0, F.buf.rs, 256, 256, h->stream);
-    launch_forensics(F.buf, 1, full != 0, h->color, F.twiddle, h->stream);
-    if (S.has_prev) launch_absdiff(F.buf.gray, (const uint8_t*)S.prev_gray, F.diff_part, h->stream);
-    double st[FORENSIC_STATS], noise[64], ela[64], dpart[256];
-    DFD_HIP_TRY(h, hipMemcpyAsync(st, F.buf.stats, sizeof st, hipMemcpyDeviceToHost, h->stream));
-    if (full) {
-        DFD_HIP_TRY(h, hipMemcpyAsync(noise, F.buf.stats_noise, sizeof noise, hipMemcpyDeviceToHost, h->stream));
-        DFD_HIP_TRY(h, hipMemcpyAsync(ela, F.buf.stats_ela, sizeof ela, hipMemcpyDeviceToHost, h->stream));
+// the fused single-frame entries: the stream at the size and on the chain it holds
+int forensics_stream_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh, int ww, int stride, int full,
+                         double* scores_out, double* prob_out) {
+    bool general = false;
+    int size = FIXED_EDGE;
+    if (h->forensic) {
+        auto it = h->forensic->streams.find(stream_id);
+        if (it != h->forensic->streams.end() && on_general_chain(it->second)) {
+            general = true;
+            size = it->second.size;
+        }
     }
-    if (S.has_prev) DFD_HIP_TRY(h, hipMemcpyAsync(dpart, F.diff_part, sizeof dpart, hipMemcpyDeviceToHost, h->stream));
-    DFD_HIP_TRY(h, hipMemcpyAsync(S.prev_gray, F.buf.gray, 65536, hipMemcpyDeviceToDevice, h->stream));
-    DFD_HIP_TRY(h, stream_sync(h));
-    DFD_HIP_TRY(h, hipGetLastError());
-
-    const double nan = std::nan("");
-    double sc[6], ex[10], mean_diff, temporal_cv;
-    *prob_out = score_frame(S, st, noise, ela, full != 0, dpart, sc, ex, &mean_diff, &temporal_cv);
-    const double lo = ex[0], mi = ex[1], hi = ex[2], hr = ex[3], mr = ex[4], mid_cv = ex[5];
-    const double noise_mean = ex[6], noise_cv = ex[7], ela_mean = ex[8], ela_cv = ex[9];
-    const double density = st[ST_EDGE_COUNT] / 65536.0, lap_var = st[ST_LAP_VAR];
-    for (int i = 0; i < 6; ++i) scores_out[i] = sc[i];
-    if (stats_out) {
-        const double out[DFD_FORENSIC_NSTATS] = {lo, mi, hi, hr, mr, mid_cv, noise_mean, noise_cv, ela_mean, ela_cv,
-                                                 density, lap_var, full ? st[ST_SAT_STD] : nan, full ? st[ST_VAL_STD] : nan,
-                                                 full ? st[ST_HUES] : nan, mean_diff, temporal_cv, (double)S.frame_count};
-        for (int i = 0; i < DFD_FORENSIC_NSTATS; ++i) stats_out[i] = out[i];
-    }
-    return DFD_OK;
+    return forensics_chain_run(h, stream_id, general, size, frame_dev, hh, ww, stride, full, scores_out, prob_out, nullptr);
 }
 
 // n frames of any streams and sizes in one pass (POST /analyze_batch, the session pool).  The frames are grouped by the
@@ -310,7 +298,7 @@ int forensics_streams_run(dfd_handle* h, const uint8_t* frames_dev, const FrameD
                           const int* full, double* scores_out, double* prob_out) {
     if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
     int rc = DFD_OK;
-    if ((rc = state_init(h, 1))) return rc;
+    if (!h->forensic) h->forensic = new ForensicState();
     ForensicState& F = *h->forensic;
     std::vector<int> plain;                                          // frames on the 256x256 kernels, in call order
     std::map<int, std::vector<int>> groups;                          // analysis edge -> frames on the general chain
@@ -320,7 +308,7 @@ int forensics_streams_run(dfd_handle* h, const uint8_t* frames_dev, const FrameD
     for (int f = 0; f < n; ++f) {
         ForensicStream& S = F.streams[stream_ids[f]];
         edge[f] = on_general_chain(S) ? S.size : 0;
-        if ((rc = stream_plane(h, S, edge[f] ? edge[f] : 256))) return rc;
+        if ((rc = stream_plane(h, S, edge[f] ? edge[f] : FIXED_EDGE))) return rc;
         if (!edge[f]) { plain.push_back(f); continue; }
         groups[edge[f]].push_back(f);
         gray_bytes += (size_t)edge[f] * edge[f];
@@ -329,19 +317,25 @@ int forensics_streams_run(dfd_handle* h, const uint8_t* frames_dev, const FrameD
         ++n_sized;
     }
     const int n_plain = (int)plain.size();
-    if (n_plain && (rc = state_init(h, n_plain))) return rc;
+    ForensicChain* P = nullptr;                                      // the 256x256 group's chain: all of its frames at once
+    if (n_plain && (rc = chain_reserve(h, false, FIXED_EDGE, n_plain, &P))) return rc;
+    const size_t plain_parts = n_plain ? (size_t)n_plain * P->G.npart : 0;
+    std::vector<const ForensicChain*> chain(n, P);                   // every frame's chain
     if ((rc = ensure(h, &F.sized_gray, gray_bytes))) return rc;
     if ((rc = ensure(h, &F.sized_part, part_doubles * 8))) return rc;
-    struct Chunk { int S, first, count; ForensicState::Sized* Z; bool full; };   // first: index into the group's frames
+    struct Chunk { int S, first, count; ForensicChain* Z; bool full; };   // first: index into the group's frames
     std::vector<Chunk> chunks;
     for (const auto& g : groups) {
         const int S = g.first, cnt = (int)g.second.size();
         const size_t fit = h->forensic_chunk_bytes / forensic_sized_bytes_per_frame(S);
         const int per = (int)std::min<size_t>(std::max<size_t>(fit, 1), (size_t)cnt);
-        ForensicState::Sized* Z = nullptr;
-        if ((rc = sized_init(h, S, per, &Z))) return rc;
+        ForensicChain* Z = nullptr;
+        if ((rc = chain_reserve(h, true, S, per, &Z))) return rc;
         bool any = false;
-        for (int f : g.second) any = any || full[f] != 0;
+        for (int f : g.second) {
+            any = any || full[f] != 0;
+            chain[f] = Z;
+        }
         for (int c0 = 0; c0 < cnt; c0 += per) chunks.push_back(Chunk{S, c0, std::min(per, cnt - c0), Z, any});
     }
     // where every frame's gray plane and partial sums are, and its slot in the descriptor table (group by group)
@@ -350,7 +344,8 @@ int forensics_streams_run(dfd_handle* h, const uint8_t* frames_dev, const FrameD
     std::vector<FrameDesc> desc;
     desc.reserve(n);
     for (int j = 0; j < n_plain; ++j) {
-        gray[plain[j]] = F.buf.gray + (size_t)j * 65536;
+        gray[plain[j]] = P->buf.gray + (size_t)j * P->G.S * P->G.S;
+        part_at[plain[j]] = (size_t)j * P->G.npart;
         desc.push_back(fd[plain[j]]);
     }
     {
@@ -390,74 +385,70 @@ int forensics_streams_run(dfd_handle* h, const uint8_t* frames_dev, const FrameD
     if ((rc = ensure(h, &F.frame_desc, (size_t)n * sizeof(FrameDesc)))) return rc;
     if ((rc = ensure(h, &F.prev_tab, (size_t)n_plain * sizeof(void*)))) return rc;
     if ((rc = ensure(h, &F.copy_tab, back.size() * sizeof(PlaneCopy)))) return rc;
-    if ((rc = ensure(h, &F.pair_part, (size_t)n_plain * 256 * 8))) return rc;
+    if ((rc = ensure(h, &F.pair_part, plain_parts * 8))) return rc;
     if ((rc = ensure(h, &F.sized_diff_tab, rows.size() * sizeof(SizedDiffRow)))) return rc;
     if ((rc = ensure(h, &F.sized_copy_tab, back_sized.size() * sizeof(SizedPlaneCopy)))) return rc;
     if ((rc = mailbox_h2d(h, F.frame_desc.p, desc.data(), (size_t)n * sizeof(FrameDesc)))) return rc;
     const FrameDesc* desc_dev = (const FrameDesc*)F.frame_desc.p;
-    // per frame: where the host finds its statistics once the stream has been waited for
+    // per frame: where the host finds its statistics once the stream has been waited for.  One launch set's statistics
+    // (count frames from `frames`, in the order of its buffers B) through the mailbox; blocks: the block arrays too.
     std::vector<const double*> st(n, nullptr), noise(n, nullptr), ela(n, nullptr), part(n, nullptr);
+    auto fetch_stats = [&](const ForensicBuffers& B, const ForensicGeometry& G, const int* frames, int count, bool blocks) {
+        const double* a = (const double*)mailbox_d2h(h, B.stats, (size_t)count * FORENSIC_STATS * 8);
+        const double* b = blocks ? (const double*)mailbox_d2h(h, B.stats_noise, (size_t)count * G.nblk * 8) : nullptr;
+        const double* e = blocks ? (const double*)mailbox_d2h(h, B.stats_ela, (size_t)count * G.nblk * 8) : nullptr;
+        if (!a || (blocks && (!b || !e))) return false;
+        for (int j = 0; j < count; ++j) {
+            const int f = frames[j];
+            st[f] = a + (size_t)j * FORENSIC_STATS;
+            if (blocks) {
+                noise[f] = b + (size_t)j * G.nblk;
+                ela[f] = e + (size_t)j * G.nblk;
+            }
+        }
+        return true;
+    };
+    // the partial sums of every frame of one kind (on the general chain or not), `doubles` of them at src
+    auto fetch_parts = [&](const void* src, size_t doubles, bool general) {
+        const double* d = (const double*)mailbox_d2h(h, src, doubles * 8);
+        if (!d) return false;
+        for (int f = 0; f < n; ++f)
+            if ((edge[f] != 0) == general) part[f] = d + part_at[f];
+        return true;
+    };
     if (n_plain) {
         if ((rc = mailbox_h2d(h, F.prev_tab.p, prev.data(), (size_t)n_plain * sizeof(void*)))) return rc;
         if ((rc = mailbox_h2d(h, F.copy_tab.p, back.data(), back.size() * sizeof(PlaneCopy)))) return rc;
-        launch_resize_bgr_ragged(frames_dev, desc_dev, n_plain, F.buf.rs, 256, 256, h->stream);
-        launch_forensics(F.buf, n_plain, any_full, h->color, F.twiddle, h->stream);
-        launch_absdiff_prev(F.buf.gray, (const uint8_t* const*)F.prev_tab.p, (double*)F.pair_part.p, n_plain, h->stream);
+        launch_resize_bgr_ragged(frames_dev, desc_dev, n_plain, P->buf.rs, P->G.S, P->G.S, h->stream);
+        DFD_HIP_TRY(h, chain_launch(*P, P->buf, n_plain, any_full, h->color, h->stream));
+        launch_absdiff_prev(P->buf.gray, (const uint8_t* const*)F.prev_tab.p, (double*)F.pair_part.p, n_plain, h->stream);
         launch_copy_planes((const PlaneCopy*)F.copy_tab.p, (int)back.size(), h->stream);
-        const double* a = (const double*)mailbox_d2h(h, F.buf.stats, (size_t)n_plain * FORENSIC_STATS * 8);
-        const double* b = (const double*)mailbox_d2h(h, F.buf.stats_noise, (size_t)n_plain * 64 * 8);
-        const double* c = (const double*)mailbox_d2h(h, F.buf.stats_ela, (size_t)n_plain * 64 * 8);
-        const double* d = (const double*)mailbox_d2h(h, F.pair_part.p, (size_t)n_plain * 256 * 8);
-        if (!a || !b || !c || !d) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
-        for (int j = 0; j < n_plain; ++j) {
-            const int f = plain[j];
-            st[f] = a + (size_t)j * FORENSIC_STATS;
-            noise[f] = b + (size_t)j * 64;
-            ela[f] = c + (size_t)j * 64;
-            part[f] = d + (size_t)j * 256;
-        }
+        if (!fetch_stats(P->buf, P->G, plain.data(), n_plain, true) ||
+            !fetch_parts(F.pair_part.p, plain_parts, false))
+            return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
     }
     if (n_sized) {
         if ((rc = mailbox_h2d(h, F.sized_diff_tab.p, rows.data(), rows.size() * sizeof(SizedDiffRow)))) return rc;
         if ((rc = mailbox_h2d(h, F.sized_copy_tab.p, back_sized.data(), back_sized.size() * sizeof(SizedPlaneCopy)))) return rc;
         int at = n_plain;                                            // the chunk's first slot of the descriptor table
         for (const Chunk& c : chunks) {
-            const std::vector<int>& frames = groups[c.S];
-            const size_t nblk = (size_t)sized_blocks(c.S);
+            const int* frames = groups[c.S].data() + c.first;
             ForensicBuffers B = c.Z->buf;                            // the chunk's work memory, its gray planes in the call's store
-            B.gray = const_cast<uint8_t*>(gray[frames[c.first]]);
+            B.gray = const_cast<uint8_t*>(gray[frames[0]]);
             launch_resize_bgr_ragged(frames_dev, desc_dev + at, c.count, B.rs, c.S, c.S, h->stream);
-            DFD_HIP_TRY(h, launch_forensics_sized(B, c.S, c.count, c.full, h->color, c.Z->table, h->stream));
-            const double* a = (const double*)mailbox_d2h(h, B.stats, (size_t)c.count * FORENSIC_STATS * 8);
-            const double* b = c.full ? (const double*)mailbox_d2h(h, B.stats_noise, (size_t)c.count * nblk * 8) : nullptr;
-            const double* e = c.full ? (const double*)mailbox_d2h(h, B.stats_ela, (size_t)c.count * nblk * 8) : nullptr;
-            if (!a || (c.full && (!b || !e))) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
-            for (int j = 0; j < c.count; ++j) {
-                const int f = frames[c.first + j];
-                st[f] = a + (size_t)j * FORENSIC_STATS;
-                if (c.full) {
-                    noise[f] = b + (size_t)j * nblk;
-                    ela[f] = e + (size_t)j * nblk;
-                }
-            }
+            DFD_HIP_TRY(h, chain_launch(*c.Z, B, c.count, c.full, h->color, h->stream));
+            if (!fetch_stats(B, c.Z->G, frames, c.count, c.full)) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
             at += c.count;
         }
         launch_absdiff_prev_sized((const SizedDiffRow*)F.sized_diff_tab.p, n_sized, max_S, h->stream);
         launch_copy_planes_sized((const SizedPlaneCopy*)F.sized_copy_tab.p, (int)back_sized.size(), max_S, h->stream);
-        const double* d = (const double*)mailbox_d2h(h, F.sized_part.p, part_doubles * 8);
-        if (!d) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
-        for (int f = 0; f < n; ++f)
-            if (edge[f]) part[f] = d + part_at[f];
+        if (!fetch_parts(F.sized_part.p, part_doubles, true)) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
     }
     DFD_HIP_TRY(h, stream_sync(h));
     DFD_HIP_TRY(h, hipGetLastError());
     for (int f = 0; f < n; ++f) {
         double sc[6], ex[10], md, tcv;
-        ForensicStream& S = F.streams[stream_ids[f]];
-        const int e = edge[f];
-        prob_out[f] = e ? score_frame(S, st[f], noise[f], ela[f], full[f] != 0, part[f], sc, ex, &md, &tcv, e, (double)e * (double)e,
-                                      sized_blocks(e), true)
-                        : score_frame(S, st[f], noise[f], ela[f], full[f] != 0, part[f], sc, ex, &md, &tcv);
+        prob_out[f] = score_frame(F.streams[stream_ids[f]], chain[f]->G, st[f], noise[f], ela[f], full[f] != 0, part[f], sc, ex, &md, &tcv);
         for (int i = 0; i < 6; ++i) scores_out[(size_t)f * 6 + i] = sc[i];
     }
     return DFD_OK;
@@ -468,36 +459,30 @@ int forensics_streams_run(dfd_handle* h, const uint8_t* frames_dev, const FrameD
 int forensics_batch_run(dfd_handle* h, const uint8_t* frames_dev, int n, int hh, int ww, int stride, size_t frame_bytes,
                         double* prob_out, double* scores_out) {
     if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
-    int rc = state_init(h, n);
+    ForensicChain* C = nullptr;
+    int rc = chain_reserve(h, false, FIXED_EDGE, n, &C);
     if (rc) return rc;
-    ForensicState& F = *h->forensic;
-    launch_resize_bgr(frames_dev, n, hh, ww, stride, frame_bytes, F.buf.rs, 256, 256, h->stream);
-    launch_forensics(F.buf, n, true, h->color, F.twiddle, h->stream);
+    const ForensicGeometry& G = C->G;
+    launch_resize_bgr(frames_dev, n, hh, ww, stride, frame_bytes, C->buf.rs, G.S, G.S, h->stream);
+    DFD_HIP_TRY(h, chain_launch(*C, C->buf, n, true, h->color, h->stream));
     // a few KB per frame, through the mailbox (dfd_common.h) rather than the DMA engines
-    const double* st = (const double*)mailbox_d2h(h, F.buf.stats, (size_t)n * FORENSIC_STATS * 8);
-    const double* noise = (const double*)mailbox_d2h(h, F.buf.stats_noise, (size_t)n * 64 * 8);
-    const double* ela = (const double*)mailbox_d2h(h, F.buf.stats_ela, (size_t)n * 64 * 8);
+    const double* st = (const double*)mailbox_d2h(h, C->buf.stats, (size_t)n * FORENSIC_STATS * 8);
+    const double* noise = (const double*)mailbox_d2h(h, C->buf.stats_noise, (size_t)n * G.nblk * 8);
+    const double* ela = (const double*)mailbox_d2h(h, C->buf.stats_ela, (size_t)n * G.nblk * 8);
     if (!st || !noise || !ela) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
     DFD_HIP_TRY(h, stream_sync(h));
     DFD_HIP_TRY(h, hipGetLastError());
-    const double w[6] = {0.25, 0.20, 0.20, 0.15, 0.10, 0.10};
-    for (int f = 0; f < n; ++f) {
-        double sc[6], ex[10];
-        static_scores(&st[(size_t)f * FORENSIC_STATS], &noise[(size_t)f * 64], &ela[(size_t)f * 64], true, sc, ex);
-        double comb = 0.0;
-        for (int i = 0; i < 6; ++i) comb += sc[i] * w[i];
-        prob_out[f] = clip01(comb);
-        if (scores_out)
-            for (int i = 0; i < 6; ++i) scores_out[(size_t)f * 6 + i] = sc[i];
-    }
+    score_stateless(G, st, noise, ela, n, prob_out, scores_out);
     return DFD_OK;
 }
 
 int forensics_batch_begin(dfd_handle* h, const uint8_t* frames_dev, int n, int hh, int ww, int stride, size_t frame_bytes) {
     if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
-    int rc = state_init(h, n);
+    ForensicChain* C = nullptr;
+    int rc = chain_reserve(h, false, FIXED_EDGE, n, &C);
     if (rc) return rc;
     ForensicState& F = *h->forensic;
+    const ForensicGeometry& G = C->G;
     if (!h->aux_stream) {
         // LOWEST priority: the signals have the whole call to finish; their workgroups should take the CUs the main
         // stream leaves idle (DetectionOutput runs 64 blocks on 256 CUs, the detector's tail layers and the cascade's
@@ -508,7 +493,7 @@ int forensics_batch_begin(dfd_handle* h, const uint8_t* frames_dev, int n, int h
         DFD_HIP_TRY(h, hipEventCreateWithFlags(&h->aux_go, hipEventDisableTiming));
         DFD_HIP_TRY(h, hipEventCreateWithFlags(&h->aux_done, hipEventDisableTiming));
     }
-    const size_t per = FORENSIC_STATS + 128, need = (size_t)n * per * 8;
+    const size_t per = FORENSIC_STATS + 2 * (size_t)G.nblk, need = (size_t)n * per * 8;
     if (need > F.host_res_cap) {
         if (F.host_res) DFD_HIP_TRY(h, hipHostFree(F.host_res));
         F.host_res = nullptr;
@@ -519,32 +504,23 @@ int forensics_batch_begin(dfd_handle* h, const uint8_t* frames_dev, int n, int h
     // the frames are complete where the main stream stands now (an upload it waited for, a decode it ran)
     DFD_HIP_TRY(h, hipEventRecord(h->aux_go, h->stream));
     DFD_HIP_TRY(h, hipStreamWaitEvent(h->aux_stream, h->aux_go, 0));
-    launch_resize_bgr(frames_dev, n, hh, ww, stride, frame_bytes, F.buf.rs, 256, 256, h->aux_stream);
-    launch_forensics(F.buf, n, true, h->color, F.twiddle, h->aux_stream);
-    copy_kernel_async(F.host_res, F.buf.stats, (size_t)n * FORENSIC_STATS * 8, h->aux_stream);
-    copy_kernel_async(F.host_res + (size_t)n * FORENSIC_STATS, F.buf.stats_noise, (size_t)n * 64 * 8, h->aux_stream);
-    copy_kernel_async(F.host_res + (size_t)n * (FORENSIC_STATS + 64), F.buf.stats_ela, (size_t)n * 64 * 8, h->aux_stream);
+    launch_resize_bgr(frames_dev, n, hh, ww, stride, frame_bytes, C->buf.rs, G.S, G.S, h->aux_stream);
+    DFD_HIP_TRY(h, chain_launch(*C, C->buf, n, true, h->color, h->aux_stream));
+    copy_kernel_async(F.host_res, C->buf.stats, (size_t)n * FORENSIC_STATS * 8, h->aux_stream);
+    copy_kernel_async(F.host_res + (size_t)n * FORENSIC_STATS, C->buf.stats_noise, (size_t)n * G.nblk * 8, h->aux_stream);
+    copy_kernel_async(F.host_res + (size_t)n * (FORENSIC_STATS + G.nblk), C->buf.stats_ela, (size_t)n * G.nblk * 8, h->aux_stream);
     DFD_HIP_TRY(h, hipGetLastError());
     DFD_HIP_TRY(h, hipEventRecord(h->aux_done, h->aux_stream));
     return DFD_OK;
 }
 
 int forensics_batch_end(dfd_handle* h, int n, double* prob_out, double* scores_out) {
-    ForensicState& F = *h->forensic;
+    ForensicChain* C = nullptr;                                      // the chain forensics_batch_begin ran on
+    const int rc = chain_reserve(h, false, FIXED_EDGE, n, &C);
+    if (rc) return rc;
+    const double* res = h->forensic->host_res;
     DFD_HIP_TRY(h, hipEventSynchronize(h->aux_done));
-    const double* st = F.host_res;
-    const double* noise = F.host_res + (size_t)n * FORENSIC_STATS;
-    const double* ela = F.host_res + (size_t)n * (FORENSIC_STATS + 64);
-    const double w[6] = {0.25, 0.20, 0.20, 0.15, 0.10, 0.10};
-    for (int f = 0; f < n; ++f) {
-        double sc[6], ex[10];
-        static_scores(&st[(size_t)f * FORENSIC_STATS], &noise[(size_t)f * 64], &ela[(size_t)f * 64], true, sc, ex);
-        double comb = 0.0;
-        for (int i = 0; i < 6; ++i) comb += sc[i] * w[i];
-        prob_out[f] = clip01(comb);
-        if (scores_out)
-            for (int i = 0; i < 6; ++i) scores_out[(size_t)f * 6 + i] = sc[i];
-    }
+    score_stateless(C->G, res, res + (size_t)n * FORENSIC_STATS, res + (size_t)n * (FORENSIC_STATS + C->G.nblk), n, prob_out, scores_out);
     return DFD_OK;
 }
 
@@ -561,7 +537,25 @@ int dfd_forensics(dfd_handle* h, int stream_id, const uint8_t* bgr, int hh, int 
     const int rc = ensure(h, &h->frame_buf, (size_t)hh * stride);
     if (rc) return rc;
     DFD_HIP_TRY(h, hipMemcpyAsync(h->frame_buf.p, bgr, (size_t)hh * stride, hipMemcpyHostToDevice, h->stream));
-    return forensics_run(h, stream_id, (const uint8_t*)h->frame_buf.p, hh, ww, stride, full, scores_out, prob_out, stats_out);
+    return forensics_chain_run(h, stream_id, false, FIXED_EDGE, (const uint8_t*)h->frame_buf.p, hh, ww, stride, full, scores_out,
+                               prob_out, stats_out);
+}
+
+int dfd_forensics_sized(dfd_handle* h, int stream_id, const uint8_t* bgr, int hh, int ww, int stride, int size, int full,
+                        double* scores_out, double* prob_out, double* stats_out) {
+    if (!h) return DFD_ERR_ARG;
+    if (!bgr || !scores_out || !prob_out || hh <= 0 || ww <= 0 || stride < ww * 3)
+        return fail(h, DFD_ERR_ARG, "forensics_sized: bad pointer or geometry");
+    if (!sized_ok(size))
+        return fail(h, DFD_ERR_ARG, "forensics_sized: analysis size %d is not a multiple of 16 in %d..%d", size, SIZED_MIN, SIZED_MAX);
+    if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    int rc = stream_size_check(h, stream_id, size);
+    if (rc) return rc;
+    if ((rc = ensure(h, &h->frame_buf, (size_t)hh * stride))) return rc;
+    DFD_HIP_TRY(h, hipMemcpyAsync(h->frame_buf.p, bgr, (size_t)hh * stride, hipMemcpyHostToDevice, h->stream));
+    return forensics_chain_run(h, stream_id, true, size, (const uint8_t*)h->frame_buf.p, hh, ww, stride, full, scores_out, prob_out,
+                               stats_out);
 }
 
 int dfd_forensic_signals_device(dfd_handle* h, const uint8_t* frames_dev, int n, int hh, int ww, const int32_t* prev_index,
@@ -581,21 +575,23 @@ int dfd_forensic_signals_device(dfd_handle* h, const uint8_t* frames_dev, int n,
     if (ns == 0) return fail(h, DFD_ERR_ARG, "forensic_signals: every frame of the batch is predecessor-only (-2): nothing to compute");
     if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
     DFD_HIP_TRY(h, hipSetDevice(h->device));
-    int rc = state_init(h, n);
+    ForensicChain* C = nullptr;
+    int rc = chain_reserve(h, false, FIXED_EDGE, n, &C);
     if (rc) return rc;
     ForensicState& F = *h->forensic;
+    const ForensicGeometry& G = C->G;
     if ((rc = ensure(h, &F.pair_idx, (size_t)n * 4))) return rc;
-    if ((rc = ensure(h, &F.pair_part, (size_t)n * 256 * 8))) return rc;
+    if ((rc = ensure(h, &F.pair_part, (size_t)n * G.npart * 8))) return rc;
     const int stride = ww * 3;
     if ((rc = mailbox_h2d(h, F.pair_idx.p, prev_index, (size_t)n * 4))) return rc;
-    launch_resize_bgr(frames_dev, n, hh, ww, stride, (size_t)hh * stride, F.buf.rs, 256, 256, h->stream);
-    launch_forensics(F.buf, ns, true, h->color, F.twiddle, h->stream, n - ns);
-    if (ns > 0) launch_absdiff_pairs(F.buf.gray, (const int*)F.pair_idx.p, (double*)F.pair_part.p, ns, h->stream);
+    launch_resize_bgr(frames_dev, n, hh, ww, stride, (size_t)hh * stride, C->buf.rs, G.S, G.S, h->stream);
+    DFD_HIP_TRY(h, chain_launch(*C, C->buf, ns, true, h->color, h->stream, n - ns));
+    if (ns > 0) launch_absdiff_pairs(C->buf.gray, (const int*)F.pair_idx.p, (double*)F.pair_part.p, ns, h->stream);
     const size_t nz = ns > 0 ? ns : 1;
-    const double* st = (const double*)mailbox_d2h(h, F.buf.stats, nz * FORENSIC_STATS * 8);
-    const double* noise = (const double*)mailbox_d2h(h, F.buf.stats_noise, nz * 64 * 8);
-    const double* ela = (const double*)mailbox_d2h(h, F.buf.stats_ela, nz * 64 * 8);
-    const double* part = (const double*)mailbox_d2h(h, F.pair_part.p, nz * 256 * 8);
+    const double* st = (const double*)mailbox_d2h(h, C->buf.stats, nz * FORENSIC_STATS * 8);
+    const double* noise = (const double*)mailbox_d2h(h, C->buf.stats_noise, nz * G.nblk * 8);
+    const double* ela = (const double*)mailbox_d2h(h, C->buf.stats_ela, nz * G.nblk * 8);
+    const double* part = (const double*)mailbox_d2h(h, F.pair_part.p, nz * G.npart * 8);
     if (!st || !noise || !ela || !part) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
     DFD_HIP_TRY(h, stream_sync(h));
     DFD_HIP_TRY(h, hipGetLastError());
@@ -605,15 +601,10 @@ int dfd_forensic_signals_device(dfd_handle* h, const uint8_t* frames_dev, int n,
     }
     for (int f = 0; f < ns; ++f) {
         double sc[6], ex[10];
-        static_scores(&st[(size_t)f * FORENSIC_STATS], &noise[(size_t)f * 64], &ela[(size_t)f * 64], true, sc, ex);
+        static_scores(G, &st[(size_t)f * FORENSIC_STATS], &noise[(size_t)f * G.nblk], &ela[(size_t)f * G.nblk], true, sc, ex);
         for (int i = 0; i < 5; ++i) scores5_out[(size_t)f * 5 + i] = sc[i];
-        if (prev_index[f] < 0) {
-            mean_diff_out[f] = -1.0;
-        } else {
-            double sum = 0;                                      // the summation order of forensics_run
-            for (int i = 0; i < 256; ++i) sum += part[(size_t)f * 256 + i];
-            mean_diff_out[f] = sum / 65536.0;
-        }
+        // the summation order of a stream's frame (score_frame)
+        mean_diff_out[f] = prev_index[f] < 0 ? -1.0 : mean_abs_diff(G, &part[(size_t)f * G.npart]);
     }
     return DFD_OK;
 }
@@ -623,74 +614,17 @@ int dfd_forensic_tap(dfd_handle* h, const uint8_t* bgr256, int n, int full, cons
     if (!h) return DFD_ERR_ARG;
     if (!start || !name || !out || !bytes || n <= 0 || n > 64 || frame < -1 || frame >= n)
         return fail(h, DFD_ERR_ARG, "forensic_tap: bad pointer, frame index or frame count (1..64)");
-    constexpr size_t PIX = 65536;
-    static const char* const starts[4] = {"rs", "gray", "grad", "map"};
-    int st = -1;
-    for (int i = 0; i < 4; ++i)
-        if (!std::strcmp(start, starts[i])) st = i;
-    if (st < 0) return fail(h, DFD_ERR_ARG, "forensic_tap: start '%s' is none of rs, gray, grad, map", start);
-    if (st == FROM_RS ? !bgr256 : !start_data) return fail(h, DFD_ERR_ARG, "forensic_tap: no data for start '%s'", start);
-    if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
-    DFD_HIP_TRY(h, hipSetDevice(h->device));
-    int rc = state_init(h, n);
-    if (rc) return rc;
-    ForensicState& F = *h->forensic;
-    if ((rc = ensure(h, &F.tap_store, (size_t)n * PIX * (sizeof(float2) + sizeof(float) + 1)))) return rc;
-    ForensicTaps T;
-    T.spectrum = static_cast<float2*>(F.tap_store.p);
-    T.logmag = reinterpret_cast<float*>(T.spectrum + (size_t)n * PIX);
-    T.edges = reinterpret_cast<uint8_t*>(T.logmag + (size_t)n * PIX);
-    const ForensicBuffers& B = F.buf;
-    // which buffer, bytes per frame, the last start that still computes it, and whether only full mode does
-    struct Tap { const char* name; const void* p; size_t per; int last_start; bool full_only; };
-    const bool stats_full = full && st == FROM_RS;
-    const Tap taps[] = {
-        {"rs", B.rs, PIX * 3, FROM_RS, false}, {"gray", B.gray, PIX, FROM_GRAY, false},
-        {"fft_tmp", B.fft_tmp, PIX * sizeof(float2), FROM_GRAY, false}, {"spectrum", T.spectrum, PIX * sizeof(float2), FROM_GRAY, false},
-        {"logmag", T.logmag, PIX * sizeof(float), FROM_GRAY, false}, {"fft_part", B.fft_part, 256 * 7 * 8, FROM_GRAY, false},
-        {"grad", B.grad, PIX * sizeof(short2), FROM_GRAD, false}, {"lap_part", B.lap_part, 256 * 2 * 8, FROM_GRAY, false},
-        {"map", B.map, PIX, FROM_MAP, false}, {"edges", T.edges, PIX, FROM_MAP, false}, {"edge_count", B.edge_count, 8, FROM_MAP, false},
-        {"jy", B.jy, PIX, FROM_RS, true}, {"jcb", B.jcb, PIX / 4, FROM_RS, true}, {"jcr", B.jcr, PIX / 4, FROM_RS, true},
-        {"stats_ela", B.stats_ela, 64 * 8, FROM_RS, true}, {"stats_noise", B.stats_noise, 64 * 8, FROM_GRAY, true},
-        {"hsv_part", B.hsv_part, 256 * 4 * 8, FROM_RS, true}, {"hue_bits", B.hue_bits, 6 * 4, FROM_RS, true},
-        {"stats", B.stats, (size_t)(stats_full ? FORENSIC_STATS : ST_SAT_STD) * 8, FROM_GRAY, false},
-    };
-    const char* src = nullptr;
-    size_t per = 0, stride = 0;
-    if (!std::strcmp(name, "twiddle")) {                        // the table every FFT launch reads; not per frame
-        src = reinterpret_cast<const char*>(F.twiddle);
-        per = 128 * sizeof(float2);
-        frame = 0;
-    }
-    for (const Tap& t : taps)
-        if (!src && !std::strcmp(name, t.name)) {
-            if (st > t.last_start || (t.full_only && !full))
-                return fail(h, DFD_ERR_ARG, "forensic_tap: '%s' is not computed from start '%s' with full = %d", name, start, full);
-            src = static_cast<const char*>(t.p);
-            per = t.per;
-            stride = !std::strcmp(name, "stats") ? FORENSIC_STATS * 8 : t.per;
-        }
-    if (!src) return fail(h, DFD_ERR_ARG, "forensic_tap: no buffer named '%s'", name);
-    const size_t nout = frame < 0 ? (size_t)n : 1, total = nout * per;
-    *bytes = total;
-    if (total > capacity) return fail(h, DFD_ERR_ARG, "forensic_tap '%s' needs %zu bytes, capacity %zu", name, total, capacity);
-    if (st == FROM_RS) {
-        DFD_HIP_TRY(h, hipMemcpyAsync(B.rs, bgr256, (size_t)n * PIX * 3, hipMemcpyHostToDevice, h->stream));
-    } else {
-        void* dst = st == FROM_GRAY ? (void*)B.gray : st == FROM_GRAD ? (void*)B.grad : (void*)B.map;
-        DFD_HIP_TRY(h, hipMemcpyAsync(dst, start_data, (size_t)n * PIX * (st == FROM_GRAD ? sizeof(short2) : 1), hipMemcpyHostToDevice, h->stream));
-    }
-    launch_forensics(B, n, full != 0, h->color, F.twiddle, h->stream, 0, (ForensicStart)st, &T);
-    DFD_HIP_TRY(h, hipGetLastError());
-    const size_t first = frame < 0 ? 0 : (size_t)frame;
-    if (stride == per || nout == 1) {
-        DFD_HIP_TRY(h, hipMemcpyAsync(out, src + first * stride, total, hipMemcpyDeviceToHost, h->stream));
-    } else {
-        for (size_t f = 0; f < nout; ++f)
-            DFD_HIP_TRY(h, hipMemcpyAsync((char*)out + f * per, src + f * stride, per, hipMemcpyDeviceToHost, h->stream));
-    }
-    DFD_HIP_TRY(h, stream_sync(h));
-    return DFD_OK;
+    return forensic_tap_run(h, "forensic_tap", false, FIXED_EDGE, bgr256, n, full, start, start_data, name, frame, out, capacity, bytes);
+}
+
+int dfd_forensic_tap_sized(dfd_handle* h, const uint8_t* frames, int n, int size, int full, const char* start, const void* start_data,
+                           const char* name, int frame, void* out, size_t capacity, size_t* bytes) {
+    if (!h) return DFD_ERR_ARG;
+    if (!start || !name || !out || !bytes || n <= 0 || n > 16 || frame < -1 || frame >= n)
+        return fail(h, DFD_ERR_ARG, "forensic_tap_sized: bad pointer, frame index or frame count (1..16)");
+    if (!sized_ok(size))
+        return fail(h, DFD_ERR_ARG, "forensic_tap_sized: analysis size %d is not a multiple of 16 in %d..%d", size, SIZED_MIN, SIZED_MAX);
+    return forensic_tap_run(h, "forensic_tap_sized", true, size, frames, n, full, start, start_data, name, frame, out, capacity, bytes);
 }
 
 int dfd_forensics_reset(dfd_handle* h, int stream_id) {
@@ -732,89 +666,6 @@ int dfd_forensics_state(dfd_handle* h, int stream_id, int* frame_count, int* n_d
     return DFD_OK;
 }
 
-// ---- any square analysis size (forensic_sized_kernels.hip): the same host half, S in place of 256
-}  // extern "C"
-
-namespace dfd {
-
-// the analyzer at analysis edge `size` on a frame that is already in HBM (shared by dfd_forensics_sized and the fused
-// single-frame entries on a stream of the general chain)
-int forensics_sized_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh, int ww, int stride, int size, int full,
-                        double* scores_out, double* prob_out, double* stats_out) {
-    if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
-    int rc = stream_size_check(h, stream_id, size);
-    if (rc) return rc;
-    if ((rc = state_init(h, 1))) return rc;
-    ForensicState& F = *h->forensic;
-    ForensicState::Sized* Z = nullptr;
-    if ((rc = sized_init(h, size, 1, &Z))) return rc;
-    ForensicStream& S = F.streams[stream_id];
-    if ((rc = stream_plane(h, S, size))) return rc;
-    const size_t pix = (size_t)size * size;
-    const int nblk = sized_blocks(size);
-    const ForensicBuffers& B = Z->buf;
-
-    launch_resize_bgr(frame_dev, 1, hh, ww, stride, 0, B.rs, size, size, h->stream);
-    DFD_HIP_TRY(h, launch_forensics_sized(B, size, 1, full != 0, h->color, Z->table, h->stream));
-    if (S.has_prev) launch_absdiff_sized(B.gray, (const uint8_t*)S.prev_gray, Z->diff_part, size, h->stream);
-    double st[FORENSIC_STATS];
-    std::vector<double> blk((size_t)2 * nblk + size);
-    double *noise = blk.data(), *ela = noise + nblk, *dpart = ela + nblk;
-    DFD_HIP_TRY(h, hipMemcpyAsync(st, B.stats, sizeof st, hipMemcpyDeviceToHost, h->stream));
-    if (full) {
-        DFD_HIP_TRY(h, hipMemcpyAsync(noise, B.stats_noise, (size_t)nblk * 8, hipMemcpyDeviceToHost, h->stream));
-        DFD_HIP_TRY(h, hipMemcpyAsync(ela, B.stats_ela, (size_t)nblk * 8, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (S.has_prev) DFD_HIP_TRY(h, hipMemcpyAsync(dpart, Z->diff_part, (size_t)size * 8, hipMemcpyDeviceToHost, h->stream));
-    DFD_HIP_TRY(h, hipMemcpyAsync(S.prev_gray, B.gray, pix, hipMemcpyDeviceToDevice, h->stream));
-    DFD_HIP_TRY(h, stream_sync(h));
-    DFD_HIP_TRY(h, hipGetLastError());
-
-    const double nan = std::nan("");
-    double sc[6], ex[10], mean_diff, temporal_cv;
-    *prob_out = score_frame(S, st, noise, ela, full != 0, dpart, sc, ex, &mean_diff, &temporal_cv, size, (double)pix, nblk, true);
-    for (int i = 0; i < 6; ++i) scores_out[i] = sc[i];
-    if (stats_out) {
-        const double out[DFD_FORENSIC_NSTATS] = {ex[0], ex[1], ex[2], ex[3], ex[4], ex[5], ex[6], ex[7], ex[8], ex[9],
-                                                 st[ST_EDGE_COUNT] / (double)pix, st[ST_LAP_VAR], full ? st[ST_SAT_STD] : nan,
-                                                 full ? st[ST_VAL_STD] : nan, full ? st[ST_HUES] : nan, mean_diff, temporal_cv,
-                                                 (double)S.frame_count};
-        for (int i = 0; i < DFD_FORENSIC_NSTATS; ++i) stats_out[i] = out[i];
-    }
-    return DFD_OK;
-}
-
-// the fused single-frame entries: the stream at the size and on the chain it holds
-int forensics_stream_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh, int ww, int stride, int full,
-                         double* scores_out, double* prob_out) {
-    if (h->forensic) {
-        auto it = h->forensic->streams.find(stream_id);
-        if (it != h->forensic->streams.end() && on_general_chain(it->second))
-            return forensics_sized_run(h, stream_id, frame_dev, hh, ww, stride, it->second.size, full, scores_out, prob_out, nullptr);
-    }
-    return forensics_run(h, stream_id, frame_dev, hh, ww, stride, full, scores_out, prob_out, nullptr);
-}
-
-}  // namespace dfd
-
-extern "C" {
-
-int dfd_forensics_sized(dfd_handle* h, int stream_id, const uint8_t* bgr, int hh, int ww, int stride, int size, int full,
-                        double* scores_out, double* prob_out, double* stats_out) {
-    if (!h) return DFD_ERR_ARG;
-    if (!bgr || !scores_out || !prob_out || hh <= 0 || ww <= 0 || stride < ww * 3)
-        return fail(h, DFD_ERR_ARG, "forensics_sized: bad pointer or geometry");
-    if (!sized_ok(size))
-        return fail(h, DFD_ERR_ARG, "forensics_sized: analysis size %d is not a multiple of 16 in %d..%d", size, SIZED_MIN, SIZED_MAX);
-    if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
-    DFD_HIP_TRY(h, hipSetDevice(h->device));
-    int rc = stream_size_check(h, stream_id, size);
-    if (rc) return rc;
-    if ((rc = ensure(h, &h->frame_buf, (size_t)hh * stride))) return rc;
-    DFD_HIP_TRY(h, hipMemcpyAsync(h->frame_buf.p, bgr, (size_t)hh * stride, hipMemcpyHostToDevice, h->stream));
-    return forensics_sized_run(h, stream_id, (const uint8_t*)h->frame_buf.p, hh, ww, stride, size, full, scores_out, prob_out, stats_out);
-}
-
 int dfd_forensics_open(dfd_handle* h, int stream_id, int size) {
     if (!h) return DFD_ERR_ARG;
     if (!sized_ok(size))
@@ -822,87 +673,11 @@ int dfd_forensics_open(dfd_handle* h, int stream_id, int size) {
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     int rc = stream_size_check(h, stream_id, size);                  // another size already: refused, nothing changes
     if (rc) return rc;
-    if ((rc = state_init(h, 1))) return rc;
+    if (!h->forensic) h->forensic = new ForensicState();
     ForensicStream& S = h->forensic->streams[stream_id];
     if (S.size) return DFD_OK;                                       // the same size: as it is
     S.size = size;
     S.general = true;
-    return DFD_OK;
-}
-
-int dfd_forensic_tap_sized(dfd_handle* h, const uint8_t* frames, int n, int size, int full, const char* start, const void* start_data,
-                           const char* name, int frame, void* out, size_t capacity, size_t* bytes) {
-    if (!h) return DFD_ERR_ARG;
-    if (!start || !name || !out || !bytes || n <= 0 || n > 16 || frame < -1 || frame >= n)
-        return fail(h, DFD_ERR_ARG, "forensic_tap_sized: bad pointer, frame index or frame count (1..16)");
-    if (!sized_ok(size))
-        return fail(h, DFD_ERR_ARG, "forensic_tap_sized: analysis size %d is not a multiple of 16 in %d..%d", size, SIZED_MIN, SIZED_MAX);
-    const size_t PIX = (size_t)size * size, NB = (size_t)sized_blocks(size), SS = (size_t)size;
-    static const char* const starts[4] = {"rs", "gray", "grad", "map"};
-    int st = -1;
-    for (int i = 0; i < 4; ++i)
-        if (!std::strcmp(start, starts[i])) st = i;
-    if (st < 0) return fail(h, DFD_ERR_ARG, "forensic_tap_sized: start '%s' is none of rs, gray, grad, map", start);
-    if (st == FROM_RS ? !frames : !start_data) return fail(h, DFD_ERR_ARG, "forensic_tap_sized: no data for start '%s'", start);
-    if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
-    DFD_HIP_TRY(h, hipSetDevice(h->device));
-    int rc = state_init(h, 1);
-    if (rc) return rc;
-    ForensicState::Sized* Z = nullptr;
-    if ((rc = sized_init(h, size, n, &Z))) return rc;
-    if ((rc = ensure(h, &Z->tap_store, (size_t)n * PIX * (sizeof(float2) + sizeof(float) + 1)))) return rc;
-    ForensicTaps T;
-    T.spectrum = static_cast<float2*>(Z->tap_store.p);
-    T.logmag = reinterpret_cast<float*>(T.spectrum + (size_t)n * PIX);
-    T.edges = reinterpret_cast<uint8_t*>(T.logmag + (size_t)n * PIX);
-    const ForensicBuffers& B = Z->buf;
-    struct Tap { const char* name; const void* p; size_t per; int last_start; bool full_only; };
-    const bool stats_full = full && st == FROM_RS;
-    const Tap taps[] = {
-        {"rs", B.rs, PIX * 3, FROM_RS, false}, {"gray", B.gray, PIX, FROM_GRAY, false},
-        {"fft_tmp", B.fft_tmp, PIX * sizeof(float2), FROM_GRAY, false}, {"spectrum", T.spectrum, PIX * sizeof(float2), FROM_GRAY, false},
-        {"logmag", T.logmag, PIX * sizeof(float), FROM_GRAY, false}, {"fft_part", B.fft_part, SS * 7 * 8, FROM_GRAY, false},
-        {"grad", B.grad, PIX * sizeof(short2), FROM_GRAD, false}, {"lap_part", B.lap_part, SS * 2 * 8, FROM_GRAY, false},
-        {"map", B.map, PIX, FROM_MAP, false}, {"edges", T.edges, PIX, FROM_MAP, false}, {"edge_count", B.edge_count, 8, FROM_MAP, false},
-        {"jy", B.jy, PIX, FROM_RS, true}, {"jcb", B.jcb, PIX / 4, FROM_RS, true}, {"jcr", B.jcr, PIX / 4, FROM_RS, true},
-        {"stats_ela", B.stats_ela, NB * 8, FROM_RS, true}, {"stats_noise", B.stats_noise, NB * 8, FROM_GRAY, true},
-        {"hsv_part", B.hsv_part, SS * 4 * 8, FROM_RS, true}, {"hue_bits", B.hue_bits, 6 * 4, FROM_RS, true},
-        {"stats", B.stats, (size_t)(stats_full ? FORENSIC_STATS : ST_SAT_STD) * 8, FROM_GRAY, false},
-    };
-    const char* src = nullptr;
-    size_t per = 0, stride = 0;
-    if (!std::strcmp(name, "twiddle")) {                        // the table both DFT launches read; not per frame
-        src = reinterpret_cast<const char*>(Z->table);
-        per = SS * sizeof(float2);
-        frame = 0;
-    }
-    for (const Tap& t : taps)
-        if (!src && !std::strcmp(name, t.name)) {
-            if (st > t.last_start || (t.full_only && !full))
-                return fail(h, DFD_ERR_ARG, "forensic_tap_sized: '%s' is not computed from start '%s' with full = %d", name, start, full);
-            src = static_cast<const char*>(t.p);
-            per = t.per;
-            stride = !std::strcmp(name, "stats") ? FORENSIC_STATS * 8 : t.per;
-        }
-    if (!src) return fail(h, DFD_ERR_ARG, "forensic_tap_sized: no buffer named '%s'", name);
-    const size_t nout = frame < 0 ? (size_t)n : 1, total = nout * per;
-    *bytes = total;
-    if (total > capacity) return fail(h, DFD_ERR_ARG, "forensic_tap_sized '%s' needs %zu bytes, capacity %zu", name, total, capacity);
-    if (st == FROM_RS) {
-        DFD_HIP_TRY(h, hipMemcpyAsync(B.rs, frames, (size_t)n * PIX * 3, hipMemcpyHostToDevice, h->stream));
-    } else {
-        void* dst = st == FROM_GRAY ? (void*)B.gray : st == FROM_GRAD ? (void*)B.grad : (void*)B.map;
-        DFD_HIP_TRY(h, hipMemcpyAsync(dst, start_data, (size_t)n * PIX * (st == FROM_GRAD ? sizeof(short2) : 1), hipMemcpyHostToDevice, h->stream));
-    }
-    DFD_HIP_TRY(h, launch_forensics_sized(B, size, n, full != 0, h->color, Z->table, h->stream, (ForensicStart)st, &T));
-    const size_t first = frame < 0 ? 0 : (size_t)frame;
-    if (stride == per || nout == 1) {
-        DFD_HIP_TRY(h, hipMemcpyAsync(out, src + first * stride, total, hipMemcpyDeviceToHost, h->stream));
-    } else {
-        for (size_t f = 0; f < nout; ++f)
-            DFD_HIP_TRY(h, hipMemcpyAsync((char*)out + f * per, src + f * stride, per, hipMemcpyDeviceToHost, h->stream));
-    }
-    DFD_HIP_TRY(h, stream_sync(h));
     return DFD_OK;
 }
 

@@ -3,15 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "forensic_score.h"   // ForensicStat: the per-frame scalar statistics produced on the device
 #include "imgproc_kernels.h"
 
 namespace dfd {
-
-// per-frame scalar statistics produced on the device (doubles)
-enum ForensicStat {
-    ST_FREQ_LOW = 0, ST_FREQ_MID, ST_FREQ_HIGH, ST_FREQ_MID_STD, ST_LAP_VAR, ST_EDGE_COUNT,
-    ST_SAT_STD, ST_VAL_STD, ST_HUES, FORENSIC_STATS
-};
 
 struct ForensicBuffers {
     uint8_t* rs;         // [n][256][256][3] resized BGR

@@ -16,6 +16,7 @@
 //   absdiff_kernel         sum |gray - prev gray|                     frame_analysis.py:363-364
 //
 // Compiled with -ffp-contract=off (operation orders restate OpenCV's float filters).
+#include "forensic_device.h"
 #include "forensic_kernels.h"
 #include "jpeg_dct.h"
 
@@ -25,7 +26,6 @@ constexpr int FS = 256;            // analysis edge
 constexpr int FPIX = FS * FS;
 
 __device__ __forceinline__ int r101(int i) { i = i < 0 ? -i : i; return i >= FS ? 2 * (FS - 1) - i : i; }
-__device__ __forceinline__ int clampi2(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // block-wide sum of doubles (256 or 1024 threads); result valid in thread 0
 template <int NT>
@@ -40,30 +40,6 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
         for (int i = 0; i < NT / 64; ++i) r += sh[i];
     __syncthreads();
     return r;
-}
-
-// N block-wide sums at once: the same shuffle tree and the same wave-order fold per value as block_sum (identical bits),
-// one barrier pair for all of them instead of one per value (fft_band: 7, hsv_stats: 4, sobel_lap: 2 - the barriers were
-// most of what these 256-pixel blocks did after their loads).  Results valid in thread 0.
-template <int NT, int N>
-__device__ __forceinline__ void block_sum_n(double (&v)[N], double* sh) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < N; ++j)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[j] += __shfl_xor(v[j], off);
-    if ((tid & 63) == 0)
-#pragma unroll
-        for (int j = 0; j < N; ++j) sh[(tid >> 6) * N + j] = v[j];
-    __syncthreads();
-    if (tid == 0)
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            double r = 0.0;
-            for (int i = 0; i < NT / 64; ++i) r += sh[i * N + j];
-            v[j] = r;
-        }
-    __syncthreads();
 }
 
 // ---------------------------------------------------------------------------------- gray
@@ -179,25 +155,6 @@ __global__ __launch_bounds__(256) void noise_block_kernel(const uint8_t* __restr
 // quantise + dequantise at quality 90 with the divisors as compile-time constants (the tables again as constexpr: after
 // unrolling every `/ dv` is a multiply-shift; with the divisor read from __constant__ memory each of the 64 divisions
 // per block was a ~25-instruction sequence - a quarter of this kernel's instructions)
-template <bool CHROMA>
-__device__ __forceinline__ void jpeg_quant_q90(int* d) {
-    constexpr int L[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57,
-                           69, 56, 14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64,
-                           81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
-    constexpr int C[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
-                           99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
-                           99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
-#pragma unroll
-    for (int i = 0; i < 64; ++i) {                                // quality 90: scale = 200 - 2*90 = 20
-        const int q0 = CHROMA ? C[i] : L[i];
-        int qv = (q0 * 20 + 50) / 100;
-        qv = qv < 1 ? 1 : (qv > 255 ? 255 : qv);
-        const int dv = qv << 3, a = d[i] < 0 ? -d[i] : d[i];
-        const int lev = (a + (dv >> 1)) / dv;
-        d[i] = (d[i] < 0 ? -lev : lev) * qv;                       // quantise, then dequantise
-    }
-}
-
 // (libjpeg fixed-point colour conversion and jfdctint / jidctint passes: jpeg_dct.h, shared with jpeg_decode.hip)
 // blocks 0..1023: Y (32x32 blocks); 1024..1279: Cb (16x16); 1280..1535: Cr
 __global__ __launch_bounds__(64) void jpeg_block_kernel(const uint8_t* __restrict__ bgr, uint8_t* __restrict__ yp,
@@ -246,7 +203,7 @@ __global__ __launch_bounds__(64) void jpeg_block_kernel(const uint8_t* __restric
 #pragma unroll
     for (int r = 0; r < 8; ++r) idct8<false>(d + 8 * r, 1);
 #pragma unroll
-    for (int i = 0; i < 64; ++i) dst[(i >> 3) * dstride + (i & 7)] = (uint8_t)clampi2(d[i] + 128, 0, 255);
+    for (int i = 0; i < 64; ++i) dst[(i >> 3) * dstride + (i & 7)] = (uint8_t)clampi(d[i] + 128, 0, 255);
 }
 
 __device__ __forceinline__ int fancy_up(const uint8_t* p, int Y, int X) {      // p: 128x128 plane
@@ -275,9 +232,9 @@ __global__ __launch_bounds__(256) void ela_block_kernel(const uint8_t* __restric
         const int y = by + (i >> 5), x = bx + (i & 31);
         const int Yv = yp[f * FPIX + y * FS + x];
         const int cb = fancy_up(cbp + f * (FPIX / 4), y, x) - 128, cr = fancy_up(crp + f * (FPIX / 4), y, x) - 128;
-        const int r = clampi2(Yv + ((JFIX(1.40200) * cr + 32768) >> 16), 0, 255);
-        const int g = clampi2(Yv + ((-JFIX(0.34414) * cb + 32768 - JFIX(0.71414) * cr) >> 16), 0, 255);
-        const int b = clampi2(Yv + ((JFIX(1.77200) * cb + 32768) >> 16), 0, 255);
+        const int r = clampi(Yv + ((JFIX(1.40200) * cr + 32768) >> 16), 0, 255);
+        const int g = clampi(Yv + ((-JFIX(0.34414) * cb + 32768 - JFIX(0.71414) * cr) >> 16), 0, 255);
+        const int b = clampi(Yv + ((JFIX(1.77200) * cb + 32768) >> 16), 0, 255);
         const uint8_t* p = bgr + (f * FPIX + y * FS + x) * 3;
         const int db = abs((int)p[0] - b), dg = abs((int)p[1] - g), dr = abs((int)p[2] - r);
         s += (db * 1868 + dg * 9617 + dr * 4899 + (1 << 13)) >> 14;
@@ -351,25 +308,6 @@ __global__ __launch_bounds__(256) void canny_nms_kernel(const short2* __restrict
 // the set OpenCV's stack-based flood fill reaches, whatever the visiting order.  (The byte-map version of this kernel
 // scanned 64 pixels x 9 LDS reads per thread and sweep: 480 us per 64 frames, more than the other nine forensic
 // kernels together.)
-__device__ __forceinline__ unsigned long long fill_row(unsigned long long gen, unsigned long long pro) {
-    unsigned long long g = gen, p = pro;                    // towards higher columns
-    g |= p & (g << 1);  p &= p << 1;
-    g |= p & (g << 2);  p &= p << 2;
-    g |= p & (g << 4);  p &= p << 4;
-    g |= p & (g << 8);  p &= p << 8;
-    g |= p & (g << 16); p &= p << 16;
-    g |= p & (g << 32);
-    unsigned long long h = gen;                             // towards lower columns
-    p = pro;
-    h |= p & (h >> 1);  p &= p >> 1;
-    h |= p & (h >> 2);  p &= p >> 2;
-    h |= p & (h >> 4);  p &= p >> 4;
-    h |= p & (h >> 8);  p &= p >> 8;
-    h |= p & (h >> 16); p &= p >> 16;
-    h |= p & (h >> 32);
-    return g | h;
-}
-
 // edges_out: test tap, the final edge set as one byte (0 / 1) per pixel; null on every production launch, which runs the
 // TAP = false instantiation (with the store compiled in behind a run-time test of the pointer alone, the kernel measured
 // 36 -> 40 us per 64 frames with the branch never taken).

@@ -22,6 +22,7 @@
 
 #include <cmath>
 
+#include "forensic_device.h"
 #include "jpeg_dct.h"
 
 namespace dfd {
@@ -31,30 +32,8 @@ namespace {
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ int r101(int i, int S) { i = i < 0 ? -i : i; return i >= S ? 2 * (S - 1) - i : i; }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// block-wide sums of doubles over NT threads (all of them active); results valid in thread 0
-template <int NT, int N>
-__device__ __forceinline__ void block_sum_n(double (&v)[N], double* sh) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < N; ++j)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[j] += __shfl_xor(v[j], off);
-    if ((tid & 63) == 0)
-#pragma unroll
-        for (int j = 0; j < N; ++j) sh[(tid >> 6) * N + j] = v[j];
-    __syncthreads();
-    if (tid == 0)
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            double r = 0.0;
-            for (int i = 0; i < NT / 64; ++i) r += sh[i * N + j];
-            v[j] = r;
-        }
-    __syncthreads();
-}
-
+// one block-wide sum; result valid in thread 0
 template <int NT>
 __device__ __forceinline__ double block_sum(double v, double* sh) {
     double a[1] = {v};
@@ -314,31 +293,12 @@ __global__ __launch_bounds__(256) void sz_noise_block_kernel(const uint8_t* __re
 // ---------------------------------------------------------------------------------- JPEG
 // libjpeg integer pipeline per 8x8 block, one thread per block; quality 90 divisors as compile-time constants
 template <bool CHROMA>
-__device__ __forceinline__ void sz_jpeg_quant_q90(int* d) {
-    constexpr int L[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57,
-                           69, 56, 14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64,
-                           81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
-    constexpr int C[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
-                           99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
-                           99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
-#pragma unroll
-    for (int i = 0; i < 64; ++i) {                                // quality 90: scale = 200 - 2*90 = 20
-        const int q0 = CHROMA ? C[i] : L[i];
-        int qv = (q0 * 20 + 50) / 100;
-        qv = qv < 1 ? 1 : (qv > 255 ? 255 : qv);
-        const int dv = qv << 3, a = d[i] < 0 ? -d[i] : d[i];
-        const int lev = (a + (dv >> 1)) / dv;
-        d[i] = (d[i] < 0 ? -lev : lev) * qv;                       // quantise, then dequantise
-    }
-}
-
-template <bool CHROMA>
 __device__ __forceinline__ void sz_jpeg_roundtrip(int* d, uint8_t* dst, int dstride) {
 #pragma unroll
     for (int r = 0; r < 8; ++r) fdct8<true>(d + 8 * r, 1);
 #pragma unroll
     for (int c = 0; c < 8; ++c) fdct8<false>(d + c, 8);
-    sz_jpeg_quant_q90<CHROMA>(d);
+    jpeg_quant_q90<CHROMA>(d);
 #pragma unroll
     for (int c = 0; c < 8; ++c) idct8<true>(d + c, 8);
 #pragma unroll
@@ -496,25 +456,6 @@ __global__ __launch_bounds__(256) void sz_canny_nms_kernel(const short2* __restr
 // neither the dilation (ANDed with the weak set) nor the fill along the row (inside strong | weak) can reach them.  A
 // sweep reads every word's neighbourhood, a barrier separates the reads from the writes, and sweeps repeat until no
 // word changes: the fixpoint is the set OpenCV's stack-based flood fill reaches, whatever the visiting order.
-__device__ __forceinline__ unsigned long long sz_fill_row(unsigned long long gen, unsigned long long pro) {
-    unsigned long long g = gen, p = pro;                    // towards higher columns
-    g |= p & (g << 1);  p &= p << 1;
-    g |= p & (g << 2);  p &= p << 2;
-    g |= p & (g << 4);  p &= p << 4;
-    g |= p & (g << 8);  p &= p << 8;
-    g |= p & (g << 16); p &= p << 16;
-    g |= p & (g << 32);
-    unsigned long long h = gen;                             // towards lower columns
-    p = pro;
-    h |= p & (h >> 1);  p &= p >> 1;
-    h |= p & (h >> 2);  p &= p >> 2;
-    h |= p & (h >> 4);  p &= p >> 4;
-    h |= p & (h >> 8);  p &= p >> 8;
-    h |= p & (h >> 16); p &= p >> 16;
-    h |= p & (h >> 32);
-    return g | h;
-}
-
 constexpr int HYST_MAXW = 16;                               // words per thread at S = 1024: 1024 * 16 / 1024
 
 __global__ __launch_bounds__(1024) void sz_canny_hyst_kernel(const uint8_t* __restrict__ map, double* __restrict__ count,
@@ -571,7 +512,7 @@ __global__ __launch_bounds__(1024) void sz_canny_hyst_kernel(const uint8_t* __re
                 const unsigned long long vl = (has_l >> k) & 1u ? (Sw[wi - wpr - 1] | Sw[wi - 1] | Sw[wi + wpr - 1]) : 0ull;
                 const unsigned long long vr = (has_r >> k) & 1u ? (Sw[wi - wpr + 1] | Sw[wi + 1] | Sw[wi + wpr + 1]) : 0ull;
                 const unsigned long long dil = v | (v << 1) | (v >> 1) | (vl >> 63) | (vr << 63);
-                nw[k] = sz_fill_row(s | (wk[k] & dil), s | wk[k]);
+                nw[k] = fill_row(s | (wk[k] & dil), s | wk[k]);
                 changed |= nw[k] != s;
             }
         }

@@ -12,6 +12,9 @@
 //   host_asan_driver blob  FILE            -> "rc=<0|-2> tensors=<n>"
 //   host_asan_driver rows  FILE H W THR    -> SSD rows [n][5] f32 -> "n=<kept> total=<all> boxes..."
 //   host_asan_driver rects FILE THR        -> int32 [n][4] -> grouped rectangles
+//   host_asan_driver score FILE            -> the analyzer's host half (forensic_score.h) on the frames of ONE stream, float64
+//                                             records {full, S, npix, nblk, npart, f32_means, st[9], noise[nblk], ela[nblk],
+//                                             part[npart]}: per frame "sc0 .. sc5 prob mean_diff temporal_cv" as hex floats
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -21,6 +24,7 @@
 #include <vector>
 
 #include "blob_reader.h"
+#include "forensic_score.h"
 #include "host_boxes.h"
 #include "jpeg_entropy.h"
 
@@ -146,6 +150,34 @@ int main(int argc, char** argv) {
         printf("n=%zu", out.size());
         for (const dfd::Rect& r : out) printf(" (%d,%d,%d,%d)", r.x, r.y, r.w, r.h);
         printf("\n");
+        return 0;
+    }
+    if (cmd == "score") {
+        std::vector<double> v(data.size() / 8);
+        memcpy(v.data(), data.data(), v.size() * 8);
+        dfd::ForensicTemporal stream;                       // carried across the records
+        for (size_t at = 0; at < v.size();) {
+            if (v.size() - at < 6) { fprintf(stderr, "truncated record header\n"); return 2; }
+            dfd::ForensicGeometry G;
+            const bool full = v[at] != 0;
+            G.S = (int)v[at + 1]; G.npix = v[at + 2]; G.nblk = (int)v[at + 3]; G.npart = (int)v[at + 4];
+            G.f32_means = v[at + 5] != 0;
+            at += 6;
+            if (G.nblk < 0 || G.npart < 0 || v.size() - at < (size_t)dfd::FORENSIC_STATS + 2 * (size_t)G.nblk + (size_t)G.npart) {
+                fprintf(stderr, "truncated record\n");
+                return 2;
+            }
+            // exact-size copies: a read past nblk or npart hits a redzone
+            const std::vector<double> st(v.begin() + at, v.begin() + at + dfd::FORENSIC_STATS);
+            at += dfd::FORENSIC_STATS;
+            const std::vector<double> noise(v.begin() + at, v.begin() + at + G.nblk), ela(v.begin() + at + G.nblk, v.begin() + at + 2 * G.nblk);
+            at += 2 * (size_t)G.nblk;
+            const std::vector<double> part(v.begin() + at, v.begin() + at + G.npart);
+            at += G.npart;
+            double sc[6], ex[10], md, tcv;
+            const double prob = dfd::score_frame(stream, G, st.data(), noise.data(), ela.data(), full, part.data(), sc, ex, &md, &tcv);
+            printf("%a %a %a %a %a %a %a %a %a\n", sc[0], sc[1], sc[2], sc[3], sc[4], sc[5], prob, md, tcv);
+        }
         return 0;
     }
     fprintf(stderr, "unknown command\n");

@@ -11,7 +11,7 @@ Everything else is a pure function of one frame.  A rank therefore computes per 
 probability of faces[0] (or none), the five stateless forensic scores and mean|gray(t) - gray(t-1)| - it holds
 frame t-1 too and recomputes its gray plane (64 KB) instead of receiving it - and ships them as one
 80-byte record.  `StreamReplica.replay` is the rest of the flow; fed the records of all ranks in frame order
-it performs exactly the arithmetic of the single-GPU stateful path (csrc/forensic_api.hip forensics_run +
+it performs exactly the arithmetic of the single-GPU stateful path (csrc/forensic_score.h score_frame +
 DeepfakeDetector.analyze_request), so every rank ends each wave with bit-identical vote state.
 
 Transports for the exchange: "rccl" = dfd_vote_allgather through the C ABI (ncclAllGather on the handle's
@@ -55,7 +55,8 @@ class StreamReplica:
         self.next_frame = 0
 
     def forensic_probability(self, rec) -> float:
-        """temporal score + weighted sum for this frame (the host half of csrc/forensic_api.hip forensics_run)"""
+        """temporal score + weighted sum for this frame (csrc/forensic_score.h score_frame; tests/test_host_asan.py holds
+        the two equal as doubles)"""
         full = self.frame_count % self.full_forensic_interval == 0     # before the counter moves (server order)
         self.analyzer_frames += 1
         temporal = 0.0

@@ -208,7 +208,44 @@ def _open_all(h, base):
             h.forensics_open(base + s, size)
 
 
-def test_streams_of_mixed_sizes_in_one_pass(b0_handle):
+def _chain_kinds_in_one_pass(pkg, seeded_sd, h):
+    """the three kinds of chain in ONE batched call - a 256 stream nobody opened (256x256 kernels), an opened 256 stream
+    (general chain at 256) and a 48 stream (one block: fewer than 4) - with one frame a chunk, so the opened stream's
+    three frames take three chunks of its group; every frame against the single entries on a fresh handle"""
+    sizes, order, base = {0: None, 1: 256, 2: 48}, [0, 1, 2, 1, 0, 2, 1], 8700
+    fresh = pkg._lib.Handle(pkg.weights.pack_all(seeded_sd, pkg.weights.seeded_ssd_state_dict(0)), device=0, max_batch=16)
+    try:
+        for s, size in sizes.items():
+            _fresh(h, base + s)
+            if size:
+                h.forensics_open(base + s, size)
+        seen, items = {}, []
+        for s in order:
+            seen[s] = seen.get(s, 0) + 1
+            items.append(X.stream_frames(s, 1, start=seen[s] - 1)[0])
+        full = [k % 2 == 0 for k in range(len(order))]
+        h.set_option("forensic_chunk_bytes", 1)
+        try:
+            got = h.analyze_streams_batch(items, [base + s for s in order], full, max_faces=MAX_FACES)
+        finally:
+            h.set_option("forensic_chunk_bytes", 0)                # the default
+        for k, s in enumerate(order):
+            if sizes[s]:
+                scores, prob, _ = fresh.forensics_sized(items[k], sizes[s], full[k], base + s)
+            else:
+                scores, prob, _ = fresh.forensics(items[k], full[k], base + s)
+            assert got[k][0] == scores and got[k][1] == prob, (k, s, got[k][:2], scores, prob)
+            if sizes[s] == 48 and full[k]:
+                assert (scores["noise"], scores["ela"]) == (0.0, 0.0)
+        for s in sizes:
+            assert h.forensics_state(base + s) == fresh.forensics_state(base + s) == (seen[s], seen[s] - 1, True), s
+    finally:
+        fresh.close()
+        for s in sizes:
+            h.forensics_release(base + s)
+
+
+def test_streams_of_mixed_sizes_in_one_pass(pkg, seeded_sd, b0_handle):
     h = b0_handle
     new, ref = 8100, 8200
     _open_all(h, new)
@@ -233,6 +270,7 @@ def test_streams_of_mixed_sizes_in_one_pass(b0_handle):
     for s in STREAM_SIZE:
         h.forensics_release(new + s)
         h.forensics_release(ref + s)
+    _chain_kinds_in_one_pass(pkg, seeded_sd, h)
 
 
 # ------------------------------------------------------------------------------------------------ 6: chunking

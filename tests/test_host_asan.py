@@ -184,3 +184,155 @@ def test_detector_box_logic_on_hostile_rows(driver, tmp_path):
     p.write_bytes(rects.tobytes())
     assert driver("rects", p, 3) == "n=1 (11,10,50,50)"
     assert driver("rects", p, 0).startswith("n=5")
+
+
+# ------------------------------------------------------------------------------------------------ forensic scoring
+# The analyzer's host half (csrc/forensic_score.h: thresholds, temporal deque, weighted sum) on seeded statistics, against
+# the project's Python restatements: oracle.forensics_ref.ForensicsRef for the five stateless scores and the mean
+# difference, streams.StreamReplica.forensic_probability for the temporal signal and the weighted sum.  ForensicsRef
+# works on images, so every chosen statistic is REALISED as a small array on which the oracle's own numpy expression
+# gives exactly that number (all values sit on a binary grid: the sums are exact in any order), with the image
+# operators of oracle.imgproc_ref / jpeg_ref and the spectrum replaced by stand-ins that hand the prepared array on.
+class _Operators:
+    """stand-in for oracle.imgproc_ref and oracle.jpeg_ref: the prepared arrays ARE the operators' results"""
+    edge_map = lap = None
+    bgr2gray_u8 = bgr2hsv_u8 = staticmethod(lambda a: a)
+    gaussian5_f32 = staticmethod(np.zeros_like)
+    roundtrip_np = staticmethod(lambda frame, quality: np.zeros_like(frame))
+
+    def canny_u8(self, gray, lo, hi):
+        return self.edge_map
+
+    def laplacian_i32(self, gray):
+        return self.lap
+
+
+class _PlainSpectrum:
+    """numpy as ForensicsRef.frequency sees it on a prepared log-magnitude plane: transform and logarithm hand it on"""
+    class fft:
+        fft2 = fftshift = staticmethod(lambda a: a)
+    log1p = staticmethod(lambda a: a)
+
+    def __getattr__(self, name):
+        return getattr(np, name)
+
+
+def _blocks_plane(S, values, dtype, checker):
+    """S x S plane whose 32x32 block b holds values[b] everywhere, or +-values[b] as a checkerboard"""
+    p = np.zeros((S, S), dtype)
+    sign = (1 - 2 * (np.add.outer(np.arange(32), np.arange(32)) % 2)).astype(dtype) if checker else 1
+    nb = S // 32
+    for b, v in enumerate(values):
+        i, j = divmod(b, nb)
+        p[32 * i:32 * i + 32, 32 * j:32 * j + 32] = dtype(v) * sign
+    return p
+
+
+def _spread(total, S):
+    """uint8 S x S plane whose pixels sum to `total`"""
+    q, r = divmod(total, S * S)
+    flat = np.full(S * S, q, np.uint8)
+    flat[:r] += 1
+    return flat.reshape(S, S)
+
+
+def _forensic_stream(ref, ops, rs, S, f32_means, fulls, totals):
+    """one stream's records for the driver, and what the restatements say of every frame: (five scores, mean_diff)"""
+    npix, nblk = S * S, (S // 32) ** 2
+    ref._dist, (ref._inner, ref._mid, ref._outer) = np.array([[0, 0, 1, 1, 1, 1, 2, 2]]), (0, 1, 2)
+    records, want, seen = [], [], set()
+    half = np.arange(npix).reshape(S, S) % 2 == 0
+    for t, (full, total) in enumerate(zip(fulls, totals)):
+        pick = lambda *options: options[rs.randint(len(options))]      # noqa: E731
+        ref.stats = {}
+        # frequency: band means lo / mi / hi, the mid band's std a
+        lo, mi, hi = pick(8.0, 3.0), pick(4.0, 6.5, 2.0), pick(1.0, 2.5, 3.5, 6.0)
+        a = mi * pick(0.125, 0.5, 0.75)
+        freq = ref.frequency(np.array([[lo, lo, mi + a, mi - a, mi + a, mi - a, hi, hi]]))
+        hr, mr = hi / (lo + mi + hi), mi / (lo + mi + hi)
+        seen |= {("hr", hr < 0.18, hr < 0.22), ("mid_cv", a / mi > 0.6, a / mi > 0.45), ("mr", mr > 0.45 and hr < 0.2)}
+        # edges: `count` pixels set, Laplacian values +-lv
+        count, lv = int(pick(0.01, 0.03, 0.06) * npix), pick(5.0, 8.0, 12.0)
+        ops.edge_map = (np.arange(npix) < count).astype(np.uint8).reshape(S, S)
+        ops.lap = np.array([lv, -lv])
+        edge = ref.edges(None)
+        seen |= {("density", count / npix < 0.02, count / npix < 0.04), ("lap", lv * lv < 50, lv * lv < 100)}
+        # noise / ELA block values, colour: S and V stds sv / vv about 100, `hues` hue values
+        nv, ev = pick((0.5, 0.5), (0.25, 2.75), (1.25, 4.75), (1.5, 1.5)), pick((12, 12), (1, 39), (3, 13), (20, 20))
+        noise_b, ela_b = [nv[b % 2] for b in range(nblk)], [ev[b % 2] for b in range(nblk)]
+        sv, vv, hues = pick(10, 20, 40), pick(10, 20, 40), pick(20, 40, 90)
+        noise = ela = color = float("nan")
+        if full:
+            noise = ref.noise(_blocks_plane(S, noise_b, np.float32, True))
+            ela = ref.ela(_blocks_plane(S, ela_b, np.uint8, False))
+            hsv = np.stack([(np.arange(npix) % hues).reshape(S, S), np.where(half, 100 + sv, 100 - sv),
+                            np.where(half, 100 + vv, 100 - vv)], -1).astype(np.uint8)
+            color = ref.color(hsv)
+            seen |= {("sat", sv < 15, sv < 25), ("val", vv < 15, vv < 25), ("hues", hues < 30, hues < 50)}
+            if nblk >= 4:
+                for name, vals, cuts in (("noise", noise_b, (0.7, 0.5, 1.0, 2.0)), ("ela", ela_b, (0.9, 0.6, 15, 10))):
+                    m, sd = np.mean(vals), np.std(vals)
+                    assert min(abs(sd / m - cuts[0]), abs(sd / m - cuts[1]), abs(m - cuts[2]), abs(m - cuts[3])) > 1e-3
+                    seen |= {(name, sd / m > cuts[0], sd / m > cuts[1], m > cuts[2], m > cuts[3])}
+        # temporal: a gray plane that sums to `total` against a predecessor of zeros, so |difference| is that plane
+        plane = _spread(total, S)
+        if t:
+            ref.prev_frame_gray = np.zeros((S, S), np.float32)
+        ref.temporal(plane)
+        part = plane.sum(axis=1).astype(np.float64) if t else np.zeros(S)
+        md = ref.stats["mean_diff"] if f32_means or t == 0 else total / npix     # np.mean of float32 | divided in double
+        st = [lo, mi, hi, a, lv * lv, count, sv, vv, hues]
+        records += [float(full), S, npix, nblk, S, float(f32_means), *st, *noise_b, *ela_b, *part]
+        want.append(((freq, noise, ela, edge, color), md))
+    return np.array(records, np.float64), want, seen
+
+
+def test_forensic_scoring_equals_the_python_restatements(driver, tmp_path, pkg, monkeypatch):
+    from oracle import forensics_ref as R
+
+    ops = _Operators()
+    monkeypatch.setattr(R, "I", ops)
+    monkeypatch.setattr(R, "J", ops)
+    monkeypatch.setattr(R, "np", _PlainSpectrum())
+    S = pkg.streams
+    rs = np.random.RandomState(20)
+    # totals of |difference| per frame as a fraction of the plane: calm (< 0.3 a pixel), moving (< 0.8), busy, and spikes
+    calm, moving, busy, spike = 0.2, 0.6, 2.0, 60.0
+    # coefficient of variation of the last 30: below 1.0 up to frame 16, above 1.5 from the first spike, 1.46 at the end
+    long_run = [calm, moving] * 5 + [calm, moving, busy] * 2 + [spike] + [calm] * 5 + [spike, moving, spike, calm, busy] * 4
+    assert len(long_run) == 42                                     # the 30-deep deque wraps, frame 10 is crossed
+    cases = [(256, False, long_run), (48, True, long_run), (96, True, long_run[:12]), (96, False, long_run[:12])]
+    seen, temporal = set(), set()
+    for k, (edge, f32_means, run) in enumerate(cases):
+        fulls = [rs.randint(3) > 0 for _ in run]
+        totals = [int(v * edge * edge) + int(rs.randint(7)) for v in run]
+        records, want, hit = _forensic_stream(R.ForensicsRef((edge, edge)), ops, rs, edge, f32_means, fulls, totals)
+        seen |= hit
+        p = tmp_path / f"score{k}.bin"
+        p.write_bytes(records.tobytes())
+        lines = driver("score", p).splitlines()
+        assert len(lines) == len(run)
+        replica = S.StreamReplica(full_forensic_interval=2)
+        for t, (line, (scores, md), full) in enumerate(zip(lines, want, fulls)):
+            got = [float.fromhex(v) for v in line.split()]
+            for i, w in enumerate(scores):                          # the five stateless scores: equal, or absent alike
+                assert got[i] == w or (np.isnan(w) and np.isnan(got[i]) and not full), (k, t, i, got, scores)
+            assert got[7] == md and (t > 0) == (md >= 0), (k, t, got[7], md)
+            rec = np.zeros(S.RECORD_FLOATS)
+            rec[S.F_MEAN_DIFF] = md
+            rec[S.F_FREQ:S.F_COLOR + 1] = scores
+            replica.frame_count = 0 if full else 1                  # its full / fast schedule: this frame's mode
+            assert got[6] == replica.forensic_probability(rec), (k, t)
+            if not np.isnan(got[8]):
+                temporal.add((got[8] > 1.5, got[8] > 1.0, md < 0.3, md < 0.8, t + 1 > 10))
+        if edge == 96:
+            assert (want[5][1] == totals[5] / edge ** 2) == (not f32_means)      # the two mean rules differ here
+        assert len(replica.diffs) == min(len(run) - 1, 30)
+    # both sides of every threshold: all branches of each rule were taken
+    for name, n in (("hr", 3), ("mid_cv", 3), ("mr", 2), ("density", 3), ("lap", 3), ("sat", 3), ("val", 3), ("hues", 3)):
+        assert len({s for s in seen if s[0] == name}) == n, (name, seen)
+    for name, i in (("noise", 1), ("noise", 2), ("noise", 3), ("noise", 4), ("ela", 1), ("ela", 2), ("ela", 3), ("ela", 4)):
+        assert {s[i] for s in seen if s[0] == name} == {True, False}, (name, i)
+    assert len({s[:2] for s in temporal}) == 3, temporal            # cv above 1.5, between, below 1.0
+    assert len({s[2:4] for s in temporal if s[4]}) == 3, temporal   # past frame 10: below 0.3, below 0.8, above
+    assert (True, True, False) in {s[2:5] for s in temporal}        # a calm frame before frame 10 scores nothing for it
