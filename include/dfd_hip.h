@@ -525,6 +525,37 @@ int dfd_analyze_jpeg(dfd_handle* h, int stream_id, const uint8_t* jpeg, size_t l
                      int max_faces, int apply_clahe, double* scores_out, double* forensic_prob_out, int32_t* xywh_out,
                      int* n_faces_out, float* logits_out, int* height_out, int* width_out);
 
+/* ---- baseline JPEG encode on the device (csrc/jpeg_encode.hip) ----------------------------------
+ * Pixels -> a JFIF file whose BYTES equal what libjpeg(-turbo) writes for the same pixels with its default settings and
+ * the Annex K Huffman tables (Pillow's `save(..., quality=q, subsampling=s, optimize=False)`): colour conversion, edge
+ * replication, h2v1 / h2v2 downsampling, the islow FDCT, quantisation, Huffman coding, byte stuffing and the RSTn markers all
+ * run on the device; only the ~600-byte header is built on the host.  One call encodes a batch of images of any sizes and
+ * modes in one chain of launches; an image's bytes do not depend on what else is in the batch.
+ * A source is BGR (rgb = 0) or RGB (rgb = 1) u8 with 3 bytes per pixel, or with subsampling DFD_JPEG_GRAY one u8 plane;
+ * stride in bytes.  quality 1..100; restart_blocks = MCUs per restart interval (0 = none, at most 65535; Pillow's
+ * restart_marker_blocks).  Images of fewer than 1 x 1 pixels or more than 65535 a side, quality outside 1..100, an unknown
+ * subsampling or a bad restart_blocks: DFD_ERR_ARG.  An image above 2^24 pixels: DFD_ERR_UNSUPPORTED (a block codes to at
+ * most 1,658 bits and a 4:4:4 image of 2^24 pixels has 3 x 2^18 blocks, so every bit offset inside one image fits 32 bits).
+ * Output: host memory.  dfd_encode_jpeg writes one file to out and its size to *len.  The batch calls write the files back
+ * to back into out, file i at offsets[i] with lens[i] bytes, and the sum to *total.  Sizes are exact before anything is
+ * written: when capacity is too small the call returns DFD_ERR_ARG, *len / *total (and lens) hold what is needed, and out is
+ * untouched.  dfd_encode_jpeg_bound: a capacity that always suffices for one image (0 for arguments the encoder refuses).
+ * dfd_encode_jpeg_device: the sources' pixels are in HBM (frames of dfd_decode_jpeg_batch, dfd_device_alloc buffers);
+ * only JPEG bytes cross to the host. */
+enum { DFD_JPEG_444 = 0, DFD_JPEG_422 = 1, DFD_JPEG_420 = 2, DFD_JPEG_GRAY = 3 };
+typedef struct dfd_jpeg_source {
+    const uint8_t* pixels;
+    int32_t height, width, stride;
+    int32_t rgb, quality, subsampling, restart_blocks;
+} dfd_jpeg_source;
+size_t dfd_encode_jpeg_bound(int height, int width, int subsampling);
+int dfd_encode_jpeg(dfd_handle* h, const uint8_t* pixels, int height, int width, int stride, int rgb, int quality,
+                    int subsampling, int restart_blocks, uint8_t* out, size_t capacity, size_t* len);
+int dfd_encode_jpeg_batch(dfd_handle* h, int n, const dfd_jpeg_source* images, uint8_t* out, size_t capacity, size_t* offsets,
+                          size_t* lens, size_t* total);
+int dfd_encode_jpeg_device(dfd_handle* h, int n, const dfd_jpeg_source* images, uint8_t* out, size_t capacity, size_t* offsets,
+                           size_t* lens, size_t* total);
+
 /* ---- one request, several consecutive frames of ONE stream (POST /analyze_batch) --------------
  * The per-frame flow of dfd_analyze_frame / dfd_analyze_jpeg (reference backend_server.py:139-164, executed once per
  * request there) for n frames in stream order with every stage batched: data[i] is a JPEG of len[i] bytes (entropy

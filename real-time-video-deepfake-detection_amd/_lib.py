@@ -105,6 +105,13 @@ SIGNATURES = {
                                   C.POINTER(C.c_int)]),
     "dfd_decode_jpeg_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
                                         C.POINTER(C.c_int)]),
+    "dfd_encode_jpeg_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "dfd_encode_jpeg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "dfd_encode_jpeg_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_size_t)]),
+    "dfd_encode_jpeg_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_size_t)]),
     "dfd_jpeg_decode_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "dfd_analyze_jpeg": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int),
@@ -157,6 +164,16 @@ class MtcnnParams(C.Structure):
     """`dfd_mtcnn_params` (include/dfd_hip.h): the constructor arguments of facenet_pytorch.MTCNN."""
     _fields_ = [("image_size", C.c_int), ("margin", C.c_int), ("min_face_size", C.c_int), ("thresholds", C.c_float * 3),
                 ("factor", C.c_double), ("selection", C.c_int), ("keep_all", C.c_int), ("post_process", C.c_int)]
+
+
+class JpegSource(C.Structure):
+    """`dfd_jpeg_source` (include/dfd_hip.h): one image of a batched JPEG encode."""
+    _fields_ = [("pixels", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32), ("stride", C.c_int32), ("rgb", C.c_int32),
+                ("quality", C.c_int32), ("subsampling", C.c_int32), ("restart_blocks", C.c_int32)]
+
+
+JPEG_GRAY = 3                 # DFD_JPEG_GRAY; 0 / 1 / 2 = 4:4:4 / 4:2:2 / 4:2:0 as in Pillow
+JPEG_ENC_SCAN_TILE = 1024     # blocks one workgroup of the encoder's prefix sum covers in one pass (csrc/jpeg_encode.hip kEncScanTile)
 
 
 class TtaDraw(C.Structure):
@@ -724,6 +741,60 @@ class Handle:
         out = np.empty((n, hh.value, ww.value, 3), np.uint8)
         self._check(self._lib.dfd_memcpy_d2h(self._p, _ptr(out), self.frame_ptr(), out.nbytes))
         return out
+
+    # -- JPEG encode (csrc/jpeg_encode.hip)
+    @staticmethod
+    def _jpeg_source(img, quality, subsampling, restart_blocks, rgb, ptr=None) -> "JpegSource":
+        """img: (H, W) gray or (H, W, 3) u8 array; or with `ptr` a (height, width, stride, channels) tuple of an image in HBM"""
+        if ptr is None:
+            if img.dtype != np.uint8 or img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] != 3) or not img.flags.c_contiguous:
+                raise ValueError("encode_jpeg expects a contiguous (H, W) or (H, W, 3) uint8 array")
+            ch = 1 if img.ndim == 2 else 3
+            hh, ww, stride, ptr = img.shape[0], img.shape[1], img.shape[1] * ch, img.ctypes.data
+        else:
+            hh, ww, stride, ch = img
+        return JpegSource(ptr, hh, ww, stride, int(bool(rgb)), int(quality), JPEG_GRAY if ch == 1 else int(subsampling),
+                          int(restart_blocks))
+
+    def _encode_call(self, fn, srcs, guess: int):
+        n = len(srcs)
+        arr = (JpegSource * n)(*srcs)
+        offs, lens = np.zeros(n, np.uintp), np.zeros(n, np.uintp)
+        total = C.c_size_t()
+        out = np.empty(max(int(guess), 1), np.uint8)
+        rc = fn(self._p, n, arr, _ptr(out), out.size, _ptr(offs), _ptr(lens), C.byref(total))
+        if rc == -1 and total.value > out.size:       # sizes are exact once the passes before the scatter have run: once more, with room
+            out = np.empty(total.value, np.uint8)
+            rc = fn(self._p, n, arr, _ptr(out), out.size, _ptr(offs), _ptr(lens), C.byref(total))
+        self._check(rc)
+        return [out[int(o):int(o) + int(k)].tobytes() for o, k in zip(offs, lens)]
+
+    def encode_jpegs(self, images, quality=75, subsampling=2, restart_blocks=0, rgb=False):
+        """A list of (H, W, 3) BGR (rgb=True: RGB) or (H, W) gray uint8 images of any sizes -> a list of JPEG files, encoded in
+        one device pass (dfd_encode_jpeg_batch); each file's bytes equal Pillow's `save(quality=, subsampling=, optimize=False)`.
+        quality / subsampling / restart_blocks / rgb: one value for all, or a list with one per image."""
+        imgs = [np.ascontiguousarray(a) for a in images]
+        n = len(imgs)
+        if n == 0:
+            return []
+        per = [v if isinstance(v, (list, tuple)) else [v] * n for v in (quality, subsampling, restart_blocks, rgb)]
+        srcs = [self._jpeg_source(a, per[0][i], per[1][i], per[2][i], per[3][i]) for i, a in enumerate(imgs)]
+        return self._encode_call(self._lib.dfd_encode_jpeg_batch, srcs, sum(a.size // 2 + 4096 for a in imgs))
+
+    def encode_jpeg(self, img, quality=75, subsampling=2, restart_blocks=0, rgb=False) -> bytes:
+        """One image -> the bytes of its JPEG file (see encode_jpegs)."""
+        return self.encode_jpegs([img], quality, subsampling, restart_blocks, rgb)[0]
+
+    def encode_jpegs_device(self, sources, quality=75, subsampling=2, restart_blocks=0, rgb=False):
+        """encode_jpegs for images already in HBM: sources = [(device address, height, width, stride in bytes, channels 1 or 3)];
+        only the JPEG bytes cross to the host (dfd_encode_jpeg_device)."""
+        n = len(sources)
+        if n == 0:
+            return []
+        per = [v if isinstance(v, (list, tuple)) else [v] * n for v in (quality, subsampling, restart_blocks, rgb)]
+        srcs = [self._jpeg_source(tuple(int(v) for v in s[1:]), per[0][i], per[1][i], per[2][i], per[3][i], ptr=int(s[0]))
+                for i, s in enumerate(sources)]
+        return self._encode_call(self._lib.dfd_encode_jpeg_device, srcs, sum(s[1] * s[2] * s[4] // 2 + 4096 for s in sources))
 
     def jpeg_decode_counts(self):
         """(frames of batch calls entropy-decoded on the device, frames decoded by the host decoder)"""

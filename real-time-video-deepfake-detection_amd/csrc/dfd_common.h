@@ -156,6 +156,8 @@ struct dfd_handle {
     int jpeg_rounds = 16;                // rounds of that decoder's fixed-point iteration (option "jpeg_rounds", 2 .. 32; converged rounds cost ~nothing)
     int jpeg_chunk_bytes = 512;          // bytes of de-stuffed scan per lane of that decoder (option "jpeg_chunk_bytes", >= 256, % 4)
     unsigned long long jpeg_frames_device = 0, jpeg_frames_host = 0;   // frames of batch calls decoded there / by the host decoder
+    dfd::DevBuf jpeg_enc[6];             // dfd_encode_jpeg*: staged sources, tables + descriptors, coefficients, scan arrays,
+                                         // the unstuffed bit buffer, the packed files (jpeg_encode.hip)
     dfd::DevBuf tap_buf;                 // fp32 staging for taps of bf16 buffers
     std::map<const float*, unsigned short*> wsplit;   // fp32 weight tensor -> its three-plane bf16 split
     dfd::S6Table* gemm = nullptr;        // split-GEMM tile per shape (measured by dfd_warmup, heuristic otherwise)

@@ -286,11 +286,12 @@ class DeepfakeDetector:
             log.warning("face analysis error: %s", e)
             return None, None, None
 
-    def explain_face(self, face_region):
+    def explain_face(self, face_region, as_jpeg=False):
         """Where in the face the classifier saw a fake: {'fake_probability' (as `analyze_face` without TTA: same
         calibration and small-face heuristic), 'heatmap' (224,224) float32 Grad-CAM map of the head conv in [0,1],
         'overlay' (224,224,3) BGR uint8 (show_cam_on_image on the classifier input)}, or None when the MTCNN stage
-        finds no face.  The maps are in the 224x224 classifier frame of the (MTCNN-aligned) face."""
+        finds no face.  The maps are in the 224x224 classifier frame of the (MTCNN-aligned) face.  `as_jpeg`: also
+        'overlay_jpeg', the overlay as a JPEG file encoded on the device at cv2.imwrite's defaults (quality 95, 4:2:0)."""
         face = np.ascontiguousarray(face_region)
         if face.ndim != 3 or face.shape[2] != 3 or face.shape[0] < 1 or face.shape[1] < 1:
             return None
@@ -300,7 +301,11 @@ class DeepfakeDetector:
         p = self._finish_face(logits[0, 0], h, w)
         if p is None:
             return None
-        return {'fake_probability': p, 'heatmap': heat[0], 'overlay': overlay[0]}
+        res = {'fake_probability': p, 'heatmap': heat[0], 'overlay': overlay[0]}
+        if as_jpeg:
+            with self._lock:
+                res['overlay_jpeg'] = self.handle.encode_jpeg(overlay[0], quality=95, subsampling=2)
+        return res
 
     def _open_stream(self):
         """before a fused call: a sized analyzer's stream holds its analysis size on this detector's handle (a no-op

@@ -81,10 +81,9 @@ class MTCNN:
         """Per image a (3, S, S) float RGB tensor (``keep_all``: (n, 3, S, S)), 0..255 or standardised with
         ``post_process`` (torch when importable, else numpy), or None; a list of those for a list of images.  With
         ``return_prob`` also the probability (``keep_all``: an array of them; [None] / None where no face passes)."""
-        if save_path is not None:
-            raise ValueError("save_path is not supported")
         batch = self._is_batch(img)
-        if not batch and self._is_reference_call():          # the reference's construction: its own entry point
+        paths = self._save_paths(save_path, img, batch)
+        if paths is None and not batch and self._is_reference_call():   # the reference's construction: its own entry point
             face, box = self.handle.mtcnn_align(self._as_bgr(img))
             face = None if face is None else self._tensor(face)
             return (face, None if box is None else float(box[4])) if return_prob else face
@@ -103,11 +102,46 @@ class MTCNN:
             else:
                 faces.append(self._tensor(crops[0]))
                 probs.append(float(rows[0, 4]))
+        if paths is not None:
+            self._save(res, paths)
         if not batch:
             faces, probs = faces[0], probs[0]
         return (faces, probs) if return_prob else faces
 
     __call__ = forward
+
+    @staticmethod
+    def _save_paths(save_path, img, batch):
+        """None, or one path per image (the package takes a string for one image, a list of strings for a list)"""
+        if save_path is None:
+            return None
+        paths = list(save_path) if isinstance(save_path, (list, tuple)) else [save_path]
+        if len(paths) != (len(img) if batch else 1):
+            raise ValueError("save_path: one path per image")
+        for p in paths:
+            if not isinstance(p, str) or not p.lower().endswith((".jpg", ".jpeg")):
+                raise ValueError(f"save_path {p!r}: only .jpg / .jpeg files are written")
+        return paths
+
+    def _save(self, res, paths):
+        """The package's `save_img` of every crop: the uint8 RGB crop before `post_process`, as Pillow's default JPEG
+        (quality 75, 4:2:0), face 0 at `path`, face k at `name_<k + 1>.ext`.  The crops of the whole call are encoded
+        in one device pass; the files' bytes equal `PIL.Image.fromarray(crop).save(path)`."""
+        import os
+
+        crops, names = [], []
+        for (rows, _lm, faces), path in zip(res, paths):
+            stem, ext = os.path.splitext(path)
+            for k in range(len(rows) if self.keep_all else min(1, len(rows))):
+                f = faces[k]
+                if self.post_process:
+                    f = f * 128.0 + 127.5                   # fixed_image_standardization, undone exactly (float32)
+                crops.append(np.ascontiguousarray(f.transpose(1, 2, 0)).astype(np.uint8))
+                names.append(path if k == 0 else f"{stem}_{k + 1}{ext}")
+        for name, data in zip(names, self.handle.encode_jpegs(crops, quality=75, subsampling=2, rgb=True)):
+            os.makedirs(os.path.dirname(name) or ".", exist_ok=True)
+            with open(name, "wb") as fh:
+                fh.write(data)
 
     def detect(self, img, landmarks: bool = False):
         """(boxes (n, 4) float32, probs (n,)[, points (n, 5, 2)]) of every face that passes the cascade, by descending
@@ -165,9 +199,7 @@ class MTCNN:
     def extract(self, img, batch_boxes, save_path=None):
         """The package's ``extract``: the crops of ``forward`` for this object's configuration (the boxes are found again
         on the device in the same pass that crops them; ``batch_boxes`` only says where there is none)."""
-        if save_path is not None:
-            raise ValueError("save_path is not supported")
-        faces = self.forward(img)
+        faces = self.forward(img, save_path=save_path)
         if self._is_batch(img):
             return [None if b is None else f for f, b in zip(faces, batch_boxes)]
         return None if batch_boxes is None else faces
