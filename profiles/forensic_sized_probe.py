@@ -1,4 +1,4 @@
-"""Milliseconds per frame of the general forensic chain (csrc/forensic_sized_kernels.hip) at n = 16 frames for
+"""Milliseconds per frame of the general forensic chain (csrc/forensic_kernels.hip, run-time edge) at n = 16 frames for
 S in 128, 256, 512, 1024, and of the specialised 256x256 chain in the same run (DESIGN sections 4f / 5).
 
 What is timed: one `forensic_tap_sized(..., "stats")` call (full mode) between HIP events on the handle's stream - the

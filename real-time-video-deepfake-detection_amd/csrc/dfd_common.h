@@ -200,8 +200,8 @@ int color_tables_init(dfd_handle* h);
 
 // stages that work on a frame already resident in HBM (forensic_api / ssd_api / imgproc_api)
 // the analyzer for the fused single-frame entries: the stream at the analysis size and on the chain it holds - the general
-// chain (forensic_sized_kernels.hip) for a stream that was opened (dfd_forensics_open) or holds another size than 256,
-// the 256x256 kernels otherwise.  One host path (forensic_api.hip forensics_chain_run) serves both, and dfd_forensics /
+// chain (forensic_kernels.hip with a run-time edge) for a stream that was opened (dfd_forensics_open) or holds another size
+// than 256, the 256x256 chain (the same kernels with the edge a constant) otherwise.  One host path (forensic_api.hip forensics_chain_run) serves both, and dfd_forensics /
 // dfd_forensics_sized with them.
 int forensics_stream_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev, int hh, int ww, int stride, int full,
                          double* scores_out, double* prob_out);

@@ -1,6 +1,7 @@
 // C ABI of the forensic analyzer: device statistics -> the reference's threshold scoring (forensic_score.h; reference
-// frame_analysis.py:58-389), with the per-stream temporal state kept here.  The 256x256 kernels and the general chain
-// at any edge S share ONE host path: a ForensicChain says which launcher, carve and table a call uses.
+// frame_analysis.py:58-389), with the per-stream temporal state kept here.  The 256x256 chain and the general chain at
+// any edge S are two instantiations of one set of kernels (forensic_kernels.hip) behind ONE host path: a ForensicChain
+// holds the geometry, work memory and table of one of them.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -8,7 +9,6 @@
 
 #include "dfd_common.h"
 #include "forensic_kernels.h"
-#include "forensic_sized_kernels.h"
 
 using namespace dfd;
 
@@ -20,14 +20,13 @@ struct ForensicStream : ForensicTemporal {
     bool general = false;          // opened (dfd_forensics_open): the fused entries run it on the general chain, at 256 too
 };
 
-// one chain's device resources: the 256x256 kernels (forensic_kernels.hip, G.general = false) or the general chain at
-// one analysis edge (forensic_sized_kernels.hip)
+// one chain's device resources: the 256x256 chain (G.general = false) or the general chain at one analysis edge
 struct ForensicChain {
     ForensicGeometry G;
     DevBuf work, tap_store;        // work: carved into `buf` for `cap` frames; tap_store: spectrum, logmag, edges of the test tap
     int cap = 0;
     ForensicBuffers buf{};
-    float2* table = nullptr;       // exp(-2 pi i j / S): S entries on the general chain, the first S / 2 on the 256x256 kernels
+    float2* table = nullptr;       // exp(-2 pi i j / S): S entries on the general chain, the first S / 2 on the 256x256 chain
     double* diff_part = nullptr;   // G.npart partial sums of the single-frame difference
 };
 
@@ -35,15 +34,15 @@ constexpr int FIXED_EDGE = 256;
 
 struct ForensicState {
     std::map<int, ForensicStream> streams;
-    // keyed by (general, S): the 256x256 kernels and a general chain at 256 differ in table length and in f32_means
+    // keyed by (general, S): the 256x256 chain and a general chain at 256 differ in spectrum, table length and f32_means
     std::map<std::pair<bool, int>, ForensicChain> chains;
     DevBuf pair_idx, pair_part;    // dfd_forensic_signals_device: predecessor indices, [n][256] partial sums
     double* host_res = nullptr;    // pinned: statistics of a batch that ran on the second stream (forensics_batch_begin)
     size_t host_res_cap = 0;
-    DevBuf frame_desc, prev_tab, copy_tab;   // forensics_streams_run: FrameDesc [n], predecessor planes [n], write-backs
-    DevBuf sized_gray, sized_part;           // ... its frames on the general chain: their gray planes, kept for the whole call
-                                             // (a predecessor may sit in an earlier chunk), and their per-row partial sums
-    DevBuf sized_diff_tab, sized_copy_tab;   // ... SizedDiffRow per such frame, SizedPlaneCopy per such stream
+    DevBuf frame_desc, diff_tab, copy_tab;   // forensics_streams_run: FrameDesc and DiffRow per frame, PlaneCopy per stream
+    DevBuf stream_part;                      // ... every frame's per-row partial sums of the difference
+    DevBuf sized_gray;                       // ... the gray planes of its frames on the general chain, kept for the whole call
+                                             // (a predecessor may sit in an earlier chunk)
     std::map<int, std::vector<void*>> free_planes;   // stored planes of released streams by analysis edge, reused by the
                                                      // next new stream of that edge
 };
@@ -58,30 +57,13 @@ void forensic_destroy(dfd_handle* h) {
 
 namespace {
 
-// ---- what differs between the two chains on the host: table length, bytes per frame + carve, launchers
+// the table's length is what differs between the two chains on the host: the FFT reads half of it
 size_t chain_table_entries(const ForensicGeometry& G) { return (size_t)(G.general ? G.S : G.S / 2); }
-
-size_t chain_bytes_per_frame(const ForensicGeometry& G) {
-    return G.general ? forensic_sized_bytes_per_frame(G.S) : forensic_bytes_per_frame();
-}
-
-void chain_carve(const ForensicGeometry& G, void* base, int n, ForensicBuffers* out) {
-    if (G.general) forensic_sized_carve(base, G.S, n, out);
-    else forensic_carve(base, n, out);
-}
 
 // B: the chain's own buffers, or a copy with some of them elsewhere (forensics_streams_run)
 hipError_t chain_launch(const ForensicChain& C, const ForensicBuffers& B, int n, bool full, const ColorTables& T, hipStream_t s,
                         int gray_only = 0, ForensicStart start = FROM_RS, const ForensicTaps* taps = nullptr) {
-    if (C.G.general) return launch_forensics_sized(B, C.G.S, n, full, T, C.table, s, start, taps);
-    launch_forensics(B, n, full, T, C.table, s, gray_only, start, taps);
-    return hipSuccess;
-}
-
-// frame 0 of the chain's buffers against `prev` -> C.diff_part
-void chain_absdiff(const ForensicChain& C, const uint8_t* prev, hipStream_t s) {
-    if (C.G.general) launch_absdiff_sized(C.buf.gray, prev, C.diff_part, C.G.S, s);
-    else launch_absdiff(C.buf.gray, prev, C.diff_part, s);
+    return launch_forensics(B, C.G.general, C.G.S, n, full, T, C.table, s, gray_only, start, taps);
 }
 
 // the chain (general, S) with work memory for `frames` frames; creates the handle's forensic state and the chain's table
@@ -92,11 +74,11 @@ int chain_reserve(dfd_handle* h, bool general, int S, int frames, ForensicChain*
     if (!C.table) {
         C.G.S = S;
         C.G.npix = (double)S * (double)S;
-        C.G.nblk = sized_blocks(S);
+        C.G.nblk = edge_blocks(S);
         C.G.npart = S;
         C.G.f32_means = C.G.general = general;
         std::vector<float2> tw(S);
-        forensic_sized_table(S, tw.data());
+        forensic_table(S, tw.data());
         const size_t bytes = chain_table_entries(C.G) * sizeof(float2);
         void *t = nullptr, *d = nullptr;
         DFD_HIP_TRY(h, hipMalloc(&t, bytes));
@@ -108,9 +90,9 @@ int chain_reserve(dfd_handle* h, bool general, int S, int frames, ForensicChain*
         C.table = static_cast<float2*>(t);
     }
     if (frames > C.cap) {
-        const int rc = ensure(h, &C.work, chain_bytes_per_frame(C.G) * frames + 65536);
+        const int rc = ensure(h, &C.work, forensic_bytes_per_frame(S) * frames + 65536);
         if (rc) return rc;
-        chain_carve(C.G, C.work.p, frames, &C.buf);
+        forensic_carve(C.work.p, S, frames, &C.buf);
         C.cap = frames;
     }
     *out = &C;
@@ -164,7 +146,7 @@ int forensics_chain_run(dfd_handle* h, int stream_id, bool general, int size, co
 
     launch_resize_bgr(frame_dev, 1, hh, ww, stride, 0, B.rs, size, size, h->stream);
     DFD_HIP_TRY(h, chain_launch(*C, B, 1, full != 0, h->color, h->stream));
-    if (S.has_prev) chain_absdiff(*C, (const uint8_t*)S.prev_gray, h->stream);
+    if (S.has_prev) launch_absdiff(B.gray, (const uint8_t*)S.prev_gray, C->diff_part, size, h->stream);
     double st[FORENSIC_STATS];
     std::vector<double> blk((size_t)2 * G.nblk + G.npart);
     double *noise = blk.data(), *ela = noise + G.nblk, *dpart = ela + G.nblk;
@@ -285,49 +267,49 @@ int forensics_stream_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev,
 }
 
 // n frames of any streams and sizes in one pass (POST /analyze_batch, the session pool).  The frames are grouped by the
-// chain and analysis edge of their stream: the frames of 256x256 streams nobody opened run on the 256x256 kernels as one
+// chain and analysis edge of their stream: the frames of 256x256 streams nobody opened run on the 256x256 chain as one
 // launch set, the frames of every other edge S on the general chain - one ragged resize to S x S and one launch set per
 // chunk of the group, a chunk being as many frames as fit the handle's work-memory budget (forensic_chunk_bytes; the
 // kernels treat every frame on its own, so the split changes no result).  The gray planes of the general chain are kept
-// for the whole call outside the chunk memory, so that ONE launch differences every such frame, whatever its edge and
+// for the whole call outside the chunk memory, so that ONE launch differences every frame, whatever its chain, edge and
 // chunk, against its predecessor - the previous frame of its stream in this call, else the stream's stored plane - and
-// ONE launch writes every stream's last gray plane back to its stored slot (the 256x256 group: its own two launches, as
-// before).  Then the host half is replayed frame by frame in call order: every stream's temporal deque, frame counter
-// and stored plane end exactly where single calls in order would leave them.  No stream's state moves before the wait.
+// ONE launch writes every stream's last gray plane back to its stored slot.  Then the host half is replayed frame by
+// frame in call order: every stream's temporal deque, frame counter and stored plane end exactly where single calls in
+// order would leave them.  No stream's state moves before the wait.
 int forensics_streams_run(dfd_handle* h, const uint8_t* frames_dev, const FrameDesc* fd, int n, const int* stream_ids,
                           const int* full, double* scores_out, double* prob_out) {
     if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
     int rc = DFD_OK;
     if (!h->forensic) h->forensic = new ForensicState();
     ForensicState& F = *h->forensic;
-    std::vector<int> plain;                                          // frames on the 256x256 kernels, in call order
+    std::vector<int> plain;                                          // frames on the 256x256 chain, in call order
     std::map<int, std::vector<int>> groups;                          // analysis edge -> frames on the general chain
-    std::vector<int> edge(n);                                        // 0: 256x256 kernels
+    std::vector<int> edge(n);                                        // every frame's analysis edge
+    std::vector<bool> general(n);
     size_t gray_bytes = 0, part_doubles = 0;
-    int n_sized = 0, max_S = 0;
+    int max_S = 0;
     for (int f = 0; f < n; ++f) {
         ForensicStream& S = F.streams[stream_ids[f]];
-        edge[f] = on_general_chain(S) ? S.size : 0;
-        if ((rc = stream_plane(h, S, edge[f] ? edge[f] : FIXED_EDGE))) return rc;
-        if (!edge[f]) { plain.push_back(f); continue; }
-        groups[edge[f]].push_back(f);
-        gray_bytes += (size_t)edge[f] * edge[f];
+        general[f] = on_general_chain(S);
+        edge[f] = general[f] ? S.size : FIXED_EDGE;
+        if ((rc = stream_plane(h, S, edge[f]))) return rc;
         part_doubles += (size_t)edge[f];
         max_S = std::max(max_S, edge[f]);
-        ++n_sized;
+        if (!general[f]) { plain.push_back(f); continue; }
+        groups[edge[f]].push_back(f);
+        gray_bytes += (size_t)edge[f] * edge[f];
     }
     const int n_plain = (int)plain.size();
     ForensicChain* P = nullptr;                                      // the 256x256 group's chain: all of its frames at once
     if (n_plain && (rc = chain_reserve(h, false, FIXED_EDGE, n_plain, &P))) return rc;
-    const size_t plain_parts = n_plain ? (size_t)n_plain * P->G.npart : 0;
     std::vector<const ForensicChain*> chain(n, P);                   // every frame's chain
     if ((rc = ensure(h, &F.sized_gray, gray_bytes))) return rc;
-    if ((rc = ensure(h, &F.sized_part, part_doubles * 8))) return rc;
+    if ((rc = ensure(h, &F.stream_part, part_doubles * 8))) return rc;
     struct Chunk { int S, first, count; ForensicChain* Z; bool full; };   // first: index into the group's frames
     std::vector<Chunk> chunks;
     for (const auto& g : groups) {
         const int S = g.first, cnt = (int)g.second.size();
-        const size_t fit = h->forensic_chunk_bytes / forensic_sized_bytes_per_frame(S);
+        const size_t fit = h->forensic_chunk_bytes / forensic_bytes_per_frame(S);
         const int per = (int)std::min<size_t>(std::max<size_t>(fit, 1), (size_t)cnt);
         ForensicChain* Z = nullptr;
         if ((rc = chain_reserve(h, true, S, per, &Z))) return rc;
@@ -338,25 +320,22 @@ int forensics_streams_run(dfd_handle* h, const uint8_t* frames_dev, const FrameD
         }
         for (int c0 = 0; c0 < cnt; c0 += per) chunks.push_back(Chunk{S, c0, std::min(per, cnt - c0), Z, any});
     }
-    // where every frame's gray plane and partial sums are, and its slot in the descriptor table (group by group)
+    // where every frame's gray plane is, and its slot in the descriptor and difference tables (the 256x256 group, then
+    // group by group): the 256x256 group's planes in its chain's own buffers, the others in the call's store
     std::vector<const uint8_t*> gray(n);
-    std::vector<size_t> part_at(n, 0);
-    std::vector<FrameDesc> desc;
-    desc.reserve(n);
+    std::vector<int> order;
+    order.reserve(n);
     for (int j = 0; j < n_plain; ++j) {
-        gray[plain[j]] = P->buf.gray + (size_t)j * P->G.S * P->G.S;
-        part_at[plain[j]] = (size_t)j * P->G.npart;
-        desc.push_back(fd[plain[j]]);
+        gray[plain[j]] = P->buf.gray + (size_t)j * FIXED_EDGE * FIXED_EDGE;
+        order.push_back(plain[j]);
     }
     {
-        size_t go = 0, po = 0;
+        size_t go = 0;
         for (const auto& g : groups)
             for (int f : g.second) {
                 gray[f] = (const uint8_t*)F.sized_gray.p + go;
-                part_at[f] = po;
                 go += (size_t)g.first * g.first;
-                po += (size_t)g.first;
-                desc.push_back(fd[f]);
+                order.push_back(f);
             }
     }
     bool any_full = false;                                           // of the 256x256 group
@@ -367,32 +346,31 @@ int forensics_streams_run(dfd_handle* h, const uint8_t* frames_dev, const FrameD
         auto it = last.find(stream_ids[f]);
         pred[f] = it != last.end() ? gray[it->second] : S.has_prev ? (const uint8_t*)S.prev_gray : nullptr;
         last[stream_ids[f]] = f;
-        if (!edge[f]) any_full = any_full || full[f] != 0;
+        if (!general[f]) any_full = any_full || full[f] != 0;
     }
-    std::vector<const uint8_t*> prev(n_plain);
-    for (int j = 0; j < n_plain; ++j) prev[j] = pred[plain[j]];
-    std::vector<SizedDiffRow> rows;
-    for (const auto& g : groups)
-        for (int f : g.second) rows.push_back(SizedDiffRow{gray[f], pred[f], (double*)F.sized_part.p + part_at[f], g.first, 0});
+    std::vector<FrameDesc> desc;
+    std::vector<DiffRow> rows;
+    std::vector<size_t> part_at(n, 0);                               // every frame's partial sums in F.stream_part
+    size_t po = 0;
+    for (int f : order) {
+        desc.push_back(fd[f]);
+        rows.push_back(DiffRow{gray[f], pred[f], (double*)F.stream_part.p + po, edge[f], 0});
+        part_at[f] = po;
+        po += (size_t)edge[f];
+    }
     std::vector<PlaneCopy> back;
-    std::vector<SizedPlaneCopy> back_sized;
-    for (const auto& kv : last) {
-        uint8_t* dst = (uint8_t*)F.streams[kv.first].prev_gray;
-        const int S = edge[kv.second];
-        if (S) back_sized.push_back(SizedPlaneCopy{gray[kv.second], dst, (size_t)S * S});
-        else back.push_back(PlaneCopy{gray[kv.second], dst});
-    }
+    for (const auto& kv : last)
+        back.push_back(PlaneCopy{gray[kv.second], (uint8_t*)F.streams[kv.first].prev_gray, (size_t)edge[kv.second] * edge[kv.second]});
     if ((rc = ensure(h, &F.frame_desc, (size_t)n * sizeof(FrameDesc)))) return rc;
-    if ((rc = ensure(h, &F.prev_tab, (size_t)n_plain * sizeof(void*)))) return rc;
+    if ((rc = ensure(h, &F.diff_tab, rows.size() * sizeof(DiffRow)))) return rc;
     if ((rc = ensure(h, &F.copy_tab, back.size() * sizeof(PlaneCopy)))) return rc;
-    if ((rc = ensure(h, &F.pair_part, plain_parts * 8))) return rc;
-    if ((rc = ensure(h, &F.sized_diff_tab, rows.size() * sizeof(SizedDiffRow)))) return rc;
-    if ((rc = ensure(h, &F.sized_copy_tab, back_sized.size() * sizeof(SizedPlaneCopy)))) return rc;
     if ((rc = mailbox_h2d(h, F.frame_desc.p, desc.data(), (size_t)n * sizeof(FrameDesc)))) return rc;
+    if ((rc = mailbox_h2d(h, F.diff_tab.p, rows.data(), rows.size() * sizeof(DiffRow)))) return rc;
+    if ((rc = mailbox_h2d(h, F.copy_tab.p, back.data(), back.size() * sizeof(PlaneCopy)))) return rc;
     const FrameDesc* desc_dev = (const FrameDesc*)F.frame_desc.p;
     // per frame: where the host finds its statistics once the stream has been waited for.  One launch set's statistics
     // (count frames from `frames`, in the order of its buffers B) through the mailbox; blocks: the block arrays too.
-    std::vector<const double*> st(n, nullptr), noise(n, nullptr), ela(n, nullptr), part(n, nullptr);
+    std::vector<const double*> st(n, nullptr), noise(n, nullptr), ela(n, nullptr);
     auto fetch_stats = [&](const ForensicBuffers& B, const ForensicGeometry& G, const int* frames, int count, bool blocks) {
         const double* a = (const double*)mailbox_d2h(h, B.stats, (size_t)count * FORENSIC_STATS * 8);
         const double* b = blocks ? (const double*)mailbox_d2h(h, B.stats_noise, (size_t)count * G.nblk * 8) : nullptr;
@@ -408,47 +386,30 @@ int forensics_streams_run(dfd_handle* h, const uint8_t* frames_dev, const FrameD
         }
         return true;
     };
-    // the partial sums of every frame of one kind (on the general chain or not), `doubles` of them at src
-    auto fetch_parts = [&](const void* src, size_t doubles, bool general) {
-        const double* d = (const double*)mailbox_d2h(h, src, doubles * 8);
-        if (!d) return false;
-        for (int f = 0; f < n; ++f)
-            if ((edge[f] != 0) == general) part[f] = d + part_at[f];
-        return true;
-    };
     if (n_plain) {
-        if ((rc = mailbox_h2d(h, F.prev_tab.p, prev.data(), (size_t)n_plain * sizeof(void*)))) return rc;
-        if ((rc = mailbox_h2d(h, F.copy_tab.p, back.data(), back.size() * sizeof(PlaneCopy)))) return rc;
         launch_resize_bgr_ragged(frames_dev, desc_dev, n_plain, P->buf.rs, P->G.S, P->G.S, h->stream);
         DFD_HIP_TRY(h, chain_launch(*P, P->buf, n_plain, any_full, h->color, h->stream));
-        launch_absdiff_prev(P->buf.gray, (const uint8_t* const*)F.prev_tab.p, (double*)F.pair_part.p, n_plain, h->stream);
-        launch_copy_planes((const PlaneCopy*)F.copy_tab.p, (int)back.size(), h->stream);
-        if (!fetch_stats(P->buf, P->G, plain.data(), n_plain, true) ||
-            !fetch_parts(F.pair_part.p, plain_parts, false))
-            return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
+        if (!fetch_stats(P->buf, P->G, plain.data(), n_plain, true)) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
     }
-    if (n_sized) {
-        if ((rc = mailbox_h2d(h, F.sized_diff_tab.p, rows.data(), rows.size() * sizeof(SizedDiffRow)))) return rc;
-        if ((rc = mailbox_h2d(h, F.sized_copy_tab.p, back_sized.data(), back_sized.size() * sizeof(SizedPlaneCopy)))) return rc;
-        int at = n_plain;                                            // the chunk's first slot of the descriptor table
-        for (const Chunk& c : chunks) {
-            const int* frames = groups[c.S].data() + c.first;
-            ForensicBuffers B = c.Z->buf;                            // the chunk's work memory, its gray planes in the call's store
-            B.gray = const_cast<uint8_t*>(gray[frames[0]]);
-            launch_resize_bgr_ragged(frames_dev, desc_dev + at, c.count, B.rs, c.S, c.S, h->stream);
-            DFD_HIP_TRY(h, chain_launch(*c.Z, B, c.count, c.full, h->color, h->stream));
-            if (!fetch_stats(B, c.Z->G, frames, c.count, c.full)) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
-            at += c.count;
-        }
-        launch_absdiff_prev_sized((const SizedDiffRow*)F.sized_diff_tab.p, n_sized, max_S, h->stream);
-        launch_copy_planes_sized((const SizedPlaneCopy*)F.sized_copy_tab.p, (int)back_sized.size(), max_S, h->stream);
-        if (!fetch_parts(F.sized_part.p, part_doubles, true)) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
+    int at = n_plain;                                                // the chunk's first slot of the descriptor table
+    for (const Chunk& c : chunks) {
+        const int* frames = groups[c.S].data() + c.first;
+        ForensicBuffers B = c.Z->buf;                                // the chunk's work memory, its gray planes in the call's store
+        B.gray = const_cast<uint8_t*>(gray[frames[0]]);
+        launch_resize_bgr_ragged(frames_dev, desc_dev + at, c.count, B.rs, c.S, c.S, h->stream);
+        DFD_HIP_TRY(h, chain_launch(*c.Z, B, c.count, c.full, h->color, h->stream));
+        if (!fetch_stats(B, c.Z->G, frames, c.count, c.full)) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
+        at += c.count;
     }
+    launch_absdiff_prev((const DiffRow*)F.diff_tab.p, n, max_S, h->stream);
+    launch_copy_planes((const PlaneCopy*)F.copy_tab.p, (int)back.size(), max_S, h->stream);
+    const double* parts = (const double*)mailbox_d2h(h, F.stream_part.p, part_doubles * 8);
+    if (!parts) return fail(h, DFD_ERR_HIP, "forensics: mailbox allocation failed");
     DFD_HIP_TRY(h, stream_sync(h));
     DFD_HIP_TRY(h, hipGetLastError());
     for (int f = 0; f < n; ++f) {
         double sc[6], ex[10], md, tcv;
-        prob_out[f] = score_frame(F.streams[stream_ids[f]], chain[f]->G, st[f], noise[f], ela[f], full[f] != 0, part[f], sc, ex, &md, &tcv);
+        prob_out[f] = score_frame(F.streams[stream_ids[f]], chain[f]->G, st[f], noise[f], ela[f], full[f] != 0, parts + part_at[f], sc, ex, &md, &tcv);
         for (int i = 0; i < 6; ++i) scores_out[(size_t)f * 6 + i] = sc[i];
     }
     return DFD_OK;
@@ -546,8 +507,8 @@ int dfd_forensics_sized(dfd_handle* h, int stream_id, const uint8_t* bgr, int hh
     if (!h) return DFD_ERR_ARG;
     if (!bgr || !scores_out || !prob_out || hh <= 0 || ww <= 0 || stride < ww * 3)
         return fail(h, DFD_ERR_ARG, "forensics_sized: bad pointer or geometry");
-    if (!sized_ok(size))
-        return fail(h, DFD_ERR_ARG, "forensics_sized: analysis size %d is not a multiple of 16 in %d..%d", size, SIZED_MIN, SIZED_MAX);
+    if (!edge_ok(size))
+        return fail(h, DFD_ERR_ARG, "forensics_sized: analysis size %d is not a multiple of 16 in %d..%d", size, EDGE_MIN, EDGE_MAX);
     if (!h->has_color) return fail(h, DFD_ERR_STATE, "forensics needs the colour tables (blob packed without luts)");
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     int rc = stream_size_check(h, stream_id, size);
@@ -622,8 +583,8 @@ int dfd_forensic_tap_sized(dfd_handle* h, const uint8_t* frames, int n, int size
     if (!h) return DFD_ERR_ARG;
     if (!start || !name || !out || !bytes || n <= 0 || n > 16 || frame < -1 || frame >= n)
         return fail(h, DFD_ERR_ARG, "forensic_tap_sized: bad pointer, frame index or frame count (1..16)");
-    if (!sized_ok(size))
-        return fail(h, DFD_ERR_ARG, "forensic_tap_sized: analysis size %d is not a multiple of 16 in %d..%d", size, SIZED_MIN, SIZED_MAX);
+    if (!edge_ok(size))
+        return fail(h, DFD_ERR_ARG, "forensic_tap_sized: analysis size %d is not a multiple of 16 in %d..%d", size, EDGE_MIN, EDGE_MAX);
     return forensic_tap_run(h, "forensic_tap_sized", true, size, frames, n, full, start, start_data, name, frame, out, capacity, bytes);
 }
 
@@ -668,8 +629,8 @@ int dfd_forensics_state(dfd_handle* h, int stream_id, int* frame_count, int* n_d
 
 int dfd_forensics_open(dfd_handle* h, int stream_id, int size) {
     if (!h) return DFD_ERR_ARG;
-    if (!sized_ok(size))
-        return fail(h, DFD_ERR_ARG, "forensics_open: analysis size %d is not a multiple of 16 in %d..%d", size, SIZED_MIN, SIZED_MAX);
+    if (!edge_ok(size))
+        return fail(h, DFD_ERR_ARG, "forensics_open: analysis size %d is not a multiple of 16 in %d..%d", size, EDGE_MIN, EDGE_MAX);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     int rc = stream_size_check(h, stream_id, size);                  // another size already: refused, nothing changes
     if (rc) return rc;

@@ -1,5 +1,5 @@
-// __device__ helpers that the 256x256 kernels (forensic_kernels.hip) and the general chain (forensic_sized_kernels.hip)
-// share word for word.  Internal to those two files; all __forceinline__, so moving them here changes no instruction.
+// __device__ helpers of the forensic kernels (forensic_kernels.hip) that do not depend on the analysis edge.  Internal to
+// that file; all __forceinline__.
 #pragma once
 #include <hip/hip_runtime.h>
 

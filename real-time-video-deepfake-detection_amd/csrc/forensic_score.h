@@ -23,7 +23,7 @@ struct ForensicGeometry {
     int npart = 256;         // partial sums of a frame's difference against its predecessor (one per image row)
     bool f32_means = false;  // the reference's np.mean of float32 values, divided in float32 (the general chain); in double
                              // otherwise (the 256x256 chain, where both quotients are exact)
-    bool general = false;    // the chain of forensic_sized_kernels.hip
+    bool general = false;    // the run-time-edge instantiation of forensic_kernels.hip (DFT spectrum)
 };
 
 // what crosses the frames of a stream (frame_analysis.py:34-37)

@@ -1,4 +1,4 @@
-// libjpeg's integer arithmetic, restated once for the ELA round trip (forensic_kernels.hip, reference
+// libjpeg's integer arithmetic, restated once for the ELA round trip (forensic_kernels.hip at every analysis size, reference
 // frame_analysis.py:233-236) and the JPEG decoder at the HTTP edge (jpeg_decode.hip, reference backend_server.py:139-145):
 // RGB <-> YCbCr (jccolor.c / jdcolor.c, 16-bit fixed point), jfdctint.c / jidctint.c ("islow") passes.
 #pragma once

@@ -1,5 +1,5 @@
-"""Test helper (CPU): per-stage references for the forensic kernels (csrc/forensic_kernels.hip), the inputs the stage
-tests run them on, and the bars they are held to.  Everything is built from oracle/imgproc_ref.py and
+"""Test helper (CPU): per-stage references for the forensic kernels at 256x256 (csrc/forensic_kernels.hip, the
+compile-time edge), the inputs the stage tests run them on, and the bars they are held to.  Everything is built from oracle/imgproc_ref.py and
 oracle/jpeg_ref.py; the integer stages are exact, the noise residual is the oracle's fp32 blur bit for bit, and the FFT
 has two references: numpy's float64 fft2 and `fft_mirror`, the kernel's radix-2 butterflies restated in numpy float32
 (every operation a single IEEE add or multiply, as the kernels are compiled without contraction).

@@ -1,4 +1,4 @@
-"""Test helper (CPU): size-generic per-stage references for the general forensic chain (csrc/forensic_sized_kernels.hip),
+"""Test helper (CPU): size-generic per-stage references for the general forensic chain (csrc/forensic_kernels.hip, run-time edge),
 built only on oracle/imgproc_ref.py, oracle/jpeg_ref.py and numpy float64, the fixture frames of the sized tests and the
 condition they must meet.  Buffer layouts are the device's: see dfd_forensic_tap_sized in include/dfd_hip.h."""
 import functools

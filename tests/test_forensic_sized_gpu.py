@@ -1,4 +1,4 @@
-"""GPU: the general forensic chain (dfd_forensics_sized / dfd_forensic_tap_sized, csrc/forensic_sized_kernels.hip) against
+"""GPU: the general forensic chain (dfd_forensics_sized / dfd_forensic_tap_sized: csrc/forensic_kernels.hip, run-time edge) against
 oracle/forensics_ref.ForensicsRef((S, S)) and the size-generic stage references of tests/forensic_sized_oracle.py.
 Bars are those of tests/test_forensics_gpu.py and tests/test_forensic_stages_gpu.py."""
 import numpy as np
@@ -183,6 +183,28 @@ def test_size_256_equals_the_specialised_chain(b0_handle):
                 assert (np.isnan(want) and np.isnan(have)) or abs(have - want) <= Z.STAT_RTOL * max(1.0, abs(want)), (name, k, have, want)
     b0_handle.forensics_release(944)
     b0_handle.forensics_release(945)
+
+
+def test_the_two_instantiations_are_one_function_outside_the_spectrum(b0_handle):
+    """The 256x256 chain and the general chain are two instantiations of one set of kernel bodies (compile-time edge
+    256 / run-time edge): at S = 256 every buffer that does not pass through the spectrum - a radix-2 FFT on one, a
+    dense DFT on the other - is the same bytes, frame slot by frame slot."""
+    frames = O256.fixture_frames()
+    stack = np.stack([frames[k] for k in ("noisy", "face_vga", "gradient")])
+    assert stack.shape == (3, 256, 256, 3)
+    for t in ("gray", "grad", "lap_part", "map", "edges", "edge_count", "jy", "jcb", "jcr", "stats_ela", "stats_noise", "hsv_part",
+              "hue_bits"):
+        a = b0_handle.forensic_tap(stack, t)
+        b = b0_handle.forensic_tap_sized(stack, 256, t)
+        assert a.dtype == b.dtype and a.shape == b.shape, (t, a.dtype, b.dtype, a.shape, b.shape)
+        assert a.tobytes() == b.tobytes(), t
+    a = b0_handle.forensic_tap(stack, "stats")
+    b = b0_handle.forensic_tap_sized(stack, 256, "stats")
+    assert a.shape == b.shape == (3, 9)
+    assert a[:, 4:].tobytes() == b[:, 4:].tobytes()               # lap_var, edge count, sat / val std, hues
+    for f in range(3):
+        for j in range(4):                                           # freq low, mid, high, mid std: through the spectrum
+            assert abs(b[f, j] - a[f, j]) <= Z.STAT_RTOL * max(1.0, abs(a[f, j])), (f, j, a[f, j], b[f, j])
 
 
 # ------------------------------------------------------------------------------------------------ 5: batch slots
