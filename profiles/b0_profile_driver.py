@@ -3,7 +3,7 @@
     DFD_TILE_CACHE=gpurun_out/tiles.txt python profiles/b0_profile_driver.py          # un-profiled: measures + saves tiles
     rocprofv3 --pmc ... -- python3 profiles/b0_profile_driver.py                       # profiled: loads them, no tuning launches
 
-env: B0_STEPS (default 4), B0_BF16=1 (bf16 activation storage), DFD_MB_VARIANT_* as usual."""
+env: B0_STEPS (default 4), B0_BF16=1 (bf16 activation storage), DFD_FUSE_* as usual."""
 import os
 import sys
 

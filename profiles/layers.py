@@ -1,6 +1,6 @@
 """Per-launch times of one classifier step at batch 256 (HIP events on the library's stream, every step instrumented)
 and the logit error of the first 8 crops against the CPU oracle.  `python profiles/layers.py [bf16] [planes]`;
-environment switches of the kernels (DFD_MB_VARIANT_*, DFD_DW_ROWS7, ...) apply."""
+the library's environment switches (DFD_FUSE_*, DFD_S6_*, ...) apply."""
 import os
 import sys
 

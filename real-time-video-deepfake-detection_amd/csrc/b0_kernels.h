@@ -93,13 +93,13 @@ bool launch_mbconv_front(const XT* Xin, int Cin, const unsigned short* We3, int 
 // Block 1's front half with block 0's projection folded into its prologue (option "fuse_proj0", fp32 only): Xdw0 is block
 // 0's depthwise output [n][H][H][32], gate0 its squeeze-excite gate [n][32], Wp3 / plane / Kp / bp the three bf16 planes
 // of its projection weights [16][32] and the bias; the rest as launch_mbconv_front.  The block input it computes per halo
-// pixel has the bits the separate projection launch stores.  `supported`: the shape is block 1's and no kernel experiment
-// is selected for it; the launcher returns false otherwise.
+// pixel has the bits the separate projection launch stores.  `supported`: the shape is block 1's; the launcher
+// returns false otherwise.
 bool mbconv_proj0_supported(int H, int C, int k, int stride, int Cin, int C0);
 bool launch_mbconv_front_proj0(const float* Xdw0, const float* gate0, const unsigned short* Wp3, int plane, int Kp, const float* bp,
                                const float* Wef, const float* be, const float* Wd, const float* bd, float* Y, float* P, int n,
                                int H, int C, int k, int stride, int Cin, int pad_lo, int* tiles, hipStream_t s);
-// largest pool-tile count of the fused variants, -1: none.  late: also the whole-image launches of blocks 6-15
+// pool-tile count of the fused launch (the larger of the fp32 and bf16 kernels'), -1: none.  late: also the whole-image launches of blocks 6-15
 // (mbconv_late_kernel, option "fuse_late")
 int mbconv_tiles(int H, int C, int k, int stride, int Cin, bool late = false);
 

@@ -1,22 +1,31 @@
-// EfficientNet-B0 kernels for gfx950 (CDNA4, wave64).  NHWC fp32 activations.
+// EfficientNet-B0 kernels for gfx950 (CDNA4, wave64).  NHWC activations, stored as fp32 or bf16 (XT).
 //
-//  stem_kernel      3x3 s2 conv from the NCHW network input, folded BN + swish
-//  pw_kernel<NT>    1x1 conv = GEMM on v_mfma_f32_16x16x4_f32 (exact fp32 FMA chain),
-//                   W tile double-buffered in LDS, X fragments straight to VGPRs,
-//                   epilogue: bias (+swish|relu) (+residual); optional SE gate folded
-//                   into the X operand load
-//  dw_kernel<...>   depthwise kxk conv: halo tile staged in LDS with 16-byte coalesced
-//                   channel vectors, folded BN + swish, per-tile channel sums for the
-//                   squeeze-excite pool reduced with wave shuffles
-//  se_kernel        pool finish + two tiny FCs -> per-(image,channel) gate
-//  avgpool_kernel   global average pool of the head conv output
+//  stem_kernel         3x3 s2 conv from the NCHW network input, folded BN + swish
+//  pw_kernel<NT>       1x1 conv = GEMM on v_mfma_f32_16x16x4_f32 (exact fp32 FMA chain),
+//                      W tile double-buffered in LDS, X fragments straight to VGPRs,
+//                      epilogue: bias (+swish|relu) (+residual); optional SE gate folded
+//                      into the X operand load; CONV: implicit-GEMM k x k conv (SSD detector)
+//  dw_kernel<...>      depthwise kxk conv: halo tile staged in LDS with 16-byte coalesced
+//                      channel vectors, folded BN + swish, per-tile channel sums for the
+//                      squeeze-excite pool reduced with wave shuffles
+//  dw_rows7_kernel     the 7 x 7 stride-1 depthwise layers: an output row per thread, no LDS tile
+//  stem_dw_kernel      stem + block 0's depthwise conv in one launch (the stem activation stays in LDS)
+//  mbconv_kernel       1x1 expand + depthwise in one launch, first generation: fp32 blocks 1, 3, 5
+//                      (PROJ0: block 0's projection folded into block 1's launch)
+//  mbconv2_kernel      the same, second generation: fp32 blocks 2, 4 and bf16 blocks 1-5
+//  mbconv_late_kernel  the same for blocks 6-10 and 12-15: whole 14 x 14 / 7 x 7 images per block
+//  se_kernel           pool finish + two tiny FCs -> per-(image,channel) gate
+//  avgpool_kernel      global average pool of the head conv output
+//
+// DFD_MB_TABLE names the one mbconv instance that runs each of blocks 1-5; the variants that were measured
+// against them and lost are recorded in DESIGN.md section 5.
 //
 // Semantics follow reference model.py:63-72 (forward = EfficientNet-B0 + MLP head); the
 // arithmetic of each layer is checked against oracle/b0_ref.py by tests/test_b0_gpu.py.
 #include "b0_kernels.h"
 #include "kernel_util.h"
 
-#include <cstdlib>
+#include <type_traits>
 
 namespace dfd {
 
@@ -315,9 +324,8 @@ static PwTile pick_tile(int M, int N) {
     const int tiles = (N + 15) / 16;
     PwTile best{2, 1, 0, 0};
     double best_score = -1.0;
-    static const double fill_target = getenv("DFD_PW_FILL") ? atof(getenv("DFD_PW_FILL")) : 768.0;
-    static const double one_nb_bonus = getenv("DFD_PW_BONUS") ? atof(getenv("DFD_PW_BONUS")) : 1.15;
-    static const int mt_max = getenv("DFD_PW_MTMAX") ? atoi(getenv("DFD_PW_MTMAX")) : 2;
+    constexpr double fill_target = 768.0, one_nb_bonus = 1.15;
+    constexpr int mt_max = 2;
     for (int mt = 1; mt <= mt_max; ++mt)
         for (int nt = 1; nt <= 10; ++nt) {
             const int mb = (M + 64 * mt - 1) / (64 * mt), nb = (tiles + nt - 1) / nt;
@@ -331,14 +339,14 @@ static PwTile pick_tile(int M, int N) {
     return best;
 }
 
-#define DFD_PW_NT_CASES(OP) OP(1) OP(2) OP(3) OP(4) OP(5) OP(6) OP(7) OP(8) OP(9) OP(10)
+#define DFD_POINTWISE_NT_CASES(OP) OP(1) OP(2) OP(3) OP(4) OP(5) OP(6) OP(7) OP(8) OP(9) OP(10)
 
 template <bool CONV, bool GATE>
 static void pw_dispatch(const PwTile& t, const float* X, const float* W, const float* bias, const float* gate,
                         const float* R, float* Y, int M, int K, int N, int HW, int act, const ConvGeom& g,
                         int res_first, hipStream_t s) {
     const int grid = ((t.mblocks + 7) / 8) * 8 * t.nblocks;
-#define DFD_PW_CASE(NTV)                                                                                             \
+#define DFD_POINTWISE_CASE(NTV)                                                                                      \
     case NTV:                                                                                                        \
         if (t.mt == 2)                                                                                               \
             hipLaunchKernelGGL((pw_kernel<NTV, CONV, 2, GATE>), dim3(grid), dim3(256), 0, s, X, W, bias, gate, R, Y, \
@@ -347,8 +355,8 @@ static void pw_dispatch(const PwTile& t, const float* X, const float* W, const f
             hipLaunchKernelGGL((pw_kernel<NTV, CONV, 1, GATE>), dim3(grid), dim3(256), 0, s, X, W, bias, gate, R, Y, \
                                M, K, N, HW, act, t.mblocks, t.nblocks, g, res_first);                                \
         break;
-    switch (t.nt) { DFD_PW_NT_CASES(DFD_PW_CASE) }
-#undef DFD_PW_CASE
+    switch (t.nt) { DFD_POINTWISE_NT_CASES(DFD_POINTWISE_CASE) }
+#undef DFD_POINTWISE_CASE
 }
 
 void launch_pointwise(const float* X, const float* W, const float* bias, const float* gate,
@@ -419,7 +427,7 @@ struct DwShape {
 // depthwise conv of the LDS tile + folded BN + swish + store + per-tile SE partial sums.
 // Ends with a barrier-protected write of P; callers that reuse tile/wl/red afterwards must
 // __syncthreads() first.
-template <int K, int S, int CB, int TH, int TW, int RP, int SWZ = 0, typename XT = float, int ABL = 0, int NT = 256>
+template <int K, int S, int CB, int TH, int TW, int RP, int SWZ = 0, typename XT = float, int NT = 256>
 __device__ __forceinline__ void dw_compute(const v4f* tile, const v4f* wl, v4f* red,
                                            const v4f bv, XT* __restrict__ Y,
                                            float* __restrict__ P, int n, int Ho, int C, int c0, int ty0,
@@ -460,8 +468,8 @@ __device__ __forceinline__ void dw_compute(const v4f* tile, const v4f* wl, v4f* 
             for (int p = 0; p < RP; ++p) {
                 const int gx = tx0 + ox0 + p;
                 if (gy < Ho && gx < Ho) {
-                    const v4f v = ABL == 4 ? acc[p] : swish4(acc[p]);
-                    if (ABL != 5) st4(yb + ((size_t)gy * Ho + gx) * C, v);
+                    const v4f v = swish4(acc[p]);
+                    st4(yb + ((size_t)gy * Ho + gx) * C, v);
                     psum += v;
                 }
             }
@@ -775,8 +783,7 @@ __global__ __launch_bounds__(256, ((S == 1 && (((TH - 1) * S + K) * ((TW - 1) * 
 //   * (round 3) the activation ring is refilled AFTER the tile's MFMAs have issued: refilled before them the slot's
 //     old value had to be copied aside, the copy landed in the loop latch behind `s_waitcnt vmcnt(0)` (ISA), and every
 //     4-tile iteration drained the whole ring - an s_memtime trace put 64 % of block 4's time in that loop.
-template <int K, int S, int CB, int TH, int TW, int RP, int NK, typename XT, int ABL = 0, int NT = 256, bool INS = false,
-          int CI = 0, int MINB = (NT == 256 ? 2 : 4), bool SKEW = false>
+template <int K, int S, int CB, int TH, int TW, int RP, int NK, typename XT, int NT, bool INS, int CI, int MINB>
 __global__ __launch_bounds__(NT, MINB) void mbconv2_kernel(const XT* __restrict__ X,
                                                       const unsigned short* __restrict__ We3, int plane, int Kp,
                                                       const float* __restrict__ Wef,
@@ -911,9 +918,8 @@ __global__ __launch_bounds__(NT, MINB) void mbconv2_kernel(const XT* __restrict_
     }
     MB_TP(1);
 
-    // SKEW (off): the MFMAs of tile t are issued, then the epilogue of tile t - 1 (swish + LDS store) while they sit in the
-    // matrix pipe.  Measured again in round 3, after the wait-count fixes: block 2 186.6 vs 185.4 us, block 4 119.3 vs
-    // 117.6, bf16 the same - within noise in both directions; four waves per SIMD already fill each other's gaps.
+    // Running the epilogue of tile t - 1 behind the MFMAs of tile t (a one-tile skew) was measured and tied: four waves
+    // per SIMD already fill each other's gaps.
     auto epilogue = [&](int mt, const v4f (&acc)[NTB]) {
         int pr, pcol;
         tile_rc(mt * 16 + j, pr, pcol);
@@ -923,13 +929,9 @@ __global__ __launch_bounds__(NT, MINB) void mbconv2_kernel(const XT* __restrict_
         if (mt < nmt && mt * 16 + j < (INS ? npin : NPX)) {
 #pragma unroll
             for (int nt = 0; nt < NTB; ++nt)
-                tile[tile_unit<CG, SWZ>(p, nt * 4 + q)] = inside ? (ABL == 2 ? acc[nt] : swish4(acc[nt])) : (v4f){0.f, 0.f, 0.f, 0.f};
+                tile[tile_unit<CG, SWZ>(p, nt * 4 + q)] = inside ? swish4(acc[nt]) : (v4f){0.f, 0.f, 0.f, 0.f};
         }
     };
-    v4f prev[NTB];
-#pragma unroll
-    for (int nt = 0; nt < NTB; ++nt) prev[nt] = (v4f){0.f, 0.f, 0.f, 0.f};
-    int prev_mt = nmt;                                              // no tile yet: the first epilogue stores nothing
 #pragma unroll 1
     for (int it0 = 0; it0 < NIT; it0 += RD) {
 #pragma unroll
@@ -942,10 +944,7 @@ __global__ __launch_bounds__(NT, MINB) void mbconv2_kernel(const XT* __restrict_
         for (int nt = 0; nt < NTB; ++nt) acc[nt] = bex[nt];
         v4f acc1 = (v4f){0.f, 0.f, 0.f, 0.f};
         // the NTB accumulators interleaved (independent chains)
-        if constexpr (ABL == 1) {
-#pragma unroll
-            for (int nt = 0; nt < NTB; ++nt) acc[nt] = xa.raw[0] + wfr[nt][0];
-        } else if constexpr (ESZ == 4) {
+        if constexpr (ESZ == 4) {
             if constexpr (NTB == 1) {
                 // one 16-channel tile: the K steps alternate between two accumulators (two independent MFMA chains instead
                 // of one dependent chain of NM), folded once at the end
@@ -975,28 +974,15 @@ __global__ __launch_bounds__(NT, MINB) void mbconv2_kernel(const XT* __restrict_
             const int mn = mt + NW * RD;
             load_tile(mn < nmt ? mn : nmt - 1, ring[d]);
         }
-        if constexpr (SKEW) {
-            epilogue(prev_mt, prev);                                // the previous tile, while this tile's MFMAs run
-            if constexpr (ESZ == 4 && NTB == 1) acc[0] += acc1;
-#pragma unroll
-            for (int nt = 0; nt < NTB; ++nt) prev[nt] = acc[nt];
-            prev_mt = mt;
-        } else {
-            if constexpr (ESZ == 4 && NTB == 1) acc[0] += acc1;
-            epilogue(mt, acc);
-        }
+        if constexpr (ESZ == 4 && NTB == 1) acc[0] += acc1;
+        epilogue(mt, acc);
       }
     }
-    if constexpr (SKEW) epilogue(prev_mt, prev);
     if (tid < K * K * CG) wl[tid] = wl_v;
     MB_TP(4);
     __syncthreads();
     MB_TP(5);
-    if constexpr (ABL == 3) {
-        if (tid < CG) stg4(P + ((size_t)n * tiles_sp + t) * C + c0 + 4 * tid, tile[tid] + bv);
-    } else {
-        dw_compute<K, S, CB, TH, TW, RP, SWZ, XT, ABL, NT>(tile, wl, red, bv, Y, P, n, Ho, C, c0, ty0, tx0, t, tiles_sp);
-    }
+    dw_compute<K, S, CB, TH, TW, RP, SWZ, XT, NT>(tile, wl, red, bv, Y, P, n, Ho, C, c0, ty0, tx0, t, tiles_sp);
     MB_TP(6);
 #ifdef MB_TRACE
     if (H == MB_TRACE_H && S == MB_TRACE_S && bid.x == 5 && bid.n == 3 && threadIdx.x == 0) g_mb_trace[255] = mtp;
@@ -1252,19 +1238,19 @@ __global__ __launch_bounds__(256) void dw_rows7_kernel(const XT* __restrict__ X,
 template <int K, typename XT>
 static void dw_rows7_launch(const XT* X, const float* W, const float* b, XT* Y, float* P, int n, int C, int* tiles, hipStream_t s) {
     *tiles = 1;
-    if constexpr (sizeof(XT) == 2) {
-        static const int cpt = getenv("DFD_ROWS7_CPT") ? atoi(getenv("DFD_ROWS7_CPT")) : (K == 5 ? 4 : 8);
-        if (cpt == 8) {
-            const int groups = (C + 255) / 256;
-            hipLaunchKernelGGL((dw_rows7_kernel<K, 8, XT>), dim3(groups * n), dim3(256), 0, s, X, W, b, Y, P, C, groups);
-            return;
-        }
-    }
-    const int groups = (C + 127) / 128;
-    hipLaunchKernelGGL((dw_rows7_kernel<K, 4, XT>), dim3(groups * n), dim3(256), 0, s, X, W, b, Y, P, C, groups);
+    // bf16 at k = 3: 8 channels = 16 bytes per load; at k = 5 that form needs a rolled kernel-row loop, which exposes
+    // each row's load latency
+    constexpr int CPT = sizeof(XT) == 2 && K == 3 ? 8 : 4;
+    const int groups = (C + 32 * CPT - 1) / (32 * CPT);
+    hipLaunchKernelGGL((dw_rows7_kernel<K, CPT, XT>), dim3(groups * n), dim3(256), 0, s, X, W, b, Y, P, C, groups);
 }
 
-// tile shapes per B0 depthwise layer class: (k, stride, H_in, C) -> <K,S,CB,TH,TW,RP>
+// the layers dw_rows7_kernel runs (blocks 12-15): one pool tile per image
+static bool dw_rows7_shape(int H, int C, int k, int stride) {
+    return H == 7 && stride == 1 && C % 8 == 0 && (k == 3 || k == 5);
+}
+
+// tile shapes per B0 depthwise layer class: (k, stride, H_in, C) -> <K,S,CB,TH,TW,RP>; blocks 12-15: dw_rows7_shape
 #define DFD_DW_TABLE(OP)                                  \
     OP(3, 1, 112, 32, 32, 8, 16, 4)   /* block 0      */  \
     OP(3, 2, 112, 96, 32, 8, 8, 2)    /* block 1      */  \
@@ -1275,9 +1261,7 @@ static void dw_rows7_launch(const XT* X, const float* W, const float* b, XT* Y, 
     OP(3, 1, 14, 480, 32, 14, 14, 7)  /* blocks 6,7   */  \
     OP(5, 1, 14, 480, 32, 14, 14, 7)  /* block 8      */  \
     OP(5, 1, 14, 672, 32, 14, 14, 7)  /* blocks 9,10  */  \
-    OP(5, 2, 14, 672, 32, 7, 7, 1)    /* block 11     */  \
-    OP(5, 1, 7, 1152, 32, 7, 7, 1)    /* blocks 12-14 */  \
-    OP(3, 1, 7, 1152, 32, 7, 7, 1)    /* block 15     */
+    OP(5, 2, 14, 672, 32, 7, 7, 1)    /* block 11     */
 
 template <typename XT>
 bool launch_depthwise(const XT* X, const float* W, const float* bias, XT* Y, float* P, int n,
@@ -1287,9 +1271,8 @@ bool launch_depthwise(const XT* X, const float* W, const float* bias, XT* Y, flo
         dw_launch<KK, SS, CB, TH, TW, RP, XT>(X, W, bias, Y, P, n, H, C, pad_lo, tiles, s); \
         return true;                                                                   \
     }
-    // 7 x 7 stride-1 layers: the row-per-thread kernel (DFD_DW_ROWS7=0: the LDS-tile kernel, for A/B runs)
-    static const bool rows7 = !(getenv("DFD_DW_ROWS7") && atoi(getenv("DFD_DW_ROWS7")) == 0);
-    if (rows7 && H == 7 && stride == 1 && C % 8 == 0 && (k == 3 || k == 5) && pad_lo == (k - 1) / 2) {
+    if (dw_rows7_shape(H, C, k, stride)) {
+        if (pad_lo != (k - 1) / 2) return false;                 // the kernel's padding is TF-SAME at stride 1
         if (k == 3) dw_rows7_launch<3, XT>(X, W, bias, Y, P, n, C, tiles, s);
         else dw_rows7_launch<5, XT>(X, W, bias, Y, P, n, C, tiles, s);
         return true;
@@ -1477,7 +1460,7 @@ __global__ __launch_bounds__(256, 2) void mbconv_late_kernel(const XT* __restric
     MB_TP(5);
     if constexpr (HW == 14) {
         constexpr int RP = S == 1 ? 7 : 1;
-        dw_compute<K, S, CB, TH, TH, RP, SWZ, XT, 0, 256>(tile, wl, red, bv, Y, P, grp, TH, C, c0, 0, 0, 0, 1);
+        dw_compute<K, S, CB, TH, TH, RP, SWZ, XT, 256>(tile, wl, red, bv, Y, P, grp, TH, C, c0, 0, 0, 0, 1);
     } else {
         // an output row (7 pixels x 4 channels) per thread: 4 images x 7 rows x 8 channel quads = 224 threads
         constexpr int H = 7, PAD = (K - 1) / 2;
@@ -1552,85 +1535,43 @@ static void mb_late_launch(const XT* X, const unsigned short* We3, int plane, in
     OP(5, 1, 7, 1152, 192)     \
     OP(3, 1, 7, 1152, 192)
 
-// expand (1x1 + BN + swish) fused into the depthwise kernel; only the five large-spatial MBConv
-// blocks (1..5) are instantiated: there the expanded tensor dominates HBM traffic and C_in <= 48.
-// (k, stride, H, C, Cin) -> <K,S,CB,TH,TW,RP, NK = ceil(Cin/32)>; several variants per block, the first is the
-// default, DFD_MB_VARIANT_<H>_<stride>=i selects another (kernel experiments; the tile counts follow).
-#define DFD_MB2_TABLE(OP)                                  \
-    OP(0, 3, 2, 112, 96, 16, 32, 8, 8, 2, 1)               \
-    OP(1, 3, 2, 112, 96, 16, 16, 8, 8, 2, 1)               \
-    OP(0, 3, 1, 56, 144, 24, 16, 14, 28, 7, 1)             \
-    OP(1, 3, 1, 56, 144, 24, 16, 14, 28, 2, 1)             \
-    OP(0, 5, 2, 56, 144, 24, 16, 7, 14, 7, 1)              \
-    OP(1, 5, 2, 56, 144, 24, 16, 7, 14, 2, 1)              \
-    OP(0, 5, 1, 28, 240, 40, 16, 28, 28, 7, 2)             \
-    OP(1, 5, 1, 28, 240, 40, 16, 14, 28, 4, 2)             \
-    OP(0, 3, 2, 28, 240, 40, 16, 7, 14, 2, 2)              \
-    OP(1, 3, 2, 28, 240, 40, 16, 7, 14, 7, 2)
+// The fused expand + depthwise launch of blocks 1-5, where the expanded tensor dominates HBM traffic and C_in <= 48: one
+// row per activation type and block names the ONE kernel instance that runs it.  launch_mbconv_front, the "fuse_proj0"
+// launch and mbconv_tiles all read this table.  Key: (XT, k, stride, H, C, Cin).  Row kinds:
+//   G1   mbconv_kernel  <K,S,CB,TH,TW,RP, KC = ceil(Cin/16), NSUB = channel chunks per block> (fp32 activations only)
+//   G1P  a G1 row whose instance is also built with PROJ0 (block 1: launch_mbconv_front_proj0 runs that one)
+//   G2   mbconv2_kernel <K,S,CB,TH,TW,RP, NK = ceil(Cin/32), NT, INS, MINB>
+// Chosen by measurement at batch 256 (round 3, us per launch; what lost is in DESIGN.md section 5):
+//   fp32  block 1: first generation 237 (second: 261)
+//         block 2: second generation with INS 190 (without: 203)
+//         block 3: first generation 158 (second: 178-254)
+//         block 4: second generation, 14 x 28 tiles at four blocks per CU (100 VGPRs, ring of 3) 115 (three blocks: 121;
+//                  whole image: 132)
+//         block 5: first generation, 3 channel chunks per block 69 (1 chunk: 78; second generation: 93)
+//   bf16  the second generation everywhere: 203 / 127 / 117 / 83 / 51; block 4 takes the whole image with 512 threads
+//         (14 x 28 tiles, 256 threads: 92)
+#define DFD_MB_TABLE(G1P, G1, G2)                                                     \
+    G1P(float, 3, 2, 112, 96, 16, 32, 8, 8, 2, 1, 3)                  /* block 1 */   \
+    G2(float, 3, 1, 56, 144, 24, 16, 14, 28, 7, 1, 256, true, 2)      /* block 2 */   \
+    G1(float, 5, 2, 56, 144, 24, 16, 7, 14, 2, 2, 3)                  /* block 3 */   \
+    G2(float, 5, 1, 28, 240, 40, 16, 14, 28, 7, 2, 256, false, 4)     /* block 4 */   \
+    G1(float, 3, 2, 28, 240, 40, 16, 7, 14, 2, 3, 3)                  /* block 5 */   \
+    G2(bf16_t, 3, 2, 112, 96, 16, 32, 8, 8, 2, 1, 256, false, 2)      /* block 1 */   \
+    G2(bf16_t, 3, 1, 56, 144, 24, 16, 14, 28, 7, 1, 256, false, 2)    /* block 2 */   \
+    G2(bf16_t, 5, 2, 56, 144, 24, 16, 7, 14, 7, 1, 256, false, 2)     /* block 3 */   \
+    G2(bf16_t, 5, 1, 28, 240, 40, 16, 28, 28, 7, 2, 512, false, 4)    /* block 4 */   \
+    G2(bf16_t, 3, 2, 28, 240, 40, 16, 7, 14, 2, 2, 256, false, 2)     /* block 5 */
+#define DFD_MB_SKIP(...)
+#define DFD_MB_KEY(KK, SS, HH, CC, CI) (k == KK && stride == SS && H == HH && C == CC && Cin == CI)
 
-// round 3 variants: + NT (threads per block), INS (pixel tiles enumerate only in-image pixels)
-#define DFD_MB3_TABLE(OP)                                          \
-    OP(6, 3, 1, 56, 144, 24, 16, 14, 28, 7, 1, 256, true)          \
-    OP(7, 3, 1, 56, 144, 24, 16, 28, 28, 7, 1, 512, true)          \
-    OP(8, 3, 1, 56, 144, 24, 16, 14, 28, 7, 1, 512, true)          \
-    OP(10, 3, 1, 56, 144, 24, 16, 28, 28, 7, 1, 512, false)        \
-    OP(6, 5, 2, 56, 144, 24, 16, 7, 14, 7, 1, 256, true)           \
-    OP(7, 5, 2, 56, 144, 24, 16, 14, 14, 7, 1, 512, true)          \
-    OP(8, 5, 2, 56, 144, 24, 16, 14, 14, 2, 1, 512, true)          \
-    OP(6, 5, 1, 28, 240, 40, 16, 28, 28, 7, 2, 256, true)          \
-    OP(7, 5, 1, 28, 240, 40, 16, 28, 28, 7, 2, 512, false)         \
-    OP(8, 5, 1, 28, 240, 40, 16, 28, 28, 7, 2, 512, true)          \
-    OP(9, 5, 1, 28, 240, 40, 16, 14, 28, 7, 2, 256, true)          \
-    OP(10, 5, 1, 28, 240, 40, 16, 14, 28, 7, 2, 512, true)         \
-    OP(11, 5, 1, 28, 240, 40, 16, 14, 28, 7, 2, 512, false)        \
-    OP(12, 5, 1, 28, 240, 40, 16, 14, 28, 7, 2, 256, false)        \
-    OP(6, 3, 2, 28, 240, 40, 16, 7, 14, 2, 2, 256, true)           \
-    OP(7, 3, 2, 28, 240, 40, 16, 14, 14, 2, 2, 512, true)          \
-    OP(8, 3, 2, 28, 240, 40, 16, 14, 14, 7, 2, 512, true)          \
-    OP(9, 3, 2, 28, 240, 40, 16, 14, 14, 7, 2, 256, true)
-
-// first-generation instances still used with fp32 activations where they measure faster (blocks 1, 3, 5:
-// 248 / 183 / 85 us against 329 / 185 / 89 us of the second generation at batch 256; blocks 2 and 4 run the second
-// generation: 214 / 148 us against 263 / 164 us).  With bf16 activations the second generation wins everywhere
-// (229 / 128 / 124 / 99 / 53 us against 263 / 179 / 152 / 151 / 62 us).
-// (k, stride, H, C, Cin) -> <K,S,CB,TH,TW,RP, KC = ceil(Cin/16), NSUB = channel chunks per block>
-#define DFD_MB1_TABLE(OP)                               \
-    OP(-1, 3, 2, 112, 96, 16, 32, 8, 8, 2, 1, 3)        \
-    OP(-1, 5, 2, 56, 144, 24, 16, 7, 14, 2, 2, 3)       \
-    OP(-3, 5, 2, 56, 144, 24, 16, 7, 14, 2, 2, 9)       \
-    OP(-1, 3, 2, 28, 240, 40, 16, 7, 14, 2, 3, 1)       \
-    OP(-3, 3, 2, 28, 240, 40, 16, 7, 14, 2, 3, 3)       \
-    OP(-4, 3, 2, 28, 240, 40, 16, 7, 14, 2, 3, 5)       \
-    OP(-5, 3, 2, 28, 240, 40, 16, 7, 14, 7, 3, 1)       \
-    OP(-1, 5, 1, 28, 240, 40, 16, 14, 28, 7, 3, 3)      \
-    OP(-3, 5, 1, 28, 240, 40, 16, 14, 28, 7, 3, 5)      \
-    OP(-4, 5, 1, 28, 240, 40, 16, 7, 28, 7, 3, 5)       \
-    OP(-5, 5, 1, 28, 240, 40, 16, 14, 14, 7, 3, 5)      \
-    OP(-1, 3, 1, 56, 144, 24, 16, 14, 28, 7, 2, 3)      \
-    OP(-3, 3, 1, 56, 144, 24, 16, 14, 28, 7, 2, 9)      \
-    OP(-4, 3, 1, 56, 144, 24, 16, 14, 14, 7, 2, 9)
-
-// ablation builds of the default tiles of blocks 2 and 4 (variant 20 + ABL): where does the time go?
-//   1 no MFMAs, 2 no swish on the expanded tile, 3 no depthwise phase, 4 no swish after the depthwise conv, 5 no stores
-#define DFD_MB2_ABL(OP) OP(1) OP(2) OP(3) OP(4) OP(5)
-
-// DFD_MB_VARIANT_<H>_<stride>=i: kernel experiments (profiles/mb_variants.py); -1 = first generation where built
-static int mb_variant(int H, int stride) {
-    char name[48];
-    snprintf(name, sizeof name, "DFD_MB_VARIANT_%d_%d", H, stride);
-    const char* e = getenv(name);
-    return e ? atoi(e) : -2;
-}
-
-template <int K, int S, int CB, int TH, int TW, int RP, int NK, typename XT, int NT = 256, bool INS = false, int CI = 0,
-          int MINB = (NT == 256 ? 2 : 4), bool SKEW = false>
+template <int K, int S, int CB, int TH, int TW, int RP, int NK, typename XT, int NT, bool INS, int CI, int MINB>
 static void mb2_launch(const XT* X, int Cin, const unsigned short* We3, int plane, int Kp, const float* Wef, const float* be,
                        const float* W, const float* b, XT* Y, float* P, int n, int H, int C, int pad_lo, int* tiles, hipStream_t s) {
     const int Ho = (H + S - 1) / S;
     const int tx = (Ho + TW - 1) / TW, ty = (Ho + TH - 1) / TH;
     const int tiles_sp = tx * ty;
     *tiles = tiles_sp;
-    hipLaunchKernelGGL((mbconv2_kernel<K, S, CB, TH, TW, RP, NK, XT, 0, NT, INS, CI, MINB, SKEW>), dim3(tiles_sp * (C / CB) * n), dim3(NT), 0, s, X,
+    hipLaunchKernelGGL((mbconv2_kernel<K, S, CB, TH, TW, RP, NK, XT, NT, INS, CI, MINB>), dim3(tiles_sp * (C / CB) * n), dim3(NT), 0, s, X,
                        We3, plane, Kp, Wef, be, W, b, Y, P, H, Ho, C, Cin, pad_lo, tx, tiles_sp);
 }
 
@@ -1650,136 +1591,63 @@ bool launch_mbconv_front(const XT* Xin, int Cin, const unsigned short* We3, int 
 #undef DFD_MB_LATE_DISPATCH
         return false;
     }
-    int var = mb_variant(H, stride);
-    if (var == -2) {
-        // defaults by measurement at batch 256 (profiles/mb_variants.py, round 3, us fp32 / bf16):
-        //   block 1 (112, s2): first generation 237 (second: 261) / variant 0 203
-        //   block 2 (56, s1):  variant 6 (INS) 190 (variant 0: 203) / variant 0 127
-        //   block 3 (56, s2):  first generation 158 (second: 178-254) / variant 0 117
-        //   block 4 (28, s1):  variant 13 (14 x 28 tiles, four blocks per CU: 100 VGPRs, ring of 3) 115 (three blocks: 121;
-        //                      whole image: 132) / variant 7 (whole image, 512 threads) 83 (variant 0: 92)
-        //   block 5 (28, s2):  first generation, 3 channel chunks per block 69 (1 chunk: 78; second generation: 93) / variant 0 51
-        if (sizeof(XT) == 4) var = stride == 2 ? (H == 28 ? -3 : -1) : (H == 56 ? 6 : 13);
-        else var = (H == 28 && stride == 1) ? 7 : 0;
+    // a row is instantiated for its own activation type only
+#define DFD_MB_G1(TY, KK, SS, HH, CC, CI, CB, TH, TW, RP, KC, NSUB)                                                  \
+    if constexpr (std::is_same_v<XT, TY>) {                                                                         \
+        if (DFD_MB_KEY(KK, SS, HH, CC, CI)) {                                                                       \
+            mb_launch<KK, SS, CB, TH, TW, RP, KC, NSUB, XT, CI>(Xin, Cin, Wef, be, Wd, bd, Y, P, n, H, C, pad_lo, tiles, s); \
+            return true;                                                                                            \
+        }                                                                                                           \
     }
-    if constexpr (sizeof(XT) == 4) {
-        if (var <= -1) {
-#define DFD_MB1_DISPATCH(VV, KK, SS, HH, CC, CI, CB, TH, TW, RP, KC, NSUB)                                            \
-    if (var == VV && k == KK && stride == SS && H == HH && C == CC && Cin == CI) {                                  \
-        mb_launch<KK, SS, CB, TH, TW, RP, KC, NSUB, XT, CI>(Xin, Cin, Wef, be, Wd, bd, Y, P, n, H, C, pad_lo, tiles, s); \
-        return true;                                                                                                \
+#define DFD_MB_G2(TY, KK, SS, HH, CC, CI, CB, TH, TW, RP, NK, NT, INS, MINB)                                         \
+    if constexpr (std::is_same_v<XT, TY>) {                                                                         \
+        if (DFD_MB_KEY(KK, SS, HH, CC, CI)) {                                                                       \
+            mb2_launch<KK, SS, CB, TH, TW, RP, NK, XT, NT, INS, CI, MINB>(Xin, Cin, We3, plane, Kp, Wef, be, Wd, bd, Y, P, n, H, C, \
+                                                                          pad_lo, tiles, s);                        \
+            return true;                                                                                            \
+        }                                                                                                           \
     }
-            DFD_MB1_TABLE(DFD_MB1_DISPATCH)
-#undef DFD_MB1_DISPATCH
-        }
-    }
-    if (var < 0) var = 0;
-#define DFD_MB2_DISPATCH(VV, KK, SS, HH, CC, CI, CB, TH, TW, RP, NK)                                                 \
-    if (var == VV && k == KK && stride == SS && H == HH && C == CC && Cin == CI) {                                  \
-        mb2_launch<KK, SS, CB, TH, TW, RP, NK, XT, 256, false, CI>(Xin, Cin, We3, plane, Kp, Wef, be, Wd, bd, Y, P, n, H, C, pad_lo, tiles, s); \
-        return true;                                                                                                \
-    }
-    DFD_MB2_TABLE(DFD_MB2_DISPATCH)
-#undef DFD_MB2_DISPATCH
-#define DFD_MB3_DISPATCH(VV, KK, SS, HH, CC, CI, CB, TH, TW, RP, NK, NT, INS)                                       \
-    if (var == VV && k == KK && stride == SS && H == HH && C == CC && Cin == CI) {                                  \
-        mb2_launch<KK, SS, CB, TH, TW, RP, NK, XT, NT, INS, CI>(Xin, Cin, We3, plane, Kp, Wef, be, Wd, bd, Y, P, n, H, C, pad_lo, tiles, s); \
-        return true;                                                                                                \
-    }
-    DFD_MB3_TABLE(DFD_MB3_DISPATCH)
-#undef DFD_MB3_DISPATCH
-    // four blocks per CU (128 VGPRs, ring of 3): more waves in different phases on a SIMD
-    if (var == 13 && k == 5 && stride == 1 && H == 28 && C == 240 && Cin == 40) {
-        mb2_launch<5, 1, 16, 14, 28, 7, 2, XT, 256, false, 40, 4>(Xin, Cin, We3, plane, Kp, Wef, be, Wd, bd, Y, P, n, H, C, pad_lo, tiles, s);
-        return true;
-    }
-    if (var == 18 && k == 5 && stride == 1 && H == 28 && C == 240 && Cin == 40) {             // variant 13 with the one-tile skew
-        mb2_launch<5, 1, 16, 14, 28, 7, 2, XT, 256, false, 40, 4, true>(Xin, Cin, We3, plane, Kp, Wef, be, Wd, bd, Y, P, n, H, C, pad_lo, tiles, s);
-        return true;
-    }
-    if (var == 18 && k == 3 && stride == 1 && H == 56 && C == 144 && Cin == 24) {             // variant 6 with the one-tile skew
-        mb2_launch<3, 1, 16, 14, 28, 7, 1, XT, 256, true, 24, 2, true>(Xin, Cin, We3, plane, Kp, Wef, be, Wd, bd, Y, P, n, H, C, pad_lo, tiles, s);
-        return true;
-    }
-    if (var == 15 && k == 5 && stride == 1 && H == 28 && C == 240 && Cin == 40) {
-        mb2_launch<5, 1, 16, 14, 28, 7, 2, XT, 256, true, 40, 4>(Xin, Cin, We3, plane, Kp, Wef, be, Wd, bd, Y, P, n, H, C, pad_lo, tiles, s);
-        return true;
-    }
-    if (var == 16 && k == 5 && stride == 1 && H == 28 && C == 240 && Cin == 40) {
-        mb2_launch<5, 1, 16, 14, 28, 14, 2, XT, 256, false, 40, 4>(Xin, Cin, We3, plane, Kp, Wef, be, Wd, bd, Y, P, n, H, C, pad_lo, tiles, s);
-        return true;
-    }
-    if (var == 17 && k == 5 && stride == 1 && H == 28 && C == 240 && Cin == 40) {
-        mb2_launch<5, 1, 16, 14, 28, 4, 2, XT, 256, false, 40, 4>(Xin, Cin, We3, plane, Kp, Wef, be, Wd, bd, Y, P, n, H, C, pad_lo, tiles, s);
-        return true;
-    }
-    if (var == 14 && k == 5 && stride == 1 && H == 28 && C == 240 && Cin == 40) {
-        mb2_launch<5, 1, 16, 7, 28, 7, 2, XT, 256, false, 40, 4>(Xin, Cin, We3, plane, Kp, Wef, be, Wd, bd, Y, P, n, H, C, pad_lo, tiles, s);
-        return true;
-    }
-    if (var == 13 && k == 3 && stride == 1 && H == 56 && C == 144 && Cin == 24) {
-        mb2_launch<3, 1, 16, 14, 28, 7, 1, XT, 256, true, 24, 4>(Xin, Cin, We3, plane, Kp, Wef, be, Wd, bd, Y, P, n, H, C, pad_lo, tiles, s);
-        return true;
-    }
-#ifdef DFD_MB_ABLATION
-#define DFD_ABL_CASE(A)                                                                                              \
-    if (var == 20 + A && H == 56 && stride == 1) {                                                                  \
-        const int tx = 2, ty = 4;                                                                                   \
-        *tiles = tx * ty;                                                                                           \
-        hipLaunchKernelGGL((mbconv2_kernel<3, 1, 16, 14, 28, 7, 1, XT, A, 256, false, 24>), dim3(tx * ty * (C / 16) * n), dim3(256), 0, s, Xin, \
-                           We3, plane, Kp, Wef, be, Wd, bd, Y, P, H, 56, C, Cin, pad_lo, tx, tx * ty);              \
-        return true;                                                                                                \
-    }                                                                                                               \
-    if (var == 20 + A && H == 28 && stride == 1) {                                                                  \
-        *tiles = 1;                                                                                                 \
-        hipLaunchKernelGGL((mbconv2_kernel<5, 1, 16, 28, 28, 7, 2, XT, A, 256, false, 40>), dim3((C / 16) * n), dim3(256), 0, s, Xin,   \
-                           We3, plane, Kp, Wef, be, Wd, bd, Y, P, H, 28, C, Cin, pad_lo, 1, 1);                     \
-        return true;                                                                                                \
-    }
-    DFD_MB2_ABL(DFD_ABL_CASE)
-#undef DFD_ABL_CASE
-#endif
+    DFD_MB_TABLE(DFD_MB_G1, DFD_MB_G1, DFD_MB_G2)
+#undef DFD_MB_G2
+#undef DFD_MB_G1
     return false;
 }
-// Option "fuse_proj0": block 1's launch with block 0's projection folded in (mbconv_kernel, PROJ0).  Only the default
-// kernel of block 1 has the instance: with a DFD_MB_VARIANT_112_2 experiment selected the plan keeps the two launches.
+// Option "fuse_proj0": block 1's launch with block 0's projection folded in - the PROJ0 instance of the table's G1P row.
 bool mbconv_proj0_supported(int H, int C, int k, int stride, int Cin, int C0) {
-    return k == 3 && stride == 2 && H == 112 && C == 96 && Cin == 16 && C0 == 32 && mb_variant(H, stride) == -2;
+#define DFD_MB_P0(TY, KK, SS, HH, CC, CI, ...) \
+    if (DFD_MB_KEY(KK, SS, HH, CC, CI) && C0 == 32) return true;
+    DFD_MB_TABLE(DFD_MB_P0, DFD_MB_SKIP, DFD_MB_SKIP)
+#undef DFD_MB_P0
+    return false;
 }
 bool launch_mbconv_front_proj0(const float* Xdw0, const float* gate0, const unsigned short* Wp3, int plane, int Kp, const float* bp,
                                const float* Wef, const float* be, const float* Wd, const float* bd, float* Y, float* P, int n,
                                int H, int C, int k, int stride, int Cin, int pad_lo, int* tiles, hipStream_t s) {
-    if (!mbconv_proj0_supported(H, C, k, stride, Cin, 32)) return false;
     const Proj0Args<true> pj{gate0, Wp3, bp, plane, Kp};
-    mb_launch<3, 2, 32, 8, 8, 2, 1, 3, float, 16, true>(Xdw0, Cin, Wef, be, Wd, bd, Y, P, n, H, C, pad_lo, tiles, s, pj);   // block 1's row of DFD_MB1_TABLE
-    return true;
+#define DFD_MB_P0(TY, KK, SS, HH, CC, CI, CB, TH, TW, RP, KC, NSUB)                                                  \
+    if (DFD_MB_KEY(KK, SS, HH, CC, CI)) {                                                                           \
+        mb_launch<KK, SS, CB, TH, TW, RP, KC, NSUB, TY, CI, true>(Xdw0, Cin, Wef, be, Wd, bd, Y, P, n, H, C, pad_lo, tiles, s, pj); \
+        return true;                                                                                                \
+    }
+    DFD_MB_TABLE(DFD_MB_P0, DFD_MB_SKIP, DFD_MB_SKIP)
+#undef DFD_MB_P0
+    return false;
 }
 
 template bool launch_mbconv_front<float>(const float*, int, const unsigned short*, int, int, const float*, const float*, const float*, const float*, float*, float*, int, int, int, int, int, int, int*, hipStream_t, bool);
 template bool launch_mbconv_front<bf16_t>(const bf16_t*, int, const unsigned short*, int, int, const float*, const float*, const float*, const float*, bf16_t*, float*, int, int, int, int, int, int, int*, hipStream_t, bool);
 
-// SE pool partial-sum tiles of a fused launch (the workspace is sized for the largest count over all variants)
+// SE pool partial-sum tiles of a fused launch (the workspace is sized for the larger count of the two activation types)
 int mbconv_tiles(int H, int C, int k, int stride, int Cin, bool late) {
     const int Ho = (H + stride - 1) / stride;
     int best = -1;
-#define DFD_MB2_TILES(VV, KK, SS, HH, CC, CI, CB, TH, TW, RP, NK)                    \
-    if (k == KK && stride == SS && H == HH && C == CC && Cin == CI) {                \
+#define DFD_MB_TILES(TY, KK, SS, HH, CC, CI, CB, TH, TW, ...)                        \
+    if (DFD_MB_KEY(KK, SS, HH, CC, CI)) {                                            \
         const int tl = ((Ho + TW - 1) / TW) * ((Ho + TH - 1) / TH);                  \
         if (tl > best) best = tl;                                                    \
     }
-    DFD_MB2_TABLE(DFD_MB2_TILES)
-#define DFD_MB3_TILES(VV, KK, SS, HH, CC, CI, CB, TH, TW, RP, NK, NT, INS) DFD_MB2_TILES(VV, KK, SS, HH, CC, CI, CB, TH, TW, RP, NK)
-    DFD_MB3_TABLE(DFD_MB3_TILES)
-#undef DFD_MB3_TILES
-#undef DFD_MB2_TILES
-#define DFD_MB1_TILES(VV, KK, SS, HH, CC, CI, CB, TH, TW, RP, KC, NSUB)              \
-    if (k == KK && stride == SS && H == HH && C == CC && Cin == CI) {                \
-        const int tl = ((Ho + TW - 1) / TW) * ((Ho + TH - 1) / TH);                  \
-        if (tl > best) best = tl;                                                    \
-    }
-    DFD_MB1_TABLE(DFD_MB1_TILES)
-#undef DFD_MB1_TILES
-    if (k == 5 && stride == 1 && H == 28 && C == 240 && Cin == 40 && best < 4) best = 4;      // variant 14: 7 x 28 tiles
+    DFD_MB_TABLE(DFD_MB_TILES, DFD_MB_TILES, DFD_MB_TILES)
+#undef DFD_MB_TILES
 #define DFD_MB_LATE_TILES(KK, SS, HH, CC, CI) \
     if (late && k == KK && stride == SS && H == HH && C == CC && Cin == CI && best < 1) best = 1;
     DFD_MB_LATE_TABLE(DFD_MB_LATE_TILES)
@@ -1788,6 +1656,7 @@ int mbconv_tiles(int H, int C, int k, int stride, int Cin, bool late) {
 }
 
 int depthwise_tiles(int H, int C, int k, int stride) {
+    if (dw_rows7_shape(H, C, k, stride)) return 1;
     const int Ho = (H + stride - 1) / stride;
 #define DFD_DW_TILES(KK, SS, HH, CC, CB, TH, TW, RP) \
     if (k == KK && stride == SS && H == HH && C == CC) return ((Ho + TW - 1) / TW) * ((Ho + TH - 1) / TH);
