@@ -280,6 +280,17 @@ int dfd_classifier_crop_count(const dfd_handle* h, unsigned long long* total);
  * "<source>.head", "prob", "boxes" (per prior) or "rows" (DetectionOutput: score,x1,y1,x2,y2). */
 int dfd_ssd_tap(dfd_handle* h, const uint8_t* bgr, int height, int width, int stride,
                 const char* name, float* out, size_t capacity, size_t* count);
+/* The detector's tail on caller-supplied host arrays, for parity tests (as dfd_mtcnn_net_tap): values and counts no
+ * image produces.  n = 1..8 images in one call, P = the plan's prior count (8732), with the handle's own prior table,
+ * variances, thresholds and keep_top_k, through the buffers the production path uses.
+ *   heads != NULL (boxes_in = prob_in = NULL): the six head outputs as ssd_decode_kernel reads them, source after source,
+ *   each [n][cells][p * 6] (p * 4 loc values, then p * 2 logits: background, face); runs the decode, then
+ *   DetectionOutput; boxes_out [n][P][4] and prob_out [n][P] (either may be NULL) receive the decode's result.
+ *   heads == NULL: boxes_in [n][P][4] and prob_in [n][P]; runs DetectionOutput alone.
+ * rows_out [n][keep_top_k][5] (score, x1, y1, x2, y2; zero past an image's count; rows_capacity = its size in floats),
+ * count_out [n].  DFD_ERR_HIP when an image's count comes back as -1 (see dfd_detect_faces). */
+int dfd_ssd_detection_tap(dfd_handle* h, int n, const float* heads, const float* boxes_in, const float* prob_in,
+                          float* boxes_out, float* prob_out, float* rows_out, size_t rows_capacity, int* count_out);
 
 /* ---- Haar cascade fallback -------------------------------------------------------------
  * _detect_haar, reference face_detection.py:108-123: cv2.CascadeClassifier.detectMultiScale(gray, scaleFactor,

@@ -121,6 +121,8 @@ def jaccard(a, b) -> float:
         return 0.0
     ix = np.float32(min(a[2], b[2])) - np.float32(max(a[0], b[0]))
     iy = np.float32(min(a[3], b[3])) - np.float32(max(a[1], b[1]))
+    if not (ix > 0 and iy > 0):            # Caffe's JaccardOverlap: 0 unless the intersection has positive width and height
+        return 0.0                         # (touching or zero-area boxes: never 0 / 0)
     inter = np.float32(ix * iy)
     return float(inter / np.float32(np.float32(_area(a)) + np.float32(_area(b)) - inter))
 

@@ -80,6 +80,8 @@ SIGNATURES = {
     "dfd_classifier_crop_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "dfd_ssd_tap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_void_p,
                               C.c_size_t, C.POINTER(C.c_size_t)]),
+    "dfd_ssd_detection_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
     "dfd_has_haar": (C.c_int, [C.c_void_p]),
     "dfd_detect_faces_haar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                         C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -1207,6 +1209,27 @@ class Handle:
         self._check(self._lib.dfd_ssd_tap(self._p, _ptr(a), a.shape[0], a.shape[1], a.strides[0], name.encode(),
                                           _ptr(out), out.size, C.byref(cnt)))
         return out[: cnt.value]
+
+    def ssd_detection_tap(self, heads=None, boxes=None, prob=None, n_priors: int = 8732, keep_top_k: int = 200):
+        """The detector's tail on injected inputs (dfd_ssd_detection_tap), n images in one call.  `heads`: the six head
+        outputs, source after source, each (n, cells, p * 6) flattened and concatenated -> decode + DetectionOutput,
+        returns (boxes (n, P, 4), prob (n, P), rows, count).  `boxes` (n, P, 4) and `prob` (n, P): DetectionOutput
+        alone, returns (rows, count).  rows (n, keep_top_k, 5) = score, x1, y1, x2, y2, zero past count[i]."""
+        if heads is not None:
+            x = np.ascontiguousarray(heads, np.float32).ravel()
+            n, rem = divmod(x.size, n_priors * 6)
+            assert rem == 0 and n >= 1, x.size
+            bo, po = np.empty((n, n_priors, 4), np.float32), np.empty((n, n_priors), np.float32)
+            args = (_ptr(x), None, None, _ptr(bo), _ptr(po))
+        else:
+            b, p = np.ascontiguousarray(boxes, np.float32), np.ascontiguousarray(prob, np.float32)
+            assert b.ndim == 3 and b.shape[1:] == (n_priors, 4) and p.shape == b.shape[:2], (b.shape, p.shape)
+            n = b.shape[0]
+            args = (None, _ptr(b), _ptr(p), None, None)
+        rows = np.empty((n, keep_top_k, 5), np.float32)
+        count = np.zeros(n, np.int32)
+        self._check(self._lib.dfd_ssd_detection_tap(self._p, n, *args, _ptr(rows), rows.size, _ptr(count)))
+        return (bo, po, rows, count) if heads is not None else (rows, count)
 
 
 class ClassifierLanes:

@@ -256,11 +256,8 @@ int ssd_init(dfd_handle* h) {
     return DFD_OK;
 }
 
-// frames_u8: [n][300][300][3] resized BGR on the device.  Leaves DetectionOutput rows in S->rows/count.
-int ssd_forward(dfd_handle* h, const uint8_t* in300, int n, const char* tap_name, float* tap_out, size_t tap_cap,
-                size_t* tap_count) {
-    SsdState* S = h->ssd;
-    if (!S || !S->ready) return fail(h, DFD_ERR_STATE, "detector weights were not packed into the blob (weights.pack_all)");
+// workspace and DetectionOutput buffers for n images (they only grow)
+static int ssd_reserve(dfd_handle* h, SsdState* S, int n) {
     int rc;
     if (n > S->cap) {
         if ((rc = ensure(h, &S->work, S->floats_per_image * 4 * n))) return rc;
@@ -270,6 +267,16 @@ int ssd_forward(dfd_handle* h, const uint8_t* in300, int n, const char* tap_name
         if ((rc = ensure(h, &S->count, (size_t)n * 4))) return rc;
         S->cap = n;
     }
+    return DFD_OK;
+}
+
+// frames_u8: [n][300][300][3] resized BGR on the device.  Leaves DetectionOutput rows in S->rows/count.
+int ssd_forward(dfd_handle* h, const uint8_t* in300, int n, const char* tap_name, float* tap_out, size_t tap_cap,
+                size_t* tap_count) {
+    SsdState* S = h->ssd;
+    if (!S || !S->ready) return fail(h, DFD_ERR_STATE, "detector weights were not packed into the blob (weights.pack_all)");
+    int rc;
+    if ((rc = ssd_reserve(h, S, n))) return rc;
     hipStream_t s = h->stream;
     float* base = static_cast<float*>(S->work.p);
     // tensor t of image i lives at base + off(t)*n + i*size(t)   (frame-major per tensor)
@@ -481,6 +488,58 @@ int detect_frames_run(dfd_handle* h, const uint8_t* frames_dev, const FrameDesc*
     return DFD_OK;
 }
 
+// dfd_ssd_detection_tap: decode + DetectionOutput (heads given) or DetectionOutput alone (boxes and prob given) on
+// host arrays, through the buffers and parameters of ssd_forward
+int ssd_detection_tap(dfd_handle* h, int n, const float* heads, const float* boxes_in, const float* prob_in, float* boxes_out,
+                      float* prob_out, float* rows_out, size_t rows_capacity, int* count_out) {
+    SsdState* S = h->ssd;
+    int rc;
+    if ((rc = ssd_reserve(h, S, n))) return rc;
+    const size_t P = (size_t)S->n_priors, nrows = (size_t)n * S->keep_top_k * 5;
+    if (rows_capacity < nrows) return fail(h, DFD_ERR_ARG, "ssd_detection_tap: rows need %zu floats", nrows);
+    hipStream_t s = h->stream;
+    if (heads) {
+        float* base = static_cast<float*>(S->work.p);
+        SsdHeads H{};
+        H.prior_tab = S->prior_tab;
+        int first = 0;
+        const float* src = heads;
+        for (int i = 0; i < 6; ++i) {
+            const SsdSource& so = S->sources[i];
+            const int p = 2 + 2 * so.nar;
+            const SsdTensor& t = S->t[std::string(so.tensor) + ".head"];
+            float* dst = base + t.off * n;                                // frame-major per tensor, as in ssd_forward
+            const size_t cnt = (size_t)n * so.map * so.map * p * 6;
+            DFD_HIP_TRY(h, hipMemcpyAsync(dst, src, cnt * 4, hipMemcpyHostToDevice, s));
+            src += cnt;
+            H.out[i] = dst;
+            H.first[i] = first;
+            H.priors[i] = p;
+            H.map[i] = so.map;
+            first += so.map * so.map * p;
+        }
+        H.first[6] = first;
+        launch_ssd_decode(H, (float*)S->boxes.p, (float*)S->prob.p, n, S->n_priors, (float)SSD_IN, S->var, s);
+    } else {
+        DFD_HIP_TRY(h, hipMemcpyAsync(S->boxes.p, boxes_in, (size_t)n * P * 16, hipMemcpyHostToDevice, s));
+        DFD_HIP_TRY(h, hipMemcpyAsync(S->prob.p, prob_in, (size_t)n * P * 4, hipMemcpyHostToDevice, s));
+    }
+    launch_ssd_nms((const float*)S->boxes.p, (const float*)S->prob.p, n, S->n_priors, S->conf_thr, S->nms_thr, S->keep_top_k,
+                   (float*)S->rows.p, (int*)S->count.p, s);
+    if (boxes_out) DFD_HIP_TRY(h, hipMemcpyAsync(boxes_out, S->boxes.p, (size_t)n * P * 16, hipMemcpyDeviceToHost, s));
+    if (prob_out) DFD_HIP_TRY(h, hipMemcpyAsync(prob_out, S->prob.p, (size_t)n * P * 4, hipMemcpyDeviceToHost, s));
+    DFD_HIP_TRY(h, hipMemcpyAsync(rows_out, S->rows.p, nrows * 4, hipMemcpyDeviceToHost, s));
+    DFD_HIP_TRY(h, hipMemcpyAsync(count_out, S->count.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    DFD_HIP_TRY(h, hipGetLastError());
+    DFD_HIP_TRY(h, stream_sync(h));
+    for (int f = 0; f < n; ++f)
+        if (count_out[f] < 0)
+            return fail(h, DFD_ERR_HIP, "detector: DetectionOutput of image %d gave up waiting for its overlap rows (ssd_nms_kernel)", f);
+    for (int f = 0; f < n; ++f)                                           // rows past the count were never written
+        for (size_t r = (size_t)count_out[f] * 5; r < (size_t)S->keep_top_k * 5; ++r) rows_out[(size_t)f * S->keep_top_k * 5 + r] = 0.f;
+    return DFD_OK;
+}
+
 }  // namespace dfd
 
 extern "C" {
@@ -529,6 +588,16 @@ int dfd_ssd_tap(dfd_handle* h, const uint8_t* bgr, int hh, int ww, int stride, c
         return DFD_OK;
     }
     return ssd_forward(h, (const uint8_t*)h->ssd->in_u8.p, 1, name, out, capacity, count);
+}
+
+int dfd_ssd_detection_tap(dfd_handle* h, int n, const float* heads, const float* boxes_in, const float* prob_in,
+                          float* boxes_out, float* prob_out, float* rows_out, size_t rows_capacity, int* count_out) {
+    if (!h) return DFD_ERR_ARG;
+    if (n < 1 || n > 8 || !rows_out || !count_out || (!heads && (!boxes_in || !prob_in)) || (heads && (boxes_in || prob_in)))
+        return fail(h, DFD_ERR_ARG, "ssd_detection_tap: 1..8 images, either heads or boxes and prob, rows and count");
+    if (!h->ssd || !h->ssd->ready) return fail(h, DFD_ERR_STATE, "detector weights were not packed into the blob");
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    return ssd_detection_tap(h, n, heads, boxes_in, prob_in, boxes_out, prob_out, rows_out, rows_capacity, count_out);
 }
 
 }  // extern "C"
