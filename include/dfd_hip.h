@@ -62,8 +62,20 @@ int dfd_max_batch(const dfd_handle* h);
  *   "fuse_late" (default 1 since round 4, env DFD_FUSE_LATE; needs "fuse_expand"): blocks 6-10 and 12-15 (14 x 14 / 7 x 7
  *   maps) do the same with whole images per thread block - the faster configuration; 0 = expand
  *   GEMM and depthwise kernel as separate launches.
- *   "fuse_late_skip" (default blocks 8 and 9: bit b set = block b keeps separate launches although "fuse_late" is on; chosen
- *   per block by measurement at batch 256).
+ *   "fuse_late_skip" (bit b set = block b keeps separate launches although "fuse_late" is on; chosen per block by
+ *   measurement at batch 256; env DFD_FUSE_LATE_SKIP).  Default: unset = blocks 8 and 9.  Changed with "fuse_k5": the
+ *   value is signed now and any value < 0 means "unset" (it used to be read as an unsigned mask of every block); an
+ *   unset mask and the explicit value (1 << 8) | (1 << 9) give the same results, but only the unset one lets "fuse_k5"
+ *   take blocks 8 and 9.
+ *   "fuse_k5" (default 1, env DFD_FUSE_K5; fp32 activations with "fuse_late"): blocks 8-10 (k5, stride 1, 14 x 14) run
+ *   expand + depthwise with ONE thread block per image that walks every 32-channel chunk - inputs loaded and split into
+ *   bf16 terms once, four waves expanding chunk c + 1 while four run the depthwise phase of chunk c (mbconv_k5_kernel).
+ *   A launch of one block per image takes the same time for 1 image and for one per compute unit, so the plan takes it
+ *   only where the last round of blocks holds at least "fuse_k5_min" images (default, and any value <= 0: 208 of 256,
+ *   the measured break-even; env DFD_FUSE_K5_MIN); smaller batches run the launches of "fuse_k5" = 0.  The kernel
+ *   replaces whatever the block would run otherwise with that form's result bits (a block the unset mask covers: those
+ *   of the separate launches; an unmasked block: those of the one-block-per-chunk launch; an explicitly masked block is
+ *   left alone), so for a given "fuse_late_skip" neither this option nor the batch size changes a result.
  *   "fuse_stem" (default 1, env DFD_FUSE_STEM): the stem conv is computed inside block 0's depthwise
  *   kernel (the 112x112x32 stem activation stays in LDS).
  *   "fuse_proj0" (default 1, env DFD_FUSE_PROJ0; fp32 activations with "fuse_expand" and "split_gemm"): block 0's projection

@@ -86,10 +86,13 @@ int depthwise_tiles(int H, int C, int k, int stride);
 // split-precision operands (We3 = the three bf16 planes of We [C][Cin] from launch_split_weights, `plane`
 // elements apart, rows Kp long), then the depthwise conv as above.  Xin: block input [n][H][H][Cin]; be [C].
 // Returns false when no instantiation covers the shape (callers then run the GEMM + launch_depthwise).
+// late: the whole-image launches of blocks 6-15 (option "fuse_late"); k5: among those, fp32 blocks 8-10 through
+// mbconv_k5_kernel (option "fuse_k5"): 1 = with mbconv_late_kernel's result bits, 2 = with those of expand GEMM + depthwise
+// kernel (the expand bias added after the products instead of in front of them).
 template <typename XT>
 bool launch_mbconv_front(const XT* Xin, int Cin, const unsigned short* We3, int plane, int Kp, const float* Wef, const float* be,
                          const float* Wd, const float* bd, XT* Y, float* P, int n, int H, int C, int k, int stride,
-                         int pad_lo, int* tiles, hipStream_t s, bool late = false);
+                         int pad_lo, int* tiles, hipStream_t s, bool late = false, int k5 = 0);
 // Block 1's front half with block 0's projection folded into its prologue (option "fuse_proj0", fp32 only): Xdw0 is block
 // 0's depthwise output [n][H][H][32], gate0 its squeeze-excite gate [n][32], Wp3 / plane / Kp / bp the three bf16 planes
 // of its projection weights [16][32] and the bias; the rest as launch_mbconv_front.  The block input it computes per halo
@@ -102,6 +105,8 @@ bool launch_mbconv_front_proj0(const float* Xdw0, const float* gate0, const unsi
 // pool-tile count of the fused launch (the larger of the fp32 and bf16 kernels'), -1: none.  late: also the whole-image launches of blocks 6-15
 // (mbconv_late_kernel, option "fuse_late")
 int mbconv_tiles(int H, int C, int k, int stride, int Cin, bool late = false);
+// the block shapes (and padding) mbconv_k5_kernel covers; launch_mbconv_front with k5 != 0 fails for any other
+bool mbconv_k5_shape(int H, int C, int k, int stride, int Cin, int pad_lo);
 
 // squeeze-excite gate: mean over tiles*pixels -> FC(c_se)+swish -> FC(C)+sigmoid.
 void launch_se(const float* P, int tiles, float inv_hw, const float* w1, const float* b1,

@@ -14,6 +14,8 @@
 //                      (PROJ0: block 0's projection folded into block 1's launch)
 //  mbconv2_kernel      the same, second generation: fp32 blocks 2, 4 and bf16 blocks 1-5
 //  mbconv_late_kernel  the same for blocks 6-10 and 12-15: whole 14 x 14 / 7 x 7 images per block
+//  mbconv_k5_kernel    the same for the fp32 blocks 8-10 (k5 at 14 x 14): one block per image walks every channel chunk,
+//                      four waves expand chunk c + 1 while four run the depthwise phase of chunk c
 //  se_kernel           pool finish + two tiny FCs -> per-(image,channel) gate
 //  avgpool_kernel      global average pool of the head conv output
 //
@@ -426,7 +428,8 @@ struct DwShape {
 
 // depthwise conv of the LDS tile + folded BN + swish + store + per-tile SE partial sums.
 // Ends with a barrier-protected write of P; callers that reuse tile/wl/red afterwards must
-// __syncthreads() first.
+// __syncthreads() first.  EXACTLY ONE barrier on every path: mbconv_k5_kernel calls this from half of its waves and
+// matches that barrier with one of its own in the other half - a second barrier here would hang that kernel.
 template <int K, int S, int CB, int TH, int TW, int RP, int SWZ = 0, typename XT = float, int NT = 256>
 __device__ __forceinline__ void dw_compute(const v4f* tile, const v4f* wl, v4f* red,
                                            const v4f bv, XT* __restrict__ Y,
@@ -1526,14 +1529,220 @@ static void mb_late_launch(const XT* X, const unsigned short* We3, int plane, in
                        Y, P, n, C, pad_lo);
 }
 
+// ---- blocks 8-10 (k5, stride 1, 14 x 14, C_exp = 480 / 672): ONE block per image (round 6, option "fuse_k5") -----------
+// mbconv_late_kernel gives an image to C_exp / 32 = 15 or 21 blocks, and each of them reads the image's 196 x C_in
+// activations again, splits them into the three bf16 planes again (170 of the 1,323 VALU instructions of a wave), rewrites
+// the tile's zero border, restages its weight rows and runs expand and depthwise one after the other.  Here a block of
+// eight waves owns the image and walks its channel chunks:
+//   waves 4-7  (producers) load their three 16-pixel tiles once, split them once and keep the 3 x NK x 3 fragments in
+//              registers for every chunk (the 13th tile, four valid pixels, is split once into LDS and belongs to the first
+//              producer).  Per chunk: accumulators = expand bias, K-steps outermost, the six plane products smallest
+//              first - mbconv_late_kernel's order per accumulator - then swish into LDS tile (chunk & 1).
+//   waves 0-3  (consumers) run dw_compute on the tile of the chunk before, with the thread -> strip mapping and the pool
+//              fold of the 256-thread launches (their thread ids are 0-255), and stage what the next steps need: the
+//              expand weight rows of chunk + 2 (registers -> wlds slot at the start of the next step), the depthwise
+//              weights, the biases.
+// A SIMD holds one wave of each kind, so the MFMAs of chunk c + 1 issue beside the LDS reads and VALU work of chunk c.
+// Two barriers per chunk, back to back for the producers: the one inside dw_compute (pool partials) and the hand-over.
+// The zero border of both tiles is written once per block.  Result bits: those of mbconv_late_kernel, or - BIAS_LAST:
+// accumulators start at zero and the expand bias is added in front of the swish, the one operation in which the expand
+// GEMM's epilogue (s6_products + bias + swish) differs from the fused launches - those of expand GEMM + dw_kernel.
+template <int CEXP, int CIN, bool BIAS_LAST>
+__global__ __launch_bounds__(512) void mbconv_k5_kernel(const float* __restrict__ X, const unsigned short* __restrict__ We3,
+                                                        int plane, int Kp, const float* __restrict__ be,
+                                                        const float* __restrict__ Wt, const float* __restrict__ bias,
+                                                        float* __restrict__ Y, float* __restrict__ P) {
+    constexpr int K = 5, CB = 32, CG = 8, NTB = 2, NPX = 196, MTR = 3, PAD = 2;
+    constexpr int NK = (CIN + 31) / 32, NC = CEXP / CB;
+    constexpr int IW = 14 - 1 + K, SWZ = 2, NPIX = IW * IW, NUNIT = NPIX * (CG + 1);
+    constexpr int KROW = NK * 32 + 8, WROWS = 3 * CB * KROW;          // as mbconv_late_kernel's wlds
+    constexpr int CPR = NK * 4, NCH = 3 * CB * CPR, NLD = (NCH + 255) / 256;
+    constexpr int NWL = K * K * CG;
+    static_assert(CIN % 8 == 0 && CEXP % CB == 0 && NWL <= 256 && NK * 16 <= 256, "shape");
+    __shared__ v4f tile[2 * NUNIT];
+    __shared__ v4f wl[2 * NWL];
+    __shared__ v4f red[4 * CG];
+    __shared__ v4f bel[2 * CG];                                       // expand bias of a chunk
+    __shared__ v4f x12[NK * 3 * 16];                                  // pixels 192-195: [K-step][plane][8-channel group][pixel]
+    __shared__ __attribute__((aligned(16))) unsigned short wlds[2 * WROWS];
+    const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, q = lane >> 4;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int img = blockIdx.x;
+    const float* xb = X + (size_t)img * NPX * CIN;
+
+    // what the consumers stage for later steps: expand weight rows + expand bias of chunk ce, depthwise weights + bias of chunk
+    // cd (chunks past the last: the last one again, never used)
+    struct WStage { v4f w[NLD], dw, be, bv; };
+    auto stage_load = [&](int ce, int cd, WStage& st) {
+        const int e0 = (ce < NC ? ce : NC - 1) * CB, d0 = (cd < NC ? cd : NC - 1) * CB;
+#pragma unroll
+        for (int u = 0; u < NLD; ++u) {
+            const int ch = tid + u * 256 < NCH ? tid + u * 256 : NCH - 1;
+            const int row = ch / CPR, kc = ch - row * CPR, pl = row / CB, r = row - pl * CB;
+            st.w[u] = *reinterpret_cast<const v4f*>(We3 + (size_t)pl * plane + (size_t)(e0 + r) * Kp + kc * 8);
+        }
+        const int wli = tid < NWL ? tid : 0;
+        st.dw = ldg4(Wt + (size_t)(wli / CG) * CEXP + d0 + 4 * (wli % CG));
+        st.be = ldg4(be + e0 + 4 * (tid % CG));
+        st.bv = ldg4(bias + d0 + 4 * (tid % CG));
+    };
+    auto stage_store = [&](int ce, int cd, const WStage& st) {
+#pragma unroll
+        for (int u = 0; u < NLD; ++u) {
+            const int ch = tid + u * 256;
+            const int row = ch / CPR, kc = ch - row * CPR;
+            if (ch < NCH) *reinterpret_cast<v4f*>(&wlds[(ce & 1) * WROWS + row * KROW + kc * 8]) = st.w[u];
+        }
+        if (tid < NWL) wl[(cd & 1) * NWL + tid] = st.dw;
+        if (tid < CG) bel[(ce & 1) * CG + tid] = st.be;
+    };
+
+    // the zero border of the TF-SAME padding, both tiles, once (disjoint from the units the producers write)
+    for (int i = tid; i < 2 * NPIX * CG; i += 512) {
+        const int b = i / (NPIX * CG), u = i - b * (NPIX * CG), pp = u / CG, r = pp / IW - PAD, c = pp % IW - PAD;
+        if ((unsigned)r >= 14u || (unsigned)c >= 14u) tile[b * NUNIT + tile_unit<CG, SWZ>(pp, u % CG)] = (v4f){0.f, 0.f, 0.f, 0.f};
+    }
+    if (wv < 4) {
+        WStage st;
+        stage_load(0, 0, st);
+        if (tid < NK * 16) {                                          // the 13th pixel tile: four pixels, split once
+            const int ks = tid >> 4, q2 = (tid >> 2) & 3, j2 = tid & 3;
+            const int k = ks * 32 + 8 * q2, kk = k < CIN ? k : 0;     // channels >= Cin: any address, the planes are zero there
+            const float* px = xb + (size_t)(192 + j2) * CIN + kk;
+            bf8 x0, x1, x2;
+            split8(ldg4(px), ldg4(px + 4), x0, x1, x2);
+            x12[(ks * 3 + 0) * 16 + q2 * 4 + j2] = __builtin_bit_cast(v4f, x0);
+            x12[(ks * 3 + 1) * 16 + q2 * 4 + j2] = __builtin_bit_cast(v4f, x1);
+            x12[(ks * 3 + 2) * 16 + q2 * 4 + j2] = __builtin_bit_cast(v4f, x2);
+        }
+        stage_store(0, 0, st);
+        stage_load(1, 0, st);
+        v4f bv_prev = (v4f){0.f, 0.f, 0.f, 0.f};
+        __syncthreads();
+        // step t: the producers expand chunk t, the consumers run the depthwise phase of chunk t - 1
+#pragma unroll 1
+        for (int t = 0; t <= NC; ++t) {
+            stage_store(t + 1, t, st);                                // loaded a step ago; both slots were last read a step ago
+            const v4f bv = bv_prev;
+            bv_prev = st.bv;
+            stage_load(t + 2, t + 1, st);
+            if (t > 0)
+                dw_compute<K, 1, CB, 14, 14, 7, SWZ, float, 256>(tile + ((t - 1) & 1) * NUNIT, wl + ((t - 1) & 1) * NWL, red, bv, Y, P,
+                                                                  img, 14, CEXP, (t - 1) * CB, 0, 0, 0, 1);
+            else
+                __syncthreads();
+            __syncthreads();
+        }
+    } else {
+        const int pw = wv - 4;
+        bf8 xs[MTR][NK][3];
+#pragma unroll
+        for (int i = 0; i < MTR; ++i) {
+            const float* px = xb + (size_t)((pw + 4 * i) * 16 + j) * CIN;   // tiles 0-11: every pixel is one of the 196
+            v4f lo[NK], hi[NK];
+#pragma unroll
+            for (int ks = 0; ks < NK; ++ks) {
+                const int k = ks * 32 + 8 * q, kk = k < CIN ? k : 0;
+                lo[ks] = ldg4(px + kk);
+                hi[ks] = ldg4(px + kk + 4);
+            }
+#pragma unroll
+            for (int ks = 0; ks < NK; ++ks) split8(lo[ks], hi[ks], xs[i][ks][0], xs[i][ks][1], xs[i][ks][2]);
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (int t = 0; t < NC; ++t) {
+            const unsigned short* wb = wlds + (t & 1) * WROWS;
+            v4f* tl = tile + (t & 1) * NUNIT;
+            v4f acc[MTR + 1][NTB];
+#pragma unroll
+            for (int nt = 0; nt < NTB; ++nt) {
+                const v4f bex = BIAS_LAST ? (v4f){0.f, 0.f, 0.f, 0.f} : bel[(t & 1) * CG + nt * 4 + q];
+#pragma unroll
+                for (int i = 0; i <= MTR; ++i) acc[i][nt] = bex;
+            }
+            const int wsel[6] = {2, 1, 0, 1, 0, 0}, xsel[6] = {0, 1, 2, 0, 1, 0};   // smallest terms first
+            // weight fragments of (K-step, 16-channel half) g + 1 are requested before the MFMAs of g issue
+            bf8 wa[2][3];
+            auto load_wa = [&](int g, bf8* w) {
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl)
+                    w[pl] = *reinterpret_cast<const bf8*>(&wb[((pl * CB) + (g % NTB) * 16 + j) * KROW + (g / NTB) * 32 + 8 * q]);
+            };
+            load_wa(0, wa[0]);
+#pragma unroll
+            for (int g = 0; g < NK * NTB; ++g) {
+                const int ks = g / NTB, nt = g % NTB;
+                const bf8* w = wa[g & 1];
+                bf8 xl[3];
+                if (pw == 0) {
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl) xl[pl] = __builtin_bit_cast(bf8, x12[(ks * 3 + pl) * 16 + q * 4 + (j & 3)]);
+                }
+                if (g + 1 < NK * NTB) load_wa(g + 1, wa[(g + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < MTR; ++i)
+#pragma unroll
+                    for (int p6 = 0; p6 < 6; ++p6)
+                        acc[i][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[wsel[p6]], xs[i][ks][xsel[p6]], acc[i][nt], 0, 0, 0);
+                if (pw == 0) {
+#pragma unroll
+                    for (int p6 = 0; p6 < 6; ++p6)
+                        acc[MTR][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[wsel[p6]], xl[xsel[p6]], acc[MTR][nt], 0, 0, 0);
+                }
+            }
+            // swish -> LDS tile
+#pragma unroll
+            for (int i = 0; i <= MTR; ++i) {
+                const int p = (i < MTR ? (pw + 4 * i) * 16 : 192) + j;
+                if (i < MTR || (pw == 0 && j < 4)) {
+                    const int y = p / 14, x = p - y * 14;
+                    const int unit_p = (y + PAD) * IW + x + PAD;
+#pragma unroll
+                    for (int nt = 0; nt < NTB; ++nt) {
+                        v4f v = acc[i][nt];
+                        if constexpr (BIAS_LAST) v = v + bel[(t & 1) * CG + nt * 4 + q];
+                        tl[tile_unit<CG, SWZ>(unit_p, nt * 4 + q)] = swish4(v);
+                    }
+                }
+            }
+            __syncthreads();                                          // the consumers' two: inside dw_compute, and the hand-over
+            __syncthreads();
+        }
+        __syncthreads();                                              // step NC: the consumers finish the last chunk
+        __syncthreads();
+    }
+}
+
+// the shapes mbconv_k5_kernel has an instance for: the K5 rows of DFD_MB_LATE_TABLE with TF-SAME padding (the plan asks
+// before it requests the kernel; a request the launcher cannot serve is an error there, not a fall-back)
+bool mbconv_k5_shape(int H, int C, int k, int stride, int Cin, int pad_lo) {
+    return H == 14 && k == 5 && stride == 1 && pad_lo == 2 && ((C == 480 && Cin == 80) || (C == 672 && Cin == 112));
+}
+
+template <int C, int CIN>
+static bool mb_k5_launch(const float* X, const unsigned short* We3, int plane, int Kp, const float* be, const float* W, const float* b,
+                         float* Y, float* P, int n, int pad_lo, int* tiles, hipStream_t s, bool bias_last) {
+    if (!mbconv_k5_shape(14, C, 5, 1, CIN, pad_lo)) return false;     // (the plan asks first: it never gets here)
+    *tiles = 1;
+    if (bias_last) hipLaunchKernelGGL((mbconv_k5_kernel<C, CIN, true>), dim3(n), dim3(512), 0, s, X, We3, plane, Kp, be, W, b, Y, P);
+    else hipLaunchKernelGGL((mbconv_k5_kernel<C, CIN, false>), dim3(n), dim3(512), 0, s, X, We3, plane, Kp, be, W, b, Y, P);
+    return true;
+}
+
 // (k, stride, H, C, Cin) of blocks 6-10 and 12-15 (block 11, 14 -> 7 at stride 2, measured 115 us in this form against
-// 110 us as GEMM + depthwise: left out)
-#define DFD_MB_LATE_TABLE(OP)  \
-    OP(3, 1, 14, 480, 80)      \
-    OP(5, 1, 14, 480, 80)      \
-    OP(5, 1, 14, 672, 112)     \
-    OP(5, 1, 7, 1152, 192)     \
-    OP(3, 1, 7, 1152, 192)
+// 110 us as GEMM + depthwise: left out).  Row kinds:
+//   L    mbconv_late_kernel<K,S,H,Cin,XT>: one block per image (7 x 7: per four images) and 32 channels
+//   K5   an L row that fp32 activations also run as mbconv_k5_kernel<C,Cin,BIAS_LAST>, one block per image, where the plan asks
+//        for it (option "fuse_k5" and a batch that fills the CUs; BIAS_LAST: with the bits of expand GEMM + depthwise
+//        kernel instead of mbconv_late_kernel's)
+#define DFD_MB_LATE_TABLE(L, K5)  \
+    L(3, 1, 14, 480, 80)       \
+    K5(5, 1, 14, 480, 80)      \
+    K5(5, 1, 14, 672, 112)     \
+    L(5, 1, 7, 1152, 192)      \
+    L(3, 1, 7, 1152, 192)
 
 // The fused expand + depthwise launch of blocks 1-5, where the expanded tensor dominates HBM traffic and C_in <= 48: one
 // row per activation type and block names the ONE kernel instance that runs it.  launch_mbconv_front, the "fuse_proj0"
@@ -1578,16 +1787,23 @@ static void mb2_launch(const XT* X, int Cin, const unsigned short* We3, int plan
 template <typename XT>
 bool launch_mbconv_front(const XT* Xin, int Cin, const unsigned short* We3, int plane, int Kp, const float* Wef, const float* be,
                          const float* Wd, const float* bd, XT* Y, float* P, int n, int H, int C, int k, int stride,
-                         int pad_lo, int* tiles, hipStream_t s, bool late) {
+                         int pad_lo, int* tiles, hipStream_t s, bool late, int k5) {
     if (H <= 14) {
-        // option "fuse_late"
+        // options "fuse_late" and "fuse_k5"
         if (!late) return false;
 #define DFD_MB_LATE_DISPATCH(KK, SS, HH, CC, CI)                                                                     \
     if (k == KK && stride == SS && H == HH && C == CC && Cin == CI) {                                               \
         mb_late_launch<KK, SS, HH, CI, XT>(Xin, We3, plane, Kp, be, Wd, bd, Y, P, n, C, pad_lo, tiles, s);          \
         return true;                                                                                                \
     }
-        DFD_MB_LATE_TABLE(DFD_MB_LATE_DISPATCH)
+#define DFD_MB_K5_DISPATCH(KK, SS, HH, CC, CI)                                                                       \
+    if constexpr (std::is_same_v<XT, float>) {                                                                      \
+        if (k5 && k == KK && stride == SS && H == HH && C == CC && Cin == CI)  /* no quiet fall-back to the L row */  \
+            return mb_k5_launch<CC, CI>(Xin, We3, plane, Kp, be, Wd, bd, Y, P, n, pad_lo, tiles, s, k5 == 2);        \
+    }                                                                                                               \
+    DFD_MB_LATE_DISPATCH(KK, SS, HH, CC, CI)
+        DFD_MB_LATE_TABLE(DFD_MB_LATE_DISPATCH, DFD_MB_K5_DISPATCH)
+#undef DFD_MB_K5_DISPATCH
 #undef DFD_MB_LATE_DISPATCH
         return false;
     }
@@ -1634,8 +1850,8 @@ bool launch_mbconv_front_proj0(const float* Xdw0, const float* gate0, const unsi
     return false;
 }
 
-template bool launch_mbconv_front<float>(const float*, int, const unsigned short*, int, int, const float*, const float*, const float*, const float*, float*, float*, int, int, int, int, int, int, int*, hipStream_t, bool);
-template bool launch_mbconv_front<bf16_t>(const bf16_t*, int, const unsigned short*, int, int, const float*, const float*, const float*, const float*, bf16_t*, float*, int, int, int, int, int, int, int*, hipStream_t, bool);
+template bool launch_mbconv_front<float>(const float*, int, const unsigned short*, int, int, const float*, const float*, const float*, const float*, float*, float*, int, int, int, int, int, int, int*, hipStream_t, bool, int);
+template bool launch_mbconv_front<bf16_t>(const bf16_t*, int, const unsigned short*, int, int, const float*, const float*, const float*, const float*, bf16_t*, float*, int, int, int, int, int, int, int*, hipStream_t, bool, int);
 
 // SE pool partial-sum tiles of a fused launch (the workspace is sized for the larger count of the two activation types)
 int mbconv_tiles(int H, int C, int k, int stride, int Cin, bool late) {
@@ -1650,7 +1866,7 @@ int mbconv_tiles(int H, int C, int k, int stride, int Cin, bool late) {
 #undef DFD_MB_TILES
 #define DFD_MB_LATE_TILES(KK, SS, HH, CC, CI) \
     if (late && k == KK && stride == SS && H == HH && C == CC && Cin == CI && best < 1) best = 1;
-    DFD_MB_LATE_TABLE(DFD_MB_LATE_TILES)
+    DFD_MB_LATE_TABLE(DFD_MB_LATE_TILES, DFD_MB_LATE_TILES)
 #undef DFD_MB_LATE_TILES
     return best;
 }

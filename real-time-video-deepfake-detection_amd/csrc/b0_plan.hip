@@ -264,20 +264,36 @@ static int b0_forward_t(dfd_handle* h, const float* x, int n, float* logits_dev,
                                                   "(dfd_set_option(h, \"fuse_expand\", 0))", tap->name);
             }
         }
-        // whole-image launches (blocks 6-15) where they measure faster: per block, batch 256 (section 5, round 4) - blocks 8
-        // and 9 (k5, 480 / 672 channels at 14 x 14) are 2-4 us quicker as expand GEMM + depthwise kernel ("fuse_late_skip")
-        const bool late_here = h->fuse_late && !((h->fuse_late_skip >> bi) & 1u);
+        // whole-image launches (blocks 6-15) where they measure faster: per block, batch 256 (section 5, rounds 4 and 6).  As
+        // mbconv_late_kernel launches blocks 8 and 9 (k5, 480 / 672 channels at 14 x 14) are 2-4 us slower than expand GEMM +
+        // depthwise kernel: an unset "fuse_late_skip" masks them.
+        // mbconv_k5_kernel (option "fuse_k5") runs ONE block per image, so its launch takes the same time for 1 and for
+        // cu_count images: it is taken where the last round of blocks holds at least K5_MIN_DEFAULT images (measured,
+        // section 5) and replaces whatever form the block would run otherwise WITH THAT FORM'S BITS - mode 2 (the separate
+        // launches' bias order) for a block the unset mask covers, mode 1 (mbconv_late_kernel's) for an unmasked one; a block
+        // masked explicitly keeps its separate launches.  So neither the option nor the batch size changes a result.
+        constexpr int K5_MIN_DEFAULT = 208;
+        const int k5_rounds = (n + h->cu_count - 1) / h->cu_count, k5_last = n - (k5_rounds - 1) * h->cu_count;
+        const bool k5on = sizeof(XT) == 4 && h->fuse_k5 && h->fuse_late && h->fuse_expand && b.expand != 1 &&
+                          k5_last >= (h->fuse_k5_min > 0 ? h->fuse_k5_min : K5_MIN_DEFAULT) &&
+                          mbconv_k5_shape(b.h_in, b.c_exp, b.kernel, b.stride, b.c_in, b.pad_lo);
+        const bool mask_unset = h->fuse_late_skip < 0;
+        const unsigned late_skip = mask_unset ? (1u << 8) | (1u << 9) : (unsigned)h->fuse_late_skip;
+        const bool masked = (late_skip >> bi) & 1u;
+        const int k5 = !k5on ? 0 : (!masked ? 1 : (mask_unset ? 2 : 0));
+        const bool late_here = h->fuse_late && (!masked || k5 == 2);
         if (!fused && b.expand != 1 && h->fuse_expand && mbconv_tiles(b.h_in, b.c_exp, b.kernel, b.stride, b.c_in, late_here) > 0 &&
             !(we3 = split_weights(h, b.exp_w, b.c_exp, b.c_in))) return DFD_ERR_HIP;
         if (we3 && launch_mbconv_front<XT>(cur, b.c_in, we3, (int)split_weights_count(b.c_exp, b.c_in), (b.c_in + 63) / 64 * 64,
                                            b.exp_w, b.exp_b, b.dw_w, b.dw_b, dwbuf, h->pool, n, b.h_in, b.c_exp,
-                                           b.kernel, b.stride, b.pad_lo, &tiles, s, late_here)) {
+                                           b.kernel, b.stride, b.pad_lo, &tiles, s, late_here, k5)) {
             fused = true;
             mk.mark(layer_name(bi, "dw"));            // expand + depthwise in one launch
             if (tap && tap->name && q + ".exp" == tap->name)
                 return fail(h, DFD_ERR_STATE, "tap '%s': the expanded tensor is not materialised when expand is fused "
                                               "(dfd_set_option(h, \"fuse_expand\", 0))", tap->name);
         }
+        if (!fused && k5) return fail(h, DFD_ERR_STATE, "no k5 kernel for block %d", bi);
         if (!fused && b.expand != 1) {
             if ((rc = pointwise_t<XT>(h, cur, b.exp_w, b.exp_b, nullptr, nullptr, expbuf, m_in, b.c_in, b.c_exp,
                                       b.h_in * b.h_in, ACT_SWISH))) return rc;

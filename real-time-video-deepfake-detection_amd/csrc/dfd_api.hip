@@ -34,12 +34,15 @@ int create_impl(dfd_handle* h, int device, const void* blob, size_t blob_len, in
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(h, DFD_ERR_NO_DEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
     h->device = device;
+    h->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     h->max_batch = max_batch;
     if (const char* e = getenv("DFD_FUSE_EXPAND")) h->fuse_expand = atoi(e) != 0;
     if (const char* e = getenv("DFD_FUSE_STEM")) h->fuse_stem = atoi(e) != 0;
     if (const char* e = getenv("DFD_FUSE_PROJ0")) h->fuse_proj0 = atoi(e) != 0;
     if (const char* e = getenv("DFD_FUSE_LATE")) h->fuse_late = atoi(e) != 0;
-    if (const char* e = getenv("DFD_FUSE_LATE_SKIP")) h->fuse_late_skip = (unsigned)atoi(e);
+    if (const char* e = getenv("DFD_FUSE_LATE_SKIP")) h->fuse_late_skip = atoi(e);
+    if (const char* e = getenv("DFD_FUSE_K5")) h->fuse_k5 = atoi(e) != 0;
+    if (const char* e = getenv("DFD_FUSE_K5_MIN")) h->fuse_k5_min = atoi(e);
     if (const char* e = getenv("DFD_SPLIT_GEMM")) h->split_gemm = atoi(e) != 0;
     if (const char* e = getenv("DFD_BF16_ACTIVATIONS")) h->act_bf16 = atoi(e) != 0;
     if (const char* e = getenv("DFD_JPEG_DEVICE_RESTART")) h->jpeg_device_restart = atoi(e) != 0;
@@ -163,7 +166,9 @@ int dfd_set_option(dfd_handle* h, const char* name, int value) {
     if (!h || !name) return DFD_ERR_ARG;
     if (strcmp(name, "fuse_expand") == 0) { h->fuse_expand = value != 0; return DFD_OK; }
     if (strcmp(name, "fuse_late") == 0) { h->fuse_late = value != 0; return DFD_OK; }
-    if (strcmp(name, "fuse_late_skip") == 0) { h->fuse_late_skip = (unsigned)value; return DFD_OK; }
+    if (strcmp(name, "fuse_late_skip") == 0) { h->fuse_late_skip = value; return DFD_OK; }   // < 0: the default again
+    if (strcmp(name, "fuse_k5") == 0) { h->fuse_k5 = value != 0; return DFD_OK; }
+    if (strcmp(name, "fuse_k5_min") == 0) { h->fuse_k5_min = value; return DFD_OK; }                  // <= 0: the default again
     if (strcmp(name, "fuse_stem") == 0) { h->fuse_stem = value != 0; return DFD_OK; }
     if (strcmp(name, "fuse_proj0") == 0) { h->fuse_proj0 = value != 0; return DFD_OK; }
     if (strcmp(name, "split_gemm") == 0) { h->split_gemm = value != 0; return DFD_OK; }

@@ -136,9 +136,15 @@ struct dfd_handle {
     bool warming = false;                // inside dfd_warmup: every GEMM shape of the unfused plan is launched, so that its tile is measured
     bool fuse_late = true;               // blocks 6-10 / 12-15: expand + depthwise of whole images in one launch (mbconv_late_kernel):
                                          // the faster configuration (round 3: +2.2-2.6 % per step, strictly fewer bytes), default since round 4
-    unsigned fuse_late_skip = (1u << 8) | (1u << 9);   // blocks that keep expand GEMM + depthwise kernel although fuse_late is on:
-                                         // measured per block at batch 256 (fused - separate, us): b6 -17.8, b7 -5.5, b8 +2.1, b9 +3.6,
-                                         // b10 -1.4, b12 -9.8, b13 -4.9, b14 -4.7, b15 -2.3 (option "fuse_late_skip", a bit per block)
+    int fuse_late_skip = -1;             // blocks that keep expand GEMM + depthwise kernel although fuse_late is on (option
+                                         // "fuse_late_skip", a bit per block).  -1 = not set: blocks 8 and 9 where mbconv_late_kernel
+                                         // would run them - measured per block at batch 256 (fused - separate, us): b6 -17.8, b7 -5.5,
+                                         // b8 +2.1, b9 +3.6, b10 -1.4, b12 -9.8, b13 -4.9, b14 -4.7, b15 -2.3; only the unset mask
+                                         // lets mbconv_k5_kernel take blocks 8 and 9 (fuse_k5; b0_plan.hip)
+    int fuse_k5_min = 0;                 // crops in the last round of blocks from which the k5 kernel runs (<= 0: measured default, b0_plan.hip)
+    int cu_count = 256;                  // compute units of the device (dfd_create)
+    bool fuse_k5 = true;                 // fp32 blocks 8-10 (k5 at 14 x 14) of the fuse_late launches: one block per image
+                                         // (mbconv_k5_kernel, round 6) instead of one per image and 32 channels; same result bits
     bool split_gemm = true;              // 1x1 / k x k convs on the bf16x3-split MFMA path (gemm_split.hip)
     bool act_bf16 = false;               // classifier activations stored as bf16 (fp32 arithmetic): configs[3]
     int bf16_planes = 3;                 // weight planes the bf16-activation GEMMs use: 3 = fp32-exact weights, 1 = bf16 weights
