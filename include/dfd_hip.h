@@ -669,6 +669,57 @@ int dfd_vote_allgather(dfd_handle* h, const void* local_records, size_t bytes_pe
  * all_records_out = [world][bytes_per_rank] of wave w), one download, one stream wait. */
 int dfd_vote_allgather_waves(dfd_handle* h, const void* local_records, int waves, size_t bytes_per_rank, void* all_records_out);
 
+/* ---- classifier head training ---------------------------------------------------------------
+ * The reference's training recipe (train.py: FocalLoss :360-392, mixup_criterion :352-354, AdamW :910, gradient
+ * clipping and accumulation :587-605, EMAModel :398-416) for the 1280 -> 512 -> 256 -> 1 head (model.py:50-61) on the
+ * pooled features dfd_extract_features returns; the backbone stays frozen.  fp32 throughout (no AMP).  A trainer hangs
+ * off the handle between begin and end (dfd_destroy ends an open one), is single-caller like the handle and touches
+ * nothing the inference entries read until dfd_head_train_commit.  Calling anything but begin without an open
+ * trainer, a second begin, max_n outside 2..256, dropout outside [0,1), n > max_n, and n < 2 in accumulate
+ * (BatchNorm1d's batch statistics need two rows) are DFD_ERR_ARG; host memory running out is DFD_ERR_CAPACITY, a failed
+ * device allocation DFD_ERR_HIP.  All pointers are host memory.
+ *
+ * Dropout keep masks are a stateless hash of (seed, accumulate counter since begin, layer 0..2, row * width + col)
+ * compared against floor(p * 2^32); head_training.dropout_keep_mask (Python, numpy) is its specification and the
+ * kernels reproduce it bit for bit.  Layer rates: dropout, 0.7 dropout, 0.5 dropout (as doubles of the float). */
+typedef struct dfd_head_params {      /* torch layouts: w [out][in]; g / be = BatchNorm1d weight / bias; rm / rv = running stats */
+    float *w1, *b1, *g1, *be1, *rm1, *rv1, *w2, *b2, *g2, *be2, *rm2, *rv2, *w3, *b3;
+} dfd_head_params;
+typedef struct dfd_head_config {
+    int max_n;                         /* rows of one accumulate / eval call, 2..256 */
+    unsigned long long seed;
+    float dropout, beta1, beta2, eps, weight_decay, focal_gamma, focal_alpha, label_smoothing, clip_norm, ema_decay,
+        bn_momentum;
+} dfd_head_config;
+/* train.py's argparse defaults: max_n 32, seed 0, dropout 0.5, weight_decay 0.05, focal 2.0 / 0.25, label_smoothing 0.1,
+ * ema_decay 0.999; clip_norm 1.0, betas 0.9 / 0.999, eps 1e-8 (torch.optim.AdamW), bn_momentum 0.1 */
+void dfd_head_config_default(dfd_head_config* cfg);
+/* uploads the unfolded head (every pointer of `init` required); EMA shadow = the parameters, moments and gradients 0 */
+int dfd_head_train_begin(dfd_handle* h, const dfd_head_params* init, const dfd_head_config* cfg);
+/* train-mode forward (batch statistics, running statistics updated), loss = lam FL(z, labels_a) + (1 - lam) FL(z, labels_b)
+ * (labels_b NULL: FL(z, labels_a)), mean over the n rows, and the backward of loss * loss_scale ADDED to the gradient
+ * buffer.  *loss_out: the unscaled loss; logits_out [n] or NULL. */
+int dfd_head_train_accumulate(dfd_handle* h, const float* feat, int n, const float* labels_a, const float* labels_b,
+                              float lam, float loss_scale, float* loss_out, float* logits_out);
+/* clip_grad_norm_ (coef = min(1, clip_norm / (norm + 1e-6))), torch.optim.AdamW's step with the given learning rate on
+ * every trainable tensor (one group: biases and BN gamma / beta decay too), EMA update, gradients zeroed.
+ * *grad_norm_out (or NULL): the global L2 norm before clipping. */
+int dfd_head_train_apply(dfd_handle* h, float lr, float* grad_norm_out);
+/* eval-mode forward (running statistics, no dropout) of n <= max_n rows on the live or the EMA parameters */
+int dfd_head_train_eval(dfd_handle* h, const float* feat, int n, int use_ema, float* logits_out);
+/* parameters (live or EMA) and the live running statistics into the caller's arrays */
+int dfd_head_train_export(dfd_handle* h, int use_ema, dfd_head_params* out);
+/* test tap: read (set = 0) or replace (set = 1) the accumulated gradients; rm / rv are not used */
+int dfd_head_train_grads(dfd_handle* h, dfd_head_params* io, int set);
+/* test tap of the last accumulate: "mask0" [n][1280], "mask1" [n][512], "mask2" [n][256] (1.0 = kept), "z1" [n][512],
+ * "z2" [n][256] (BatchNorm outputs before ReLU).  capacity in floats; too small: DFD_ERR_ARG */
+int dfd_head_train_tap(dfd_handle* h, const char* name, float* out, size_t capacity);
+/* folds BatchNorm into fc1 / fc2 (float64 on the host, rounded once: weights._fold) and overwrites the tensors the
+ * inference plan reads, on the handle's stream; the cached bf16 splits of fc1.w / fc2.w are rebuilt in place.  From
+ * the next call on, every classify / fused / Grad-CAM entry of this handle uses the new head. */
+int dfd_head_train_commit(dfd_handle* h, int use_ema);
+int dfd_head_train_end(dfd_handle* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,17 @@ SIGNATURES = {
     "dfd_b0_profile_begin": (C.c_int, [C.c_void_p]),
     "dfd_b0_profile_end": (C.c_int, [C.c_void_p, c_float_p, C.POINTER(C.c_char_p), C.c_int,
                                       C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dfd_head_config_default": (None, [C.c_void_p]),
+    "dfd_head_train_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dfd_head_train_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                            c_float_p, C.c_void_p]),
+    "dfd_head_train_apply": (C.c_int, [C.c_void_p, C.c_float, c_float_p]),
+    "dfd_head_train_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dfd_head_train_export": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "dfd_head_train_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "dfd_head_train_tap": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]),
+    "dfd_head_train_commit": (C.c_int, [C.c_void_p, C.c_int]),
+    "dfd_head_train_end": (C.c_int, [C.c_void_p]),
 }
 
 
@@ -176,6 +187,51 @@ class JpegSource(C.Structure):
 
 JPEG_GRAY = 3                 # DFD_JPEG_GRAY; 0 / 1 / 2 = 4:4:4 / 4:2:2 / 4:2:0 as in Pillow
 JPEG_ENC_SCAN_TILE = 1024     # blocks one workgroup of the encoder's prefix sum covers in one pass (csrc/jpeg_encode.hip kEncScanTile)
+
+
+HEAD_FIELDS = ("w1", "b1", "g1", "be1", "rm1", "rv1", "w2", "b2", "g2", "be2", "rm2", "rv2", "w3", "b3")
+HEAD_SHAPES = {"w1": (512, 1280), "b1": (512,), "g1": (512,), "be1": (512,), "rm1": (512,), "rv1": (512,),
+               "w2": (256, 512), "b2": (256,), "g2": (256,), "be2": (256,), "rm2": (256,), "rv2": (256,),
+               "w3": (1, 256), "b3": (1,)}
+
+
+class HeadParams(C.Structure):
+    """`dfd_head_params` (include/dfd_hip.h): host arrays of the unfolded head, torch layouts."""
+    _fields_ = [(k, C.c_void_p) for k in HEAD_FIELDS]
+
+
+class HeadConfig(C.Structure):
+    """`dfd_head_config` (include/dfd_hip.h)"""
+    _fields_ = [("max_n", C.c_int), ("seed", C.c_ulonglong), ("dropout", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("eps", C.c_float), ("weight_decay", C.c_float), ("focal_gamma", C.c_float), ("focal_alpha", C.c_float),
+                ("label_smoothing", C.c_float), ("clip_norm", C.c_float), ("ema_decay", C.c_float), ("bn_momentum", C.c_float)]
+
+
+def head_config(**kw) -> HeadConfig:
+    """The library's defaults (dfd_head_config_default: train.py's argparse defaults), then the given fields."""
+    c = HeadConfig()
+    load().dfd_head_config_default(C.byref(c))
+    names = {f[0] for f in HeadConfig._fields_}
+    for k, v in kw.items():
+        if k not in names:
+            raise TypeError(f"unknown head-training setting {k!r}")
+        setattr(c, k, int(v) if k in ("max_n", "seed") else float(v))
+    return c
+
+
+def _head_arrays(arrays=None, skip=()):
+    """(HeadParams, dict of the float32 arrays it points to); missing entries are allocated"""
+    out, hp = {}, HeadParams()
+    for k in HEAD_FIELDS:
+        if k in skip:
+            continue
+        if arrays is not None and k in arrays:
+            a = np.ascontiguousarray(np.asarray(arrays[k], dtype=np.float32).reshape(HEAD_SHAPES[k]))
+        else:
+            a = np.zeros(HEAD_SHAPES[k], np.float32)
+        out[k] = a
+        setattr(hp, k, a.ctypes.data)
+    return hp, out
 
 
 class TtaDraw(C.Structure):
@@ -390,6 +446,75 @@ class Handle:
         out = np.empty((a.shape[0], 1280), dtype=np.float32)
         self._check(self._lib.dfd_extract_features(self._p, _ptr(a), a.shape[0], _ptr(out)))
         return out
+
+    # -- head training (include/dfd_hip.h "classifier head training"; head_training.HeadTrainer is the front end)
+    @staticmethod
+    def _as_features(x) -> np.ndarray:
+        a = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
+        if a.ndim != 2 or a.shape[1] != 1280:
+            raise ValueError(f"expected (n,1280) features, got {a.shape}")
+        return a
+
+    def head_train_begin(self, params, config: "HeadConfig"):
+        """params: dict of the 14 `HEAD_FIELDS` arrays"""
+        missing = [k for k in HEAD_FIELDS if k not in params]
+        if missing:
+            raise KeyError(f"head parameters missing: {missing}")
+        hp, _keep = _head_arrays(params)
+        self._check(self._lib.dfd_head_train_begin(self._p, C.byref(hp), C.byref(config)))
+
+    def head_train_accumulate(self, feat, labels_a, labels_b=None, lam: float = 1.0, loss_scale: float = 1.0):
+        """-> (unscaled loss, logits (n,))"""
+        a = self._as_features(feat)
+        n = a.shape[0]
+        ya = np.ascontiguousarray(np.asarray(labels_a, dtype=np.float32).reshape(-1))
+        yb = None if labels_b is None else np.ascontiguousarray(np.asarray(labels_b, dtype=np.float32).reshape(-1))
+        if ya.size != n or (yb is not None and yb.size != n):
+            raise ValueError("one label per feature row")
+        loss = C.c_float()
+        logits = np.empty(max(n, 1), np.float32)
+        self._check(self._lib.dfd_head_train_accumulate(self._p, _ptr(a), n, _ptr(ya), None if yb is None else _ptr(yb),
+                                                        float(lam), float(loss_scale), C.byref(loss), _ptr(logits)))
+        return float(loss.value), logits[:n]
+
+    def head_train_apply(self, lr: float) -> float:
+        """-> global gradient norm before clipping"""
+        norm = C.c_float()
+        self._check(self._lib.dfd_head_train_apply(self._p, float(lr), C.byref(norm)))
+        return float(norm.value)
+
+    def head_train_eval(self, feat, use_ema: bool = False) -> np.ndarray:
+        a = self._as_features(feat)
+        out = np.empty(max(a.shape[0], 1), np.float32)
+        self._check(self._lib.dfd_head_train_eval(self._p, _ptr(a), a.shape[0], int(bool(use_ema)), _ptr(out)))
+        return out[: a.shape[0]]
+
+    def head_train_export(self, use_ema: bool = False):
+        hp, out = _head_arrays()
+        self._check(self._lib.dfd_head_train_export(self._p, int(bool(use_ema)), C.byref(hp)))
+        return out
+
+    def head_train_grads(self, set_to=None):
+        """the accumulated gradients (dict without rm / rv); `set_to`: replace them first"""
+        skip = ("rm1", "rv1", "rm2", "rv2")
+        if set_to is not None:
+            hp, _keep = _head_arrays(set_to, skip)
+            self._check(self._lib.dfd_head_train_grads(self._p, C.byref(hp), 1))
+        hp, out = _head_arrays(None, skip)
+        self._check(self._lib.dfd_head_train_grads(self._p, C.byref(hp), 0))
+        return out
+
+    def head_train_tap(self, name: str, n: int) -> np.ndarray:
+        width = {"mask0": 1280, "mask1": 512, "mask2": 256, "z1": 512, "z2": 256}.get(name, 1280)   # unknown names: the library refuses
+        out = np.empty((int(n), width), np.float32)
+        self._check(self._lib.dfd_head_train_tap(self._p, name.encode(), _ptr(out), out.size))
+        return out
+
+    def head_train_commit(self, use_ema: bool = True):
+        self._check(self._lib.dfd_head_train_commit(self._p, int(bool(use_ema))))
+
+    def head_train_end(self):
+        self._check(self._lib.dfd_head_train_end(self._p))
 
     def tap(self, x_dev: int, n: int, name: str, capacity: int) -> np.ndarray:
         out = np.empty(int(capacity), dtype=np.float32)

@@ -97,6 +97,7 @@ void destroy_impl(dfd_handle* h) {
     hipSetDevice(h->device);
     if (h->stream) stream_sync(h);
     comm_destroy(h);
+    head_train_destroy(h);
     haar_destroy(h);
     forensic_destroy(h);
     ssd_destroy(h);

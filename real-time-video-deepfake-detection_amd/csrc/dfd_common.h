@@ -34,6 +34,8 @@ struct S6Table;         // gemm_split.hip: measured split-GEMM tiles of this han
 struct MtcnnState;      // mtcnn_api.hip
 int mtcnn_init(dfd_handle* h);
 void mtcnn_destroy(dfd_handle* h);
+struct HeadTrainState;  // head_train.hip: trainer of the classifier head (null until dfd_head_train_begin)
+void head_train_destroy(dfd_handle* h);
 
 // Tensor + parse_blob: blob_reader.h (plain C++, also built into the sanitizer harness)
 
@@ -129,6 +131,7 @@ struct dfd_handle {
     dfd::MtcnnState* mtcnn = nullptr;         // MTCNN cascade (null: blob has none)
     dfd::HaarState* haar = nullptr;           // Haar cascade (null: blob has none)
     dfd::CommState* comm = nullptr;           // vote exchange (null until dfd_comm_init)
+    dfd::HeadTrainState* head_train = nullptr; // open head trainer (dfd_head_train_begin .. _end)
     bool use_mtcnn = true;                    // classify paths align each crop with the cascade when the blob has one
     bool fuse_stem = true;               // stem conv computed inside block 0's depthwise kernel
     bool fuse_expand = true;             // MBConv blocks 1-5: expand conv computed inside the depthwise kernel

@@ -1,0 +1,286 @@
+"""Training of the classifier head on the device, on the engine's own pooled features.
+
+The reference's recipe (train.py: FocalLoss, AdamW, gradient clipping, gradient accumulation, EMA, OneCycleLR)
+applied to the 1280 -> 512 -> 256 -> 1 head (model.py:50-61) with the backbone frozen.  The arithmetic of a step runs
+in libdfd_hip.so (csrc/head_train.hip, `dfd_head_train_*` in include/dfd_hip.h); this module holds what lives on the
+host: the learning-rate schedule, the specification of the dropout masks, the epoch loop and the state-dict names.
+
+Deviations from train.py: fp32 instead of AMP / GradScaler; the backbone is not fine-tuned; Mixup works on feature
+rows (no image-space Mixup / CutMix); a last batch of one row is dropped (BatchNorm1d needs two).
+"""
+from __future__ import annotations
+
+import math
+import time
+from typing import Dict, List, Mapping, Optional
+
+import numpy as np
+
+from . import _lib
+
+# reference state-dict key -> `dfd_head_params` field
+KEYS = {
+    "net._fc.1.weight": "w1", "net._fc.1.bias": "b1",
+    "net._fc.2.weight": "g1", "net._fc.2.bias": "be1", "net._fc.2.running_mean": "rm1", "net._fc.2.running_var": "rv1",
+    "net._fc.5.weight": "w2", "net._fc.5.bias": "b2",
+    "net._fc.6.weight": "g2", "net._fc.6.bias": "be2", "net._fc.6.running_mean": "rm2", "net._fc.6.running_var": "rv2",
+    "net._fc.9.weight": "w3", "net._fc.9.bias": "b3",
+}
+TRACKED = ("net._fc.2.num_batches_tracked", "net._fc.6.num_batches_tracked")
+LAYER_WIDTHS = (1280, 512, 256)          # what dropout layer 0 / 1 / 2 acts on
+LAYER_RATES = (1.0, 0.7, 0.5)            # model.py:51,55,59: dropout, dropout * 0.7, dropout * 0.5
+
+
+# --------------------------------------------------------------------------- schedule
+def one_cycle_lr(step: int, total_steps: int, max_lr: float, pct_start: float = 0.1, div_factor: float = 25.0,
+                 final_div_factor: float = 1000.0) -> float:
+    """torch.optim.lr_scheduler.OneCycleLR(anneal_strategy='cos', three_phase=False) in closed form: the value
+    `get_last_lr()` returns after `step` calls of `scheduler.step()` (train.py:916-924; step 0 = the initial rate)."""
+    if total_steps <= 0:
+        raise ValueError("total_steps must be positive")
+    initial, min_lr = max_lr / div_factor, max_lr / div_factor / final_div_factor
+    up_end = float(pct_start * total_steps) - 1.0
+    if step <= up_end:
+        start, end, pct = initial, max_lr, step / up_end
+    else:
+        start, end, pct = max_lr, min_lr, (step - up_end) / ((total_steps - 1) - up_end)
+    return end + (start - end) / 2.0 * (math.cos(math.pi * pct) + 1.0)
+
+
+# --------------------------------------------------------------------------- dropout masks
+def _fmix32(x: np.ndarray) -> np.ndarray:
+    """MurmurHash3's 32-bit finaliser on uint32 arrays (arithmetic mod 2^32)"""
+    x = x.astype(np.uint32)
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x85EBCA6B)
+    x = x ^ (x >> np.uint32(13))
+    x = x * np.uint32(0xC2B2AE35)
+    return x ^ (x >> np.uint32(16))
+
+
+def _u32(v: int) -> np.ndarray:
+    return np.array([v & 0xFFFFFFFF], dtype=np.uint32)
+
+
+def dropout_rates(dropout: float):
+    """the three layer rates as the library computes them: doubles of the float32 setting"""
+    d = float(np.float32(dropout))
+    return tuple(r * d for r in LAYER_RATES)
+
+
+def dropout_keep_mask(seed: int, counter: int, layer: int, n: int, width: int, p: float) -> np.ndarray:
+    """The specification of the trainer's dropout: bool (n, width), True = kept (and scaled by 1 / (1 - p)).
+
+    key  = fmix(fmix(fmix(fmix(fmix(seed_lo + 0x9E3779B9) ^ seed_hi) ^ counter_lo) ^ counter_hi) ^ (layer + 1))
+    u(i) = fmix(fmix(i ^ key) + key),   i = row * width + col
+    keep = u(i) >= floor(p * 2^32)
+    all in uint32 arithmetic; `counter` = accumulate calls since the trainer was opened, `layer` = 0, 1, 2."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError("p outside [0, 1)")
+    seed, counter = int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1)
+    with np.errstate(over="ignore"):
+        k = _fmix32(_u32(seed) + np.uint32(0x9E3779B9))
+        k = _fmix32(k ^ _u32(seed >> 32))
+        k = _fmix32(k ^ _u32(counter))
+        k = _fmix32(k ^ _u32(counter >> 32))
+        k = _fmix32(k ^ _u32(layer + 1))
+        idx = np.arange(n * width, dtype=np.uint32)
+        u = _fmix32(_fmix32(idx ^ k) + k)
+    return (u >= np.uint32(int(p * 4294967296.0))).reshape(n, width)
+
+
+# --------------------------------------------------------------------------- loss and metrics on the host
+def focal_loss(logits, targets, gamma: float = 2.0, alpha: float = 0.25, label_smoothing: float = 0.0) -> float:
+    """train.py:380-392 in float64 numpy (validation loss; the training loss comes from the device)"""
+    z = np.asarray(logits, np.float64).reshape(-1)
+    t = np.asarray(targets, np.float64).reshape(-1)
+    if label_smoothing > 0:
+        t = t * (1.0 - label_smoothing) + 0.5 * label_smoothing
+    e = np.exp(-np.abs(z))
+    bce = np.maximum(z, 0.0) - z * t + np.log1p(e)
+    p = np.where(z >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+    p_t = p * t + (1.0 - p) * (1.0 - t)
+    a_t = alpha * t + (1.0 - alpha) * (1.0 - t)
+    return float(np.mean(a_t * (1.0 - p_t) ** gamma * bce))
+
+
+def _metrics(logits: np.ndarray, labels: np.ndarray) -> Dict[str, float]:
+    """accuracy / F1 / AUC as train.py:649-672 computes them (AUC by ranks, ties averaged)"""
+    pred = (logits > 0).astype(np.float64)                 # sigmoid(z) > 0.5
+    acc = float((pred == labels).mean()) if labels.size else 0.0
+    tp, fp = float(((pred == 1) & (labels == 1)).sum()), float(((pred == 1) & (labels == 0)).sum())
+    fn = float(((pred == 0) & (labels == 1)).sum())
+    prec, rec = tp / (tp + fp + 1e-10), tp / (tp + fn + 1e-10)
+    f1 = 2 * prec * rec / (prec + rec + 1e-10)
+    pos, neg = int((labels == 1).sum()), int((labels == 0).sum())
+    auc = 0.0
+    if pos and neg:
+        order = np.argsort(logits, kind="mergesort")
+        ranks = np.empty(labels.size, np.float64)
+        sl = logits[order]
+        i = 0
+        while i < sl.size:
+            j = i
+            while j + 1 < sl.size and sl[j + 1] == sl[i]:
+                j += 1
+            ranks[order[i:j + 1]] = 0.5 * (i + j) + 1.0
+            i = j + 1
+        auc = float((ranks[labels == 1].sum() - pos * (pos + 1) / 2.0) / (pos * neg))
+    return {"acc": acc, "f1": float(f1), "auc": auc}
+
+
+# --------------------------------------------------------------------------- the epoch loop
+def fit_loop(trainer, features, labels, epochs: int, batch_size: int = 32, grad_accum: int = 2, lr: float = 3e-4,
+             mix_alpha: float = 0.0, val=None, patience: int = 5, rng=None) -> List[Dict[str, float]]:
+    """train.py's `train_one_epoch` / `validate` loop over any object with `accumulate`, `apply`, `evaluate`,
+    `max_n` and `loss_settings` (HeadTrainer; the tests' float64 oracle).  Returns a log shaped like
+    weights/training_log.json: one dict per epoch (epoch, train_loss, train_acc, val_loss, val_acc, val_f1, val_auc,
+    lr, time_seconds).
+
+    Draws, all from `rng` (a numpy RandomState; default RandomState(0)), in this order: per epoch one
+    `permutation(len(features))` (the shuffle); then per batch, only when mix_alpha > 0: `random_sample()` (mix this
+    batch when < 0.5, train.py:566-567), and for a mixed batch `beta(mix_alpha, mix_alpha)` then `permutation(rows)`.
+    A mixed batch is lam x + (1 - lam) x[perm] on the feature rows with lam = max(lam, 1 - lam), labels (y, y[perm]).
+
+    One optimizer step per `grad_accum` batches and at the last batch of an epoch (train.py:596); the rate of step k
+    is one_cycle_lr(k, total optimizer steps, lr).  Validation (on `val` = (features, labels)) runs on the EMA
+    parameters as train.py:992-999 does; training stops after `patience` epochs without a lower validation loss."""
+    x = np.ascontiguousarray(np.asarray(features, np.float32))
+    y = np.asarray(labels, np.float32).reshape(-1)
+    if x.ndim != 2 or x.shape[0] != y.size:
+        raise ValueError("features (N, 1280) and one label per row")
+    if batch_size < 2 or batch_size > trainer.max_n:
+        raise ValueError(f"batch_size outside 2..{trainer.max_n}")
+    rng = rng if rng is not None else np.random.RandomState(0)
+    starts = [s for s in range(0, y.size, batch_size) if min(batch_size, y.size - s) >= 2]
+    if not starts:
+        raise ValueError("not enough rows for one batch")
+    steps_per_epoch = -(-len(starts) // grad_accum)
+    total_steps = steps_per_epoch * epochs
+    gamma, alpha, ls = trainer.loss_settings
+    log: List[Dict[str, float]] = []
+    step, best, stale = 0, math.inf, 0
+    for epoch in range(1, epochs + 1):
+        t0 = time.time()
+        perm = rng.permutation(y.size)
+        loss_sum, correct, seen, cur_lr = 0.0, 0, 0, one_cycle_lr(step, total_steps, lr)
+        for bi, s in enumerate(starts):
+            idx = perm[s:s + batch_size]
+            xb, ya, yb, lam = x[idx], y[idx], None, 1.0
+            if mix_alpha > 0 and rng.random_sample() < 0.5:
+                lam = float(rng.beta(mix_alpha, mix_alpha))
+                lam = max(lam, 1.0 - lam)
+                p2 = rng.permutation(idx.size)
+                xb = (lam * xb + (1.0 - lam) * xb[p2]).astype(np.float32)
+                yb = ya[p2]
+            loss, logits = trainer.accumulate(xb, ya, yb, lam, 1.0 / grad_accum)
+            loss_sum += loss * idx.size
+            correct += int(((logits > 0) == (y[idx] > 0.5)).sum())
+            seen += idx.size
+            if (bi + 1) % grad_accum == 0 or bi + 1 == len(starts):
+                cur_lr = one_cycle_lr(step, total_steps, lr)
+                trainer.apply(cur_lr)
+                step += 1
+        entry = {"epoch": epoch, "train_loss": round(loss_sum / max(seen, 1), 5), "train_acc": round(correct / max(seen, 1), 4),
+                 "val_loss": None, "val_acc": None, "val_f1": None, "val_auc": None, "lr": cur_lr}
+        if val is not None:
+            vx, vy = np.asarray(val[0], np.float32), np.asarray(val[1], np.float32).reshape(-1)
+            vz = trainer.evaluate(vx, use_ema=True)
+            m = _metrics(vz.astype(np.float64), vy.astype(np.float64))
+            vloss = focal_loss(vz, vy, gamma, alpha, ls)
+            entry.update(val_loss=round(vloss, 5), val_acc=round(m["acc"], 4), val_f1=round(m["f1"], 4), val_auc=round(m["auc"], 4))
+        entry["time_seconds"] = round(time.time() - t0, 1)
+        log.append(entry)
+        if val is not None:
+            if vloss < best:
+                best, stale = vloss, 0
+            else:
+                stale += 1
+                if stale >= patience:
+                    break
+    return log
+
+
+# --------------------------------------------------------------------------- the trainer
+class HeadTrainer:
+    """A trainer opened on a handle (`dfd_head_train_begin` .. `_end`); use as a context manager or `close()` it.
+
+    `model_or_handle`: a `DeepfakeEfficientNet` (its handle and state dict are used) or a `_lib.Handle` with
+    `state_dict` (reference key names, at least the ten ``net._fc.*`` tensors and the four running statistics).
+    `config`: fields of `dfd_head_config` - max_n, seed, dropout, beta1, beta2, eps, weight_decay, focal_gamma,
+    focal_alpha, label_smoothing, clip_norm, ema_decay, bn_momentum (defaults: train.py's)."""
+
+    def __init__(self, model_or_handle, state_dict: Optional[Mapping[str, np.ndarray]] = None, **config):
+        if isinstance(model_or_handle, _lib.Handle):
+            handle = model_or_handle
+            if state_dict is None:
+                raise ValueError("a bare handle needs the head's state_dict")
+        else:
+            handle = model_or_handle.handle
+            if state_dict is None:
+                state_dict = model_or_handle.state_dict()
+        sd = {(k if k.startswith("net.") else "net." + k): v for k, v in state_dict.items()}
+        params = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
+                  for k, f in KEYS.items()}
+        self._tracked = [int(np.asarray(sd[k])) if k in sd else 0 for k in TRACKED]
+        self.config = _lib.head_config(**config)
+        self.max_n = int(self.config.max_n)
+        self.loss_settings = (float(self.config.focal_gamma), float(self.config.focal_alpha), float(self.config.label_smoothing))
+        self._h = handle
+        self._open = False
+        handle.head_train_begin(params, self.config)
+        self._open = True
+        self.accumulates = 0
+        self.steps = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *_exc):
+        self.close()
+
+    def close(self):
+        if self._open:
+            self._open = False
+            if getattr(self._h, "_p", None):
+                self._h.head_train_end()
+
+    def accumulate(self, features, labels_a, labels_b=None, lam: float = 1.0, loss_scale: float = 1.0):
+        """one train-mode forward / backward added to the gradients -> (unscaled loss, logits (n,))"""
+        out = self._h.head_train_accumulate(features, labels_a, labels_b, lam, loss_scale)
+        self.accumulates += 1
+        return out
+
+    def apply(self, lr: float) -> float:
+        """clip, AdamW step, EMA update, gradients zeroed -> gradient norm before clipping"""
+        norm = self._h.head_train_apply(lr)
+        self.steps += 1
+        return norm
+
+    def evaluate(self, features, use_ema: bool = False) -> np.ndarray:
+        """eval-mode logits (n,) on the live or the EMA parameters; any n (chunks of max_n)"""
+        a = np.ascontiguousarray(np.asarray(features, np.float32))
+        if a.shape[0] == 0:
+            return np.empty(0, np.float32)
+        return np.concatenate([self._h.head_train_eval(a[i:i + self.max_n], use_ema) for i in range(0, a.shape[0], self.max_n)])
+
+    def export_state_dict(self, use_ema: bool = False) -> Dict[str, np.ndarray]:
+        """the head under the reference's names: ten ``net._fc.*`` parameters, four running statistics (always the live
+        ones) and the two ``num_batches_tracked`` counters"""
+        out = self._h.head_train_export(use_ema)
+        sd = {k: out[f] for k, f in KEYS.items()}
+        for k, t in zip(TRACKED, self._tracked):
+            sd[k] = np.array(t + self.accumulates, dtype=np.int64)
+        return sd
+
+    def commit(self, use_ema: bool = True):
+        """fold BatchNorm and swap the head the handle classifies with (`dfd_head_train_commit`)"""
+        self._h.head_train_commit(use_ema)
+
+    def fit(self, features, labels, epochs: int, batch_size: int = 32, grad_accum: int = 2, lr: float = 3e-4,
+            mix_alpha: float = 0.0, val=None, patience: int = 5, rng=None):
+        """`fit_loop` on this trainer"""
+        return fit_loop(self, features, labels, epochs, batch_size, grad_accum, lr, mix_alpha, val, patience, rng)
+
+
+__all__ = ["HeadTrainer", "fit_loop", "one_cycle_lr", "dropout_keep_mask", "dropout_rates", "focal_loss", "KEYS"]

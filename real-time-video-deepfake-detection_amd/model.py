@@ -3,8 +3,9 @@
 `DeepfakeEfficientNet` keeps the constructor and call surface of reference
 model.py:21-102 (``forward(rgb, freq=None) -> (B,1)`` logits, ``extract_features ->
 (B,1280)``, ``forward_with_projection``); the arithmetic runs in libdfd_hip.so
-(`dfd_classify_nchw`, include/dfd_hip.h).  It is inference-only (the reference's
-``.eval()`` path); there is no CPU implementation behind it.
+(`dfd_classify_nchw`, include/dfd_hip.h).  The forward is the reference's ``.eval()``
+path; `fit_head` trains the MLP head on the device with the backbone frozen
+(head_training.py).  There is no CPU implementation behind either.
 """
 from __future__ import annotations
 
@@ -78,8 +79,13 @@ class DeepfakeEfficientNet:
             log.info("pretrained=True: no ImageNet weights offline; using seeded random init (seed=%d)", seed)
 
     # ---- torch.nn.Module look-alikes used by the reference call sites
-    def eval(self):
+    def train(self, mode: bool = True):
+        """signature parity only: the forward is always the eval path; training goes through `fit_head`"""
+        self.training = bool(mode)
         return self
+
+    def eval(self):
+        return self.train(False)
 
     def to(self, *_a, **_k):
         return self
@@ -143,6 +149,32 @@ class DeepfakeEfficientNet:
     def forward_with_projection(self, rgb_input, freq_input=None):
         """reference model.py:91-98"""
         return self.forward(rgb_input), None
+
+    def fit_head(self, images_or_features, labels, *, epochs: int = 20, val=None, commit_ema: bool = True,
+                 trainer_config: Optional[Mapping] = None, **fit_kw):
+        """Train the 1280 -> 512 -> 256 -> 1 head on this engine's own pooled features and swap it in.
+
+        `images_or_features`: (N,3,224,224) normalised RGB (features are extracted here, `max_batch` crops at a time) or
+        (N,1280) features; `val`: the same pair for validation, or None.  `trainer_config`: `HeadTrainer` settings
+        (seed, dropout, weight_decay, ...; max_n defaults to the batch size); `fit_kw`: `head_training.fit_loop`'s
+        (batch_size, grad_accum, lr, mix_alpha, patience, rng).  The trained head (EMA by default) is committed to the
+        open handle in place - the handle is NOT re-created - and `state_dict()` returns it from then on.  -> the log."""
+        from .head_training import HeadTrainer
+
+        def feats(x):
+            a = x.detach().cpu().numpy() if _is_torch(x) else np.asarray(x)
+            return np.ascontiguousarray(a, np.float32) if a.ndim == 2 else np.asarray(self.extract_features(a), np.float32)
+
+        cfg = dict(trainer_config or {})
+        cfg.setdefault("max_n", max(2, int(fit_kw.get("batch_size", 32))))
+        x = feats(images_or_features)
+        v = None if val is None else (feats(val[0]), np.asarray(val[1], np.float32))
+        y = labels.detach().cpu().numpy() if _is_torch(labels) else np.asarray(labels)
+        with HeadTrainer(self, **cfg) as tr:
+            log_ = tr.fit(x, y, epochs, val=v, **fit_kw)
+            tr.commit(use_ema=commit_ema)
+            self._state.update(tr.export_state_dict(use_ema=commit_ema))
+        return log_
 
     def get_feature_extractor(self):
         """reference model.py:100-102 (GradCAM hook target; descriptor only here)."""
