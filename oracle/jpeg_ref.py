@@ -217,7 +217,8 @@ def h2v1_fancy_upsample(p: np.ndarray) -> np.ndarray:
 
 def decode_from_coefficients(info: dict) -> np.ndarray:
     """What libjpeg does after entropy decoding, for the dict `_lib.jpeg_coefficients` returns: dequantise, islow
-    IDCT, crop each component plane to its real (downsampled) size, fancy upsample, YCbCr -> RGB.  -> BGR u8."""
+    IDCT, crop each component plane to its real (downsampled) size, fancy upsample (replication for chroma planes one or
+    two samples wide), YCbCr -> RGB.  -> BGR u8."""
     W, H, n = info["width"], info["height"], info["components"]
     planes, off = [], 0
     for c, (bw, bh, tq) in enumerate(info["comps"]):
@@ -232,7 +233,10 @@ def decode_from_coefficients(info: dict) -> np.ndarray:
     hmax, vmax = info["hmax"], info["vmax"]
     cw, ch = -(-W // hmax), -(-H // vmax)
     cb, cr = planes[1][:ch, :cw], planes[2][:ch, :cw]
-    if hmax == 2 and vmax == 2:
+    if hmax == 2 and cw <= 2:
+        # jdsample.c jinit_upsampler: fancy upsampling only for downsampled_width > 2; narrower planes are replicated
+        cb, cr = (np.repeat(np.repeat(p, 2, 1), vmax, 0) for p in (cb, cr))
+    elif hmax == 2 and vmax == 2:
         cb, cr = h2v2_fancy_upsample(cb), h2v2_fancy_upsample(cr)
     elif hmax == 2:
         cb, cr = h2v1_fancy_upsample(cb), h2v1_fancy_upsample(cr)

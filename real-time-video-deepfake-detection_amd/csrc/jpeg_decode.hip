@@ -86,12 +86,14 @@ __global__ __launch_bounds__(64) void jpeg_idct_kernel(JpegPlanes J, const uint1
 }
 
 // jdsample.c h2v2_fancy_upsample on a chroma plane with `cw` x `ch` real samples (row stride `cs`)
+// (jinit_upsampler picks the fancy routine only for downsampled_width > 2: a plane one or two samples wide is replicated,
+// horizontally AND vertically)
 __device__ __forceinline__ int fancy_h2v2(const uint8_t* p, int cs, int cw, int ch, int Y, int X) {
     const int i = Y >> 1, c = X >> 1;
+    if (cw <= 2) return p[(size_t)i * cs + c];
     const int nb = (Y & 1) ? (i + 1 < ch ? i + 1 : ch - 1) : (i > 0 ? i - 1 : 0);
     const uint8_t *r0 = p + (size_t)i * cs, *r1 = p + (size_t)nb * cs;
     const int cur = 3 * r0[c] + r1[c];
-    if (cw == 1) return (4 * cur + ((X & 1) ? 7 : 8)) >> 4;
     if ((X & 1) == 0) {
         if (c == 0) return (4 * cur + 8) >> 4;
         return (3 * cur + (3 * r0[c - 1] + r1[c - 1]) + 8) >> 4;
@@ -100,11 +102,11 @@ __device__ __forceinline__ int fancy_h2v2(const uint8_t* p, int cs, int cw, int 
     return (3 * cur + (3 * r0[c + 1] + r1[c + 1]) + 7) >> 4;
 }
 
-// jdsample.c h2v1_fancy_upsample
+// jdsample.c h2v1_fancy_upsample (downsampled_width > 2), h2v1_upsample (replication) below that
 __device__ __forceinline__ int fancy_h2v1(const uint8_t* p, int cs, int cw, int Y, int X) {
     const uint8_t* r = p + (size_t)Y * cs;
     const int c = X >> 1;
-    if (cw == 1) return r[0];
+    if (cw <= 2) return r[c];
     if ((X & 1) == 0) return c == 0 ? r[0] : (3 * r[c] + r[c - 1] + 1) >> 2;
     return c == cw - 1 ? r[c] : (3 * r[c] + r[c + 1] + 2) >> 2;
 }
@@ -196,7 +198,8 @@ __global__ __launch_bounds__(256) void jpeg_color4_kernel(JpegPlanes J, int mode
 // Per plane it loads chroma rows i - 1, i, i + 1 (clamped) at columns c0 - 1 .. c0 + 4 (one dword + two bytes per row) and
 // blends vertically once per column; clamping the neighbour indices reproduces fancy_h2v2's edge rules exactly (at the
 // first / last column 3 * cur + cur = 4 * cur).  22 loads and 12 dword stores for 16 pixels; the four-pixel kernel issues
-// 36 byte loads per 4 pixels.
+// 36 byte loads per 4 pixels.  (width % 8 == 0 means at least four chroma columns: libjpeg's replication of planes one or
+// two samples wide, fancy_h2v2's first line, cannot apply here.)
 __global__ __launch_bounds__(256) void jpeg_color420_kernel(JpegPlanes J, int width, int height, uint8_t* __restrict__ out, int out_stride,
                                                             size_t plane_stride, size_t out_frame_stride) {
     const int x0 = 8 * (blockIdx.x * 256 + threadIdx.x), i = blockIdx.y;
@@ -444,7 +447,8 @@ static bool jpeg_same_tables(const Parsed& A, const ScanLayout& LA, const Parsed
 
 // One batch on the device decoder, in two halves so that the caller decides where the wait goes:
 //   enqueue()  descriptors up, de-stuffing, rounds, scan, emit, IDCT, colour, verdicts down - nothing waits;
-//   finish()   AFTER the stream has been waited for: reads the verdicts; frames the device decoder does not vouch for
+//   finish()   AFTER the stream has been waited for: reads the verdicts; a batch with a frame that has not converged gets
+//              a second device pass (it waits for that); frames the device decoder does not vouch for
 //              go through the host decoder, their coefficients are uploaded and IDCT / colour run again (then it waits).
 struct JpegGpuJob {
     dfd_handle* h = nullptr;
@@ -460,8 +464,14 @@ struct JpegGpuJob {
     uint32_t* redone_h = nullptr;
     uint16_t* qd = nullptr;
     int16_t* coef = nullptr;
-    size_t chunks = 0;
+    size_t chunks = 0, ncblk = 0;
     std::vector<char> on_host;
+    JgFrame* Fd = nullptr;                       // the device images enqueue() set up (decode_passes reads them)
+    JgTableSet* Td = nullptr;
+    uint16_t* cmd = nullptr;
+    uint8_t* dsd = nullptr;
+    uint32_t* segtab = nullptr;
+    JgChunks S{};
 
     int idct_colour() {
         const Parsed& P0 = (*P)[0];
@@ -499,6 +509,26 @@ struct JpegGpuJob {
         else
             hipLaunchKernelGGL(jpeg_color_kernel, dim3((P0.width + 255) / 256, P0.height, n), dim3(256), 0, s, J, mode, P0.width,
                                P0.height, frames_dev, P0.width * 3, W.plane_stride, fstride);
+        DFD_HIP_TRY(h, hipGetLastError());
+        return DFD_OK;
+    }
+
+    // rounds, scan, emit on the de-stuffed scans; verdicts down.  `rst`: the RST = true instantiations - what a batch with
+    // restart-interval files needs, and the round kernel that also iterates inside a launch (finish() asks for it again)
+    int decode_passes(bool rst) {
+        hipStream_t s = this->s ? this->s : h->stream;
+        DFD_HIP_TRY(h, hipMemsetAsync(S.redone, 0, 4 * JG_MAX_ROUNDS, s));
+        if (ncblk) {
+            for (int r = 0; r < rounds; ++r) {
+                if (rst) hipLaunchKernelGGL(jg_round_kernel<true>, dim3((unsigned)ncblk), dim3(JG_CB), 0, s, dsd, Fd, Td, cmd, S, r, segtab);
+                else hipLaunchKernelGGL(jg_round_kernel<false>, dim3((unsigned)ncblk), dim3(JG_CB), 0, s, dsd, Fd, Td, cmd, S, r, segtab);
+            }
+            hipLaunchKernelGGL(jg_scan_kernel, dim3(n), dim3(1024), 0, s, Fd, S, rounds - 1, segtab);
+            if (rst) hipLaunchKernelGGL(jg_emit_kernel<true>, dim3((unsigned)ncblk), dim3(JG_CB), 0, s, dsd, Fd, Td, cmd, S, coef, segtab);
+            else hipLaunchKernelGGL(jg_emit_kernel<false>, dim3((unsigned)ncblk), dim3(JG_CB), 0, s, dsd, Fd, Td, cmd, S, coef, segtab);
+        }
+        DFD_HIP_TRY(h, hipMemcpyAsync(Fback, Fd, sizeof(JgFrame) * (size_t)n, hipMemcpyDeviceToHost, s));
+        DFD_HIP_TRY(h, hipMemcpyAsync(redone_h, S.redone, 4 * JG_MAX_ROUNDS, hipMemcpyDeviceToHost, s));
         DFD_HIP_TRY(h, hipGetLastError());
         return DFD_OK;
     }
@@ -564,10 +594,10 @@ struct JpegGpuJob {
             for (uint32_t b = 0; b < F.ndsblk; ++b) bm[dsblk++] = (uint16_t)i;
             for (int c = 0; c < 3; ++c) memcpy(qh + (size_t)i * 192 + 64 * c, PP[i].q[PP[i].comp[c < PP[i].ncomp ? c : 0].tq], 128);
         }
-        JgFrame* Fd = reinterpret_cast<JgFrame*>(work + W.frames);
-        JgTableSet* Td = reinterpret_cast<JgTableSet*>(work + W.tabs);
+        Fd = reinterpret_cast<JgFrame*>(work + W.frames);
+        Td = reinterpret_cast<JgTableSet*>(work + W.tabs);
         uint16_t* bmd = reinterpret_cast<uint16_t*>(work + W.blkmap);
-        uint16_t* cmd = reinterpret_cast<uint16_t*>(work + W.cblkmap);
+        cmd = reinterpret_cast<uint16_t*>(work + W.cblkmap);
         qd = reinterpret_cast<uint16_t*>(work + W.q);
         DFD_HIP_TRY(h, hipMemcpyAsync(Fd, Fh, sizeof(JgFrame) * (size_t)n, hipMemcpyHostToDevice, s));
         if (nsets) DFD_HIP_TRY(h, hipMemcpyAsync(Td, Th, sizeof(JgTableSet) * (size_t)nsets, hipMemcpyHostToDevice, s));
@@ -576,7 +606,6 @@ struct JpegGpuJob {
         DFD_HIP_TRY(h, hipMemcpyAsync(qd, qh, (size_t)n * 192 * 2, hipMemcpyHostToDevice, s));
         coef = reinterpret_cast<int16_t*>(work + W.coef);
         DFD_HIP_TRY(h, hipMemsetAsync(coef, 0, W.coef_stride * 2 * (size_t)n, s));
-        JgChunks S;
         S.st = reinterpret_cast<uint2*>(work + W.st);
         S.en[0] = reinterpret_cast<uint2*>(work + W.en0);
         S.en[1] = reinterpret_cast<uint2*>(work + W.en1);
@@ -587,12 +616,12 @@ struct JpegGpuJob {
         S.err = work + W.err;
         S.rs = reinterpret_cast<uint2*>(work + W.rs);
         S.redone = reinterpret_cast<uint32_t*>(work + W.redone);
-        DFD_HIP_TRY(h, hipMemsetAsync(S.redone, 0, 4 * JG_MAX_ROUNDS, s));
         rounds = h->jpeg_rounds < 2 ? 2 : (h->jpeg_rounds > JG_MAX_ROUNDS ? JG_MAX_ROUNDS : h->jpeg_rounds);
-        uint8_t* dsd = work + W.ds;
+        dsd = work + W.ds;
         uint32_t* removed = reinterpret_cast<uint32_t*>(work + W.removed);
         uint32_t* markers = reinterpret_cast<uint32_t*>(work + W.markers);
-        uint32_t* segtab = reinterpret_cast<uint32_t*>(work + W.segtab);
+        segtab = reinterpret_cast<uint32_t*>(work + W.segtab);
+        ncblk = cblk;
         // a batch without restart-interval files runs the RST = false instantiations: the kernels of the restart-less decoder
         const bool rst = W.any_restart;
         if (dsblk) {
@@ -606,18 +635,8 @@ struct JpegGpuJob {
                                    markers, segtab);
             }
         }
-        if (cblk) {
-            for (int r = 0; r < rounds; ++r) {
-                if (rst) hipLaunchKernelGGL(jg_round_kernel<true>, dim3((unsigned)cblk), dim3(JG_CB), 0, s, dsd, Fd, Td, cmd, S, r, segtab);
-                else hipLaunchKernelGGL(jg_round_kernel<false>, dim3((unsigned)cblk), dim3(JG_CB), 0, s, dsd, Fd, Td, cmd, S, r, segtab);
-            }
-            hipLaunchKernelGGL(jg_scan_kernel, dim3(n), dim3(1024), 0, s, Fd, S, rounds - 1, segtab);
-            if (rst) hipLaunchKernelGGL(jg_emit_kernel<true>, dim3((unsigned)cblk), dim3(JG_CB), 0, s, dsd, Fd, Td, cmd, S, coef, segtab);
-            else hipLaunchKernelGGL(jg_emit_kernel<false>, dim3((unsigned)cblk), dim3(JG_CB), 0, s, dsd, Fd, Td, cmd, S, coef, segtab);
-        }
-        DFD_HIP_TRY(h, hipMemcpyAsync(Fback, Fd, sizeof(JgFrame) * (size_t)n, hipMemcpyDeviceToHost, s));
-        DFD_HIP_TRY(h, hipMemcpyAsync(redone_h, S.redone, 4 * JG_MAX_ROUNDS, hipMemcpyDeviceToHost, s));
-        DFD_HIP_TRY(h, hipGetLastError());
+        const int rc = decode_passes(rst);
+        if (rc) return rc;
         return idct_colour();
     }
 
@@ -629,6 +648,20 @@ struct JpegGpuJob {
                     W.any_restart ? " (restart intervals)" : "", chunks, chunk_bytes);
             for (int r = 0; r < rounds; ++r) fprintf(stderr, " %u", redone_h[r]);
             fprintf(stderr, "\n");
+        }
+        // A frame whose lanes have not reached the fixed point after `rounds` launches - a scan that hardly resynchronises:
+        // nearly all codes of Annex K's tables with their symbols reversed have one length, and the true state then moves one
+        // chunk per launch - gets a second pass with the round kernel that also iterates INSIDE a launch (the RST = true
+        // instantiation; a frame without restart interval has no segment table entry to meet there): 16 chunks of a block
+        // per launch whatever the data.  Nothing of this runs for a batch that converged.
+        bool again = false;
+        if (!W.any_restart)
+            for (int i = 0; i < n; ++i) again = again || (!on_host[i] && Fback[i].status != JG_OK);
+        if (again) {
+            if (getenv("DFD_JPEG_VERBOSE")) fprintf(stderr, "[dfd] jpeg device entropy: not at the fixed point after %d rounds: second pass\n", rounds);
+            const int rc = decode_passes(true);
+            if (rc) return rc;
+            DFD_HIP_TRY(h, hipStreamSynchronize(this->s ? this->s : h->stream));
         }
         int host_decoded = 0;
         for (int i = 0; i < n; ++i) {
@@ -648,7 +681,7 @@ struct JpegGpuJob {
             ++host_decoded;
         }
         if (host_decoded_out) *host_decoded_out = host_decoded;
-        if (host_decoded) {
+        if (host_decoded || again) {
             const int rc = idct_colour();
             if (rc) return rc;
             DFD_HIP_TRY(h, hipStreamSynchronize(this->s ? this->s : h->stream));

@@ -88,7 +88,8 @@ inline int parse_headers(dfd_handle* h, const uint8_t* d, size_t len, Parsed* P)
     if (len < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(h, DFD_ERR_ARG, "decode_jpeg: not a JPEG (no SOI)");
     size_t pos = 2;
     P->end = d + len;
-    bool have_sof = false;
+    bool have_sof = false, jfif = false, adobe = false;
+    int adobe_transform = 0;
     while (pos + 4 <= len) {
         if (d[pos] != 0xFF) return fail(h, DFD_ERR_ARG, "decode_jpeg: marker expected at byte %zu", pos);
         while (pos < len && d[pos] == 0xFF) ++pos;                 // fill bytes
@@ -149,6 +150,10 @@ inline int parse_headers(dfd_handle* h, const uint8_t* d, size_t len, Parsed* P)
             have_sof = true;
         } else if (m >= 0xC2 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
             return fail(h, DFD_ERR_UNSUPPORTED, "decode_jpeg: SOF%d (progressive / lossless / arithmetic) is not decoded on the GPU path", m - 0xC0);
+        } else if (m == 0xE0) {                                    // APP0 (jdmarker.c examine_app0)
+            if (n >= 14 && !memcmp(s, "JFIF", 5)) jfif = true;
+        } else if (m == 0xEE) {                                    // APP14 (examine_app14)
+            if (n >= 12 && !memcmp(s, "Adobe", 5)) { adobe = true; adobe_transform = s[11]; }
         } else if (m == 0xDD) {
             if (n >= 2) P->restart = be16(s);
         } else if (m == 0xDA) {                                    // SOS
@@ -174,6 +179,13 @@ inline int parse_headers(dfd_handle* h, const uint8_t* d, size_t len, Parsed* P)
         const bool ok = B.h == 1 && B.v == 1 && R.h == 1 && R.v == 1 &&
                         ((Y.h == 1 && Y.v == 1) || (Y.h == 2 && Y.v == 1) || (Y.h == 2 && Y.v == 2));
         if (!ok) return fail(h, DFD_ERR_UNSUPPORTED, "decode_jpeg: sampling %dx%d,%dx%d,%dx%d", Y.h, Y.v, B.h, B.v, R.h, R.v);
+        // the colour space of three components (jdapimin.c default_decompress_parms): JFIF says YCbCr; without it Adobe's
+        // transform byte decides (0: RGB); without either the component ids 'R','G','B' mean RGB; anything else is YCbCr.
+        // The device half converts YCbCr only: RGB samples go back to the caller's own decoder.
+        if (!jfif && adobe && adobe_transform == 0)
+            return fail(h, DFD_ERR_UNSUPPORTED, "decode_jpeg: RGB samples (Adobe marker with transform 0), only YCbCr is decoded on the GPU path");
+        if (!jfif && !adobe && Y.id == 'R' && B.id == 'G' && R.id == 'B')
+            return fail(h, DFD_ERR_UNSUPPORTED, "decode_jpeg: RGB samples (component ids R, G, B), only YCbCr is decoded on the GPU path");
     }
     P->hmax = P->comp[0].h;
     P->vmax = P->comp[0].v;

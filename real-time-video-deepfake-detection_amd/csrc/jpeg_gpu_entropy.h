@@ -15,7 +15,10 @@
 //      rounds count blocks and sum DC differences per component, nothing is written;
 //   3. jg_scan_kernel: per frame, prefix sums over the chunks give every chunk its first block index and its DC
 //      predictions; it also CHECKS the fixed point (start of chunk t == end of chunk t - 1, slot == block index mod
-//      blocks per MCU, block total == the frame's) - a frame that fails any check is decoded by the host path instead;
+//      blocks per MCU, block total == the frame's) - a frame that fails any check gets ONE more pass with the round
+//      kernel that also iterates inside a launch (RST = true below; jpeg_decode.hip JpegGpuJob::finish): a scan whose
+//      codes nearly all have one length hardly resynchronises, and the true state then moves one chunk per launch.  A
+//      frame that fails again is decoded by the host path instead;
 //   4. jg_emit_kernel decodes every chunk once more from its true start and writes the coefficients (natural order,
 //      DC integrated) where the IDCT kernel reads them; the buffer is zeroed first (most coefficients are zero).
 //

@@ -113,14 +113,16 @@ def component_planes(img: np.ndarray, subsampling):
     return out, (mx, my)
 
 
-def scan_blocks(img: np.ndarray, quality: int, subsampling):
+def scan_blocks(img: np.ndarray, quality: int, subsampling, qtabs=None):
     """The quantised blocks in the order the scan codes them: (coef (n, 64) in zig-zag order, comp (n,) component of each
-    block, blocks per MCU, MCU count)."""
+    block, blocks per MCU, MCU count).  qtabs: one 8x8 table per component instead of the two that `quality` scales."""
     planes, (mx, my) = component_planes(img, subsampling)
     tabs = [quant_table(J._LUMA, quality), quant_table(J._CHROMA, quality)]
+    if qtabs is None:
+        qtabs = [tabs[0 if c == 0 else 1] for c in range(len(planes))]
     per_comp = []
     for c, (p, wb, hb, h, v) in enumerate(planes):
-        q = J.quantize(J.fdct_islow(J._blocks(p - 128)), tabs[0 if c == 0 else 1]).reshape(hb, wb, 64)[..., ZIGZAG]
+        q = J.quantize(J.fdct_islow(J._blocks(p - 128)), qtabs[c]).reshape(hb, wb, 64)[..., ZIGZAG]
         full = np.zeros((my * v, mx * h, 64), np.int64)
         full[:hb, :wb] = q
         # dummy blocks (jccoefct.c compress_data): right of the real ones first, then whole dummy rows from the block
@@ -147,9 +149,13 @@ def _nbits(a):
 _TABLES = [(_derive(DC_LUMA), _derive(AC_LUMA)), (_derive(DC_CHROMA), _derive(AC_CHROMA))]
 
 
-def block_symbols(coef, comp, bpm, restart_blocks):
+def block_symbols(coef, comp, bpm, restart_blocks, tables=None, comp_table=None):
     """Per block 65 slots (DC, 63 AC positions, EOB) of (bits, length <= 59): the exact bit string of the block is the
-    slots' bits in order.  Also the statistics the corpus asserts on."""
+    slots' bits in order.  Also the statistics the corpus asserts on.
+    tables: [((DC bits, symbols), (AC bits, symbols))] and comp_table: component -> index into it, instead of Annex K's
+    luma pair for component 0 and chroma pair for the others.  A slot is built in 62 bits: where three ZRLs, a code and
+    its value bits of some other table need more, the call fails; so it does where a block needs a symbol its table lacks."""
+    derived = _TABLES if tables is None else [(_derive(d), _derive(a)) for d, a in tables]
     n = coef.shape[0]
     mcu = np.arange(n) // bpm
     pred = np.zeros(n, np.int64)
@@ -161,20 +167,21 @@ def block_symbols(coef, comp, bpm, restart_blocks):
             first = np.concatenate([[True], (mcu[idx][1:] // restart_blocks) != (mcu[idx][:-1] // restart_blocks)])
             prev[first] = 0
         pred[idx] = prev
-    t = (comp > 0).astype(np.int64)
+    t = (comp > 0).astype(np.int64) if comp_table is None else np.asarray(comp_table, np.int64)[comp]
     val = np.zeros((n, 65), np.uint64)
     ln = np.zeros((n, 65), np.int64)
     # DC
     diff = coef[:, 0] - pred
     s = _nbits(diff)
-    dco = np.stack([_TABLES[0][0][0], _TABLES[1][0][0]])
-    dsi = np.stack([_TABLES[0][0][1], _TABLES[1][0][1]])
+    dco = np.stack([tab[0][0] for tab in derived])
+    dsi = np.stack([tab[0][1] for tab in derived])
+    assert (dsi[t, s] > 0).all(), "a DC category without a code"
     extra = np.where(diff < 0, diff - 1, diff) & ((1 << s) - 1)
     val[:, 0] = ((dco[t, s] << s) | extra).astype(np.uint64)
     ln[:, 0] = dsi[t, s] + s
     # AC
-    aco = np.stack([_TABLES[0][1][0], _TABLES[1][1][0]])
-    asi = np.stack([_TABLES[0][1][1], _TABLES[1][1][1]])
+    aco = np.stack([tab[1][0] for tab in derived])
+    asi = np.stack([tab[1][1] for tab in derived])
     ac = coef[:, 1:]
     nz = ac != 0
     pos = np.arange(1, 64)[None, :]
@@ -199,6 +206,9 @@ def block_symbols(coef, comp, bpm, restart_blocks):
     val[:, 1:64] = np.where(nz, v, 0).astype(np.uint64)
     ln[:, 1:64] = np.where(nz, l, 0)
     eob = lastnz[:, -1] < 63
+    assert (asi[tt, sym][nz] > 0).all() and (np.broadcast_to(asi[tt, 0xF0], nz.shape)[nz & (zrl > 0)] > 0).all() and (asi[t, 0][eob] > 0).all(), \
+        "a run/size symbol without a code"
+    assert int(np.where(nz, l, 0).max(initial=0)) <= 62, "a slot longer than 62 bits"
     val[:, 64] = np.where(eob, aco[t, 0], 0).astype(np.uint64)
     ln[:, 64] = np.where(eob, asi[t, 0], 0)
     stats = dict(zrl=int((zrl * nz).sum()), max_ac_size=int((sz * nz).max(initial=0)),

@@ -107,6 +107,22 @@ def test_good_files_decode_clean_and_independent_of_chunking(driver, tmp_path, p
     assert _fields(driver("jpeg", p))["rc"] == "0"
 
 
+def test_stream_corpus_decodes_clean_and_independent_of_chunking(driver, tmp_path):
+    """every file of tests/jpeg_stream_cases.py - valid dialects Pillow never writes: reversed Annex K tables (13 to 16-bit
+    codes, a fifth of the scan stuffed), 2-bit blocks, six tables, table ids 2 and 3, 16-bit DQT, fill bytes, a 65,533-byte
+    APPn, bytes behind EOI, hand-made coefficients - through the stand-alone driver at 1 and 7 chunks: a clean exit, the
+    expected status, the same hash"""
+    import jpeg_stream_cases as C
+
+    for row in C.ROWS:
+        for i, f in enumerate(C.files(row.name)):
+            p = tmp_path / f"{row.name}-{i}.jpg"
+            p.write_bytes(f.data)
+            one = _fields(driver("jpeg", p, 1))
+            assert int(one["rc"]) == (0 if row.kind == "decode" else -7), (row.name, i, one)
+            assert _fields(driver("jpeg", p, 7)) == one, (row.name, i)
+
+
 def test_truncations_and_header_edits_are_rejected_without_memory_errors(driver, tmp_path):
     data = _jpeg(_img(128, 128, 33), quality=90)
     sos = data.index(b"\xff\xda")
