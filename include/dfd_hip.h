@@ -720,6 +720,70 @@ int dfd_head_train_tap(dfd_handle* h, const char* name, float* out, size_t capac
 int dfd_head_train_commit(dfd_handle* h, int use_ema);
 int dfd_head_train_end(dfd_handle* h);
 
+/* ---- train-time image augmentation ------------------------------------------------------------
+ * The reference's training transform (train.py:462-489, 298-349) on `n` uint8 RGB crops of one size H x W (multiples
+ * of 16 in 32..512): Pillow's bilinear Resize to (T + 20)^2, RandomCrop to T x T and flip, ColorJitter in a per-image
+ * order, RandomGrayscale, RandomRotation, RandomAffine, RandomPerspective, GaussianBlur, ToTensor + Normalize,
+ * RandomErasing, GaussianNoise and Mixup / CutMix over the batch, T = out_size (12..492).  The host draws every
+ * parameter (train_augment.draw_batch) and passes one row per image; the kernels draw nothing but the noise, a
+ * stateless hash of (seed, counter, image, element) specified by train_augment.noise_normal.  A stage whose flag is
+ * clear leaves the image bit-identical; an image without DFD_AUG_CROP is resized straight to T x T (the reference's
+ * validation transform).  The chain opens with the reference's JPEG round trip (DFD_AUG_JPEG, train.py:282-295): libjpeg
+ * as cv2 runs it - 4:2:0, Annex K tables scaled by the quality, islow DCT, fancy upsampling - without the lossless
+ * entropy coding.  The reference hands its RGB array to an encoder that reads BGR, so its result is the round trip of
+ * the channel-reversed image; DFD_AUG_JPEG_RGB asks for the round trip of the image itself instead.  Sizes outside the
+ * ranges above, n < 1, a quality outside 1..100, an unknown jitter op, an erase box outside the image and a mix
+ * permutation outside 0..n-1 are DFD_ERR_ARG; nothing is kept from a refused call. */
+enum {
+    DFD_AUG_JPEG = 1, DFD_AUG_CROP = 2, DFD_AUG_FLIP = 4, DFD_AUG_GRAY = 8, DFD_AUG_ROTATE = 16, DFD_AUG_AFFINE = 32,
+    DFD_AUG_PERSPECTIVE = 64, DFD_AUG_BLUR = 128, DFD_AUG_ERASE = 256, DFD_AUG_NOISE = 512, DFD_AUG_JPEG_RGB = 1024
+};
+enum { DFD_JITTER_NONE = 0, DFD_JITTER_BRIGHTNESS = 1, DFD_JITTER_CONTRAST = 2, DFD_JITTER_SATURATION = 3, DFD_JITTER_HUE = 4 };
+enum { DFD_MIX_NONE = 0, DFD_MIX_MIXUP = 1, DFD_MIX_CUTMIX = 2 };
+typedef struct dfd_train_aug_image {
+    double rotate[6];               /* inverse matrix of Image.rotate (NEAREST, fill 0)                              */
+    double affine[6];               /* inverse matrix of RandomAffine (NEAREST, fill 0)                              */
+    double perspective[8];          /* Pillow PERSPECTIVE coefficients (BILINEAR, fill 0)                            */
+    unsigned int flags;             /* DFD_AUG_*                                                                     */
+    int jpeg_quality;               /* 1..100                                                                        */
+    int crop_x, crop_y;             /* RandomCrop offset inside the (T + 20)^2 image, 0..20                          */
+    int jitter_op[4];               /* DFD_JITTER_* of the four ColorJitter slots, in the order they run             */
+    float jitter_factor[4];
+    float blur_k[2];                /* float32 normalised Gaussian: outer tap, centre tap                            */
+    int erase[4];                   /* x, y, w, h of the erased rectangle                                            */
+    float noise_std;
+    int reserved;
+} dfd_train_aug_image;
+typedef struct dfd_train_aug_batch {
+    unsigned long long seed, counter;   /* noise key                                                                 */
+    const int* perm;                    /* partner of every image (n entries); NULL allowed when mix_kind = 0        */
+    int mix_kind;                       /* DFD_MIX_*                                                                 */
+    float lam;                          /* Mixup: lam x + (1 - lam) x[perm]                                          */
+    int box[4];                         /* CutMix: x1, y1, x2, y2 (exclusive) copied from the partner                */
+} dfd_train_aug_batch;
+/* the chain alone: rgb_host [n][H][W][3] -> nchw_out_host [n][3][T][T] float32 */
+int dfd_train_augment(dfd_handle* h, const unsigned char* rgb_host, int n, int H, int W, int out_size,
+                      const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, float* nchw_out_host);
+/* the chain at T = 224 on all n images, then the backbone in chunks of max_batch -> feat_out_host [n][1280].  Only the
+ * uint8 crops are uploaded; on_device = 1: `rgb` is device memory (dfd_device_alloc), e.g. a resident training set. */
+int dfd_train_augment_features(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
+                               const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, float* feat_out_host);
+/* crops idx[0 .. n) (host ints, each in 0 .. n_src - 1) of a resident set rgb_dev [n_src][H][W][3] -> out_dev [n][H][W][3],
+ * both device memory (dfd_device_alloc), enqueued on the handle's stream: the shuffled batch of a training set that stays
+ * in HBM, ready for dfd_train_augment_features(on_device = 1).  An index out of range is DFD_ERR_ARG. */
+int dfd_train_augment_gather(dfd_handle* h, const unsigned char* rgb_dev, int n_src, int H, int W, const int* idx, int n,
+                             unsigned char* out_dev);
+/* test tap of the noise hash, on the host: the two uint32 words behind elements first .. first + count - 1 of image `row`
+ * (the functions the noise kernel calls; train_augment.noise_words is their specification).  No handle, no GPU. */
+int dfd_train_augment_noise_words(unsigned long long seed, unsigned long long counter, int row, unsigned int first,
+                                  unsigned int count, unsigned int* u1_out, unsigned int* u2_out);
+/* test tap: the images after the named stage - "jpeg" uint8 [n][H][W][3], "resize" uint8 [n][(T+20)^2 * 3] slots (an image without DFD_AUG_CROP
+ * fills the first T * T * 3 bytes of its slot), "crop", "jitter0".."jitter3", "gray", "rotate", "affine", "perspective",
+ * "blur" uint8 [n][T][T][3]; "norm", "erase", "noise", "mix" float32 [n][3][T][T].  capacity in bytes. */
+int dfd_train_augment_tap(dfd_handle* h, const unsigned char* rgb_host, int n, int H, int W, int out_size,
+                          const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, const char* stage_name,
+                          void* out, size_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,13 @@ SIGNATURES = {
     "dfd_head_train_tap": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]),
     "dfd_head_train_commit": (C.c_int, [C.c_void_p, C.c_int]),
     "dfd_head_train_end": (C.c_int, [C.c_void_p]),
+    "dfd_train_augment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dfd_train_augment_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "dfd_train_augment_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "dfd_train_augment_noise_words": (C.c_int, [C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]),
+    "dfd_train_augment_tap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_char_p, C.c_void_p, C.c_size_t]),
 }
 
 
@@ -313,6 +320,17 @@ def jpeg_coefficients(data: bytes):
             "comps": [(info[5 + 3 * c], info[6 + 3 * c], info[7 + 3 * c]) for c in range(n)], "qtables": q, "coef": coef}
 
 
+def train_augment_noise_words(seed: int, counter: int, row: int, first: int, count: int):
+    """the two uint32 words behind elements first .. first + count - 1 of image `row`, from the functions `aug_noise_kernel`
+    calls (host side, no GPU): what train_augment.noise_words specifies"""
+    u1, u2 = np.empty(count, np.uint32), np.empty(count, np.uint32)
+    rc = load().dfd_train_augment_noise_words(int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1), int(row), int(first), int(count),
+                                              _ptr(u1), _ptr(u2))
+    if rc != 0:
+        raise DfdError(rc, "train_augment_noise_words: bad arguments")
+    return u1, u2
+
+
 class DeviceBuffer:
     """A raw HBM allocation owned by a Handle."""
 
@@ -445,6 +463,84 @@ class Handle:
         a = self._as_nchw(x)
         out = np.empty((a.shape[0], 1280), dtype=np.float32)
         self._check(self._lib.dfd_extract_features(self._p, _ptr(a), a.shape[0], _ptr(out)))
+        return out
+
+    # -- train-time augmentation (include/dfd_hip.h "train-time image augmentation"; train_augment.draw_batch makes the tables)
+    @staticmethod
+    def _aug_tables(n, rows, batch):
+        """(rows array, batch record with its partner pointer set, the partner array) for `n` images - kept alive by the caller"""
+        from . import train_augment as TA
+        r = np.ascontiguousarray(np.asarray(rows, dtype=TA.ROW_DTYPE)).reshape(-1)
+        if r.size != n:
+            raise ValueError(f"{n} images but {r.size} parameter rows")
+        b = np.array(batch, dtype=TA.BATCH_DTYPE).reshape(())
+        partners = TA.batch_perm(batch)
+        if partners is not None:
+            partners = np.ascontiguousarray(np.asarray(partners, np.int32))
+            if partners.size != n:
+                raise ValueError("one mix partner per image")
+        b["perm"] = partners.ctypes.data if partners is not None else 0
+        return r, b, partners
+
+    @classmethod
+    def _aug_args(cls, rgb, rows, batch):
+        """(uint8 (n,H,W,3) array, rows array, batch record, partner array)"""
+        a = np.ascontiguousarray(np.asarray(rgb))
+        if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3:
+            raise ValueError(f"expected (n,H,W,3) uint8 crops, got {a.dtype} {a.shape}")
+        return (a,) + cls._aug_tables(a.shape[0], rows, batch)
+
+    AUG_U8_STAGES = ("jpeg", "resize", "crop", "jitter0", "jitter1", "jitter2", "jitter3", "gray", "rotate", "affine", "perspective", "blur")
+    AUG_F32_STAGES = ("norm", "erase", "noise", "mix")
+
+    def train_augment(self, rgb, rows, batch, out_size: int = 224) -> np.ndarray:
+        """the augmentation chain alone: (n,H,W,3) uint8 -> (n,3,T,T) float32"""
+        a, r, b, _keep = self._aug_args(rgb, rows, batch)
+        out = np.empty((a.shape[0], 3, int(out_size), int(out_size)), np.float32)
+        self._check(self._lib.dfd_train_augment(self._p, _ptr(a), a.shape[0], a.shape[1], a.shape[2], int(out_size), _ptr(r), _ptr(b),
+                                                _ptr(out)))
+        return out
+
+    def train_augment_tap(self, rgb, rows, batch, stage: str, out_size: int = 224) -> np.ndarray:
+        """the images after `stage`: uint8 (n,T,T,3) ("jpeg": (n,H,W,3); "resize": (n,T+20,T+20,3) slots), float32 (n,3,T,T)
+        from "norm" on"""
+        a, r, b, _keep = self._aug_args(rgb, rows, batch)
+        n, t = a.shape[0], int(out_size)
+        if stage in self.AUG_F32_STAGES:
+            out = np.empty((n, 3, t, t), np.float32)
+        elif stage == "jpeg":
+            out = np.empty(a.shape, np.uint8)
+        elif stage == "resize":
+            out = np.zeros((n, t + 20, t + 20, 3), np.uint8)
+        else:
+            out = np.empty((n, t, t, 3), np.uint8)
+        self._check(self._lib.dfd_train_augment_tap(self._p, _ptr(a), n, a.shape[1], a.shape[2], t, _ptr(r), _ptr(b), stage.encode(),
+                                                    _ptr(out), out.nbytes))
+        return out
+
+    def train_augment_gather(self, src: "DeviceBuffer", shape, idx, dst: "DeviceBuffer"):
+        """crops `idx` of the resident (N,H,W,3) uint8 set in `src` (`shape` = (N,H,W)) -> contiguous in `dst` (device to device)"""
+        n_src, hh, ww = (int(v) for v in shape)
+        i = np.ascontiguousarray(np.asarray(idx, np.int32)).reshape(-1)
+        if n_src * hh * ww * 3 > src.nbytes or i.size * hh * ww * 3 > dst.nbytes:
+            raise ValueError("shape larger than the device buffer")
+        self._check(self._lib.dfd_train_augment_gather(self._p, C.c_void_p(src.ptr), n_src, hh, ww, _ptr(i), i.size, C.c_void_p(dst.ptr)))
+
+    def train_augment_features(self, rgb, rows, batch, shape=None) -> np.ndarray:
+        """chain at 224 + backbone -> (n,1280) pooled features.  `rgb`: (n,H,W,3) uint8, or a DeviceBuffer holding such an
+        array with `shape` = (n,H,W) (a resident training set costs no upload)"""
+        if isinstance(rgb, DeviceBuffer):
+            n, hh, ww = (int(v) for v in shape)
+            if n * hh * ww * 3 > rgb.nbytes:
+                raise ValueError("shape larger than the device buffer")
+            r, b, _keep = self._aug_tables(n, rows, batch)
+            src, on_device = C.c_void_p(rgb.ptr), 1
+        else:
+            a, r, b, _keep = self._aug_args(rgb, rows, batch)
+            n, hh, ww = a.shape[:3]
+            src, on_device = _ptr(a), 0
+        out = np.empty((n, 1280), np.float32)
+        self._check(self._lib.dfd_train_augment_features(self._p, src, on_device, n, hh, ww, _ptr(r), _ptr(b), _ptr(out)))
         return out
 
     # -- head training (include/dfd_hip.h "classifier head training"; head_training.HeadTrainer is the front end)

@@ -168,6 +168,9 @@ struct dfd_handle {
     dfd::DevBuf jpeg_enc[6];             // dfd_encode_jpeg*: staged sources, tables + descriptors, coefficients, scan arrays,
                                          // the unstuffed bit buffer, the packed files (jpeg_encode.hip)
     dfd::DevBuf tap_buf;                 // fp32 staging for taps of bf16 buffers
+    dfd::DevBuf aug_idx;                 // dfd_train_augment_gather: the batch's indices
+    dfd::DevBuf aug_u8, aug_f32, aug_tab; // train-time augmentation (train_augment.hip): uint8 source + ping-pong regions, the
+                                         // float tensors, rows + resize tables + luma sums + partners
     std::map<const float*, unsigned short*> wsplit;   // fp32 weight tensor -> its three-plane bf16 split
     dfd::S6Table* gemm = nullptr;        // split-GEMM tile per shape (measured by dfd_warmup, heuristic otherwise)
     dfd::B0Prof prof;                    // layer events between profile_begin/end

@@ -4,6 +4,8 @@
 
 #include <cstdint>
 
+#include "pil_resize.h"
+
 namespace dfd {
 
 struct MtWindow { int x, y, w, h; };      // source window in pixels

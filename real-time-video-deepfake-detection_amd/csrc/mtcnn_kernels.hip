@@ -118,13 +118,6 @@ void launch_mt_heads(const float* f, const float* w1, const float* b1, const flo
 // extract_face for all crops of a step in two launches (blockIdx.y = crop): the horizontal pass of every crop whose
 // window is not 160 wide, then the vertical pass / plain copy / zero fill that completes each 160x160x3 face slot.
 // Per element the arithmetic is mt_pil_pass_kernel's.
-__device__ __forceinline__ uint8_t pil_tap_sum(const uint8_t* __restrict__ p, size_t step, const int* __restrict__ kk, int cnt) {
-    int ss = 1 << 21;
-    for (int k = 0; k < cnt; ++k) ss += kk[k] * (int)p[(size_t)k * step];
-    int v = ss >> 22;
-    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
-
 __global__ __launch_bounds__(256) void mt_extract_h_kernel(const MtFaceJob* __restrict__ jobs, const int* __restrict__ tables,
                                                            uint8_t* __restrict__ faces, uint8_t* __restrict__ tmp) {
     const MtFaceJob j = jobs[blockIdx.y];

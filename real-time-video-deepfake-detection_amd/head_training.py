@@ -6,7 +6,8 @@ in libdfd_hip.so (csrc/head_train.hip, `dfd_head_train_*` in include/dfd_hip.h);
 host: the learning-rate schedule, the specification of the dropout masks, the epoch loop and the state-dict names.
 
 Deviations from train.py: fp32 instead of AMP / GradScaler; the backbone is not fine-tuned; Mixup works on feature
-rows (no image-space Mixup / CutMix); a last batch of one row is dropped (BatchNorm1d needs two).
+rows unless `augment=` is given (then the crops are augmented on the device every epoch and Mixup / CutMix act on the
+images, train_augment.py); a last batch of one row is dropped (BatchNorm1d needs two).
 """
 from __future__ import annotations
 
@@ -130,8 +131,12 @@ def _metrics(logits: np.ndarray, labels: np.ndarray) -> Dict[str, float]:
 
 
 # --------------------------------------------------------------------------- the epoch loop
+_VAL_CHUNK = 256          # validation crops per `train_augment_features` call of fit_loop(augment=...)
+
+
 def fit_loop(trainer, features, labels, epochs: int, batch_size: int = 32, grad_accum: int = 2, lr: float = 3e-4,
-             mix_alpha: float = 0.0, val=None, patience: int = 5, rng=None) -> List[Dict[str, float]]:
+             mix_alpha: float = 0.0, val=None, patience: int = 5, rng=None, augment=None,
+             cutmix_alpha: float = 0.0) -> List[Dict[str, float]]:
     """train.py's `train_one_epoch` / `validate` loop over any object with `accumulate`, `apply`, `evaluate`,
     `max_n` and `loss_settings` (HeadTrainer; the tests' float64 oracle).  Returns a log shaped like
     weights/training_log.json: one dict per epoch (epoch, train_loss, train_acc, val_loss, val_acc, val_f1, val_auc,
@@ -144,10 +149,46 @@ def fit_loop(trainer, features, labels, epochs: int, batch_size: int = 32, grad_
 
     One optimizer step per `grad_accum` batches and at the last batch of an epoch (train.py:596); the rate of step k
     is one_cycle_lr(k, total optimizer steps, lr).  Validation (on `val` = (features, labels)) runs on the EMA
-    parameters as train.py:992-999 does; training stops after `patience` epochs without a lower validation loss."""
-    x = np.ascontiguousarray(np.asarray(features, np.float32))
+    parameters as train.py:992-999 does; training stops after `patience` epochs without a lower validation loss.
+
+    `augment=(extractor, policy)`: `features` (and `val[0]`) are (N, H, W, 3) uint8 crops (or `ResidentCrops`); every batch is augmented and
+    pushed through the backbone anew by `extractor.train_augment_features` (a `_lib.Handle`), `policy` a
+    `train_augment.AugmentPolicy`.  Draws then: first, when `val` is given, `draw_batch(AugmentPolicy.validation(), ...)`
+    for the validation crops (extracted once, before the first epoch); per epoch the permutation; per batch the mix
+    decision - `random_sample()` (mix when < 0.5) when mix_alpha > 0 or cutmix_alpha > 0, then, whenever
+    cutmix_alpha > 0 (mix_alpha = 0 included, as train.py:569 draws it), a second `random_sample()` (Mixup when < 0.5 and
+    mix_alpha > 0, else CutMix, train.py:566-576); with cutmix_alpha = 0 a mixed batch is always Mixup, as without augment;
+    Mixup draws `beta(mix_alpha, mix_alpha)` and `permutation(rows)`, CutMix `beta(cutmix_alpha, cutmix_alpha)`,
+    `permutation(rows)`, `randint(0, 225)` for cy and for cx (lam recomputed from the clipped box) - and then
+    `train_augment.draw_batch`'s draws for the batch.  Mixing happens in image space on the device; the trainer gets
+    (y, y[perm], lam).  Training accuracy is counted against the original labels.  Without `augment` nothing of this
+    runs: no draw is added (cutmix_alpha needs `augment`).  The crops are a host array or a
+    `train_augment.ResidentCrops` (the set uploaded once; each shuffled batch is gathered device to device); both give the
+    same bits.  Validation crops are extracted in chunks of 256 images."""
+    if augment is not None:
+        from . import train_augment as _ta
+        extractor, policy = augment
+        def crops_of(src, what):
+            src = src if isinstance(src, _ta.ResidentCrops) else np.ascontiguousarray(np.asarray(src))
+            if src.dtype != np.uint8 or src.ndim != 4 or src.shape[3] != 3:
+                raise ValueError(f"with augment= the {what} are (N, H, W, 3) uint8 crops")
+            return src
+
+        def extract(src, idx, rows, batch):
+            if isinstance(src, _ta.ResidentCrops):                 # device gather, no upload
+                buf, shape = src.gather(idx)
+                return extractor.train_augment_features(buf, rows, batch, shape=shape)
+            return extractor.train_augment_features(src[idx], rows, batch)
+
+        x = crops_of(features, "features")
+    else:
+        if cutmix_alpha > 0:
+            raise ValueError("cutmix_alpha needs augment= (CutMix acts on images)")
+        x = np.ascontiguousarray(np.asarray(features, np.float32))
+        if x.ndim != 2:
+            raise ValueError("features (N, 1280) and one label per row")
     y = np.asarray(labels, np.float32).reshape(-1)
-    if x.ndim != 2 or x.shape[0] != y.size:
+    if x.shape[0] != y.size:
         raise ValueError("features (N, 1280) and one label per row")
     if batch_size < 2 or batch_size > trainer.max_n:
         raise ValueError(f"batch_size outside 2..{trainer.max_n}")
@@ -160,14 +201,39 @@ def fit_loop(trainer, features, labels, epochs: int, batch_size: int = 32, grad_
     gamma, alpha, ls = trainer.loss_settings
     log: List[Dict[str, float]] = []
     step, best, stale = 0, math.inf, 0
+    if augment is not None and val is not None:
+        vimg = crops_of(val[0], "validation features")
+        vrows, vbatch = _ta.draw_batch(_ta.AugmentPolicy.validation(), rng, vimg.shape[0], vimg.shape[1], vimg.shape[2])
+        # no stage of the validation policy looks at another image: chunks bound the work memory of a call
+        val = (np.concatenate([extract(vimg, np.arange(i, min(i + _VAL_CHUNK, vimg.shape[0])), vrows[i:i + _VAL_CHUNK], vbatch)
+                               for i in range(0, vimg.shape[0], _VAL_CHUNK)]), val[1])
     for epoch in range(1, epochs + 1):
         t0 = time.time()
         perm = rng.permutation(y.size)
         loss_sum, correct, seen, cur_lr = 0.0, 0, 0, one_cycle_lr(step, total_steps, lr)
         for bi, s in enumerate(starts):
             idx = perm[s:s + batch_size]
-            xb, ya, yb, lam = x[idx], y[idx], None, 1.0
-            if mix_alpha > 0 and rng.random_sample() < 0.5:
+            ya, yb, lam = y[idx], None, 1.0
+            xb = x[idx] if augment is None else None
+            if augment is not None:
+                mix = None
+                if (mix_alpha > 0 or cutmix_alpha > 0) and rng.random_sample() < 0.5:
+                    which = rng.random_sample() if cutmix_alpha > 0 else 0.0
+                    if mix_alpha > 0 and which < 0.5:
+                        lam = float(rng.beta(mix_alpha, mix_alpha))
+                        lam = max(lam, 1.0 - lam)
+                        p2 = rng.permutation(idx.size)
+                        mix = (_ta.MIX_MIXUP, lam, p2)
+                    else:
+                        lam = float(rng.beta(cutmix_alpha, cutmix_alpha))
+                        p2 = rng.permutation(idx.size)
+                        cy, cx = int(rng.randint(0, 225)), int(rng.randint(0, 225))
+                        box, lam = _ta.cutmix_box(lam, cy, cx, 224)
+                        mix = (_ta.MIX_CUTMIX, lam, p2, box)
+                    yb = ya[p2]
+                rows, batch = _ta.draw_batch(policy, rng, idx.size, x.shape[1], x.shape[2], mix=mix)
+                xb = extract(x, idx, rows, batch)
+            elif mix_alpha > 0 and rng.random_sample() < 0.5:
                 lam = float(rng.beta(mix_alpha, mix_alpha))
                 lam = max(lam, 1.0 - lam)
                 p2 = rng.permutation(idx.size)
@@ -278,9 +344,10 @@ class HeadTrainer:
         self._h.head_train_commit(use_ema)
 
     def fit(self, features, labels, epochs: int, batch_size: int = 32, grad_accum: int = 2, lr: float = 3e-4,
-            mix_alpha: float = 0.0, val=None, patience: int = 5, rng=None):
+            mix_alpha: float = 0.0, val=None, patience: int = 5, rng=None, augment=None, cutmix_alpha: float = 0.0):
         """`fit_loop` on this trainer"""
-        return fit_loop(self, features, labels, epochs, batch_size, grad_accum, lr, mix_alpha, val, patience, rng)
+        return fit_loop(self, features, labels, epochs, batch_size, grad_accum, lr, mix_alpha, val, patience, rng, augment,
+                        cutmix_alpha)
 
 
 __all__ = ["HeadTrainer", "fit_loop", "one_cycle_lr", "dropout_keep_mask", "dropout_rates", "focal_loss", "KEYS"]

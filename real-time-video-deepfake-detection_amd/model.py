@@ -151,14 +151,18 @@ class DeepfakeEfficientNet:
         return self.forward(rgb_input), None
 
     def fit_head(self, images_or_features, labels, *, epochs: int = 20, val=None, commit_ema: bool = True,
-                 trainer_config: Optional[Mapping] = None, **fit_kw):
+                 trainer_config: Optional[Mapping] = None, augment=None, **fit_kw):
         """Train the 1280 -> 512 -> 256 -> 1 head on this engine's own pooled features and swap it in.
 
         `images_or_features`: (N,3,224,224) normalised RGB (features are extracted here, `max_batch` crops at a time) or
         (N,1280) features; `val`: the same pair for validation, or None.  `trainer_config`: `HeadTrainer` settings
         (seed, dropout, weight_decay, ...; max_n defaults to the batch size); `fit_kw`: `head_training.fit_loop`'s
         (batch_size, grad_accum, lr, mix_alpha, patience, rng).  The trained head (EMA by default) is committed to the
-        open handle in place - the handle is NOT re-created - and `state_dict()` returns it from then on.  -> the log."""
+        open handle in place - the handle is NOT re-created - and `state_dict()` returns it from then on.  -> the log.
+
+        `augment`: a `train_augment.AugmentPolicy`, with `images_or_features` (and `val[0]`) (N,H,W,3) uint8 RGB crops: every
+        batch of every epoch is augmented on the device and pushed through the backbone anew, on this model's own handle
+        (`fit_loop`'s `augment=`; `fit_kw` may then carry `cutmix_alpha`)."""
         from .head_training import HeadTrainer
 
         def feats(x):
@@ -167,8 +171,17 @@ class DeepfakeEfficientNet:
 
         cfg = dict(trainer_config or {})
         cfg.setdefault("max_n", max(2, int(fit_kw.get("batch_size", 32))))
-        x = feats(images_or_features)
-        v = None if val is None else (feats(val[0]), np.asarray(val[1], np.float32))
+        if augment is not None:
+            from .train_augment import ResidentCrops
+
+            x = images_or_features if isinstance(images_or_features, ResidentCrops) else np.asarray(images_or_features)
+            if x.dtype != np.uint8 or x.ndim != 4 or x.shape[3] != 3:
+                raise ValueError("fit_head(augment=...) needs (N,H,W,3) uint8 crops or a ResidentCrops of this model's handle")
+            v = val                                                # fit_loop extracts the validation crops itself
+            fit_kw = dict(fit_kw, augment=(self.handle, augment))
+        else:
+            x = feats(images_or_features)
+            v = None if val is None else (feats(val[0]), np.asarray(val[1], np.float32))
         y = labels.detach().cpu().numpy() if _is_torch(labels) else np.asarray(labels)
         with HeadTrainer(self, **cfg) as tr:
             log_ = tr.fit(x, y, epochs, val=v, **fit_kw)
