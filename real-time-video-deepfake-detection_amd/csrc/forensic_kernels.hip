@@ -30,7 +30,7 @@
 #include <cmath>
 
 #include "forensic_device.h"
-#include "jpeg_dct.h"
+#include "jpeg_sample.h"
 
 namespace dfd {
 
@@ -372,24 +372,14 @@ __global__ __launch_bounds__(256) void noise_block_kernel(const uint8_t* __restr
 }
 
 // ---------------------------------------------------------------------------------- JPEG
-// libjpeg integer pipeline per 8x8 block, one thread per block (64 coefficients in registers); quality 90 divisors as
-// compile-time constants (forensic_device.h).  The fixed-point colour conversion and the jfdctint / jidctint passes are
-// jpeg_dct.h, shared with jpeg_decode.hip.
-template <bool CHROMA>
-__device__ __forceinline__ void jpeg_roundtrip(int* d, uint8_t* dst, int dstride) {
-#pragma unroll
-    for (int r = 0; r < 8; ++r) fdct8<true>(d + 8 * r, 1);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) fdct8<false>(d + c, 8);
-    jpeg_quant_q90<CHROMA>(d);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) idct8<true>(d + c, 8);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) idct8<false>(d + 8 * r, 1);
-#pragma unroll
-    for (int i = 0; i < 64; ++i) dst[(size_t)(i >> 3) * dstride + (i & 7)] = (uint8_t)clampi(d[i] + 128, 0, 255);
-}
-
+// libjpeg integer pipeline per 8x8 block, one thread per block (64 coefficients in registers): the arithmetic of
+// jpeg_sample.h with the quantiser of quality 90, every divisor a compile-time constant after unrolling.
+// The two block loads below are jpeg420_luma_block / jpeg420_chroma_block written out.  Calling the shared loaders gives
+// the same IR after inlining but another register allocation at this kernel's 256 VGPRs: jpeg_block_kernel<256> grew
+// from 12,945 to 13,206-13,670 instructions and took 41.6-42.3 us against 40.1-40.5 us for 16 frames on the MI355X, twice
+// in two shapes of the helper, outside the 0.4 us spread of the same build.  Written out, both
+// instantiations compile to the instructions they had.
+//
 // grid x: ceil((S/8)^2 / 64) blocks of luma 8x8 blocks, then ceil(2 (S/16)^2 / 64) blocks of chroma ones (Cb, then Cr),
 // so a wave is all luma or all chroma (at 256: 16 + 8 blocks)
 template <int CS>
@@ -409,7 +399,8 @@ __global__ __launch_bounds__(64) void jpeg_block_kernel(const uint8_t* __restric
             const uint8_t* p = img + ((size_t)(by + (i >> 3)) * S + bx + (i & 7)) * 3;
             d[i] = ycc_y(p[2], p[1], p[0]) - 128;
         }
-        jpeg_roundtrip<false>(d, yp + (size_t)blockIdx.y * fpix + (size_t)by * S + bx, S);
+        jpeg_roundtrip(d, [](int i) { return jpeg_quant_value(0, i, jpeg_quality_scale(90)); },
+                       yp + (size_t)blockIdx.y * fpix + (size_t)by * S + bx, S);
     } else {
         const int b = (blockIdx.x - gy) * 64 + threadIdx.x;
         if (b >= 2 * n_c) return;
@@ -427,24 +418,13 @@ __global__ __launch_bounds__(64) void jpeg_block_kernel(const uint8_t* __restric
             }
             d[i] = ((s + ((cx & 1) ? 2 : 1)) >> 2) - 128;          // h2v2_downsample, bias 1,2,1,2,...
         }
-        jpeg_roundtrip<true>(d, (is_cr ? crp : cbp) + (size_t)blockIdx.y * (fpix / 4) + (size_t)by * hs + bx, hs);
+        jpeg_roundtrip(d, [](int i) { return jpeg_quant_value(1, i, jpeg_quality_scale(90)); },
+                       (is_cr ? crp : cbp) + (size_t)blockIdx.y * (fpix / 4) + (size_t)by * hs + bx, hs);
     }
 }
 
-__device__ __forceinline__ int fancy_up(const uint8_t* p, int Y, int X, int hs) {      // p: hs x hs plane
-    const int i = Y >> 1, c = X >> 1;
-    const int nb = (Y & 1) ? (i + 1 < hs ? i + 1 : hs - 1) : (i > 0 ? i - 1 : 0);
-    const uint8_t *r0 = p + (size_t)i * hs, *r1 = p + (size_t)nb * hs;
-    const int cur = 3 * r0[c] + r1[c];
-    if ((X & 1) == 0) {
-        if (c == 0) return (4 * cur + 8) >> 4;
-        return (3 * cur + (3 * r0[c - 1] + r1[c - 1]) + 8) >> 4;
-    }
-    if (c == hs - 1) return (4 * cur + 7) >> 4;
-    return (3 * cur + (3 * r0[c + 1] + r1[c + 1]) + 7) >> 4;
-}
-
-// per 32x32 block: sum of gray(|frame - decoded|); exact integers
+// per 32x32 block: sum of gray(|frame - decoded|); exact integers.  The chroma planes are hs = S / 2 >= 16 samples wide:
+// fancy_h2v2's cw > 2 holds
 template <int CS>
 __global__ __launch_bounds__(256) void ela_block_kernel(const uint8_t* __restrict__ bgr, const uint8_t* __restrict__ yp,
                                                         const uint8_t* __restrict__ cbp, const uint8_t* __restrict__ crp,
@@ -459,10 +439,9 @@ __global__ __launch_bounds__(256) void ela_block_kernel(const uint8_t* __restric
         const int y = by + (i >> 5), x = bx + (i & 31);
         const size_t o = f * fpix + (size_t)y * S + x;
         const int Yv = yp[o];
-        const int cb = fancy_up(cbp + f * (fpix / 4), y, x, hs) - 128, cr = fancy_up(crp + f * (fpix / 4), y, x, hs) - 128;
-        const int r = clampi(Yv + ((JFIX(1.40200) * cr + 32768) >> 16), 0, 255);
-        const int g = clampi(Yv + ((-JFIX(0.34414) * cb + 32768 - JFIX(0.71414) * cr) >> 16), 0, 255);
-        const int b = clampi(Yv + ((JFIX(1.77200) * cb + 32768) >> 16), 0, 255);
+        const int cb = fancy_h2v2(cbp + f * (fpix / 4), hs, hs, hs, y, x) - 128, cr = fancy_h2v2(crp + f * (fpix / 4), hs, hs, hs, y, x) - 128;
+        int r, g, b;
+        ycc_to_rgb(Yv, cb, cr, r, g, b);
         const uint8_t* p = bgr + o * 3;
         const int db = abs((int)p[0] - b), dg = abs((int)p[1] - g), dr = abs((int)p[2] - r);
         s += (db * 1868 + dg * 9617 + dr * 4899 + (1 << 13)) >> 14;

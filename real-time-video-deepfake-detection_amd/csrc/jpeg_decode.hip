@@ -9,8 +9,8 @@
 //          path of single files, of restart-interval files while that option is off (the default), and of any frame the
 //          device decoder's own checks reject (a malformed restart structure among them);
 //   device dequantisation + jidctint.c (one thread per 8x8 block), then per output pixel h2v2 / h2v1 "fancy"
-//          (triangle) chroma upsampling + YCbCr -> RGB in libjpeg's 16-bit fixed point - the kernels of the ELA
-//          round trip (forensic_kernels.hip) generalised to any image size - written as packed BGR where
+//          (triangle) chroma upsampling + YCbCr -> RGB in libjpeg's 16-bit fixed point - the arithmetic of
+//          jpeg_sample.h, which the ELA round trip (forensic_kernels.hip) shares - written as packed BGR where
 //          dfd_analyze_frame would have uploaded the frame.
 //
 // Supported: what browsers and cv2.imencode write - 8-bit baseline (SOF0) or extended-sequential Huffman (SOF1),
@@ -31,7 +31,7 @@
 #include <vector>
 
 #include "dfd_common.h"
-#include "jpeg_dct.h"
+#include "jpeg_sample.h"
 
 using namespace dfd;
 
@@ -50,8 +50,6 @@ struct JpegPlanes {
     int bw[3], bh[3];                          // blocks
     int qoff[3];                               // offset of the component's table in q (64 entries each)
 };
-
-__device__ __forceinline__ int clampu8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 // one thread per 8x8 block: dequantise, jidctint.c (columns, then rows), +128, clamp
 // (blockIdx.y = frame of a batch: coefficients / planes / tables of frame f lie f * stride further on)
@@ -76,8 +74,8 @@ __global__ __launch_bounds__(64) void jpeg_idct_kernel(JpegPlanes J, const uint1
         uint32_t lo = 0, hi = 0;
 #pragma unroll
         for (int x = 0; x < 4; ++x) {
-            lo |= (uint32_t)clampu8(d[8 * r + x] + 128) << (8 * x);
-            hi |= (uint32_t)clampu8(d[8 * r + 4 + x] + 128) << (8 * x);
+            lo |= (uint32_t)clamp_u8(d[8 * r + x] + 128) << (8 * x);
+            hi |= (uint32_t)clamp_u8(d[8 * r + 4 + x] + 128) << (8 * x);
         }
         uint32_t* o = reinterpret_cast<uint32_t*>(dst + (size_t)r * (J.bw[c] * 8));
         o[0] = lo;
@@ -85,30 +83,15 @@ __global__ __launch_bounds__(64) void jpeg_idct_kernel(JpegPlanes J, const uint1
     }
 }
 
-// jdsample.c h2v2_fancy_upsample on a chroma plane with `cw` x `ch` real samples (row stride `cs`)
-// (jinit_upsampler picks the fancy routine only for downsampled_width > 2: a plane one or two samples wide is replicated,
-// horizontally AND vertically)
-__device__ __forceinline__ int fancy_h2v2(const uint8_t* p, int cs, int cw, int ch, int Y, int X) {
-    const int i = Y >> 1, c = X >> 1;
-    if (cw <= 2) return p[(size_t)i * cs + c];
-    const int nb = (Y & 1) ? (i + 1 < ch ? i + 1 : ch - 1) : (i > 0 ? i - 1 : 0);
-    const uint8_t *r0 = p + (size_t)i * cs, *r1 = p + (size_t)nb * cs;
-    const int cur = 3 * r0[c] + r1[c];
-    if ((X & 1) == 0) {
-        if (c == 0) return (4 * cur + 8) >> 4;
-        return (3 * cur + (3 * r0[c - 1] + r1[c - 1]) + 8) >> 4;
-    }
-    if (c == cw - 1) return (4 * cur + 7) >> 4;
-    return (3 * cur + (3 * r0[c + 1] + r1[c + 1]) + 7) >> 4;
+// jdsample.c jinit_upsampler: the fancy routines (jpeg_sample.h) only for downsampled_width > 2; a chroma plane one or two
+// samples wide is replicated (h2v2_upsample: horizontally AND vertically; h2v1_upsample).  Only a decoder meets such a plane.
+__device__ __forceinline__ int upsample_h2v2(const uint8_t* p, int cs, int cw, int ch, int Y, int X) {
+    if (cw <= 2) return p[(size_t)(Y >> 1) * cs + (X >> 1)];
+    return fancy_h2v2(p, cs, cw, ch, Y, X);
 }
-
-// jdsample.c h2v1_fancy_upsample (downsampled_width > 2), h2v1_upsample (replication) below that
-__device__ __forceinline__ int fancy_h2v1(const uint8_t* p, int cs, int cw, int Y, int X) {
-    const uint8_t* r = p + (size_t)Y * cs;
-    const int c = X >> 1;
-    if (cw <= 2) return r[c];
-    if ((X & 1) == 0) return c == 0 ? r[0] : (3 * r[c] + r[c - 1] + 1) >> 2;
-    return c == cw - 1 ? r[c] : (3 * r[c] + r[c + 1] + 2) >> 2;
+__device__ __forceinline__ int upsample_h2v1(const uint8_t* p, int cs, int cw, int Y, int X) {
+    if (cw <= 2) return p[(size_t)Y * cs + (X >> 1)];
+    return fancy_h2v1(p, cs, cw, Y, X);
 }
 
 // mode 0 gray, 1 4:4:4, 2 h2v1, 3 h2v2.  Output: packed BGR rows of `out_stride` bytes (cv2.imdecode IMREAD_COLOR)
@@ -131,18 +114,18 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(JpegPlanes J, int mode,
         cr = J.plane[2][(size_t)y * cs + x];
     } else if (mode == 2) {
         const int cw = (width + 1) >> 1;
-        cb = fancy_h2v1(J.plane[1], cs, cw, y, x);
-        cr = fancy_h2v1(J.plane[2], cs, cw, y, x);
+        cb = upsample_h2v1(J.plane[1], cs, cw, y, x);
+        cr = upsample_h2v1(J.plane[2], cs, cw, y, x);
     } else {
         const int cw = (width + 1) >> 1, ch = (height + 1) >> 1;
-        cb = fancy_h2v2(J.plane[1], cs, cw, ch, y, x);
-        cr = fancy_h2v2(J.plane[2], cs, cw, ch, y, x);
+        cb = upsample_h2v2(J.plane[1], cs, cw, ch, y, x);
+        cr = upsample_h2v2(J.plane[2], cs, cw, ch, y, x);
     }
-    cb -= 128;
-    cr -= 128;
-    o[2] = (uint8_t)clampu8(Yv + ((JFIX(1.40200) * cr + 32768) >> 16));
-    o[1] = (uint8_t)clampu8(Yv + ((-JFIX(0.34414) * cb + 32768 - JFIX(0.71414) * cr) >> 16));
-    o[0] = (uint8_t)clampu8(Yv + ((JFIX(1.77200) * cb + 32768) >> 16));
+    int r, g, b;
+    ycc_to_rgb(Yv, cb - 128, cr - 128, r, g, b);
+    o[2] = (uint8_t)r;
+    o[1] = (uint8_t)g;
+    o[0] = (uint8_t)b;
 }
 
 // the same arithmetic, four pixels per thread: 12 bytes leave as three dword stores (the one-pixel kernel writes three
@@ -169,17 +152,17 @@ __global__ __launch_bounds__(256) void jpeg_color4_kernel(JpegPlanes J, int mode
             cb = J.plane[1][(size_t)y * cs + x];
             cr = J.plane[2][(size_t)y * cs + x];
         } else if (mode == 2) {
-            cb = fancy_h2v1(J.plane[1], cs, cw, y, x);
-            cr = fancy_h2v1(J.plane[2], cs, cw, y, x);
+            cb = upsample_h2v1(J.plane[1], cs, cw, y, x);
+            cr = upsample_h2v1(J.plane[2], cs, cw, y, x);
         } else {
-            cb = fancy_h2v2(J.plane[1], cs, cw, ch, y, x);
-            cr = fancy_h2v2(J.plane[2], cs, cw, ch, y, x);
+            cb = upsample_h2v2(J.plane[1], cs, cw, ch, y, x);
+            cr = upsample_h2v2(J.plane[2], cs, cw, ch, y, x);
         }
-        cb -= 128;
-        cr -= 128;
-        px[3 * i + 2] = (uint8_t)clampu8(Yv + ((JFIX(1.40200) * cr + 32768) >> 16));
-        px[3 * i + 1] = (uint8_t)clampu8(Yv + ((-JFIX(0.34414) * cb + 32768 - JFIX(0.71414) * cr) >> 16));
-        px[3 * i] = (uint8_t)clampu8(Yv + ((JFIX(1.77200) * cb + 32768) >> 16));
+        int r, g, b;
+        ycc_to_rgb(Yv, cb - 128, cr - 128, r, g, b);
+        px[3 * i + 2] = (uint8_t)r;
+        px[3 * i + 1] = (uint8_t)g;
+        px[3 * i] = (uint8_t)b;
     }
     uint8_t* o = out + (size_t)y * out_stride + 3 * x0;
     if (x0 + 4 <= width) {
@@ -199,7 +182,7 @@ __global__ __launch_bounds__(256) void jpeg_color4_kernel(JpegPlanes J, int mode
 // blends vertically once per column; clamping the neighbour indices reproduces fancy_h2v2's edge rules exactly (at the
 // first / last column 3 * cur + cur = 4 * cur).  22 loads and 12 dword stores for 16 pixels; the four-pixel kernel issues
 // 36 byte loads per 4 pixels.  (width % 8 == 0 means at least four chroma columns: libjpeg's replication of planes one or
-// two samples wide, fancy_h2v2's first line, cannot apply here.)
+// two samples wide, upsample_h2v2's other branch, cannot apply here.)
 __global__ __launch_bounds__(256) void jpeg_color420_kernel(JpegPlanes J, int width, int height, uint8_t* __restrict__ out, int out_stride,
                                                             size_t plane_stride, size_t out_frame_stride) {
     const int x0 = 8 * (blockIdx.x * 256 + threadIdx.x), i = blockIdx.y;
@@ -258,11 +241,11 @@ __global__ __launch_bounds__(256) void jpeg_color420_kernel(JpegPlanes J, int wi
                 cbv = (k & 1) ? (3 * vo[0][c] + vo[0][c + 1] + 7) >> 4 : (3 * vo[0][c] + vo[0][c - 1] + 8) >> 4;
                 crv = (k & 1) ? (3 * vo[1][c] + vo[1][c + 1] + 7) >> 4 : (3 * vo[1][c] + vo[1][c - 1] + 8) >> 4;
             }
-            cbv -= 128;
-            crv -= 128;
-            px[3 * k + 2] = (uint8_t)clampu8(Yv + ((JFIX(1.40200) * crv + 32768) >> 16));
-            px[3 * k + 1] = (uint8_t)clampu8(Yv + ((-JFIX(0.34414) * cbv + 32768 - JFIX(0.71414) * crv) >> 16));
-            px[3 * k] = (uint8_t)clampu8(Yv + ((JFIX(1.77200) * cbv + 32768) >> 16));
+            int r, g, b;
+            ycc_to_rgb(Yv, cbv - 128, crv - 128, r, g, b);
+            px[3 * k + 2] = (uint8_t)r;
+            px[3 * k + 1] = (uint8_t)g;
+            px[3 * k] = (uint8_t)b;
         }
         uint2 w[3];
         memcpy(w, px, 24);

@@ -26,7 +26,7 @@
 #include <algorithm>
 
 #include "dfd_common.h"
-#include "jpeg_dct.h"
+#include "jpeg_sample.h"
 #include "kernel_util.h"
 
 namespace dfd {
@@ -36,15 +36,6 @@ constexpr int kEncScanTile = 1024;        // elements one workgroup of the scan 
 constexpr int kEncChunk = 64;             // bytes of the unstuffed buffer per lane of the stuffing passes
 constexpr size_t kEncMaxPixels = (size_t)1 << 24;
 
-constexpr unsigned char kZig[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                    30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-// jcparam.c std_luminance_quant_tbl / std_chrominance_quant_tbl (ITU-T T.81 Annex K.1), natural order
-const unsigned char kBaseQ[2][64] = {
-    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
-     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
-    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
-     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
 // ITU-T T.81 Annex K.3: codes per length 1..16, then the symbols in code order
 const unsigned char kDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
 const unsigned char kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
@@ -159,10 +150,10 @@ __global__ __launch_bounds__(64) void enc_block_kernel(const EncImage* __restric
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
         u4 v;
-        v.x = enc_pack2(d[kZig[8 * g]], d[kZig[8 * g + 1]]);
-        v.y = enc_pack2(d[kZig[8 * g + 2]], d[kZig[8 * g + 3]]);
-        v.z = enc_pack2(d[kZig[8 * g + 4]], d[kZig[8 * g + 5]]);
-        v.w = enc_pack2(d[kZig[8 * g + 6]], d[kZig[8 * g + 7]]);
+        v.x = enc_pack2(d[kJpegZigzag[8 * g]], d[kJpegZigzag[8 * g + 1]]);
+        v.y = enc_pack2(d[kJpegZigzag[8 * g + 2]], d[kJpegZigzag[8 * g + 3]]);
+        v.z = enc_pack2(d[kJpegZigzag[8 * g + 4]], d[kJpegZigzag[8 * g + 5]]);
+        v.w = enc_pack2(d[kJpegZigzag[8 * g + 6]], d[kJpegZigzag[8 * g + 7]]);
         dst[g] = v;
     }
 }
@@ -430,9 +421,8 @@ void enc_derive(const unsigned char* bits, const unsigned char* vals, unsigned s
     }
 }
 
-void enc_quant(int which, int quality, unsigned char* q) {            // jpeg_quality_scaling + jpeg_add_quant_table(force_baseline)
-    const int scale = quality < 50 ? 5000 / quality : 200 - quality * 2;
-    for (int i = 0; i < 64; ++i) q[i] = (unsigned char)std::min(255, std::max(1, (kBaseQ[which][i] * scale + 50) / 100));
+void enc_quant(int which, int quality, unsigned char* q) {
+    for (int i = 0; i < 64; ++i) q[i] = (unsigned char)jpeg_quant_value(which, i, jpeg_quality_scale(quality));
 }
 
 struct EncGeom { int hs, vs, comps, bpm, mcux, mcuy; };
@@ -469,7 +459,7 @@ void enc_header(const dfd_jpeg_source& s, const EncGeom& g, const unsigned char 
         o.push_back(0xFF); o.push_back(0xDB);
         enc_put16(o, 67);
         o.push_back((uint8_t)t);
-        for (int i = 0; i < 64; ++i) o.push_back(q[t][kZig[i]]);
+        for (int i = 0; i < 64; ++i) o.push_back(q[t][kJpegZigzag[i]]);
     }
     o.push_back(0xFF); o.push_back(0xC0);
     enc_put16(o, 8 + 3 * g.comps);

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/dfd_hip.h"
+#include "jpeg_tables.h"
 
 namespace dfd {
 int fail(dfd_handle* h, int code, const char* fmt, ...);
@@ -27,10 +28,6 @@ int fail(dfd_handle* h, int code, const char* fmt, ...);
 
 namespace dfd_jpeg {
 using dfd::fail;
-
-static const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 constexpr size_t kMaxJpegPixels = (size_t)1 << 26;       // 8192 x 8192: 0.4 GB of coefficients at 4:4:4
 
@@ -109,7 +106,7 @@ inline int parse_headers(dfd_handle* h, const uint8_t* d, size_t len, Parsed* P)
                 ++i;
                 if (tq > 3 || i + (pq ? 128 : 64) > n) return fail(h, DFD_ERR_ARG, "decode_jpeg: bad DQT");
                 for (int k = 0; k < 64; ++k) {
-                    P->q[tq][kZigzag[k]] = (uint16_t)(pq ? be16(s + i + 2 * k) : s[i + k]);
+                    P->q[tq][dfd::kJpegZigzag[k]] = (uint16_t)(pq ? be16(s + i + 2 * k) : s[i + k]);
                 }
                 P->qpresent[tq] = true;
                 i += pq ? 128 : 64;
@@ -372,7 +369,7 @@ inline bool decode_block(const uint8_t* c, uint64_t* bp, uint64_t nbits, const H
         }
         k += r;
         if (k > 63) { *bp = b + used + len + sz; return false; }
-        blk[kZigzag[k]] = (int16_t)extend((int)((ww << len) >> (64 - sz)), sz);
+        blk[dfd::kJpegZigzag[k]] = (int16_t)extend((int)((ww << len) >> (64 - sz)), sz);
         used += len + sz;
         ++k;
     }

@@ -333,9 +333,6 @@ struct JgLds {
     uint4 slot[8];                               // per MCU slot: coefficient offset of its block in MCU (0, 0), per MCU row, per MCU column
     uint8_t zigzag[64];
 };
-__device__ const uint8_t jg_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                          41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                          30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 __device__ __forceinline__ int jg_extend(uint32_t v, int s) {
     return s == 0 ? 0 : ((int)v < (1 << (s - 1)) ? (int)v - (1 << s) + 1 : (int)v);
@@ -561,7 +558,7 @@ __device__ __forceinline__ void jg_load_lds(JgLds& L, const JgFrame* F, const Jg
         uint32_t* dst = reinterpret_cast<uint32_t*>(&L.fr);
         for (int i = tid; i < (int)(sizeof(JgFrame) / 4); i += JG_CB) dst[i] = src[i];
     }
-    if (tid < 64) L.zigzag[tid] = jg_zigzag[tid];
+    if (tid < 64) L.zigzag[tid] = dfd::kJpegZigzag[tid];
     __syncthreads();
     if (tid < 8) {
         const int z = tid < L.fr.bpm ? tid : 0, c = L.fr.slot_comp[z];

@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "dfd_common.h"
-#include "jpeg_dct.h"
+#include "jpeg_sample.h"
 #include "pil_resize.h"
 #include "train_augment.h"
 
@@ -48,37 +48,6 @@ __device__ __forceinline__ void copy_image(const uint8_t* __restrict__ s, uint8_
 }
 
 // ------------------------------------------------------------------------------------------------ JPEG round trip
-// jcparam.c std_luminance_quant_tbl / std_chrominance_quant_tbl (ITU-T T.81 Annex K.1), natural order
-__constant__ unsigned char kAugQuant[2][64] = {
-    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
-     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
-    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
-     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
-
-__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
-// one 8 x 8 block of samples - 128 through FDCT, quantiser (jpeg_quality_scaling, force_baseline), dequantiser and IDCT
-__device__ __forceinline__ void aug_jpeg_roundtrip(int* d, int chroma, int scale, uint8_t* dst, int dstride) {
-#pragma unroll
-    for (int r = 0; r < 8; ++r) fdct8<true>(d + 8 * r, 1);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) fdct8<false>(d + c, 8);
-#pragma unroll
-    for (int i = 0; i < 64; ++i) {
-        int q = ((int)kAugQuant[chroma][i] * scale + 50) / 100;
-        q = q < 1 ? 1 : (q > 255 ? 255 : q);
-        const int qv = q << 3, v = d[i];
-        const int a = ((v < 0 ? -v : v) + (qv >> 1)) / qv;
-        d[i] = (v < 0 ? -a : a) * q;
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) idct8<true>(d + c, 8);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) idct8<false>(d + 8 * r, 1);
-#pragma unroll
-    for (int i = 0; i < 64; ++i) dst[(size_t)(i >> 3) * dstride + (i & 7)] = (uint8_t)clamp255(d[i] + 128);
-}
-
 // a thread per 8 x 8 block: grid x = the luma blocks of an image in groups of 64, then its Cb and Cr blocks (a wave is all
 // luma or all chroma).  planes: per image Y [H][W], Cb [H/2][W/2], Cr [H/2][W/2].  The reference hands its RGB array to an
 // encoder that reads BGR: unless DFD_AUG_JPEG_RGB is set the encoder's R is the image's B.
@@ -87,7 +56,7 @@ __global__ __launch_bounds__(64) void aug_jpeg_block_kernel(const uint8_t* __res
     const int img = blockIdx.y;
     const Row& r = rows[img];
     if (!(r.flags & DFD_AUG_JPEG)) return;
-    const int quality = r.jpeg_quality, scale = quality < 50 ? 5000 / quality : 200 - quality * 2;
+    const int quality = r.jpeg_quality, scale = jpeg_quality_scale(quality);
     const int ir = (r.flags & DFD_AUG_JPEG_RGB) ? 0 : 2, ib = 2 - ir;
     const int lw = W >> 3, n_y = lw * (H >> 3), cw = W >> 4, n_c = cw * (H >> 4), gy = (n_y + 63) >> 6, hw = W >> 1;
     const size_t fpix = (size_t)H * W;
@@ -98,45 +67,18 @@ __global__ __launch_bounds__(64) void aug_jpeg_block_kernel(const uint8_t* __res
         const int b = blockIdx.x * 64 + threadIdx.x;
         if (b >= n_y) return;
         const int by = (b / lw) * 8, bx = (b % lw) * 8;
-#pragma unroll
-        for (int i = 0; i < 64; ++i) {
-            const uint8_t* p = im + ((size_t)(by + (i >> 3)) * W + bx + (i & 7)) * 3;
-            d[i] = ycc_y(p[ir], p[1], p[ib]) - 128;
-        }
-        aug_jpeg_roundtrip(d, 0, scale, yp + (size_t)by * W + bx, W);
+        jpeg420_luma_block(im, W, ir, ib, by, bx, d);
+        jpeg_roundtrip(d, [scale](int i) { return jpeg_quant_value(0, i, scale); }, yp + (size_t)by * W + bx, W);
     } else {
         const int b = (blockIdx.x - gy) * 64 + threadIdx.x;
         if (b >= 2 * n_c) return;
         const bool is_cr = b >= n_c;
         const int c = is_cr ? b - n_c : b;
         const int by = (c / cw) * 8, bx = (c % cw) * 8;          // in the H/2 x W/2 chroma plane
-#pragma unroll
-        for (int i = 0; i < 64; ++i) {
-            const int cy = by + (i >> 3), cx = bx + (i & 7);
-            int s = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint8_t* p = im + ((size_t)(2 * cy + (k >> 1)) * W + 2 * cx + (k & 1)) * 3;
-                s += is_cr ? ycc_cr(p[ir], p[1], p[ib]) : ycc_cb(p[ir], p[1], p[ib]);
-            }
-            d[i] = ((s + ((cx & 1) ? 2 : 1)) >> 2) - 128;          // h2v2_downsample, bias 1,2,1,2,...
-        }
-        aug_jpeg_roundtrip(d, 1, scale, yp + fpix + (is_cr ? fpix / 4 : 0) + (size_t)by * hw + bx, hw);
+        jpeg420_chroma_block(im, W, ir, ib, is_cr, by, bx, d);
+        jpeg_roundtrip(d, [scale](int i) { return jpeg_quant_value(1, i, scale); },
+                       yp + fpix + (is_cr ? fpix / 4 : 0) + (size_t)by * hw + bx, hw);
     }
-}
-
-// jdsample.c h2v2_fancy_upsample at (Y, X) of a hh x hw chroma plane
-__device__ __forceinline__ int aug_fancy_up(const uint8_t* p, int Y, int X, int hh, int hw) {
-    const int i = Y >> 1, c = X >> 1;
-    const int nb = (Y & 1) ? (i + 1 < hh ? i + 1 : hh - 1) : (i > 0 ? i - 1 : 0);
-    const uint8_t *r0 = p + (size_t)i * hw, *r1 = p + (size_t)nb * hw;
-    const int cur = 3 * r0[c] + r1[c];
-    if ((X & 1) == 0) {
-        if (c == 0) return (4 * cur + 8) >> 4;
-        return (3 * cur + (3 * r0[c - 1] + r1[c - 1]) + 8) >> 4;
-    }
-    if (c == hw - 1) return (4 * cur + 7) >> 4;
-    return (3 * cur + (3 * r0[c + 1] + r1[c + 1]) + 7) >> 4;
 }
 
 // decoded planes -> RGB (jdcolor.c); an image without the stage is copied
@@ -155,10 +97,13 @@ __global__ __launch_bounds__(256) void aug_jpeg_color_kernel(const uint8_t* __re
     for (int t = blockIdx.x * 256 + threadIdx.x; t < (int)fpix; t += gridDim.x * 256) {
         const int y = t / W, x = t % W;
         const int Yv = yp[t];
-        const int cb = aug_fancy_up(cbp, y, x, H >> 1, W >> 1) - 128, cr = aug_fancy_up(crp, y, x, H >> 1, W >> 1) - 128;
-        d[3 * t] = (uint8_t)clamp255(Yv + ((JFIX(1.40200) * cr + 32768) >> 16));
-        d[3 * t + 1] = (uint8_t)clamp255(Yv + ((-JFIX(0.34414) * cb + 32768 - JFIX(0.71414) * cr) >> 16));
-        d[3 * t + 2] = (uint8_t)clamp255(Yv + ((JFIX(1.77200) * cb + 32768) >> 16));
+        const int hh = H >> 1, hw = W >> 1;                          // W >= 32 (aug_check): fancy_h2v2's cw > 2 holds
+        const int cb = fancy_h2v2(cbp, hw, hw, hh, y, x) - 128, cr = fancy_h2v2(crp, hw, hw, hh, y, x) - 128;
+        int r, g, b;
+        ycc_to_rgb(Yv, cb, cr, r, g, b);
+        d[3 * t] = (uint8_t)r;
+        d[3 * t + 1] = (uint8_t)g;
+        d[3 * t + 2] = (uint8_t)b;
     }
 }
 
