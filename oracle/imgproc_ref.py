@@ -238,8 +238,17 @@ def lab2bgr_u8(lab: np.ndarray, t=None) -> np.ndarray:
 
 # --------------------------------------------------------------------------- CLAHE
 def _reflect101(i, n):
-    i = np.abs(i)
-    return np.where(i >= n, 2 * (n - 1) - i, i)
+    """OpenCV borderInterpolate(p, len, BORDER_REFLECT_101): 0 when len == 1, else p = p < 0 ? -p : 2*(len-1) - p
+    repeated until p is in [0, len).  One pass suffices for the filters below (offsets of at most 2, n >= 3: their
+    indices are what the single reflection gave); CLAHE's pad of up to 8 needs more for n in {2, 3, 4, 8}."""
+    i = np.array(i, dtype=np.int64)
+    if n == 1:
+        return np.zeros_like(i)
+    while True:
+        out = (i < 0) | (i >= n)
+        if not out.any():
+            return i
+        i = np.where(out, np.where(i < 0, -i, 2 * (n - 1) - i), i)
 
 
 def clahe_u8(src: np.ndarray, clip_limit: float = 2.0, tiles=(8, 8)) -> np.ndarray:
@@ -297,9 +306,10 @@ def clahe_u8(src: np.ndarray, clip_limit: float = 2.0, tiles=(8, 8)) -> np.ndarr
     return np.clip(np.rint(res), 0, 255).astype(np.uint8)
 
 
-def preprocess_face_quality(bgr: np.ndarray) -> np.ndarray:
-    """reference deepfake_detection.py:357-370: BGR->Lab, CLAHE(2.0, 8x8) on L, Lab->BGR."""
-    t = lab_tables()
+def preprocess_face_quality(bgr: np.ndarray, t=None) -> np.ndarray:
+    """reference deepfake_detection.py:357-370: BGR->Lab, CLAHE(2.0, 8x8) on L, Lab->BGR.  `t`: lab_tables() built
+    once by a caller with many crops."""
+    t = t or lab_tables()
     lab = bgr2lab_u8(bgr, t)
     lab[..., 0] = clahe_u8(lab[..., 0], 2.0, (8, 8))
     return lab2bgr_u8(lab, t)

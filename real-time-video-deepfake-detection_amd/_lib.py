@@ -635,8 +635,9 @@ class Handle:
         a = np.asarray(frame)
         if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
             raise ValueError(f"expected (H,W,3) uint8 BGR image, got {a.dtype} {a.shape}")
-        if not a.flags["C_CONTIGUOUS"]:
-            a = np.ascontiguousarray(a)
+        # a one-row (or one-pixel) view counts as contiguous whatever its row stride, which the callers pass on
+        if not a.flags["C_CONTIGUOUS"] or a.strides[0] != a.shape[1] * 3:
+            a = np.array(a, order="C", copy=True)
         return a
 
     @staticmethod

@@ -15,9 +15,16 @@ namespace dfd {
 
 __device__ __forceinline__ int descale(long long x, int n) { return (int)((x + (1ll << (n - 1))) >> n); }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// OpenCV borderInterpolate(BORDER_REFLECT_101): 0 for a single sample, else p = p < 0 ? -p : 2 * (n - 1) - p until p lands
+// in [0, n) - a triangle wave of period 2 * (n - 1), so without the loop: fold by the period, then reflect once.  CLAHE's
+// pad of up to 8 passes the first reflection when n is 1, 2, 3, 4 or 8 (the division runs for those crops only).
 __device__ __forceinline__ int reflect101(int i, int n) {
     if (i < 0) i = -i;
-    if (i >= n) i = 2 * (n - 1) - i;
+    if (i >= n) {
+        const int period = 2 * (n - 1);
+        if (i > period) i = period ? i % period : 0;
+        if (i >= n) i = period - i;
+    }
     return i;
 }
 
@@ -148,6 +155,26 @@ __device__ __forceinline__ void bgr2lab_lds(const ColorTables& T, const LabLds& 
     B = clampi((200 * (fY - fZ) + 128 * (1 << 15) + (1 << 14)) >> 15, 0, 255);
 }
 
+// the one-pixel path of clahe_hist_kernel: cnt pixels from (ex0, ey) of the extended crop.  PAD: the group reaches
+// into the reflected border (its samples are counted, only those inside the crop are written)
+template <bool PAD>
+__device__ __forceinline__ void hist_pixels(const ColorTables& T, const LabLds& S, const uint8_t* __restrict__ src, size_t fstride,
+                                            uint8_t* __restrict__ lab, const CropDesc& cd, int ex0, int ey, int cnt, int* myhist) {
+    const int sy = PAD ? reflect101(ey, cd.h) : ey;
+    for (int k = 0; k < cnt; ++k) {
+        const int ex = ex0 + k;
+        const int sx = PAD ? reflect101(ex, cd.w) : ex;
+        const uint8_t* p = src + (size_t)sy * fstride + (size_t)sx * 3;
+        int L, A, B;
+        bgr2lab_lds(T, S, p[0], p[1], p[2], L, A, B);
+        atomicAdd(&myhist[L], 1);
+        if (!PAD || (ex < cd.w && ey < cd.h)) {
+            uint8_t* o = lab + ((size_t)ey * cd.w + ex) * 3;
+            o[0] = (uint8_t)L; o[1] = (uint8_t)A; o[2] = (uint8_t)B;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void clahe_hist_kernel(const uint8_t* __restrict__ frame,
                                                          const CropDesc* __restrict__ crops,
                                                          uint8_t* __restrict__ lab_out,
@@ -187,19 +214,10 @@ __global__ __launch_bounds__(256) void clahe_hist_kernel(const uint8_t* __restri
                 res[3 * k] = (unsigned char)L; res[3 * k + 1] = (unsigned char)A; res[3 * k + 2] = (unsigned char)B;
             }
             __builtin_memcpy(lab + ((size_t)ey * cd.w + ex0) * 3, res, 12);
+        } else if (ex0 + cnt <= cd.w && ey < cd.h) {                        // a tile row's short last group, inside the crop
+            hist_pixels<false>(T, S, src, fstride, lab, cd, ex0, ey, cnt, myhist);
         } else {
-            for (int k = 0; k < cnt; ++k) {
-                const int ex = ex0 + k;
-                const int sx = reflect101(ex, cd.w), sy = reflect101(ey, cd.h);
-                const uint8_t* p = src + (size_t)sy * fstride + (size_t)sx * 3;
-                int L, A, B;
-                bgr2lab_lds(T, S, p[0], p[1], p[2], L, A, B);
-                atomicAdd(&myhist[L], 1);
-                if (ex < cd.w && ey < cd.h) {
-                    uint8_t* o = lab + ((size_t)ey * cd.w + ex) * 3;
-                    o[0] = (uint8_t)L; o[1] = (uint8_t)A; o[2] = (uint8_t)B;
-                }
-            }
+            hist_pixels<true>(T, S, src, fstride, lab, cd, ex0, ey, cnt, myhist);
         }
     }
     __syncthreads();
