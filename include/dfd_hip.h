@@ -309,10 +309,22 @@ int dfd_ssd_detection_tap(dfd_handle* h, int n, const float* heads, const float*
  * minNeighbors, minSize=(min_size, min_size)) for a stump cascade with upright HAAR features packed into the blob
  * (haar.load_cascade_xml reads OpenCV's XML; weights.pack_all(..., haar=...)).  The reference uses this path
  * whenever its SSD files are missing.  Boxes are the grouped rectangles in OpenCV's order; n_candidates (may be
- * NULL) receives the number of windows that passed the cascade before grouping. */
+ * NULL) receives the number of windows that passed the cascade before grouping.
+ * scale_factor (> 1) is a double, as OpenCV's scaleFactor: the loop multiplies it up in double, and the float 1.1f would
+ * round some scaled sizes the other way from scale 5 on.  dfd_create refuses (DFD_ERR_BLOB) a cascade whose stage,
+ * feature or rectangle numbers would index outside its tables or its window. */
 int dfd_has_haar(const dfd_handle* h);
-int dfd_detect_faces_haar(dfd_handle* h, const uint8_t* bgr, int height, int width, int stride, float scale_factor,
+int dfd_detect_faces_haar(dfd_handle* h, const uint8_t* bgr, int height, int width, int stride, double scale_factor,
                           int min_neighbors, int min_size, int32_t* xywh_out, int max_out, int* n_out, int* n_candidates);
+/* One named buffer of ONE scale of that loop, for parity tests (as dfd_ssd_tap): the production kernels through the
+ * production buffers on the host frame `bgr`, at the scale_index-th factor 1, scale_factor, scale_factor^2, ... (every
+ * scale counts; there is no min_size here).  name: "gray" (u8 [height][width]), "scaled" (u8 [sh][sw], the gray image
+ * itself where the scale keeps the frame's size), "sum" (u32 [sh + 1][sw + 1]), "sqsum" (u64, same shape), "result"
+ * (i32 [ny][nx] per grid position: 1 = passed, 0 = rejected by stage 0, -s = rejected by stage s), or NULL for the
+ * geometry alone.  out receives *bytes bytes (capacity in bytes); dims[8] = sh, sw, ny, nx, grid step, reported window
+ * width, height, number of scales; *factor = the factor used.  A scale_index past the last scale is DFD_ERR_ARG. */
+int dfd_haar_tap(dfd_handle* h, const uint8_t* bgr, int height, int width, int stride, double scale_factor, int scale_index,
+                 const char* name, void* out, size_t capacity, size_t* bytes, int32_t* dims, double* factor);
 
 /* ---- MTCNN align/crop -------------------------------------------------
  * The reference runs facenet-pytorch's MTCNN(select_largest=False, post_process=False) on every

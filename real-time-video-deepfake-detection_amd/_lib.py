@@ -83,8 +83,10 @@ SIGNATURES = {
     "dfd_ssd_detection_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_void_p]),
     "dfd_has_haar": (C.c_int, [C.c_void_p]),
-    "dfd_detect_faces_haar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
+    "dfd_detect_faces_haar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
                                         C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dfd_haar_tap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_char_p, C.c_void_p,
+                               C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_double)]),
     "dfd_has_mtcnn": (C.c_int, [C.c_void_p]),
     "dfd_mtcnn_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.POINTER(C.c_int)]),
@@ -913,13 +915,51 @@ class Handle:
     def detect_faces_haar(self, frame, scale_factor: float = 1.1, min_neighbors: int = 5, min_size: int = 30,
                           max_out: int = 256, with_candidates: bool = False):
         """cv2 detectMultiScale on the blob's Haar cascade -> [(x, y, w, h), ...] (reference face_detection.py:108-123)"""
-        a = self._as_bgr(frame)
-        boxes = np.zeros((max_out, 4), np.int32)
+        a = self._as_bgr_rows(frame)
+        boxes = np.zeros((max(int(max_out), 1), 4), np.int32)
         n, nc = C.c_int(), C.c_int()
         self._check(self._lib.dfd_detect_faces_haar(self._p, _ptr(a), a.shape[0], a.shape[1], a.strides[0], float(scale_factor),
-                                                    int(min_neighbors), int(min_size), _ptr(boxes), max_out, C.byref(n), C.byref(nc)))
+                                                    int(min_neighbors), int(min_size), _ptr(boxes), int(max_out), C.byref(n),
+                                                    C.byref(nc)))
         out = [tuple(int(v) for v in boxes[i]) for i in range(n.value)]
         return (out, nc.value) if with_candidates else out
+
+    @classmethod
+    def _as_bgr_rows(cls, frame) -> np.ndarray:
+        """_as_bgr, but a view whose rows are padded (packed pixels, row stride >= 3 * width, every row backed by a whole
+        stride of the buffer it views) is passed on as it is: the Haar entries take the stride"""
+        a = np.asarray(frame)
+        if (a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3 and a.strides[1:] == (3, 1) and a.strides[0] >= a.shape[1] * 3
+                and isinstance(a.base, np.ndarray) and a.base.flags["C_CONTIGUOUS"] and a.base.ndim == 2
+                and a.base.shape == (a.shape[0], a.strides[0]) and a.base.dtype == np.uint8
+                and a.__array_interface__["data"][0] == a.base.__array_interface__["data"][0]):
+            return a
+        return cls._as_bgr(frame)
+
+    _HAAR_TAPS = {"gray": np.uint8, "scaled": np.uint8, "sum": np.uint32, "sqsum": np.uint64, "result": np.int32}
+
+    def haar_tap(self, frame, scale_factor: float = 1.1, scale_index: int = 0, names=("gray", "scaled", "sum", "sqsum", "result")):
+        """dfd_haar_tap: the named buffers of one scale of detectMultiScale's loop, shaped, with the geometry: {"gray": u8
+        (h, w), "scaled": u8 (sh, sw), "sum": u32 (sh + 1, sw + 1), "sqsum": u64, "result": i32 (ny, nx), "factor", "step",
+        "window": (w, h) as reported, "n_scales"}.  DfdError (DFD_ERR_ARG) for a scale index past the last scale."""
+        a = self._as_bgr_rows(frame)
+        dims = np.zeros(8, np.int32)
+        factor = C.c_double()
+        nb = C.c_size_t()
+
+        def call(name, out, cap):
+            self._check(self._lib.dfd_haar_tap(self._p, _ptr(a), a.shape[0], a.shape[1], a.strides[0], float(scale_factor),
+                                               int(scale_index), name, out, cap, C.byref(nb), _ptr(dims), C.byref(factor)))
+        call(None, None, 0)
+        sh, sw, ny, nx, step, ww, wh, n_scales = (int(v) for v in dims)
+        shapes = {"gray": a.shape[:2], "scaled": (sh, sw), "sum": (sh + 1, sw + 1), "sqsum": (sh + 1, sw + 1), "result": (ny, nx)}
+        res = {"factor": factor.value, "step": step, "window": (ww, wh), "n_scales": n_scales}
+        for name in names:
+            out = np.empty(shapes[name], self._HAAR_TAPS[name])
+            call(name.encode(), _ptr(out), out.nbytes)
+            assert nb.value == out.nbytes, (name, nb.value, out.nbytes)
+            res[name] = out
+        return res
 
     def analyze_frame(self, frame, full_forensics: bool, stream_id: int = 0, confidence_threshold: float = 0.5,
                       max_faces: int = 16, apply_clahe: bool = True, tta=None):

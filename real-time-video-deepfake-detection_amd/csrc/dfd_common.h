@@ -220,7 +220,7 @@ int forensics_stream_run(dfd_handle* h, int stream_id, const uint8_t* frame_dev,
 int detect_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride, float conf_thr, int32_t* xywh_out,
                float* conf_out, int max_out, int* n_out);
 // haar_api.hip: detectMultiScale + groupRectangles on a resident frame; *n_total = groups before the max_out cut
-int haar_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride, float scale_factor, int min_neighbors,
+int haar_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride, double scale_factor, int min_neighbors,
              int min_size, int32_t* xywh_out, int max_out, int* n_out, int* n_candidates, int* n_total = nullptr);
 // frame_offs: per-crop byte offset of its frame inside frame_dev (null = single frame)
 // compact: in_nchw receives only the crops the MTCNN stage kept (h->n_compact rows, flags in h->crop_valid)

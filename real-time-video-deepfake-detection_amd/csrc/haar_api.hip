@@ -21,6 +21,7 @@
 #include <numeric>
 
 #include "dfd_common.h"
+#include "haar_validate.h"
 #include "host_boxes.h"
 
 using namespace dfd;
@@ -45,19 +46,24 @@ int haar_init(dfd_handle* h) {
     if (st == h->tensors.end() || sp == h->tensors.end() || rc == h->tensors.end() || w->second.count != 2 ||
         st->second.count % 3 || sp->second.count % 4 || rc->second.count % 15)
         return fail(h, DFD_ERR_BLOB, "weights blob: malformed haar.* tensors");
+    // the cascade is a few KB: checked on the host before a kernel ever indexes with it (haar_validate.h)
+    std::vector<float> hw(2), hst(st->second.count), hsp(sp->second.count), hrc(rc->second.count);
+    DFD_HIP_TRY(h, hipMemcpy(hw.data(), w->second.dev, 8, hipMemcpyDeviceToHost));
+    if (!hst.empty()) DFD_HIP_TRY(h, hipMemcpy(hst.data(), st->second.dev, hst.size() * 4, hipMemcpyDeviceToHost));
+    if (!hsp.empty()) DFD_HIP_TRY(h, hipMemcpy(hsp.data(), sp->second.dev, hsp.size() * 4, hipMemcpyDeviceToHost));
+    if (!hrc.empty()) DFD_HIP_TRY(h, hipMemcpy(hrc.data(), rc->second.dev, hrc.size() * 4, hipMemcpyDeviceToHost));
+    if (const char* why = haar_cascade_error(hw.data(), hst.data(), hst.size() / 3, hsp.data(), hsp.size() / 4, hrc.data(), hrc.size() / 15))
+        return fail(h, DFD_ERR_BLOB, "weights blob: haar cascade refused: %s", why);
     HaarState* S = new HaarState();
     h->haar = S;
-    float wh[2];
-    DFD_HIP_TRY(h, hipMemcpy(wh, w->second.dev, 8, hipMemcpyDeviceToHost));
-    S->win_w = (int)wh[0];
-    S->win_h = (int)wh[1];
-    S->n_stages = (int)(st->second.count / 3);
-    S->n_stumps = (int)(sp->second.count / 4);
-    S->n_feats = (int)(rc->second.count / 15);
+    S->win_w = (int)hw[0];
+    S->win_h = (int)hw[1];
+    S->n_stages = (int)(hst.size() / 3);
+    S->n_stumps = (int)(hsp.size() / 4);
+    S->n_feats = (int)(hrc.size() / 15);
     S->stages = st->second.dev;
     S->stumps = sp->second.dev;
     S->rects = rc->second.dev;
-    if (S->win_w < 4 || S->win_h < 4 || S->n_stages < 1) return fail(h, DFD_ERR_BLOB, "weights blob: empty Haar cascade");
     return DFD_OK;
 }
 
@@ -167,16 +173,78 @@ __global__ __launch_bounds__(64) void haar_collect_kernel(const int* __restrict_
     }
 }
 
+constexpr int CAP = 1 << 16;                                      // candidate windows one call can hold
+
+// one scale of detectMultiScale's loop: the window as reported, the scaled image, the grid
+struct HaarScale {
+    double factor;
+    int win_w, win_h, sw, sh, step, nx, ny;
+};
+
+// false from the first factor at which the scaled image no longer exceeds the window (where the loop ends)
+bool haar_scale_at(const HaarState* S, int hh, int ww, double factor, HaarScale* G) {
+    G->factor = factor;
+    G->win_w = cv_round(S->win_w * factor);
+    G->win_h = cv_round(S->win_h * factor);
+    G->sw = cv_round(ww / factor);
+    G->sh = cv_round(hh / factor);
+    if (G->sw - S->win_w <= 0 || G->sh - S->win_h <= 0) return false;
+    G->step = factor > 2.0 ? 1 : 2;
+    G->nx = (G->sw - S->win_w + G->step - 1) / G->step;
+    G->ny = (G->sh - S->win_h + G->step - 1) / G->step;
+    return true;
+}
+
+// work buffers for a frame of this size, its gray image, an empty candidate list
+int haar_begin(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride) {
+    HaarState* S = h->haar;
+    int rc;
+    const size_t npix = (size_t)hh * ww;
+    if ((rc = ensure(h, &S->gray, npix))) return rc;
+    if ((rc = ensure(h, &S->scaled, npix))) return rc;
+    if ((rc = ensure(h, &S->sum, (size_t)(hh + 1) * (ww + 1) * 4))) return rc;
+    if ((rc = ensure(h, &S->sqsum, (size_t)(hh + 1) * (ww + 1) * 8))) return rc;
+    if ((rc = ensure(h, &S->result, npix * 4))) return rc;
+    if ((rc = ensure(h, &S->cand, (size_t)CAP * 12))) return rc;
+    if ((rc = ensure(h, &S->count, 4))) return rc;
+    hipLaunchKernelGGL(haar_gray_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->stream, frame_dev, ww,
+                       stride, (uint8_t*)S->gray.p, (long long)npix);
+    DFD_HIP_TRY(h, hipMemsetAsync(S->count.p, 0, 4, h->stream));
+    return DFD_OK;
+}
+
+// the launches of one scale, for the detector and for dfd_haar_tap alike: resize (unless the scale keeps the frame's size),
+// both integral images, the cascade per grid position, the candidates appended.  Returns the image that was evaluated.
+const uint8_t* haar_scale_run(dfd_handle* h, int hh, int ww, const HaarScale& G, int scale_idx) {
+    HaarState* S = h->haar;
+    hipStream_t s = h->stream;
+    const uint8_t* img = (const uint8_t*)S->gray.p;
+    if (G.sw != ww || G.sh != hh) {
+        launch_resize_gray((const uint8_t*)S->gray.p, hh, ww, (uint8_t*)S->scaled.p, G.sh, G.sw, s);
+        img = (const uint8_t*)S->scaled.p;
+    }
+    hipLaunchKernelGGL(haar_rowscan_kernel, dim3((G.sh + 1 + 63) / 64), dim3(64), 0, s, img, G.sw, G.sh, (unsigned*)S->sum.p,
+                       (unsigned long long*)S->sqsum.p);
+    hipLaunchKernelGGL(haar_colscan_kernel, dim3((G.sw + 1 + 255) / 256), dim3(256), 0, s, G.sw, G.sh, (unsigned*)S->sum.p,
+                       (unsigned long long*)S->sqsum.p);
+    hipLaunchKernelGGL(haar_eval_kernel, dim3((G.nx * G.ny + 255) / 256), dim3(256), 0, s, (const unsigned*)S->sum.p,
+                       (const unsigned long long*)S->sqsum.p, G.sw, G.nx, G.ny, G.step, S->win_w, S->win_h, S->stages, S->n_stages,
+                       S->stumps, S->rects, (int*)S->result.p);
+    hipLaunchKernelGGL(haar_collect_kernel, dim3((G.ny + 63) / 64), dim3(64), 0, s, (const int*)S->result.p, G.nx, G.ny, G.step,
+                       (int*)S->cand.p, (int*)S->count.p, CAP, scale_idx);
+    return img;
+}
+
 }  // namespace
 
 extern "C" {
 
 int dfd_has_haar(const dfd_handle* h) { return h && h->haar ? 1 : 0; }
 
-int dfd_detect_faces_haar(dfd_handle* h, const uint8_t* bgr, int hh, int ww, int stride, float scale_factor, int min_neighbors,
+int dfd_detect_faces_haar(dfd_handle* h, const uint8_t* bgr, int hh, int ww, int stride, double scale_factor, int min_neighbors,
                           int min_size, int32_t* xywh_out, int max_out, int* n_out, int* n_candidates) {
     if (!h) return DFD_ERR_ARG;
-    if (!bgr || !xywh_out || !n_out || max_out <= 0 || hh <= 0 || ww <= 0 || stride < ww * 3 || !(scale_factor > 1.0f))
+    if (!bgr || !xywh_out || !n_out || max_out <= 0 || hh <= 0 || ww <= 0 || stride < ww * 3 || !(scale_factor > 1.0))
         return fail(h, DFD_ERR_ARG, "detect_faces_haar: bad pointer, geometry or scale factor");
     *n_out = 0;
     if (n_candidates) *n_candidates = 0;
@@ -189,6 +257,47 @@ int dfd_detect_faces_haar(dfd_handle* h, const uint8_t* bgr, int hh, int ww, int
                     n_out, n_candidates);
 }
 
+int dfd_haar_tap(dfd_handle* h, const uint8_t* bgr, int hh, int ww, int stride, double scale_factor, int scale_index,
+                 const char* name, void* out, size_t capacity, size_t* bytes, int32_t* dims, double* factor) {
+    if (!h) return DFD_ERR_ARG;
+    if (!bgr || !dims || !factor || (name && (!out || !bytes)) || hh <= 0 || ww <= 0 || stride < ww * 3 || !(scale_factor > 1.0) ||
+        scale_index < 0)
+        return fail(h, DFD_ERR_ARG, "haar_tap: bad pointer, geometry, scale factor or scale index");
+    HaarState* S = h->haar;
+    if (!S) return fail(h, DFD_ERR_STATE, "no Haar cascade in the weights blob (weights.pack_all(..., haar=...))");
+    HaarScale G{}, at{};
+    int n_scales = 0;
+    for (double f = 1.0; haar_scale_at(S, hh, ww, f, &at); f *= scale_factor)
+        if (n_scales++ == scale_index) G = at;
+    if (scale_index >= n_scales) return fail(h, DFD_ERR_ARG, "haar_tap: scale index %d of %d scales", scale_index, n_scales);
+    const int d[8] = {G.sh, G.sw, G.ny, G.nx, G.step, G.win_w, G.win_h, n_scales};
+    std::copy(d, d + 8, dims);
+    *factor = G.factor;
+    if (!name) return DFD_OK;
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = ensure(h, &h->frame_buf, (size_t)hh * stride))) return rc;
+    DFD_HIP_TRY(h, hipMemcpyAsync(h->frame_buf.p, bgr, (size_t)hh * stride, hipMemcpyHostToDevice, h->stream));
+    if ((rc = haar_begin(h, (const uint8_t*)h->frame_buf.p, hh, ww, stride))) return rc;
+    const uint8_t* img = haar_scale_run(h, hh, ww, G, scale_index);
+    const std::string n(name);
+    const size_t sums = (size_t)(G.sh + 1) * (G.sw + 1);
+    const void* src = nullptr;
+    size_t nb = 0;
+    if (n == "gray") { src = S->gray.p; nb = (size_t)hh * ww; }
+    else if (n == "scaled") { src = img; nb = (size_t)G.sh * G.sw; }
+    else if (n == "sum") { src = S->sum.p; nb = sums * 4; }
+    else if (n == "sqsum") { src = S->sqsum.p; nb = sums * 8; }
+    else if (n == "result") { src = S->result.p; nb = (size_t)G.ny * G.nx * 4; }
+    else return fail(h, DFD_ERR_ARG, "haar_tap: no buffer named '%s' (gray, scaled, sum, sqsum, result)", name);
+    *bytes = nb;
+    if (nb > capacity) return fail(h, DFD_ERR_ARG, "haar_tap: '%s' holds %zu bytes, capacity %zu", name, nb, capacity);
+    DFD_HIP_TRY(h, hipMemcpyAsync(out, src, nb, hipMemcpyDeviceToHost, h->stream));
+    DFD_HIP_TRY(h, stream_sync(h));
+    DFD_HIP_TRY(h, hipGetLastError());
+    return DFD_OK;
+}
+
 }  // extern "C"
 
 namespace dfd {
@@ -196,7 +305,7 @@ namespace dfd {
 // detectMultiScale + groupRectangles on a frame already resident in HBM (the fallback inside dfd_analyze_frame /
 // dfd_analyze_jpeg when the handle has no SSD or the SSD pass failed: reference face_detection.py:58-66).
 // *n_total (optional) = number of grouped rectangles before max_out cut the list.
-int haar_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride, float scale_factor, int min_neighbors,
+int haar_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride, double scale_factor, int min_neighbors,
              int min_size, int32_t* xywh_out, int max_out, int* n_out, int* n_candidates, int* n_total) {
     *n_out = 0;
     if (n_candidates) *n_candidates = 0;
@@ -204,42 +313,15 @@ int haar_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride
     HaarState* S = h->haar;
     if (!S) return fail(h, DFD_ERR_STATE, "no Haar cascade in the weights blob (weights.pack_all(..., haar=...))");
     int rc;
-    const size_t npix = (size_t)hh * ww;
-    constexpr int CAP = 1 << 16;
-    if ((rc = ensure(h, &S->gray, npix))) return rc;
-    if ((rc = ensure(h, &S->scaled, npix))) return rc;
-    if ((rc = ensure(h, &S->sum, (size_t)(hh + 1) * (ww + 1) * 4))) return rc;
-    if ((rc = ensure(h, &S->sqsum, (size_t)(hh + 1) * (ww + 1) * 8))) return rc;
-    if ((rc = ensure(h, &S->result, npix * 4))) return rc;
-    if ((rc = ensure(h, &S->cand, (size_t)CAP * 12))) return rc;
-    if ((rc = ensure(h, &S->count, 4))) return rc;
+    if ((rc = haar_begin(h, frame_dev, hh, ww, stride))) return rc;
     hipStream_t s = h->stream;
-    hipLaunchKernelGGL(haar_gray_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, frame_dev, ww,
-                       stride, (uint8_t*)S->gray.p, (long long)npix);
-    DFD_HIP_TRY(h, hipMemsetAsync(S->count.p, 0, 4, s));
-    std::vector<double> factors;
-    for (double factor = 1.0;; factor *= (double)scale_factor) {
-        const int win_w = cv_round(S->win_w * factor), win_h = cv_round(S->win_h * factor);
-        const int sw = cv_round(ww / factor), sh = cv_round(hh / factor);
-        if (sw - S->win_w <= 0 || sh - S->win_h <= 0) break;
-        factors.push_back(factor);
-        if (win_w < min_size || win_h < min_size) continue;
-        const int step = factor > 2.0 ? 1 : 2;
-        const int nx = (sw - S->win_w + step - 1) / step, ny = (sh - S->win_h + step - 1) / step;
-        const uint8_t* img = (const uint8_t*)S->gray.p;
-        if (sw != ww || sh != hh) {
-            launch_resize_gray((const uint8_t*)S->gray.p, hh, ww, (uint8_t*)S->scaled.p, sh, sw, s);
-            img = (const uint8_t*)S->scaled.p;
-        }
-        hipLaunchKernelGGL(haar_rowscan_kernel, dim3((sh + 1 + 63) / 64), dim3(64), 0, s, img, sw, sh, (unsigned*)S->sum.p,
-                           (unsigned long long*)S->sqsum.p);
-        hipLaunchKernelGGL(haar_colscan_kernel, dim3((sw + 1 + 255) / 256), dim3(256), 0, s, sw, sh, (unsigned*)S->sum.p,
-                           (unsigned long long*)S->sqsum.p);
-        hipLaunchKernelGGL(haar_eval_kernel, dim3((nx * ny + 255) / 256), dim3(256), 0, s, (const unsigned*)S->sum.p,
-                           (const unsigned long long*)S->sqsum.p, sw, nx, ny, step, S->win_w, S->win_h, S->stages, S->n_stages,
-                           S->stumps, S->rects, (int*)S->result.p);
-        hipLaunchKernelGGL(haar_collect_kernel, dim3((ny + 63) / 64), dim3(64), 0, s, (const int*)S->result.p, nx, ny, step,
-                           (int*)S->cand.p, (int*)S->count.p, CAP, (int)factors.size() - 1);
+    std::vector<HaarScale> scales;
+    HaarScale G;
+    // the factor is a double product of the double scale factor, as OpenCV's: 1.1f would round some image sizes the other way
+    for (double factor = 1.0; haar_scale_at(S, hh, ww, factor, &G); factor *= scale_factor) {
+        scales.push_back(G);
+        if (G.win_w < min_size || G.win_h < min_size) continue;
+        haar_scale_run(h, hh, ww, G, (int)scales.size() - 1);
     }
     int count = 0;
     DFD_HIP_TRY(h, hipMemcpyAsync(&count, S->count.p, 4, hipMemcpyDeviceToHost, s));
@@ -253,8 +335,8 @@ int haar_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride
     std::sort(c3.begin(), c3.end());                              // (scale, y, x): the sequential scan order
     std::vector<Rect> rects;
     for (const auto& c : c3) {
-        const double f = factors[c[0]];
-        rects.push_back(Rect{cv_round(c[2] * f), cv_round(c[1] * f), cv_round(S->win_w * f), cv_round(S->win_h * f)});
+        const HaarScale& g = scales[c[0]];
+        rects.push_back(Rect{cv_round(c[2] * g.factor), cv_round(c[1] * g.factor), g.win_w, g.win_h});
     }
     if (n_candidates) *n_candidates = count;
     const std::vector<Rect> out = group_rectangles(rects, min_neighbors, 0.2);
@@ -270,3 +352,4 @@ int haar_run(dfd_handle* h, const uint8_t* frame_dev, int hh, int ww, int stride
 }
 
 }  // namespace dfd
+

@@ -10,6 +10,8 @@
 //                                             one process: "ok=<decoded> rejected=<errors>"; any memory error aborts
 //   host_asan_driver blobfuzz FILE SEED N  -> the same for the weights blob's table
 //   host_asan_driver blob  FILE            -> "rc=<0|-2> tensors=<n>"
+//   host_asan_driver haar  FILE            -> the cascade check of haar_init (haar_validate.h) on the "haar.*" tensors of a
+//                                             weights blob: "rc=<0|-2> <what is wrong>"
 //   host_asan_driver rows  FILE H W THR    -> SSD rows [n][5] f32 -> "n=<kept> total=<all> boxes..."
 //   host_asan_driver rects FILE THR        -> int32 [n][4] -> grouped rectangles
 //   host_asan_driver score FILE            -> the analyzer's host half (forensic_score.h) on the frames of ONE stream, float64
@@ -25,6 +27,7 @@
 
 #include "blob_reader.h"
 #include "forensic_score.h"
+#include "haar_validate.h"
 #include "host_boxes.h"
 #include "jpeg_entropy.h"
 
@@ -125,6 +128,23 @@ int main(int argc, char** argv) {
             for (auto& kv : t)
                 for (size_t i = 0; i < kv.second.count; ++i) sum += kv.second.host[i];
         printf("rc=%d tensors=%zu sum=%g %s\n", ok ? 0 : DFD_ERR_BLOB, t.size(), sum, err.c_str());
+        return 0;
+    }
+    if (cmd == "haar") {
+        std::map<std::string, dfd::Tensor> t;
+        std::string err;
+        if (!dfd::parse_blob(data.data(), data.size(), &t, &err)) { printf("rc=%d %s\n", DFD_ERR_BLOB, err.c_str()); return 0; }
+        // haar_init's own size checks, then exact-size heap copies: an index past a table hits a redzone
+        const dfd::Tensor &w = t["haar.win"], &st = t["haar.stages"], &sp = t["haar.stumps"], &rc = t["haar.rects"];
+        if (!w.host || !st.host || !sp.host || !rc.host || w.count != 2 || st.count % 3 || sp.count % 4 || rc.count % 15) {
+            printf("rc=%d malformed haar.* tensors\n", DFD_ERR_BLOB);
+            return 0;
+        }
+        const std::vector<float> hw(w.host, w.host + 2), hst(st.host, st.host + st.count), hsp(sp.host, sp.host + sp.count),
+            hrc(rc.host, rc.host + rc.count);
+        const char* why = dfd::haar_cascade_error(hw.data(), hst.data(), hst.size() / 3, hsp.data(), hsp.size() / 4, hrc.data(),
+                                                  hrc.size() / 15);
+        printf("rc=%d %s\n", why ? DFD_ERR_BLOB : 0, why ? why : "sound");
         return 0;
     }
     if (cmd == "rows" && argc >= 6) {

@@ -516,7 +516,7 @@ int analyze_frame_resident(dfd_handle* h, int stream_id, int hh, int ww, int str
     rc = h->ssd ? detect_run(h, fd, hh, ww, stride, conf_thr, xywh_out, nullptr, max_faces, &n) : DFD_ERR_STATE;
     if (rc) {
         if (!h->haar) return rc;
-        if ((rc = haar_run(h, fd, hh, ww, stride, 1.1f, 5, 30, xywh_out, max_faces, &n, nullptr, &h->last_detections))) return rc;
+        if ((rc = haar_run(h, fd, hh, ww, stride, 1.1, 5, 30, xywh_out, max_faces, &n, nullptr, &h->last_detections))) return rc;
     }
     *n_faces_out = n;
     // every returned face is classified, in chunks of the handle's batch capacity (predict votes on all detections,

@@ -187,7 +187,7 @@ int analyze_streams(dfd_handle* h, int n, const uint8_t* const* data, const size
     if (rc) {                                                        // reference face_detection.py:58-66
         if (!h->haar) return rc;
         for (int f : det)
-            if ((rc = haar_run(h, frames + fd[f].offset, fh[f], fw[f], fd[f].stride, 1.1f, 5, 30, xywh_out + (size_t)f * max_faces * 4,
+            if ((rc = haar_run(h, frames + fd[f].offset, fh[f], fw[f], fd[f].stride, 1.1, 5, 30, xywh_out + (size_t)f * max_faces * 4,
                                max_faces, &n_faces_out[f], nullptr, &total[f])))
                 return rc;
     }

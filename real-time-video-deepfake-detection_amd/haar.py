@@ -7,7 +7,9 @@ into the arrays `weights.pack_all(..., haar=...)` puts into the blob; csrc/haar_
 
 The XML itself ships with OpenCV, not with the reference tree or this one: point ``$DFD_HAAR_CASCADE`` at it.
 Not supported (rejected with a clear error): tilted features, trees deeper than stumps, LBP / HOG cascades, the old
-(OpenCV 1.x) cascade layout.
+(OpenCV 1.x) cascade layout.  A cascade whose numbers would take the device outside its tables or its window - a feature
+index past the feature table, a rectangle past the window, non-finite values - is a ``ValueError`` here
+(`validate_cascade`) and ``DFD_ERR_BLOB`` at `dfd_create` (csrc/haar_validate.h, the same list).
 """
 from __future__ import annotations
 
@@ -47,8 +49,51 @@ def load_cascade_xml(path_or_text: str) -> Dict[str, np.ndarray]:
         while len(rs) < 3:
             rs.append([0, 0, 0, 0, 0.0])
         rects.append(rs)
-    return {"haar.win": np.asarray(win, np.float32), "haar.stages": np.asarray(stages, np.float32),
-            "haar.stumps": np.asarray(stumps, np.float32), "haar.rects": np.asarray(rects, np.float32).reshape(len(rects), 15)}
+    cas = {"haar.win": np.asarray(win, np.float32), "haar.stages": np.asarray(stages, np.float32).reshape(-1, 3),
+           "haar.stumps": np.asarray(stumps, np.float32).reshape(-1, 4),
+           "haar.rects": np.asarray(rects, np.float32).reshape(len(rects), 15)}
+    validate_cascade(cas)
+    return cas
+
+
+def validate_cascade(cas: Dict[str, np.ndarray]) -> None:
+    """ValueError unless the arrays are a cascade the device can evaluate inside its buffers: the list of
+    csrc/haar_validate.h, which `dfd_create` applies to the blob (DFD_ERR_BLOB).  Slots 0 and 1 of a feature are always
+    read, so their geometry must fit whatever their weight; slot 2 is read only with a non-zero weight."""
+    def bad(what):
+        raise ValueError("Haar cascade: " + what)
+
+    def ints(v, lo, hi):
+        return bool(np.all((v >= lo) & (v <= hi) & (v == np.floor(v))))       # NaN and infinities fail every comparison
+
+    win = np.asarray(cas["haar.win"], np.float32).ravel()
+    stages = np.asarray(cas["haar.stages"], np.float32).reshape(-1, 3)
+    stumps = np.asarray(cas["haar.stumps"], np.float32).reshape(-1, 4)
+    rects = np.asarray(cas["haar.rects"], np.float32).reshape(-1, 3, 5)
+    if win.size != 2 or not ints(win, 4, 4096):
+        bad("window is not an integer size of 4 .. 4096")
+    if not (len(stages) and len(stumps) and len(rects)):
+        bad("no stages, stumps or features")
+    first, count = stages[:, 0].astype(np.float64), stages[:, 1].astype(np.float64)
+    if not (ints(first, 0, len(stumps)) and ints(count, 1, len(stumps)) and np.all(first + count <= len(stumps))):
+        bad("a stage's stumps run outside the stump table")
+    if np.any(first[1:] != (first + count)[:-1]):
+        bad("stages are not contiguous in order")
+    if not np.all(np.isfinite(stages[:, 2])):
+        bad("a stage threshold is not finite")
+    if not ints(stumps[:, 0], 0, len(rects) - 1):
+        bad("a stump's feature index is outside the feature table")
+    if not np.all(np.isfinite(stumps[:, 1:])):
+        bad("a stump's threshold or leaf is not finite")
+    if not np.all(np.isfinite(rects)):
+        bad("a rectangle holds a value that is not finite")
+    unused = rects[:, 2, 4] == 0
+    if np.any(rects[unused, 2, :4] != 0):
+        bad("an unused third rectangle has geometry")
+    r = np.concatenate([rects[:, :2].reshape(-1, 5), rects[~unused, 2]]).astype(np.float64)
+    if not (ints(r[:, 0], 0, win[0]) and ints(r[:, 1], 0, win[1]) and ints(r[:, 2], 1, win[0]) and ints(r[:, 3], 1, win[1])
+            and np.all(r[:, 0] + r[:, 2] <= win[0]) and np.all(r[:, 1] + r[:, 3] <= win[1])):
+        bad("a rectangle is not an integer box inside the window")
 
 
 def detect_faces_haar(frame, handle):

@@ -3,57 +3,15 @@ test in OpenCV's XML layout (bright blob on a darker surround: centre-surround, 
 stumps over three stages) stands in for haarcascade_frontalface_default.xml, which ships with OpenCV, not with the
 reference.  CPU: XML reader, the oracle's grouping against hand-worked cases.  GPU: dfd_detect_faces_haar equals the
 oracle - candidate count and grouped boxes - on frames with planted blobs of several sizes, on noise and on a frame
-smaller than the window; the host falls back to it when the handle has no SSD."""
+smaller than the window; the host falls back to it when the handle has no SSD.  The cascade and the frame builder live
+in tests/haar_cases.py; tests/test_haar_stages_gpu.py holds the same path to the oracle launch by launch."""
 import numpy as np
 import pytest
 
 from oracle import haar_ref
 
-XML = """<?xml version="1.0"?>
-<opencv_storage>
-<cascade>
-  <stageType>BOOST</stageType>
-  <featureType>HAAR</featureType>
-  <height>24</height>
-  <width>24</width>
-  <stageParams><boostType>GAB</boostType><maxWeakCount>3</maxWeakCount></stageParams>
-  <featureParams><maxCatCount>0</maxCatCount><featSize>1</featSize><mode>BASIC</mode></featureParams>
-  <stageNum>3</stageNum>
-  <stages>
-    <_><maxWeakCount>1</maxWeakCount><stageThreshold>0.5</stageThreshold>
-      <weakClassifiers>
-        <_><internalNodes>0 -1 0 0.7</internalNodes><leafValues>-1. 1.</leafValues></_>
-      </weakClassifiers></_>
-    <_><maxWeakCount>2</maxWeakCount><stageThreshold>1.5</stageThreshold>
-      <weakClassifiers>
-        <_><internalNodes>0 -1 1 -0.2</internalNodes><leafValues>-1. 1.</leafValues></_>
-        <_><internalNodes>0 -1 1 0.2</internalNodes><leafValues>1. -1.</leafValues></_>
-      </weakClassifiers></_>
-    <_><maxWeakCount>3</maxWeakCount><stageThreshold>2.5</stageThreshold>
-      <weakClassifiers>
-        <_><internalNodes>0 -1 2 -0.2</internalNodes><leafValues>-1. 1.</leafValues></_>
-        <_><internalNodes>0 -1 2 0.2</internalNodes><leafValues>1. -1.</leafValues></_>
-        <_><internalNodes>0 -1 3 0.4</internalNodes><leafValues>-1. 1.</leafValues></_>
-      </weakClassifiers></_>
-  </stages>
-  <features>
-    <_><rects><_>0 0 24 24 -1.</_><_>6 6 12 12 4.</_></rects><tilted>0</tilted></_>
-    <_><rects><_>0 0 24 24 -1.</_><_>0 0 12 24 2.</_></rects><tilted>0</tilted></_>
-    <_><rects><_>0 0 24 24 -1.</_><_>0 0 24 12 2.</_></rects><tilted>0</tilted></_>
-    <_><rects><_>2 2 20 20 -1.</_><_>8 8 8 8 6.25</_><_>0 0 1 1 0.5</_></rects><tilted>0</tilted></_>
-  </features>
-</cascade>
-</opencv_storage>
-"""
-
-
-def _frame(h, w, blobs, seed):
-    rs = np.random.RandomState(seed)
-    f = rs.randint(30, 70, (h, w, 3)).astype(np.float32)
-    yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
-    for cx, cy, r in blobs:
-        f += 150.0 * np.exp(-(((xx - cx) / r) ** 2 + ((yy - cy) / r) ** 2))[..., None]
-    return np.clip(f, 0, 255).astype(np.uint8)
+from haar_cases import TOY_XML as XML            # the cascade and the frame builder live with the other Haar test material
+from haar_cases import noise_frame as _frame
 
 
 def test_xml_reader(pkg):

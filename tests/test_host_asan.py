@@ -202,6 +202,37 @@ def test_detector_box_logic_on_hostile_rows(driver, tmp_path):
     assert driver("rects", p, 0).startswith("n=5")
 
 
+def test_haar_cascade_check_on_sound_and_malformed_cascades(driver, tmp_path, pkg):
+    """haar_init's host-side check (csrc/haar_validate.h) over exact-size copies of the four tensors: every cascade of
+    tests/haar_cases.py is sound, every malformed one is refused (DFD_ERR_BLOB = -2) for the reason the Python reader
+    gives, and no index the check follows leaves a table"""
+    import haar_cases as C
+
+    def run(cas, tag):
+        p = tmp_path / f"haar-{tag}.blob"
+        p.write_bytes(bytes(pkg.weights.serialize({k: np.asarray(v, np.float32) for k, v in cas.items()})))
+        return driver("haar", p)
+
+    for name, make in C.CASCADES.items():
+        assert run(make(), name) == "rc=0 sound", name
+    n = 0
+    for b, base in enumerate((C.ties(), C.wide())):
+        for i, (what, cas, _) in enumerate(C.malformed(base)):
+            with pytest.raises(ValueError) as e:
+                pkg.haar.validate_cascade(cas)
+            assert run(cas, f"{b}-{i}") == "rc=-2 " + str(e.value).replace("Haar cascade: ", ""), what
+            n += 1
+    assert n >= 36
+    # tensor sizes that do not divide, a missing tensor, an empty table
+    odd = dict(C.ties())
+    odd["haar.rects"] = odd["haar.rects"].ravel()[:-1]
+    assert run(odd, "odd").startswith("rc=-2 malformed")
+    assert run({k: v for k, v in C.ties().items() if k != "haar.stumps"}, "missing").startswith("rc=-2 malformed")
+    empty = dict(C.ties())
+    empty["haar.stumps"] = np.zeros((0, 4), np.float32)
+    assert run(empty, "empty").startswith("rc=-2 no stages")
+
+
 # ------------------------------------------------------------------------------------------------ forensic scoring
 # The analyzer's host half (csrc/forensic_score.h: thresholds, temporal deque, weighted sum) on seeded statistics, against
 # the project's Python restatements: oracle.forensics_ref.ForensicsRef for the five stateless scores and the mean
