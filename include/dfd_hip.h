@@ -67,9 +67,12 @@ int dfd_max_batch(const dfd_handle* h);
  *   value is signed now and any value < 0 means "unset" (it used to be read as an unsigned mask of every block); an
  *   unset mask and the explicit value (1 << 8) | (1 << 9) give the same results, but only the unset one lets "fuse_k5"
  *   take blocks 8 and 9.
- *   "fuse_k5" (default 1, env DFD_FUSE_K5; fp32 activations with "fuse_late"): blocks 8-10 (k5, stride 1, 14 x 14) run
+ *   "fuse_k5" (default 1, env DFD_FUSE_K5; fp32 activations with "fuse_late"): blocks 6-11, every block whose input is
+ *   a 14 x 14 map (6 and 7: k3; 8-10: k5; 11: k5 at stride 2, 14 -> 7), run
  *   expand + depthwise with ONE thread block per image that walks every 32-channel chunk - inputs loaded and split into
  *   bf16 terms once, four waves expanding chunk c + 1 while four run the depthwise phase of chunk c (mbconv_k5_kernel).
+ *   Block 11 has no "fuse_late" form of its own: with this option off, below the threshold, or with bit 11 set in an
+ *   explicit "fuse_late_skip" it runs expand GEMM + depthwise kernel, and the kernel gives it those launches' bits.
  *   A launch of one block per image takes the same time for 1 image and for one per compute unit, so the plan takes it
  *   only where the last round of blocks holds at least "fuse_k5_min" images (default, and any value <= 0: 208 of 256,
  *   the measured break-even; env DFD_FUSE_K5_MIN); smaller batches run the launches of "fuse_k5" = 0.  The kernel

@@ -86,9 +86,10 @@ int depthwise_tiles(int H, int C, int k, int stride);
 // split-precision operands (We3 = the three bf16 planes of We [C][Cin] from launch_split_weights, `plane`
 // elements apart, rows Kp long), then the depthwise conv as above.  Xin: block input [n][H][H][Cin]; be [C].
 // Returns false when no instantiation covers the shape (callers then run the GEMM + launch_depthwise).
-// late: the whole-image launches of blocks 6-15 (option "fuse_late"); k5: among those, fp32 blocks 8-10 through
+// late: the whole-image launches of blocks 6-15 (option "fuse_late"); k5: among those, fp32 blocks 6-11 through
 // mbconv_k5_kernel (option "fuse_k5"): 1 = with mbconv_late_kernel's result bits, 2 = with those of expand GEMM + depthwise
-// kernel (the expand bias added after the products instead of in front of them).
+// kernel (the expand bias added after the products instead of in front of them).  Block 11 has form 2 only, blocks 6 and 7
+// form 1 only; a request for a form the block has no instance of returns false.
 template <typename XT>
 bool launch_mbconv_front(const XT* Xin, int Cin, const unsigned short* We3, int plane, int Kp, const float* Wef, const float* be,
                          const float* Wd, const float* bd, XT* Y, float* P, int n, int H, int C, int k, int stride,
@@ -103,8 +104,8 @@ bool launch_mbconv_front_proj0(const float* Xdw0, const float* gate0, const unsi
                                const float* Wef, const float* be, const float* Wd, const float* bd, float* Y, float* P, int n,
                                int H, int C, int k, int stride, int Cin, int pad_lo, int* tiles, hipStream_t s);
 // pool-tile count of the fused launch (the larger of the fp32 and bf16 kernels'), -1: none.  late: also the whole-image launches of blocks 6-15
-// (mbconv_late_kernel, option "fuse_late")
-int mbconv_tiles(int H, int C, int k, int stride, int Cin, bool late = false);
+// (mbconv_late_kernel, option "fuse_late"); k5: also a block that has no such instance but one of mbconv_k5_kernel (block 11)
+int mbconv_tiles(int H, int C, int k, int stride, int Cin, bool late = false, bool k5 = false);
 // the block shapes (and padding) mbconv_k5_kernel covers; launch_mbconv_front with k5 != 0 fails for any other
 bool mbconv_k5_shape(int H, int C, int k, int stride, int Cin, int pad_lo);
 

@@ -14,8 +14,8 @@
 //                      (PROJ0: block 0's projection folded into block 1's launch)
 //  mbconv2_kernel      the same, second generation: fp32 blocks 2, 4 and bf16 blocks 1-5
 //  mbconv_late_kernel  the same for blocks 6-10 and 12-15: whole 14 x 14 / 7 x 7 images per block
-//  mbconv_k5_kernel    the same for the fp32 blocks 8-10 (k5 at 14 x 14): one block per image walks every channel chunk,
-//                      four waves expand chunk c + 1 while four run the depthwise phase of chunk c
+//  mbconv_k5_kernel    the same for the fp32 blocks 6-11 (k3 / k5 at 14 x 14, block 11 at stride 2): one block per image
+//                      walks every channel chunk, four waves expand chunk c + 1 while four run the depthwise phase of chunk c
 //  se_kernel           pool finish + two tiny FCs -> per-(image,channel) gate
 //  avgpool_kernel      global average pool of the head conv output
 //
@@ -1529,7 +1529,10 @@ static void mb_late_launch(const XT* X, const unsigned short* We3, int plane, in
                        Y, P, n, C, pad_lo);
 }
 
-// ---- blocks 8-10 (k5, stride 1, 14 x 14, C_exp = 480 / 672): ONE block per image (round 6, option "fuse_k5") -----------
+// ---- blocks 6-11 (14 x 14 input, C_exp = 480 / 672): ONE block per image (rounds 6 and 7, option "fuse_k5") ------------
+// Instances: k5 stride 1 (blocks 8-10, round 6), k3 stride 1 (blocks 6 and 7) and k5 stride 2 (block 11, 14 -> 7).  The
+// tile geometry follows K and S: width IW = (14 / S - 1) * S + K = 18 / 16 / 17, PAD = (IW - 14) / 2 = 2 / 1 / 1 zero rows
+// and columns on the low side, the rest (block 11: two) on the high side.
 // mbconv_late_kernel gives an image to C_exp / 32 = 15 or 21 blocks, and each of them reads the image's 196 x C_in
 // activations again, splits them into the three bf16 planes again (170 of the 1,323 VALU instructions of a wave), rewrites
 // the tile's zero border, restages its weight rows and runs expand and depthwise one after the other.  Here a block of
@@ -1547,18 +1550,20 @@ static void mb_late_launch(const XT* X, const unsigned short* We3, int plane, in
 // The zero border of both tiles is written once per block.  Result bits: those of mbconv_late_kernel, or - BIAS_LAST:
 // accumulators start at zero and the expand bias is added in front of the swish, the one operation in which the expand
 // GEMM's epilogue (s6_products + bias + swish) differs from the fused launches - those of expand GEMM + dw_kernel.
-template <int CEXP, int CIN, bool BIAS_LAST>
+template <int K, int S, int CEXP, int CIN, bool BIAS_LAST>
 __global__ __launch_bounds__(512) void mbconv_k5_kernel(const float* __restrict__ X, const unsigned short* __restrict__ We3,
                                                         int plane, int Kp, const float* __restrict__ be,
                                                         const float* __restrict__ Wt, const float* __restrict__ bias,
                                                         float* __restrict__ Y, float* __restrict__ P) {
-    constexpr int K = 5, CB = 32, CG = 8, NTB = 2, NPX = 196, MTR = 3, PAD = 2;
+    constexpr int CB = 32, CG = 8, NTB = 2, NPX = 196, MTR = 3;
     constexpr int NK = (CIN + 31) / 32, NC = CEXP / CB;
-    constexpr int IW = 14 - 1 + K, SWZ = 2, NPIX = IW * IW, NUNIT = NPIX * (CG + 1);
+    constexpr int HO = 14 / S, RP = S == 1 ? 7 : 1;                   // depthwise output = the whole image; outputs per strip
+    constexpr int IW = (HO - 1) * S + K, PAD = (IW - 14) / 2;         // TF-SAME: the odd row / column of padding on the high side
+    constexpr int SWZ = 2, NPIX = IW * IW, NUNIT = NPIX * (CG + 1);
     constexpr int KROW = NK * 32 + 8, WROWS = 3 * CB * KROW;          // as mbconv_late_kernel's wlds
     constexpr int CPR = NK * 4, NCH = 3 * CB * CPR, NLD = (NCH + 255) / 256;
     constexpr int NWL = K * K * CG;
-    static_assert(CIN % 8 == 0 && CEXP % CB == 0 && NWL <= 256 && NK * 16 <= 256, "shape");
+    static_assert(CIN % 8 == 0 && CEXP % CB == 0 && NWL <= 256 && NK * 16 <= 256 && 14 % S == 0 && IW >= 14, "shape");
     __shared__ v4f tile[2 * NUNIT];
     __shared__ v4f wl[2 * NWL];
     __shared__ v4f red[4 * CG];
@@ -1627,8 +1632,8 @@ __global__ __launch_bounds__(512) void mbconv_k5_kernel(const float* __restrict_
             bv_prev = st.bv;
             stage_load(t + 2, t + 1, st);
             if (t > 0)
-                dw_compute<K, 1, CB, 14, 14, 7, SWZ, float, 256>(tile + ((t - 1) & 1) * NUNIT, wl + ((t - 1) & 1) * NWL, red, bv, Y, P,
-                                                                  img, 14, CEXP, (t - 1) * CB, 0, 0, 0, 1);
+                dw_compute<K, S, CB, HO, HO, RP, SWZ, float, 256>(tile + ((t - 1) & 1) * NUNIT, wl + ((t - 1) & 1) * NWL, red, bv, Y, P,
+                                                                   img, HO, CEXP, (t - 1) * CB, 0, 0, 0, 1);
             else
                 __syncthreads();
             __syncthreads();
@@ -1715,34 +1720,55 @@ __global__ __launch_bounds__(512) void mbconv_k5_kernel(const float* __restrict_
     }
 }
 
-// the shapes mbconv_k5_kernel has an instance for: the K5 rows of DFD_MB_LATE_TABLE with TF-SAME padding (the plan asks
-// before it requests the kernel; a request the launcher cannot serve is an error there, not a fall-back)
-bool mbconv_k5_shape(int H, int C, int k, int stride, int Cin, int pad_lo) {
-    return H == 14 && k == 5 && stride == 1 && pad_lo == 2 && ((C == 480 && Cin == 80) || (C == 672 && Cin == 112));
-}
-
-template <int C, int CIN>
-static bool mb_k5_launch(const float* X, const unsigned short* We3, int plane, int Kp, const float* be, const float* W, const float* b,
-                         float* Y, float* P, int n, int pad_lo, int* tiles, hipStream_t s, bool bias_last) {
-    if (!mbconv_k5_shape(14, C, 5, 1, CIN, pad_lo)) return false;     // (the plan asks first: it never gets here)
-    *tiles = 1;
-    if (bias_last) hipLaunchKernelGGL((mbconv_k5_kernel<C, CIN, true>), dim3(n), dim3(512), 0, s, X, We3, plane, Kp, be, W, b, Y, P);
-    else hipLaunchKernelGGL((mbconv_k5_kernel<C, CIN, false>), dim3(n), dim3(512), 0, s, X, We3, plane, Kp, be, W, b, Y, P);
-    return true;
-}
-
-// (k, stride, H, C, Cin) of blocks 6-10 and 12-15 (block 11, 14 -> 7 at stride 2, measured 115 us in this form against
-// 110 us as GEMM + depthwise: left out).  Row kinds:
+// (k, stride, H, C, Cin) of blocks 6-15.  Row kinds:
 //   L    mbconv_late_kernel<K,S,H,Cin,XT>: one block per image (7 x 7: per four images) and 32 channels
-//   K5   an L row that fp32 activations also run as mbconv_k5_kernel<C,Cin,BIAS_LAST>, one block per image, where the plan asks
-//        for it (option "fuse_k5" and a batch that fills the CUs; BIAS_LAST: with the bits of expand GEMM + depthwise
+//   K5   an L row that fp32 activations also run as mbconv_k5_kernel<K,S,C,Cin,BIAS_LAST>, one block per image, where the plan
+//        asks for it (option "fuse_k5" and a batch that fills the CUs; BIAS_LAST: with the bits of expand GEMM + depthwise
 //        kernel instead of mbconv_late_kernel's)
-#define DFD_MB_LATE_TABLE(L, K5)  \
-    L(3, 1, 14, 480, 80)       \
+//   K5L  a K5 row without the BIAS_LAST instance (blocks 6 and 7: no mask covers them by default, so nothing asks for it)
+//   K5O  mbconv_k5_kernel only, always BIAS_LAST (block 11, 14 -> 7 at stride 2: as an mbconv_late_kernel launch, 21 blocks
+//        per image, it measured 115 us against 110 us as GEMM + depthwise, so it has no L instance).  Without the plan's
+//        request the block runs as expand GEMM + depthwise kernel
+#define DFD_MB_LATE_TABLE(L, K5, K5L, K5O)  \
+    K5L(3, 1, 14, 480, 80)     \
     K5(5, 1, 14, 480, 80)      \
     K5(5, 1, 14, 672, 112)     \
+    K5O(5, 2, 14, 672, 112)    \
     L(5, 1, 7, 1152, 192)      \
     L(3, 1, 7, 1152, 192)
+#define DFD_MB_SKIP(...)
+#define DFD_MB_KEY(KK, SS, HH, CC, CI) (k == KK && stride == SS && H == HH && C == CC && Cin == CI)
+
+// the shapes mbconv_k5_kernel has an instance for: the K5, K5L and K5O rows of DFD_MB_LATE_TABLE with TF-SAME padding (the plan
+// asks before it requests the kernel; a request the launcher cannot serve is an error there, not a fall-back)
+bool mbconv_k5_shape(int H, int C, int k, int stride, int Cin, int pad_lo) {
+#define DFD_MB_K5_SHAPE(KK, SS, HH, CC, CI) \
+    if (DFD_MB_KEY(KK, SS, HH, CC, CI) && pad_lo == ((HH / SS - 1) * SS + KK - HH) / 2) return true;
+    DFD_MB_LATE_TABLE(DFD_MB_SKIP, DFD_MB_K5_SHAPE, DFD_MB_K5_SHAPE, DFD_MB_K5_SHAPE)
+#undef DFD_MB_K5_SHAPE
+    return false;
+}
+
+// FORMS: the instances the row has - bit 0 mbconv_late_kernel's bits, bit 1 BIAS_LAST; a request for the other one fails
+template <int K, int S, int C, int CIN, int FORMS>
+static bool mb_k5_launch(const float* X, const unsigned short* We3, int plane, int Kp, const float* be, const float* W, const float* b,
+                         float* Y, float* P, int n, int pad_lo, int* tiles, hipStream_t s, bool bias_last) {
+    if (!mbconv_k5_shape(14, C, K, S, CIN, pad_lo)) return false;     // (the plan asks first: it never gets here)
+    *tiles = 1;
+    if constexpr ((FORMS & 2) != 0) {
+        if (bias_last) {
+            hipLaunchKernelGGL((mbconv_k5_kernel<K, S, C, CIN, true>), dim3(n), dim3(512), 0, s, X, We3, plane, Kp, be, W, b, Y, P);
+            return true;
+        }
+    }
+    if constexpr ((FORMS & 1) != 0) {
+        if (!bias_last) {
+            hipLaunchKernelGGL((mbconv_k5_kernel<K, S, C, CIN, false>), dim3(n), dim3(512), 0, s, X, We3, plane, Kp, be, W, b, Y, P);
+            return true;
+        }
+    }
+    return false;
+}
 
 // The fused expand + depthwise launch of blocks 1-5, where the expanded tensor dominates HBM traffic and C_in <= 48: one
 // row per activation type and block names the ONE kernel instance that runs it.  launch_mbconv_front, the "fuse_proj0"
@@ -1770,8 +1796,6 @@ static bool mb_k5_launch(const float* X, const unsigned short* We3, int plane, i
     G2(bf16_t, 5, 2, 56, 144, 24, 16, 7, 14, 7, 1, 256, false, 2)     /* block 3 */   \
     G2(bf16_t, 5, 1, 28, 240, 40, 16, 28, 28, 7, 2, 512, false, 4)    /* block 4 */   \
     G2(bf16_t, 3, 2, 28, 240, 40, 16, 7, 14, 2, 2, 256, false, 2)     /* block 5 */
-#define DFD_MB_SKIP(...)
-#define DFD_MB_KEY(KK, SS, HH, CC, CI) (k == KK && stride == SS && H == HH && C == CC && Cin == CI)
 
 template <int K, int S, int CB, int TH, int TW, int RP, int NK, typename XT, int NT, bool INS, int CI, int MINB>
 static void mb2_launch(const XT* X, int Cin, const unsigned short* We3, int plane, int Kp, const float* Wef, const float* be,
@@ -1796,14 +1820,19 @@ bool launch_mbconv_front(const XT* Xin, int Cin, const unsigned short* We3, int 
         mb_late_launch<KK, SS, HH, CI, XT>(Xin, We3, plane, Kp, be, Wd, bd, Y, P, n, C, pad_lo, tiles, s);          \
         return true;                                                                                                \
     }
-#define DFD_MB_K5_DISPATCH(KK, SS, HH, CC, CI)                                                                       \
+#define DFD_MB_K5_FORMS(KK, SS, HH, CC, CI, FORMS)                                                                   \
     if constexpr (std::is_same_v<XT, float>) {                                                                      \
         if (k5 && k == KK && stride == SS && H == HH && C == CC && Cin == CI)  /* no quiet fall-back to the L row */  \
-            return mb_k5_launch<CC, CI>(Xin, We3, plane, Kp, be, Wd, bd, Y, P, n, pad_lo, tiles, s, k5 == 2);        \
-    }                                                                                                               \
-    DFD_MB_LATE_DISPATCH(KK, SS, HH, CC, CI)
-        DFD_MB_LATE_TABLE(DFD_MB_LATE_DISPATCH, DFD_MB_K5_DISPATCH)
+            return mb_k5_launch<KK, SS, CC, CI, FORMS>(Xin, We3, plane, Kp, be, Wd, bd, Y, P, n, pad_lo, tiles, s, k5 == 2); \
+    }
+#define DFD_MB_K5_DISPATCH(KK, SS, HH, CC, CI) DFD_MB_K5_FORMS(KK, SS, HH, CC, CI, 3) DFD_MB_LATE_DISPATCH(KK, SS, HH, CC, CI)
+#define DFD_MB_K5L_DISPATCH(KK, SS, HH, CC, CI) DFD_MB_K5_FORMS(KK, SS, HH, CC, CI, 1) DFD_MB_LATE_DISPATCH(KK, SS, HH, CC, CI)
+#define DFD_MB_K5O_DISPATCH(KK, SS, HH, CC, CI) DFD_MB_K5_FORMS(KK, SS, HH, CC, CI, 2)
+        DFD_MB_LATE_TABLE(DFD_MB_LATE_DISPATCH, DFD_MB_K5_DISPATCH, DFD_MB_K5L_DISPATCH, DFD_MB_K5O_DISPATCH)
+#undef DFD_MB_K5O_DISPATCH
+#undef DFD_MB_K5L_DISPATCH
 #undef DFD_MB_K5_DISPATCH
+#undef DFD_MB_K5_FORMS
 #undef DFD_MB_LATE_DISPATCH
         return false;
     }
@@ -1854,7 +1883,7 @@ template bool launch_mbconv_front<float>(const float*, int, const unsigned short
 template bool launch_mbconv_front<bf16_t>(const bf16_t*, int, const unsigned short*, int, int, const float*, const float*, const float*, const float*, bf16_t*, float*, int, int, int, int, int, int, int*, hipStream_t, bool, int);
 
 // SE pool partial-sum tiles of a fused launch (the workspace is sized for the larger count of the two activation types)
-int mbconv_tiles(int H, int C, int k, int stride, int Cin, bool late) {
+int mbconv_tiles(int H, int C, int k, int stride, int Cin, bool late, bool k5) {
     const int Ho = (H + stride - 1) / stride;
     int best = -1;
 #define DFD_MB_TILES(TY, KK, SS, HH, CC, CI, CB, TH, TW, ...)                        \
@@ -1866,7 +1895,10 @@ int mbconv_tiles(int H, int C, int k, int stride, int Cin, bool late) {
 #undef DFD_MB_TILES
 #define DFD_MB_LATE_TILES(KK, SS, HH, CC, CI) \
     if (late && k == KK && stride == SS && H == HH && C == CC && Cin == CI && best < 1) best = 1;
-    DFD_MB_LATE_TABLE(DFD_MB_LATE_TILES, DFD_MB_LATE_TILES)
+#define DFD_MB_K5O_TILES(KK, SS, HH, CC, CI) /* no mbconv_late_kernel instance: only where the plan asks for the k5 kernel */ \
+    if (late && k5 && k == KK && stride == SS && H == HH && C == CC && Cin == CI && best < 1) best = 1;
+    DFD_MB_LATE_TABLE(DFD_MB_LATE_TILES, DFD_MB_LATE_TILES, DFD_MB_LATE_TILES, DFD_MB_K5O_TILES)
+#undef DFD_MB_K5O_TILES
 #undef DFD_MB_LATE_TILES
     return best;
 }

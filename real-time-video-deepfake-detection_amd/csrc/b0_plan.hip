@@ -87,7 +87,7 @@ int b0_build_plan(dfd_handle* h) {
             b.proj_b = need(h, q + ".proj.b", {co}, &ok);
             b.dw_tiles = depthwise_tiles(b.h_in, b.c_exp, b.kernel, b.stride);
             if (b.dw_tiles < 0) return fail(h, DFD_ERR_STATE, "no depthwise kernel for block %d", idx);
-            b.dw_tiles = std::max(b.dw_tiles, mbconv_tiles(b.h_in, b.c_exp, b.kernel, b.stride, b.c_in, true));
+            b.dw_tiles = std::max(b.dw_tiles, mbconv_tiles(b.h_in, b.c_exp, b.kernel, b.stride, b.c_in, true, true));
             auto mx = [](size_t& a, size_t v) { if (v > a) a = v; };
             mx(P.io_floats, (size_t)b.h_out * b.h_out * b.c_out);
             if (b.expand != 1) mx(P.exp_floats, (size_t)b.h_in * b.h_in * b.c_exp);
@@ -272,6 +272,9 @@ static int b0_forward_t(dfd_handle* h, const float* x, int n, float* logits_dev,
         // section 5) and replaces whatever form the block would run otherwise WITH THAT FORM'S BITS - mode 2 (the separate
         // launches' bias order) for a block the unset mask covers, mode 1 (mbconv_late_kernel's) for an unmasked one; a block
         // masked explicitly keeps its separate launches.  So neither the option nor the batch size changes a result.
+        // Blocks 6 and 7 (k3) and block 11 (k5, 14 -> 7) run on instances of the same kernel (round 7).  Block 11 has no
+        // mbconv_late_kernel form (k5_only): it always takes mode 2, the bits of the launches it runs otherwise, and bit 11
+        // of an explicit mask keeps those launches.
         constexpr int K5_MIN_DEFAULT = 208;
         const int k5_rounds = (n + h->cu_count - 1) / h->cu_count, k5_last = n - (k5_rounds - 1) * h->cu_count;
         const bool k5on = sizeof(XT) == 4 && h->fuse_k5 && h->fuse_late && h->fuse_expand && b.expand != 1 &&
@@ -280,9 +283,10 @@ static int b0_forward_t(dfd_handle* h, const float* x, int n, float* logits_dev,
         const bool mask_unset = h->fuse_late_skip < 0;
         const unsigned late_skip = mask_unset ? (1u << 8) | (1u << 9) : (unsigned)h->fuse_late_skip;
         const bool masked = (late_skip >> bi) & 1u;
-        const int k5 = !k5on ? 0 : (!masked ? 1 : (mask_unset ? 2 : 0));
+        const bool k5_only = k5on && mbconv_tiles(b.h_in, b.c_exp, b.kernel, b.stride, b.c_in, true) < 1;
+        const int k5 = !k5on || (masked && !mask_unset) ? 0 : (masked || k5_only ? 2 : 1);
         const bool late_here = h->fuse_late && (!masked || k5 == 2);
-        if (!fused && b.expand != 1 && h->fuse_expand && mbconv_tiles(b.h_in, b.c_exp, b.kernel, b.stride, b.c_in, late_here) > 0 &&
+        if (!fused && b.expand != 1 && h->fuse_expand && mbconv_tiles(b.h_in, b.c_exp, b.kernel, b.stride, b.c_in, late_here, k5 != 0) > 0 &&
             !(we3 = split_weights(h, b.exp_w, b.c_exp, b.c_in))) return DFD_ERR_HIP;
         if (we3 && launch_mbconv_front<XT>(cur, b.c_in, we3, (int)split_weights_count(b.c_exp, b.c_in), (b.c_in + 63) / 64 * 64,
                                            b.exp_w, b.exp_b, b.dw_w, b.dw_b, dwbuf, h->pool, n, b.h_in, b.c_exp,

@@ -146,8 +146,10 @@ struct dfd_handle {
                                          // lets mbconv_k5_kernel take blocks 8 and 9 (fuse_k5; b0_plan.hip)
     int fuse_k5_min = 0;                 // crops in the last round of blocks from which the k5 kernel runs (<= 0: measured default, b0_plan.hip)
     int cu_count = 256;                  // compute units of the device (dfd_create)
-    bool fuse_k5 = true;                 // fp32 blocks 8-10 (k5 at 14 x 14) of the fuse_late launches: one block per image
-                                         // (mbconv_k5_kernel, round 6) instead of one per image and 32 channels; same result bits
+    bool fuse_k5 = true;                 // fp32 blocks 6-11 (k3 / k5 on the 14 x 14 maps; block 11 at stride 2) of the fuse_late
+                                         // launches: one block per image (mbconv_k5_kernel, rounds 6 and 7) instead of one per image
+                                         // and 32 channels (block 11: instead of expand GEMM + depthwise kernel); same result bits.
+                                         // Bit 11 of an explicit fuse_late_skip keeps block 11's two launches
     bool split_gemm = true;              // 1x1 / k x k convs on the bf16x3-split MFMA path (gemm_split.hip)
     bool act_bf16 = false;               // classifier activations stored as bf16 (fp32 arithmetic): configs[3]
     int bf16_planes = 3;                 // weight planes the bf16-activation GEMMs use: 3 = fp32-exact weights, 1 = bf16 weights
