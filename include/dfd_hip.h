@@ -799,6 +799,42 @@ int dfd_train_augment_tap(dfd_handle* h, const unsigned char* rgb_host, int n, i
                           const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, const char* stage_name,
                           void* out, size_t capacity);
 
+/* ---- fine-tuning the head conv with the head ----------------------------------------------------
+ * The first layer of the reference's unfrozen backbone group (train.py:863-924): net._conv_head (320 -> 1280, 1 x 1, no
+ * bias), net._bn1 in train mode, swish and the 7 x 7 average pool, trained together with the MLP head as a second AdamW
+ * group at lr * lr_scale.  Its input is block 15's output, "trunk rows": float32 NHWC [n][7][7][320] (15680 floats a crop). */
+#define DFD_TRUNK_ROW 15680   /* 7 * 7 * 320 floats of one crop */
+
+/* the forward up to block 15's output -> trunk_host [n][7][7][320]; equals dfd_b0_tap(.., "b15.out") bit for bit (under
+ * "bf16_activations": the stored bf16 values, widened).  n as dfd_extract_features. */
+int dfd_extract_trunk(dfd_handle* h, const float* nchw_host, int n, float* trunk_host);
+/* dfd_train_augment_features with trunk rows in place of pooled rows -> trunk_out_host [n][7][7][320] */
+int dfd_train_augment_trunk(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
+                            const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, float* trunk_out_host);
+
+typedef struct dfd_headconv_params {   /* torch layouts: w [1280][320] (the 1 x 1 kernel), g / be = BatchNorm2d weight / bias, rm / rv = running stats */
+    float *w, *g, *be, *rm, *rv;
+} dfd_headconv_params;
+/* Adds the conv stage to an open trainer: legal once, after dfd_head_train_begin and before the first accumulate
+ * (anything else: DFD_ERR_ARG).  Allocates everything the stage needs for max_n crops.  The Python side passes lr_scale
+ * 0.1, bn_momentum 0.01 and bn_eps 1e-3 (efficientnet_pytorch's; the float 1e-3f stands for weights._fold's double 1e-3).
+ * From here on dfd_head_train_accumulate / _eval (pooled rows) are DFD_ERR_ARG and the _trunk entries take their place;
+ * dfd_head_train_apply takes ONE gradient norm over both groups and steps the head at lr, w / g / be at lr * lr_scale
+ * (product in double; same betas, eps, weight decay; EMA and zeroing cover both); dfd_head_train_commit also folds
+ * _bn1 into _conv_head (float64, rounded once) and overwrites head.w / head.b and the cached split of head.w in place;
+ * dfd_head_train_tap knows "cfeat" [n][1280] (pooled features), "dfeat" [n][1280] (their gradient) and "cz"
+ * [n][49][1280] (the BatchNorm output before swish).  The stage has no dropout of its own. */
+int dfd_head_train_unfreeze_conv(dfd_handle* h, const dfd_headconv_params* init, float lr_scale, float bn_momentum, float bn_eps);
+/* dfd_head_train_accumulate on n trunk rows (2 <= n <= max_n): BatchNorm2d batch statistics over the 49 n positions */
+int dfd_head_train_accumulate_trunk(dfd_handle* h, const float* trunk, int n, const float* labels_a, const float* labels_b,
+                                    float lam, float loss_scale, float* loss_out, float* logits_out);
+/* dfd_head_train_eval on n trunk rows (1 <= n <= max_n): running statistics; per row, so any chunking gives the same bits */
+int dfd_head_train_eval_trunk(dfd_handle* h, const float* trunk, int n, int use_ema, float* logits_out);
+/* w / g / be (live or EMA) and the live running statistics into the caller's arrays */
+int dfd_head_train_export_conv(dfd_handle* h, int use_ema, dfd_headconv_params* out);
+/* test tap, as dfd_head_train_grads: read (set = 0) or replace (set = 1) the gradients of w / g / be; rm / rv are not used */
+int dfd_head_train_conv_grads(dfd_handle* h, dfd_headconv_params* io, int set);
+
 #ifdef __cplusplus
 }
 #endif

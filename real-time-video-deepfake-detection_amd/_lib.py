@@ -172,6 +172,15 @@ SIGNATURES = {
     "dfd_head_train_tap": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]),
     "dfd_head_train_commit": (C.c_int, [C.c_void_p, C.c_int]),
     "dfd_head_train_end": (C.c_int, [C.c_void_p]),
+    "dfd_extract_trunk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "dfd_train_augment_trunk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "dfd_head_train_unfreeze_conv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float]),
+    "dfd_head_train_accumulate_trunk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                                  c_float_p, C.c_void_p]),
+    "dfd_head_train_eval_trunk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dfd_head_train_export_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "dfd_head_train_conv_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "dfd_train_augment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dfd_train_augment_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),
@@ -207,6 +216,32 @@ HEAD_SHAPES = {"w1": (512, 1280), "b1": (512,), "g1": (512,), "be1": (512,), "rm
 class HeadParams(C.Structure):
     """`dfd_head_params` (include/dfd_hip.h): host arrays of the unfolded head, torch layouts."""
     _fields_ = [(k, C.c_void_p) for k in HEAD_FIELDS]
+
+
+TRUNK_SHAPE = (7, 7, 320)     # block 15's output of one crop, NHWC (DFD_TRUNK_ROW floats)
+TRUNK_ROW = 7 * 7 * 320
+CONV_FIELDS = ("w", "g", "be", "rm", "rv")
+CONV_SHAPES = {"w": (1280, 320), "g": (1280,), "be": (1280,), "rm": (1280,), "rv": (1280,)}
+
+
+class HeadConvParams(C.Structure):
+    """`dfd_headconv_params` (include/dfd_hip.h): host arrays of net._conv_head / net._bn1, torch layouts."""
+    _fields_ = [(k, C.c_void_p) for k in CONV_FIELDS]
+
+
+def _conv_arrays(arrays=None, skip=()):
+    """(HeadConvParams, dict of the float32 arrays it points to); missing entries are allocated"""
+    out, cp = {}, HeadConvParams()
+    for k in CONV_FIELDS:
+        if k in skip:
+            continue
+        if arrays is not None and k in arrays:
+            a = np.ascontiguousarray(np.asarray(arrays[k], dtype=np.float32).reshape(CONV_SHAPES[k]))
+        else:
+            a = np.zeros(CONV_SHAPES[k], np.float32)
+        out[k] = a
+        setattr(cp, k, a.ctypes.data)
+    return cp, out
 
 
 class HeadConfig(C.Structure):
@@ -467,6 +502,13 @@ class Handle:
         self._check(self._lib.dfd_extract_features(self._p, _ptr(a), a.shape[0], _ptr(out)))
         return out
 
+    def extract_trunk(self, x) -> np.ndarray:
+        """block 15's output, (n,7,7,320) float32 NHWC: the rows the head trainer's conv stage trains on"""
+        a = self._as_nchw(x)
+        out = np.empty((a.shape[0],) + TRUNK_SHAPE, dtype=np.float32)
+        self._check(self._lib.dfd_extract_trunk(self._p, _ptr(a), a.shape[0], _ptr(out)))
+        return out
+
     # -- train-time augmentation (include/dfd_hip.h "train-time image augmentation"; train_augment.draw_batch makes the tables)
     @staticmethod
     def _aug_tables(n, rows, batch):
@@ -528,9 +570,7 @@ class Handle:
             raise ValueError("shape larger than the device buffer")
         self._check(self._lib.dfd_train_augment_gather(self._p, C.c_void_p(src.ptr), n_src, hh, ww, _ptr(i), i.size, C.c_void_p(dst.ptr)))
 
-    def train_augment_features(self, rgb, rows, batch, shape=None) -> np.ndarray:
-        """chain at 224 + backbone -> (n,1280) pooled features.  `rgb`: (n,H,W,3) uint8, or a DeviceBuffer holding such an
-        array with `shape` = (n,H,W) (a resident training set costs no upload)"""
+    def _train_augment_forward(self, fn, width, rgb, rows, batch, shape):
         if isinstance(rgb, DeviceBuffer):
             n, hh, ww = (int(v) for v in shape)
             if n * hh * ww * 3 > rgb.nbytes:
@@ -541,9 +581,18 @@ class Handle:
             a, r, b, _keep = self._aug_args(rgb, rows, batch)
             n, hh, ww = a.shape[:3]
             src, on_device = _ptr(a), 0
-        out = np.empty((n, 1280), np.float32)
-        self._check(self._lib.dfd_train_augment_features(self._p, src, on_device, n, hh, ww, _ptr(r), _ptr(b), _ptr(out)))
+        out = np.empty((n,) + width, np.float32)
+        self._check(fn(self._p, src, on_device, n, hh, ww, _ptr(r), _ptr(b), _ptr(out)))
         return out
+
+    def train_augment_features(self, rgb, rows, batch, shape=None) -> np.ndarray:
+        """chain at 224 + backbone -> (n,1280) pooled features.  `rgb`: (n,H,W,3) uint8, or a DeviceBuffer holding such an
+        array with `shape` = (n,H,W) (a resident training set costs no upload)"""
+        return self._train_augment_forward(self._lib.dfd_train_augment_features, (1280,), rgb, rows, batch, shape)
+
+    def train_augment_trunk(self, rgb, rows, batch, shape=None) -> np.ndarray:
+        """`train_augment_features` with block 15's output in place of the pooled rows -> (n,7,7,320)"""
+        return self._train_augment_forward(self._lib.dfd_train_augment_trunk, TRUNK_SHAPE, rgb, rows, batch, shape)
 
     # -- head training (include/dfd_hip.h "classifier head training"; head_training.HeadTrainer is the front end)
     @staticmethod
@@ -604,7 +653,7 @@ class Handle:
 
     def head_train_tap(self, name: str, n: int) -> np.ndarray:
         width = {"mask0": 1280, "mask1": 512, "mask2": 256, "z1": 512, "z2": 256}.get(name, 1280)   # unknown names: the library refuses
-        out = np.empty((int(n), width), np.float32)
+        out = np.empty((int(n), 49, 1280) if name == "cz" else (int(n), width), np.float32)
         self._check(self._lib.dfd_head_train_tap(self._p, name.encode(), _ptr(out), out.size))
         return out
 
@@ -613,6 +662,57 @@ class Handle:
 
     def head_train_end(self):
         self._check(self._lib.dfd_head_train_end(self._p))
+
+    # -- the conv stage of the head trainer (include/dfd_hip.h "fine-tuning the head conv with the head")
+    @staticmethod
+    def _as_trunk(x) -> np.ndarray:
+        a = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
+        if a.ndim < 2 or a.shape[1:] not in (TRUNK_SHAPE, (TRUNK_ROW,)):
+            raise ValueError(f"expected (n,7,7,320) or (n,{TRUNK_ROW}) trunk rows, got {a.shape}")
+        return a
+
+    def head_train_unfreeze_conv(self, params, lr_scale: float = 0.1, bn_momentum: float = 0.01, bn_eps: float = 1e-3):
+        """params: dict of the 5 `CONV_FIELDS` arrays (w (1280,320) or (1280,320,1,1))"""
+        missing = [k for k in CONV_FIELDS if k not in params]
+        if missing:
+            raise KeyError(f"conv parameters missing: {missing}")
+        cp, _keep = _conv_arrays(params)
+        self._check(self._lib.dfd_head_train_unfreeze_conv(self._p, C.byref(cp), float(lr_scale), float(bn_momentum), float(bn_eps)))
+
+    def head_train_accumulate_trunk(self, trunk, labels_a, labels_b=None, lam: float = 1.0, loss_scale: float = 1.0):
+        """-> (unscaled loss, logits (n,))"""
+        a = self._as_trunk(trunk)
+        n = a.shape[0]
+        ya = np.ascontiguousarray(np.asarray(labels_a, dtype=np.float32).reshape(-1))
+        yb = None if labels_b is None else np.ascontiguousarray(np.asarray(labels_b, dtype=np.float32).reshape(-1))
+        if ya.size != n or (yb is not None and yb.size != n):
+            raise ValueError("one label per trunk row")
+        loss = C.c_float()
+        logits = np.empty(max(n, 1), np.float32)
+        self._check(self._lib.dfd_head_train_accumulate_trunk(self._p, _ptr(a), n, _ptr(ya), None if yb is None else _ptr(yb),
+                                                              float(lam), float(loss_scale), C.byref(loss), _ptr(logits)))
+        return float(loss.value), logits[:n]
+
+    def head_train_eval_trunk(self, trunk, use_ema: bool = False) -> np.ndarray:
+        a = self._as_trunk(trunk)
+        out = np.empty(max(a.shape[0], 1), np.float32)
+        self._check(self._lib.dfd_head_train_eval_trunk(self._p, _ptr(a), a.shape[0], int(bool(use_ema)), _ptr(out)))
+        return out[: a.shape[0]]
+
+    def head_train_export_conv(self, use_ema: bool = False):
+        cp, out = _conv_arrays()
+        self._check(self._lib.dfd_head_train_export_conv(self._p, int(bool(use_ema)), C.byref(cp)))
+        return out
+
+    def head_train_conv_grads(self, set_to=None):
+        """the accumulated gradients of w / g / be; `set_to`: replace them first"""
+        skip = ("rm", "rv")
+        if set_to is not None:
+            cp, _keep = _conv_arrays(set_to, skip)
+            self._check(self._lib.dfd_head_train_conv_grads(self._p, C.byref(cp), 1))
+        cp, out = _conv_arrays(None, skip)
+        self._check(self._lib.dfd_head_train_conv_grads(self._p, C.byref(cp), 0))
+        return out
 
     def tap(self, x_dev: int, n: int, name: str, capacity: int) -> np.ndarray:
         out = np.empty(int(capacity), dtype=np.float32)

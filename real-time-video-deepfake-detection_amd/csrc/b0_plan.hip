@@ -350,6 +350,22 @@ static int b0_forward_t(dfd_handle* h, const float* x, int n, float* logits_dev,
 // block count (16), in io1 otherwise.
 float* b0_last_block_out(const dfd_handle* h) { return h->b0.blocks.size() % 2 == 0 ? h->io0 : h->io1; }
 
+// The forward on n crops with block 15's output copied out as fp32 [n][7][7][320] (dfd_extract_trunk,
+// dfd_train_augment_trunk): the "b15.out" tap of the forward that stops at the pooled features, so the rows are the
+// tap's bits (bf16 storage widened) by construction.  Waits on the stream.
+int b0_trunk_to_host(dfd_handle* h, const float* x, int n, float* out_host) {
+    const std::string name = "b" + std::to_string(h->b0.blocks.size() - 1) + ".out";
+    const B0Block& last = h->b0.blocks.back();
+    B0Tap tap;
+    tap.name = name.c_str();
+    tap.out = out_host;
+    tap.capacity = (size_t)n * last.h_out * last.h_out * last.c_out;
+    const int rc = b0_forward(h, x, n, nullptr, &tap, nullptr);
+    if (rc) return rc;
+    if (!tap.found) return fail(h, DFD_ERR_STATE, "the forward wrote no '%s'", name.c_str());
+    return DFD_OK;
+}
+
 // Grad-CAM's z (gradcam.hip): after b0_forward on n crops, the head conv of the last block's output once more with
 // ACT_NONE - BN(conv_head(x15)) with BN folded into head.w / head.b, the pre-swish values of the head GEMM - into
 // z_out [n][49][1280] in the handle's activation type.  One extra launch of the same GEMM (same tile-table entry: the

@@ -371,6 +371,15 @@ int dfd_extract_features(dfd_handle* h, const float* nchw_host, int n, float* fe
     return DFD_OK;
 }
 
+int dfd_extract_trunk(dfd_handle* h, const float* nchw_host, int n, float* trunk_host) {
+    if (!h) return DFD_ERR_ARG;
+    if (!nchw_host || !trunk_host) return fail(h, DFD_ERR_ARG, "extract_trunk: null pointer");
+    if (n <= 0 || n > h->max_batch) return fail(h, n <= 0 ? DFD_ERR_ARG : DFD_ERR_CAPACITY, "extract_trunk: batch %d outside 1..%d", n, h->max_batch);
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    DFD_HIP_TRY(h, hipMemcpyAsync(h->in_nchw, nchw_host, (size_t)n * 3 * 224 * 224 * 4, hipMemcpyHostToDevice, h->stream));
+    return b0_trunk_to_host(h, h->in_nchw, n, trunk_host);
+}
+
 int dfd_b0_tap(dfd_handle* h, const float* nchw_dev, int n, const char* name, float* out_host,
                size_t capacity, size_t* count) {
     if (!h) return DFD_ERR_ARG;

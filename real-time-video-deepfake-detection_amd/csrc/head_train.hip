@@ -29,19 +29,14 @@
 
 #include "b0_kernels.h"
 #include "dfd_common.h"
+#include "head_train_state.h"
 #include "kernel_util.h"
 
 using namespace dfd;
 
 namespace {
 
-constexpr int HT_IN = 1280, HT_H1 = 512, HT_H2 = 256, HT_MAX_N = 256, HT_THREADS = 256, HT_SLAB = 16;
-// flat parameter arena (floats): every offset a multiple of 4, so weight rows stay 16-byte aligned
-constexpr int O_W1 = 0, O_B1 = O_W1 + HT_H1 * HT_IN, O_G1 = O_B1 + HT_H1, O_BE1 = O_G1 + HT_H1;
-constexpr int O_W2 = O_BE1 + HT_H1, O_B2 = O_W2 + HT_H2 * HT_H1, O_G2 = O_B2 + HT_H2, O_BE2 = O_G2 + HT_H2;
-constexpr int O_W3 = O_BE2 + HT_H2, O_B3 = O_W3 + HT_H2, HT_COUNT = O_B3 + 1;
-static_assert(O_W2 % 4 == 0 && O_W3 % 4 == 0, "weight rows must stay 16-byte aligned");
-constexpr int NORM_BLOCKS = 256;
+// sizes and the layout of the parameter arena: head_train_state.h
 static_assert(HT_THREADS == HT_H2, "ht_loss_kernel: one thread per column of w3");
 
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -263,6 +258,49 @@ __global__ __launch_bounds__(HT_THREADS) void ht_loss_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------- backward
+// Y slab [n][16] = dYn [n][NOUT] . Wn [NOUT][N] columns col0 .. col0 + 16 into LDS, on the exact fp32 MFMA: the backward's
+// dY . W form (ht_layer_bwd_kernel, ht_dfeat_kernel).
+template <int NOUT, int N>
+__device__ __forceinline__ void slab_gemm_dyw(const float* __restrict__ dYn, const float* __restrict__ Wn, int n, int col0,
+                                              float (*ys)[HT_SLAB + 1]) {
+    const int t = threadIdx.x;
+    const int lane = t & 63, wv = t >> 6, r16 = lane & 15, q = lane >> 4;
+    const int ntiles = (n + 15) >> 4;
+    f4 acc[4][4];                                            // 4 independent chains per tile (k mod 4), as the forward
+    const float* arow[4];
+    bool ok[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[i][c] = (f4){0.f, 0.f, 0.f, 0.f};
+        const int row = (wv + 4 * i) * 16 + r16;
+        ok[i] = row < n;
+        arow[i] = dYn + (size_t)(ok[i] ? row : 0) * NOUT + 4 * q;
+    }
+    const float* wcol = Wn + (size_t)(4 * q) * N + col0 + r16;      // B[k][j] = Wn[k][col0 + j]
+    for (int k0 = 0; k0 < NOUT; k0 += 16) {
+        const float* wp = wcol + (size_t)k0 * N;
+        const float b0 = wp[0], b1 = wp[N], b2 = wp[2 * N], b3 = wp[3 * N];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (wv + 4 * i >= ntiles) continue;
+            f4 a = *reinterpret_cast<const f4*>(arow[i] + k0);
+            if (!ok[i]) a = (f4){0.f, 0.f, 0.f, 0.f};
+            acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b0, acc[i][0], 0, 0, 0);
+            acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b1, acc[i][1], 0, 0, 0);
+            acc[i][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b2, acc[i][2], 0, 0, 0);
+            acc[i][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b3, acc[i][3], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (wv + 4 * i >= ntiles) continue;
+        const f4 s = (acc[i][0] + acc[i][1]) + (acc[i][2] + acc[i][3]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ys[(wv + 4 * i) * 16 + q * 4 + e][r16] = s[e];
+    }
+}
+
 // One layer backward for a 16-column slab.  Upstream gradient of the layer's output a = dropout(relu(z)):
 //   LAST: da[r][c] = dlogit[r] w3[c]                       (Wn = w3, dYn = dlogit)
 //   else: da = dYn [n][NOUT] . Wn [NOUT][N]                 (MFMA, reduction over NOUT)
@@ -281,41 +319,7 @@ __global__ __launch_bounds__(HT_THREADS) void ht_layer_bwd_kernel(
     if constexpr (LAST) {
         for (int e = t; e < n * HT_SLAB; e += HT_THREADS) ys[e >> 4][e & 15] = dYn[e >> 4] * Wn[col0 + (e & 15)];
     } else {
-        const int lane = t & 63, wv = t >> 6, r16 = lane & 15, q = lane >> 4;
-        const int ntiles = (n + 15) >> 4;
-        f4 acc[4][4];                                            // 4 independent chains per tile (k mod 4), as the forward
-        const float* arow[4];
-        bool ok[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[i][c] = (f4){0.f, 0.f, 0.f, 0.f};
-            const int row = (wv + 4 * i) * 16 + r16;
-            ok[i] = row < n;
-            arow[i] = dYn + (size_t)(ok[i] ? row : 0) * NOUT + 4 * q;
-        }
-        const float* wcol = Wn + (size_t)(4 * q) * N + col0 + r16;      // B[k][j] = Wn[k][col0 + j]
-        for (int k0 = 0; k0 < NOUT; k0 += 16) {
-            const float* wp = wcol + (size_t)k0 * N;
-            const float b0 = wp[0], b1 = wp[N], b2 = wp[2 * N], b3 = wp[3 * N];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (wv + 4 * i >= ntiles) continue;
-                f4 a = *reinterpret_cast<const f4*>(arow[i] + k0);
-                if (!ok[i]) a = (f4){0.f, 0.f, 0.f, 0.f};
-                acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b0, acc[i][0], 0, 0, 0);
-                acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b1, acc[i][1], 0, 0, 0);
-                acc[i][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b2, acc[i][2], 0, 0, 0);
-                acc[i][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b3, acc[i][3], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (wv + 4 * i >= ntiles) continue;
-            const f4 s = (acc[i][0] + acc[i][1]) + (acc[i][2] + acc[i][3]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ys[(wv + 4 * i) * 16 + q * 4 + e][r16] = s[e];
-        }
+        slab_gemm_dyw<NOUT, N>(dYn, Wn, n, col0, ys);
     }
     __syncthreads();
     for (int e = t; e < n * HT_SLAB; e += HT_THREADS) {
@@ -335,6 +339,22 @@ __global__ __launch_bounds__(HT_THREADS) void ht_layer_bwd_kernel(
     if (t < HT_SLAB) {
         ggamma[col0 + t] += (float)sdx[t];
         gbeta[col0 + t] += (float)sdz[t];
+    }
+}
+
+// The gradient with respect to the pooled features, for the conv stage (head_train_conv.hip): dfeat [n][1280] =
+// (dY1 [n][512] . W1 [512][1280]) * mask0 * dscale0 - layer 0's dropout has no BatchNorm or ReLU behind it.  grid = 1280 / 16.
+__global__ __launch_bounds__(HT_THREADS) void ht_dfeat_kernel(const float* __restrict__ dY1, const float* __restrict__ W1,
+                                                              const uint8_t* __restrict__ M0, float dscale,
+                                                              float* __restrict__ dfeat, int n) {
+    __shared__ float ys[HT_MAX_N][HT_SLAB + 1];
+    const int t = threadIdx.x, col0 = blockIdx.x * HT_SLAB;
+    slab_gemm_dyw<HT_H1, HT_IN>(dY1, W1, n, col0, ys);
+    __syncthreads();
+    for (int e = t; e < n * HT_SLAB; e += HT_THREADS) {
+        const int r = e >> 4, c = e & 15;
+        const size_t o = (size_t)r * HT_IN + col0 + c;
+        dfeat[o] = M0[o] ? ys[r][c] * dscale : 0.f;
     }
 }
 
@@ -394,15 +414,19 @@ __global__ __launch_bounds__(HT_THREADS) void ht_sumsq_kernel(const float* __res
 
 // clip_grad_norm_ + torch.optim.AdamW (single-tensor path, in its order) + EMAModel.update + zero_grad, one element per thread.
 // decay_mul = 1 - lr wd, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t): computed on the host in double.
+// The squared norm is the sum of partial[] (and, entry by entry, partial2[] when given).
 __global__ __launch_bounds__(HT_THREADS) void ht_adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                               float* __restrict__ v, float* __restrict__ ema, int count,
-                                                              const double* __restrict__ partial, float clip_norm,
+                                                              const double* __restrict__ partial,
+                                                              const double* __restrict__ partial2, float clip_norm,
                                                               float decay_mul, float w1, float beta2, float w2, float step_size,
                                                               float bc2_sqrt, float eps, float ema_decay, float ema_w,
                                                               float* __restrict__ norm_out) {
     __shared__ double sh[HT_THREADS];
     static_assert(NORM_BLOCKS == HT_THREADS, "one partial per thread");
-    const float norm = (float)sqrt(block_sum(partial[threadIdx.x], sh));
+    double mine = partial[threadIdx.x];
+    if (partial2) mine += partial2[threadIdx.x];                // the conv stage's arena: one norm over both groups
+    const float norm = (float)sqrt(block_sum(mine, sh));
     const float coef = fminf(clip_norm / (norm + 1e-6f), 1.f);
     const int i = blockIdx.x * HT_THREADS + threadIdx.x;
     if (i == 0) norm_out[0] = norm;
@@ -425,29 +449,27 @@ __global__ __launch_bounds__(HT_THREADS) void ht_adamw_kernel(float* __restrict_
 // ---------------------------------------------------------------------------------------------- host
 namespace dfd {
 
-struct HeadTrainState {
-    dfd_head_config cfg{};
-    int max_n = 0, last_n = 0;
-    unsigned long long step = 0, counter = 0;
-    double p[3] = {0, 0, 0};                                    // dropout rate per layer
-    uint32_t thr[3] = {0, 0, 0};
-    float dscale[3] = {1, 1, 1};
-    float *param = nullptr, *grad = nullptr, *m = nullptr, *v = nullptr, *ema = nullptr;
-    float *rm1 = nullptr, *rv1 = nullptr, *rm2 = nullptr, *rv2 = nullptr;
-    float *feat = nullptr, *x0 = nullptr, *z1 = nullptr, *xh1 = nullptr, *a1 = nullptr, *dy1 = nullptr, *z2 = nullptr,
-          *xh2 = nullptr, *a2 = nullptr, *dy2 = nullptr, *istd1 = nullptr, *istd2 = nullptr, *logits = nullptr,
-          *dlogit = nullptr, *ya = nullptr, *yb = nullptr, *scalars = nullptr;   // scalars[0] = loss, [1] = grad norm
-    double* partial = nullptr;
-    uint8_t *mask0 = nullptr, *mask1 = nullptr, *mask2 = nullptr;
-    void* pool = nullptr;
-};
-
+// HeadTrainState: head_train_state.h
 void head_train_destroy(dfd_handle* h) {
     HeadTrainState* S = h->head_train;
     if (!S) return;
+    headconv_destroy(S);
     if (S->pool) hipFree(S->pool);
     delete S;
     h->head_train = nullptr;
+}
+
+void head_train_launch_sumsq(hipStream_t s, const float* g, int count, double* partial) {
+    hipLaunchKernelGGL(ht_sumsq_kernel, dim3(NORM_BLOCKS), dim3(HT_THREADS), 0, s, g, count, partial);
+}
+
+void head_train_launch_adamw(hipStream_t s, float* p, float* g, float* m, float* v, float* ema, int count, const double* partial,
+                             const double* partial2, const dfd_head_config& c, double lr, double t, float* norm_out) {
+    const double bc1 = 1.0 - std::pow((double)c.beta1, t), bc2 = 1.0 - std::pow((double)c.beta2, t);
+    hipLaunchKernelGGL(ht_adamw_kernel, dim3((count + HT_THREADS - 1) / HT_THREADS), dim3(HT_THREADS), 0, s, p, g, m, v, ema, count,
+                       partial, partial2, c.clip_norm, (float)(1.0 - lr * (double)c.weight_decay), (float)(1.0 - (double)c.beta1),
+                       c.beta2, (float)(1.0 - (double)c.beta2), (float)(lr / bc1), (float)std::sqrt(bc2), c.eps, c.ema_decay,
+                       (float)(1.0 - (double)c.ema_decay), norm_out);
 }
 
 }  // namespace dfd
@@ -504,6 +526,43 @@ int forward(dfd_handle* h, HeadTrainState* S, const float* P, int n, bool train)
 }
 
 }  // namespace
+
+namespace dfd {
+
+int head_train_step(dfd_handle* h, HeadTrainState* S, int n, const float* labels_a, const float* labels_b, float lam,
+                    float loss_scale, float* dfeat) {
+    hipStream_t s = h->stream;
+    int rc;
+    DFD_HIP_TRY(h, hipMemcpyAsync(S->ya, labels_a, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (labels_b) DFD_HIP_TRY(h, hipMemcpyAsync(S->yb, labels_b, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    const float* P = S->param;
+    float* G = S->grad;
+    if ((rc = forward(h, S, P, n, true))) return rc;
+    hipLaunchKernelGGL(ht_loss_kernel, dim3(1), dim3(HT_THREADS), 0, s, S->a2, P + O_W3, P + O_B3, S->ya, labels_b ? S->yb : nullptr, lam,
+                       loss_scale, S->cfg.focal_gamma, S->cfg.focal_alpha, S->cfg.label_smoothing, S->logits, S->dlogit, S->scalars,
+                       G + O_W3, G + O_B3, n, 1);
+    hipLaunchKernelGGL((ht_layer_bwd_kernel<1, HT_H2, true>), dim3(HT_H2 / HT_SLAB), dim3(HT_THREADS), 0, s, S->dlogit, P + O_W3, S->z2,
+                       S->xh2, S->istd2, P + O_G2, S->mask2, S->dscale[2], S->dy2, G + O_G2, G + O_BE2, n);
+    hipLaunchKernelGGL((ht_layer_bwd_kernel<HT_H2, HT_H1, false>), dim3(HT_H1 / HT_SLAB), dim3(HT_THREADS), 0, s, S->dy2, P + O_W2, S->z1,
+                       S->xh1, S->istd1, P + O_G1, S->mask1, S->dscale[1], S->dy1, G + O_G1, G + O_BE1, n);
+    if (dfeat)
+        hipLaunchKernelGGL(ht_dfeat_kernel, dim3(HT_IN / HT_SLAB), dim3(HT_THREADS), 0, s, S->dy1, P + O_W1, S->mask0, S->dscale[0], dfeat, n);
+    hipLaunchKernelGGL(ht_wgrad_kernel, dim3((HT_H1 + 255) / 256, HT_H2 / 16), dim3(HT_THREADS), 0, s, S->dy2, S->a1, G + O_W2, n, HT_H2, HT_H1);
+    hipLaunchKernelGGL(ht_wgrad_kernel, dim3((HT_IN + 255) / 256, HT_H1 / 16), dim3(HT_THREADS), 0, s, S->dy1, S->x0, G + O_W1, n, HT_H1, HT_IN);
+    DFD_HIP_TRY(h, hipGetLastError());
+    return DFD_OK;
+}
+
+int head_train_eval_step(dfd_handle* h, HeadTrainState* S, const float* P, int n) {
+    int rc;
+    if ((rc = forward(h, S, P, n, false))) return rc;
+    hipLaunchKernelGGL(ht_loss_kernel, dim3(1), dim3(HT_THREADS), 0, h->stream, S->a2, P + O_W3, P + O_B3, nullptr, nullptr, 1.f, 1.f, 0.f,
+                       0.f, 0.f, S->logits, nullptr, nullptr, nullptr, nullptr, n, 0);
+    DFD_HIP_TRY(h, hipGetLastError());
+    return DFD_OK;
+}
+
+}  // namespace dfd
 
 extern "C" {
 
@@ -594,27 +653,14 @@ int dfd_head_train_accumulate(dfd_handle* h, const float* feat, int n, const flo
     int rc;
     HeadTrainState* S = open_state(h, "head_train_accumulate", &rc);
     if (!S) return rc;
+    if (S->conv) return fail(h, DFD_ERR_ARG, "head_train_accumulate: the conv stage is unfrozen, rows are trunk rows (dfd_head_train_accumulate_trunk)");
     if (!feat || !labels_a || !loss_out) return fail(h, DFD_ERR_ARG, "head_train_accumulate: null pointer");
     if (n < 2) return fail(h, DFD_ERR_ARG, "head_train_accumulate: %d rows; batch statistics need at least 2", n);
     if (n > S->max_n) return fail(h, DFD_ERR_ARG, "head_train_accumulate: %d rows exceed the trainer's max_n %d", n, S->max_n);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     DFD_HIP_TRY(h, hipMemcpyAsync(S->feat, feat, (size_t)n * HT_IN * 4, hipMemcpyHostToDevice, s));
-    DFD_HIP_TRY(h, hipMemcpyAsync(S->ya, labels_a, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    if (labels_b) DFD_HIP_TRY(h, hipMemcpyAsync(S->yb, labels_b, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    const float* P = S->param;
-    float* G = S->grad;
-    if ((rc = forward(h, S, P, n, true))) return rc;
-    hipLaunchKernelGGL(ht_loss_kernel, dim3(1), dim3(HT_THREADS), 0, s, S->a2, P + O_W3, P + O_B3, S->ya, labels_b ? S->yb : nullptr, lam,
-                       loss_scale, S->cfg.focal_gamma, S->cfg.focal_alpha, S->cfg.label_smoothing, S->logits, S->dlogit, S->scalars,
-                       G + O_W3, G + O_B3, n, 1);
-    hipLaunchKernelGGL((ht_layer_bwd_kernel<1, HT_H2, true>), dim3(HT_H2 / HT_SLAB), dim3(HT_THREADS), 0, s, S->dlogit, P + O_W3, S->z2,
-                       S->xh2, S->istd2, P + O_G2, S->mask2, S->dscale[2], S->dy2, G + O_G2, G + O_BE2, n);
-    hipLaunchKernelGGL((ht_layer_bwd_kernel<HT_H2, HT_H1, false>), dim3(HT_H1 / HT_SLAB), dim3(HT_THREADS), 0, s, S->dy2, P + O_W2, S->z1,
-                       S->xh1, S->istd1, P + O_G1, S->mask1, S->dscale[1], S->dy1, G + O_G1, G + O_BE1, n);
-    hipLaunchKernelGGL(ht_wgrad_kernel, dim3((HT_H1 + 255) / 256, HT_H2 / 16), dim3(HT_THREADS), 0, s, S->dy2, S->a1, G + O_W2, n, HT_H2, HT_H1);
-    hipLaunchKernelGGL(ht_wgrad_kernel, dim3((HT_IN + 255) / 256, HT_H1 / 16), dim3(HT_THREADS), 0, s, S->dy1, S->x0, G + O_W1, n, HT_H1, HT_IN);
-    DFD_HIP_TRY(h, hipGetLastError());
+    if ((rc = head_train_step(h, S, n, labels_a, labels_b, lam, loss_scale, nullptr))) return rc;
     DFD_HIP_TRY(h, hipMemcpyAsync(loss_out, S->scalars, 4, hipMemcpyDeviceToHost, s));
     if (logits_out) DFD_HIP_TRY(h, hipMemcpyAsync(logits_out, S->logits, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     DFD_HIP_TRY(h, stream_sync(h));
@@ -629,14 +675,12 @@ int dfd_head_train_apply(dfd_handle* h, float lr, float* grad_norm_out) {
     if (!S) return rc;
     if (!(lr >= 0.f)) return fail(h, DFD_ERR_ARG, "head_train_apply: learning rate %g", (double)lr);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
-    const dfd_head_config& c = S->cfg;
     const double t = (double)(S->step + 1);
-    const double bc1 = 1.0 - std::pow((double)c.beta1, t), bc2 = 1.0 - std::pow((double)c.beta2, t);
-    hipLaunchKernelGGL(ht_sumsq_kernel, dim3(NORM_BLOCKS), dim3(HT_THREADS), 0, h->stream, S->grad, HT_COUNT, S->partial);
-    hipLaunchKernelGGL(ht_adamw_kernel, dim3((HT_COUNT + HT_THREADS - 1) / HT_THREADS), dim3(HT_THREADS), 0, h->stream, S->param, S->grad,
-                       S->m, S->v, S->ema, HT_COUNT, S->partial, c.clip_norm, (float)(1.0 - (double)lr * (double)c.weight_decay),
-                       (float)(1.0 - (double)c.beta1), c.beta2, (float)(1.0 - (double)c.beta2), (float)((double)lr / bc1),
-                       (float)std::sqrt(bc2), c.eps, c.ema_decay, (float)(1.0 - (double)c.ema_decay), S->scalars + 1);
+    head_train_launch_sumsq(h->stream, S->grad, HT_COUNT, S->partial);
+    const double* partial2 = S->conv ? headconv_sumsq(h, S) : nullptr;          // one norm over both groups
+    head_train_launch_adamw(h->stream, S->param, S->grad, S->m, S->v, S->ema, HT_COUNT, S->partial, partial2, S->cfg, (double)lr, t,
+                            S->scalars + 1);
+    if (S->conv) headconv_adamw(h, S, (double)lr, t);
     DFD_HIP_TRY(h, hipGetLastError());
     ++S->step;
     if (grad_norm_out) {
@@ -650,15 +694,13 @@ int dfd_head_train_eval(dfd_handle* h, const float* feat, int n, int use_ema, fl
     int rc;
     HeadTrainState* S = open_state(h, "head_train_eval", &rc);
     if (!S) return rc;
+    if (S->conv) return fail(h, DFD_ERR_ARG, "head_train_eval: the conv stage is unfrozen, rows are trunk rows (dfd_head_train_eval_trunk)");
     if (!feat || !logits_out) return fail(h, DFD_ERR_ARG, "head_train_eval: null pointer");
     if (n < 1 || n > S->max_n) return fail(h, DFD_ERR_ARG, "head_train_eval: %d rows outside 1..%d", n, S->max_n);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     const float* P = use_ema ? S->ema : S->param;
     DFD_HIP_TRY(h, hipMemcpyAsync(S->feat, feat, (size_t)n * HT_IN * 4, hipMemcpyHostToDevice, h->stream));
-    if ((rc = forward(h, S, P, n, false))) return rc;
-    hipLaunchKernelGGL(ht_loss_kernel, dim3(1), dim3(HT_THREADS), 0, h->stream, S->a2, P + O_W3, P + O_B3, nullptr, nullptr, 1.f, 1.f, 0.f,
-                       0.f, 0.f, S->logits, nullptr, nullptr, nullptr, nullptr, n, 0);
-    DFD_HIP_TRY(h, hipGetLastError());
+    if ((rc = head_train_eval_step(h, S, P, n))) return rc;
     DFD_HIP_TRY(h, hipMemcpyAsync(logits_out, S->logits, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     DFD_HIP_TRY(h, stream_sync(h));
     return DFD_OK;
@@ -701,6 +743,7 @@ int dfd_head_train_tap(dfd_handle* h, const char* name, float* out, size_t capac
     if (!S) return rc;
     if (!name || !out) return fail(h, DFD_ERR_ARG, "head_train_tap: null pointer");
     if (S->last_n == 0) return fail(h, DFD_ERR_ARG, "head_train_tap: no accumulate has run yet");
+    if (!strcmp(name, "cfeat") || !strcmp(name, "dfeat") || !strcmp(name, "cz")) return headconv_tap(h, S, name, out, capacity);
     const uint8_t* mask = nullptr;
     const float* act = nullptr;
     int width = 0;
@@ -729,6 +772,7 @@ int dfd_head_train_commit(dfd_handle* h, int use_ema) {
     HeadTrainState* S = open_state(h, "head_train_commit", &rc);
     if (!S) return rc;
     DFD_HIP_TRY(h, hipSetDevice(h->device));
+    if (S->conv && (rc = headconv_commit(h, S, use_ema))) return rc;           // _bn1 folded into _conv_head, head.w / head.b
     std::vector<float> P(HT_COUNT), rm1(HT_H1), rv1(HT_H1), rm2(HT_H2), rv2(HT_H2);
     DFD_HIP_TRY(h, hipMemcpyAsync(P.data(), use_ema ? S->ema : S->param, (size_t)HT_COUNT * 4, hipMemcpyDeviceToHost, h->stream));
     DFD_HIP_TRY(h, hipMemcpyAsync(rm1.data(), S->rm1, HT_H1 * 4, hipMemcpyDeviceToHost, h->stream));

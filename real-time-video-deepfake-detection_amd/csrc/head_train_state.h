@@ -1,0 +1,61 @@
+// What head_train.hip and head_train_conv.hip share: the trainer's state, the layout of the head's parameter arena and
+// the host entry points each file offers the other.  The conv stage (dfd_head_train_unfreeze_conv) hangs off the head
+// trainer's state; everything from the pooled features on runs in head_train.hip's kernels.
+#pragma once
+#include <cstdint>
+
+#include "dfd_common.h"
+
+namespace dfd {
+
+constexpr int HT_IN = 1280, HT_H1 = 512, HT_H2 = 256, HT_MAX_N = 256, HT_THREADS = 256, HT_SLAB = 16;
+// flat parameter arena (floats): every offset a multiple of 4, so weight rows stay 16-byte aligned
+constexpr int O_W1 = 0, O_B1 = O_W1 + HT_H1 * HT_IN, O_G1 = O_B1 + HT_H1, O_BE1 = O_G1 + HT_H1;
+constexpr int O_W2 = O_BE1 + HT_H1, O_B2 = O_W2 + HT_H2 * HT_H1, O_G2 = O_B2 + HT_H2, O_BE2 = O_G2 + HT_H2;
+constexpr int O_W3 = O_BE2 + HT_H2, O_B3 = O_W3 + HT_H2, HT_COUNT = O_B3 + 1;
+static_assert(O_W2 % 4 == 0 && O_W3 % 4 == 0, "weight rows must stay 16-byte aligned");
+constexpr int NORM_BLOCKS = 256;
+
+struct HeadConvState;   // head_train_conv.hip: _conv_head + _bn1 under training (null until dfd_head_train_unfreeze_conv)
+
+struct HeadTrainState {
+    dfd_head_config cfg{};
+    int max_n = 0, last_n = 0;
+    unsigned long long step = 0, counter = 0;
+    double p[3] = {0, 0, 0};                                    // dropout rate per layer
+    uint32_t thr[3] = {0, 0, 0};
+    float dscale[3] = {1, 1, 1};
+    float *param = nullptr, *grad = nullptr, *m = nullptr, *v = nullptr, *ema = nullptr;
+    float *rm1 = nullptr, *rv1 = nullptr, *rm2 = nullptr, *rv2 = nullptr;
+    float *feat = nullptr, *x0 = nullptr, *z1 = nullptr, *xh1 = nullptr, *a1 = nullptr, *dy1 = nullptr, *z2 = nullptr,
+          *xh2 = nullptr, *a2 = nullptr, *dy2 = nullptr, *istd1 = nullptr, *istd2 = nullptr, *logits = nullptr,
+          *dlogit = nullptr, *ya = nullptr, *yb = nullptr, *scalars = nullptr;   // scalars[0] = loss, [1] = grad norm
+    double* partial = nullptr;
+    uint8_t *mask0 = nullptr, *mask1 = nullptr, *mask2 = nullptr;
+    void* pool = nullptr;
+    HeadConvState* conv = nullptr;
+};
+
+// ---- head_train.hip, for the conv stage
+// One train-mode forward / loss / backward on the n rows already in S->feat (device): uploads the labels, leaves the
+// loss in S->scalars[0] and the logits in S->logits, adds the head's gradients.  dfeat (device, [n][1280]) or null:
+// the gradient with respect to S->feat.  Nothing is downloaded and the stream is not waited on.
+int head_train_step(dfd_handle* h, HeadTrainState* S, int n, const float* labels_a, const float* labels_b, float lam,
+                    float loss_scale, float* dfeat);
+// eval-mode forward of the n rows in S->feat with the parameters at P -> S->logits
+int head_train_eval_step(dfd_handle* h, HeadTrainState* S, const float* P, int n);
+void head_train_launch_sumsq(hipStream_t s, const float* g, int count, double* partial);
+// clip + AdamW + EMA + zeroing over one arena at the rate `lr`; partial2 (or null): a second arena's partial sums of
+// squares, added to `partial` entry by entry before the norm is taken.  t = 1-based step number.
+void head_train_launch_adamw(hipStream_t s, float* p, float* g, float* m, float* v, float* ema, int count,
+                             const double* partial, const double* partial2, const dfd_head_config& c, double lr, double t,
+                             float* norm_out);
+
+// ---- head_train_conv.hip, for the head trainer
+void headconv_destroy(HeadTrainState* S);
+const double* headconv_sumsq(dfd_handle* h, HeadTrainState* S);             // launches; -> the conv arena's partials
+void headconv_adamw(dfd_handle* h, HeadTrainState* S, double lr, double t);  // the conv group's step at lr * lr_scale
+int headconv_commit(dfd_handle* h, HeadTrainState* S, int use_ema);
+int headconv_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out, size_t capacity);   // "cfeat", "dfeat", "cz"
+
+}  // namespace dfd

@@ -736,12 +736,13 @@ int dfd_train_augment_tap(dfd_handle* h, const unsigned char* rgb_host, int n, i
     return aug_to_host(h, rgb_host, n, H, W, out_size, rows, batch, stage_name, out, capacity);
 }
 
-int dfd_train_augment_features(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
-                               const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, float* feat_out_host) {
+// the chain at 224 on all n images, then the backbone in chunks of max_batch: pooled rows, or (trunk) block 15's output
+static int augment_forward(dfd_handle* h, const char* who, const unsigned char* rgb, int on_device, int n, int H, int W,
+                           const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, float* out_host, bool trunk) {
     if (!h) return DFD_ERR_ARG;
     int rc = aug_check(h, rgb, n, H, W, DFD_CROP, rows, batch);
     if (rc) return rc;
-    if (!feat_out_host) return fail(h, DFD_ERR_ARG, "train_augment_features: null pointer");
+    if (!out_host) return fail(h, DFD_ERR_ARG, "%s: null pointer", who);
     bool tapped = false;
     AugOut o;
     // partners of Mixup / CutMix may sit in another chunk: the chain runs on all n images before the first forward
@@ -755,13 +756,27 @@ int dfd_train_augment_features(dfd_handle* h, const unsigned char* rgb, int on_d
             launch_mix(h, o, batch, first, m, DFD_CROP, h->in_nchw);
             in = h->in_nchw;
         }
+        if (trunk) {
+            if ((rc = b0_trunk_to_host(h, in, m, out_host + (size_t)first * DFD_TRUNK_ROW))) return rc;
+            continue;
+        }
         rc = b0_forward(h, in, m, nullptr, nullptr, nullptr);
         if (rc) return rc;
-        DFD_HIP_TRY(h, hipMemcpyAsync(feat_out_host + (size_t)first * DFD_FEATURES, h->feat, (size_t)m * DFD_FEATURES * 4,
+        DFD_HIP_TRY(h, hipMemcpyAsync(out_host + (size_t)first * DFD_FEATURES, h->feat, (size_t)m * DFD_FEATURES * 4,
                                       hipMemcpyDeviceToHost, h->stream));
     }
     DFD_HIP_TRY(h, stream_sync(h));
     return DFD_OK;
+}
+
+int dfd_train_augment_features(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
+                               const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, float* feat_out_host) {
+    return augment_forward(h, "train_augment_features", rgb, on_device, n, H, W, rows, batch, feat_out_host, false);
+}
+
+int dfd_train_augment_trunk(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
+                            const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, float* trunk_out_host) {
+    return augment_forward(h, "train_augment_trunk", rgb, on_device, n, H, W, rows, batch, trunk_out_host, true);
 }
 
 }  // extern "C"

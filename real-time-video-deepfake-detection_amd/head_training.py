@@ -5,8 +5,10 @@ applied to the 1280 -> 512 -> 256 -> 1 head (model.py:50-61) with the backbone f
 in libdfd_hip.so (csrc/head_train.hip, `dfd_head_train_*` in include/dfd_hip.h); this module holds what lives on the
 host: the learning-rate schedule, the specification of the dropout masks, the epoch loop and the state-dict names.
 
-Deviations from train.py: fp32 instead of AMP / GradScaler; the backbone is not fine-tuned; Mixup works on feature
-rows unless `augment=` is given (then the crops are augmented on the device every epoch and Mixup / CutMix act on the
+Deviations from train.py: fp32 instead of AMP / GradScaler; of the backbone only `_conv_head` + `_bn1` can be
+fine-tuned (`HeadTrainer(train_conv_head=True)`: csrc/head_train_conv.hip, the rows are then block 15's output, "trunk
+rows", and the conv is a second AdamW group at `backbone_lr_scale` x lr as train.py:891-924); Mixup works on feature
+rows (trunk rows with the conv stage) unless `augment=` is given (then the crops are augmented on the device every epoch and Mixup / CutMix act on the
 images, train_augment.py); a last batch of one row is dropped (BatchNorm1d needs two).
 """
 from __future__ import annotations
@@ -28,6 +30,12 @@ KEYS = {
     "net._fc.9.weight": "w3", "net._fc.9.bias": "b3",
 }
 TRACKED = ("net._fc.2.num_batches_tracked", "net._fc.6.num_batches_tracked")
+# reference state-dict key -> `dfd_headconv_params` field (the conv stage, train_conv_head=True)
+CONV_KEYS = {"net._conv_head.weight": "w", "net._bn1.weight": "g", "net._bn1.bias": "be", "net._bn1.running_mean": "rm",
+             "net._bn1.running_var": "rv"}
+CONV_TRACKED = "net._bn1.num_batches_tracked"
+BN_MOMENTUM_BACKBONE = 0.01              # efficientnet_pytorch: 1 - batch_norm_momentum (0.99)
+BN_EPS_BACKBONE = 1e-3                   # efficientnet_pytorch's batch_norm_epsilon, the eps weights.pack_b0 folds with
 LAYER_WIDTHS = (1280, 512, 256)          # what dropout layer 0 / 1 / 2 acts on
 LAYER_RATES = (1.0, 0.7, 0.5)            # model.py:51,55,59: dropout, dropout * 0.7, dropout * 0.5
 
@@ -138,7 +146,10 @@ def fit_loop(trainer, features, labels, epochs: int, batch_size: int = 32, grad_
              mix_alpha: float = 0.0, val=None, patience: int = 5, rng=None, augment=None,
              cutmix_alpha: float = 0.0) -> List[Dict[str, float]]:
     """train.py's `train_one_epoch` / `validate` loop over any object with `accumulate`, `apply`, `evaluate`,
-    `max_n` and `loss_settings` (HeadTrainer; the tests' float64 oracle).  Returns a log shaped like
+    `max_n` and `loss_settings` (HeadTrainer; the tests' float64 oracle).  A trainer may carry `row_width` (floats of one
+    row; default 1280) and `extract_method` (the extractor call `augment=` uses; default "train_augment_features"): a
+    trainer with the conv stage takes trunk rows of 15680 floats from "train_augment_trunk", and feature-space Mixup then
+    acts on trunk rows.  Returns a log shaped like
     weights/training_log.json: one dict per epoch (epoch, train_loss, train_acc, val_loss, val_acc, val_f1, val_auc,
     lr, time_seconds).
 
@@ -165,9 +176,11 @@ def fit_loop(trainer, features, labels, epochs: int, batch_size: int = 32, grad_
     runs: no draw is added (cutmix_alpha needs `augment`).  The crops are a host array or a
     `train_augment.ResidentCrops` (the set uploaded once; each shuffled batch is gathered device to device); both give the
     same bits.  Validation crops are extracted in chunks of 256 images."""
+    width = int(getattr(trainer, "row_width", 1280))
     if augment is not None:
         from . import train_augment as _ta
         extractor, policy = augment
+        extract_rows = getattr(extractor, getattr(trainer, "extract_method", "train_augment_features"))
         def crops_of(src, what):
             src = src if isinstance(src, _ta.ResidentCrops) else np.ascontiguousarray(np.asarray(src))
             if src.dtype != np.uint8 or src.ndim != 4 or src.shape[3] != 3:
@@ -177,19 +190,21 @@ def fit_loop(trainer, features, labels, epochs: int, batch_size: int = 32, grad_
         def extract(src, idx, rows, batch):
             if isinstance(src, _ta.ResidentCrops):                 # device gather, no upload
                 buf, shape = src.gather(idx)
-                return extractor.train_augment_features(buf, rows, batch, shape=shape)
-            return extractor.train_augment_features(src[idx], rows, batch)
+                return extract_rows(buf, rows, batch, shape=shape)
+            return extract_rows(src[idx], rows, batch)
 
         x = crops_of(features, "features")
     else:
         if cutmix_alpha > 0:
             raise ValueError("cutmix_alpha needs augment= (CutMix acts on images)")
         x = np.ascontiguousarray(np.asarray(features, np.float32))
-        if x.ndim != 2:
-            raise ValueError("features (N, 1280) and one label per row")
+        if width != 1280 and x.ndim > 2:
+            x = x.reshape(x.shape[0], -1)                          # (N, 7, 7, 320) trunk rows
+        if x.ndim != 2 or (width != 1280 and x.shape[1] != width):
+            raise ValueError(f"features (N, {width}) and one label per row")
     y = np.asarray(labels, np.float32).reshape(-1)
     if x.shape[0] != y.size:
-        raise ValueError("features (N, 1280) and one label per row")
+        raise ValueError(f"features (N, {width}) and one label per row")
     if batch_size < 2 or batch_size > trainer.max_n:
         raise ValueError(f"batch_size outside 2..{trainer.max_n}")
     rng = rng if rng is not None else np.random.RandomState(0)
@@ -251,6 +266,8 @@ def fit_loop(trainer, features, labels, epochs: int, batch_size: int = 32, grad_
                  "val_loss": None, "val_acc": None, "val_f1": None, "val_auc": None, "lr": cur_lr}
         if val is not None:
             vx, vy = np.asarray(val[0], np.float32), np.asarray(val[1], np.float32).reshape(-1)
+            if width != 1280:
+                vx = vx.reshape(vx.shape[0], -1)
             vz = trainer.evaluate(vx, use_ema=True)
             m = _metrics(vz.astype(np.float64), vy.astype(np.float64))
             vloss = focal_loss(vz, vy, gamma, alpha, ls)
@@ -274,9 +291,14 @@ class HeadTrainer:
     `model_or_handle`: a `DeepfakeEfficientNet` (its handle and state dict are used) or a `_lib.Handle` with
     `state_dict` (reference key names, at least the ten ``net._fc.*`` tensors and the four running statistics).
     `config`: fields of `dfd_head_config` - max_n, seed, dropout, beta1, beta2, eps, weight_decay, focal_gamma,
-    focal_alpha, label_smoothing, clip_norm, ema_decay, bn_momentum (defaults: train.py's)."""
+    focal_alpha, label_smoothing, clip_norm, ema_decay, bn_momentum (defaults: train.py's).
 
-    def __init__(self, model_or_handle, state_dict: Optional[Mapping[str, np.ndarray]] = None, **config):
+    `train_conv_head=True` also trains ``net._conv_head`` and ``net._bn1`` (`dfd_head_train_unfreeze_conv`; the state
+    dict must hold them): `accumulate` / `evaluate` then take trunk rows - `Handle.extract_trunk`'s (n, 7, 7, 320) or
+    (n, 15680) - the conv tensors step at `backbone_lr_scale` x lr, and `commit` / `export_state_dict` cover both."""
+
+    def __init__(self, model_or_handle, state_dict: Optional[Mapping[str, np.ndarray]] = None, train_conv_head: bool = False,
+                 backbone_lr_scale: float = 0.1, **config):
         if isinstance(model_or_handle, _lib.Handle):
             handle = model_or_handle
             if state_dict is None:
@@ -289,6 +311,13 @@ class HeadTrainer:
         params = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
                   for k, f in KEYS.items()}
         self._tracked = [int(np.asarray(sd[k])) if k in sd else 0 for k in TRACKED]
+        self.train_conv_head = bool(train_conv_head)
+        self.row_width = _lib.TRUNK_ROW if self.train_conv_head else 1280
+        self.extract_method = "train_augment_trunk" if self.train_conv_head else "train_augment_features"
+        if self.train_conv_head:
+            conv = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
+                    for k, f in CONV_KEYS.items()}
+            self._conv_tracked = int(np.asarray(sd[CONV_TRACKED])) if CONV_TRACKED in sd else 0
         self.config = _lib.head_config(**config)
         self.max_n = int(self.config.max_n)
         self.loss_settings = (float(self.config.focal_gamma), float(self.config.focal_alpha), float(self.config.label_smoothing))
@@ -296,6 +325,12 @@ class HeadTrainer:
         self._open = False
         handle.head_train_begin(params, self.config)
         self._open = True
+        if self.train_conv_head:
+            try:
+                handle.head_train_unfreeze_conv(conv, backbone_lr_scale, BN_MOMENTUM_BACKBONE, BN_EPS_BACKBONE)
+            except Exception:
+                self.close()
+                raise
         self.accumulates = 0
         self.steps = 0
 
@@ -313,7 +348,8 @@ class HeadTrainer:
 
     def accumulate(self, features, labels_a, labels_b=None, lam: float = 1.0, loss_scale: float = 1.0):
         """one train-mode forward / backward added to the gradients -> (unscaled loss, logits (n,))"""
-        out = self._h.head_train_accumulate(features, labels_a, labels_b, lam, loss_scale)
+        fn = self._h.head_train_accumulate_trunk if self.train_conv_head else self._h.head_train_accumulate
+        out = fn(features, labels_a, labels_b, lam, loss_scale)
         self.accumulates += 1
         return out
 
@@ -328,19 +364,26 @@ class HeadTrainer:
         a = np.ascontiguousarray(np.asarray(features, np.float32))
         if a.shape[0] == 0:
             return np.empty(0, np.float32)
-        return np.concatenate([self._h.head_train_eval(a[i:i + self.max_n], use_ema) for i in range(0, a.shape[0], self.max_n)])
+        fn = self._h.head_train_eval_trunk if self.train_conv_head else self._h.head_train_eval
+        return np.concatenate([fn(a[i:i + self.max_n], use_ema) for i in range(0, a.shape[0], self.max_n)])
 
     def export_state_dict(self, use_ema: bool = False) -> Dict[str, np.ndarray]:
         """the head under the reference's names: ten ``net._fc.*`` parameters, four running statistics (always the live
-        ones) and the two ``num_batches_tracked`` counters"""
+        ones) and the two ``num_batches_tracked`` counters; with the conv stage also ``net._conv_head.weight``
+        ((1280, 320, 1, 1)), ``net._bn1.*`` and its counter"""
         out = self._h.head_train_export(use_ema)
         sd = {k: out[f] for k, f in KEYS.items()}
         for k, t in zip(TRACKED, self._tracked):
             sd[k] = np.array(t + self.accumulates, dtype=np.int64)
+        if self.train_conv_head:
+            conv = self._h.head_train_export_conv(use_ema)
+            sd.update({k: (conv[f].reshape(1280, 320, 1, 1) if f == "w" else conv[f]) for k, f in CONV_KEYS.items()})
+            sd[CONV_TRACKED] = np.array(self._conv_tracked + self.accumulates, dtype=np.int64)
         return sd
 
     def commit(self, use_ema: bool = True):
-        """fold BatchNorm and swap the head the handle classifies with (`dfd_head_train_commit`)"""
+        """fold BatchNorm and swap the head (and, with the conv stage, the head conv) the handle classifies with
+        (`dfd_head_train_commit`)"""
         self._h.head_train_commit(use_ema)
 
     def fit(self, features, labels, epochs: int, batch_size: int = 32, grad_accum: int = 2, lr: float = 3e-4,
@@ -350,4 +393,4 @@ class HeadTrainer:
                         cutmix_alpha)
 
 
-__all__ = ["HeadTrainer", "fit_loop", "one_cycle_lr", "dropout_keep_mask", "dropout_rates", "focal_loss", "KEYS"]
+__all__ = ["HeadTrainer", "fit_loop", "one_cycle_lr", "dropout_keep_mask", "dropout_rates", "focal_loss", "KEYS", "CONV_KEYS"]

@@ -146,12 +146,16 @@ class DeepfakeEfficientNet:
         """(B,1280) pooled backbone features (reference model.py:74-89)."""
         return self._run(rgb_input, self.handle.extract_features)
 
+    def extract_trunk(self, rgb_input):
+        """(B,7,7,320) block 15's output, NHWC: the rows `fit_head(train_conv_head=True)` trains on."""
+        return self._run(rgb_input, self.handle.extract_trunk)
+
     def forward_with_projection(self, rgb_input, freq_input=None):
         """reference model.py:91-98"""
         return self.forward(rgb_input), None
 
     def fit_head(self, images_or_features, labels, *, epochs: int = 20, val=None, commit_ema: bool = True,
-                 trainer_config: Optional[Mapping] = None, augment=None, **fit_kw):
+                 trainer_config: Optional[Mapping] = None, augment=None, train_conv_head: bool = False, **fit_kw):
         """Train the 1280 -> 512 -> 256 -> 1 head on this engine's own pooled features and swap it in.
 
         `images_or_features`: (N,3,224,224) normalised RGB (features are extracted here, `max_batch` crops at a time) or
@@ -162,11 +166,19 @@ class DeepfakeEfficientNet:
 
         `augment`: a `train_augment.AugmentPolicy`, with `images_or_features` (and `val[0]`) (N,H,W,3) uint8 RGB crops: every
         batch of every epoch is augmented on the device and pushed through the backbone anew, on this model's own handle
-        (`fit_loop`'s `augment=`; `fit_kw` may then carry `cutmix_alpha`)."""
+        (`fit_loop`'s `augment=`; `fit_kw` may then carry `cutmix_alpha`).
+
+        `train_conv_head=True`: ``net._conv_head`` + ``net._bn1`` are fine-tuned with the head (`HeadTrainer`'s flag):
+        images go through `extract_trunk`, arrays that are not images are taken as trunk rows ((N,7,7,320) or (N,15680)),
+        and both the conv and the head are committed and returned by `state_dict()`."""
         from .head_training import HeadTrainer
 
         def feats(x):
             a = x.detach().cpu().numpy() if _is_torch(x) else np.asarray(x)
+            if train_conv_head:
+                if a.ndim == 4 and a.shape[1:] == (3, A.IMAGE_SIZE, A.IMAGE_SIZE):
+                    a = self.extract_trunk(a)
+                return np.ascontiguousarray(a, np.float32).reshape(a.shape[0], -1)
             return np.ascontiguousarray(a, np.float32) if a.ndim == 2 else np.asarray(self.extract_features(a), np.float32)
 
         cfg = dict(trainer_config or {})
@@ -183,7 +195,7 @@ class DeepfakeEfficientNet:
             x = feats(images_or_features)
             v = None if val is None else (feats(val[0]), np.asarray(val[1], np.float32))
         y = labels.detach().cpu().numpy() if _is_torch(labels) else np.asarray(labels)
-        with HeadTrainer(self, **cfg) as tr:
+        with HeadTrainer(self, train_conv_head=train_conv_head, **cfg) as tr:
             log_ = tr.fit(x, y, epochs, val=v, **fit_kw)
             tr.commit(use_ema=commit_ema)
             self._state.update(tr.export_state_dict(use_ema=commit_ema))
