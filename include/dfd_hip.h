@@ -835,6 +835,45 @@ int dfd_head_train_export_conv(dfd_handle* h, int use_ema, dfd_headconv_params* 
 /* test tap, as dfd_head_train_grads: read (set = 0) or replace (set = 1) the gradients of w / g / be; rm / rv are not used */
 int dfd_head_train_conv_grads(dfd_handle* h, dfd_headconv_params* io, int set);
 
+/* ---- fine-tuning block 15 with the head conv and the head ---------------------------------------
+ * The last block of the backbone, net._blocks.15 (MBConv k3, 192 -> 1152 -> 320, squeeze-excite 48, 7 x 7, no skip), in
+ * train mode in front of the conv stage: its three BatchNorm2d layers use batch statistics.  Its input is block 14's
+ * output: float32 NHWC [n][7][7][192] (9408 floats a crop). */
+#define DFD_BLOCK14_ROW 9408   /* 7 * 7 * 192 floats of one crop */
+
+/* dfd_extract_trunk / dfd_train_augment_trunk with the block whose output is returned: 15 gives the bits of those two,
+ * 14 gives [n][7][7][192], the "b14.out" tap of the same forward.  Any other block: DFD_ERR_ARG. */
+int dfd_extract_trunk_at(dfd_handle* h, const float* nchw_host, int n, int block, float* out_host);
+int dfd_train_augment_trunk_at(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
+                               const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, int block, float* out_host);
+
+typedef struct dfd_mbconv_params {   /* torch layouts: exp_w [1152][192], dw_w [1152][3][3], se_w1 [48][1152], se_b1 [48], se_w2 [1152][48],
+                                        se_b2 [1152], proj_w [320][1152]; g / be / rm / rv of _bn0, _bn1 (1152) and _bn2 (320) */
+    float *exp_w, *dw_w, *se_w1, *se_b1, *se_w2, *se_b2, *proj_w;
+    float *g0, *be0, *rm0, *rv0, *g1, *be1, *rm1, *rv1, *g2, *be2, *rm2, *rv2;
+} dfd_mbconv_params;
+/* Adds block `block` to an open trainer: legal once, after dfd_head_train_unfreeze_conv and before the first accumulate
+ * (anything else: DFD_ERR_ARG); `block` must be the last block, 15 (any other: DFD_ERR_UNSUPPORTED).  Allocates everything
+ * the stage needs for max_n crops in one piece.  The Python side passes bn_momentum 0.01 and bn_eps 1e-3.  The block's 717 232
+ * floats are a third arena that steps with the conv stage's lr_scale.  From here on the pooled and the _trunk entries are
+ * DFD_ERR_ARG and the _block entries take their place; dfd_head_train_apply takes ONE gradient norm over the three
+ * arenas (their partial sums added entry by entry: head, conv, block) and one clip coefficient, with the same betas, eps
+ * and weight decay on every tensor; EMA and zeroing cover all three; dfd_head_train_commit also folds the block's three
+ * BatchNorms (float64, rounded once) and overwrites the ten b15.* tensors and their cached splits in place;
+ * dfd_head_train_tap knows "b15.out" [n][49][320] (BN2's output), "b15.gate" [n][1152], "b15.ad" [n][49][1152] (the
+ * depthwise activation), "b15.dout" [n][49][320] (the gradient of b15.out) and "b15.dae" [n][49][1152] (the gradient of
+ * the expand activation).  Block 14 stays frozen: no gradient leaves the stage. */
+int dfd_head_train_unfreeze_block(dfd_handle* h, int block, const dfd_mbconv_params* init, float bn_momentum, float bn_eps);
+/* dfd_head_train_accumulate on n rows of block 14's output (2 <= n <= max_n) */
+int dfd_head_train_accumulate_block(dfd_handle* h, const float* rows, int n, const float* labels_a, const float* labels_b,
+                                    float lam, float loss_scale, float* loss_out, float* logits_out);
+/* dfd_head_train_eval on n such rows (1 <= n <= max_n): running statistics; per row, so any chunking gives the same bits */
+int dfd_head_train_eval_block(dfd_handle* h, const float* rows, int n, int use_ema, float* logits_out);
+/* the trainable tensors (live or EMA) and the live running statistics into the caller's arrays */
+int dfd_head_train_export_block(dfd_handle* h, int use_ema, dfd_mbconv_params* out);
+/* test tap: read (set = 0) or replace (set = 1) the gradients of the trainable tensors; rm / rv are not used */
+int dfd_head_train_block_grads(dfd_handle* h, dfd_mbconv_params* io, int set);
+
 #ifdef __cplusplus
 }
 #endif

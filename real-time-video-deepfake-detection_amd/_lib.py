@@ -181,6 +181,15 @@ SIGNATURES = {
     "dfd_head_train_eval_trunk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dfd_head_train_export_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "dfd_head_train_conv_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "dfd_extract_trunk_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dfd_train_augment_trunk_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_int, C.c_void_p]),
+    "dfd_head_train_unfreeze_block": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float]),
+    "dfd_head_train_accumulate_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                                  c_float_p, C.c_void_p]),
+    "dfd_head_train_eval_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dfd_head_train_export_block": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "dfd_head_train_block_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "dfd_train_augment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dfd_train_augment_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),
@@ -242,6 +251,37 @@ def _conv_arrays(arrays=None, skip=()):
         out[k] = a
         setattr(cp, k, a.ctypes.data)
     return cp, out
+
+
+BLOCK14_SHAPE = (7, 7, 192)   # block 14's output of one crop, NHWC (DFD_BLOCK14_ROW floats): the rows block 15's stage trains on
+BLOCK14_ROW = 7 * 7 * 192
+TRUNK_SHAPES = {14: BLOCK14_SHAPE, 15: TRUNK_SHAPE}
+BLOCK_FIELDS = ("exp_w", "dw_w", "se_w1", "se_b1", "se_w2", "se_b2", "proj_w",
+                "g0", "be0", "rm0", "rv0", "g1", "be1", "rm1", "rv1", "g2", "be2", "rm2", "rv2")
+BLOCK_STAT_FIELDS = ("rm0", "rv0", "rm1", "rv1", "rm2", "rv2")
+BLOCK_SHAPES = {"exp_w": (1152, 192), "dw_w": (1152, 3, 3), "se_w1": (48, 1152), "se_b1": (48,), "se_w2": (1152, 48),
+                "se_b2": (1152,), "proj_w": (320, 1152)}
+BLOCK_SHAPES.update({k + str(l): ((1152,) if l < 2 else (320,)) for l in range(3) for k in ("g", "be", "rm", "rv")})
+
+
+class MBConvParams(C.Structure):
+    """`dfd_mbconv_params` (include/dfd_hip.h): host arrays of net._blocks.15, torch layouts."""
+    _fields_ = [(k, C.c_void_p) for k in BLOCK_FIELDS]
+
+
+def _block_arrays(arrays=None, skip=()):
+    """(MBConvParams, dict of the float32 arrays it points to); missing entries are allocated"""
+    out, bp = {}, MBConvParams()
+    for k in BLOCK_FIELDS:
+        if k in skip:
+            continue
+        if arrays is not None and k in arrays:
+            a = np.ascontiguousarray(np.asarray(arrays[k], dtype=np.float32).reshape(BLOCK_SHAPES[k]))
+        else:
+            a = np.zeros(BLOCK_SHAPES[k], np.float32)
+        out[k] = a
+        setattr(bp, k, a.ctypes.data)
+    return bp, out
 
 
 class HeadConfig(C.Structure):
@@ -502,11 +542,16 @@ class Handle:
         self._check(self._lib.dfd_extract_features(self._p, _ptr(a), a.shape[0], _ptr(out)))
         return out
 
-    def extract_trunk(self, x) -> np.ndarray:
-        """block 15's output, (n,7,7,320) float32 NHWC: the rows the head trainer's conv stage trains on"""
+    def extract_trunk(self, x, block: int = 15) -> np.ndarray:
+        """block 15's output, (n,7,7,320) float32 NHWC: the rows the head trainer's conv stage trains on; `block=14`:
+        block 14's, (n,7,7,192), the rows block 15's stage trains on"""
         a = self._as_nchw(x)
-        out = np.empty((a.shape[0],) + TRUNK_SHAPE, dtype=np.float32)
-        self._check(self._lib.dfd_extract_trunk(self._p, _ptr(a), a.shape[0], _ptr(out)))
+        if block == 15:
+            out = np.empty((a.shape[0],) + TRUNK_SHAPE, dtype=np.float32)
+            self._check(self._lib.dfd_extract_trunk(self._p, _ptr(a), a.shape[0], _ptr(out)))
+            return out
+        out = np.empty((a.shape[0],) + TRUNK_SHAPES.get(int(block), TRUNK_SHAPE), dtype=np.float32)
+        self._check(self._lib.dfd_extract_trunk_at(self._p, _ptr(a), a.shape[0], int(block), _ptr(out)))
         return out
 
     # -- train-time augmentation (include/dfd_hip.h "train-time image augmentation"; train_augment.draw_batch makes the tables)
@@ -590,9 +635,20 @@ class Handle:
         array with `shape` = (n,H,W) (a resident training set costs no upload)"""
         return self._train_augment_forward(self._lib.dfd_train_augment_features, (1280,), rgb, rows, batch, shape)
 
-    def train_augment_trunk(self, rgb, rows, batch, shape=None) -> np.ndarray:
-        """`train_augment_features` with block 15's output in place of the pooled rows -> (n,7,7,320)"""
-        return self._train_augment_forward(self._lib.dfd_train_augment_trunk, TRUNK_SHAPE, rgb, rows, batch, shape)
+    def train_augment_trunk(self, rgb, rows, batch, shape=None, block: int = 15) -> np.ndarray:
+        """`train_augment_features` with block 15's output in place of the pooled rows -> (n,7,7,320); `block=14`:
+        block 14's -> (n,7,7,192)"""
+        if block == 15:
+            return self._train_augment_forward(self._lib.dfd_train_augment_trunk, TRUNK_SHAPE, rgb, rows, batch, shape)
+
+        def fn(p, src, on_device, n, hh, ww, r, b, out):
+            return self._lib.dfd_train_augment_trunk_at(p, src, on_device, n, hh, ww, r, b, int(block), out)
+
+        return self._train_augment_forward(fn, TRUNK_SHAPES.get(int(block), TRUNK_SHAPE), rgb, rows, batch, shape)
+
+    def train_augment_block14(self, rgb, rows, batch, shape=None) -> np.ndarray:
+        """`train_augment_trunk(block=14)`: the extractor of a trainer with block 15 unfrozen"""
+        return self.train_augment_trunk(rgb, rows, batch, shape, block=14)
 
     # -- head training (include/dfd_hip.h "classifier head training"; head_training.HeadTrainer is the front end)
     @staticmethod
@@ -653,7 +709,9 @@ class Handle:
 
     def head_train_tap(self, name: str, n: int) -> np.ndarray:
         width = {"mask0": 1280, "mask1": 512, "mask2": 256, "z1": 512, "z2": 256}.get(name, 1280)   # unknown names: the library refuses
-        out = np.empty((int(n), 49, 1280) if name == "cz" else (int(n), width), np.float32)
+        wide = {"cz": (49, 1280), "b15.out": (49, 320), "b15.dout": (49, 320), "b15.ad": (49, 1152), "b15.dae": (49, 1152),
+                "b15.gate": (1152,)}
+        out = np.empty((int(n),) + wide.get(name, (width,)), np.float32)
         self._check(self._lib.dfd_head_train_tap(self._p, name.encode(), _ptr(out), out.size))
         return out
 
@@ -712,6 +770,56 @@ class Handle:
             self._check(self._lib.dfd_head_train_conv_grads(self._p, C.byref(cp), 1))
         cp, out = _conv_arrays(None, skip)
         self._check(self._lib.dfd_head_train_conv_grads(self._p, C.byref(cp), 0))
+        return out
+
+    # -- block 15 of the head trainer (include/dfd_hip.h "fine-tuning block 15 with the head conv and the head")
+    @staticmethod
+    def _as_block14(x) -> np.ndarray:
+        a = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
+        if a.ndim < 2 or a.shape[1:] not in (BLOCK14_SHAPE, (BLOCK14_ROW,)):
+            raise ValueError(f"expected (n,7,7,192) or (n,{BLOCK14_ROW}) rows of block 14's output, got {a.shape}")
+        return a
+
+    def head_train_unfreeze_block(self, params, block: int = 15, bn_momentum: float = 0.01, bn_eps: float = 1e-3):
+        """params: dict of the 19 `BLOCK_FIELDS` arrays (torch layouts; conv kernels with or without their 1 x 1 axes)"""
+        missing = [k for k in BLOCK_FIELDS if k not in params]
+        if missing:
+            raise KeyError(f"block parameters missing: {missing}")
+        bp, _keep = _block_arrays(params)
+        self._check(self._lib.dfd_head_train_unfreeze_block(self._p, int(block), C.byref(bp), float(bn_momentum), float(bn_eps)))
+
+    def head_train_accumulate_block(self, rows, labels_a, labels_b=None, lam: float = 1.0, loss_scale: float = 1.0):
+        """-> (unscaled loss, logits (n,))"""
+        a = self._as_block14(rows)
+        n = a.shape[0]
+        ya = np.ascontiguousarray(np.asarray(labels_a, dtype=np.float32).reshape(-1))
+        yb = None if labels_b is None else np.ascontiguousarray(np.asarray(labels_b, dtype=np.float32).reshape(-1))
+        if ya.size != n or (yb is not None and yb.size != n):
+            raise ValueError("one label per row")
+        loss = C.c_float()
+        logits = np.empty(max(n, 1), np.float32)
+        self._check(self._lib.dfd_head_train_accumulate_block(self._p, _ptr(a), n, _ptr(ya), None if yb is None else _ptr(yb),
+                                                              float(lam), float(loss_scale), C.byref(loss), _ptr(logits)))
+        return float(loss.value), logits[:n]
+
+    def head_train_eval_block(self, rows, use_ema: bool = False) -> np.ndarray:
+        a = self._as_block14(rows)
+        out = np.empty(max(a.shape[0], 1), np.float32)
+        self._check(self._lib.dfd_head_train_eval_block(self._p, _ptr(a), a.shape[0], int(bool(use_ema)), _ptr(out)))
+        return out[: a.shape[0]]
+
+    def head_train_export_block(self, use_ema: bool = False):
+        bp, out = _block_arrays()
+        self._check(self._lib.dfd_head_train_export_block(self._p, int(bool(use_ema)), C.byref(bp)))
+        return out
+
+    def head_train_block_grads(self, set_to=None):
+        """the accumulated gradients of the 13 trainable tensors; `set_to`: replace them first"""
+        if set_to is not None:
+            bp, _keep = _block_arrays(set_to, BLOCK_STAT_FIELDS)
+            self._check(self._lib.dfd_head_train_block_grads(self._p, C.byref(bp), 1))
+        bp, out = _block_arrays(None, BLOCK_STAT_FIELDS)
+        self._check(self._lib.dfd_head_train_block_grads(self._p, C.byref(bp), 0))
         return out
 
     def tap(self, x_dev: int, n: int, name: str, capacity: int) -> np.ndarray:

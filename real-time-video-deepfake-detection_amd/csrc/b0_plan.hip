@@ -352,10 +352,13 @@ float* b0_last_block_out(const dfd_handle* h) { return h->b0.blocks.size() % 2 =
 
 // The forward on n crops with block 15's output copied out as fp32 [n][7][7][320] (dfd_extract_trunk,
 // dfd_train_augment_trunk): the "b15.out" tap of the forward that stops at the pooled features, so the rows are the
-// tap's bits (bf16 storage widened) by construction.  Waits on the stream.
-int b0_trunk_to_host(dfd_handle* h, const float* x, int n, float* out_host) {
-    const std::string name = "b" + std::to_string(h->b0.blocks.size() - 1) + ".out";
-    const B0Block& last = h->b0.blocks.back();
+// tap's bits (bf16 storage widened) by construction.  Waits on the stream.  `block` (dfd_extract_trunk_at): the "b<block>.out"
+// tap of the same forward instead, [n][h_out][h_out][c_out] of that block; -1 = the last block.
+int b0_trunk_to_host(dfd_handle* h, const float* x, int n, float* out_host, int block) {
+    if (block < 0) block = (int)h->b0.blocks.size() - 1;
+    if (block >= (int)h->b0.blocks.size()) return fail(h, DFD_ERR_ARG, "no block %d", block);
+    const std::string name = "b" + std::to_string(block) + ".out";
+    const B0Block& last = h->b0.blocks[block];
     B0Tap tap;
     tap.name = name.c_str();
     tap.out = out_host;

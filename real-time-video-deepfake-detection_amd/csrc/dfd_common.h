@@ -310,6 +310,6 @@ float* b0_last_block_out(const dfd_handle* h);
 // after b0_forward on n crops: the head conv WITHOUT its swish into z_out [n][49][1280] (activation type of the handle)
 int b0_head_preact(dfd_handle* h, int n, void* z_out);
 // b0_forward up to the pooled features with block 15's output copied to the host as fp32 [n][7][7][320]; waits on the stream
-int b0_trunk_to_host(dfd_handle* h, const float* x, int n, float* out_host);
+int b0_trunk_to_host(dfd_handle* h, const float* x, int n, float* out_host, int block = -1);   // block: -1 = the last one
 
 }  // namespace dfd

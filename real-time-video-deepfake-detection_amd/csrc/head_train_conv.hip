@@ -29,6 +29,7 @@
 
 #include "b0_kernels.h"
 #include "dfd_common.h"
+#include "head_train_gemm.h"
 #include "head_train_state.h"
 #include "kernel_util.h"
 
@@ -248,6 +249,21 @@ __global__ __launch_bounds__(HT_THREADS) void hc_wreduce_kernel(const double* __
     G[i] += (float)s;
 }
 
+// The stage's dZ as a gradient source of head_train_gemm.h's dY . W form (block 15's stage: dX15 = dZ . W): the element
+// functions above, so the input gradient sees the bits the weight gradient sees.
+struct ConvGrad {
+    typedef ht64::BnK K;
+    ht64::BnC bn;
+    const float *Z, *dfeat;
+    __device__ __forceinline__ K load(int c) const { return bn.load(c); }
+    __device__ __forceinline__ void dy_xh(const K& k, size_t row, int c, double* dy, double* xh) const {
+        const float y = hc_bn(Z[row * HC_N + c], k.mean, k.istd, k.gamma, k.beta, xh);
+        *dy = hc_dy(y, dfeat[(row / HC_HW) * HC_N + c]);
+    }
+};
+constexpr int HC_DX_J = 5;                // 80 columns of dX a workgroup: every dZ is formed four times
+static_assert(HC_K % (16 * HC_DX_J) == 0 && HC_N % 16 == 0, "tiles");
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------- host
@@ -280,8 +296,8 @@ const double* headconv_sumsq(dfd_handle* h, HeadTrainState* S) {
 void headconv_adamw(dfd_handle* h, HeadTrainState* S, double lr, double t) {
     HeadConvState* C = S->conv;
     // S->partial comes first in the norm's sum, as in the head's own launch: both launches see the same norm
-    head_train_launch_adamw(h->stream, C->param, C->grad, C->m, C->v, C->ema, CV_COUNT, S->partial, C->partial, S->cfg,
-                            lr * (double)C->lr_scale, t, S->scalars + 2);
+    head_train_launch_adamw(h->stream, C->param, C->grad, C->m, C->v, C->ema, CV_COUNT, S->partial, C->partial,
+                            S->block ? headblock_partial(S) : nullptr, S->cfg, lr * (double)C->lr_scale, t, S->scalars + 2);
 }
 
 int headconv_commit(dfd_handle* h, HeadTrainState* S, int use_ema) {
@@ -368,6 +384,48 @@ int conv_forward(dfd_handle* h, HeadTrainState* S, const float* P, int n, bool t
 
 }  // namespace
 
+namespace dfd {
+
+float* headconv_rows(HeadTrainState* S) { return S->conv->x; }
+float headconv_lr_scale(HeadTrainState* S) { return S->conv->lr_scale; }
+const double* headconv_partial(HeadTrainState* S) { return S->conv->partial; }
+
+int headconv_step(dfd_handle* h, HeadTrainState* S, int n, const float* labels_a, const float* labels_b, float lam, float loss_scale,
+                  float* dx) {
+    HeadConvState* C = S->conv;
+    hipStream_t s = h->stream;
+    const int m = n * HC_HW;
+    int rc;
+    const float* P = C->param;
+    if ((rc = conv_forward(h, S, P, n, true))) return rc;
+    if ((rc = head_train_step(h, S, n, labels_a, labels_b, lam, loss_scale, C->dfeat))) return rc;
+    const dim3 blk(HT_THREADS);
+    const int sch = stat_chunks(m), wch = wg_chunks(m);
+    hipLaunchKernelGGL(hc_colstat_kernel<2>, dim3(HC_N / 64, sch), blk, 0, s, C->z, C->mean, C->istd, P + CO_G, P + CO_BE, C->dfeat,
+                       C->spart, C->spart2, m);
+    hipLaunchKernelGGL(hc_finalize_kernel<2>, dim3((HC_N + HT_THREADS - 1) / HT_THREADS), blk, 0, s, C->spart, C->spart2, sch, m, C->sdy,
+                       C->sdx, C->grad + CO_G, C->grad + CO_BE, 0.f, 0.0);
+    hipLaunchKernelGGL(hc_wgrad_kernel, dim3(HC_N / 16 * (HC_K / HC_WG_COLS) / 4, wch), blk, 0, s, C->z, C->x, C->dfeat, C->mean, C->istd,
+                       P + CO_G, P + CO_BE, C->sdy, C->sdx, C->wpart, m);
+    hipLaunchKernelGGL(hc_wreduce_kernel, dim3((HC_N * HC_K + HT_THREADS - 1) / HT_THREADS), blk, 0, s, C->wpart, wch, C->grad + CO_W);
+    if (dx) {                                                  // dX = dZ . W [1280][320], for the stage below
+        const ConvGrad g{{C->mean, C->istd, C->sdy, C->sdx, P + CO_G, P + CO_BE, m}, C->z, C->dfeat};
+        hipLaunchKernelGGL((ht64::gemm_dyw_kernel<HC_DX_J, ConvGrad>), dim3(HC_K / (16 * HC_DX_J), (m + 15) / 16), blk, 0, s, g, P + CO_W,
+                           dx, m, HC_N, HC_K);
+    }
+    DFD_HIP_TRY(h, hipGetLastError());
+    return DFD_OK;
+}
+
+int headconv_eval_step(dfd_handle* h, HeadTrainState* S, int use_ema, int n) {
+    HeadConvState* C = S->conv;
+    int rc;
+    if ((rc = conv_forward(h, S, use_ema ? C->ema : C->param, n, false))) return rc;
+    return head_train_eval_step(h, S, use_ema ? S->ema : S->param, n);
+}
+
+}  // namespace dfd
+
 extern "C" {
 
 int dfd_head_train_unfreeze_conv(dfd_handle* h, const dfd_headconv_params* init, float lr_scale, float bn_momentum, float bn_eps) {
@@ -431,27 +489,15 @@ int dfd_head_train_accumulate_trunk(dfd_handle* h, const float* trunk, int n, co
     int rc;
     HeadTrainState* S = open_conv(h, "head_train_accumulate_trunk", true, &rc);
     if (!S) return rc;
+    if (S->block) return fail(h, DFD_ERR_ARG, "head_train_accumulate_trunk: block 15 is unfrozen, rows are block 14's output (dfd_head_train_accumulate_block)");
     if (!trunk || !labels_a || !loss_out) return fail(h, DFD_ERR_ARG, "head_train_accumulate_trunk: null pointer");
     if (n < 2) return fail(h, DFD_ERR_ARG, "head_train_accumulate_trunk: %d rows; batch statistics need at least 2", n);
     if (n > S->max_n) return fail(h, DFD_ERR_ARG, "head_train_accumulate_trunk: %d rows exceed the trainer's max_n %d", n, S->max_n);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     HeadConvState* C = S->conv;
     hipStream_t s = h->stream;
-    const int m = n * HC_HW;
     DFD_HIP_TRY(h, hipMemcpyAsync(C->x, trunk, (size_t)n * HC_ROW * 4, hipMemcpyHostToDevice, s));
-    const float* P = C->param;
-    if ((rc = conv_forward(h, S, P, n, true))) return rc;
-    if ((rc = head_train_step(h, S, n, labels_a, labels_b, lam, loss_scale, C->dfeat))) return rc;
-    const dim3 blk(HT_THREADS);
-    const int sch = stat_chunks(m), wch = wg_chunks(m);
-    hipLaunchKernelGGL(hc_colstat_kernel<2>, dim3(HC_N / 64, sch), blk, 0, s, C->z, C->mean, C->istd, P + CO_G, P + CO_BE, C->dfeat,
-                       C->spart, C->spart2, m);
-    hipLaunchKernelGGL(hc_finalize_kernel<2>, dim3((HC_N + HT_THREADS - 1) / HT_THREADS), blk, 0, s, C->spart, C->spart2, sch, m, C->sdy,
-                       C->sdx, C->grad + CO_G, C->grad + CO_BE, 0.f, 0.0);
-    hipLaunchKernelGGL(hc_wgrad_kernel, dim3(HC_N / 16 * (HC_K / HC_WG_COLS) / 4, wch), blk, 0, s, C->z, C->x, C->dfeat, C->mean, C->istd,
-                       P + CO_G, P + CO_BE, C->sdy, C->sdx, C->wpart, m);
-    hipLaunchKernelGGL(hc_wreduce_kernel, dim3((HC_N * HC_K + HT_THREADS - 1) / HT_THREADS), blk, 0, s, C->wpart, wch, C->grad + CO_W);
-    DFD_HIP_TRY(h, hipGetLastError());
+    if ((rc = headconv_step(h, S, n, labels_a, labels_b, lam, loss_scale, nullptr))) return rc;
     DFD_HIP_TRY(h, hipMemcpyAsync(loss_out, S->scalars, 4, hipMemcpyDeviceToHost, s));
     if (logits_out) DFD_HIP_TRY(h, hipMemcpyAsync(logits_out, S->logits, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     DFD_HIP_TRY(h, stream_sync(h));
@@ -464,13 +510,13 @@ int dfd_head_train_eval_trunk(dfd_handle* h, const float* trunk, int n, int use_
     int rc;
     HeadTrainState* S = open_conv(h, "head_train_eval_trunk", true, &rc);
     if (!S) return rc;
+    if (S->block) return fail(h, DFD_ERR_ARG, "head_train_eval_trunk: block 15 is unfrozen, rows are block 14's output (dfd_head_train_eval_block)");
     if (!trunk || !logits_out) return fail(h, DFD_ERR_ARG, "head_train_eval_trunk: null pointer");
     if (n < 1 || n > S->max_n) return fail(h, DFD_ERR_ARG, "head_train_eval_trunk: %d rows outside 1..%d", n, S->max_n);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     HeadConvState* C = S->conv;
     DFD_HIP_TRY(h, hipMemcpyAsync(C->x, trunk, (size_t)n * HC_ROW * 4, hipMemcpyHostToDevice, h->stream));
-    if ((rc = conv_forward(h, S, use_ema ? C->ema : C->param, n, false))) return rc;
-    if ((rc = head_train_eval_step(h, S, use_ema ? S->ema : S->param, n))) return rc;
+    if ((rc = headconv_eval_step(h, S, use_ema, n))) return rc;
     DFD_HIP_TRY(h, hipMemcpyAsync(logits_out, S->logits, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     DFD_HIP_TRY(h, stream_sync(h));
     return DFD_OK;

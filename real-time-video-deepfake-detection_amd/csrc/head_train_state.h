@@ -1,6 +1,7 @@
 // What head_train.hip and head_train_conv.hip share: the trainer's state, the layout of the head's parameter arena and
 // the host entry points each file offers the other.  The conv stage (dfd_head_train_unfreeze_conv) hangs off the head
-// trainer's state; everything from the pooled features on runs in head_train.hip's kernels.
+// trainer's state; everything from the pooled features on runs in head_train.hip's kernels.  Block 15
+// (dfd_head_train_unfreeze_block, head_train_block.hip) hangs off it in turn and feeds the conv stage on the device.
 #pragma once
 #include <cstdint>
 
@@ -17,6 +18,7 @@ static_assert(O_W2 % 4 == 0 && O_W3 % 4 == 0, "weight rows must stay 16-byte ali
 constexpr int NORM_BLOCKS = 256;
 
 struct HeadConvState;   // head_train_conv.hip: _conv_head + _bn1 under training (null until dfd_head_train_unfreeze_conv)
+struct HeadBlockState;  // head_train_block.hip: _blocks.15 under training (null until dfd_head_train_unfreeze_block)
 
 struct HeadTrainState {
     dfd_head_config cfg{};
@@ -34,6 +36,7 @@ struct HeadTrainState {
     uint8_t *mask0 = nullptr, *mask1 = nullptr, *mask2 = nullptr;
     void* pool = nullptr;
     HeadConvState* conv = nullptr;
+    HeadBlockState* block = nullptr;
 };
 
 // ---- head_train.hip, for the conv stage
@@ -45,11 +48,12 @@ int head_train_step(dfd_handle* h, HeadTrainState* S, int n, const float* labels
 // eval-mode forward of the n rows in S->feat with the parameters at P -> S->logits
 int head_train_eval_step(dfd_handle* h, HeadTrainState* S, const float* P, int n);
 void head_train_launch_sumsq(hipStream_t s, const float* g, int count, double* partial);
-// clip + AdamW + EMA + zeroing over one arena at the rate `lr`; partial2 (or null): a second arena's partial sums of
-// squares, added to `partial` entry by entry before the norm is taken.  t = 1-based step number.
+// clip + AdamW + EMA + zeroing over one arena at the rate `lr`; partial2 / partial3 (or null): a second and a third
+// arena's partial sums of squares, added to `partial` entry by entry, in this order, before the norm is taken.
+// t = 1-based step number.
 void head_train_launch_adamw(hipStream_t s, float* p, float* g, float* m, float* v, float* ema, int count,
-                             const double* partial, const double* partial2, const dfd_head_config& c, double lr, double t,
-                             float* norm_out);
+                             const double* partial, const double* partial2, const double* partial3, const dfd_head_config& c,
+                             double lr, double t, float* norm_out);
 
 // ---- head_train_conv.hip, for the head trainer
 void headconv_destroy(HeadTrainState* S);
@@ -57,5 +61,22 @@ const double* headconv_sumsq(dfd_handle* h, HeadTrainState* S);             // l
 void headconv_adamw(dfd_handle* h, HeadTrainState* S, double lr, double t);  // the conv group's step at lr * lr_scale
 int headconv_commit(dfd_handle* h, HeadTrainState* S, int use_ema);
 int headconv_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out, size_t capacity);   // "cfeat", "dfeat", "cz"
+// ---- head_train_conv.hip, for block 15's stage: the conv stage on rows that are already on the device
+float* headconv_rows(HeadTrainState* S);     // the stage's input, device [max_n][49][320]
+float headconv_lr_scale(HeadTrainState* S);
+const double* headconv_partial(HeadTrainState* S);   // the conv arena's partials of the last headconv_sumsq
+// dfd_head_train_accumulate_trunk's launches on the n rows in headconv_rows(): forward, head, loss, backward.  dx (device
+// [n][49][320]) or null: the gradient with respect to the rows, dZ . W.  Nothing is downloaded, the stream is not waited on.
+int headconv_step(dfd_handle* h, HeadTrainState* S, int n, const float* labels_a, const float* labels_b, float lam,
+                  float loss_scale, float* dx);
+int headconv_eval_step(dfd_handle* h, HeadTrainState* S, int use_ema, int n);    // -> S->logits
+
+// ---- head_train_block.hip, for the head trainer
+void headblock_destroy(HeadTrainState* S);
+const double* headblock_sumsq(dfd_handle* h, HeadTrainState* S);             // launches; -> the block arena's partials
+const double* headblock_partial(HeadTrainState* S);
+void headblock_adamw(dfd_handle* h, HeadTrainState* S, double lr, double t);  // the block group's step at lr * the conv stage's lr_scale
+int headblock_commit(dfd_handle* h, HeadTrainState* S, int use_ema);
+int headblock_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out, size_t capacity);  // "b15.*"
 
 }  // namespace dfd

@@ -9,7 +9,9 @@ Deviations from train.py: fp32 instead of AMP / GradScaler; of the backbone only
 fine-tuned (`HeadTrainer(train_conv_head=True)`: csrc/head_train_conv.hip, the rows are then block 15's output, "trunk
 rows", and the conv is a second AdamW group at `backbone_lr_scale` x lr as train.py:891-924); Mixup works on feature
 rows (trunk rows with the conv stage) unless `augment=` is given (then the crops are augmented on the device every epoch and Mixup / CutMix act on the
-images, train_augment.py); a last batch of one row is dropped (BatchNorm1d needs two).
+images, train_augment.py); a last batch of one row is dropped (BatchNorm1d needs two).  `HeadTrainer(train_block15=True)`
+adds the backbone's last block, ``net._blocks.15`` (csrc/head_train_block.hip): the rows are then block 14's output,
+(n, 7, 7, 192), and the block's tensors join the conv's group; blocks 14 down to 9 of train.py's recipe stay frozen.
 """
 from __future__ import annotations
 
@@ -34,6 +36,21 @@ TRACKED = ("net._fc.2.num_batches_tracked", "net._fc.6.num_batches_tracked")
 CONV_KEYS = {"net._conv_head.weight": "w", "net._bn1.weight": "g", "net._bn1.bias": "be", "net._bn1.running_mean": "rm",
              "net._bn1.running_var": "rv"}
 CONV_TRACKED = "net._bn1.num_batches_tracked"
+# reference state-dict key -> `dfd_mbconv_params` field (block 15, train_block15=True); "nbt<l>" are not fields of the
+# struct: BatchNorm's num_batches_tracked counters live on the host, as TRACKED and CONV_TRACKED do
+BLOCK_PREFIX = "net._blocks.15."
+BLOCK_KEYS = {BLOCK_PREFIX + "_expand_conv.weight": "exp_w", BLOCK_PREFIX + "_depthwise_conv.weight": "dw_w",
+              BLOCK_PREFIX + "_se_reduce.weight": "se_w1", BLOCK_PREFIX + "_se_reduce.bias": "se_b1",
+              BLOCK_PREFIX + "_se_expand.weight": "se_w2", BLOCK_PREFIX + "_se_expand.bias": "se_b2",
+              BLOCK_PREFIX + "_project_conv.weight": "proj_w"}
+for _l in range(3):
+    BLOCK_KEYS.update({f"{BLOCK_PREFIX}_bn{_l}.weight": f"g{_l}", f"{BLOCK_PREFIX}_bn{_l}.bias": f"be{_l}",
+                       f"{BLOCK_PREFIX}_bn{_l}.running_mean": f"rm{_l}", f"{BLOCK_PREFIX}_bn{_l}.running_var": f"rv{_l}",
+                       f"{BLOCK_PREFIX}_bn{_l}.num_batches_tracked": f"nbt{_l}"})
+BLOCK_TRACKED = tuple(k for k, f in BLOCK_KEYS.items() if f.startswith("nbt"))
+# the state dict's shapes of the conv kernels (the struct holds them without the 1 x 1 axes)
+BLOCK_SD_SHAPES = {"exp_w": (1152, 192, 1, 1), "dw_w": (1152, 1, 3, 3), "se_w1": (48, 1152, 1, 1), "se_w2": (1152, 48, 1, 1),
+                   "proj_w": (320, 1152, 1, 1)}
 BN_MOMENTUM_BACKBONE = 0.01              # efficientnet_pytorch: 1 - batch_norm_momentum (0.99)
 BN_EPS_BACKBONE = 1e-3                   # efficientnet_pytorch's batch_norm_epsilon, the eps weights.pack_b0 folds with
 LAYER_WIDTHS = (1280, 512, 256)          # what dropout layer 0 / 1 / 2 acts on
@@ -148,8 +165,8 @@ def fit_loop(trainer, features, labels, epochs: int, batch_size: int = 32, grad_
     """train.py's `train_one_epoch` / `validate` loop over any object with `accumulate`, `apply`, `evaluate`,
     `max_n` and `loss_settings` (HeadTrainer; the tests' float64 oracle).  A trainer may carry `row_width` (floats of one
     row; default 1280) and `extract_method` (the extractor call `augment=` uses; default "train_augment_features"): a
-    trainer with the conv stage takes trunk rows of 15680 floats from "train_augment_trunk", and feature-space Mixup then
-    acts on trunk rows.  Returns a log shaped like
+    trainer with the conv stage takes trunk rows of 15680 floats from "train_augment_trunk", one with block 15 rows of 9408
+    floats from "train_augment_block14", and feature-space Mixup then acts on those rows.  Returns a log shaped like
     weights/training_log.json: one dict per epoch (epoch, train_loss, train_acc, val_loss, val_acc, val_f1, val_auc,
     lr, time_seconds).
 
@@ -288,6 +305,11 @@ def fit_loop(trainer, features, labels, epochs: int, batch_size: int = 32, grad_
 class HeadTrainer:
     """A trainer opened on a handle (`dfd_head_train_begin` .. `_end`); use as a context manager or `close()` it.
 
+    `train_block15=True` (implies `train_conv_head`) also trains ``net._blocks.15`` (`dfd_head_train_unfreeze_block`):
+    `accumulate` / `evaluate` then take rows of block 14's output - `Handle.extract_trunk(x, block=14)`'s (n, 7, 7, 192) or
+    (n, 9408) - the block's tensors step at `backbone_lr_scale` x lr with the conv's, and `commit` / `export_state_dict`
+    cover all three groups.
+
     `model_or_handle`: a `DeepfakeEfficientNet` (its handle and state dict are used) or a `_lib.Handle` with
     `state_dict` (reference key names, at least the ten ``net._fc.*`` tensors and the four running statistics).
     `config`: fields of `dfd_head_config` - max_n, seed, dropout, beta1, beta2, eps, weight_decay, focal_gamma,
@@ -298,7 +320,7 @@ class HeadTrainer:
     (n, 15680) - the conv tensors step at `backbone_lr_scale` x lr, and `commit` / `export_state_dict` cover both."""
 
     def __init__(self, model_or_handle, state_dict: Optional[Mapping[str, np.ndarray]] = None, train_conv_head: bool = False,
-                 backbone_lr_scale: float = 0.1, **config):
+                 backbone_lr_scale: float = 0.1, train_block15: bool = False, **config):
         if isinstance(model_or_handle, _lib.Handle):
             handle = model_or_handle
             if state_dict is None:
@@ -311,9 +333,15 @@ class HeadTrainer:
         params = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
                   for k, f in KEYS.items()}
         self._tracked = [int(np.asarray(sd[k])) if k in sd else 0 for k in TRACKED]
-        self.train_conv_head = bool(train_conv_head)
-        self.row_width = _lib.TRUNK_ROW if self.train_conv_head else 1280
-        self.extract_method = "train_augment_trunk" if self.train_conv_head else "train_augment_features"
+        self.train_block15 = bool(train_block15)
+        self.train_conv_head = bool(train_conv_head) or self.train_block15
+        self.row_width = _lib.BLOCK14_ROW if self.train_block15 else _lib.TRUNK_ROW if self.train_conv_head else 1280
+        self.extract_method = ("train_augment_block14" if self.train_block15 else
+                               "train_augment_trunk" if self.train_conv_head else "train_augment_features")
+        if self.train_block15:
+            block = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
+                     for k, f in BLOCK_KEYS.items() if not f.startswith("nbt")}
+            self._block_tracked = [int(np.asarray(sd[k])) if k in sd else 0 for k in BLOCK_TRACKED]
         if self.train_conv_head:
             conv = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
                     for k, f in CONV_KEYS.items()}
@@ -328,6 +356,12 @@ class HeadTrainer:
         if self.train_conv_head:
             try:
                 handle.head_train_unfreeze_conv(conv, backbone_lr_scale, BN_MOMENTUM_BACKBONE, BN_EPS_BACKBONE)
+            except Exception:
+                self.close()
+                raise
+        if self.train_block15:
+            try:
+                handle.head_train_unfreeze_block(block, 15, BN_MOMENTUM_BACKBONE, BN_EPS_BACKBONE)
             except Exception:
                 self.close()
                 raise
@@ -348,7 +382,8 @@ class HeadTrainer:
 
     def accumulate(self, features, labels_a, labels_b=None, lam: float = 1.0, loss_scale: float = 1.0):
         """one train-mode forward / backward added to the gradients -> (unscaled loss, logits (n,))"""
-        fn = self._h.head_train_accumulate_trunk if self.train_conv_head else self._h.head_train_accumulate
+        fn = (self._h.head_train_accumulate_block if self.train_block15 else
+              self._h.head_train_accumulate_trunk if self.train_conv_head else self._h.head_train_accumulate)
         out = fn(features, labels_a, labels_b, lam, loss_scale)
         self.accumulates += 1
         return out
@@ -364,13 +399,15 @@ class HeadTrainer:
         a = np.ascontiguousarray(np.asarray(features, np.float32))
         if a.shape[0] == 0:
             return np.empty(0, np.float32)
-        fn = self._h.head_train_eval_trunk if self.train_conv_head else self._h.head_train_eval
+        fn = (self._h.head_train_eval_block if self.train_block15 else
+              self._h.head_train_eval_trunk if self.train_conv_head else self._h.head_train_eval)
         return np.concatenate([fn(a[i:i + self.max_n], use_ema) for i in range(0, a.shape[0], self.max_n)])
 
     def export_state_dict(self, use_ema: bool = False) -> Dict[str, np.ndarray]:
         """the head under the reference's names: ten ``net._fc.*`` parameters, four running statistics (always the live
         ones) and the two ``num_batches_tracked`` counters; with the conv stage also ``net._conv_head.weight``
-        ((1280, 320, 1, 1)), ``net._bn1.*`` and its counter"""
+        ((1280, 320, 1, 1)), ``net._bn1.*`` and its counter; with block 15 also the 22 ``net._blocks.15.*`` entries of
+        `BLOCK_KEYS` (conv kernels in the state dict's 4-d shapes)"""
         out = self._h.head_train_export(use_ema)
         sd = {k: out[f] for k, f in KEYS.items()}
         for k, t in zip(TRACKED, self._tracked):
@@ -379,11 +416,16 @@ class HeadTrainer:
             conv = self._h.head_train_export_conv(use_ema)
             sd.update({k: (conv[f].reshape(1280, 320, 1, 1) if f == "w" else conv[f]) for k, f in CONV_KEYS.items()})
             sd[CONV_TRACKED] = np.array(self._conv_tracked + self.accumulates, dtype=np.int64)
+        if self.train_block15:
+            blk = self._h.head_train_export_block(use_ema)
+            sd.update({k: blk[f].reshape(BLOCK_SD_SHAPES.get(f, blk[f].shape)) for k, f in BLOCK_KEYS.items() if f in blk})
+            for k, t in zip(BLOCK_TRACKED, self._block_tracked):
+                sd[k] = np.array(t + self.accumulates, dtype=np.int64)
         return sd
 
     def commit(self, use_ema: bool = True):
-        """fold BatchNorm and swap the head (and, with the conv stage, the head conv) the handle classifies with
-        (`dfd_head_train_commit`)"""
+        """fold BatchNorm and swap the head (and, with the conv stage, the head conv; with block 15, its ten tensors) the
+        handle classifies with (`dfd_head_train_commit`)"""
         self._h.head_train_commit(use_ema)
 
     def fit(self, features, labels, epochs: int, batch_size: int = 32, grad_accum: int = 2, lr: float = 3e-4,
@@ -393,4 +435,4 @@ class HeadTrainer:
                         cutmix_alpha)
 
 
-__all__ = ["HeadTrainer", "fit_loop", "one_cycle_lr", "dropout_keep_mask", "dropout_rates", "focal_loss", "KEYS", "CONV_KEYS"]
+__all__ = ["HeadTrainer", "fit_loop", "one_cycle_lr", "dropout_keep_mask", "dropout_rates", "focal_loss", "KEYS", "CONV_KEYS", "BLOCK_KEYS"]

@@ -146,16 +146,20 @@ class DeepfakeEfficientNet:
         """(B,1280) pooled backbone features (reference model.py:74-89)."""
         return self._run(rgb_input, self.handle.extract_features)
 
-    def extract_trunk(self, rgb_input):
-        """(B,7,7,320) block 15's output, NHWC: the rows `fit_head(train_conv_head=True)` trains on."""
-        return self._run(rgb_input, self.handle.extract_trunk)
+    def extract_trunk(self, rgb_input, block: int = 15):
+        """(B,7,7,320) block 15's output, NHWC: the rows `fit_head(train_conv_head=True)` trains on; `block=14`:
+        (B,7,7,192) block 14's output, the rows `fit_head(train_block15=True)` trains on."""
+        if block == 15:
+            return self._run(rgb_input, self.handle.extract_trunk)
+        return self._run(rgb_input, lambda a: self.handle.extract_trunk(a, block=block))
 
     def forward_with_projection(self, rgb_input, freq_input=None):
         """reference model.py:91-98"""
         return self.forward(rgb_input), None
 
     def fit_head(self, images_or_features, labels, *, epochs: int = 20, val=None, commit_ema: bool = True,
-                 trainer_config: Optional[Mapping] = None, augment=None, train_conv_head: bool = False, **fit_kw):
+                 trainer_config: Optional[Mapping] = None, augment=None, train_conv_head: bool = False,
+                 train_block15: bool = False, **fit_kw):
         """Train the 1280 -> 512 -> 256 -> 1 head on this engine's own pooled features and swap it in.
 
         `images_or_features`: (N,3,224,224) normalised RGB (features are extracted here, `max_batch` crops at a time) or
@@ -170,14 +174,18 @@ class DeepfakeEfficientNet:
 
         `train_conv_head=True`: ``net._conv_head`` + ``net._bn1`` are fine-tuned with the head (`HeadTrainer`'s flag):
         images go through `extract_trunk`, arrays that are not images are taken as trunk rows ((N,7,7,320) or (N,15680)),
-        and both the conv and the head are committed and returned by `state_dict()`."""
+        and both the conv and the head are committed and returned by `state_dict()`.
+
+        `train_block15=True` (implies `train_conv_head`): ``net._blocks.15`` is fine-tuned as well: images go through
+        `extract_trunk(block=14)`, other arrays are rows of block 14's output ((N,7,7,192) or (N,9408)), `augment=` extracts
+        them anew every batch, and block, conv and head are committed and returned by `state_dict()`."""
         from .head_training import HeadTrainer
 
         def feats(x):
             a = x.detach().cpu().numpy() if _is_torch(x) else np.asarray(x)
-            if train_conv_head:
+            if train_conv_head or train_block15:
                 if a.ndim == 4 and a.shape[1:] == (3, A.IMAGE_SIZE, A.IMAGE_SIZE):
-                    a = self.extract_trunk(a)
+                    a = self.extract_trunk(a, block=14 if train_block15 else 15)
                 return np.ascontiguousarray(a, np.float32).reshape(a.shape[0], -1)
             return np.ascontiguousarray(a, np.float32) if a.ndim == 2 else np.asarray(self.extract_features(a), np.float32)
 
@@ -195,7 +203,7 @@ class DeepfakeEfficientNet:
             x = feats(images_or_features)
             v = None if val is None else (feats(val[0]), np.asarray(val[1], np.float32))
         y = labels.detach().cpu().numpy() if _is_torch(labels) else np.asarray(labels)
-        with HeadTrainer(self, train_conv_head=train_conv_head, **cfg) as tr:
+        with HeadTrainer(self, train_conv_head=train_conv_head, train_block15=train_block15, **cfg) as tr:
             log_ = tr.fit(x, y, epochs, val=v, **fit_kw)
             tr.commit(use_ema=commit_ema)
             self._state.update(tr.export_state_dict(use_ema=commit_ema))

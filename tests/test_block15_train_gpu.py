@@ -1,0 +1,559 @@
+"""GPU: block 15's stage of the head trainer (csrc/head_train_block.hip: dfd_head_train_unfreeze_block, _accumulate_block,
+_eval_block, _export_block, _block_grads, the three-arena dfd_head_train_apply and _commit) and the extraction at a block
+(dfd_extract_trunk_at, dfd_train_augment_trunk_at) against the float64 oracle of tests/block15_train_oracle.py.
+
+Bars: as tests/test_head_train_gpu.py and tests/test_headconv_train_gpu.py - every compared tensor's rms(d) / rms(ref) and
+max|d| / max|ref| against the float64 oracle at most 4 x / 8 x the same metrics of the float32 CPU oracle, floored at
+2^-23 / 2^-21 (`O.bar_ratio` <= 1).  Every figure is printed before it is asserted.
+
+Inputs: "real" rows are `extract_trunk(block=14)` of b0_layer_oracle.stress_state_dict weights on random_crops (block,
+conv stage and head start from the same state dict); "synthetic" rows are standard normals.
+
+Preconditions, all on the oracles alone and asserted before the device is looked at: the head's ReLU gates are discrete,
+so the two oracles must agree on every gate with `gate_margin` >= 1; the head must be well conditioned on its float32
+input, `rounding_share` <= 1 (tests/headconv_train_oracle.py); and the fp32 storage of the stage's tensors alone must
+leave at least half of every bar, `storage_share` <= 0.5 (tests/block15_train_oracle.py).  The seeds were picked at
+authoring time on the CPU (real rows from a float32 CPU forward of the same weights and crops): of seeds 0..59 those
+that meet both share conditions in every variant of a size, and of these the largest gate margin (SEEDS below, with
+their margins and shares).  On the device's own rows, which differ from the CPU's in the last bits, the cases measured
+(gate margin, rounding share, storage share) 3953, 0.13, 0.06 (n = 2); 87, 0.40, 0.06 (5); 36, 0.37, 0.05 (11); 11, 0.23, 0.04 (37);
+13, 0.36, 0.05 (synthetic 64).
+
+m = 49 n rows: 98 (under one chunk, no multiple of 16), 245, 539 (one 512-row chunk and a remainder, two 256-row chunks
+and a remainder), 1813 (several chunks, ragged), 3136 (synthetic, a multiple of 64; 64 crops are this file's max_n).
+
+The gradient of _bn2's bias is the column sum of dX15, which is zero in exact arithmetic (the conv stage's BatchNorm
+removes a constant per input channel): reference, yardstick and device all hold rounding noise there, and the bar
+compares the device's noise with the yardstick's as it compares everything else.
+"""
+import numpy as np
+import pytest
+import torch
+
+import b0_layer_oracle as B
+import block15_train_oracle as BO
+import head_train_oracle as O
+import headconv_train_oracle as CO
+from rtdfd_amd import head_training as T
+from rtdfd_amd import train_augment as TA
+
+pytestmark = pytest.mark.gpu
+
+# seed per size -> gate margin, rounding share, storage share of the worst variant at authoring time (CPU rows):
+#   n = 2: 10 -> 6721, 0.62, 0.10 (6 of 60 seeds meet the shares; rounding shares run from 0.03 to 140, storage shares to 5.0)
+#   n = 5: 0 -> 82, 0.40, 0.05 (57 of 60)      n = 11: 3 -> 47, 0.34, 0.11 (60 of 60)      n = 37: 33 -> 12, 0.21, 0.04 (60 of 60)
+#   synthetic 64: 52 -> 8.8, 0.36, 0.05 (60 of 60)
+REAL_SEED = {2: 10, 5: 0, 11: 3, 37: 33}
+SYN64_SEED = 52
+ACC_SEED = 10       # two accumulates: of seeds 0..29 with both rounding shares <= 0.5 the largest smaller margin (5.9, 18); storage 0.10 / 0.11
+EVAL_SEED = 10      # eval case: of seeds 0..19 the largest smaller margin of the live and the EMA forward (22, 27)
+MAX_N = 64
+VARIANTS = {"plain": (False, 1.0), "mix": (True, 1.0), "scaled": (False, 0.5)}     # (two label vectors with lam, loss_scale)
+CASES = [("real", n, v) for n in (2, 5, 11, 37) for v in VARIANTS] + [("synthetic", 64, "plain")]
+
+
+@pytest.fixture(scope="module")
+def stress_sd():
+    return B.stress_state_dict(0)
+
+
+@pytest.fixture(scope="module")
+def conv0(stress_sd):
+    return CO.conv_params(stress_sd)
+
+
+@pytest.fixture(scope="module")
+def block0(stress_sd):
+    return BO.block_params(stress_sd)
+
+
+@pytest.fixture(scope="module")
+def sh(pkg, stress_sd):
+    """the handle of this module's trainers and extractions: stress weights, classifier only"""
+    h = pkg._lib.Handle(pkg.weights.pack_b0(stress_sd), device=0, max_batch=16)
+    yield h
+    h.close()
+
+
+@pytest.fixture(scope="module")
+def real_rows(sh):
+    x = B.random_crops(37, 42)
+    return np.concatenate([sh.extract_trunk(x[i:i + 16], block=14) for i in range(0, 37, 16)])
+
+
+def _labels(seed, n):
+    return (np.random.RandomState(seed).rand(n) < 0.5).astype(np.float32)
+
+
+def _open(pkg, h, head, conv, block, **kw):
+    cfg = pkg._lib.head_config(**kw)
+    h.head_train_begin(head, cfg)
+    try:
+        h.head_train_unfreeze_conv(conv)
+        h.head_train_unfreeze_block(block)
+    except Exception:
+        h.head_train_end()
+        raise
+    return O.config_values(cfg)
+
+
+def _check(name, got, ref64, yard32, record):
+    r = O.bar_ratio(got, ref64, yard32)
+    print(f"{name}: rms {r['rms']:.3e} (yard {r['yard_rms']:.3e}) max {r['max']:.3e} (yard {r['yard_max']:.3e}) ratio {r['ratio']:.3f}")
+    record.append((name, r["ratio"]))
+
+
+def _assert_all(record):
+    bad = [(k, round(v, 3)) for k, v in record if not v <= 1.0]
+    assert not bad, bad
+
+
+def _all_grads(h):
+    g = dict(h.head_train_grads())
+    g.update({"conv." + k: v for k, v in h.head_train_conv_grads().items()})
+    g.update({"b15." + k: v for k, v in h.head_train_block_grads().items()})
+    return g
+
+
+def _all_export(h, ema=False):
+    e = dict(h.head_train_export(ema))
+    e.update({"conv." + k: v for k, v in h.head_train_export_conv(ema).items()})
+    e.update({"b15." + k: v for k, v in h.head_train_export_block(ema).items()})
+    return e
+
+
+GRAD_KEYS = tuple("b15." + k for k in BO.BLOCK_GRAD_FIELDS) + tuple("conv." + k for k in CO.CONV_GRAD_FIELDS) + O.GRAD_FIELDS
+STAT_KEYS = tuple("b15." + k for k in BO.BLOCK_STAT_FIELDS) + tuple("conv." + k for k in CO.CONV_STAT_FIELDS) + O.STAT_FIELDS
+
+
+def _compare_state(h, o64, o32, rec):
+    g, g64, g32 = _all_grads(h), o64.grads(), o32.grads()
+    for k in GRAD_KEYS:
+        _check("grad " + k, g[k], g64[k], g32[k], rec)
+    e, e64, e32 = _all_export(h), o64.export(), o32.export()
+    for k in STAT_KEYS:
+        _check(k, e[k], e64[k], e32[k], rec)
+
+
+def _preconditions(o64, o32, ost, losses, ya, yb=None, lam=1.0, what=""):
+    margin, rshare = BO.gate_margin(o64, o32), BO.rounding_share(o64, ya, yb, lam)
+    sshare = BO.storage_share(o64, o32, ost, losses)
+    worst = max((k for k in sshare if k != "max"), key=lambda k: sshare[k])
+    print(f"gate margin{what} {margin:.2f}, rounding share {rshare:.3f}, storage share {sshare['max']:.3f} ({worst})")
+    assert margin >= 1.0 and rshare <= 1.0 and sshare["max"] <= 0.5   # conditions on the inputs, checked on the oracles alone
+
+
+# --------------------------------------------------------------------------- 1. one accumulate
+@pytest.mark.parametrize("kind,n,variant", CASES)
+def test_one_accumulate_matches_float64(pkg, sh, block0, conv0, real_rows, kind, n, variant):
+    if kind == "real":
+        seed, x = REAL_SEED[n], real_rows[:n]
+    else:
+        seed = SYN64_SEED
+        x = BO.synthetic_rows(seed + 100, n)
+    two, scale = VARIANTS[variant]
+    head, ya = O.default_params(seed), _labels(seed + 200, n)
+    yb, lam = (_labels(seed + 201, n), 0.7) if two else (None, 1.0)
+    cfg = _open(pkg, sh, head, conv0, block0, max_n=MAX_N, seed=seed)
+    try:
+        o64, o32, ost = BO.triple(block0, conv0, head, cfg)
+        (l64, z64), (l32, z32), (lst, _) = (o.accumulate(x, ya, yb, lam, scale) for o in (o64, o32, ost))
+        _preconditions(o64, o32, ost, (l64, l32, lst), ya, yb, lam)
+        loss, logits = sh.head_train_accumulate_block(x, ya, yb, lam, scale)
+        rec = []
+        _check("loss", [loss], [l64], [l32], rec)
+        _check("logits", logits, z64, z32, rec)
+        for k in BO.TAPS + ("cfeat", "dfeat"):
+            _check(k, sh.head_train_tap(k, n), o64.taps[k].numpy(), o32.taps[k].numpy(), rec)
+        _compare_state(sh, o64, o32, rec)
+        _assert_all(rec)
+    finally:
+        sh.head_train_end()
+
+
+# --------------------------------------------------------------------------- 2. accumulation
+def test_two_accumulates_add_up(pkg, sh, stress_sd, block0, conv0, real_rows):
+    seed = ACC_SEED
+    head = O.default_params(seed)
+    sd = dict(stress_sd)
+    sd.update({k: head[f] for k, f in T.KEYS.items()})
+    with T.HeadTrainer(sh, sd, train_block15=True, max_n=16, seed=seed) as tr:
+        assert tr.train_conv_head and tr.row_width == 9408 and tr.extract_method == "train_augment_block14"
+        o64, o32, ost = BO.triple(block0, conv0, head, O.config_values(tr.config))
+        for k, x in enumerate((real_rows[:16], real_rows[16:21])):
+            y = _labels(seed + 400 + k, x.shape[0])
+            losses = tuple(o.accumulate(x, y, None, 1.0, 0.5)[0] for o in (o64, o32, ost))
+            _preconditions(o64, o32, ost, losses, y, what=f", accumulate {k}:")
+            tr.accumulate(x.reshape(x.shape[0], -1), y, None, 1.0, 0.5)        # both row layouts are taken
+        rec = []
+        _compare_state(sh, o64, o32, rec)
+        _assert_all(rec)
+        exported = tr.export_state_dict()
+        for k in T.BLOCK_TRACKED + (T.CONV_TRACKED,) + T.TRACKED:
+            assert int(exported[k]) == int(np.asarray(stress_sd[k])) + 2, k
+        assert set(T.BLOCK_KEYS) <= set(exported) and exported["net._blocks.15._depthwise_conv.weight"].shape == (1152, 1, 3, 3)
+
+
+# --------------------------------------------------------------------------- 3. apply, teacher-forced
+def _forced_grads(pkg, seed):
+    """magnitudes log-uniform in [1e-4, 1], random signs: Adam's g / (sqrt(v) + eps) is well conditioned everywhere"""
+    rs = np.random.RandomState(seed)
+    shapes = {k: pkg._lib.HEAD_SHAPES[k] for k in O.GRAD_FIELDS}
+    shapes.update({"conv." + k: pkg._lib.CONV_SHAPES[k] for k in CO.CONV_GRAD_FIELDS})
+    shapes.update({"b15." + k: pkg._lib.BLOCK_SHAPES[k] for k in BO.BLOCK_GRAD_FIELDS})
+    return {k: (10.0 ** rs.uniform(-4.0, 0.0, s) * np.where(rs.rand(*s) < 0.5, -1.0, 1.0)).astype(np.float32) for k, s in shapes.items()}
+
+
+def _force(h, g):
+    h.head_train_grads(set_to={k: g[k] for k in O.GRAD_FIELDS})
+    h.head_train_conv_grads(set_to={k: g["conv." + k] for k in CO.CONV_GRAD_FIELDS})
+    h.head_train_block_grads(set_to={k: g["b15." + k] for k in BO.BLOCK_GRAD_FIELDS})
+
+
+@pytest.mark.parametrize("clip_norm", [1.0e4, 1.0])            # the forced norm is ~3e2: coefficient 1, and far above the clip
+def test_apply_steps_three_groups_at_their_rates_under_one_norm(pkg, sh, block0, conv0, clip_norm):
+    """Three forced applies.  The block and the conv group step at 0.1 x the head's rate: three Adam steps at the head's
+    rate would move their tensors by ~2.7 lr more, 1e-3 of their size - a thousand times the bar.  One norm: the forced
+    gradients give each arena about a third of the squared norm, so a norm over two arenas is 0.8 of the true one, and
+    under clip_norm = 1 every parameter of every group is scaled by 1 / norm."""
+    head = O.default_params(3)
+    cfg = _open(pkg, sh, head, conv0, block0, max_n=16, seed=0, clip_norm=clip_norm)
+    try:
+        o64, o32 = BO.pair(block0, conv0, head, cfg)
+        rec = []
+        for step, lr in enumerate((3e-4, 1.2e-5, 1e-3)):
+            lr = float(np.float32(lr))
+            g = _forced_grads(pkg, 50 + step)
+            _force(sh, g)
+            o64.set_grads(g)
+            o32.set_grads(g)
+            n64, n32 = o64.apply(lr), o32.apply(lr)
+            norm = sh.head_train_apply(lr)
+            assert (n64 < clip_norm) == (clip_norm > 1.0)
+            _check(f"grad norm, step {step}", [norm], [n64], [n32], rec)
+            sq = {p: sum(float((v.astype(np.float64) ** 2).sum()) for k, v in g.items() if k.startswith(p)) for p in ("b15.", "conv.")}
+            total = sum(float((v.astype(np.float64) ** 2).sum()) for v in g.values())
+            print(f"step {step}: norm {norm:.4f}, all three {np.sqrt(total):.4f}, without the block {np.sqrt(total - sq['b15.']):.4f}, "
+                  f"without the conv {np.sqrt(total - sq['conv.']):.4f}")
+            assert abs(norm - np.sqrt(total)) <= 1e-5 * np.sqrt(total)
+            assert np.sqrt(total - sq["b15."]) < 0.9 * norm and np.sqrt(total - sq["conv."]) < 0.95 * norm
+            assert all(not v.any() for v in _all_grads(sh).values())          # zeroed exactly, all three groups
+        for ema in (False, True):
+            e, e64, e32 = _all_export(sh, ema), o64.export(ema), o32.export(ema)
+            for k in GRAD_KEYS:
+                _check(("ema " if ema else "param ") + k, e[k], e64[k], e32[k], rec)
+        _assert_all(rec)
+        # the block's rate made explicit: the same three steps in the float64 oracle at lr_scale = 1 move exp_w ten times as far
+        if clip_norm > 1.0:
+            other = BO.BlockOracle(block0, conv0, head, cfg, torch.float64, lr_scale=1.0)
+            for step, lr in enumerate((3e-4, 1.2e-5, 1e-3)):
+                other.set_grads(_forced_grads(pkg, 50 + step))
+                other.apply(float(np.float32(lr)))
+            w0 = block0["exp_w"].astype(np.float64)
+            moved, at_scale, at_one = (np.abs(w - w0).mean() for w in (_all_export(sh)["b15.exp_w"], o64.export()["b15.exp_w"], other.export()["b15.exp_w"]))
+            print(f"mean |step| of exp_w: device {moved:.4e}, oracle at lr_scale x lr {at_scale:.4e}, oracle at lr {at_one:.4e}")
+            assert abs(moved - at_scale) <= 1e-3 * at_scale and at_one > 5.0 * at_scale
+    finally:
+        sh.head_train_end()
+
+
+# --------------------------------------------------------------------------- 4. eval
+def test_eval_block_matches_float64_and_ignores_the_chunking(pkg, sh, block0, conv0, real_rows):
+    seed = EVAL_SEED
+    head, x = O.default_params(seed), real_rows[:16]
+    cfg = _open(pkg, sh, head, conv0, block0, max_n=16, seed=seed, clip_norm=1.0e4, ema_decay=0.5)
+    try:
+        o64, o32 = BO.pair(block0, conv0, head, cfg)
+        g = _forced_grads(pkg, 70)
+        _force(sh, g)
+        o64.set_grads(g)
+        o32.set_grads(g)
+        lr = float(np.float32(1e-3))
+        o64.apply(lr), o32.apply(lr), sh.head_train_apply(lr)  # live and EMA parameters differ from here on
+        rec, seen = [], []
+        for ema in (False, True):
+            z64, z32 = o64.evaluate(x, ema), o32.evaluate(x, ema)
+            margin = BO.gate_margin(o64, o32)
+            print(f"gate margin, use_ema={ema}: {margin:.2f}")
+            assert margin >= 1.0
+            whole = sh.head_train_eval_block(x, ema)
+            _check(f"eval logits, use_ema={ema}", whole, z64, z32, rec)
+            for chunk in (1, 7):
+                parts = np.concatenate([sh.head_train_eval_block(x[i:i + chunk], ema) for i in range(0, 16, chunk)])
+                assert np.array_equal(whole, parts), chunk
+            seen.append(whole)
+        assert not np.array_equal(seen[0], seen[1])
+        _assert_all(rec)
+    finally:
+        sh.head_train_end()
+
+
+# --------------------------------------------------------------------------- 5. reproducibility
+def test_a_step_is_reproducible_bit_for_bit(pkg, sh, block0, conv0, real_rows):
+    head, y = O.default_params(1), _labels(5, 37)
+    seen = []
+    for _ in range(2):
+        _open(pkg, sh, head, conv0, block0, max_n=37, seed=11)
+        try:
+            loss, logits = sh.head_train_accumulate_block(real_rows, y)
+            seen.append((loss, logits.copy(), _all_grads(sh), _all_export(sh)))
+        finally:
+            sh.head_train_end()
+    a, b = seen
+    assert a[0] == b[0] and np.array_equal(a[1], b[1])
+    for k in GRAD_KEYS:
+        assert np.array_equal(a[2][k], b[2][k]), k
+        assert a[2][k].any() or k in ("b1", "b2"), k
+    for k in STAT_KEYS:
+        assert np.array_equal(a[3][k], b[3][k]), k
+
+
+# --------------------------------------------------------------------------- 6. commit
+def test_commit_swaps_block_conv_and_head_in_place(pkg, stress_sd, real_rows):
+    imgs = B.random_crops(2, 7)
+    L = pkg._lib
+    blob = pkg.weights.pack_b0(stress_sd)
+    h, never = L.Handle(blob, device=0, max_batch=2), L.Handle(blob, device=0, max_batch=2)
+
+    def outputs(handle, mode):
+        handle.set_option("bf16_activations", mode)
+        try:
+            lg = handle.classify(imgs).copy()
+            lg2, heat = handle.gradcam(imgs)
+            assert np.array_equal(lg, lg2)
+            return lg, heat.copy()
+        finally:
+            handle.set_option("bf16_activations", 0)
+
+    try:
+        before = [outputs(h, mode) for mode in (0, 1)]         # also builds the cached weight splits
+        rows14 = h.extract_trunk(imgs, block=14)
+        with T.HeadTrainer(h, stress_sd, train_block15=True, max_n=16, seed=4, ema_decay=0.5) as tr:
+            for k in range(3):
+                tr.accumulate(real_rows[k:k + 16], _labels(20 + k, 16))
+                tr.apply(1e-3)
+            for mode in (0, 1):                                # an open, trained, uncommitted trainer changes nothing
+                lg, heat = outputs(h, mode)
+                lg0, heat0 = outputs(never, mode)
+                assert np.array_equal(lg, lg0) and np.array_equal(heat, heat0)
+                assert np.array_equal(lg, before[mode][0]) and np.array_equal(heat, before[mode][1])
+            for ema in (False, True):
+                tr.commit(use_ema=ema)
+                sd = dict(stress_sd)
+                exported = tr.export_state_dict(use_ema=ema)
+                assert int(exported["net._blocks.15._bn2.num_batches_tracked"]) == int(np.asarray(stress_sd["net._blocks.15._bn2.num_batches_tracked"])) + 3
+                sd.update(exported)
+                fresh = L.Handle(pkg.weights.pack_b0(sd), device=0, max_batch=2)
+                try:
+                    for mode in (0, 1):
+                        got, want = outputs(h, mode), outputs(fresh, mode)
+                        last = got if mode == 0 else last
+                        print(f"use_ema={ema} bf16={mode}: before {before[mode][0].ravel()} committed {got[0].ravel()} fresh {want[0].ravel()}")
+                        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+                        assert not np.array_equal(got[0], before[mode][0])
+                    assert np.array_equal(h.extract_trunk(imgs), fresh.extract_trunk(imgs))
+                finally:
+                    fresh.close()
+                assert np.array_equal(h.extract_trunk(imgs, block=14), rows14)      # block 14 and everything below are untouched
+            for k in ("net._blocks.15._expand_conv.weight", "net._blocks.15._depthwise_conv.weight", "net._blocks.15._se_expand.bias",
+                      "net._blocks.15._bn1.weight", "net._conv_head.weight"):
+                assert not np.array_equal(exported[k], np.asarray(stress_sd[k])), k
+        assert np.array_equal(outputs(h, 0)[0], last[0])        # the committed tensors stay after the trainer is gone
+        lg0, heat0 = outputs(never, 0)
+        assert np.array_equal(lg0, before[0][0]) and np.array_equal(heat0, before[0][1])
+    finally:
+        h.close()
+        never.close()
+
+
+# --------------------------------------------------------------------------- 7. extraction
+def test_extract_trunk_at_is_the_blocks_tap(pkg, sh):
+    x = B.random_crops(5, 3)
+    xd = sh.alloc(x.nbytes).upload(x)
+    try:
+        for mode in (0, 1):
+            sh.set_option("bf16_activations", mode)
+            got = sh.extract_trunk(x, block=14)
+            want = sh.tap(xd.ptr, 5, "b14.out", 5 * 9408)
+            assert got.shape == (5, 7, 7, 192) and want.size == 5 * 9408
+            assert np.array_equal(got.ravel(), want) and np.abs(got).max() > 0
+            assert np.array_equal(sh.extract_trunk(x, block=15), sh.extract_trunk(x))
+            got15 = np.empty((5, 7, 7, 320), np.float32)                          # the new entry itself at block 15
+            sh._check(sh._lib.dfd_extract_trunk_at(sh._p, x.ctypes.data, 5, 15, got15.ctypes.data))
+            assert np.array_equal(got15, sh.extract_trunk(x))
+    finally:
+        sh.set_option("bf16_activations", 0)
+        xd.free()
+    with pytest.raises(pkg._lib.DfdError) as e:
+        sh.extract_trunk(x, block=13)
+    assert e.value.code == -1
+    with pytest.raises(pkg._lib.DfdError):
+        sh.extract_trunk(B.random_crops(17, 3), block=14)      # n > max_batch is the caller's chunking
+    m = pkg.model.DeepfakeEfficientNet(pretrained=False, max_batch=2, seed=0)
+    try:
+        got = m.extract_trunk(x, block=14)                     # chunks of 2, 2, 1
+        want = np.concatenate([m.handle.extract_trunk(x[i:i + 2], block=14) for i in range(0, 5, 2)])
+        assert got.shape == (5, 7, 7, 192) and np.array_equal(got, want)
+        assert np.array_equal(m.extract_trunk(x, block=15), m.extract_trunk(x))
+    finally:
+        m.handle.close()
+
+
+def test_train_augment_trunk_at_equals_augment_then_extract(pkg, seeded_sd):
+    h = pkg._lib.Handle(pkg.weights.pack_b0(seeded_sd), device=0, max_batch=2)
+    try:
+        rgb = np.random.RandomState(8).randint(0, 256, (5, 64, 96, 3)).astype(np.uint8)
+        rows, batch = TA.draw_batch(TA.AugmentPolicy(), np.random.RandomState(6), 5, 64, 96, 224,
+                                    mix=(TA.MIX_MIXUP, 0.8, np.array([4, 3, 0, 1, 2])))
+        x = h.train_augment(rgb, rows, batch, 224)
+        want = np.concatenate([h.extract_trunk(x[i:i + 2], block=14) for i in range(0, 5, 2)])
+        got = h.train_augment_trunk(rgb, rows, batch, block=14)
+        assert got.shape == (5, 7, 7, 192) and np.array_equal(got, want)
+        assert np.array_equal(h.train_augment_block14(rgb, rows, batch), want)
+        assert np.array_equal(h.train_augment_trunk(rgb, rows, batch, block=15), h.train_augment_trunk(rgb, rows, batch))
+        buf = h.alloc(rgb.nbytes).upload(rgb)
+        try:
+            assert np.array_equal(h.train_augment_trunk(buf, rows, batch, shape=rgb.shape[:3], block=14), want)
+        finally:
+            buf.free()
+    finally:
+        h.close()
+
+
+# --------------------------------------------------------------------------- 8. outcome
+def _two_classes(seed, n, sep=1.0):
+    rs = np.random.RandomState(seed)
+    y = (np.arange(n) % 2).astype(np.float32)
+    d = np.random.RandomState(99).randn(192)
+    d /= np.linalg.norm(d)
+    x = rs.randn(n, 49, 192) + (2 * y - 1)[:, None, None] * d * sep * np.sqrt(192.0) / 4.0
+    return x.reshape(n, -1).astype(np.float32), y
+
+
+def test_fit_separates_two_classes_of_block14_rows(pkg, sh, stress_sd, block0, conv0):
+    """40 optimizer steps at n = 16, oracle and device side by side; the figures are printed.  The shift (sep = 1.0) was
+    chosen on the float64 oracle alone: at the sibling test's 0.35 the oracle leaves 6 of the 32 held-out rows on the wrong
+    side after 40 steps; at 1.0 it takes the EMA validation loss from 0.0920 to 0.0038 with min |logit| 1.35."""
+    x, y = _two_classes(1, 160)
+    vx, vy = _two_classes(2, 32)
+    head = O.default_params(0)
+    sd = dict(stress_sd)
+    sd.update({k: head[f] for k, f in T.KEYS.items()})
+    kw = dict(epochs=4, batch_size=16, grad_accum=1, lr=1e-3, val=(vx, vy), patience=10)           # 40 optimizer steps
+    with T.HeadTrainer(sh, sd, train_block15=True, max_n=16, seed=3, ema_decay=0.9) as tr:
+        oracle = BO.BlockOracle(block0, conv0, head, O.config_values(tr.config), torch.float64)
+        v0_ref = T.focal_loss(oracle.evaluate(vx, True), vy, *oracle.loss_settings)
+        log_ref = T.fit_loop(oracle, x, y, rng=np.random.RandomState(5), **kw)
+        z_ref = oracle.evaluate(vx, True)
+        assert oracle.counter == 40
+        assert ((z_ref > 0) == (vy > 0.5)).all()               # precondition, on the oracle
+        assert log_ref[-1]["val_loss"] < v0_ref
+        v0 = T.focal_loss(tr.evaluate(vx, True), vy, *tr.loss_settings)
+        log = tr.fit(x, y, rng=np.random.RandomState(5), **kw)
+        z = tr.evaluate(vx.reshape(-1, 7, 7, 192), True)       # both row layouts are taken
+        diff = float(np.abs(z - z_ref).max())
+        print(f"oracle: val loss {v0_ref:.5f} -> {log_ref[-1]['val_loss']:.5f}, min|z| {np.abs(z_ref).min():.4f}; "
+              f"device: {v0:.5f} -> {log[-1]['val_loss']:.5f}, min|z| {np.abs(z).min():.4f}; max|z - z_ref| {diff:.3e}")
+        assert tr.steps == 40 and len(log) == 4
+        assert ((z > 0) == (z_ref > 0)).all()
+        assert log[-1]["val_loss"] < v0
+        assert min(np.abs(z).min(), np.abs(z_ref).min()) >= 10.0 * diff
+        sdo = tr.export_state_dict(True)
+        assert set(T.BLOCK_KEYS) | set(T.CONV_KEYS) <= set(sdo) and int(sdo[T.BLOCK_TRACKED[0]]) == int(np.asarray(stress_sd[T.BLOCK_TRACKED[0]])) + 40
+
+
+def test_fit_head_trains_block_conv_and_head_on_the_models_handle(pkg):
+    """DeepfakeEfficientNet.fit_head(train_block15=True): images in (block-14 rows extracted here), then uint8 crops with
+    `augment=` (every batch through `train_augment_trunk(block=14)`); all three committed on the SAME handle"""
+    m = pkg.model.DeepfakeEfficientNet(pretrained=False, max_batch=2, seed=0)
+    try:
+        imgs = (np.random.RandomState(4).randn(6, 3, 224, 224) * 0.8).astype(np.float32)
+        y = (np.arange(6) % 2).astype(np.float32)
+        key = "net._blocks.15._project_conv.weight"
+        before, handle, w0 = m(imgs[:2]).copy(), m.handle, np.array(m.state_dict()[key])
+        log = m.fit_head(imgs, y, epochs=1, batch_size=3, grad_accum=1, lr=1e-3, train_block15=True, trainer_config={"ema_decay": 0.5})
+        assert len(log) == 1 and m.handle is handle
+        after, w1 = m(imgs[:2]).copy(), np.array(m.state_dict()[key])
+        assert not np.array_equal(after, before) and w1.shape == w0.shape and not np.array_equal(w1, w0)
+        crops = np.random.RandomState(14).randint(0, 256, (8, 32, 32, 3)).astype(np.uint8)
+        y8 = (np.arange(8) % 2).astype(np.float32)
+        log = m.fit_head(crops, y8, epochs=1, batch_size=4, grad_accum=2, lr=1e-3, mix_alpha=0.4, cutmix_alpha=0.3, train_block15=True,
+                         augment=TA.AugmentPolicy(), val=(crops[:3], y8[:3]), rng=np.random.RandomState(2))
+        assert len(log) == 1 and np.isfinite(log[0]["train_loss"]) and np.isfinite(log[0]["val_loss"]) and m.handle is handle
+        last = m(imgs[:2])
+        assert not np.array_equal(last, after) and int(m.state_dict()["net._blocks.15._bn0.num_batches_tracked"]) == 4
+        fresh = pkg._lib.Handle(pkg.weights.pack_b0(m.state_dict()), device=0, max_batch=2)
+        try:
+            assert np.array_equal(fresh.classify(imgs[:2]), last)
+        finally:
+            fresh.close()
+    finally:
+        m.handle.close()
+
+
+# --------------------------------------------------------------------------- 9. refusals
+def test_refusals_leave_the_handle_usable(pkg, sh, block0, conv0):
+    L = pkg._lib
+    head, x, y = O.default_params(0), BO.synthetic_rows(0, 4), _labels(0, 4)
+    feat, trunk = O.features(0, 4), CO.synthetic_trunk(0, 4)
+
+    def refused(fn, *a, code=-1, **k):
+        with pytest.raises(L.DfdError) as e:
+            fn(*a, **k)
+        assert e.value.code == code and len(str(e.value)) > 30, str(e.value)    # the documented code with a message
+
+    refused(sh.head_train_unfreeze_block, block0)                               # no trainer is open
+    sh.head_train_begin(head, L.head_config(max_n=4))
+    try:
+        refused(sh.head_train_unfreeze_block, block0)                           # without the conv stage
+        for call in (lambda: sh.head_train_accumulate_block(x, y), lambda: sh.head_train_eval_block(x), sh.head_train_export_block,
+                     sh.head_train_block_grads):
+            refused(call)                                                       # the block entries before it is unfrozen
+        sh.head_train_unfreeze_conv(conv0)
+        for call in (lambda: sh.head_train_accumulate_block(x, y), lambda: sh.head_train_eval_block(x), sh.head_train_export_block,
+                     sh.head_train_block_grads):
+            refused(call)
+        sh.head_train_accumulate_trunk(trunk, y)                                # the conv-stage trainer still works
+        refused(sh.head_train_tap, "b15.out", 4)
+        refused(sh.head_train_unfreeze_block, block0)                           # after an accumulate
+    finally:
+        sh.head_train_end()
+    sh.head_train_begin(head, L.head_config(max_n=4))
+    try:
+        sh.head_train_unfreeze_conv(conv0)
+        for other in (14, 9, 0, 16, -1):
+            refused(sh.head_train_unfreeze_block, block0, other, code=-7)       # DFD_ERR_UNSUPPORTED: only the last block
+        refused(sh.head_train_unfreeze_block, block0, bn_eps=0.0)
+        bp, keep = L._block_arrays(block0)
+        bp.se_b2 = None                                                         # a null field
+        refused(lambda: sh._check(sh._lib.dfd_head_train_unfreeze_block(sh._p, 15, L.C.byref(bp), 0.01, 1e-3)))
+        sh.head_train_unfreeze_block(block0)
+        refused(sh.head_train_unfreeze_block, block0)                           # a second time
+        refused(sh.head_train_accumulate, feat, y)                              # pooled rows, once unfrozen
+        refused(sh.head_train_eval, feat)
+        refused(sh.head_train_accumulate_trunk, trunk, y)                       # trunk rows, once unfrozen
+        refused(sh.head_train_eval_trunk, trunk)
+        with pytest.raises(ValueError):
+            sh.head_train_accumulate_block(trunk, y)                            # rows of the wrong shape
+        with pytest.raises(ValueError):
+            sh.head_train_eval_block(x.reshape(4, 49, 192)[:, :48])
+        refused(sh.head_train_accumulate_block, x[:1], y[:1])                   # n < 2
+        refused(sh.head_train_accumulate_block, BO.synthetic_rows(0, 5), _labels(0, 5))    # n > max_n
+        refused(sh.head_train_eval_block, BO.synthetic_rows(0, 5))
+        refused(sh.head_train_tap, "b15.ad", 4)                                 # nothing accumulated yet
+        loss, logits = sh.head_train_accumulate_block(x, y)
+        assert np.isfinite(loss) and np.isfinite(logits).all()
+        assert sh.head_train_tap("b15.ad", 4).shape == (4, 49, 1152) and sh.head_train_tap("b15.gate", 4).shape == (4, 1152)
+        refused(sh.head_train_tap, "b15.nothing", 4)
+        assert np.isfinite(sh.head_train_apply(1e-3)) and np.isfinite(sh.head_train_eval_block(x)).all()
+    finally:
+        sh.head_train_end()
+    refused(sh.head_train_accumulate_block, x, y)                               # after end
+    assert np.isfinite(sh.classify(B.random_crops(1, 0))).all()
+    # dfd_destroy with an open trainer and both stages frees all three
+    h = L.Handle(pkg.weights.pack_b0(pkg.weights.seeded_state_dict(0)), device=0, max_batch=1)
+    h.head_train_begin(head, L.head_config(max_n=4))
+    h.head_train_unfreeze_conv(conv0)
+    h.head_train_unfreeze_block(block0)
+    h.head_train_accumulate_block(x, y)
+    h.close()
