@@ -105,7 +105,9 @@ int dfd_set_option(dfd_handle* h, const char* name, int value);
  *   bf16 planes of the fp32 weights (3) or against bf16-rounded weights (1).
  *   "gemm_tile" (default -1): >= 0 forces split-GEMM instance number value % (candidates of the shape) for every
  *   1x1 / k x k conv - parity tests walk 0 .. dfd_gemm_tile_count()-1 and require identical bits; -1 = the
- *   handle's tile table (measured by dfd_warmup, heuristic for shapes it has not seen). */
+ *   handle's tile table (measured by dfd_warmup, heuristic for shapes it has not seen).
+ *   dfd_gemm_tile_count() is the largest candidate count any call can have, the pw8 / pw9 instances that only some
+ *   calls may run included, so that walk reaches every instance of every shape. */
 int dfd_gemm_tile_count(void);
 
 /* One untimed pass over the classifier at batch `n_crops` (0 = skip; <= max_batch) and the detector at
@@ -127,6 +129,42 @@ int dfd_tiles_import(dfd_handle* h, const char* text, size_t length, int* accept
  * 2^31 bytes, -1 when a single image does not).  Batches above that are issued as several launches, so every
  * max_batch dfd_create accepts is addressable.  No GPU needed. */
 long long dfd_gemm_chunk_rows(long long rows, long long row_bytes, long long rows_per_image);
+
+/* One split-GEMM call on host data, through the launchers every network uses (launch_pointwise_split /
+ * launch_conv_gemm_split on the handle's own tile table, so "gemm_tile" applies): tests/test_gemm_direct_gpu.py.
+ *   pointwise (conv = 0): Y[M][N] = act((X[M][K] * gate[m / HW][K]) W^T + bias [+ R]) [+ R]
+ *   conv      (conv = 1): n_img NHWC images H x W x Cin -> Ho x Wo x N, K = ksize^2 * Cin, M = n_img * Ho * Wo (M, K and
+ *                         HW of the struct are ignored and filled in)
+ * X, R and Y are fp32, or - bf16 = 1 - bf16 bit patterns (uint16); Wt is fp32 [N][K] (conv: [N][ky][kx][ci]), split on
+ * the device; bias holds N values, followed by the N slopes when act = 3 (PReLU; 0 none, 1 swish, 2 relu); gate (may
+ * be NULL, pointwise only) holds ceil(M / HW) rows of K; R (may be NULL) is added before (res_first = 1) or after the
+ * activation; planes = 3, or 1 with bf16.  x_rows > 0 (pointwise): the host X holds only x_rows rows and the device
+ * operand repeats them down all M rows (a 2 GiB operand from a small host block).
+ * Y receives (M + 2 * DFD_GEMM_TAP_GUARD) rows of N: the device buffer is pre-filled with DFD_GEMM_TAP_SENTINEL (its
+ * upper 16 bits with bf16) and returned whole - guard rows, result, guard rows - so a store past a ragged edge shows as a
+ * changed guard and a missing store as a surviving sentinel.
+ * Out: `candidates` = the number of instances "gemm_tile" indexes for this very call (its first launch), `tile` = the
+ * instance that ran last (kind, wm, wn, mt, nt, ks; kind 0 pw6, 1 pw7, 2 pw8, 3 pw9), `launches` = kernel launches (the
+ * 2^31-byte chunks of dfd_gemm_chunk_rows).
+ * DFD_ERR_UNSUPPORTED, without a launch and with Y at the sentinel, for shapes the launchers refuse (K % 8, K < 16,
+ * conv Cin % 32). */
+#define DFD_GEMM_TAP_GUARD 64
+#define DFD_GEMM_TAP_SENTINEL 0x7FC5A5A5u
+typedef struct dfd_gemm_tap_params {
+    int32_t conv, bf16, planes, act, res_first, reserved;
+    int32_t M, K, N, HW;
+    int32_t n_img, H, W, Cin, ksize, stride, pad, dil, Ho, Wo;
+    int64_t x_rows;
+    const void* X;
+    const float* Wt;
+    const float* bias;
+    const float* gate;
+    const void* R;
+    void* Y;
+    int32_t candidates, launches;
+    int32_t tile[6];
+} dfd_gemm_tap_params;
+int dfd_gemm_tap(dfd_handle* h, dfd_gemm_tap_params* p);
 
 /* ---- device memory and stream plumbing (no reference counterpart) -------------- */
 int dfd_device_alloc(dfd_handle* h, size_t bytes, void** dptr);

@@ -39,6 +39,7 @@ SIGNATURES = {
     "dfd_tiles_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "dfd_tiles_import": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_int)]),
     "dfd_gemm_chunk_rows": (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_longlong]),
+    "dfd_gemm_tap": (C.c_int, [C.c_void_p, C.c_void_p]),
     "dfd_device_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "dfd_device_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "dfd_memcpy_h2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -198,6 +199,20 @@ SIGNATURES = {
     "dfd_train_augment_tap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_char_p, C.c_void_p, C.c_size_t]),
 }
+
+
+GEMM_TAP_GUARD = 64                  # DFD_GEMM_TAP_GUARD: guard rows in front of and behind the result
+GEMM_TAP_SENTINEL = 0x7FC5A5A5       # DFD_GEMM_TAP_SENTINEL (fp32 bits; bf16: the upper 16)
+GEMM_TAP_UNSUPPORTED = -7            # DFD_ERR_UNSUPPORTED: a shape the launchers refuse
+GEMM_ACTS = {None: 0, "none": 0, "swish": 1, "relu": 2, "prelu": 3}
+
+
+class GemmTapParams(C.Structure):
+    """`dfd_gemm_tap_params` (include/dfd_hip.h)"""
+    _fields_ = ([(k, C.c_int32) for k in ("conv", "bf16", "planes", "act", "res_first", "reserved", "M", "K", "N", "HW", "n_img", "H",
+                                          "W", "Cin", "ksize", "stride", "pad", "dil", "Ho", "Wo")] +
+                [("x_rows", C.c_int64)] + [(k, C.c_void_p) for k in ("X", "Wt", "bias", "gate", "R", "Y")] +
+                [("candidates", C.c_int32), ("launches", C.c_int32), ("tile", C.c_int32 * 6)])
 
 
 class MtcnnParams(C.Structure):
@@ -827,6 +842,61 @@ class Handle:
         cnt = C.c_size_t()
         self._check(self._lib.dfd_b0_tap(self._p, x_dev, int(n), name.encode(), _ptr(out), out.size, C.byref(cnt)))
         return out[: cnt.value]
+
+    def gemm_tap(self, x, w, bias, act=None, gate=None, res=None, res_first=False, hw=1, bf16=False, planes=3, conv=None,
+                 rows=None):
+        """One split-GEMM call on host data (dfd_gemm_tap).  Pointwise: x (M, K), w (N, K), bias (N,) - (2N,) = bias then
+        slopes with act "prelu" -, gate (ceil(M / hw), K), res (M, N); `rows` = M when x holds only a block of rows that the
+        device operand repeats.  conv = dict(n_img, H, W, Cin, ksize, stride, pad, dil): x (n_img, H, W, Cin), w (N, ksize,
+        ksize, Cin).  bf16: x, res and the result are uint16 bf16 bit patterns.
+        -> dict(rc (0, or GEMM_TAP_UNSUPPORTED for a refused shape), y (M, N), before / after (the guard rows), candidates,
+        launches, tile (kind, wm, wn, mt, nt, ks))"""
+        xt = np.uint16 if bf16 else np.float32
+        x = np.ascontiguousarray(x, xt)
+        w = np.ascontiguousarray(w, np.float32)
+        b = np.ascontiguousarray(bias, np.float32).ravel()
+        p = GemmTapParams()
+        p.bf16, p.planes, p.act, p.res_first = int(bool(bf16)), int(planes), GEMM_ACTS[act], int(bool(res_first))
+        n_out = w.shape[0]
+        if conv is not None:
+            p.conv = 1
+            for k in ("n_img", "H", "W", "Cin", "ksize", "stride", "pad", "dil"):
+                setattr(p, k, int(conv[k]))
+            span = p.dil * (p.ksize - 1) + 1
+            ho, wo = (p.H + 2 * p.pad - span) // p.stride + 1, (p.W + 2 * p.pad - span) // p.stride + 1
+            m, k_in = p.n_img * ho * wo, p.ksize * p.ksize * p.Cin
+            if x.size != p.n_img * p.H * p.W * p.Cin:
+                raise ValueError("x does not hold n_img x H x W x Cin values")
+        else:
+            m, k_in = int(rows if rows is not None else x.shape[0]), x.shape[1]
+            p.M, p.K, p.HW = m, k_in, int(hw)
+            p.x_rows = x.shape[0] if rows is not None else 0
+            if x.ndim != 2 or x.shape[0] > m:
+                raise ValueError("x must be (M, K), or a block of at most `rows` rows")
+        p.N = n_out
+        if w.size != n_out * k_in or b.size != (2 * n_out if p.act == 3 else n_out) or m <= 0:
+            raise ValueError("w must hold N x K values, bias N (2N with prelu)")
+        keep = [x, w, b]
+        p.X, p.Wt, p.bias = x.ctypes.data, w.ctypes.data, b.ctypes.data
+        if gate is not None:
+            g = np.ascontiguousarray(gate, np.float32)
+            if conv is not None or g.shape != (-(-m // p.HW), k_in):
+                raise ValueError("gate must be (ceil(M / hw), K), pointwise only")
+            keep.append(g)
+            p.gate = g.ctypes.data
+        if res is not None:
+            r = np.ascontiguousarray(res, xt)
+            if r.size != m * n_out:
+                raise ValueError("res must hold M x N values")
+            keep.append(r)
+            p.R = r.ctypes.data
+        y = np.zeros((m + 2 * GEMM_TAP_GUARD, n_out), xt)
+        p.Y = y.ctypes.data
+        rc = self._lib.dfd_gemm_tap(self._p, C.byref(p))
+        if rc not in (0, GEMM_TAP_UNSUPPORTED):
+            self._check(rc)
+        return {"rc": rc, "y": y[GEMM_TAP_GUARD:GEMM_TAP_GUARD + m], "before": y[:GEMM_TAP_GUARD], "after": y[GEMM_TAP_GUARD + m:],
+                "candidates": int(p.candidates), "launches": int(p.launches), "tile": tuple(int(v) for v in p.tile)}
 
     def profile_begin(self):
         self._check(self._lib.dfd_b0_profile_begin(self._p))

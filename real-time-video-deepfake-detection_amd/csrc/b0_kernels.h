@@ -61,7 +61,13 @@ void s6_table_destroy(S6Table* t);
 void s6_table_set_force(S6Table* t, int idx);      // >= 0: run candidate idx (mod count) everywhere; -1: normal
 void s6_table_set_tuning(S6Table* t, bool on);
 int s6_table_measured(const S6Table* t);           // shapes with a measured tile
-int s6_max_candidates();                           // upper bound of the candidate count over all shapes
+int s6_max_candidates();                           // largest candidate count of any call (pw8 / pw9 extras included)
+// host-side bookkeeping for dfd_gemm_tap: the candidates "gemm_tile" indexes for one launch (pw8 / pw9 decided as the
+// launchers decide them), the instance the table dispatched last and how many launches it has dispatched
+int s6_call_candidates(bool conv, bool gated, bool bf16, int planes, int M, int K, int N, int HW, int act, bool has_res,
+                       int res_first);
+void s6_table_last(const S6Table* t, int out[6]);  // kind, wm, wn, mt, nt, ks
+long long s6_table_dispatches(const S6Table* t);
 long long s6_chunk_rows(long long M, long long row_bytes, long long HW);
 std::string s6_table_export(const S6Table* t);                       // measured entries as text
 int s6_table_import(S6Table* t, const char* text, size_t len);       // -> entries accepted
@@ -69,7 +75,8 @@ int s6_table_import(S6Table* t, const char* text, size_t len);       // -> entri
 // XT = bf16_t: bf16 activation storage in and out, `planes` = 3 (fp32-exact weights) or 1 (bf16 weights).
 template <typename XT>
 bool launch_pointwise_split(S6Table* tab, const XT* X, const unsigned short* W3, const float* bias, const float* gate,
-                            const XT* R, XT* Y, int M, int K, int N, int HW, int act, int planes, hipStream_t s);
+                            const XT* R, XT* Y, int M, int K, int N, int HW, int act, int planes, hipStream_t s,
+                            int res_first = 0);      // 1: R is added before the activation (no network asks for it)
 template <typename XT>
 bool launch_conv_gemm_split(S6Table* tab, const XT* X, const unsigned short* W3, const float* bias, const XT* R,
                             XT* Y, int n_img, const ConvGeom& g, int Cout, int act, bool res_first, int planes, hipStream_t s);

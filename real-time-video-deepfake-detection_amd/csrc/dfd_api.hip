@@ -271,6 +271,102 @@ long long dfd_gemm_chunk_rows(long long rows, long long row_bytes, long long row
     return s6_chunk_rows(rows, row_bytes, rows_per_image);
 }
 
+int dfd_gemm_tap(dfd_handle* h, dfd_gemm_tap_params* p) {
+    if (!h || !p) return DFD_ERR_ARG;
+    p->candidates = p->launches = 0;
+    for (int i = 0; i < 6; ++i) p->tile[i] = 0;
+    if (!p->X || !p->Wt || !p->bias || !p->Y) return fail(h, DFD_ERR_ARG, "gemm_tap: X, Wt, bias or Y is null");
+    const bool bf = p->bf16 != 0, conv = p->conv != 0;
+    if ((p->planes != 3 && !(p->planes == 1 && bf)) || p->act < ACT_NONE || p->act > ACT_PRELU)
+        return fail(h, DFD_ERR_ARG, "gemm_tap: planes must be 3 (or 1 with bf16), act 0..3");
+    ConvGeom g{};
+    if (conv) {
+        if (p->gate || p->x_rows > 0) return fail(h, DFD_ERR_ARG, "gemm_tap: gate and x_rows are pointwise only");
+        if (p->n_img <= 0 || p->H <= 0 || p->W <= 0 || p->Cin <= 0 || p->ksize <= 0 || p->stride <= 0 || p->pad < 0 || p->dil <= 0)
+            return fail(h, DFD_ERR_ARG, "gemm_tap: bad conv geometry");
+        const int span = p->dil * (p->ksize - 1) + 1;
+        if (p->H + 2 * p->pad < span || p->W + 2 * p->pad < span) return fail(h, DFD_ERR_ARG, "gemm_tap: kernel larger than the padded image");
+        g.H = p->H; g.W = p->W; g.Cin = p->Cin; g.ksize = p->ksize; g.stride = p->stride; g.pad = p->pad; g.dil = p->dil;
+        g.Ho = (p->H + 2 * p->pad - span) / p->stride + 1;
+        g.Wo = (p->W + 2 * p->pad - span) / p->stride + 1;
+        if ((p->Ho && p->Ho != g.Ho) || (p->Wo && p->Wo != g.Wo)) return fail(h, DFD_ERR_ARG, "gemm_tap: Ho x Wo must be %d x %d", g.Ho, g.Wo);
+        const long long rows = (long long)p->n_img * g.Ho * g.Wo, kk = (long long)p->ksize * p->ksize * p->Cin;
+        if (rows > (1ll << 30) || kk > (1ll << 20)) return fail(h, DFD_ERR_ARG, "gemm_tap: conv too large");
+        p->Ho = g.Ho; p->Wo = g.Wo; p->M = (int)rows; p->K = (int)kk; p->HW = g.Ho * g.Wo;
+    }
+    const int M = p->M, K = p->K, N = p->N, HW = conv ? 1 : (p->HW > 0 ? p->HW : 1);
+    if (M <= 0 || K <= 0 || N <= 0 || K > (1 << 20) || N > (1 << 16) || p->x_rows < 0 || p->x_rows > M)
+        return fail(h, DFD_ERR_ARG, "gemm_tap: bad M, K, N or x_rows");
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    const size_t esz = bf ? 2 : 4, G = DFD_GEMM_TAP_GUARD;
+    const size_t xrows_host = conv ? 0 : (size_t)(p->x_rows > 0 ? p->x_rows : M);
+    const size_t xcount = conv ? (size_t)p->n_img * g.H * g.W * g.Cin : (size_t)M * K;
+    const size_t xhost = conv ? xcount : xrows_host * K;
+    const size_t ycount = ((size_t)M + 2 * G) * N, nb = (size_t)(p->act == ACT_PRELU ? 2 * N : N);
+    const size_t gcount = p->gate ? (size_t)((M + HW - 1) / HW) * K : 0;
+    const bool ok = split_gemm_supports(K, N) && !(conv && g.Cin % 32 != 0) &&
+                    s6_chunk_rows(conv ? p->n_img : M, conv ? (long long)g.H * g.W * g.Cin * (long long)esz : (long long)K * (long long)esz,
+                                  p->gate ? HW : 1) > 0;
+    // one allocation, 256-byte slots: Y (guard rows, result, guard rows) first, then the operands
+    size_t total = 0;
+    auto slot = [&](size_t bytes) { const size_t at = total; total += (bytes + 255) / 256 * 256; return at; };
+    const size_t oy = slot(ycount * esz);
+    const size_t ox = slot(ok ? xcount * esz : 0), ow = slot(ok ? (size_t)N * K * 4 : 0), ow3 = slot(ok ? split_weights_count(N, K) * 6 : 0);
+    const size_t ob = slot(ok ? nb * 4 : 0), og = slot(ok ? gcount * 4 : 0), orr = slot(ok && p->R ? (size_t)M * N * esz : 0);
+    char* base = nullptr;
+    DFD_HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&base), total + 256));
+    auto run = [&]() -> int {
+        void* dy = base + oy;
+        if (bf) DFD_HIP_TRY(h, hipMemsetD16Async(dy, (unsigned short)(DFD_GEMM_TAP_SENTINEL >> 16), ycount, h->stream));
+        else DFD_HIP_TRY(h, hipMemsetD32Async(dy, (int)DFD_GEMM_TAP_SENTINEL, ycount, h->stream));
+        if (ok) {
+            char* dx = base + ox;
+            float *dw = reinterpret_cast<float*>(base + ow), *db = reinterpret_cast<float*>(base + ob);
+            unsigned short* w3 = reinterpret_cast<unsigned short*>(base + ow3);
+            const float* dg = p->gate ? reinterpret_cast<const float*>(base + og) : nullptr;
+            const void* dr = p->R ? base + orr : nullptr;
+            DFD_HIP_TRY(h, hipMemcpyAsync(dx, p->X, xhost * esz, hipMemcpyHostToDevice, h->stream));
+            for (size_t r0 = xrows_host; !conv && r0 < (size_t)M; r0 += xrows_host)      // x_rows: the block repeated down the operand
+                DFD_HIP_TRY(h, hipMemcpyAsync(dx + r0 * K * esz, dx, std::min(xrows_host, (size_t)M - r0) * K * esz, hipMemcpyDeviceToDevice,
+                                              h->stream));
+            DFD_HIP_TRY(h, hipMemcpyAsync(dw, p->Wt, (size_t)N * K * 4, hipMemcpyHostToDevice, h->stream));
+            DFD_HIP_TRY(h, hipMemcpyAsync(db, p->bias, nb * 4, hipMemcpyHostToDevice, h->stream));
+            if (p->gate) DFD_HIP_TRY(h, hipMemcpyAsync(base + og, p->gate, gcount * 4, hipMemcpyHostToDevice, h->stream));
+            if (p->R) DFD_HIP_TRY(h, hipMemcpyAsync(base + orr, p->R, (size_t)M * N * esz, hipMemcpyHostToDevice, h->stream));
+            launch_split_weights(dw, w3, N, K, h->stream, false);
+            const long long before = s6_table_dispatches(h->gemm);
+            const long long chunk = conv ? M : s6_chunk_rows(M, (long long)K * (long long)esz, p->gate ? HW : 1);
+            p->candidates = s6_call_candidates(conv, p->gate != nullptr, bf, p->planes, (int)std::min<long long>(chunk, M), K, N, HW, p->act,
+                                               p->R != nullptr, p->res_first ? 1 : 0);
+            bool launched;
+            if (bf) {
+                bf16_t* y = static_cast<bf16_t*>(dy) + G * N;
+                const bf16_t *x = reinterpret_cast<const bf16_t*>(dx), *r = static_cast<const bf16_t*>(dr);
+                launched = conv ? launch_conv_gemm_split<bf16_t>(h->gemm, x, w3, db, r, y, p->n_img, g, N, p->act, p->res_first != 0, p->planes, h->stream)
+                                : launch_pointwise_split<bf16_t>(h->gemm, x, w3, db, dg, r, y, M, K, N, HW, p->act, p->planes, h->stream,
+                                                                 p->res_first ? 1 : 0);
+            } else {
+                float* y = static_cast<float*>(dy) + G * N;
+                const float *x = reinterpret_cast<const float*>(dx), *r = static_cast<const float*>(dr);
+                launched = conv ? launch_conv_gemm_split<float>(h->gemm, x, w3, db, r, y, p->n_img, g, N, p->act, p->res_first != 0, 3, h->stream)
+                                : launch_pointwise_split<float>(h->gemm, x, w3, db, dg, r, y, M, K, N, HW, p->act, 3, h->stream, p->res_first ? 1 : 0);
+            }
+            if (!launched) return fail(h, DFD_ERR_ARG, "gemm_tap: the launcher refused M=%d K=%d N=%d", M, K, N);
+            DFD_HIP_TRY(h, hipGetLastError());
+            p->launches = (int)(s6_table_dispatches(h->gemm) - before);
+            s6_table_last(h->gemm, p->tile);
+        }
+        DFD_HIP_TRY(h, hipMemcpyAsync(p->Y, dy, ycount * esz, hipMemcpyDeviceToHost, h->stream));
+        DFD_HIP_TRY(h, stream_sync(h));
+        if (!ok) return fail(h, DFD_ERR_UNSUPPORTED, "gemm_tap: K=%d N=%d%s is not a split-GEMM shape", K, N, conv ? " (conv: Cin % 32)" : "");
+        return DFD_OK;
+    };
+    const int rc = run();
+    if (rc != DFD_OK && rc != DFD_ERR_UNSUPPORTED) hipStreamSynchronize(h->stream);
+    hipFree(base);
+    return rc;
+}
+
 int dfd_device_alloc(dfd_handle* h, size_t bytes, void** dptr) {
     if (!h || !dptr) return DFD_ERR_ARG;
     DFD_HIP_TRY(h, hipSetDevice(h->device));

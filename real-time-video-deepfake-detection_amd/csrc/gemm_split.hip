@@ -1,5 +1,7 @@
 // Host side of the split-precision GEMM (kernels: gemm_split_impl.h): weight splitting, the candidate list, the
 // per-handle tile table with its measurement pass (dfd_warmup only), the 2^31-byte chunking and the launchers.
+// Every instance is walked as a candidate, one call at a time, at ragged shapes and against float64 by
+// tests/test_gemm_direct_gpu.py (through dfd_gemm_tap, dfd_api.hip), which also runs the chunk loop once.
 #include "gemm_split_impl.h"
 
 #include <algorithm>
@@ -79,8 +81,8 @@ static S6Tile pick_tile6(int M, int N) {
 
 // Every instance the library can launch for a shape, in a fixed order (what the tuner measures and what
 // dfd_set_option(h, "gemm_tile", i) indexes): pw6 with 4 waves (KS x MT x NT), pw6 with 8 waves (KS x NT), pw7.
-// thin: the shape and call may also run pw8 (all of N per wave, weights resident in LDS; s6_thin below) - appended last
-// wide: the call may run pw9 (activations resident in registers, all column blocks per block; s6_wide in s6_run_one)
+// thin: the shape and call may also run pw8 (all of N per wave, weights resident in LDS) - appended last
+// wide: the call may run pw9 (activations resident in registers, all column blocks per block); both decided by s6_extras
 static std::vector<S6Tile> s6_candidates(int M, int K, int N, bool thin = false, bool wide = false) {
     const int tiles = (N + 15) / 16;
     std::vector<S6Tile> raw, out;
@@ -114,7 +116,8 @@ static std::vector<S6Tile> s6_candidates(int M, int K, int N, bool thin = false,
 // measured rather than modelled - but only inside dfd_warmup (table->tuning), which is allowed to synchronise.
 // Everywhere else a shape that was never warmed up runs the heuristic tile and nothing blocks.  Every tile
 // computes each output with the same MFMA sequence, so the choice never changes a result bit
-// (tests/test_gemm_tiles_gpu.py walks every candidate through dfd_set_option(h, "gemm_tile", i)).
+// (tests/test_gemm_direct_gpu.py walks every candidate of single calls at ragged shapes through dfd_gemm_tap,
+// tests/test_gemm_tiles_gpu.py every candidate of the networks' shapes through dfd_set_option(h, "gemm_tile", i)).
 struct S6Key {
     int M, K, N, mode;
     bool operator<(const S6Key& o) const {
@@ -125,6 +128,8 @@ struct S6Table {
     std::map<S6Key, S6Tile> tiles;
     int force = -1;          // >= 0: candidate index (mod the shape's candidate count) for every call
     bool tuning = false;     // measure unseen shapes (synchronises the stream): dfd_warmup only
+    S6Tile last{};           // the instance of the last launch and the number of launches (host-side bookkeeping for
+    long long dispatches = 0;      // dfd_gemm_tap; the tuner's timing launches are not counted)
 };
 
 S6Table* s6_table_create() { return new (std::nothrow) S6Table(); }
@@ -177,7 +182,20 @@ int s6_table_import(S6Table* t, const char* text, size_t len) {
     return n;
 }
 
-int s6_max_candidates() { return (int)s6_candidates(1 << 20, 1152, 1280).size(); }
+void s6_table_last(const S6Table* t, int out[6]) {
+    const S6Tile z{};
+    const S6Tile& l = t ? t->last : z;
+    out[0] = l.kind; out[1] = l.wm; out[2] = l.wn; out[3] = l.mt; out[4] = l.nt; out[5] = l.ks;
+}
+long long s6_table_dispatches(const S6Table* t) { return t ? t->dispatches : 0; }
+
+// The largest list any call can have: K > 32 (both KS), N >= 192 (every pw7 config survives the padding filter) plus
+// the three pw9 instances; a pw8 shape (N <= 48: at most three column tiles) has its eight extras on a far shorter list.
+int s6_max_candidates() {
+    size_t best = s6_candidates(1 << 20, 96, 48, true, false).size();
+    for (int n = 192; n <= 1280; n += 16) best = std::max(best, s6_candidates(1 << 20, 96, n, false, true).size());
+    return (int)best;
+}
 
 // Rows of one kernel call: activations (and gates) are addressed with 32-bit byte offsets and sized with a
 // 32-bit num_records, so a call never spans 2^31 bytes of X.  Chunks are whole images (HW rows) so that the
@@ -225,18 +243,32 @@ static void s6_measure(bool conv, bool gated, const std::vector<S6Tile>& cands, 
                 key.mode, tile->kind, tile->wm, tile->wn, tile->mt, tile->nt, tile->ks, best_ms * 1000.f / 3.f);
 }
 
+// Which calls may also run pw8 (thin) / pw9 (wide); one definition for the launchers and for s6_call_candidates.
+// pw8 takes the call when the whole weight matrix fits its LDS image, a 16-row tile never straddles two images (the
+// gate row is block-uniform) and nothing but bias / activation / residual happens in the epilogue
+static void s6_extras(bool conv, bool gated, bool bf16, int planes, int M, int K, int N, int HW, int act, bool has_res,
+                      int res_first, bool* thin, bool* wide) {
+    static const bool thin_env = !(getenv("DFD_S6_THIN") && atoi(getenv("DFD_S6_THIN")) == 0);
+    static const bool wide_env = !(getenv("DFD_S6_WIDE") && atoi(getenv("DFD_S6_WIDE")) == 0);
+    *thin = thin_env && !conv && s8_supports(K, N) && (!gated || (HW % 16 == 0 && M % HW == 0)) && act != ACT_PRELU &&
+            !(has_res && res_first);
+    *wide = wide_env && !conv && !gated && !bf16 && planes == 3 && s9_supports(K, N) && act != ACT_PRELU && !has_res;
+}
+
+int s6_call_candidates(bool conv, bool gated, bool bf16, int planes, int M, int K, int N, int HW, int act, bool has_res,
+                       int res_first) {
+    bool thin, wide;
+    s6_extras(conv, gated, bf16, bf16 ? planes : 3, M, K, N, HW, act, has_res, res_first, &thin, &wide);
+    return (int)s6_candidates(M, K, N, thin, wide).size();
+}
+
 template <typename XT, int NP>
 static void s6_run_one(S6Table* tab, bool conv, bool gated, const XT* X, const unsigned short* W3, const float* bias,
                        const float* gate, const XT* R, XT* Y, int M, int K, int N, int HW, int act, const ConvGeom& g,
                        int res_first, hipStream_t s) {
     static const bool tune_env = !(getenv("DFD_S6_TUNE") && atoi(getenv("DFD_S6_TUNE")) == 0);
-    static const bool thin_env = !(getenv("DFD_S6_THIN") && atoi(getenv("DFD_S6_THIN")) == 0);
-    // pw8 takes the call when the whole weight matrix fits its LDS image, a 16-row tile never straddles two images (the
-    // gate row is block-uniform) and nothing but bias / activation / residual happens in the epilogue
-    const bool thin = thin_env && !conv && s8_supports(K, N) && (!gated || (HW % 16 == 0 && M % HW == 0)) && act != ACT_PRELU &&
-                      !(R && res_first);
-    static const bool wide_env = !(getenv("DFD_S6_WIDE") && atoi(getenv("DFD_S6_WIDE")) == 0);
-    const bool wide = wide_env && !conv && !gated && sizeof(XT) == 4 && NP == 3 && s9_supports(K, N) && act != ACT_PRELU && !R;
+    bool thin, wide;
+    s6_extras(conv, gated, sizeof(XT) == 2, NP, M, K, N, HW, act, R != nullptr, res_first, &thin, &wide);
     auto candidates = [&]() { return s6_candidates(M, K, N, thin, wide); };
     S6Tile tile;
     if (tab && tab->force >= 0) {
@@ -269,6 +301,7 @@ static void s6_run_one(S6Table* tab, bool conv, bool gated, const XT* X, const u
         }
         tile = make_tile(M, N, tile.kind, tile.wm, tile.wn, tile.mt, tile.nt, tile.ks);      // block counts for this call's M
     }
+    if (tab) { tab->last = tile; ++tab->dispatches; }
     s6_dispatch_any<XT, NP>(conv, gated, tile, X, W3, bias, gate, R, Y, M, K, N, HW, act, g, res_first, s);
 }
 
@@ -289,7 +322,7 @@ bool split_gemm_supports(int K, int N) { return K % 8 == 0 && K >= 16 && split_w
 
 template <typename XT>
 bool launch_pointwise_split(S6Table* tab, const XT* X, const unsigned short* W3, const float* bias, const float* gate,
-                            const XT* R, XT* Y, int M, int K, int N, int HW, int act, int planes, hipStream_t s) {
+                            const XT* R, XT* Y, int M, int K, int N, int HW, int act, int planes, hipStream_t s, int res_first) {
     const ConvGeom none{};
     if (HW <= 0) HW = 1;
     const long long chunk = s6_chunk_rows(M, (long long)K * (long long)sizeof(XT), gate ? HW : 1);
@@ -298,14 +331,14 @@ bool launch_pointwise_split(S6Table* tab, const XT* X, const unsigned short* W3,
         const int mc = (int)std::min<long long>(chunk, M - m0);
         s6_run_np<XT>(planes, tab, false, gate != nullptr, X + (size_t)m0 * K, W3, bias,
                       gate ? gate + (size_t)(m0 / HW) * K : nullptr, R ? R + (size_t)m0 * N : nullptr, Y + (size_t)m0 * N,
-                      mc, K, N, HW, act, none, 0, s);
+                      mc, K, N, HW, act, none, res_first ? 1 : 0, s);
     }
     return true;
 }
 template bool launch_pointwise_split<float>(S6Table*, const float*, const unsigned short*, const float*, const float*,
-                                            const float*, float*, int, int, int, int, int, int, hipStream_t);
+                                            const float*, float*, int, int, int, int, int, int, hipStream_t, int);
 template bool launch_pointwise_split<bf16_t>(S6Table*, const bf16_t*, const unsigned short*, const float*, const float*,
-                                             const bf16_t*, bf16_t*, int, int, int, int, int, int, hipStream_t);
+                                             const bf16_t*, bf16_t*, int, int, int, int, int, int, hipStream_t, int);
 
 template <typename XT>
 bool launch_conv_gemm_split(S6Table* tab, const XT* X, const unsigned short* W3, const float* bias, const XT* R,

@@ -779,7 +779,8 @@ __global__ __launch_bounds__(256, (2 * (WM * MT + WN * NT) * 16 * S6_ROWB <= 80 
 // ONCE per block; a wave then walks its 16-row tiles with NO barrier: the whole next tile (every K-step of its rows
 // and its residual fragment) is requested before the current tile is split and multiplied, so a wave has 2-9 KB in
 // flight all the time.  Products, their order and the epilogue arithmetic are pw6's (s6_products, the operations of
-// s6_epilogue): the output bits equal those of every other tile (tests/test_gemm_tiles_gpu.py walks it as a candidate).
+// s6_epilogue): the output bits equal those of every other tile (walked as a candidate by tests/test_gemm_direct_gpu.py
+// - single calls, ragged M, one and two gate rows per block - and by the network sweeps of tests/test_gemm_tiles_gpu.py).
 // STORES: an MFMA accumulator leaves lanes 0-15 with 16 different rows, so a store instruction of the plain epilogue
 // writes 16 B per lane at a row stride - measured, those stores ran at 2.3-4.1 TB/s-equivalent while the loads of the
 // same kernel stream at 6 TB/s (no-store build: 92 vs 125 us for K = 144, N = 24).  Here the finished tile goes through a
@@ -977,7 +978,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : NT * NK <= 10 ? 3 : 2)) voi
 // the launch).  Here a block keeps its 128 rows' split activations IN REGISTERS (MT = 2 row tiles x NKC K-steps x three
 // bf16 planes per wave) and walks ALL column blocks itself: the weight stream (the only thing that changes) runs through
 // the double-buffered LDS stage continuously across column blocks, the split happens once.  Products and epilogue are
-// pw6's (s6_products / s6_epilogue): identical bits, a candidate of the tile tests.  Measured (tuner, batch 256): K = 80,
+// pw6's (s6_products / s6_epilogue): identical bits - walked as a candidate by tests/test_gemm_direct_gpu.py (all three
+// instances, ragged M) and, now that dfd_gemm_tile_count() counts these extras, by the network sweeps.  Measured (tuner, batch 256): K = 80,
 // N = 480 40.2 -> 38.7 us, K = 112, N = 672 65.8 -> 60.9 us - the launch writes 96 / 135 MB and that is most of its time
 // (2.2 TB/s; MFMA work 18 us), the redundant splits were the smaller part.
 template <int NT, int NKC, bool PIPE, typename XT, int NP>
@@ -1061,6 +1063,10 @@ __global__ __launch_bounds__(256, 2) void pw9_kernel(const XT* __restrict__ X, c
         else if (act == ACT_RELU) {
             v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
         }
+        // s6_epilogue and pw8 always add the residual fragment, zeros when there is none: a -0 (swish below about -88, where
+        // the sigmoid underflows) leaves them as +0.  Without this add pw9 stored -0 there - equal, but not the same bits
+        // (tests/test_gemm_direct_gpu.py; x + 0.0 is no identity under IEEE rules, so the compiler keeps it)
+        v += (v4f){0.f, 0.f, 0.f, 0.f};
         if (n < N && m[mt] < M) st4(Y + (size_t)m[mt] * N + n, v);      // (non-temporal stores: measured, 1-2 us slower)
     };
     auto load_bias = [&](int nb, v4f (&bv)[NT]) {
@@ -1235,8 +1241,12 @@ void s6_dispatch(const S6Tile& t, const XT* X, const unsigned short* W3, const f
             // t.ks = blocks per CU the grid aims at; equal shares of the matrix' tiles, at most one image's worth (a block
             // stages two gate rows) and at least one tile per wave
             const int tpg = GATE ? HW / 16 : 1 << 30, ttot = (M + 15) / 16, nk = (K + S6_BK - 1) / S6_BK;
+            // (the image bound wins over the wave count: with fewer tiles per image than waves - HW < 16 waves - a block of
+            // `wm` tiles met three or more images and gave the third one the second one's gate row; found by
+            // tests/test_gemm_direct_gpu.py at HW = 16, no network has such a shape.  Waves without a tile just wait.)
             int tpb = (ttot + 256 * t.ks - 1) / (256 * t.ks);
-            tpb = tpb > tpg ? tpg : tpb < t.wm ? t.wm : tpb;
+            tpb = tpb < t.wm ? t.wm : tpb;
+            tpb = tpb > tpg ? tpg : tpb;
             const int nblk = (ttot + tpb - 1) / tpb;
 #define DFD_S8_LAUNCH(NTV, NKV, NWV)                                                                                 \
     hipLaunchKernelGGL((pw8_kernel<NTV, NKV, GATE, NWV, XT, NP>), dim3(nblk), dim3(NWV * 64), 0, s, X, W3, plane, Kp, bias, \
