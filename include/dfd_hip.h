@@ -304,6 +304,37 @@ int dfd_gradcam_nchw(dfd_handle* h, const float* nchw_host, int n, float* logits
 int dfd_gradcam_crops(dfd_handle* h, const uint8_t* bgr, int height, int width, int stride, const int32_t* xywh, int n,
                       int apply_clahe, float* logits_out, float* cam7_out, float* heat_out, uint8_t* overlay_out);
 
+/* The three Grad-CAM launches with every stage returned (tests/test_gradcam_stages_gpu.py): the same kernels and grids as
+ * the entry points above, on device buffers the call allocates itself.  All pointers are host memory.
+ *   start = DFD_GRADCAM_TAP_FROM_X: x (n,3,224,224) runs through the forward and the un-activated head GEMM as in
+ *     dfd_gradcam_nchw; z (n,49,1280; fp32, or bf16 bit patterns when the handle stores bf16 - z_bf16 is set on return),
+ *     fc1 (n,512) and fc2 (n,256) receive what they left (each may be NULL).
+ *   start = DFD_GRADCAM_TAP_FROM_Z: no forward; z (fp32, or uint16 bf16 bits with z_bf16 = 1, whatever the handle's
+ *     option), fc1 and fc2 are inputs; x is read only for the overlay and may be NULL without one.  The handle's own
+ *     fc1.w, fc2.w, fc3.w and head.b are used.
+ * Stage outputs, each may be NULL: D1 (n + GUARD, 512), G (n + GUARD, 1280), cam7 (n + GUARD, 49), heat (n,224,224),
+ * overlay (n,224,224,3).  The device buffers of D1, G and cam7 are pre-filled with DFD_GRADCAM_TAP_SENTINEL and returned
+ * whole, with DFD_GRADCAM_TAP_GUARD rows (one row block of the MLP-backward kernels) behind row n - 1: a store past a
+ * ragged batch shows as a changed guard, a missing store as a surviving sentinel.
+ * n outside 1..max_batch (DFD_ERR_ARG / DFD_ERR_CAPACITY) and null required pointers (DFD_ERR_ARG) fail without a launch. */
+#define DFD_GRADCAM_TAP_FROM_X 0
+#define DFD_GRADCAM_TAP_FROM_Z 1
+#define DFD_GRADCAM_TAP_GUARD 8
+#define DFD_GRADCAM_TAP_SENTINEL 0x7FC5A5A5u
+typedef struct dfd_gradcam_tap_params {
+    int32_t start, n, z_bf16, reserved;
+    const float* x;
+    void* z;
+    float* fc1;
+    float* fc2;
+    float* D1;
+    float* G;
+    float* cam7;
+    float* heat;
+    uint8_t* overlay;
+} dfd_gradcam_tap_params;
+int dfd_gradcam_tap(dfd_handle* h, dfd_gradcam_tap_params* p);
+
 /* compute_frequency_features, reference model.py:105-149: BGR (channels = 3) or gray (1) 8-bit
  * image -> gray -> cv2.resize 224x224 -> channel 0 = min-max-normalised log1p|fftshift(fft2)|,
  * channel 1 = min-max-normalised log1p|cv2.dct(gray/255)|.  out: (2,224,224) float32.  The model

@@ -73,6 +73,7 @@ SIGNATURES = {
                                           C.c_void_p]),
     "dfd_gradcam_crops": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dfd_gradcam_tap": (C.c_int, [C.c_void_p, C.c_void_p]),
     "dfd_frequency_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dfd_detect_faces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                    C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
@@ -213,6 +214,16 @@ class GemmTapParams(C.Structure):
                                           "W", "Cin", "ksize", "stride", "pad", "dil", "Ho", "Wo")] +
                 [("x_rows", C.c_int64)] + [(k, C.c_void_p) for k in ("X", "Wt", "bias", "gate", "R", "Y")] +
                 [("candidates", C.c_int32), ("launches", C.c_int32), ("tile", C.c_int32 * 6)])
+
+
+GRADCAM_TAP_GUARD = 8                # DFD_GRADCAM_TAP_GUARD: guard rows behind D1, G and cam7
+GRADCAM_TAP_SENTINEL = 0x7FC5A5A5    # DFD_GRADCAM_TAP_SENTINEL
+
+
+class GradcamTapParams(C.Structure):
+    """`dfd_gradcam_tap_params` (include/dfd_hip.h)"""
+    _fields_ = ([(k, C.c_int32) for k in ("start", "n", "z_bf16", "reserved")] +
+                [(k, C.c_void_p) for k in ("x", "z", "fc1", "fc2", "D1", "G", "cam7", "heat", "overlay")])
 
 
 class MtcnnParams(C.Structure):
@@ -1048,6 +1059,59 @@ class Handle:
                                                 int(apply_clahe), _ptr(lg), None if c7 is None else _ptr(c7), _ptr(heat),
                                                 None if ov is None else _ptr(ov)))
         return self._gradcam_result(lg, heat, ov, c7)
+
+    def gradcam_tap(self, x=None, z=None, fc1=None, fc2=None, heat: bool = True, overlay: bool = False, n: Optional[int] = None):
+        """The three Grad-CAM launches with every stage returned (dfd_gradcam_tap).  Start "x" (z is None): x
+        (n,3,224,224) runs through the forward as in `gradcam`.  Start "z": z (n,49,1280) float32, or uint16 bf16 bit
+        patterns, with fc1 (n,512) and fc2 (n,256) injected, no forward; x only for the overlay.  `n` overrides the batch
+        read from the arrays (the argument checks of the C entry).
+        -> dict(z, z_bf16, fc1, fc2, D1 (n,512), G (n,1280), cam7 (n,49), guard_D1 / guard_G / guard_cam7 (the
+        GRADCAM_TAP_GUARD rows behind them, uint32 bit patterns), heat, overlay (None when not asked for))"""
+        from_z = z is not None or x is None
+        p = GradcamTapParams()
+        keep = []
+
+        def arr(a, dtype, tail):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype)
+            if a.shape[1:] != tail:
+                raise ValueError(f"expected (n,) + {tail}, got {a.shape}")
+            keep.append(a)
+            return a
+
+        xa = arr(x, np.float32, (3, 224, 224))
+        if from_z:
+            zb = z is not None and np.asarray(z).dtype == np.uint16
+            za, f1, f2 = arr(z, np.uint16 if zb else np.float32, (49, 1280)), arr(fc1, np.float32, (512,)), arr(fc2, np.float32, (256,))
+            p.start, p.z_bf16 = 1, int(zb)
+            first = next((a for a in (za, f1, f2, xa) if a is not None), None)
+            m = int(n) if n is not None else (0 if first is None else first.shape[0])
+            if any(a is not None and a.shape[0] < m for a in (za, f1, f2, xa)):
+                raise ValueError("an input holds fewer than n rows")
+        else:
+            m = int(n) if n is not None else xa.shape[0]
+            if xa.shape[0] < m:
+                raise ValueError("x holds fewer than n crops")
+            # room for either storage type; trimmed to the handle's below
+            za, f1, f2 = np.zeros((max(m, 0), 49, 1280), np.float32), np.zeros((max(m, 0), 512), np.float32), np.zeros((max(m, 0), 256), np.float32)
+        p.n = m
+        rows = max(m, 0) + GRADCAM_TAP_GUARD
+        out = {"D1": np.zeros((rows, 512), np.uint32), "G": np.zeros((rows, 1280), np.uint32), "cam7": np.zeros((rows, 49), np.uint32)}
+        ht = np.zeros((max(m, 0), 224, 224), np.float32) if heat else None
+        ov = np.zeros((max(m, 0), 224, 224, 3), np.uint8) if overlay else None
+        for k, a in (("x", xa), ("z", za), ("fc1", f1), ("fc2", f2), ("D1", out["D1"]), ("G", out["G"]), ("cam7", out["cam7"]),
+                     ("heat", ht), ("overlay", ov)):
+            if a is not None:
+                setattr(p, k, a.ctypes.data)
+        self._check(self._lib.dfd_gradcam_tap(self._p, C.byref(p)))
+        if not from_z and p.z_bf16:
+            za = za.reshape(-1).view(np.uint16)[: m * 49 * 1280].reshape(m, 49, 1280).copy()
+        res = {"z": za, "z_bf16": bool(p.z_bf16), "fc1": f1, "fc2": f2, "heat": ht, "overlay": ov}
+        for k, a in out.items():
+            res[k] = a[:m].view(np.float32)
+            res["guard_" + k] = a[m:]
+        return res
 
     # -- frame forensics
     FORENSIC_KEYS = ("frequency", "noise", "ela", "edge", "color", "temporal")

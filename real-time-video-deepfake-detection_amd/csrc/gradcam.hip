@@ -298,6 +298,27 @@ __global__ __launch_bounds__(MAP_THREADS) void gradcam_map_kernel(const XT* __re
     }
 }
 
+// The three Grad-CAM launches on h->stream, as one function of device pointers (the product path and dfd_gradcam_tap
+// launch the same kernels with the same grids): z [n][49][1280] fp32 or - z_bf16 - bf16, fc1 [n][512] / fc2 [n][256] the
+// forward's post-ReLU activations, x the classifier input (read only for the overlay); D1 [n][512] and G [n][1280] are
+// work buffers, cam7 / heat / overlay the nullable outputs.  The weights are the handle's own.
+int gradcam_launch(dfd_handle* h, const void* z, bool z_bf16, const float* fc1, const float* fc2, const float* x, int n, float* D1,
+                   float* G, float* cam7, float* heat, uint8_t* overlay) {
+    const B0Plan& P = h->b0;
+    const unsigned row_blocks = (unsigned)((n + MB_ROWS - 1) / MB_ROWS);
+    hipLaunchKernelGGL(gradcam_mlp_d1_kernel, dim3(GC_F1 / MB_COLS, row_blocks), dim3(GC_THREADS), 0, h->stream, fc1, fc2,
+                       P.fc2_w, P.fc3_w, D1, n);
+    hipLaunchKernelGGL(gradcam_mlp_g_kernel, dim3(GC_C / MB_COLS, row_blocks), dim3(GC_THREADS), 0, h->stream, D1, P.fc1_w, G, n);
+    if (z_bf16)
+        hipLaunchKernelGGL(gradcam_map_kernel<bf16_t>, dim3((unsigned)n), dim3(MAP_THREADS), 0, h->stream,
+                           static_cast<const bf16_t*>(z), P.head_b, G, x, cam7, heat, overlay);
+    else
+        hipLaunchKernelGGL(gradcam_map_kernel<float>, dim3((unsigned)n), dim3(MAP_THREADS), 0, h->stream,
+                           static_cast<const float*>(z), P.head_b, G, x, cam7, heat, overlay);
+    DFD_HIP_TRY(h, hipGetLastError());
+    return DFD_OK;
+}
+
 // forward (logits into logits_dev) + the three Grad-CAM launches on h->stream; outputs are device pointers (nullable)
 int gradcam_run(dfd_handle* h, const float* x_dev, int n, float* logits_dev, float* cam7, float* heat, uint8_t* overlay) {
     if (n <= 0) return fail(h, DFD_ERR_ARG, "gradcam: batch must be positive");
@@ -305,21 +326,9 @@ int gradcam_run(dfd_handle* h, const float* x_dev, int n, float* logits_dev, flo
     int rc;
     if ((rc = b0_forward(h, x_dev, n, logits_dev, nullptr, nullptr))) return rc;
     if ((rc = b0_head_preact(h, n, h->expbuf))) return rc;           // expbuf: >= 112*112*96 floats per crop, dead here
-    const B0Plan& P = h->b0;
     float* G = h->dwbuf;                                               // dwbuf: >= 112*112*96 floats per crop, dead here
     float* D1 = h->dwbuf + (size_t)n * GC_C;
-    const unsigned row_blocks = (unsigned)((n + MB_ROWS - 1) / MB_ROWS);
-    hipLaunchKernelGGL(gradcam_mlp_d1_kernel, dim3(GC_F1 / MB_COLS, row_blocks), dim3(GC_THREADS), 0, h->stream, h->fc1, h->fc2,
-                       P.fc2_w, P.fc3_w, D1, n);
-    hipLaunchKernelGGL(gradcam_mlp_g_kernel, dim3(GC_C / MB_COLS, row_blocks), dim3(GC_THREADS), 0, h->stream, D1, P.fc1_w, G, n);
-    if (h->act_bf16)
-        hipLaunchKernelGGL(gradcam_map_kernel<bf16_t>, dim3((unsigned)n), dim3(MAP_THREADS), 0, h->stream,
-                           reinterpret_cast<const bf16_t*>(h->expbuf), P.head_b, G, x_dev, cam7, heat, overlay);
-    else
-        hipLaunchKernelGGL(gradcam_map_kernel<float>, dim3((unsigned)n), dim3(MAP_THREADS), 0, h->stream,
-                           h->expbuf, P.head_b, G, x_dev, cam7, heat, overlay);
-    DFD_HIP_TRY(h, hipGetLastError());
-    return DFD_OK;
+    return gradcam_launch(h, h->expbuf, h->act_bf16, h->fc1, h->fc2, x_dev, n, D1, G, cam7, heat, overlay);
 }
 
 // device staging of the host-side calls: heat in headbuf (49*1280 >= 224*224 floats per crop), cam7 and overlay in the
@@ -414,6 +423,76 @@ int dfd_gradcam_crops(dfd_handle* h, const uint8_t* bgr, int hh, int ww, int str
         if (kept) ++j;
     }
     return DFD_OK;
+}
+
+// test entry (include/dfd_hip.h): gradcam_launch on buffers of its own, every stage copied out, D1 / G / cam7 with
+// sentinel-filled guard rows behind row n - 1
+int dfd_gradcam_tap(dfd_handle* h, dfd_gradcam_tap_params* p) {
+    if (!h || !p) return DFD_ERR_ARG;
+    const bool from_z = p->start == DFD_GRADCAM_TAP_FROM_Z;
+    if (p->start != DFD_GRADCAM_TAP_FROM_X && !from_z) return fail(h, DFD_ERR_ARG, "gradcam_tap: start must be 0 (x) or 1 (z)");
+    const int n = p->n;
+    if (n <= 0 || n > h->max_batch) return fail(h, n <= 0 ? DFD_ERR_ARG : DFD_ERR_CAPACITY, "gradcam_tap: batch %d outside 1..%d", n, h->max_batch);
+    if (from_z ? (!p->z || !p->fc1 || !p->fc2 || (p->overlay && !p->x)) : !p->x)
+        return fail(h, DFD_ERR_ARG, "gradcam_tap: null input pointer");
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    const bool zb = from_z ? p->z_bf16 != 0 : h->act_bf16;
+    p->z_bf16 = zb ? 1 : 0;
+    const size_t rows = (size_t)n + DFD_GRADCAM_TAP_GUARD, zbytes = (size_t)n * GC_HW * GC_C * (zb ? 2 : 4);
+    // one allocation, 256-byte slots: the guarded stage outputs first, then the injected inputs of start "z"
+    size_t total = 0;
+    auto slot = [&](size_t bytes) { const size_t at = total; total += (bytes + 255) / 256 * 256; return at; };
+    const size_t od1 = slot(rows * GC_F1 * 4), og = slot(rows * GC_C * 4), oc = slot(rows * GC_HW * 4);
+    const size_t oh = slot(p->heat ? (size_t)n * GC_PIX * 4 : 0), oo = slot(p->overlay ? (size_t)n * GC_PIX * 3 : 0);
+    const size_t oz = slot(from_z ? zbytes : 0), o1 = slot(from_z ? (size_t)n * GC_F1 * 4 : 0), o2 = slot(from_z ? (size_t)n * GC_F2 * 4 : 0);
+    const size_t ox = slot(from_z && p->x ? (size_t)n * 3 * GC_PIX * 4 : 0);
+    char* base = nullptr;
+    DFD_HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&base), total + 256));
+    auto run = [&]() -> int {
+        float *D1 = reinterpret_cast<float*>(base + od1), *G = reinterpret_cast<float*>(base + og), *cam7 = reinterpret_cast<float*>(base + oc);
+        float* heat = p->heat ? reinterpret_cast<float*>(base + oh) : nullptr;
+        uint8_t* overlay = p->overlay ? reinterpret_cast<uint8_t*>(base + oo) : nullptr;
+        DFD_HIP_TRY(h, hipMemsetD32Async(base, (int)DFD_GRADCAM_TAP_SENTINEL, oh / 4, h->stream));     // D1, G and cam7 with their guard rows
+        const void* z;
+        const float *fc1, *fc2, *x;
+        int rc;
+        if (from_z) {
+            DFD_HIP_TRY(h, hipMemcpyAsync(base + oz, p->z, zbytes, hipMemcpyHostToDevice, h->stream));
+            DFD_HIP_TRY(h, hipMemcpyAsync(base + o1, p->fc1, (size_t)n * GC_F1 * 4, hipMemcpyHostToDevice, h->stream));
+            DFD_HIP_TRY(h, hipMemcpyAsync(base + o2, p->fc2, (size_t)n * GC_F2 * 4, hipMemcpyHostToDevice, h->stream));
+            if (p->x) DFD_HIP_TRY(h, hipMemcpyAsync(base + ox, p->x, (size_t)n * 3 * GC_PIX * 4, hipMemcpyHostToDevice, h->stream));
+            z = base + oz;
+            fc1 = reinterpret_cast<const float*>(base + o1);
+            fc2 = reinterpret_cast<const float*>(base + o2);
+            x = p->x ? reinterpret_cast<const float*>(base + ox) : nullptr;
+        } else {
+            // as gradcam_run: the forward, then the head GEMM once more without swish
+            DFD_HIP_TRY(h, hipMemcpyAsync(h->in_nchw, p->x, (size_t)n * 3 * GC_PIX * 4, hipMemcpyHostToDevice, h->stream));
+            if ((rc = b0_forward(h, h->in_nchw, n, h->logits, nullptr, nullptr))) return rc;
+            if ((rc = b0_head_preact(h, n, h->expbuf))) return rc;
+            z = h->expbuf;
+            fc1 = h->fc1;
+            fc2 = h->fc2;
+            x = h->in_nchw;
+        }
+        if ((rc = gradcam_launch(h, z, zb, fc1, fc2, x, n, D1, G, cam7, heat, overlay))) return rc;
+        if (!from_z) {
+            if (p->z) DFD_HIP_TRY(h, hipMemcpyAsync(p->z, z, zbytes, hipMemcpyDeviceToHost, h->stream));
+            if (p->fc1) DFD_HIP_TRY(h, hipMemcpyAsync(p->fc1, fc1, (size_t)n * GC_F1 * 4, hipMemcpyDeviceToHost, h->stream));
+            if (p->fc2) DFD_HIP_TRY(h, hipMemcpyAsync(p->fc2, fc2, (size_t)n * GC_F2 * 4, hipMemcpyDeviceToHost, h->stream));
+        }
+        if (p->D1) DFD_HIP_TRY(h, hipMemcpyAsync(p->D1, D1, rows * GC_F1 * 4, hipMemcpyDeviceToHost, h->stream));
+        if (p->G) DFD_HIP_TRY(h, hipMemcpyAsync(p->G, G, rows * GC_C * 4, hipMemcpyDeviceToHost, h->stream));
+        if (p->cam7) DFD_HIP_TRY(h, hipMemcpyAsync(p->cam7, cam7, rows * GC_HW * 4, hipMemcpyDeviceToHost, h->stream));
+        if (heat) DFD_HIP_TRY(h, hipMemcpyAsync(p->heat, heat, (size_t)n * GC_PIX * 4, hipMemcpyDeviceToHost, h->stream));
+        if (overlay) DFD_HIP_TRY(h, hipMemcpyAsync(p->overlay, overlay, (size_t)n * GC_PIX * 3, hipMemcpyDeviceToHost, h->stream));
+        DFD_HIP_TRY(h, stream_sync(h));
+        return DFD_OK;
+    };
+    const int rc = run();
+    if (rc != DFD_OK) hipStreamSynchronize(h->stream);
+    hipFree(base);
+    return rc;
 }
 
 }  // extern "C"

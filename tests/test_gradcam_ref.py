@@ -140,8 +140,8 @@ def test_reexports_and_abi_declarations(pkg, gc):
     assert dd.show_cam_on_image is gc.show_cam_on_image
     assert callable(dd.DeepfakeDetector.explain_face)
     hdr = open(os.path.join(ROOT, "include", "dfd_hip.h")).read()
-    for name in ("dfd_gradcam_nchw_device", "dfd_gradcam_nchw", "dfd_gradcam_crops"):
+    for name in ("dfd_gradcam_nchw_device", "dfd_gradcam_nchw", "dfd_gradcam_crops", "dfd_gradcam_tap"):
         assert re.search(r"\b%s\s*\(" % name, hdr), name
         assert name in pkg._lib.SIGNATURES, name
-    for meth in ("gradcam", "gradcam_device", "gradcam_crops"):
+    for meth in ("gradcam", "gradcam_device", "gradcam_crops", "gradcam_tap"):
         assert callable(getattr(pkg._lib.Handle, meth)), meth
