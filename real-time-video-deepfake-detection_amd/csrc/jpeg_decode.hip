@@ -384,7 +384,7 @@ static JpegGpuLayout jpeg_gpu_layout(const std::vector<Parsed>& P, const std::ve
     W.markers = take(4 * dsblk);
     W.segtab = take(4 * segs + 4);
     W.st = take(8 * chunks); W.en0 = take(8 * chunks); W.en1 = take(8 * chunks);
-    W.cnt = take(4 * chunks); W.dcs = take(12 * chunks); W.gfirst = take(4 * chunks); W.dcb = take(12 * chunks); W.err = take(chunks);
+    W.cnt = take(4 * chunks); W.dcs = take(12 * chunks); W.gfirst = take(4 * chunks); W.dcb = take(12 * chunks); W.err = take(4 * chunks);
     W.rs = take(8 * chunks);
     W.redone = take(4 * JG_MAX_ROUNDS);
     W.coef = take(W.coef_stride * 2 * (size_t)n);
@@ -596,7 +596,7 @@ struct JpegGpuJob {
         S.dcs = reinterpret_cast<int32_t*>(work + W.dcs);
         S.gfirst = reinterpret_cast<uint32_t*>(work + W.gfirst);
         S.dcb = reinterpret_cast<int32_t*>(work + W.dcb);
-        S.err = work + W.err;
+        S.err = reinterpret_cast<uint32_t*>(work + W.err);
         S.rs = reinterpret_cast<uint2*>(work + W.rs);
         S.redone = reinterpret_cast<uint32_t*>(work + W.redone);
         rounds = h->jpeg_rounds < 2 ? 2 : (h->jpeg_rounds > JG_MAX_ROUNDS ? JG_MAX_ROUNDS : h->jpeg_rounds);

@@ -454,6 +454,7 @@ inline int entropy_decode(dfd_handle* h, Parsed* P, int16_t* coef, const ScanLay
     struct Chunk {
         std::vector<int16_t> blocks;           // local blocks, 64 coefficients each (DC = difference)
         std::vector<uint64_t> end_bit;         // bit position after local block i
+        std::vector<size_t> failed;            // local blocks that did not decode (ascending)
         uint64_t start = 0, stop = 0;          // bit range [start, stop)
         bool overflow = false;
     };
@@ -490,7 +491,10 @@ inline int entropy_decode(dfd_handle* h, Parsed* P, int16_t* coef, const ScanLay
             int16_t* blk = K.blocks.data() + i * 64;
             if (!decode_block(c, &bp, nbits, *D, *A, blk)) {
                 if (t == 0) { bad.store(1); return; }              // the true stream is corrupt
-                memset(blk, 0, 128);                               // speculative garbage: carry on from here
+                memset(blk, 0, 128);                               // speculative garbage - or, once the chunk is in step with
+                try {                                              // the true stream, a corrupt block: the stitcher decides
+                    K.failed.push_back(i);
+                } catch (const std::bad_alloc&) { K.overflow = true; return; }
             }
             K.end_bit.push_back(bp);
             ++i;
@@ -557,6 +561,10 @@ inline int entropy_decode(dfd_handle* h, Parsed* P, int16_t* coef, const ScanLay
         if (match != (size_t)-1) {
             const size_t first = match + 1, avail = K.end_bit.size() - first;
             const size_t cnt = std::min(avail, L.total - G);
+            // from the matched boundary on the chunk's blocks ARE the true stream's: one of them that did not decode is a
+            // corrupt block of the file (in front of the boundary it was a wrong guess and means nothing)
+            const auto fb = std::lower_bound(K.failed.begin(), K.failed.end(), first);
+            if (fb != K.failed.end() && *fb < first + cnt) return fail(h, DFD_ERR_ARG, "decode_jpeg: corrupt entropy-coded data");
             if (cnt) {
                 pieces.push_back(Piece{K.blocks.data() + first * 64, cnt, G});
                 G += cnt;

@@ -15,7 +15,9 @@
 //      rounds count blocks and sum DC differences per component, nothing is written;
 //   3. jg_scan_kernel: per frame, prefix sums over the chunks give every chunk its first block index and its DC
 //      predictions; it also CHECKS the fixed point (start of chunk t == end of chunk t - 1, slot == block index mod
-//      blocks per MCU, block total == the frame's) - a frame that fails any check gets ONE more pass with the round
+//      blocks per MCU, block total >= the frame's: what the bits BEHIND the last block decode to is not looked at, and a
+//      chunk whose lane met an invalid code / index / DC category IN FRONT of it fails the frame - the lane says in
+//      which of its blocks) - a frame that fails any check gets ONE more pass with the round
 //      kernel that also iterates inside a launch (RST = true below; jpeg_decode.hip JpegGpuJob::finish): a scan whose
 //      codes nearly all have one length hardly resynchronises, and the true state then moves one chunk per launch.  A
 //      frame that fails again is decoded by the host path instead;
@@ -99,7 +101,8 @@ struct JgChunks {                                // per chunk, structure of arra
     int32_t* dcs;                                // [3] sum of their DC differences per component
     uint32_t* gfirst;                            // first block index (scan kernel)
     int32_t* dcb;                                // [3] DC prediction at the chunk's first block
-    uint8_t* err;                                // the chunk's decode met an invalid code / coefficient index
+    uint32_t* err;                               // complete blocks the chunk's decode had in front of its FIRST invalid code /
+                                                 // coefficient index / DC category (0xffffffff: it met none)
     uint2* rs;                                   // RST: x = blocks in front of the chunk's first segment crossing | crossed << 31 | a whole
                                                  // segment of another length than restart * bpm << 30, y = index of the segment entered there
     uint32_t* redone;                            // [JG_MAX_ROUNDS] lanes that decoded in round r (diagnostics)
@@ -343,10 +346,16 @@ __device__ __forceinline__ int jg_extend(uint32_t v, int s) {
 // RST: `seg` = the frame's segment table (nvalid entries written), segblocks = restart * bpm.  The lane carries the bit
 // position of the next segment start behind its own position; the test sits in the block-complete branch, the symbol
 // path is the one of RST = false.  !EMIT: dsum comes back as the sums since the LAST crossing, *rs_out as JgChunks::rs.
+// *bad_out: as JgChunks::err - WHERE the first defect lies, in blocks, so that the scan kernel can tell a defect inside a
+// block of the frame from the bits behind its last block.  The symbol path only raises a flag, as it always did; the
+// block-complete branch counts the blocks that end with the flag up - one add, no branch (with 64 lanes some lane
+// completes a block in nearly every step: whatever stands there is paid per symbol) - and the first of them is block
+// n - that count.  (A lane ends at a block boundary, or where the data ends - and a frame whose data ends inside a block
+// fails on its block count.)
 template <bool EMIT, bool RST>
 __device__ __forceinline__ void jg_decode(const JgLds& L, const uint32_t* __restrict__ ds, uint32_t nbits, uint32_t p0, int z0,
                                           uint32_t pend, uint32_t want, uint32_t* p_out, int* z_out, uint32_t* n_out, int (&dsum)[3],
-                                          bool* bad_out, int16_t* __restrict__ coef, uint32_t g0, const int (&pred0)[3],
+                                          uint32_t* bad_out, int16_t* __restrict__ coef, uint32_t g0, const int (&pred0)[3],
                                           const uint32_t* __restrict__ seg, uint32_t nvalid, uint32_t segblocks, uint2* rs_out) {
     const int bpm = L.fr.bpm, cws = L.fr.cw_shift;
     // slot -> DC table / AC table / component as nibbles of three registers: no LDS read on the symbol loop's critical path
@@ -368,6 +377,7 @@ __device__ __forceinline__ void jg_decode(const JgLds& L, const uint32_t* __rest
     uint32_t p = p0, pb = p0, n = 0;                              // pb: position of the last block boundary
     int z = z0, k = 0;
     bool bad = false;
+    uint32_t nbad = 0;                                             // blocks completed with `bad` up
     int pred[3] = {pred0[0], pred0[1], pred0[2]};
     // RST: entry sidx of the table is the first segment start behind p0 (0xffffffff: none, p + 7 never reaches it)
     uint32_t sidx = 0, nextseg = 0xffffffffu, rs_before = 0, rs_seg = 0, nlast = 0;
@@ -465,6 +475,7 @@ __device__ __forceinline__ void jg_decode(const JgLds& L, const uint32_t* __rest
             }
         }
         if (k >= 64) {                                             // block complete
+            nbad += bad ? 1u : 0u;
             k = 0;
             ++n;
             pb = p;
@@ -536,7 +547,7 @@ __device__ __forceinline__ void jg_decode(const JgLds& L, const uint32_t* __rest
     *p_out = pb;
     *z_out = z;
     *n_out = n;
-    *bad_out = bad;
+    *bad_out = nbad ? n - nbad : 0xffffffffu;
     if constexpr (RST && !EMIT) *rs_out = make_uint2(rs_before, rs_seg);
 }
 
@@ -606,7 +617,7 @@ __global__ __launch_bounds__(JG_CB) void jg_round_kernel(const uint8_t* __restri
         }
         uint32_t pe = start.x, n = 0;
         int ze = (int)start.y, dsum[3] = {0, 0, 0};
-        bool bad = false;
+        uint32_t bad = 0xffffffffu;
         const int zero3[3] = {0, 0, 0};
         if (start.x < b1)
             jg_decode<false, false>(L, reinterpret_cast<const uint32_t*>(ds_base + L.fr.ds_off), nbits, start.x, (int)start.y, b1, 0u, &pe, &ze,
@@ -616,7 +627,7 @@ __global__ __launch_bounds__(JG_CB) void jg_round_kernel(const uint8_t* __restri
         S.dcs[3 * gt] = dsum[0];
         S.dcs[3 * gt + 1] = dsum[1];
         S.dcs[3 * gt + 2] = dsum[2];
-        S.err[gt] = bad ? 1 : 0;
+        S.err[gt] = bad;
     } else {
         __shared__ uint2 ends[JG_CB];                                // the lanes' current end states
         const bool active = t < L.fr.nchunks && b0 < nbits;          // (the active chunks of a frame are its first ones)
@@ -640,7 +651,7 @@ __global__ __launch_bounds__(JG_CB) void jg_round_kernel(const uint8_t* __restri
                 if ((threadIdx.x & 63) == (unsigned)__ffsll((long long)m) - 1u) atomicAdd(&S.redone[round], (uint32_t)__popcll(m));
                 uint32_t pe = start.x, n = 0;
                 int ze = (int)start.y, dsum[3] = {0, 0, 0};
-                bool bad = false;
+                uint32_t bad = 0xffffffffu;
                 const int zero3[3] = {0, 0, 0};
                 uint2 rs = make_uint2(0u, 0u);
                 if (start.x < b1)
@@ -652,7 +663,7 @@ __global__ __launch_bounds__(JG_CB) void jg_round_kernel(const uint8_t* __restri
                 S.dcs[3 * gt] = dsum[0];
                 S.dcs[3 * gt + 1] = dsum[1];
                 S.dcs[3 * gt + 2] = dsum[2];
-                S.err[gt] = bad ? 1 : 0;
+                S.err[gt] = bad;
                 S.rs[gt] = rs;
             }
             ends[threadIdx.x] = end;
@@ -749,7 +760,9 @@ __global__ __launch_bounds__(1024) void jg_scan_kernel(JgFrame* __restrict__ F, 
             int bad = JG_OK;
             if (st.x != want.x || st.y != want.y) bad = JG_NOT_CONVERGED;
             else if ((uint32_t)excl[0] % (uint32_t)fr.bpm != st.y) bad = JG_SLOT;
-            else if (S.err[gt] && (uint32_t)excl[0] + (uint32_t)v[0] < (uint32_t)fr.total_blocks) bad = JG_BAD_CODE;   // (the padding bits after the last block decode to anything)
+            // a defect inside one of the frame's blocks, wherever its chunk lies (what follows the LAST block - padding bits,
+            // stray bytes in front of EOI - decodes to anything and is nobody's business: the host decoder does not look either)
+            else if (S.err[gt] != 0xffffffffu && (uint32_t)excl[0] + S.err[gt] < (uint32_t)fr.total_blocks) bad = JG_BAD_CODE;
             // the chunk's first crossing lies at the first block of the segment entered there; its later ones a whole segment on
             else if (fl && ((rs.x & 0x40000000u) || (uint32_t)excl[0] + (rs.x & 0x3fffffffu) != rs.y * segblocks)) atomicMax(&rstatus, (int)JG_RESTART);
             if (bad) atomicMax(&status, bad);
@@ -774,7 +787,7 @@ __global__ __launch_bounds__(1024) void jg_scan_kernel(JgFrame* __restrict__ F, 
     if (tid == 0) {
         int st = status;
         if (st == JG_OK) st = rstatus;
-        if (st == JG_OK && carry[0] != fr.total_blocks) st = JG_BLOCK_COUNT;
+        if (st == JG_OK && carry[0] < fr.total_blocks) st = JG_BLOCK_COUNT;   // (more: bits behind the last block made a block; emit stops at the total)
         F[f].status = st;
         F[f].blocks_found = (uint32_t)carry[0];
     }
@@ -791,15 +804,18 @@ __global__ __launch_bounds__(JG_CB) void jg_emit_kernel(const uint8_t* __restric
     const uint32_t t = (blockIdx.x - L.fr.cblk0) * JG_CB + threadIdx.x, gt = L.fr.chunk0 + t;
     const uint32_t nbits = L.fr.nbits, cbits = (uint32_t)L.fr.chunk_bytes * 8u;
     if (t >= L.fr.nchunks || t * cbits >= nbits) return;
-    const uint32_t want = S.cnt[gt];
+    // (blocks at or behind the frame's total are what the bits behind its last block happened to decode to: never written)
+    const uint32_t g0 = S.gfirst[gt], total = (uint32_t)L.fr.total_blocks;
+    if (g0 >= total) return;
+    const uint32_t want = S.cnt[gt] < total - g0 ? S.cnt[gt] : total - g0;
     if (want == 0) return;
     const uint2 start = S.st[gt];
     const int pred0[3] = {S.dcb[3 * gt], S.dcb[3 * gt + 1], S.dcb[3 * gt + 2]};
     uint32_t pe, n;
     int ze, dsum[3] = {0, 0, 0};
-    bool bad;
+    uint32_t bad;
     jg_decode<true, RST>(L, reinterpret_cast<const uint32_t*>(ds_base + L.fr.ds_off), nbits, start.x, (int)start.y, 0u, want, &pe, &ze, &n, dsum,
-                         &bad, coef, S.gfirst[gt], pred0, RST ? segtab + L.fr.seg_off : nullptr, jg_seg_valid(L.fr),
+                         &bad, coef, g0, pred0, RST ? segtab + L.fr.seg_off : nullptr, jg_seg_valid(L.fr),
                          L.fr.restart * (uint32_t)L.fr.bpm, nullptr);
 }
 

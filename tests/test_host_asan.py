@@ -123,6 +123,23 @@ def test_stream_corpus_decodes_clean_and_independent_of_chunking(driver, tmp_pat
             assert _fields(driver("jpeg", p, 7)) == one, (row.name, i)
 
 
+def test_damaged_corpus_is_judged_as_the_walker_judges_it(driver, tmp_path):
+    """every file of tests/jpeg_damage_cases.py - an unassigned code, a coefficient index past 63 or a DC category above 11
+    inside one block of the first, an interior or the last stretch of the scan, ZRLs that run past 63, zeroed padding bits,
+    bytes between the last block and EOI, cuts, seeded bit flips - through the stand-alone driver at 1 and 7 chunks: a clean exit, and the
+    status that the sequential walker (tests/jpeg_walker.py) asks for"""
+    import jpeg_damage_cases as D
+    import jpeg_walker as W
+
+    for k, case in enumerate(D.cases()):
+        p = tmp_path / f"case{k}.jpg"
+        p.write_bytes(case.data)
+        want = 0 if isinstance(W.walk(case.data), W.Ok) else -1
+        one = _fields(driver("jpeg", p, 1))
+        assert int(one["rc"]) == want, (case.id, one)
+        assert _fields(driver("jpeg", p, 7)) == one, case.id
+
+
 def test_truncations_and_header_edits_are_rejected_without_memory_errors(driver, tmp_path):
     data = _jpeg(_img(128, 128, 33), quality=90)
     sos = data.index(b"\xff\xda")

@@ -280,3 +280,50 @@ def test_truncated_jpeg_of_one_session_leaves_the_others_alone(pkg, b0_handle, m
         assert (sess.status_code, sess.get_json()) == (plain.status_code, plain.get_json())
         assert plain.status_code == 400
         c.post("/reset")
+
+
+def test_jpeg_damaged_inside_a_block_of_one_session_leaves_the_others_alone(pkg, b0_handle):
+    """as above with the device entropy decoder on and a frame whose LAST chunk holds a block with a coefficient index
+    past 63 (tests/jpeg_damage_cases.py): every block behind it stays aligned and the block total matches, so only the
+    decoders' own checks can tell.  The library refuses the part (-1) like the cut-off file; unlike that one libjpeg
+    decodes it (a warning), so - the rule of InvalidFrame: neither the device path nor Pillow - its session is answered
+    from Pillow's pixels, as the sender is without a session, never from coefficients the device decoder made up; the
+    other sessions get their answers"""
+    import jpeg_damage_cases as DC
+
+    D = pkg.deepfake_detection.DeepfakeDetector
+    work = {sid: [f if isinstance(f, bytes) else _jpeg(f) for f in frames] for sid, frames in _session_frames(4, 2).items()}
+    damaged, _ = DC.damaged_frame(_frame(405, 720, 91), 85, "index", "lastchunk", 256)
+    with pytest.raises(pkg._lib.DfdError) as e:
+        pkg._lib.jpeg_coefficients(damaged)
+    assert e.value.code == -1
+    decoded = DC.pillow(damaged)
+    lock = threading.Lock()
+    pool = pkg.sessions.SessionPool(handle=b0_handle, lock=lock)
+    got = {sid: [] for sid in list(work) + ["damaged"]}
+    b0_handle.set_option("jpeg_device_entropy", 1)
+    b0_handle.set_option("jpeg_chunk_bytes", 256)
+    try:
+        with pytest.raises(pkg._lib.DfdError) as e:                  # the library itself: refused, with the part's index
+            b0_handle.analyze_streams_batch([work["s0"][0], damaged], [7701, 7702], [False, False])
+        assert e.value.code == -1 and e.value.bad_index == 1
+        for s in (7701, 7702):
+            b0_handle.forensics_release(s)
+        for t in range(2):
+            with lock:                                               # one pass: the damaged JPEG among everyone's frames
+                futs = {sid: pool.submit(sid, [frames[t]]) for sid, frames in work.items()}
+                futs["damaged"] = pool.submit("damaged", [damaged])
+            for sid, fu in futs.items():
+                got[sid] += fu.result(timeout=120)
+        for sid, frames in work.items():
+            det = D(detection_threshold=0.55, handle=b0_handle)
+            assert got[sid] == [det.analyze_request(jpeg=f) for f in frames], sid
+            det.release()
+        det = D(detection_threshold=0.55, handle=b0_handle)
+        assert got["damaged"] == [det.analyze_request(decoded.copy()) for _ in range(2)]
+        det.release()
+    finally:
+        b0_handle.set_option("jpeg_device_entropy", 2)
+        b0_handle.set_option("jpeg_chunk_bytes", 512)
+        for sid in got:
+            pool.close(sid)
