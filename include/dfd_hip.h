@@ -146,6 +146,11 @@ long long dfd_gemm_chunk_rows(long long rows, long long row_bytes, long long row
  * Out: `candidates` = the number of instances "gemm_tile" indexes for this very call (its first launch), `tile` = the
  * instance that ran last (kind, wm, wn, mt, nt, ks; kind 0 pw6, 1 pw7, 2 pw8, 3 pw9), `launches` = kernel launches (the
  * 2^31-byte chunks of dfd_gemm_chunk_rows).
+ * A result too large to return whole (above 2^32 bytes of Y): n_ranges > 0 and y_ranges = n_ranges pairs of rows [lo, hi)
+ * - Y then receives the guard rows in front, the rows of the ranges in the order given, the guard rows behind, and
+ * nothing else.  Either way `y_sentinels` = elements of the WHOLE result (guards excluded) still at the sentinel and
+ * `y_digest` = the sum over its elements of bit pattern i x (2 i + 1) mod 2^64, computed on the device: two calls whose
+ * digests agree stored the same bits in the same places.
  * DFD_ERR_UNSUPPORTED, without a launch and with Y at the sentinel, for shapes the launchers refuse (K % 8, K < 16,
  * conv Cin % 32). */
 #define DFD_GEMM_TAP_GUARD 64
@@ -163,6 +168,9 @@ typedef struct dfd_gemm_tap_params {
     void* Y;
     int32_t candidates, launches;
     int32_t tile[6];
+    int32_t n_ranges, reserved2;
+    const int64_t* y_ranges;
+    uint64_t y_sentinels, y_digest;
 } dfd_gemm_tap_params;
 int dfd_gemm_tap(dfd_handle* h, dfd_gemm_tap_params* p);
 

@@ -213,7 +213,9 @@ class GemmTapParams(C.Structure):
     _fields_ = ([(k, C.c_int32) for k in ("conv", "bf16", "planes", "act", "res_first", "reserved", "M", "K", "N", "HW", "n_img", "H",
                                           "W", "Cin", "ksize", "stride", "pad", "dil", "Ho", "Wo")] +
                 [("x_rows", C.c_int64)] + [(k, C.c_void_p) for k in ("X", "Wt", "bias", "gate", "R", "Y")] +
-                [("candidates", C.c_int32), ("launches", C.c_int32), ("tile", C.c_int32 * 6)])
+                [("candidates", C.c_int32), ("launches", C.c_int32), ("tile", C.c_int32 * 6)] +
+                [("n_ranges", C.c_int32), ("reserved2", C.c_int32), ("y_ranges", C.c_void_p), ("y_sentinels", C.c_uint64),
+                 ("y_digest", C.c_uint64)])
 
 
 GRADCAM_TAP_GUARD = 8                # DFD_GRADCAM_TAP_GUARD: guard rows behind D1, G and cam7
@@ -444,18 +446,19 @@ class DeviceBuffer:
         handle._check(handle._lib.dfd_device_alloc(handle._p, self.nbytes, C.byref(p)))
         self.ptr = p.value
 
-    def upload(self, a: np.ndarray) -> "DeviceBuffer":
+    def upload(self, a: np.ndarray, offset: int = 0) -> "DeviceBuffer":
+        """host array -> the buffer, `offset` bytes in (a large buffer filled slab by slab)"""
         a = np.ascontiguousarray(a)
-        if a.nbytes > self.nbytes:
+        if offset < 0 or offset + a.nbytes > self.nbytes:
             raise ValueError("upload larger than buffer")
-        self._h._check(self._h._lib.dfd_memcpy_h2d(self._h._p, self.ptr, _ptr(a), a.nbytes))
+        self._h._check(self._h._lib.dfd_memcpy_h2d(self._h._p, self.ptr + int(offset), _ptr(a), a.nbytes))
         return self
 
-    def download(self, shape, dtype=np.float32) -> np.ndarray:
+    def download(self, shape, dtype=np.float32, offset: int = 0) -> np.ndarray:
         out = np.empty(shape, dtype=dtype)
-        if out.nbytes > self.nbytes:
+        if offset < 0 or offset + out.nbytes > self.nbytes:
             raise ValueError("download larger than buffer")
-        self._h._check(self._h._lib.dfd_memcpy_d2h(self._h._p, _ptr(out), self.ptr, out.nbytes))
+        self._h._check(self._h._lib.dfd_memcpy_d2h(self._h._p, _ptr(out), self.ptr + int(offset), out.nbytes))
         return out
 
     def free(self):
@@ -855,13 +858,15 @@ class Handle:
         return out[: cnt.value]
 
     def gemm_tap(self, x, w, bias, act=None, gate=None, res=None, res_first=False, hw=1, bf16=False, planes=3, conv=None,
-                 rows=None):
+                 rows=None, keep=None):
         """One split-GEMM call on host data (dfd_gemm_tap).  Pointwise: x (M, K), w (N, K), bias (N,) - (2N,) = bias then
         slopes with act "prelu" -, gate (ceil(M / hw), K), res (M, N); `rows` = M when x holds only a block of rows that the
         device operand repeats.  conv = dict(n_img, H, W, Cin, ksize, stride, pad, dil): x (n_img, H, W, Cin), w (N, ksize,
         ksize, Cin).  bf16: x, res and the result are uint16 bf16 bit patterns.
+        keep = [(lo, hi), ...]: only these row ranges come back (a result too large to return whole); y then holds them
+        one after the other.
         -> dict(rc (0, or GEMM_TAP_UNSUPPORTED for a refused shape), y (M, N), before / after (the guard rows), candidates,
-        launches, tile (kind, wm, wn, mt, nt, ks))"""
+        launches, tile (kind, wm, wn, mt, nt, ks), sentinels / digest (of the whole result, computed on the device))"""
         xt = np.uint16 if bf16 else np.float32
         x = np.ascontiguousarray(x, xt)
         w = np.ascontiguousarray(w, np.float32)
@@ -887,27 +892,34 @@ class Handle:
         p.N = n_out
         if w.size != n_out * k_in or b.size != (2 * n_out if p.act == 3 else n_out) or m <= 0:
             raise ValueError("w must hold N x K values, bias N (2N with prelu)")
-        keep = [x, w, b]
+        keep_alive = [x, w, b]
         p.X, p.Wt, p.bias = x.ctypes.data, w.ctypes.data, b.ctypes.data
         if gate is not None:
             g = np.ascontiguousarray(gate, np.float32)
             if conv is not None or g.shape != (-(-m // p.HW), k_in):
                 raise ValueError("gate must be (ceil(M / hw), K), pointwise only")
-            keep.append(g)
+            keep_alive.append(g)
             p.gate = g.ctypes.data
         if res is not None:
             r = np.ascontiguousarray(res, xt)
             if r.size != m * n_out:
                 raise ValueError("res must hold M x N values")
-            keep.append(r)
+            keep_alive.append(r)
             p.R = r.ctypes.data
-        y = np.zeros((m + 2 * GEMM_TAP_GUARD, n_out), xt)
+        back = m
+        if keep is not None:
+            rg = np.ascontiguousarray(keep, np.int64).reshape(-1, 2)
+            keep_alive.append(rg)
+            p.n_ranges, p.y_ranges = rg.shape[0], rg.ctypes.data
+            back = int((rg[:, 1] - rg[:, 0]).sum())
+        y = np.zeros((back + 2 * GEMM_TAP_GUARD, n_out), xt)
         p.Y = y.ctypes.data
         rc = self._lib.dfd_gemm_tap(self._p, C.byref(p))
         if rc not in (0, GEMM_TAP_UNSUPPORTED):
             self._check(rc)
-        return {"rc": rc, "y": y[GEMM_TAP_GUARD:GEMM_TAP_GUARD + m], "before": y[:GEMM_TAP_GUARD], "after": y[GEMM_TAP_GUARD + m:],
-                "candidates": int(p.candidates), "launches": int(p.launches), "tile": tuple(int(v) for v in p.tile)}
+        return {"rc": rc, "y": y[GEMM_TAP_GUARD:GEMM_TAP_GUARD + back], "before": y[:GEMM_TAP_GUARD], "after": y[GEMM_TAP_GUARD + back:],
+                "candidates": int(p.candidates), "launches": int(p.launches), "tile": tuple(int(v) for v in p.tile),
+                "sentinels": int(p.y_sentinels), "digest": int(p.y_digest)}
 
     def profile_begin(self):
         self._check(self._lib.dfd_b0_profile_begin(self._p))

@@ -23,6 +23,23 @@ __global__ __launch_bounds__(256) void fill_pattern_kernel(float* __restrict__ x
     x[i] = ((float)(v >> 8) * (1.0f / 16777216.0f) - 0.5f) * 4.0f;
 }
 
+// dfd_gemm_tap's view of a WHOLE result that is too large to return: out[0] += elements still at the sentinel, out[1] +=
+// sum of element i x (2 i + 1) mod 2^64 - position-sensitive (an odd multiplier is a bijection mod 2^64: a row written
+// to another place changes it) and, being a sum, independent of the order the threads arrive in
+template <typename T>
+__global__ __launch_bounds__(256) void tap_digest_kernel(const T* __restrict__ y, size_t count, T sentinel,
+                                                         unsigned long long* __restrict__ out) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    unsigned long long left = 0, sum = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+        const T v = y[i];
+        left += v == sentinel ? 1u : 0u;
+        sum += (unsigned long long)v * (2ull * i + 1ull);
+    }
+    atomicAdd(out, left);
+    atomicAdd(out + 1, sum);
+}
+
 int create_impl(dfd_handle* h, int device, const void* blob, size_t blob_len, int max_batch) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -297,6 +314,11 @@ int dfd_gemm_tap(dfd_handle* h, dfd_gemm_tap_params* p) {
     const int M = p->M, K = p->K, N = p->N, HW = conv ? 1 : (p->HW > 0 ? p->HW : 1);
     if (M <= 0 || K <= 0 || N <= 0 || K > (1 << 20) || N > (1 << 16) || p->x_rows < 0 || p->x_rows > M)
         return fail(h, DFD_ERR_ARG, "gemm_tap: bad M, K, N or x_rows");
+    if (p->n_ranges < 0 || (p->n_ranges > 0 && !p->y_ranges)) return fail(h, DFD_ERR_ARG, "gemm_tap: bad y_ranges");
+    for (int i = 0; i < p->n_ranges; ++i)
+        if (p->y_ranges[2 * i] < 0 || p->y_ranges[2 * i] >= p->y_ranges[2 * i + 1] || p->y_ranges[2 * i + 1] > M)
+            return fail(h, DFD_ERR_ARG, "gemm_tap: y_ranges[%d] is not a range of rows inside 0..%d", i, M);
+    p->y_sentinels = p->y_digest = 0;
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     const size_t esz = bf ? 2 : 4, G = DFD_GEMM_TAP_GUARD;
     const size_t xrows_host = conv ? 0 : (size_t)(p->x_rows > 0 ? p->x_rows : M);
@@ -304,15 +326,18 @@ int dfd_gemm_tap(dfd_handle* h, dfd_gemm_tap_params* p) {
     const size_t xhost = conv ? xcount : xrows_host * K;
     const size_t ycount = ((size_t)M + 2 * G) * N, nb = (size_t)(p->act == ACT_PRELU ? 2 * N : N);
     const size_t gcount = p->gate ? (size_t)((M + HW - 1) / HW) * K : 0;
+    // the launchers' rule (gemm_split.hip): a chunk is bounded by the largest of the X, Y and R rows (conv: images)
+    const long long row_bytes = conv ? std::max((long long)g.H * g.W * g.Cin, (long long)g.Ho * g.Wo * N) * (long long)esz
+                                     : (long long)std::max(K, N) * (long long)esz;
     const bool ok = split_gemm_supports(K, N) && !(conv && g.Cin % 32 != 0) &&
-                    s6_chunk_rows(conv ? p->n_img : M, conv ? (long long)g.H * g.W * g.Cin * (long long)esz : (long long)K * (long long)esz,
-                                  p->gate ? HW : 1) > 0;
+                    s6_chunk_rows(conv ? p->n_img : M, row_bytes, p->gate ? HW : 1) > 0;
     // one allocation, 256-byte slots: Y (guard rows, result, guard rows) first, then the operands
     size_t total = 0;
     auto slot = [&](size_t bytes) { const size_t at = total; total += (bytes + 255) / 256 * 256; return at; };
     const size_t oy = slot(ycount * esz);
     const size_t ox = slot(ok ? xcount * esz : 0), ow = slot(ok ? (size_t)N * K * 4 : 0), ow3 = slot(ok ? split_weights_count(N, K) * 6 : 0);
     const size_t ob = slot(ok ? nb * 4 : 0), og = slot(ok ? gcount * 4 : 0), orr = slot(ok && p->R ? (size_t)M * N * esz : 0);
+    const size_t od = slot(2 * sizeof(unsigned long long));
     char* base = nullptr;
     DFD_HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&base), total + 256));
     auto run = [&]() -> int {
@@ -335,7 +360,7 @@ int dfd_gemm_tap(dfd_handle* h, dfd_gemm_tap_params* p) {
             if (p->R) DFD_HIP_TRY(h, hipMemcpyAsync(base + orr, p->R, (size_t)M * N * esz, hipMemcpyHostToDevice, h->stream));
             launch_split_weights(dw, w3, N, K, h->stream, false);
             const long long before = s6_table_dispatches(h->gemm);
-            const long long chunk = conv ? M : s6_chunk_rows(M, (long long)K * (long long)esz, p->gate ? HW : 1);
+            const long long chunk = conv ? M : s6_chunk_rows(M, row_bytes, p->gate ? HW : 1);
             p->candidates = s6_call_candidates(conv, p->gate != nullptr, bf, p->planes, (int)std::min<long long>(chunk, M), K, N, HW, p->act,
                                                p->R != nullptr, p->res_first ? 1 : 0);
             bool launched;
@@ -356,8 +381,34 @@ int dfd_gemm_tap(dfd_handle* h, dfd_gemm_tap_params* p) {
             p->launches = (int)(s6_table_dispatches(h->gemm) - before);
             s6_table_last(h->gemm, p->tile);
         }
-        DFD_HIP_TRY(h, hipMemcpyAsync(p->Y, dy, ycount * esz, hipMemcpyDeviceToHost, h->stream));
+        // the whole result's digest, then the copy back: everything, or the guard rows and the requested ranges only
+        unsigned long long* dd = reinterpret_cast<unsigned long long*>(base + od);
+        unsigned long long digest[2] = {0, 0};
+        const size_t rcount = (size_t)M * N, row = (size_t)N * esz;
+        const unsigned dgrid = (unsigned)std::min<size_t>((rcount + 255) / 256, 4096);
+        DFD_HIP_TRY(h, hipMemsetAsync(dd, 0, sizeof digest, h->stream));
+        if (bf) hipLaunchKernelGGL(tap_digest_kernel<unsigned short>, dim3(dgrid), dim3(256), 0, h->stream, static_cast<const unsigned short*>(dy) + G * N,
+                                   rcount, (unsigned short)(DFD_GEMM_TAP_SENTINEL >> 16), dd);
+        else hipLaunchKernelGGL(tap_digest_kernel<unsigned>, dim3(dgrid), dim3(256), 0, h->stream, static_cast<const unsigned*>(dy) + G * N,
+                                rcount, (unsigned)DFD_GEMM_TAP_SENTINEL, dd);
+        DFD_HIP_TRY(h, hipMemcpyAsync(digest, dd, sizeof digest, hipMemcpyDeviceToHost, h->stream));
+        if (p->n_ranges == 0) {
+            DFD_HIP_TRY(h, hipMemcpyAsync(p->Y, dy, ycount * esz, hipMemcpyDeviceToHost, h->stream));
+        } else {
+            char* out = static_cast<char*>(p->Y);
+            const char* src = static_cast<const char*>(dy);
+            DFD_HIP_TRY(h, hipMemcpyAsync(out, src, G * row, hipMemcpyDeviceToHost, h->stream));
+            out += G * row;
+            for (int i = 0; i < p->n_ranges; ++i) {
+                const size_t lo = (size_t)p->y_ranges[2 * i], cnt = (size_t)p->y_ranges[2 * i + 1] - lo;
+                DFD_HIP_TRY(h, hipMemcpyAsync(out, src + (G + lo) * row, cnt * row, hipMemcpyDeviceToHost, h->stream));
+                out += cnt * row;
+            }
+            DFD_HIP_TRY(h, hipMemcpyAsync(out, src + (G + (size_t)M) * row, G * row, hipMemcpyDeviceToHost, h->stream));
+        }
         DFD_HIP_TRY(h, stream_sync(h));
+        p->y_sentinels = digest[0];
+        p->y_digest = digest[1];
         if (!ok) return fail(h, DFD_ERR_UNSUPPORTED, "gemm_tap: K=%d N=%d%s is not a split-GEMM shape", K, N, conv ? " (conv: Cin % 32)" : "");
         return DFD_OK;
     };

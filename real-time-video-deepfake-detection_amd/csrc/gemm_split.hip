@@ -198,8 +198,10 @@ int s6_max_candidates() {
 }
 
 // Rows of one kernel call: activations (and gates) are addressed with 32-bit byte offsets and sized with a
-// 32-bit num_records, so a call never spans 2^31 bytes of X.  Chunks are whole images (HW rows) so that the
-// gate index m / HW and the convolution's image index stay relative to the chunk base.
+// 32-bit num_records, so a call never spans 2^31 bytes of X - nor of Y or R, which pw8 addresses the same way (every
+// other instance indexes them with size_t): the callers pass the LARGEST row of the three, max(K, N) elements (a
+// convolution: the larger of an image's input and output), as row_bytes.  Chunks are whole images (HW rows) so that
+// the gate index m / HW and the convolution's image index stay relative to the chunk base.
 long long s6_chunk_rows(long long M, long long row_bytes, long long HW) {
     const long long lim = (1ll << 31) - 1;
     if (HW <= 0) HW = 1;
@@ -325,7 +327,7 @@ bool launch_pointwise_split(S6Table* tab, const XT* X, const unsigned short* W3,
                             const XT* R, XT* Y, int M, int K, int N, int HW, int act, int planes, hipStream_t s, int res_first) {
     const ConvGeom none{};
     if (HW <= 0) HW = 1;
-    const long long chunk = s6_chunk_rows(M, (long long)K * (long long)sizeof(XT), gate ? HW : 1);
+    const long long chunk = s6_chunk_rows(M, (long long)std::max(K, N) * (long long)sizeof(XT), gate ? HW : 1);
     if (chunk <= 0) return false;
     for (long long m0 = 0; m0 < M; m0 += chunk) {
         const int mc = (int)std::min<long long>(chunk, M - m0);
@@ -347,7 +349,8 @@ bool launch_conv_gemm_split(S6Table* tab, const XT* X, const unsigned short* W3,
     const int K = g.ksize * g.ksize * g.Cin;
     if (!split_gemm_supports(K, Cout)) return false;
     const long long in_img = (long long)g.H * g.W * g.Cin * (long long)sizeof(XT), out_rows = (long long)g.Ho * g.Wo;
-    const long long imgs = s6_chunk_rows(n_img, in_img, 1);        // "rows" = images of in_img bytes
+    const long long out_img = out_rows * Cout * (long long)sizeof(XT);
+    const long long imgs = s6_chunk_rows(n_img, std::max(in_img, out_img), 1);      // "rows" = images, of the larger of the two sizes
     if (imgs <= 0) return false;
     for (long long i0 = 0; i0 < n_img; i0 += imgs) {
         const int ni = (int)std::min<long long>(imgs, n_img - i0);

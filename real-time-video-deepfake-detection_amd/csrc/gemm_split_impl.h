@@ -1208,8 +1208,9 @@ inline S6Tile make_tile6(int M, int N, int mt, int nt, int ks = 1) { return make
     OP(2, 2, 1, 2) OP(2, 2, 1, 3) OP(2, 2, 1, 4) OP(2, 2, 1, 6) OP(2, 2, 2, 2) OP(2, 2, 2, 3)     \
     OP(2, 2, 2, 4) OP(2, 2, 2, 6) OP(2, 2, 4, 2) OP(2, 2, 4, 3)
 
-// one launch of tile `t`; the caller keeps every call below 2^31 bytes of activations (the kernels address X /
-// gate with 32-bit buffer offsets).  XT = activation storage (float / bf16_t), NP = weight planes used.
+// one launch of tile `t`; the caller keeps every call below 2^31 bytes of activations AND of output (the kernels address
+// X / gate with 32-bit buffer offsets, pw8 also Y / R: s6_chunk_rows with the largest of the three rows).
+// XT = activation storage (float / bf16_t), NP = weight planes used.
 template <bool CONV, bool GATE, typename XT, int NP>
 void s6_dispatch(const S6Tile& t, const XT* X, const unsigned short* W3, const float* bias,
                  const float* gate, const XT* R, XT* Y, int M, int K, int N, int HW, int act,

@@ -30,6 +30,9 @@ MEASURED on one MI355X, 164 calls and every candidate of each:
   run time: pointwise 0.12 s, pw8 0.63 s, pw9 0.24 s, gated 0.05 s, conv 0.04 s, bf16 0.03 s, exact 0.03 s (1.1 s in
   all); the call above 2^31 bytes 1.35 s (host inputs 0.21 s, the tap 0.01 s, host checks 1.12 s): tile pw6 4 x (1 x 1),
   2 launches, 0.23 of the float64 bar (1.13 x the yardstick), every row within 0.0052 of the (7K + 4) 2^-24 u bound.
+  the call above 2^32 bytes of OUTPUT (K = 16, N = 48, 22.4 M rows; the chunk is bounded by the largest of the X, Y and R
+  rows): 21 candidates (8 pw6, 5 pw7, 8 pw8), 3 launches each, rows and whole-result digest of every instance equal to the
+  heuristic tile's (pw6 4 x (1 x 3)), 0.10 of the float64 bar (0.31 x the yardstick); 4.4 s, the slowest call 1.1 s.
 """
 import time
 
@@ -204,4 +207,69 @@ def test_one_call_above_2g_takes_two_launches_and_addresses_every_row(pkg, b0_ha
         assert ratio <= 1.0, f"images {i0}..{i1}: |d| / u = {ratio * bound:.3e} > {bound:.3e}, first row {i0 * hw + int(np.argmax((d / u).max(axis=1)))}"
     print(f"\n[gemm_direct] chunked call: tile {r['tile']}, float64 bars {met}, worst |d| / ((7K + 4) 2^-24 u) {worst:.4f}; "
           f"host inputs {t1 - t0:.2f} s, tap {t2 - t1:.2f} s, checks {time.time() - t2:.2f} s")
+    assert met["ratio"] <= 1.0, met
+
+
+WIDE_K, WIDE_N, WIDE_M, WIDE_BLOCK, WIDE_EDGE = 16, 48, 22_400_000, 65536, 160
+
+
+def test_one_call_above_4g_of_output_is_chunked_by_its_largest_row_in_every_instance(pkg, b0_handle):
+    """Thin fp32 call with K < N: K = 16, N = 48, M = 22,400,000 rows (HW = 1: a row is an image) - 1.43 GB of X and
+    4.30 GB of Y, above 2^32 bytes on the OUTPUT side only.  pw8_kernel addresses Y with a 32-bit num_records and 32-bit
+    byte offsets; bounded by X alone this call was ONE launch, whose offsets wrap.  The launchers bound a chunk by the
+    largest of the X, Y and R rows: 11,184,810 rows (48 x 4 bytes each), 3 launches.  Every instance on the call's
+    candidate list runs, the eight pw8 instances included, selected through "gemm_tile".  Of each run come back the first
+    and the last 160 rows and the 160 rows on either side of both chunk borders (which are no multiples of 16: tiles
+    straddle them), plus, computed on the device over ALL rows, the count of elements still at the sentinel and a
+    position-sensitive digest.  The heuristic run's rows hold the float64 bars of this file; every forced run must
+    return the same rows AND the same digest bit for bit, with no sentinel left and the guards intact."""
+    h, t0 = b0_handle, time.time()
+    k, n, m = WIDE_K, WIDE_N, WIDE_M
+    assert m * n * 4 > 1 << 32 and m * k * 4 <= (1 << 31) - 1
+    chunk = pkg._lib.load().dfd_gemm_chunk_rows(m, max(k, n) * 4, 1)
+    assert chunk == ((1 << 31) - 1) // (n * 4) == 11_184_810 and -(-m // chunk) == 3 and chunk % 16 != 0
+    assert pkg._lib.load().dfd_gemm_chunk_rows(m, k * 4, 1) == m                      # the rule before: one launch
+    e = WIDE_EDGE
+    keep = [(0, e), (chunk - e, chunk + e), (2 * chunk - e, 2 * chunk + e), (m - e, m)]
+    rows = np.concatenate([np.arange(lo, hi) for lo, hi in keep])
+    rs = np.random.RandomState(17)
+    block = rs.standard_normal((WIDE_BLOCK, k)).astype(np.float32)
+    w = (rs.standard_normal((n, k)) / np.sqrt(k)).astype(np.float32)
+    bias = rs.standard_normal(n).astype(np.float32)
+    sub = G.Case("chunk", rows.size, k, n, 1)
+    ref = G.Reference(sub, {"x": block[rows % WIDE_BLOCK], "w": w, "bias": bias, "gate": None, "res": None})
+    fails, kinds, times = [], {}, []
+    try:
+        h.set_option("gemm_tile", -1)
+        base = h.gemm_tap(block, w, bias, rows=m, keep=keep)
+        c = base["candidates"]
+        runs = [(-1, base)]
+        for i in range(c):
+            h.set_option("gemm_tile", i)
+            t1 = time.time()
+            runs.append((i, h.gemm_tap(block, w, bias, rows=m, keep=keep)))
+            times.append(time.time() - t1)
+    finally:
+        h.set_option("gemm_tile", -1)
+    for i, r in runs:
+        fam = _family(r["tile"], k)[0]
+        kinds[fam[0]] = kinds.get(fam[0], 0) + 1
+        if r["rc"] != 0 or r["launches"] != 3:
+            fails.append(f"tile {i} {r['tile']}: rc {r['rc']}, {r['launches']} launches")
+            continue
+        outside, inside = _guards_ok(r)
+        if not outside:
+            fails.append(f"tile {i} {r['tile']} wrote into a guard row")
+        if not inside or r["sentinels"] != 0:
+            fails.append(f"tile {i} {r['tile']} left {r['sentinels']} elements of the result at the sentinel")
+        if not np.array_equal(_bits(r["y"]), _bits(base["y"])):
+            d = np.flatnonzero((_bits(r["y"]) != _bits(base["y"])).any(axis=1))
+            fails.append(f"tile {i} {r['tile']} differs from the heuristic {base['tile']} in {d.size} of the rows returned, first at row {rows[d[0]]}")
+        if r["digest"] != base["digest"]:
+            fails.append(f"tile {i} {r['tile']}: digest of all rows {r['digest']:#x} against the heuristic's {base['digest']:#x}")
+    met = ref.check(base["y"])
+    print(f"\n[gemm_direct] 4.3 GB of Y: {c} candidates {kinds}, heuristic tile {base['tile']}, {base['launches']} launches, float64 bars {met}; "
+          f"{time.time() - t0:.2f} s in all, {max(times):.2f} s the slowest forced call")
+    assert c >= 10 and kinds.get("pw8", 0) == 8, kinds
+    assert not fails, f"{len(fails)} failures, first: " + " | ".join(fails[:8])
     assert met["ratio"] <= 1.0, met
