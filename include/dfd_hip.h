@@ -770,6 +770,12 @@ int dfd_vote_allgather_waves(dfd_handle* h, const void* local_records, int waves
  * trainer, a second begin, max_n outside 2..256, dropout outside [0,1), n > max_n, and n < 2 in accumulate
  * (BatchNorm1d's batch statistics need two rows) are DFD_ERR_ARG; host memory running out is DFD_ERR_CAPACITY, a failed
  * device allocation DFD_ERR_HIP.  All pointers are host memory.
+ * dfd_head_train_begin also refuses, with DFD_ERR_ARG: a NaN or an infinity in any float field of the config; beta1 /
+ * beta2 outside [0, 1); eps or clip_norm <= 0; ema_decay, bn_momentum or label_smoothing outside [0, 1]; a negative
+ * focal_gamma; a negative weight_decay (as torch.optim.AdamW does).  Both ends of every closed range are legal, and
+ * any finite focal_alpha is (the reference's FocalLoss takes any).  dfd_head_train_apply refuses a NaN or negative lr;
+ * dfd_head_train_accumulate, _accumulate_trunk and _accumulate_block refuse a NaN lam or loss_scale and a lam outside
+ * [0, 1].  A refused call leaves the trainer (or, for begin, the handle without one) as it was.
  *
  * Dropout keep masks are a stateless hash of (seed, accumulate counter since begin, layer 0..2, row * width + col)
  * compared against floor(p * 2^32); head_training.dropout_keep_mask (Python, numpy) is its specification and the
@@ -804,7 +810,9 @@ int dfd_head_train_export(dfd_handle* h, int use_ema, dfd_head_params* out);
 /* test tap: read (set = 0) or replace (set = 1) the accumulated gradients; rm / rv are not used */
 int dfd_head_train_grads(dfd_handle* h, dfd_head_params* io, int set);
 /* test tap of the last accumulate: "mask0" [n][1280], "mask1" [n][512], "mask2" [n][256] (1.0 = kept), "z1" [n][512],
- * "z2" [n][256] (BatchNorm outputs before ReLU).  capacity in floats; too small: DFD_ERR_ARG */
+ * "z2" [n][256] (BatchNorm outputs before ReLU), "x0" [n][1280], "a1" [n][512], "a2" [n][256] (what the three
+ * Linear layers read: the features and relu(z) after dropout; a1 / a2 hold until the next eval call overwrites them).
+ * capacity in floats; too small: DFD_ERR_ARG */
 int dfd_head_train_tap(dfd_handle* h, const char* name, float* out, size_t capacity);
 /* folds BatchNorm into fc1 / fc2 (float64 on the host, rounded once: weights._fold) and overwrites the tensors the
  * inference plan reads, on the handle's stream; the cached bf16 splits of fc1.w / fc2.w are rebuilt in place.  From

@@ -737,7 +737,7 @@ class Handle:
         return out
 
     def head_train_tap(self, name: str, n: int) -> np.ndarray:
-        width = {"mask0": 1280, "mask1": 512, "mask2": 256, "z1": 512, "z2": 256}.get(name, 1280)   # unknown names: the library refuses
+        width = {"mask0": 1280, "mask1": 512, "mask2": 256, "z1": 512, "z2": 256, "a1": 512, "a2": 256}.get(name, 1280)   # unknown names: the library refuses
         wide = {"cz": (49, 1280), "b15.out": (49, 320), "b15.dout": (49, 320), "b15.ad": (49, 1152), "b15.dae": (49, 1152),
                 "b15.gate": (1152,)}
         out = np.empty((int(n),) + wide.get(name, (width,)), np.float32)

@@ -597,6 +597,17 @@ int dfd_head_train_begin(dfd_handle* h, const dfd_head_params* init, const dfd_h
           cfg->ema_decay >= 0.f && cfg->ema_decay <= 1.f && cfg->bn_momentum >= 0.f && cfg->bn_momentum <= 1.f &&
           cfg->label_smoothing >= 0.f && cfg->label_smoothing <= 1.f && cfg->focal_gamma >= 0.f))
         return fail(h, DFD_ERR_ARG, "head_train_begin: optimizer / loss setting out of range");
+    {   // every float field is a finite number (eps, clip_norm and focal_gamma have no upper end above, weight_decay and
+        // focal_alpha no range at all); torch.optim.AdamW refuses a negative weight_decay, FocalLoss takes any alpha
+        const struct { const char* name; float v; } fields[] = {
+            {"dropout", cfg->dropout}, {"beta1", cfg->beta1}, {"beta2", cfg->beta2}, {"eps", cfg->eps},
+            {"weight_decay", cfg->weight_decay}, {"focal_gamma", cfg->focal_gamma}, {"focal_alpha", cfg->focal_alpha},
+            {"label_smoothing", cfg->label_smoothing}, {"clip_norm", cfg->clip_norm}, {"ema_decay", cfg->ema_decay},
+            {"bn_momentum", cfg->bn_momentum}};
+        for (const auto& f : fields)
+            if (!std::isfinite(f.v)) return fail(h, DFD_ERR_ARG, "head_train_begin: %s %g is not a finite number", f.name, (double)f.v);
+        if (cfg->weight_decay < 0.f) return fail(h, DFD_ERR_ARG, "head_train_begin: weight_decay %g is negative", (double)cfg->weight_decay);
+    }
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     HeadTrainState* S = new (std::nothrow) HeadTrainState();
     if (!S) return fail(h, DFD_ERR_CAPACITY, "head_train_begin: out of host memory");
@@ -661,6 +672,8 @@ int dfd_head_train_accumulate(dfd_handle* h, const float* feat, int n, const flo
     if (!feat || !labels_a || !loss_out) return fail(h, DFD_ERR_ARG, "head_train_accumulate: null pointer");
     if (n < 2) return fail(h, DFD_ERR_ARG, "head_train_accumulate: %d rows; batch statistics need at least 2", n);
     if (n > S->max_n) return fail(h, DFD_ERR_ARG, "head_train_accumulate: %d rows exceed the trainer's max_n %d", n, S->max_n);
+    if (!head_train_mix_ok(lam, loss_scale))
+        return fail(h, DFD_ERR_ARG, "head_train_accumulate: lam %g outside [0, 1] or loss_scale %g not a number", (double)lam, (double)loss_scale);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     DFD_HIP_TRY(h, hipMemcpyAsync(S->feat, feat, (size_t)n * HT_IN * 4, hipMemcpyHostToDevice, s));
@@ -759,6 +772,9 @@ int dfd_head_train_tap(dfd_handle* h, const char* name, float* out, size_t capac
     else if (!strcmp(name, "mask2")) { mask = S->mask2; width = HT_H2; }
     else if (!strcmp(name, "z1")) { act = S->z1; width = HT_H1; }
     else if (!strcmp(name, "z2")) { act = S->z2; width = HT_H2; }
+    else if (!strcmp(name, "x0")) { act = S->x0; width = HT_IN; }
+    else if (!strcmp(name, "a1")) { act = S->a1; width = HT_H1; }
+    else if (!strcmp(name, "a2")) { act = S->a2; width = HT_H2; }
     else return fail(h, DFD_ERR_ARG, "head_train_tap: unknown tap '%s'", name);
     const size_t count = (size_t)S->last_n * width;
     if (capacity < count) return fail(h, DFD_ERR_ARG, "head_train_tap: '%s' holds %zu floats, capacity %zu", name, count, capacity);

@@ -660,6 +660,8 @@ int dfd_head_train_accumulate_block(dfd_handle* h, const float* rows, int n, con
     if (!rows || !labels_a || !loss_out) return fail(h, DFD_ERR_ARG, "head_train_accumulate_block: null pointer");
     if (n < 2) return fail(h, DFD_ERR_ARG, "head_train_accumulate_block: %d rows; batch statistics need at least 2", n);
     if (n > S->max_n) return fail(h, DFD_ERR_ARG, "head_train_accumulate_block: %d rows exceed the trainer's max_n %d", n, S->max_n);
+    if (!head_train_mix_ok(lam, loss_scale))
+        return fail(h, DFD_ERR_ARG, "head_train_accumulate_block: lam %g outside [0, 1] or loss_scale %g not a number", (double)lam, (double)loss_scale);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     HeadBlockState* K = S->block;
     hipStream_t s = h->stream;

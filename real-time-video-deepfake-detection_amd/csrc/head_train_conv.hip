@@ -493,6 +493,8 @@ int dfd_head_train_accumulate_trunk(dfd_handle* h, const float* trunk, int n, co
     if (!trunk || !labels_a || !loss_out) return fail(h, DFD_ERR_ARG, "head_train_accumulate_trunk: null pointer");
     if (n < 2) return fail(h, DFD_ERR_ARG, "head_train_accumulate_trunk: %d rows; batch statistics need at least 2", n);
     if (n > S->max_n) return fail(h, DFD_ERR_ARG, "head_train_accumulate_trunk: %d rows exceed the trainer's max_n %d", n, S->max_n);
+    if (!head_train_mix_ok(lam, loss_scale))
+        return fail(h, DFD_ERR_ARG, "head_train_accumulate_trunk: lam %g outside [0, 1] or loss_scale %g not a number", (double)lam, (double)loss_scale);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     HeadConvState* C = S->conv;
     hipStream_t s = h->stream;

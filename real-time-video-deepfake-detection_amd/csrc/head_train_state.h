@@ -39,6 +39,9 @@ struct HeadTrainState {
     HeadBlockState* block = nullptr;
 };
 
+// what every accumulate entry accepts for its two scalars: lam in [0, 1] and a loss_scale that is a number (NaN fails both)
+inline bool head_train_mix_ok(float lam, float loss_scale) { return lam >= 0.f && lam <= 1.f && loss_scale == loss_scale; }
+
 // ---- head_train.hip, for the conv stage
 // One train-mode forward / loss / backward on the n rows already in S->feat (device): uploads the labels, leaves the
 // loss in S->scalars[0] and the logits in S->logits, adds the head's gradients.  dfeat (device, [n][1280]) or null:

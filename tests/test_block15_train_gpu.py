@@ -25,6 +25,8 @@ and a remainder), 1813 (several chunks, ragged), 3136 (synthetic, a multiple of 
 The gradient of _bn2's bias is the column sum of dX15, which is zero in exact arithmetic (the conv stage's BatchNorm
 removes a constant per input channel): reference, yardstick and device all hold rounding noise there, and the bar
 compares the device's noise with the yardstick's as it compares everything else.
+
+Other values of lr_scale, bn_momentum, bn_eps and of the head's dropout: tests/test_head_train_config_gpu.py (stage cases).
 """
 import numpy as np
 import pytest

@@ -10,7 +10,8 @@ the device is looked at, at every forward of the case.  The seeds below were pic
 oracle-only condition.  In the multi-step case the float32 side of the condition is teacher-forced (`_five_steps`).
 
 Batch sizes: 2 (BatchNorm's minimum), 5 and 37 (tile and reduction tails in all three GEMM forms), 16 (one tile),
-64 (several tiles).
+64 (several tiles).  The other settings of dfd_head_config, n = 65 .. 256 and the new argument refusals:
+tests/test_head_train_config_gpu.py, on the case table of tests/head_train_cases.py.
 """
 import numpy as np
 import pytest

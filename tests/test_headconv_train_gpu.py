@@ -23,6 +23,8 @@ with a share <= 0.5 (30, 43, 55, 56), the one with the largest gate margin: 55 (
 asserted with the gate margin, before the device is looked at.
 
 m = 49 n rows: 98, 245 and 1813 are no multiples of 16 (row masking in both GEMMs), 784 is; 256 crops are max_n.
+
+Other values of lr_scale, bn_momentum, bn_eps and of the head's dropout: tests/test_head_train_config_gpu.py (stage cases).
 """
 import numpy as np
 import pytest
