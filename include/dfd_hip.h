@@ -959,6 +959,40 @@ int dfd_head_train_export_block(dfd_handle* h, int use_ema, dfd_mbconv_params* o
 /* test tap: read (set = 0) or replace (set = 1) the gradients of the trainable tensors; rm / rv are not used */
 int dfd_head_train_block_grads(dfd_handle* h, dfd_mbconv_params* io, int set);
 
+/* ---- frequency-domain analysis at any size -------------------------------------------------------
+ * The reference's GAN-artefact check (deepfake_detection.py:457-487) on face windows at their own h x w, and
+ * compute_frequency_features (model.py:105-149) at any even size: a rectangular, ragged, batched DFT and an orthonormal
+ * DCT-II on the fp32 MFMA.  Sides are 1..4096. */
+#define DFD_FREQ_MAX_SIDE 4096
+#define DFD_FREQ_MAX_FEATURE_SIZE 1024
+
+/* n windows boxes[n][4] = (x, y, w, h) of one uint8 frame [hh][ww][channels] (channels 3 = BGR, converted with cv2's
+ * integer gray formula; 1 = gray; stride in bytes); boxes == NULL: the whole image, n = 1.  out[n][2] = (high, total):
+ * the sum of |X| over the window's 2-D spectrum outside the central mask, and over all of it.  The mask is the
+ * reference's slice of the shifted spectrum: with m = min(h, w) / 4 and the signed frequency s = k (k < ceil(N / 2)) or
+ * k - N, a bin is masked when both of its s lie in [-m, m).  One launch set serves all windows (several when their work
+ * memory exceeds the "forensic_chunk_bytes" budget); a window gives the same bits alone and among others.
+ * A box that leaves the frame or has a side of 0: DFD_ERR_ARG; a side above 4096: DFD_ERR_UNSUPPORTED. */
+int dfd_frequency_domain(dfd_handle* h, const unsigned char* img, int hh, int ww, int stride, int channels,
+                         const int32_t* boxes, int n, double* out);
+/* the same on a frame that is resident on the device, on the handle's stream; boxes and out are host memory */
+int dfd_frequency_domain_device(dfd_handle* h, const unsigned char* img_dev, int hh, int ww, int stride, int channels,
+                                const int32_t* boxes, int n, double* out);
+/* test tap: the launches of dfd_frequency_domain on one gray window gray[hh][ww] (packed) -> the named buffer:
+ * "rows" the pass-1 output, complex float [ww][hh] (transform along x, stored transposed); "spectrum" complex float
+ * [ww][hh] ([kx][ky], the layout the kernels use); "mag" float [ww][hh], the magnitudes as summed; "sums" two doubles
+ * (high, total).  capacity in bytes. */
+int dfd_frequency_domain_tap(dfd_handle* h, const unsigned char* gray, int hh, int ww, const char* name, void* out,
+                             size_t capacity);
+/* dfd_frequency_features at any even size in 2..1024 (anything else: DFD_ERR_ARG) -> out [2][size][size]; the size-224
+ * entry above keeps its own kernels */
+int dfd_frequency_features_sized(dfd_handle* h, const unsigned char* img, int hh, int ww, int stride, int channels, int size,
+                                 float* out);
+/* test tap of the same launches: "gray" uint8 [size][size] after the resize; "spectrum" complex float [kx][ky],
+ * unshifted; "dct" float [ky][kx], the coefficients before log1p.  capacity in bytes. */
+int dfd_frequency_features_tap(dfd_handle* h, const unsigned char* img, int hh, int ww, int stride, int channels, int size,
+                               const char* name, void* out, size_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

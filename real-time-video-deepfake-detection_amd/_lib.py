@@ -75,6 +75,13 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dfd_gradcam_tap": (C.c_int, [C.c_void_p, C.c_void_p]),
     "dfd_frequency_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "dfd_frequency_domain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "dfd_frequency_domain_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                              C.c_void_p]),
+    "dfd_frequency_domain_tap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_void_p, C.c_size_t]),
+    "dfd_frequency_features_sized": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "dfd_frequency_features_tap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p,
+                                             C.c_void_p, C.c_size_t]),
     "dfd_detect_faces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                    C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "dfd_has_detector": (C.c_int, [C.c_void_p]),
@@ -1237,13 +1244,80 @@ class Handle:
         assert cnt.value == out.nbytes, (name, cnt.value, out.nbytes)
         return out[0] if (frame >= 0 or name == "twiddle") else out
 
-    def frequency_features(self, image) -> np.ndarray:
+    @staticmethod
+    def _as_gray_or_bgr(image) -> np.ndarray:
         a = np.ascontiguousarray(np.asarray(image))
         if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
             raise ValueError(f"expected (H,W,3) or (H,W) uint8 image, got {a.dtype} {a.shape}")
-        out = np.empty((2, 224, 224), np.float32)
-        self._check(self._lib.dfd_frequency_features(self._p, _ptr(a), a.shape[0], a.shape[1], a.strides[0],
-                                                     3 if a.ndim == 3 else 1, _ptr(out)))
+        return a
+
+    def frequency_features(self, image, size: int = 224, *, sized: bool = False) -> np.ndarray:
+        """(2, size, size) float32: size 224 on its own kernels (dfd_frequency_features); any other size - and 224 too
+        with `sized` - on the any-size kernels (dfd_frequency_features_sized: even sizes in 2..1024)"""
+        a = self._as_gray_or_bgr(image)
+        size = int(size)
+        if size == 224 and not sized:
+            out = np.empty((2, 224, 224), np.float32)
+            self._check(self._lib.dfd_frequency_features(self._p, _ptr(a), a.shape[0], a.shape[1], a.strides[0],
+                                                         3 if a.ndim == 3 else 1, _ptr(out)))
+            return out
+        out = np.empty((2, max(size, 0), max(size, 0)), np.float32)
+        self._check(self._lib.dfd_frequency_features_sized(self._p, _ptr(a), a.shape[0], a.shape[1], a.strides[0],
+                                                           3 if a.ndim == 3 else 1, size, _ptr(out)))
+        return out
+
+    def frequency_features_tap(self, image, size: int, name: str) -> np.ndarray:
+        """Test entry: a buffer of the dfd_frequency_features_sized launches - "gray" (size, size) uint8 after the resize,
+        "spectrum" (size, size) complex64 [kx][ky], unshifted, "dct" (size, size) float32 [ky][kx] before log1p"""
+        a = self._as_gray_or_bgr(image)
+        size = int(size)
+        dt = {"gray": np.uint8, "spectrum": np.complex64, "dct": np.float32}.get(name, np.uint8)
+        out = np.empty((max(size, 0), max(size, 0)), dt)
+        self._check(self._lib.dfd_frequency_features_tap(self._p, _ptr(a), a.shape[0], a.shape[1], a.strides[0],
+                                                         3 if a.ndim == 3 else 1, size, name.encode(), _ptr(out), out.nbytes))
+        return out
+
+    # -- the frequency-domain check on face windows (reference deepfake_detection.py:457-487)
+    @staticmethod
+    def _freq_boxes(boxes):
+        if boxes is None:
+            return None, 1
+        b = np.ascontiguousarray(np.asarray(boxes, np.int64).reshape(-1, 4))
+        if b.shape[0] < 1:
+            raise ValueError("boxes is empty")
+        if (np.abs(b) >= 2 ** 31).any():
+            raise ValueError("box coordinates do not fit 32 bits")
+        return np.ascontiguousarray(b.astype(np.int32)), b.shape[0]
+
+    def frequency_domain(self, image, boxes=None) -> np.ndarray:
+        """(n, 2) float64 = (high, total) per window (x, y, w, h) of `image` ((H,W,3) BGR or (H,W) gray uint8; boxes None:
+        the whole image): the sum of |fft2(gray window)| outside the reference's central mask, and over the whole
+        spectrum.  ONE library call for all windows (dfd_frequency_domain)."""
+        a = self._as_gray_or_bgr(image)
+        b, n = self._freq_boxes(boxes)
+        out = np.empty((n, 2), np.float64)
+        self._check(self._lib.dfd_frequency_domain(self._p, _ptr(a), a.shape[0], a.shape[1], a.strides[0],
+                                                   3 if a.ndim == 3 else 1, None if b is None else _ptr(b), n, _ptr(out)))
+        return out
+
+    def frequency_domain_device(self, frame_ptr: int, height: int, width: int, stride: int, channels: int, boxes=None) -> np.ndarray:
+        """`frequency_domain` on a frame that is resident on this handle's device (a DeviceBuffer's `ptr`)"""
+        b, n = self._freq_boxes(boxes)
+        out = np.empty((n, 2), np.float64)
+        self._check(self._lib.dfd_frequency_domain_device(self._p, C.c_void_p(frame_ptr), int(height), int(width), int(stride),
+                                                          int(channels), None if b is None else _ptr(b), n, _ptr(out)))
+        return out
+
+    def frequency_domain_tap(self, gray, name: str) -> np.ndarray:
+        """Test entry: a buffer of the dfd_frequency_domain launches on one (h, w) uint8 gray window - "rows" (w, h)
+        complex64 (pass 1: the transform along x, transposed), "spectrum" (w, h) complex64 [kx][ky], "mag" (w, h)
+        float32, "sums" (2,) float64 (high, total)"""
+        a = np.ascontiguousarray(np.asarray(gray))
+        if a.dtype != np.uint8 or a.ndim != 2:
+            raise ValueError(f"expected (H,W) uint8 gray window, got {a.dtype} {a.shape}")
+        hh, ww = a.shape
+        out = np.empty(2, np.float64) if name == "sums" else np.empty((ww, hh), np.float32 if name == "mag" else np.complex64)
+        self._check(self._lib.dfd_frequency_domain_tap(self._p, _ptr(a), hh, ww, name.encode(), _ptr(out), out.nbytes))
         return out
 
     # -- face detector

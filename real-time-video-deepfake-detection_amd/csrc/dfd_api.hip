@@ -120,6 +120,7 @@ void destroy_impl(dfd_handle* h) {
     ssd_destroy(h);
     mtcnn_destroy(h);
     freq_destroy(h);
+    freq_domain_destroy(h);
     s6_table_destroy(h->gemm);
     h->gemm = nullptr;
     for (void* p : h->owned)

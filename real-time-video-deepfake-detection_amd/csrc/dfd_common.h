@@ -21,6 +21,8 @@ struct ForensicState;   // forensic_api.hip
 void forensic_destroy(dfd_handle* h);
 struct FreqState;       // freq_kernels.hip
 void freq_destroy(dfd_handle* h);
+struct FreqDomainState; // freq_domain.hip
+void freq_domain_destroy(dfd_handle* h);
 struct SsdState;        // ssd_api.hip
 int ssd_init(dfd_handle* h);
 void ssd_destroy(dfd_handle* h);
@@ -127,6 +129,7 @@ struct dfd_handle {
     unsigned long long classifier_crops = 0;   // crops b0_forward has been asked for since dfd_create (dfd_classifier_crop_count)
     dfd::ForensicState* forensic = nullptr;   // per-stream temporal state + work buffers
     dfd::FreqState* freq = nullptr;           // compute_frequency_features tables + scratch
+    dfd::FreqDomainState* freq_domain = nullptr;   // frequency analysis at any size: tables per length + work buffers
     dfd::SsdState* ssd = nullptr;             // detector plan + workspace (null: blob has no detector)
     dfd::MtcnnState* mtcnn = nullptr;         // MTCNN cascade (null: blob has none)
     dfd::HaarState* haar = nullptr;           // Haar cascade (null: blob has none)

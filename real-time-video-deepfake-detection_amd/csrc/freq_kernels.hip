@@ -7,6 +7,7 @@
 #include <cmath>
 
 #include "dfd_common.h"
+#include "freq_domain.h"
 
 namespace dfd {
 
@@ -18,7 +19,11 @@ __global__ __launch_bounds__(256) void gray_resize_kernel(const uint8_t* __restr
     if (i >= sh * sw) return;
     const int y = i / sw, x = i % sw;
     const uint8_t* p = src + (size_t)y * sstride + (size_t)x * channels;
-    gray_full[i] = channels == 3 ? (uint8_t)((p[0] * 1868 + p[1] * 9617 + p[2] * 4899 + (1 << 13)) >> 14) : p[0];
+    gray_full[i] = channels == 3 ? bgr_to_gray_u8(p[0], p[1], p[2]) : p[0];
+}
+
+void launch_gray_full(const uint8_t* src, int sh, int sw, size_t sstride, int channels, uint8_t* gray_full, hipStream_t s) {
+    hipLaunchKernelGGL(gray_resize_kernel, dim3((sh * sw + 255) / 256), dim3(256), 0, s, src, sh, sw, sstride, channels, gray_full);
 }
 
 // one block per row: out[k][row] = sum_n in[row][n] * tw[(k*n) mod 224]   (complex; re-only input when im == null)

@@ -171,6 +171,46 @@ class DeepfakeDetector:
         except Exception:
             return raw_prob
 
+    FREQ_MAX_SIDE = 4096                    # DFD_FREQ_MAX_SIDE of the library
+
+    @staticmethod
+    def _frequency_verdict(high, total) -> float:
+        """reference :480-485, in double on the host"""
+        return 0.15 if float(high) / (float(total) + 1e-10) < 0.15 else 0.0
+
+    def analyze_frequency_domain(self, face_region):
+        """reference :457-487, the GAN-artefact check: 0.15 when less than 15 % of the magnitude of the crop's 2-D
+        spectrum (at the crop's own h x w) lies outside the central min(h, w) // 4 square, else 0.0.  The spectrum and
+        both sums are computed on the GPU (`dfd_frequency_domain`).  0.0 wherever the reference's bare `except` gives
+        it: an empty region, or an input that is not (h, w, 3).  Unlike the reference: a side
+        above 4096 or a non-uint8 array raises ValueError."""
+        face = np.asarray(face_region)
+        if face.dtype != np.uint8:
+            raise ValueError(f"analyze_frequency_domain takes a uint8 BGR crop, got {face.dtype}")
+        if face.ndim != 3 or face.shape[2] != 3 or face.shape[0] < 1 or face.shape[1] < 1:
+            return 0.0
+        if max(face.shape[:2]) > self.FREQ_MAX_SIDE:
+            raise ValueError(f"analyze_frequency_domain: crop {face.shape[1]} x {face.shape[0]}, sides above "
+                             f"{self.FREQ_MAX_SIDE} are not supported")
+        with self._lock:
+            high, total = self.handle.frequency_domain(np.ascontiguousarray(face))[0]
+        return self._frequency_verdict(high, total)
+
+    def analyze_frequency_domain_boxes(self, frame, boxes):
+        """`analyze_frequency_domain` of every box (x, y, w, h) of a BGR frame, from ONE library call -> list of 0.15 /
+        0.0.  Boxes must lie inside the frame (DfdError otherwise); no boxes: []."""
+        frame = np.asarray(frame)
+        if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+            raise ValueError("analyze_frequency_domain_boxes takes an (H, W, 3) uint8 BGR frame")
+        b = np.asarray(boxes, np.int64).reshape(-1, 4)
+        if b.shape[0] == 0:
+            return []
+        if b[:, 2:].max() > self.FREQ_MAX_SIDE:
+            raise ValueError(f"analyze_frequency_domain_boxes: sides above {self.FREQ_MAX_SIDE} are not supported")
+        with self._lock:
+            sums = self.handle.frequency_domain(np.ascontiguousarray(frame), b)
+        return [self._frequency_verdict(hi, tot) for hi, tot in sums]
+
     def apply_heuristics(self, fake_prob, face_region):
         """reference :489-502: +0.10 for crops under 80 px, clipped to [0,1]."""
         h, w = face_region.shape[:2]

@@ -10,6 +10,7 @@ path; `fit_head` trains the MLP head on the device with the backbone frozen
 from __future__ import annotations
 
 import logging
+import os
 from typing import Dict, Mapping, Optional
 
 import numpy as np
@@ -214,17 +215,34 @@ class DeepfakeEfficientNet:
         return self.net._conv_head
 
 
-def compute_frequency_features(image_bgr_or_rgb, size: int = 224, *, handle: Optional[Handle] = None):
-    """FFT log-magnitude + DCT features, (2, size, size) float32 in [0,1] (reference model.py:105-149),
-    computed on the GPU.  Only ``size=224`` (the one value the reference ever passes,
-    deepfake_detection.py:392) is built."""
+def check_frequency_size(size, any_size: bool = False) -> int:
+    """-> the size as an int, or ValueError: 224 always; with `any_size` every even size in 2..1024 (`cv2.dct` itself
+    refuses odd sizes)"""
+    size = int(size)
     if size != 224:
-        raise ValueError("compute_frequency_features is built for size=224 only")
+        if not any_size:
+            raise ValueError("compute_frequency_features is built for size=224 only (the one value the reference ever "
+                             "passes); any_size=True or DFD_FREQ_ANY_SIZE=1 admits every even size in 2..1024")
+        if size % 2 or not 2 <= size <= 1024:
+            raise ValueError(f"compute_frequency_features size {size}: supported are even sizes in 2..1024 "
+                             "(cv2.dct refuses odd sizes)")
+    return size
+
+
+def compute_frequency_features(image_bgr_or_rgb, size: int = 224, *, any_size: Optional[bool] = None,
+                               handle: Optional[Handle] = None):
+    """FFT log-magnitude + DCT features, (2, size, size) float32 in [0,1] (reference model.py:105-149),
+    computed on the GPU.  ``size=224`` (the one value the reference ever passes, deepfake_detection.py:392) runs its own
+    kernels; `any_size` (None: the environment variable DFD_FREQ_ANY_SIZE, default off) admits every even size in
+    2..1024, on the any-size kernels (`dfd_frequency_features_sized`)."""
+    if any_size is None:
+        any_size = os.environ.get("DFD_FREQ_ANY_SIZE", "").strip().lower() in ("1", "true", "yes", "on")
+    size = check_frequency_size(size, any_size)
     if handle is None:
         from . import runtime
 
         handle = runtime.default_handle()
-    return handle.frequency_features(image_bgr_or_rgb)
+    return handle.frequency_features(image_bgr_or_rgb, size)
 
 
-__all__ = ["DeepfakeEfficientNet", "DfdError", "compute_frequency_features"]
+__all__ = ["DeepfakeEfficientNet", "DfdError", "check_frequency_size", "compute_frequency_features"]
