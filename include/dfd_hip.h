@@ -598,6 +598,16 @@ int dfd_analyze_frame(dfd_handle* h, int stream_id, const uint8_t* bgr, int heig
  * upsampling + YCbCr->RGB on the device - bit-identical to libjpeg's defaults.  8-bit sequential Huffman JPEGs, gray
  * or YCbCr 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan, restart intervals; anything else returns
  * DFD_ERR_UNSUPPORTED (the host then decodes with its own library and calls dfd_analyze_frame).
+ * Supported besides, with option "jpeg_progressive" = 1 (default 0: as above; the environment variable
+ * DFD_JPEG_PROGRESSIVE sets the value a new handle starts with): 8-bit progressive Huffman files (SOF2) of the same
+ * colour spaces and samplings, any number of scans with tables and restart intervals redefined between them, whose scan
+ * script is in order (T.81 G.1.1.1.1) and COMPLETE - every coefficient of every component sent and refined to its last
+ * bit, so that libjpeg does no block smoothing.  Incomplete or out-of-order scripts, a quantisation table redefined between
+ * two scans, arithmetic, 12-bit and CMYK files stay DFD_ERR_UNSUPPORTED; a second SOF in such a file is DFD_ERR_ARG.  The option holds for every entry that takes JPEG bytes; the scans of progressive files are
+ * decoded by the host decoder (csrc/jpeg_progressive.h), in batch calls one file per pool thread - or, with option
+ * "jpeg_device_progressive" = 1 (default 0), in dfd_decode_jpeg_batch and the stream batch calls on the device
+ * (csrc/jpeg_gpu_progressive.h: the bytes cross PCIe, the scans run by dependency level, one lane per restart segment; a
+ * file the device reports a defect for is decoded again by the host decoder, which gives the status).
  * dfd_decode_jpeg: bgr_out may be NULL (size query through height / width; the frame stays on the device).
  * dfd_analyze_jpeg: dfd_analyze_frame without the raw upload - the decoded frame never visits the host. */
 /* The host half alone (no GPU needed; tests pin it against libjpeg through the oracle's IDCT): info[14] = width,
@@ -607,6 +617,11 @@ int dfd_analyze_frame(dfd_handle* h, int stream_id, const uint8_t* bgr, int heig
  * Errors of this function are reported through dfd_last_error(NULL). */
 int dfd_jpeg_coefficients(const uint8_t* jpeg, size_t len, int* info, uint16_t* qtables_out, int16_t* coef_out,
                           size_t capacity, size_t* count);
+/* dfd_jpeg_coefficients with flags: DFD_JPEG_ALLOW_PROGRESSIVE takes progressive files as option "jpeg_progressive"
+ * does for a handle's calls; flags = 0 is dfd_jpeg_coefficients. */
+#define DFD_JPEG_ALLOW_PROGRESSIVE 1u
+int dfd_jpeg_coefficients_ex(const uint8_t* jpeg, size_t len, unsigned flags, int* info, uint16_t* qtables_out, int16_t* coef_out,
+                             size_t capacity, size_t* count);
 int dfd_decode_jpeg(dfd_handle* h, const uint8_t* jpeg, size_t len, uint8_t* bgr_out, size_t capacity, int* height, int* width);
 /* n JPEGs of ONE size -> n packed BGR frames [n][H][W][3] (bgr_out may be NULL: the frames stay on the device).  Round 4:
  * in a batch the scans of restart-less files are entropy-decoded ON THE DEVICE (csrc/jpeg_gpu_entropy.h: a lane per

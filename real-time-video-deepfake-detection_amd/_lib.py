@@ -114,6 +114,8 @@ SIGNATURES = {
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "dfd_jpeg_coefficients": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.POINTER(C.c_size_t)]),
+    "dfd_jpeg_coefficients_ex": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.POINTER(C.c_size_t)]),
     "dfd_decode_jpeg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
                                   C.POINTER(C.c_int)]),
     "dfd_decode_jpeg_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
@@ -412,19 +414,30 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def jpeg_coefficients(data: bytes):
+JPEG_ALLOW_PROGRESSIVE = 1       # DFD_JPEG_ALLOW_PROGRESSIVE
+
+
+def jpeg_coefficients(data: bytes, progressive: bool = False):
     """Host half of the JPEG decoder (no GPU): -> dict(width, height, components, hmax, vmax, comps=[(bw, bh, tq)],
-    qtables (4,64) uint16, coef int16 flat).  Raises DfdError (code -7 = flavour not decoded on the device path)."""
+    qtables (4,64) uint16, coef int16 flat).  Raises DfdError (code -7 = flavour not decoded on the device path).
+    progressive: take complete progressive files too (dfd_jpeg_coefficients_ex with DFD_JPEG_ALLOW_PROGRESSIVE; what option
+    "jpeg_progressive" is to a handle's calls)"""
     lib = load()
     buf = (C.c_char * len(data)).from_buffer_copy(data)
     info = (C.c_int * 16)()
     cnt = C.c_size_t()
-    rc = lib.dfd_jpeg_coefficients(buf, len(data), info, None, None, 0, C.byref(cnt))
+    if progressive:
+        def call(*a):
+            return lib.dfd_jpeg_coefficients_ex(buf, len(data), JPEG_ALLOW_PROGRESSIVE, *a)
+    else:
+        def call(*a):
+            return lib.dfd_jpeg_coefficients(buf, len(data), *a)
+    rc = call(info, None, None, 0, C.byref(cnt))
     if rc != 0:
         raise DfdError(rc, (lib.dfd_last_error(None) or b"").decode())
     q = np.zeros((4, 64), np.uint16)
     coef = np.zeros(cnt.value, np.int16)
-    rc = lib.dfd_jpeg_coefficients(buf, len(data), info, _ptr(q), _ptr(coef), coef.size, C.byref(cnt))
+    rc = call(info, _ptr(q), _ptr(coef), coef.size, C.byref(cnt))
     if rc != 0:
         raise DfdError(rc, (lib.dfd_last_error(None) or b"").decode())
     n = info[2]

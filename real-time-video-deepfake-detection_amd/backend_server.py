@@ -7,7 +7,9 @@ frame, 429 from the 100 ms rate limiter, 500 with ``{'error': ...}`` for anythin
 per-request work is `DeepfakeDetector.analyze_request` (one GPU call).  Differences: sequential-Huffman
 JPEGs (what the extension sends) are decoded on the GPU from the request bytes (dfd_analyze_jpeg: entropy decoding
 on the host, IDCT / upsampling / colour on the device, bit-identical to libjpeg) and everything else with
-Pillow (cv2 is not a dependency here); ``POST /analyze_batch`` takes several ``frame`` parts of one stream in one
+Pillow (cv2 is not a dependency here; with ``DFD_JPEG_PROGRESSIVE=1`` in the environment when the handle is made,
+complete progressive JPEGs - what mozjpeg and most web pipelines write - are decoded by the library too instead of by
+Pillow); ``POST /analyze_batch`` takes several ``frame`` parts of one stream in one
 request; CORS headers are added by hand (no
 flask_cors), and the rate limiter and detector are guarded by locks (the reference shares them
 unsynchronised across Flask's worker threads, :57,62-80,275).

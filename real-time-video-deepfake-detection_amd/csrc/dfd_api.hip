@@ -63,6 +63,7 @@ int create_impl(dfd_handle* h, int device, const void* blob, size_t blob_len, in
     if (const char* e = getenv("DFD_SPLIT_GEMM")) h->split_gemm = atoi(e) != 0;
     if (const char* e = getenv("DFD_BF16_ACTIVATIONS")) h->act_bf16 = atoi(e) != 0;
     if (const char* e = getenv("DFD_JPEG_DEVICE_RESTART")) h->jpeg_device_restart = atoi(e) != 0;
+    if (const char* e = getenv("DFD_JPEG_PROGRESSIVE")) h->jpeg_progressive = atoi(e) != 0;
     h->gemm = s6_table_create();
     if (!h->gemm) return fail(h, DFD_ERR_ARG, "out of host memory");
     DFD_HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
@@ -203,6 +204,8 @@ int dfd_set_option(dfd_handle* h, const char* name, int value) {
     if (strcmp(name, "gemm_tile") == 0) { s6_table_set_force(h->gemm, value); return DFD_OK; }
     if (strcmp(name, "jpeg_device_entropy") == 0) { h->jpeg_device_entropy = value < 0 ? 0 : value; return DFD_OK; }
     if (strcmp(name, "jpeg_device_restart") == 0) { h->jpeg_device_restart = value != 0; return DFD_OK; }
+    if (strcmp(name, "jpeg_progressive") == 0) { h->jpeg_progressive = value != 0; return DFD_OK; }
+    if (strcmp(name, "jpeg_device_progressive") == 0) { h->jpeg_device_progressive = value != 0; return DFD_OK; }
     if (strcmp(name, "jpeg_rounds") == 0) { h->jpeg_rounds = value; return DFD_OK; }
     if (strcmp(name, "jpeg_chunk_bytes") == 0) {
         if (value < 256 || value > (1 << 20) || (value & (value - 1))) return fail(h, DFD_ERR_ARG, "jpeg_chunk_bytes: a power of two in 256 .. 2^20");

@@ -167,6 +167,10 @@ struct dfd_handle {
                                          // 1 MiB of scan data per call (below that the host pool is quicker), 1 = always, 0 = never
     int jpeg_device_restart = 0;         // 1 = files with restart intervals are eligible for that decoder too (option "jpeg_device_restart",
                                          // initial value from DFD_JPEG_DEVICE_RESTART); 0 = they take the host decoder
+    int jpeg_progressive = 0;            // 1 = progressive (SOF2) files are decoded (option "jpeg_progressive", initial value from
+                                         // DFD_JPEG_PROGRESSIVE); 0 = DFD_ERR_UNSUPPORTED as for every other flavour
+    int jpeg_device_progressive = 0;     // batch calls: 1 = the scans of progressive files are decoded on the device (jpeg_gpu_progressive.h,
+                                         // option "jpeg_device_progressive"); 0 = by the host pool
     int jpeg_rounds = 16;                // rounds of that decoder's fixed-point iteration (option "jpeg_rounds", 2 .. 32; converged rounds cost ~nothing)
     int jpeg_chunk_bytes = 512;          // bytes of de-stuffed scan per lane of that decoder (option "jpeg_chunk_bytes", >= 256, % 4)
     unsigned long long jpeg_frames_device = 0, jpeg_frames_host = 0;   // frames of batch calls decoded there / by the host decoder

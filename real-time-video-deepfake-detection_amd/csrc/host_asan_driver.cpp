@@ -6,6 +6,9 @@
 // the product and never run on the GPU box (GPU sanitizers are not available there; this file launches nothing).
 //
 //   host_asan_driver jpeg  FILE [CHUNKS]   -> "rc=<status> count=<coefficients> hash=<fnv1a of info + tables + coefficients>"
+//   host_asan_driver pjpeg FILE            -> the same with DFD_JPEG_ALLOW_PROGRESSIVE: progressive files go through the parser's
+//                                             scan script checks and the scan decoders of jpeg_progressive.h
+//   host_asan_driver pjpegfuzz FILE SEED N -> jpegfuzz with that flag
 //   host_asan_driver jpegfuzz FILE SEED N  -> N seeded mutations of FILE (byte flips, truncations, marker-length edits) in
 //                                             one process: "ok=<decoded> rejected=<errors>"; any memory error aborts
 //   host_asan_driver blobfuzz FILE SEED N  -> the same for the weights blob's table
@@ -62,16 +65,17 @@ int main(int argc, char** argv) {
     const std::vector<uint8_t> file = slurp(argv[2]);
     std::vector<uint8_t> data(file.begin(), file.end());
     data.shrink_to_fit();
-    if (cmd == "jpeg") {
+    const unsigned jflags = (cmd == "pjpeg" || cmd == "pjpegfuzz") ? DFD_JPEG_ALLOW_PROGRESSIVE : 0u;
+    if (cmd == "jpeg" || cmd == "pjpeg") {
         if (argc > 3) setenv("DFD_JPEG_CHUNKS", argv[3], 1);
         int info[16] = {0};
         uint16_t q[4 * 64] = {0};
         size_t count = 0;
-        int rc = dfd_jpeg::coefficients(data.data(), data.size(), info, q, nullptr, 0, &count);
+        int rc = dfd_jpeg::coefficients(data.data(), data.size(), info, q, nullptr, 0, &count, jflags);
         uint64_t h = 1469598103934665603ull;
         if (rc == 0) {
             std::vector<int16_t> coef(count);
-            rc = dfd_jpeg::coefficients(data.data(), data.size(), info, q, coef.data(), coef.size(), &count);
+            rc = dfd_jpeg::coefficients(data.data(), data.size(), info, q, coef.data(), coef.size(), &count, jflags);
             h = fnv(h, info, sizeof info);
             h = fnv(h, q, sizeof q);
             h = fnv(h, coef.data(), coef.size() * 2);
@@ -79,7 +83,7 @@ int main(int argc, char** argv) {
         printf("rc=%d count=%zu hash=%016llx\n", rc, count, (unsigned long long)h);
         return 0;
     }
-    if ((cmd == "jpegfuzz" || cmd == "blobfuzz") && argc >= 5) {
+    if ((cmd == "jpegfuzz" || cmd == "pjpegfuzz" || cmd == "blobfuzz") && argc >= 5) {
         uint64_t st = strtoull(argv[3], nullptr, 10) * 2654435761ull + 88172645463325252ull;
         auto rnd = [&]() { st ^= st << 13; st ^= st >> 7; st ^= st << 17; return st; };
         const int N = atoi(argv[4]);
@@ -97,12 +101,12 @@ int main(int argc, char** argv) {
                 m[rnd() % span] = (uint8_t)(kind == 3 ? 0xFF : rnd());
             }
             m.shrink_to_fit();
-            if (cmd == "jpegfuzz") {
+            if (cmd == "jpegfuzz" || cmd == "pjpegfuzz") {
                 int info[16];
                 uint16_t q[256];
                 size_t count = 0;
                 if (it & 1) setenv("DFD_JPEG_CHUNKS", (it & 2) ? "7" : "64", 1); else unsetenv("DFD_JPEG_CHUNKS");
-                int rc = dfd_jpeg::coefficients(m.data(), m.size(), info, q, nullptr, 0, &count);
+                int rc = dfd_jpeg::coefficients(m.data(), m.size(), info, q, nullptr, 0, &count, jflags);
                 rc == 0 ? ++ok : ++bad;
             } else {
                 std::map<std::string, dfd::Tensor> t;

@@ -15,8 +15,12 @@
 //
 // Supported: what browsers and cv2.imencode write - 8-bit baseline (SOF0) or extended-sequential Huffman (SOF1),
 // gray or YCbCr with 4:4:4 / 4:2:2 (h2v1) / 4:2:0 (h2v2) sampling, one interleaved scan, restart intervals.
-// Anything else (progressive, arithmetic, CMYK, 12-bit, multi-scan) returns DFD_ERR_UNSUPPORTED and the host
-// keeps its own decoder for it (backend_server.decode_image).
+// With option "jpeg_progressive" = 1 also 8-bit progressive files (SOF2) of the same colour spaces and samplings whose
+// scan script is in order and complete (jpeg_entropy.h parse_headers; the scans run on the host, jpeg_progressive.h, or
+// for a batch with option "jpeg_device_progressive" = 1 on the device, jpeg_gpu_progressive.h).
+// Anything else (progressive while the option is off, incomplete progressive scripts, arithmetic, CMYK, 12-bit,
+// sequential multi-scan) returns DFD_ERR_UNSUPPORTED and the host keeps its own decoder for it
+// (backend_server.decode_image).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -37,6 +41,7 @@ using namespace dfd;
 
 #include "jpeg_entropy.h"
 #include "jpeg_gpu_entropy.h"
+#include "jpeg_gpu_progressive.h"
 
 using namespace dfd_jpeg;
 using namespace dfd_jpeg_gpu;
@@ -323,7 +328,7 @@ static int jpeg_pinned(dfd_handle* h, size_t bytes) {
 // runtime staged 6 MB through its own bounce buffer first).
 int jpeg_decode_to_frame(dfd_handle* h, const uint8_t* jpeg, size_t len, int* hh, int* ww) {
     Parsed P;
-    int rc = parse_headers(h, jpeg, len, &P);
+    int rc = parse_headers(h, jpeg, len, &P, h->jpeg_progressive != 0);
     if (rc) return rc;
     ScanLayout L;
     scan_layout(&P, &L);
@@ -402,6 +407,7 @@ static bool jpeg_gpu_batch_ok(const dfd_handle* h, const std::vector<Parsed>& P,
     for (int i = 0; i < n; ++i) scan_total += (size_t)(P[i].end - P[i].scan) + 65536 + 64 * (size_t)h->jpeg_chunk_bytes;
     if (scan_total >= ((size_t)1 << 31) || (size_t)n * (L[0].total * 64 + 256) >= ((size_t)1 << 31)) return false;
     for (int i = 0; i < n; ++i) {
+        if (P[i].progressive) return false;                         // the scans of a progressive file run on the host
         if (!jg_supported(P[i], L[i], h->jpeg_device_restart != 0)) return false;
         if (P[i].ncomp != P[0].ncomp || P[i].hmax != P[0].hmax || P[i].vmax != P[0].vmax || P[i].width != P[0].width ||
             P[i].height != P[0].height)
@@ -673,6 +679,195 @@ struct JpegGpuJob {
     }
 };
 
+// ---- a batch with progressive files whose scans are decoded on the device (jpeg_gpu_progressive.h; option
+// "jpeg_device_progressive").  Files of one size and sampling.  The entropy-coded bytes of every scan go up, one launch
+// de-stuffs them per (file, scan), then the scans run by dependency level: a scan waits only for earlier scans of its file
+// that cover one of its components and overlap its band.  Baseline files of the batch are decoded by the host decoder and
+// their coefficients uploaded; so is, again, any file the device reports a defect for (the host gives the status).
+// -> DFD_OK and *done = true when the batch was decoded here; *done = false: not eligible, the caller takes the host pool.
+static int jpeg_progressive_device_batch(dfd_handle* h, std::vector<Parsed>& P, const std::vector<ScanLayout>& L, int n, uint8_t* frames_dev,
+                                         bool* done) {
+    using namespace dfd_pjd;
+    *done = false;
+    if (n < 1 || n > 65535) return DFD_OK;                          // (frames are grid.y of the IDCT launch)
+    const Parsed& P0 = P[0];
+    size_t raw_total = 0, nscans = 0, ntabs = 0, nsegtab = 0, njobs = 0;
+    std::vector<int> baseline;                                      // files of the batch the host decoder takes
+    for (int i = 0; i < n; ++i) {
+        if (P[i].ncomp != P0.ncomp || P[i].hmax != P0.hmax || P[i].vmax != P0.vmax || L[i].total != L[0].total) return DFD_OK;
+        if (!P[i].progressive) { baseline.push_back(i); continue; }
+        nscans += P[i].scans.size();
+        ntabs += P[i].ptabs.size();
+        for (const ProgScan& sc : P[i].scans) {
+            raw_total += al256((size_t)(sc.data_end - sc.data) + 16);
+            const size_t per = sc.restart ? (size_t)sc.restart : sc.g.units;
+            const size_t nseg = (sc.g.units + per - 1) / per;
+            nsegtab += nseg + 1;
+            njobs += nseg;
+        }
+    }
+    JpegGpuLayout W{};
+    size_t plane_total = 0;
+    for (int c = 0; c < P0.ncomp; ++c) plane_total += al256((size_t)P0.comp[c].bw * 8 * P0.comp[c].bh * 8);
+    W.coef_stride = al256(L[0].total * 64 * 2) / 2;
+    W.plane_stride = plane_total;
+    // the device descriptors hold 32-bit offsets
+    if (nscans == 0 || nscans >= 65535 || raw_total >= ((size_t)1 << 31) || (size_t)n * W.coef_stride >= ((size_t)1 << 31) || njobs >= ((size_t)1 << 30)) return DFD_OK;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += al256(bytes); return at; };
+    const size_t o_raw = take(raw_total), o_ds = take(raw_total), o_scans = take(sizeof(PjdScan) * nscans), o_tabs = take(sizeof(PjHuff) * ntabs),
+                 o_seg = take(4 * nsegtab), o_jobs = take(sizeof(PjdJob) * njobs), o_list = take(4 * nscans), o_status = take(4 * (size_t)n),
+                 o_coef = take(W.coef_stride * 2 * (size_t)n), o_planes = take(plane_total * (size_t)n), o_q = take((size_t)n * 192 * 2);
+    W.planes = o_planes;
+    int rc;
+    if ((rc = ensure(h, &h->jpeg_work, o))) return rc;
+    uint8_t* work = static_cast<uint8_t*>(h->jpeg_work.p);
+    // pinned staging: [raw bytes][scans][tables][jobs][lists][q][status back]
+    size_t so = 0;
+    auto stake = [&](size_t bytes) { const size_t at = so; so += al256(bytes); return at; };
+    const size_t s_raw = stake(raw_total), s_scans = stake(sizeof(PjdScan) * nscans), s_tabs = stake(sizeof(PjHuff) * ntabs),
+                 s_jobs = stake(sizeof(PjdJob) * njobs), s_list = stake(4 * nscans), s_q = stake((size_t)n * 192 * 2), s_status = stake(4 * (size_t)n),
+                 s_base = stake(W.coef_stride * 2 * baseline.size());
+    if ((rc = jpeg_pinned(h, so))) return rc;
+    char* pin = static_cast<char*>(h->jpeg_host);
+    // the baseline files of the batch: the host decoder, one file per pool thread, straight into pinned memory
+    if (!baseline.empty()) {
+        std::vector<int> rcs(baseline.size(), 0);
+        auto one = [&](int k, dfd_handle* eh, bool inner) {
+            rcs[k] = entropy_decode(eh, &P[baseline[k]], reinterpret_cast<int16_t*>(pin + s_base) + (size_t)k * W.coef_stride, L[baseline[k]], inner);
+        };
+        if (baseline.size() < 3) for (size_t k = 0; k < baseline.size(); ++k) one((int)k, h, true);
+        else HostPool::get().run((int)baseline.size(), [&](int k) { one(k, nullptr, false); });
+        for (size_t k = 0; k < baseline.size(); ++k) {
+            if (rcs[k] && baseline.size() < 3) return rcs[k];
+            if (rcs[k]) return fail(h, rcs[k], "analyze_stream_batch: frame %d: corrupt or truncated JPEG scan", baseline[k]);
+        }
+    }
+    PjdScan* Sh = reinterpret_cast<PjdScan*>(pin + s_scans);
+    PjHuff* Th = reinterpret_cast<PjHuff*>(pin + s_tabs);
+    PjdJob* Jh = reinterpret_cast<PjdJob*>(pin + s_jobs);
+    uint32_t* Lh = reinterpret_cast<uint32_t*>(pin + s_list);
+    uint16_t* qh = reinterpret_cast<uint16_t*>(pin + s_q);
+    int32_t* status_h = reinterpret_cast<int32_t*>(pin + s_status);
+    // descriptors; the dependency level of every scan
+    std::vector<int> level(nscans, 0);
+    std::vector<uint32_t> nseg_of(nscans, 0);
+    size_t si = 0, ti = 0, ro = 0, sg = 0;
+    int levels = 0;
+    for (int i = 0; i < n; ++i) {
+        for (int c = 0; c < 3; ++c) memcpy(qh + (size_t)i * 192 + 64 * c, P[i].q[P[i].comp[c < P[i].ncomp ? c : 0].tq], 128);
+        if (!P[i].progressive) continue;
+        const size_t first = si;
+        memcpy(Th + ti, P[i].ptabs.data(), sizeof(PjHuff) * P[i].ptabs.size());
+        for (size_t k = 0; k < P[i].scans.size(); ++k, ++si) {
+            const ProgScan& sc = P[i].scans[k];
+            PjdScan& D = Sh[si];
+            memset(&D, 0, sizeof D);
+            D.g = sc.g;
+            D.file = (uint32_t)i;
+            D.raw_off = (uint32_t)ro;
+            D.raw_len = (uint32_t)(sc.data_end - sc.data);
+            D.ds_off = (uint32_t)ro;
+            memcpy(pin + s_raw + ro, sc.data, D.raw_len);
+            ro += al256((size_t)D.raw_len + 16);
+            D.per = sc.restart ? (uint32_t)sc.restart : sc.g.units;
+            D.nseg = (sc.g.units + D.per - 1) / D.per;
+            D.seg_off = (uint32_t)sg;
+            sg += D.nseg + 1;
+            D.tab0 = (uint32_t)(ti + sc.tab0);
+            D.coef_off = (uint32_t)((size_t)i * W.coef_stride);
+            nseg_of[si] = D.nseg;
+            for (size_t e = 0; e < k; ++e) {                        // earlier scans of this file it has to wait for
+                const ProgScan& ea = P[i].scans[e];
+                if (ea.g.Se < sc.g.Ss || sc.g.Se < ea.g.Ss) continue;
+                bool shares = false;
+                for (int a = 0; a < sc.g.ncomp; ++a)
+                    for (int b = 0; b < ea.g.ncomp; ++b) shares = shares || sc.ci[a] == ea.ci[b];
+                if (shares) level[si] = std::max(level[si], level[first + e] + 1);
+            }
+            levels = std::max(levels, level[si] + 1);
+        }
+        ti += P[i].ptabs.size();
+    }
+    // per level: the walks' jobs, then the list of its DC refinement scans
+    struct Level { size_t job0 = 0, njobs = 0, list0 = 0, nlist = 0; uint32_t max_units = 0; };
+    std::vector<Level> lv(levels);
+    size_t ji = 0, li = 0;
+    for (int l = 0; l < levels; ++l) {
+        lv[l].job0 = ji;
+        lv[l].list0 = li;
+        for (size_t s = 0; s < nscans; ++s) {
+            if (level[s] != l) continue;
+            if (Sh[s].g.Ss == 0 && Sh[s].g.Ah != 0) {
+                Lh[li++] = (uint32_t)s;
+                lv[l].max_units = std::max(lv[l].max_units, Sh[s].g.units);
+            } else {
+                for (uint32_t k = 0; k < nseg_of[s]; ++k) Jh[ji++] = PjdJob{(uint32_t)s, k};
+            }
+        }
+        lv[l].njobs = ji - lv[l].job0;
+        lv[l].nlist = li - lv[l].list0;
+    }
+    hipStream_t s = h->stream;
+    uint8_t* raw_dev = work + o_raw;
+    uint8_t* ds_dev = work + o_ds;
+    PjdScan* Sd = reinterpret_cast<PjdScan*>(work + o_scans);
+    PjHuff* Td = reinterpret_cast<PjHuff*>(work + o_tabs);
+    uint32_t* segd = reinterpret_cast<uint32_t*>(work + o_seg);
+    PjdJob* Jd = reinterpret_cast<PjdJob*>(work + o_jobs);
+    uint32_t* Ld = reinterpret_cast<uint32_t*>(work + o_list);
+    int32_t* status_d = reinterpret_cast<int32_t*>(work + o_status);
+    int16_t* coef = reinterpret_cast<int16_t*>(work + o_coef);
+    uint16_t* qd = reinterpret_cast<uint16_t*>(work + o_q);
+    DFD_HIP_TRY(h, hipMemcpyAsync(raw_dev, pin + s_raw, ro, hipMemcpyHostToDevice, s));
+    DFD_HIP_TRY(h, hipMemcpyAsync(Sd, Sh, sizeof(PjdScan) * nscans, hipMemcpyHostToDevice, s));
+    DFD_HIP_TRY(h, hipMemcpyAsync(Td, Th, sizeof(PjHuff) * ntabs, hipMemcpyHostToDevice, s));
+    if (ji) DFD_HIP_TRY(h, hipMemcpyAsync(Jd, Jh, sizeof(PjdJob) * ji, hipMemcpyHostToDevice, s));
+    if (li) DFD_HIP_TRY(h, hipMemcpyAsync(Ld, Lh, 4 * li, hipMemcpyHostToDevice, s));
+    DFD_HIP_TRY(h, hipMemcpyAsync(qd, qh, (size_t)n * 192 * 2, hipMemcpyHostToDevice, s));
+    DFD_HIP_TRY(h, hipMemsetAsync(segd, 0xFF, 4 * nsegtab, s));
+    DFD_HIP_TRY(h, hipMemsetAsync(status_d, 0, 4 * (size_t)n, s));
+    DFD_HIP_TRY(h, hipMemsetAsync(coef, 0, W.coef_stride * 2 * (size_t)n, s));      // the planes are zeroed before the first level
+    for (size_t k = 0; k < baseline.size(); ++k)
+        DFD_HIP_TRY(h, hipMemcpyAsync(coef + (size_t)baseline[k] * W.coef_stride, pin + s_base + k * W.coef_stride * 2, L[0].total * 64 * 2,
+                                      hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(pjd_destuff_kernel, dim3((unsigned)nscans), dim3(PJD_DS_THREADS), 0, s, raw_dev, ds_dev, Sd, segd);
+    for (int l = 0; l < levels; ++l) {
+        if (lv[l].njobs)
+            hipLaunchKernelGGL(pjd_walk_kernel, dim3((unsigned)((lv[l].njobs + PJD_WALK_THREADS - 1) / PJD_WALK_THREADS)), dim3(PJD_WALK_THREADS), 0, s,
+                               ds_dev, Sd, Td, segd, Jd + lv[l].job0, (uint32_t)lv[l].njobs, coef, status_d);
+        if (lv[l].nlist)
+            hipLaunchKernelGGL(pjd_dc_refine_kernel, dim3((lv[l].max_units + 255) / 256, (unsigned)lv[l].nlist), dim3(256), 0, s, ds_dev, Sd, segd,
+                               Ld + lv[l].list0, coef, status_d);
+    }
+    DFD_HIP_TRY(h, hipGetLastError());
+    DFD_HIP_TRY(h, hipMemcpyAsync(status_h, status_d, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
+    DFD_HIP_TRY(h, stream_sync(h));
+    // files the device reports a defect for: the host decoder gives the status (rare: one after the other, as the baseline
+    // device decoder hands its frames back)
+    int on_host = (int)baseline.size();
+    std::vector<int16_t> tmp;
+    for (int i = 0; i < n; ++i) {
+        if (!P[i].progressive || status_h[i] == 0) continue;
+        if (getenv("DFD_JPEG_VERBOSE"))
+            fprintf(stderr, "[dfd] jpeg device progressive: frame %d defect %d -> host decoder\n", i, status_h[i]);
+        try {
+            tmp.resize(L[i].total * 64);
+        } catch (const std::bad_alloc&) { return fail(h, DFD_ERR_CAPACITY, "decode_jpeg: out of host memory"); }
+        if ((rc = entropy_decode(h, &P[i], tmp.data(), L[i], true))) return rc;
+        DFD_HIP_TRY(h, hipMemcpy(coef + (size_t)i * W.coef_stride, tmp.data(), tmp.size() * 2, hipMemcpyHostToDevice));
+        ++on_host;
+    }
+    JpegGpuJob job;
+    job.h = h; job.P = &P; job.L = &L; job.n = n; job.work = work; job.W = W; job.frames_dev = frames_dev; job.coef = coef; job.qd = qd;
+    if ((rc = job.idct_colour())) return rc;
+    DFD_HIP_TRY(h, stream_sync(h));
+    h->jpeg_frames_device += (unsigned long long)(n - on_host);
+    h->jpeg_frames_host += (unsigned long long)on_host;
+    *done = true;
+    return DFD_OK;
+}
+
 // n JPEGs of ONE size -> frames [n][H][W][3] at frames_dev (null: only parse, report the size).  The scans are entropy-
 // decoded one per pool thread (each sequentially), the device halves are queued frame by frame.
 int jpeg_decode_batch_to(dfd_handle* h, const uint8_t* const* jpegs, const size_t* lens, int n, uint8_t* frames_dev, int* hh, int* ww) {
@@ -680,7 +875,7 @@ int jpeg_decode_batch_to(dfd_handle* h, const uint8_t* const* jpegs, const size_
     std::vector<ScanLayout> L(n);
     int rc;
     for (int i = 0; i < n; ++i) {
-        if ((rc = parse_headers(h, jpegs[i], lens[i], &P[i]))) return rc;
+        if ((rc = parse_headers(h, jpegs[i], lens[i], &P[i], h->jpeg_progressive != 0))) return rc;
         scan_layout(&P[i], &L[i]);
         if (P[i].width != P[0].width || P[i].height != P[0].height)
             return fail(h, DFD_ERR_ARG, "analyze_stream_batch: frame %d is %d x %d, frame 0 is %d x %d - the frames of a batch share one size",
@@ -699,7 +894,15 @@ int jpeg_decode_batch_to(dfd_handle* h, const uint8_t* const* jpegs, const size_
     // 4.1 vs 2.4 ms, 32 x 1080p 10.5 vs 2.9 ms): option "jpeg_device_entropy" = 2 (default) takes the device from 1 MiB of
     // entropy-coded data per call, 1 always, 0 never
     size_t scan_bytes = 0;
-    for (int i = 0; i < n; ++i) scan_bytes += (size_t)(P[i].end - P[i].scan);
+    bool any_progressive = false;
+    for (int i = 0; i < n; ++i) {
+        scan_bytes += (size_t)(P[i].end - P[i].scan);
+        any_progressive = any_progressive || P[i].progressive;
+    }
+    if (any_progressive && h->jpeg_device_progressive) {
+        bool done = false;
+        if ((rc = jpeg_progressive_device_batch(h, P, L, n, frames_dev, &done)) || done) return rc;
+    }
     const bool want_device = h->jpeg_device_entropy == 1 || (h->jpeg_device_entropy >= 2 && scan_bytes >= ((size_t)1 << 20));
     if (want_device && jpeg_gpu_batch_ok(h, P, L, n)) {
         // the scans go up as bytes (16-byte aligned starts, 16 bytes of slack each) and are decoded there
@@ -773,6 +976,12 @@ extern "C" {
 int dfd_jpeg_coefficients(const uint8_t* jpeg, size_t len, int* info, uint16_t* qtables_out, int16_t* coef_out,
                           size_t capacity, size_t* count) {
     return dfd_jpeg::coefficients(jpeg, len, info, qtables_out, coef_out, capacity, count);
+}
+
+// dfd_jpeg_coefficients with flags (DFD_JPEG_ALLOW_PROGRESSIVE: progressive files as option "jpeg_progressive" takes them)
+int dfd_jpeg_coefficients_ex(const uint8_t* jpeg, size_t len, unsigned flags, int* info, uint16_t* qtables_out, int16_t* coef_out,
+                             size_t capacity, size_t* count) {
+    return dfd_jpeg::coefficients(jpeg, len, info, qtables_out, coef_out, capacity, count, flags);
 }
 
 // n JPEGs of one size -> n packed BGR frames (the batch path of dfd_analyze_stream_batch / dfd_analyze_jpegs_host on its
@@ -857,6 +1066,7 @@ int dfd_analyze_jpegs_host(dfd_handle* h, const uint8_t* const* jpegs, const siz
     const int chunk_bytes = h->jpeg_chunk_bytes;
     int hh = 0, ww = 0;
     size_t max_up = 0, max_work = 0, max_stage = 0;
+    bool any_progressive = false;
     for (int first = 0; first < n_total; first += batch) {
         chunks.emplace_back();
         Chunk& c = chunks.back();
@@ -869,7 +1079,8 @@ int dfd_analyze_jpegs_host(dfd_handle* h, const uint8_t* const* jpegs, const siz
         size_t sum_len = 0;
         bool ascending = true;
         for (int i = 0; i < c.cnt; ++i) {
-            if ((rc = parse_headers(h, jpegs[first + i], lens[first + i], &c.P[i]))) return rc;
+            if ((rc = parse_headers(h, jpegs[first + i], lens[first + i], &c.P[i], h->jpeg_progressive != 0))) return rc;
+            any_progressive = any_progressive || c.P[i].progressive;
             scan_layout(&c.P[i], &c.L[i]);
             if (hh == 0) { hh = c.P[i].height; ww = c.P[i].width; }
             if (c.P[i].height != hh || c.P[i].width != ww)
@@ -891,8 +1102,12 @@ int dfd_analyze_jpegs_host(dfd_handle* h, const uint8_t* const* jpegs, const siz
             for (int i = 0; i < c.cnt; ++i) c.roff[i] = (uint32_t)(c.P[i].scan - c.span);
             c.up = al256(span + 32);
         }
+    }
+    // every chunk is parsed: only now is it known whether the call holds a progressive file (then none of this applies)
+    for (Chunk& c : chunks) {
+        if (any_progressive) break;
         if (!jpeg_gpu_batch_ok(h, c.P, c.L, c.cnt))
-            return fail(h, DFD_ERR_UNSUPPORTED, "analyze_jpegs_host: files %d.. need the host decoder (restart intervals or mixed layouts)", first);
+            return fail(h, DFD_ERR_UNSUPPORTED, "analyze_jpegs_host: files %d.. need the host decoder (restart intervals or mixed layouts)", c.first);
         c.W = jpeg_gpu_layout(c.P, c.L, c.rlen.data(), c.cnt, chunk_bytes);
         max_up = std::max(max_up, c.up);
         max_work = std::max(max_work, c.W.total);
@@ -904,6 +1119,22 @@ int dfd_analyze_jpegs_host(dfd_handle* h, const uint8_t* const* jpegs, const siz
     if ((size_t)batch * (size_t)hh * (size_t)ww > kMaxBatchPixels)
         return fail(h, DFD_ERR_UNSUPPORTED, "analyze_jpegs_host: %d frames of %d x %d per chunk exceed the %zu-pixel budget", batch, ww, hh,
                     kMaxBatchPixels);
+    // A call with a progressive file (option "jpeg_progressive"): their scans are decoded by the host pool, so each chunk is
+    // decoded by jpeg_decode_batch_to and analysed in turn - the results of the pipelined path below, without its overlap
+    if (any_progressive) {
+        if ((rc = ensure(h, &h->stage[0], (size_t)batch * frame_bytes))) return rc;
+        for (const Chunk& c : chunks) {
+            int dh = hh, dw = ww;
+            if ((rc = jpeg_decode_batch_to(h, jpegs + c.first, lens + c.first, c.cnt, static_cast<uint8_t*>(h->stage[0].p), &dh, &dw))) return rc;
+            rc = dfd_analyze_batch_device(h, static_cast<const uint8_t*>(h->stage[0].p), c.cnt, hh, ww,
+                                          forced_xywh ? forced_xywh + (size_t)c.first * forced_k * 4 : nullptr, forced_k, conf_thr, max_faces,
+                                          apply_clahe, with_forensics, xywh_out + (size_t)c.first * max_faces * 4, n_faces_out + c.first,
+                                          logits_out + (size_t)c.first * max_faces, forensic_prob_out ? forensic_prob_out + c.first : nullptr);
+            if (rc) return rc;
+        }
+        DFD_HIP_TRY(h, stream_sync(h));
+        return DFD_OK;
+    }
     // two of everything a chunk touches: chunk k + 1 is uploaded and DECODED (third stream) while chunk k is analysed - the decode
     // kernels are latency-bound at one or two waves per SIMD and run in the shadow of the analysis
     if ((rc = jpeg_pinned(h, 2 * max_stage))) return rc;

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/dfd_hip.h"
+#include "jpeg_progressive.h"
 #include "jpeg_tables.h"
 
 namespace dfd {
@@ -68,20 +69,129 @@ struct Component { int id = 0, h = 1, v = 1, tq = 0, td = 0, ta = 0, bw = 0, bh 
 
 inline int extend(int v, int s) { return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
 
+// one scan of a progressive file
+struct ProgScan {
+    dfd_pj::PjScan g;                          // geometry filled in once the frame's sampling is known
+    int ci[3] = {0, 0, 0};                     // the scan's components (indices into Parsed::comp)
+    int restart = 0;                           // restart interval in units (MCUs, or blocks of a one-component scan)
+    int tab0 = 0;                              // its table set: ptabs[tab0 ...], indexed by g.dc_tab / g.ac_tab
+    const uint8_t* data = nullptr;             // entropy-coded bytes: [data, data_end), up to the next marker that is no RSTn
+    const uint8_t* data_end = nullptr;
+};
+
 struct Parsed {
     int width = 0, height = 0, ncomp = 0, hmax = 1, vmax = 1, restart = 0;
     Component comp[3];
-    uint16_t q[4][64];                         // natural order
+    uint16_t q[4][64] = {};                    // natural order (a table no DQT defined reads as zeros)
     bool qpresent[4] = {false, false, false, false};
     HuffTable dc[4], ac[4];
     const uint8_t* scan = nullptr;
     const uint8_t* end = nullptr;
+    // progressive (SOF2) files, parsed only when the caller allows them: every scan with the tables in force at its SOS
+    bool progressive = false;
+    std::vector<ProgScan> scans;
+    std::vector<dfd_pj::PjHuff> ptabs;
+    int8_t prec[3][64];                        // precision reached per component and coefficient: -1 = not sent yet, else Al
 };
 
 inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 
+inline void to_pj(const HuffTable& t, dfd_pj::PjHuff* o) {
+    for (int i = 0; i < 256; ++i) {
+        const uint16_t e = t.look10[i << 2];
+        o->look8[i] = (e && (e >> 8) <= 8) ? e : (uint16_t)0;
+    }
+    o->maxcode[0] = -1; o->mincode[0] = 0; o->valptr[0] = 0;
+    for (int l = 1; l <= 16; ++l) { o->maxcode[l] = t.maxcode[l]; o->mincode[l] = t.mincode[l]; o->valptr[l] = t.valptr[l]; }
+    memcpy(o->vals, t.vals, 256);
+}
+
+// first byte behind the entropy-coded data that starts at p: the next marker that is neither a stuffed zero nor RSTn
+// (the rule of destuff() below), or len
+inline size_t entropy_end(const uint8_t* d, size_t len, size_t p) {
+    while (p < len) {
+        const uint8_t* f = static_cast<const uint8_t*>(memchr(d + p, 0xFF, len - p));
+        if (!f) return len;
+        const size_t i = (size_t)(f - d);
+        if (i + 1 >= len) return len;
+        const uint8_t m = d[i + 1];
+        if (m == 0x00 || (m >= 0xD0 && m <= 0xD7)) p = i + 2;
+        else if (m == 0xFF) p = i + 1;
+        else return i;
+    }
+    return len;
+}
+
+// SOS of a progressive file (s: the segment's n bytes): the T.81 G.1.1.1.1 rules and the precision record.  A script this
+// decoder does not take (out of order, precision not continued) is DFD_ERR_UNSUPPORTED; a malformed segment DFD_ERR_ARG.
+inline int progressive_sos(dfd_handle* h, const uint8_t* s, int n, Parsed* P) {
+    const int ns = n >= 1 ? s[0] : 0;
+    if (ns < 1 || ns > P->ncomp || n != 1 + 2 * ns + 3) return fail(h, DFD_ERR_ARG, "decode_jpeg: bad SOS");
+    ProgScan sc;
+    int td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
+    for (int j = 0; j < ns; ++j) {
+        int c = -1;
+        for (int k = 0; k < P->ncomp; ++k)
+            if (P->comp[k].id == s[1 + 2 * j]) { c = k; break; }
+        if (c < 0 || (j > 0 && c <= sc.ci[j - 1])) return fail(h, DFD_ERR_ARG, "decode_jpeg: bad scan component");
+        sc.ci[j] = c;
+        td[j] = s[2 + 2 * j] >> 4;
+        ta[j] = s[2 + 2 * j] & 15;
+        if (td[j] > 3 || ta[j] > 3) return fail(h, DFD_ERR_ARG, "decode_jpeg: bad table selector");
+    }
+    const int Ss = s[1 + 2 * ns], Se = s[2 + 2 * ns], Ah = s[3 + 2 * ns] >> 4, Al = s[3 + 2 * ns] & 15;
+    bool ok = Ss == 0 ? Se == 0 : (ns == 1 && Ss <= Se && Se <= 63);
+    ok = ok && (Ah == 0 || Al == Ah - 1) && Al <= 13;
+    for (int j = 0; ok && j < ns; ++j) {
+        int8_t* pr = P->prec[sc.ci[j]];
+        if (Ss > 0 && pr[0] < 0) ok = false;                       // AC before the component's first DC scan
+        for (int k = Ss; ok && k <= Se; ++k) {
+            if (Ah == 0 ? pr[k] != -1 : pr[k] != Ah) ok = false;    // a first scan of something sent / a refinement that does not continue
+            pr[k] = (int8_t)Al;
+        }
+    }
+    if (!ok)
+        return fail(h, DFD_ERR_UNSUPPORTED, "decode_jpeg: progressive scan Ss=%d Se=%d Ah=%d Al=%d of %d components is out of order", Ss, Se, Ah,
+                    Al, ns);
+    dfd_pj::PjScan& g = sc.g;
+    memset(&g, 0, sizeof g);
+    g.ncomp = ns; g.Ss = Ss; g.Se = Se; g.Ah = Ah; g.Al = Al;
+    g.ac_tab = -1;
+    sc.restart = P->restart;
+    sc.tab0 = (int)P->ptabs.size();
+    for (int j = 0; j < 3; ++j) g.dc_tab[j] = -1;
+    auto keep = [&](const HuffTable& t) {
+        P->ptabs.emplace_back();
+        to_pj(t, &P->ptabs.back());
+        return (int)P->ptabs.size() - 1 - sc.tab0;
+    };
+    if (Ss == 0 && Ah == 0) {
+        for (int j = 0; j < ns; ++j) {
+            if (!P->dc[td[j]].present) return fail(h, DFD_ERR_ARG, "decode_jpeg: Huffman table missing");
+            g.dc_tab[j] = keep(P->dc[td[j]]);
+        }
+    } else if (Ss > 0) {
+        if (!P->ac[ta[0]].present) return fail(h, DFD_ERR_ARG, "decode_jpeg: Huffman table missing");
+        g.ac_tab = keep(P->ac[ta[0]]);
+    }
+    P->scans.push_back(sc);
+    return DFD_OK;
+}
+
 // -> DFD_OK, DFD_ERR_ARG (not a JPEG / truncated / corrupt) or DFD_ERR_UNSUPPORTED
-inline int parse_headers(dfd_handle* h, const uint8_t* d, size_t len, Parsed* P) {
+// sampling: luma h x v in {1x1, 2x1, 2x2}, chroma 1x1 (a single component counts as 1x1 whatever its SOF says)
+inline int check_sampling(dfd_handle* h, Parsed* P) {
+    if (P->ncomp == 1) { P->comp[0].h = P->comp[0].v = 1; return DFD_OK; }
+    const Component &Y = P->comp[0], &B = P->comp[1], &R = P->comp[2];
+    const bool ok = B.h == 1 && B.v == 1 && R.h == 1 && R.v == 1 &&
+                    ((Y.h == 1 && Y.v == 1) || (Y.h == 2 && Y.v == 1) || (Y.h == 2 && Y.v == 2));
+    if (!ok) return fail(h, DFD_ERR_UNSUPPORTED, "decode_jpeg: sampling %dx%d,%dx%d,%dx%d", Y.h, Y.v, B.h, B.v, R.h, R.v);
+    return DFD_OK;
+}
+
+// allow_progressive: SOF2 files whose scan script is complete and in order are taken (every scan is recorded in
+// P->scans); without it they are DFD_ERR_UNSUPPORTED like every other flavour
+inline int parse_headers(dfd_handle* h, const uint8_t* d, size_t len, Parsed* P, bool allow_progressive = false) {
     if (len < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(h, DFD_ERR_ARG, "decode_jpeg: not a JPEG (no SOI)");
     size_t pos = 2;
     P->end = d + len;
@@ -105,6 +215,10 @@ inline int parse_headers(dfd_handle* h, const uint8_t* d, size_t len, Parsed* P)
                 const int pq = s[i] >> 4, tq = s[i] & 15;
                 ++i;
                 if (tq > 3 || i + (pq ? 128 : 64) > n) return fail(h, DFD_ERR_ARG, "decode_jpeg: bad DQT");
+                // libjpeg latches a component's table at its first scan (jdinput.c latch_quant_tables); here the tables in
+                // force at the end dequantise, so a progressive file that redefines one between its scans is not taken
+                if (P->progressive && !P->scans.empty() && P->qpresent[tq])
+                    return fail(h, DFD_ERR_UNSUPPORTED, "decode_jpeg: quantisation table %d redefined between the scans of a progressive file", tq);
                 for (int k = 0; k < 64; ++k) {
                     P->q[tq][dfd::kJpegZigzag[k]] = (uint16_t)(pq ? be16(s + i + 2 * k) : s[i + k]);
                 }
@@ -124,7 +238,10 @@ inline int parse_headers(dfd_handle* h, const uint8_t* d, size_t len, Parsed* P)
                     return fail(h, DFD_ERR_ARG, "decode_jpeg: bad DHT (code lengths over-subscribed)");
                 i += 17 + total;
             }
-        } else if (m == 0xC0 || m == 0xC1) {                       // SOF0 / SOF1: sequential Huffman
+        } else if (P->progressive && m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
+            // a second frame header would change the geometry under the scans already recorded (libjpeg: JERR_SOF_DUPLICATE)
+            return fail(h, DFD_ERR_ARG, "decode_jpeg: second SOF in a progressive file");
+        } else if (m == 0xC0 || m == 0xC1 || (m == 0xC2 && allow_progressive && !have_sof)) {   // SOF0 / SOF1: sequential Huffman; SOF2
             if (n < 6 || s[0] != 8) return fail(h, DFD_ERR_UNSUPPORTED, "decode_jpeg: %d-bit samples", n >= 1 ? s[0] : 0);
             P->height = be16(s + 1);
             P->width = be16(s + 3);
@@ -145,6 +262,10 @@ inline int parse_headers(dfd_handle* h, const uint8_t* d, size_t len, Parsed* P)
                 if (C.tq > 3) return fail(h, DFD_ERR_ARG, "decode_jpeg: bad quantisation table index");
             }
             have_sof = true;
+            if (m == 0xC2) {
+                P->progressive = true;
+                memset(P->prec, -1, sizeof P->prec);
+            }
         } else if (m >= 0xC2 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
             return fail(h, DFD_ERR_UNSUPPORTED, "decode_jpeg: SOF%d (progressive / lossless / arithmetic) is not decoded on the GPU path", m - 0xC0);
         } else if (m == 0xE0) {                                    // APP0 (jdmarker.c examine_app0)
@@ -155,6 +276,20 @@ inline int parse_headers(dfd_handle* h, const uint8_t* d, size_t len, Parsed* P)
             if (n >= 2) P->restart = be16(s);
         } else if (m == 0xDA) {                                    // SOS
             if (!have_sof) return fail(h, DFD_ERR_ARG, "decode_jpeg: SOS before SOF");
+            if (P->progressive) {
+                // the frame's sampling is settled before a scan is recorded: the scans' geometry comes from it
+                if (P->scans.empty()) {
+                    const int src = check_sampling(h, P);
+                    if (src) return src;
+                }
+                const int rc = progressive_sos(h, s, n, P);
+                if (rc) return rc;
+                P->scans.back().data = d + pos + seg;
+                if (!P->scan) P->scan = d + pos + seg;
+                pos = entropy_end(d, len, pos + seg);
+                P->scans.back().data_end = d + pos;
+                continue;
+            }
             if (n < 1 || s[0] != P->ncomp || n < 1 + 2 * P->ncomp + 3)
                 return fail(h, DFD_ERR_UNSUPPORTED, "decode_jpeg: non-interleaved (multi-scan) file");
             for (int c = 0; c < P->ncomp; ++c) {
@@ -169,13 +304,12 @@ inline int parse_headers(dfd_handle* h, const uint8_t* d, size_t len, Parsed* P)
         pos += seg;
     }
     if (!have_sof || !P->scan) return fail(h, DFD_ERR_ARG, "decode_jpeg: no frame or scan found");
-    // sampling: luma h x v in {1x1, 2x1, 2x2}, chroma 1x1
-    if (P->ncomp == 1) { P->comp[0].h = P->comp[0].v = 1; }
-    else {
+    {
+        const int src = check_sampling(h, P);
+        if (src) return src;
+    }
+    if (P->ncomp != 1) {
         const Component &Y = P->comp[0], &B = P->comp[1], &R = P->comp[2];
-        const bool ok = B.h == 1 && B.v == 1 && R.h == 1 && R.v == 1 &&
-                        ((Y.h == 1 && Y.v == 1) || (Y.h == 2 && Y.v == 1) || (Y.h == 2 && Y.v == 2));
-        if (!ok) return fail(h, DFD_ERR_UNSUPPORTED, "decode_jpeg: sampling %dx%d,%dx%d,%dx%d", Y.h, Y.v, B.h, B.v, R.h, R.v);
         // the colour space of three components (jdapimin.c default_decompress_parms): JFIF says YCbCr; without it Adobe's
         // transform byte decides (0: RGB); without either the component ids 'R','G','B' mean RGB; anything else is YCbCr.
         // The device half converts YCbCr only: RGB samples go back to the caller's own decoder.
@@ -188,7 +322,42 @@ inline int parse_headers(dfd_handle* h, const uint8_t* d, size_t len, Parsed* P)
     P->vmax = P->comp[0].v;
     for (int c = 0; c < P->ncomp; ++c) {
         if (!P->qpresent[P->comp[c].tq]) return fail(h, DFD_ERR_ARG, "decode_jpeg: quantisation table %d missing", P->comp[c].tq);
+        if (P->progressive) continue;                              // (each scan checked its own tables at its SOS)
         if (!P->dc[P->comp[c].td].present || !P->ac[P->comp[c].ta].present) return fail(h, DFD_ERR_ARG, "decode_jpeg: Huffman table missing");
+    }
+    if (!P->progressive) return DFD_OK;
+    // libjpeg smooths blocks whose DC or low AC coefficients are not fully known; that arithmetic is not built here, so
+    // only a file that sends every coefficient of every component down to Al = 0 is decoded
+    for (int c = 0; c < P->ncomp; ++c)
+        for (int k = 0; k < 64; ++k)
+            if (P->prec[c][k] != 0)
+                return fail(h, DFD_ERR_UNSUPPORTED, "decode_jpeg: incomplete progressive file (component %d, coefficient %d %s)", c, k,
+                            P->prec[c][k] < 0 ? "never sent" : "not refined to the last bit");
+    // geometry of every scan (the formulas of scan_layout below)
+    const int mcux = (P->width + 8 * P->hmax - 1) / (8 * P->hmax), mcuy = (P->height + 8 * P->vmax - 1) / (8 * P->vmax);
+    size_t off[3] = {0, 0, 0}, total = 0;
+    for (int c = 0; c < P->ncomp; ++c) {
+        off[c] = total;
+        total += (size_t)mcux * P->comp[c].h * mcuy * P->comp[c].v * 64;
+    }
+    for (ProgScan& sc : P->scans) {
+        dfd_pj::PjScan& g = sc.g;
+        for (int j = 0; j < g.ncomp; ++j) {
+            const Component& C = P->comp[sc.ci[j]];
+            g.comp_off[j] = (uint32_t)off[sc.ci[j]];
+            g.bw[j] = mcux * C.h;
+            g.h[j] = C.h;
+            g.v[j] = C.v;
+        }
+        if (g.ncomp == 1) {                                        // the component's own grid (T.81 A.2.3)
+            const Component& C = P->comp[sc.ci[0]];
+            const int wc = (P->width * C.h + P->hmax - 1) / P->hmax, hc = (P->height * C.v + P->vmax - 1) / P->vmax;
+            g.units_x = (wc + 7) / 8;
+            g.units = (uint32_t)g.units_x * (uint32_t)((hc + 7) / 8);
+        } else {
+            g.units_x = mcux;
+            g.units = (uint32_t)mcux * (uint32_t)mcuy;
+        }
     }
     return DFD_OK;
 }
@@ -394,7 +563,10 @@ inline int16_t* block_ptr(const ScanLayout& L, const Parsed& P, int16_t* coef, s
 
 // `coef` must hold `total` coefficients (any content: every block is written).  -> DFD_OK / DFD_ERR_ARG
 // `inner`: use the pool inside this scan (false when the caller already runs one scan per pool thread)
+inline int progressive_decode(dfd_handle* h, Parsed* P, int16_t* coef, const ScanLayout& L, bool inner);
+
 inline int entropy_decode(dfd_handle* h, Parsed* P, int16_t* coef, const ScanLayout& L, bool inner = true) {
+    if (P->progressive) return progressive_decode(h, P, coef, L, inner);
     const bool verbose = getenv("DFD_JPEG_VERBOSE") != nullptr;
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto t_last = now();
@@ -647,6 +819,38 @@ inline int entropy_decode(dfd_handle* h, Parsed* P, int16_t* coef, const ScanLay
     return DFD_OK;
 }
 
+// A progressive file: the planes are zeroed, then the scans run in file order, the restart segments of each on the pool
+// (jpeg_progressive.h holds the arithmetic).  A segment ends where the next one starts: what reads past it is truncated.
+inline int progressive_decode(dfd_handle* h, Parsed* P, int16_t* coef, const ScanLayout& L, bool inner) {
+    memset(coef, 0, L.total * 64 * sizeof(int16_t));
+    HostPool& pool = HostPool::get();
+    Destuffed ds;
+    for (size_t si = 0; si < P->scans.size(); ++si) {
+        const ProgScan& sc = P->scans[si];
+        try {
+            destuff(sc.data, P->end, &ds);
+        } catch (const std::bad_alloc&) {
+            return fail(h, DFD_ERR_CAPACITY, "decode_jpeg: out of host memory");
+        }
+        const size_t units = sc.g.units, per = sc.restart ? (size_t)sc.restart : units;
+        const size_t nseg = (units + per - 1) / per, payload = ds.nbits / 8;
+        if (ds.seg_start.size() < nseg) return fail(h, DFD_ERR_ARG, "decode_jpeg: restart marker missing in scan %zu", si);
+        std::atomic<int> bad{0};
+        const dfd_pj::PjHuff* tabs = P->ptabs.data() + sc.tab0;
+        auto one = [&](int sidx) {
+            const size_t u0 = (size_t)sidx * per, u1 = std::min(units, u0 + per);
+            const size_t b0 = ds.seg_start[sidx], b1 = (size_t)sidx + 1 < ds.seg_start.size() ? ds.seg_start[sidx + 1] : payload;
+            const int st = dfd_pj::pj_decode_segment(sc.g, tabs, ds.bytes.data(), b1, (uint64_t)b0 * 8, (uint32_t)u0, (uint32_t)u1, coef);
+            if (st) bad.store(st);
+        };
+        if (inner) pool.run((int)nseg, one);
+        else for (size_t i = 0; i < nseg; ++i) one((int)i);
+        if (bad.load())
+            return fail(h, DFD_ERR_ARG, "decode_jpeg: corrupt or truncated entropy-coded data in scan %zu (defect %d)", si, bad.load());
+    }
+    return DFD_OK;
+}
+
 // geometry of the scan: component block grids, MCU slots
 inline void scan_layout(Parsed* P, ScanLayout* L) {
     const int mcu_w = 8 * P->hmax, mcu_h = 8 * P->vmax;
@@ -686,10 +890,10 @@ inline int decode_scan(dfd_handle* h, Parsed* P, std::vector<int16_t>* coef, siz
 
 // dfd_jpeg_coefficients without the C ABI around it (dfd_hip.h: info[16], qtables 4 x 64, coefficients)
 inline int coefficients(const uint8_t* jpeg, size_t len, int* info, uint16_t* qtables_out, int16_t* coef_out, size_t capacity,
-                        size_t* count) {
+                        size_t* count, unsigned flags = 0) {
     if (!jpeg || !info || !count) return fail(nullptr, DFD_ERR_ARG, "jpeg_coefficients: null pointer");
     Parsed P;
-    int rc = parse_headers(nullptr, jpeg, len, &P);
+    int rc = parse_headers(nullptr, jpeg, len, &P, (flags & DFD_JPEG_ALLOW_PROGRESSIVE) != 0);
     if (rc) return rc;
     std::vector<int16_t> coef;
     size_t off[3] = {0, 0, 0};
