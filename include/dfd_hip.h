@@ -964,7 +964,8 @@ typedef struct dfd_mbconv_params {   /* torch layouts: exp_w [1152][192], dw_w [
  * depthwise activation), "b15.dout" [n][49][320] (the gradient of b15.out) and "b15.dae" [n][49][1152] (the gradient of
  * the expand activation).  Block 14 stays frozen: no gradient leaves the stage. */
 int dfd_head_train_unfreeze_block(dfd_handle* h, int block, const dfd_mbconv_params* init, float bn_momentum, float bn_eps);
-/* dfd_head_train_accumulate on n rows of block 14's output (2 <= n <= max_n) */
+/* dfd_head_train_accumulate on n input rows of the deepest unfrozen block (2 <= n <= max_n): block 14's output, or, once
+ * block 14 is unfrozen (dfd_head_train_unfreeze_block_at, below), block 13's */
 int dfd_head_train_accumulate_block(dfd_handle* h, const float* rows, int n, const float* labels_a, const float* labels_b,
                                     float lam, float loss_scale, float* loss_out, float* logits_out);
 /* dfd_head_train_eval on n such rows (1 <= n <= max_n): running statistics; per row, so any chunking gives the same bits */
@@ -1007,6 +1008,46 @@ int dfd_frequency_features_sized(dfd_handle* h, const unsigned char* img, int hh
  * unshifted; "dct" float [ky][kx], the coefficients before log1p.  capacity in bytes. */
 int dfd_frequency_features_tap(dfd_handle* h, const unsigned char* img, int hh, int ww, int stride, int channels, int size,
                                const char* name, void* out, size_t capacity);
+
+/* ---- fine-tuning block 14 with block 15, the head conv and the head -----------------------------
+ * net._blocks.14 (MBConv k5, stride 1, pad 2 / 2, 192 -> 1152 -> 192, squeeze-excite 48, 7 x 7) in train mode in front of
+ * block 15's stage: out = x13 + drop_connect(BN2(project(..))), efficientnet_pytorch's per-crop drop-connect.  Its input
+ * is block 13's output, float32 NHWC [n][7][7][192]: DFD_BLOCK14_ROW floats a crop again.
+ * In dfd_mbconv_params block 14's shapes are those of block 15 except dw_w [1152][5][5], proj_w [192][1152] and g2 / be2 /
+ * rm2 / rv2 [192]: 587 952 trainable floats.
+ *
+ * dfd_head_train_unfreeze_block_at adds block `block` below block 15: `block` must be 14 (any other:
+ * DFD_ERR_UNSUPPORTED); legal once, after dfd_head_train_unfreeze_block and before the first accumulate (anything else:
+ * DFD_ERR_ARG); a null field, bn_momentum outside [0, 1], bn_eps <= 0, drop_connect outside [0, 1) or NaN: DFD_ERR_ARG.
+ * One hipMalloc holds everything the stage needs for max_n crops; it is freed with the trainer and no later call
+ * allocates.  The Python side passes bn_momentum 0.01, bn_eps 1e-3 and drop_connect 0.2 * 14 / 16 (efficientnet-b0's
+ * drop_connect_rate times idx / len(blocks)).
+ * From here on the rows of dfd_head_train_accumulate_block / _eval_block are the input rows of the deepest unfrozen
+ * block: block 13's output.  A train-mode forward keeps crop i's branch with probability keep_prob = 1 - p, p the double
+ * of the float32 drop_connect: out = x13 + (y / keep_prob) b_i, b_i = head_training.dropout_keep_mask(seed, counter,
+ * layer = 3, n, width = 1, p)[i]; a dropped crop's output is its input row bit for bit, and it still counts in the batch
+ * statistics and running updates of the block's BatchNorms, which come before the mask.  Eval applies no drop-connect.
+ * Block 15 hands dOut14 = dZe15 . We15 down; BN2's gradient source is dOut14 b_i / keep_prob; block 13 stays frozen, so
+ * no gradient leaves block 14.  dfd_head_train_apply takes ONE gradient norm over the four arenas (partial sums added
+ * entry by entry: head, conv, block 15, block 14) and one clip coefficient; block 14 steps at lr * lr_scale with the same
+ * betas, eps and weight decay; EMA and zeroing cover it.  dfd_head_train_commit also folds block 14's three BatchNorms
+ * (float64, rounded once; dw.w re-laid [ky][kx][c] with 25 taps, se.w2 transposed) and overwrites the ten b14.* tensors
+ * and the cached splits of b14.exp.w and b14.proj.w in place.
+ * dfd_head_train_tap additionally knows "b14.out" [n][49][192] (the block's output after the skip: block 15's input),
+ * "b14.gate" [n][1152], "b14.ad" [n][49][1152], "b14.keep" [n] (the factor applied to each crop's branch, 0 or
+ * 1 / keep_prob), "b14.dout" [n][49][192] (the gradient arriving at b14.out) and "b14.dae" [n][49][1152]; without the
+ * stage they are DFD_ERR_ARG.  A trainer without the stage launches exactly what it launched before. */
+int dfd_head_train_unfreeze_block_at(dfd_handle* h, int block, const dfd_mbconv_params* init, float bn_momentum, float bn_eps,
+                                     float drop_connect);
+/* dfd_head_train_export_block / _block_grads for block 14 or 15 (15: the bits of those two); any other block:
+ * DFD_ERR_UNSUPPORTED; a block that is not unfrozen: DFD_ERR_ARG */
+int dfd_head_train_export_block_at(dfd_handle* h, int block, int use_ema, dfd_mbconv_params* out);
+int dfd_head_train_block_grads_at(dfd_handle* h, int block, dfd_mbconv_params* io, int set);
+/* dfd_extract_trunk_at / dfd_train_augment_trunk_at for block 13, 14 or 15: 14 and 15 give the bits of those entries, 13
+ * gives [n][7][7][192], the "b13.out" tap of the same forward.  Any other block: DFD_ERR_ARG. */
+int dfd_extract_block_out(dfd_handle* h, const float* nchw_host, int n, int block, float* out_host);
+int dfd_train_augment_block_out(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
+                                const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, int block, float* out_host);
 
 #ifdef __cplusplus
 }

@@ -201,6 +201,12 @@ SIGNATURES = {
     "dfd_head_train_eval_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dfd_head_train_export_block": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "dfd_head_train_block_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "dfd_head_train_unfreeze_block_at": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float]),
+    "dfd_head_train_export_block_at": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dfd_head_train_block_grads_at": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "dfd_extract_block_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dfd_train_augment_block_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_void_p]),
     "dfd_train_augment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dfd_train_augment_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),
@@ -299,6 +305,10 @@ BLOCK_STAT_FIELDS = ("rm0", "rv0", "rm1", "rv1", "rm2", "rv2")
 BLOCK_SHAPES = {"exp_w": (1152, 192), "dw_w": (1152, 3, 3), "se_w1": (48, 1152), "se_b1": (48,), "se_w2": (1152, 48),
                 "se_b2": (1152,), "proj_w": (320, 1152)}
 BLOCK_SHAPES.update({k + str(l): ((1152,) if l < 2 else (320,)) for l in range(3) for k in ("g", "be", "rm", "rv")})
+# block 14 in the same struct (k5, 192 -> 1152 -> 192); blocks 13 and 12 have these shapes too
+BLOCK14_SHAPES = dict(BLOCK_SHAPES, dw_w=(1152, 5, 5), proj_w=(192, 1152), g2=(192,), be2=(192,), rm2=(192,), rv2=(192,))
+BLOCK_SHAPES_AT = {15: BLOCK_SHAPES, 14: BLOCK14_SHAPES}
+BLOCK_OUT_SHAPES = {13: BLOCK14_SHAPE, 14: BLOCK14_SHAPE, 15: TRUNK_SHAPE}     # what `Handle.extract_block` returns per crop
 
 
 class MBConvParams(C.Structure):
@@ -306,16 +316,17 @@ class MBConvParams(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in BLOCK_FIELDS]
 
 
-def _block_arrays(arrays=None, skip=()):
-    """(MBConvParams, dict of the float32 arrays it points to); missing entries are allocated"""
+def _block_arrays(arrays=None, skip=(), block: int = 15):
+    """(MBConvParams, dict of the float32 arrays it points to); missing entries are allocated; `block`: whose shapes"""
     out, bp = {}, MBConvParams()
+    shapes = BLOCK_SHAPES_AT.get(int(block), BLOCK_SHAPES)
     for k in BLOCK_FIELDS:
         if k in skip:
             continue
         if arrays is not None and k in arrays:
-            a = np.ascontiguousarray(np.asarray(arrays[k], dtype=np.float32).reshape(BLOCK_SHAPES[k]))
+            a = np.ascontiguousarray(np.asarray(arrays[k], dtype=np.float32).reshape(shapes[k]))
         else:
-            a = np.zeros(BLOCK_SHAPES[k], np.float32)
+            a = np.zeros(shapes[k], np.float32)
         out[k] = a
         setattr(bp, k, a.ctypes.data)
     return bp, out
@@ -603,6 +614,14 @@ class Handle:
         self._check(self._lib.dfd_extract_trunk_at(self._p, _ptr(a), a.shape[0], int(block), _ptr(out)))
         return out
 
+    def extract_block(self, x, block: int) -> np.ndarray:
+        """the output of block 13, 14 or 15, float32 NHWC (`dfd_extract_block_out`): (n,7,7,192) for 13 and 14 - block 13's
+        are the rows block 14's stage trains on - and (n,7,7,320) for 15; any other block is refused"""
+        a = self._as_nchw(x)
+        out = np.empty((a.shape[0],) + BLOCK_OUT_SHAPES.get(int(block), TRUNK_SHAPE), dtype=np.float32)
+        self._check(self._lib.dfd_extract_block_out(self._p, _ptr(a), a.shape[0], int(block), _ptr(out)))
+        return out
+
     # -- train-time augmentation (include/dfd_hip.h "train-time image augmentation"; train_augment.draw_batch makes the tables)
     @staticmethod
     def _aug_tables(n, rows, batch):
@@ -699,6 +718,18 @@ class Handle:
         """`train_augment_trunk(block=14)`: the extractor of a trainer with block 15 unfrozen"""
         return self.train_augment_trunk(rgb, rows, batch, shape, block=14)
 
+    def train_augment_block(self, rgb, rows, batch, shape=None, block: int = 13) -> np.ndarray:
+        """`train_augment_features` with the output of block 13, 14 or 15 in place of the pooled rows
+        (`dfd_train_augment_block_out`)"""
+        def fn(p, src, on_device, n, hh, ww, r, b, out):
+            return self._lib.dfd_train_augment_block_out(p, src, on_device, n, hh, ww, r, b, int(block), out)
+
+        return self._train_augment_forward(fn, BLOCK_OUT_SHAPES.get(int(block), TRUNK_SHAPE), rgb, rows, batch, shape)
+
+    def train_augment_block13(self, rgb, rows, batch, shape=None) -> np.ndarray:
+        """`train_augment_block(block=13)`: the extractor of a trainer with block 14 unfrozen"""
+        return self.train_augment_block(rgb, rows, batch, shape, block=13)
+
     # -- head training (include/dfd_hip.h "classifier head training"; head_training.HeadTrainer is the front end)
     @staticmethod
     def _as_features(x) -> np.ndarray:
@@ -759,7 +790,8 @@ class Handle:
     def head_train_tap(self, name: str, n: int) -> np.ndarray:
         width = {"mask0": 1280, "mask1": 512, "mask2": 256, "z1": 512, "z2": 256, "a1": 512, "a2": 256}.get(name, 1280)   # unknown names: the library refuses
         wide = {"cz": (49, 1280), "b15.out": (49, 320), "b15.dout": (49, 320), "b15.ad": (49, 1152), "b15.dae": (49, 1152),
-                "b15.gate": (1152,)}
+                "b15.gate": (1152,), "b14.out": (49, 192), "b14.dout": (49, 192), "b14.ad": (49, 1152), "b14.dae": (49, 1152),
+                "b14.gate": (1152,), "b14.keep": ()}
         out = np.empty((int(n),) + wide.get(name, (width,)), np.float32)
         self._check(self._lib.dfd_head_train_tap(self._p, name.encode(), _ptr(out), out.size))
         return out
@@ -869,6 +901,32 @@ class Handle:
             self._check(self._lib.dfd_head_train_block_grads(self._p, C.byref(bp), 1))
         bp, out = _block_arrays(None, BLOCK_STAT_FIELDS)
         self._check(self._lib.dfd_head_train_block_grads(self._p, C.byref(bp), 0))
+        return out
+
+    # -- block 14 of the head trainer (include/dfd_hip.h "fine-tuning block 14 with block 15, the head conv and the head");
+    #    once it is unfrozen `head_train_accumulate_block` / `_eval_block` take rows of block 13's output (the same width)
+    def head_train_unfreeze_block_at(self, params, block: int = 14, bn_momentum: float = 0.01, bn_eps: float = 1e-3,
+                                     drop_connect: float = 0.2 * 14 / 16):
+        """params: dict of the 19 `BLOCK_FIELDS` arrays in block 14's shapes (`BLOCK14_SHAPES`)"""
+        missing = [k for k in BLOCK_FIELDS if k not in params]
+        if missing:
+            raise KeyError(f"block parameters missing: {missing}")
+        bp, _keep = _block_arrays(params, block=14)
+        self._check(self._lib.dfd_head_train_unfreeze_block_at(self._p, int(block), C.byref(bp), float(bn_momentum), float(bn_eps),
+                                                               float(drop_connect)))
+
+    def head_train_export_block_at(self, block: int, use_ema: bool = False):
+        bp, out = _block_arrays(block=block)
+        self._check(self._lib.dfd_head_train_export_block_at(self._p, int(block), int(bool(use_ema)), C.byref(bp)))
+        return out
+
+    def head_train_block_grads_at(self, block: int, set_to=None):
+        """`head_train_block_grads` of block 14 or 15"""
+        if set_to is not None:
+            bp, _keep = _block_arrays(set_to, BLOCK_STAT_FIELDS, block)
+            self._check(self._lib.dfd_head_train_block_grads_at(self._p, int(block), C.byref(bp), 1))
+        bp, out = _block_arrays(None, BLOCK_STAT_FIELDS, block)
+        self._check(self._lib.dfd_head_train_block_grads_at(self._p, int(block), C.byref(bp), 0))
         return out
 
     def tap(self, x_dev: int, n: int, name: str, capacity: int) -> np.ndarray:

@@ -41,21 +41,7 @@ static_assert(HT_THREADS == HT_H2, "ht_loss_kernel: one thread per column of w3"
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-__host__ __device__ inline uint32_t fmix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-    return x;
-}
-// head_training.dropout_keep_mask is the specification of these two
-inline uint32_t mask_key(unsigned long long seed, unsigned long long counter, int layer) {
-    uint32_t k = fmix32((uint32_t)seed + 0x9E3779B9u);
-    k = fmix32(k ^ (uint32_t)(seed >> 32));
-    k = fmix32(k ^ (uint32_t)counter);
-    k = fmix32(k ^ (uint32_t)(counter >> 32));
-    return fmix32(k ^ (uint32_t)(layer + 1));
-}
-__device__ __forceinline__ bool mask_keep(uint32_t key, uint32_t idx, uint32_t thr) {
-    return fmix32(fmix32(idx ^ key) + key) >= thr;
-}
+// fmix32 / mask_key / mask_keep: head_train_state.h
 
 // ---------------------------------------------------------------------------------------------- forward
 __global__ __launch_bounds__(HT_THREADS) void ht_dropout0_kernel(const float* __restrict__ x, float* __restrict__ y,
@@ -414,12 +400,13 @@ __global__ __launch_bounds__(HT_THREADS) void ht_sumsq_kernel(const float* __res
 
 // clip_grad_norm_ + torch.optim.AdamW (single-tensor path, in its order) + EMAModel.update + zero_grad, one element per thread.
 // decay_mul = 1 - lr wd, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t): computed on the host in double.
-// The squared norm is the sum of partial[] (and, entry by entry, partial2[] then partial3[] when given).
+// The squared norm is the sum of partial[] (and, entry by entry, partial2[], partial3[] then partial4[] when given).
 __global__ __launch_bounds__(HT_THREADS) void ht_adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                               float* __restrict__ v, float* __restrict__ ema, int count,
                                                               const double* __restrict__ partial,
                                                               const double* __restrict__ partial2,
-                                                              const double* __restrict__ partial3, float clip_norm,
+                                                              const double* __restrict__ partial3,
+                                                              const double* __restrict__ partial4, float clip_norm,
                                                               float decay_mul, float w1, float beta2, float w2, float step_size,
                                                               float bc2_sqrt, float eps, float ema_decay, float ema_w,
                                                               float* __restrict__ norm_out) {
@@ -428,6 +415,7 @@ __global__ __launch_bounds__(HT_THREADS) void ht_adamw_kernel(float* __restrict_
     double mine = partial[threadIdx.x];
     if (partial2) mine += partial2[threadIdx.x];                // the conv stage's arena: one norm over both groups
     if (partial3) mine += partial3[threadIdx.x];                // block 15's arena: one norm over all three
+    if (partial4) mine += partial4[threadIdx.x];                // block 14's arena: one norm over all four
     const float norm = (float)sqrt(block_sum(mine, sh));
     const float coef = fminf(clip_norm / (norm + 1e-6f), 1.f);
     const int i = blockIdx.x * HT_THREADS + threadIdx.x;
@@ -467,11 +455,11 @@ void head_train_launch_sumsq(hipStream_t s, const float* g, int count, double* p
 }
 
 void head_train_launch_adamw(hipStream_t s, float* p, float* g, float* m, float* v, float* ema, int count, const double* partial,
-                             const double* partial2, const double* partial3, const dfd_head_config& c, double lr, double t,
-                             float* norm_out) {
+                             const double* partial2, const double* partial3, const double* partial4, const dfd_head_config& c,
+                             double lr, double t, float* norm_out) {
     const double bc1 = 1.0 - std::pow((double)c.beta1, t), bc2 = 1.0 - std::pow((double)c.beta2, t);
     hipLaunchKernelGGL(ht_adamw_kernel, dim3((count + HT_THREADS - 1) / HT_THREADS), dim3(HT_THREADS), 0, s, p, g, m, v, ema, count,
-                       partial, partial2, partial3, c.clip_norm, (float)(1.0 - lr * (double)c.weight_decay), (float)(1.0 - (double)c.beta1),
+                       partial, partial2, partial3, partial4, c.clip_norm, (float)(1.0 - lr * (double)c.weight_decay), (float)(1.0 - (double)c.beta1),
                        c.beta2, (float)(1.0 - (double)c.beta2), (float)(lr / bc1), (float)std::sqrt(bc2), c.eps, c.ema_decay,
                        (float)(1.0 - (double)c.ema_decay), norm_out);
 }
@@ -696,8 +684,9 @@ int dfd_head_train_apply(dfd_handle* h, float lr, float* grad_norm_out) {
     head_train_launch_sumsq(h->stream, S->grad, HT_COUNT, S->partial);
     const double* partial2 = S->conv ? headconv_sumsq(h, S) : nullptr;          // one norm over all groups
     const double* partial3 = S->block ? headblock_sumsq(h, S) : nullptr;
-    head_train_launch_adamw(h->stream, S->param, S->grad, S->m, S->v, S->ema, HT_COUNT, S->partial, partial2, partial3, S->cfg,
-                            (double)lr, t, S->scalars + 1);
+    const double* partial4 = S->block14 ? headblock_sumsq(h, S, 14) : nullptr;
+    head_train_launch_adamw(h->stream, S->param, S->grad, S->m, S->v, S->ema, HT_COUNT, S->partial, partial2, partial3, partial4,
+                            S->cfg, (double)lr, t, S->scalars + 1);
     if (S->conv) headconv_adamw(h, S, (double)lr, t);
     if (S->block) headblock_adamw(h, S, (double)lr, t);
     DFD_HIP_TRY(h, hipGetLastError());
@@ -763,7 +752,7 @@ int dfd_head_train_tap(dfd_handle* h, const char* name, float* out, size_t capac
     if (!name || !out) return fail(h, DFD_ERR_ARG, "head_train_tap: null pointer");
     if (S->last_n == 0) return fail(h, DFD_ERR_ARG, "head_train_tap: no accumulate has run yet");
     if (!strcmp(name, "cfeat") || !strcmp(name, "dfeat") || !strcmp(name, "cz")) return headconv_tap(h, S, name, out, capacity);
-    if (!strncmp(name, "b15.", 4)) return headblock_tap(h, S, name, out, capacity);
+    if (!strncmp(name, "b15.", 4) || !strncmp(name, "b14.", 4)) return headblock_tap(h, S, name, out, capacity);
     const uint8_t* mask = nullptr;
     const float* act = nullptr;
     int width = 0;
@@ -795,7 +784,7 @@ int dfd_head_train_commit(dfd_handle* h, int use_ema) {
     HeadTrainState* S = open_state(h, "head_train_commit", &rc);
     if (!S) return rc;
     DFD_HIP_TRY(h, hipSetDevice(h->device));
-    if (S->block && (rc = headblock_commit(h, S, use_ema))) return rc;         // block 15's three BatchNorms folded, b15.*
+    if (S->block && (rc = headblock_commit(h, S, use_ema))) return rc;         // the blocks' BatchNorms folded, b15.* / b14.*
     if (S->conv && (rc = headconv_commit(h, S, use_ema))) return rc;           // _bn1 folded into _conv_head, head.w / head.b
     std::vector<float> P(HT_COUNT), rm1(HT_H1), rv1(HT_H1), rm2(HT_H2), rv2(HT_H2);
     DFD_HIP_TRY(h, hipMemcpyAsync(P.data(), use_ema ? S->ema : S->param, (size_t)HT_COUNT * 4, hipMemcpyDeviceToHost, h->stream));

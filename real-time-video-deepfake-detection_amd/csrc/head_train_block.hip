@@ -12,7 +12,14 @@
 //   dyd = (dt gate + ds / 49) swish'(yd), BN1 backward -> dZd (stored over dt)                bk_dz_store_kernel
 //   dWd   bk_dw_wgrad_kernel + bk_dw_wreduce_kernel;   dae = dZd correlated with the flipped kernel   bk_dw_bwd_kernel
 //   dye = dae swish'(ye), BN0 backward: dZe formed at the load;  dWe += dZe^T X   wgrad<6, false>
-// Block 14 is frozen: no gradient with respect to X.
+// Without block 14's stage no gradient with respect to X is formed.
+//
+// Block 14 (dfd_head_train_unfreeze_block_at): net._blocks.14 (MBConv k5, pad 2, 192 -> 1152 -> 192, the identity skip with
+// per-crop drop-connect) runs the same launches in front of block 15 on a second state, through the geometry parameter
+// (Geo: kernel size, output width, skip) the host functions below are instantiated with.  Its last forward launch
+// (bk_bn_skip_kernel) writes out = x13 + (BN2(Zp) / keep_prob) b_i into block 15's input buffer; block 15's backward then
+// ends with dOut14 = dZe15 . We15 (gemm_dyw<6, Grad0>), and block 14's BN2 takes dOut14 b_i / keep_prob as its gradient
+// source (Grad2<true>).  Block 13 is frozen: no gradient leaves block 14.  Blocks 13 and 12 have block 14's geometry.
 //
 // Arithmetic as head_train_conv.hip: the GEMMs run on the fp64 MFMA with fp32 operands widened at the load
 // (head_train_gemm.h), every other element is computed in double from stored fp32 values and rounded once where it is
@@ -20,6 +27,7 @@
 // (r, q, du, dr, ds) stay in double.  Every reduction has a fixed order and no atomics: channel statistics over 256-row
 // chunks, weight gradients over 512-row chunks, the depthwise weight gradient over 8-crop chunks, the squeeze-excite
 // weight gradients over the crops one by one - added in that order, in double.  Built with -ffp-contract=off.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -38,20 +46,42 @@ using namespace dfd::ht64;
 
 namespace {
 
-constexpr int BK_IN = 192, BK_EXP = 1152, BK_SE = 48, BK_OUT = 320, BK_HW = 49, BK_H = 7, BK_ROW = BK_HW * BK_IN, BK_INDEX = 15;
-// the block group's arena (floats); every offset a multiple of 4
-constexpr int BO_WE = 0, BO_WD = BO_WE + BK_EXP * BK_IN, BO_W1 = BO_WD + BK_EXP * 9, BO_B1 = BO_W1 + BK_SE * BK_EXP;
-constexpr int BO_W2 = BO_B1 + BK_SE, BO_B2 = BO_W2 + BK_EXP * BK_SE, BO_WP = BO_B2 + BK_EXP, BO_G0 = BO_WP + BK_OUT * BK_EXP;
-constexpr int BO_BE0 = BO_G0 + BK_EXP, BO_G1 = BO_BE0 + BK_EXP, BO_BE1 = BO_G1 + BK_EXP, BO_G2 = BO_BE1 + BK_EXP;
-constexpr int BO_BE2 = BO_G2 + BK_OUT, BK_COUNT = BO_BE2 + BK_OUT;
-static_assert(BK_COUNT == 717232, "trainable floats of block 15");
-constexpr int BK_JE = 6, BK_JP = 5;       // column tiles a wave: 1152 = 12 x 96, 320 = 4 x 80
+// what blocks 12-15 share: 192 -> 1152, squeeze-excite 48, 7 x 7
+constexpr int BK_IN = 192, BK_EXP = 1152, BK_SE = 48, BK_HW = 49, BK_H = 7, BK_ROW = BK_HW * BK_IN;
+constexpr int BK_JE = 6;                  // column tiles a wave over 1152 = 12 x 96
 constexpr int BK_DW_CROPS = 8;            // crops of one partial depthwise weight gradient
-static_assert(BK_EXP % (16 * BK_JE) == 0 && BK_OUT % (16 * BK_JP) == 0 && BK_IN % 16 == 0 && BK_EXP % 64 == 0 && BK_OUT % 64 == 0, "tiles");
-static_assert((BK_OUT / 16 * (BK_EXP / (16 * BK_JE))) % 4 == 0 && (BK_EXP / 16 * (BK_IN / (16 * BK_JE))) % 4 == 0, "weight-gradient grids");
-static_assert(BK_OUT % 16 == 0, "gemm_dyw splits its channels over four waves");
-static_assert(BK_OUT == 320 && DFD_TRUNK_ROW == BK_HW * BK_OUT, "the block's output is the conv stage's row");
-const int kBnC[3] = {BK_EXP, BK_EXP, BK_OUT};
+// A block's geometry: its index, depthwise kernel size (pad KS / 2), output width, whether it has the identity skip, and JP,
+// the column tiles a wave of the projection's forward GEMM.  The block group's arena (floats); every offset a multiple of 4.
+template <int INDEX, int KS_, int OUT_, bool SKIP_, int JP_>
+struct Geo {
+    static constexpr int INDEX_ = INDEX, KS = KS_, TAPS = KS_ * KS_, PAD = KS_ / 2, OUT = OUT_, JP = JP_;
+    static constexpr bool SKIP = SKIP_;
+    static constexpr int O_WE = 0, O_WD = O_WE + BK_EXP * BK_IN, O_W1 = O_WD + BK_EXP * TAPS, O_B1 = O_W1 + BK_SE * BK_EXP;
+    static constexpr int O_W2 = O_B1 + BK_SE, O_B2 = O_W2 + BK_EXP * BK_SE, O_WP = O_B2 + BK_EXP, O_G0 = O_WP + OUT * BK_EXP;
+    static constexpr int O_BE0 = O_G0 + BK_EXP, O_G1 = O_BE0 + BK_EXP, O_BE1 = O_G1 + BK_EXP, O_G2 = O_BE1 + BK_EXP;
+    static constexpr int O_BE2 = O_G2 + OUT, COUNT = O_BE2 + OUT;
+    static_assert(BK_EXP % (16 * BK_JE) == 0 && OUT % (16 * JP) == 0 && BK_IN % 16 == 0 && BK_EXP % 64 == 0 && OUT % 64 == 0, "tiles");
+    static_assert((OUT / 16 * (BK_EXP / (16 * BK_JE))) % 4 == 0 && (BK_EXP / 16 * (BK_IN / (16 * BK_JE))) % 4 == 0, "weight-gradient grids");
+    static_assert(OUT % 16 == 0, "gemm_dyw splits its channels over four waves");
+    static_assert(O_WD % 4 == 0 && O_W1 % 4 == 0 && O_W2 % 4 == 0 && O_WP % 4 == 0, "weight rows must stay 16-byte aligned");
+};
+typedef Geo<15, 3, 320, false, 5> G15;    // 320 = 4 x 80
+typedef Geo<14, 5, 192, true, 6> G14;     // 192 = 2 x 96; blocks 13 and 12 have this geometry too
+static_assert(G15::COUNT == 717232, "trainable floats of block 15");
+static_assert(G14::COUNT == 587952, "trainable floats of block 14");
+static_assert(DFD_TRUNK_ROW == BK_HW * G15::OUT, "block 15's output is the conv stage's row");
+static_assert(G14::OUT == BK_IN && BK_IN % (16 * BK_JE) == 0, "block 14's output is block 15's input; dOut14 = dZe15 . We15 in 96-column tiles");
+// the same at run time, for the host code that only moves tensors
+struct Layout {
+    int index, ks, taps, out;
+    bool skip;
+    int o_we, o_wd, o_w1, o_b1, o_w2, o_b2, o_wp, o_g[3], o_be[3], count, bnc[3];
+};
+template <class G>
+Layout layout_of() {
+    return Layout{G::INDEX_, G::KS, G::TAPS, G::OUT, G::SKIP, G::O_WE, G::O_WD, G::O_W1, G::O_B1, G::O_W2, G::O_B2, G::O_WP,
+                  {G::O_G0, G::O_G1, G::O_G2}, {G::O_BE0, G::O_BE1, G::O_BE2}, G::COUNT, {BK_EXP, BK_EXP, G::OUT}};
+}
 
 // ---------------------------------------------------------------------------------------------- forward
 // ae = swish(BN(Ze)), one thread per element
@@ -74,6 +104,24 @@ __global__ __launch_bounds__(HT_THREADS) void bk_bn_kernel(const float* __restri
     out[i] = (float)((((double)Z[i] - k.mean) * k.istd) * k.gamma + k.beta);
 }
 
+// Block 14's output: out = x + (BN(Zp) / keep_prob) b_i (efficientnet_pytorch's drop_connect), in double, rounded once.
+// keep [crop] != 0 where b_i = 1 (null: every crop kept - eval, with keep_prob = 1); a dropped crop's output is its input
+// row bit for bit.  X and out are different buffers.
+__global__ __launch_bounds__(HT_THREADS) void bk_bn_skip_kernel(const float* __restrict__ Z, BnC bn, const float* __restrict__ X,
+                                                                const float* __restrict__ keep, double keep_prob,
+                                                                float* __restrict__ out, size_t total, int C) {
+    const size_t i = (size_t)blockIdx.x * HT_THREADS + threadIdx.x;
+    if (i >= total) return;
+    if (keep && keep[i / ((size_t)BK_HW * C)] == 0.f) {
+        out[i] = X[i];
+        return;
+    }
+    const int c = (int)(i % C);
+    const BnK k = bn.load(c);
+    const double y = (((double)Z[i] - k.mean) * k.istd) * k.gamma + k.beta;
+    out[i] = (float)((double)X[i] + y / keep_prob);
+}
+
 // eval mode: the running statistics in the place of the batch's
 __global__ __launch_bounds__(HT_THREADS) void bk_eval_consts_kernel(const float* __restrict__ rm, const float* __restrict__ rv, double eps,
                                                                     double* __restrict__ mean, double* __restrict__ istd, int C) {
@@ -83,8 +131,10 @@ __global__ __launch_bounds__(HT_THREADS) void bk_eval_consts_kernel(const float*
     istd[c] = 1.0 / sqrt((double)rv[c] + eps);
 }
 
-// Depthwise 3 x 3, pad 1, on [n][7][7][1152]: one thread per output element, channels fastest; the 9 taps in (ky, kx)
-// order in double.  W [c][ky][kx] (torch's layout).
+// Depthwise KS x KS, pad KS / 2, on [n][7][7][1152]: one thread per output element, channels fastest; the KS KS taps in
+// (ky, kx) order in double, taps outside the 7 x 7 left out (at KS = 5 every position has some, 16 of 25 in the corners).
+// W [c][ky][kx] (torch's layout).
+template <int KS>
 __global__ __launch_bounds__(HT_THREADS) void bk_dw_fwd_kernel(const float* __restrict__ A, const float* __restrict__ W,
                                                                float* __restrict__ Z, size_t total) {
     const size_t i = (size_t)blockIdx.x * HT_THREADS + threadIdx.x;
@@ -93,12 +143,12 @@ __global__ __launch_bounds__(HT_THREADS) void bk_dw_fwd_kernel(const float* __re
     const size_t base = i - (size_t)p * BK_EXP;                  // position 0 of this crop, channel c
     double s = 0.0;
 #pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
+    for (int ky = 0; ky < KS; ++ky) {
 #pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const int yy = y + ky - 1, xx = x + kx - 1;
+        for (int kx = 0; kx < KS; ++kx) {
+            const int yy = y + ky - KS / 2, xx = x + kx - KS / 2;
             if (yy < 0 || yy >= BK_H || xx < 0 || xx >= BK_H) continue;
-            s += (double)A[base + (size_t)(yy * BK_H + xx) * BK_EXP] * (double)W[c * 9 + ky * 3 + kx];
+            s += (double)A[base + (size_t)(yy * BK_H + xx) * BK_EXP] * (double)W[c * (KS * KS) + ky * KS + kx];
         }
     }
     Z[i] = (float)s;
@@ -157,16 +207,22 @@ __global__ __launch_bounds__(HT_THREADS) void bk_se_fwd_kernel(const float* __re
 }
 
 // ---------------------------------------------------------------------------------------------- gradient sources
-// BN2: dy is the stored dX15
+// BN2: dy is the stored gradient of the block's output (dX15); with the skip (SKIP) that gradient times the crop's
+// drop-connect factor, dOut14 b_i / keep_prob: exactly zero on a dropped crop
+template <bool SKIP>
 struct Grad2 {
     typedef BnK K;
     BnC bn;
     const float *Zp, *dX;
+    int out;
+    const float* keep;
+    double keep_prob;
     __device__ __forceinline__ K load(int c) const { return bn.load(c); }
     __device__ __forceinline__ void dy_xh(const K& k, size_t row, int c, double* dy, double* xh) const {
-        const size_t o = row * BK_OUT + c;
+        const size_t o = row * out + c;
         *xh = ((double)Zp[o] - k.mean) * k.istd;
-        *dy = (double)dX[o];
+        if constexpr (SKIP) *dy = keep[row / BK_HW] == 0.f ? 0.0 : (double)dX[o] / keep_prob;
+        else *dy = (double)dX[o];
     }
 };
 // BN1: dad = dt gate + ds / 49 through swish'(yd)
@@ -270,7 +326,9 @@ __global__ __launch_bounds__(HT_THREADS) void bk_dz_store_kernel(Grad1 g, float*
     out[i] = (float)bn_dz(g, k, i / BK_EXP, c);
 }
 
-// dae [y][x] = sum over (ky, kx) of dZd [y - ky + 1][x - kx + 1] W [ky][kx]: the correlation with the flipped kernel, pad 1
+// dae [y][x] = sum over (ky, kx) of dZd [y - ky + KS / 2][x - kx + KS / 2] W [ky][kx]: the correlation with the flipped
+// kernel, pad KS / 2
+template <int KS>
 __global__ __launch_bounds__(HT_THREADS) void bk_dw_bwd_kernel(const float* __restrict__ dZ, const float* __restrict__ W,
                                                                float* __restrict__ dA, size_t total) {
     const size_t i = (size_t)blockIdx.x * HT_THREADS + threadIdx.x;
@@ -279,48 +337,51 @@ __global__ __launch_bounds__(HT_THREADS) void bk_dw_bwd_kernel(const float* __re
     const size_t base = i - (size_t)p * BK_EXP;
     double s = 0.0;
 #pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
+    for (int ky = 0; ky < KS; ++ky) {
 #pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const int yy = y - ky + 1, xx = x - kx + 1;
+        for (int kx = 0; kx < KS; ++kx) {
+            const int yy = y - ky + KS / 2, xx = x - kx + KS / 2;
             if (yy < 0 || yy >= BK_H || xx < 0 || xx >= BK_H) continue;
-            s += (double)dZ[base + (size_t)(yy * BK_H + xx) * BK_EXP] * (double)W[c * 9 + ky * 3 + kx];
+            s += (double)dZ[base + (size_t)(yy * BK_H + xx) * BK_EXP] * (double)W[c * (KS * KS) + ky * KS + kx];
         }
     }
     dA[i] = (float)s;
 }
 
 // Partial depthwise weight gradient of crops [8 chunk, 8 (chunk + 1)) n [0, n): P [chunk][tap][c] = sum over those crops
-// and the positions (crop, then position order) of dZd [y][x] ae [y + ky - 1][x + kx - 1].  grid (ceil(1152 / 256), 9, chunks).
+// and the positions (crop, then position order) of dZd [y][x] ae [y + ky - KS / 2][x + kx - KS / 2].
+// grid (ceil(1152 / 256), KS KS, chunks).
+template <int KS>
 __global__ __launch_bounds__(HT_THREADS) void bk_dw_wgrad_kernel(const float* __restrict__ dZ, const float* __restrict__ A,
                                                                  double* __restrict__ P, int n) {
-    const int c = blockIdx.x * HT_THREADS + threadIdx.x, tap = blockIdx.y, ky = tap / 3, kx = tap % 3;
+    const int c = blockIdx.x * HT_THREADS + threadIdx.x, tap = blockIdx.y, ky = tap / KS, kx = tap % KS;
     if (c >= BK_EXP) return;
     const int i0 = blockIdx.z * BK_DW_CROPS, i1 = min(n, i0 + BK_DW_CROPS);
     double s = 0.0;
     for (int i = i0; i < i1; ++i) {
         const size_t base = (size_t)i * BK_HW * BK_EXP + c;
         for (int y = 0; y < BK_H; ++y) {
-            const int yy = y + ky - 1;
+            const int yy = y + ky - KS / 2;
             if (yy < 0 || yy >= BK_H) continue;
             for (int x = 0; x < BK_H; ++x) {
-                const int xx = x + kx - 1;
+                const int xx = x + kx - KS / 2;
                 if (xx < 0 || xx >= BK_H) continue;
                 s += (double)dZ[base + (size_t)(y * BK_H + x) * BK_EXP] * (double)A[base + (size_t)(yy * BK_H + xx) * BK_EXP];
             }
         }
     }
-    P[((size_t)blockIdx.z * 9 + tap) * BK_EXP + c] = s;
+    P[((size_t)blockIdx.z * (KS * KS) + tap) * BK_EXP + c] = s;
 }
 
 // G [c][tap] += the chunks' partials added in chunk order, rounded once
-__global__ __launch_bounds__(HT_THREADS) void bk_dw_wreduce_kernel(const double* __restrict__ P, int chunks, float* __restrict__ G) {
+__global__ __launch_bounds__(HT_THREADS) void bk_dw_wreduce_kernel(const double* __restrict__ P, int chunks, float* __restrict__ G,
+                                                                   int taps) {
     const int e = blockIdx.x * HT_THREADS + threadIdx.x;
-    if (e >= BK_EXP * 9) return;
+    if (e >= BK_EXP * taps) return;
     const int tap = e / BK_EXP, c = e % BK_EXP;
     double s = 0.0;
-    for (int k = 0; k < chunks; ++k) s += P[((size_t)k * 9 + tap) * BK_EXP + c];
-    G[c * 9 + tap] += (float)s;
+    for (int k = 0; k < chunks; ++k) s += P[((size_t)k * taps + tap) * BK_EXP + c];
+    G[c * taps + tap] += (float)s;
 }
 
 }  // namespace
@@ -329,52 +390,82 @@ __global__ __launch_bounds__(HT_THREADS) void bk_dw_wreduce_kernel(const double*
 namespace dfd {
 
 struct HeadBlockState {
+    Layout L{};
     float momentum = 0.01f;
     double eps = 1e-3;
     float *param = nullptr, *grad = nullptr, *m = nullptr, *v = nullptr, *ema = nullptr;
     float *rm[3] = {nullptr, nullptr, nullptr}, *rv[3] = {nullptr, nullptr, nullptr};
-    // fp32 tensors of m rows: the input, Ze, ae, Zd, ad, dt then dZd (d1), dae (d2), Zp, dX15; per crop: the pooled s, gate
+    // fp32 tensors of m rows: the input, Ze, ae, Zd, ad, dt then dZd (d1), dae (d2), Zp, the gradient of the block's output
+    // (dx: dX15, or dOut14); per crop: the pooled s, gate
     float *x = nullptr, *ze = nullptr, *ae = nullptr, *zd = nullptr, *ad = nullptr, *d1 = nullptr, *d2 = nullptr, *zp = nullptr,
-          *dx15 = nullptr, *pooled = nullptr, *gate = nullptr;
+          *dx = nullptr, *pooled = nullptr, *gate = nullptr;
     double *mean[3] = {nullptr, nullptr, nullptr}, *istd[3] = {nullptr, nullptr, nullptr}, *sdy[3] = {nullptr, nullptr, nullptr},
            *sdx[3] = {nullptr, nullptr, nullptr};
     double *spart = nullptr, *spart2 = nullptr, *wpart = nullptr, *dwpart = nullptr, *partial = nullptr;
     double *r = nullptr, *q = nullptr, *du = nullptr, *dr = nullptr, *ds = nullptr;
+    // the skip's drop-connect (block 14): rate, 1 - rate, floor(rate 2^32); per crop the factor of the last accumulate, 0 or
+    // 1 / keep_prob ("b14.keep"), on the device and as it was uploaded; the norm this arena's AdamW launch writes
+    double drop_p = 0.0, keep_prob = 1.0;
+    uint32_t drop_thr = 0;
+    float *keep = nullptr, *norm = nullptr;
+    std::vector<float> keep_host;
     void* pool = nullptr;
 };
 
-void headblock_destroy(HeadTrainState* S) {
-    HeadBlockState* K = S->block;
+namespace {
+void destroy_one(HeadBlockState** slot) {
+    HeadBlockState* K = *slot;
     if (!K) return;
     if (K->pool) hipFree(K->pool);
     delete K;
-    S->block = nullptr;
+    *slot = nullptr;
+}
+HeadBlockState* stage_of(HeadTrainState* S, int block) { return block == 14 ? S->block14 : S->block; }
+}  // namespace
+
+void headblock_destroy(HeadTrainState* S) {
+    destroy_one(&S->block14);
+    destroy_one(&S->block);
 }
 
-const double* headblock_sumsq(dfd_handle* h, HeadTrainState* S) {
-    head_train_launch_sumsq(h->stream, S->block->grad, BK_COUNT, S->block->partial);
-    return S->block->partial;
+const double* headblock_sumsq(dfd_handle* h, HeadTrainState* S, int block) {
+    HeadBlockState* K = stage_of(S, block);
+    head_train_launch_sumsq(h->stream, K->grad, K->L.count, K->partial);
+    return K->partial;
 }
 
-const double* headblock_partial(HeadTrainState* S) { return S->block->partial; }
+const double* headblock_partial(HeadTrainState* S, int block) {
+    HeadBlockState* K = stage_of(S, block);
+    return K ? K->partial : nullptr;
+}
 
 void headblock_adamw(dfd_handle* h, HeadTrainState* S, double lr, double t) {
-    HeadBlockState* K = S->block;
-    // the three arenas' partials in the order of the other two launches: all three see the same norm
-    head_train_launch_adamw(h->stream, K->param, K->grad, K->m, K->v, K->ema, BK_COUNT, S->partial, headconv_partial(S), K->partial,
+    HeadBlockState *K = S->block, *K14 = S->block14;
+    // the arenas' partials in the order of the other launches (head, conv, block 15, block 14): all see the same norm
+    const double* p4 = K14 ? K14->partial : nullptr;
+    head_train_launch_adamw(h->stream, K->param, K->grad, K->m, K->v, K->ema, K->L.count, S->partial, headconv_partial(S), K->partial, p4,
                             S->cfg, lr * (double)headconv_lr_scale(S), t, S->scalars + 3);
+    if (K14)
+        head_train_launch_adamw(h->stream, K14->param, K14->grad, K14->m, K14->v, K14->ema, K14->L.count, S->partial, headconv_partial(S),
+                                K->partial, p4, S->cfg, lr * (double)headconv_lr_scale(S), t, K14->norm);
 }
 
 int headblock_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out, size_t capacity) {
-    HeadBlockState* K = S->block;
-    if (!K) return fail(h, DFD_ERR_ARG, "head_train_tap: '%s' needs block 15's stage (dfd_head_train_unfreeze_block)", name);
+    const bool b14 = !strncmp(name, "b14.", 4);
+    HeadBlockState* K = b14 ? S->block14 : S->block;
+    if (!K)
+        return fail(h, DFD_ERR_ARG, "head_train_tap: '%s' needs block %d's stage (%s)", name, b14 ? 14 : 15,
+                    b14 ? "dfd_head_train_unfreeze_block_at" : "dfd_head_train_unfreeze_block");
     const float* src = nullptr;
     size_t per = 0;
-    if (!strcmp(name, "b15.out")) { src = headconv_rows(S); per = (size_t)BK_HW * BK_OUT; }
-    else if (!strcmp(name, "b15.gate")) { src = K->gate; per = BK_EXP; }
-    else if (!strcmp(name, "b15.ad")) { src = K->ad; per = (size_t)BK_HW * BK_EXP; }
-    else if (!strcmp(name, "b15.dout")) { src = K->dx15; per = (size_t)BK_HW * BK_OUT; }
-    else if (!strcmp(name, "b15.dae")) { src = K->d2; per = (size_t)BK_HW * BK_EXP; }
+    const char* what = name + 4;
+    // a block's output lives in the next stage's input buffer
+    if (!strcmp(what, "out")) { src = b14 ? S->block->x : headconv_rows(S); per = (size_t)BK_HW * K->L.out; }
+    else if (!strcmp(what, "gate")) { src = K->gate; per = BK_EXP; }
+    else if (!strcmp(what, "ad")) { src = K->ad; per = (size_t)BK_HW * BK_EXP; }
+    else if (!strcmp(what, "dout")) { src = K->dx; per = (size_t)BK_HW * K->L.out; }
+    else if (!strcmp(what, "dae")) { src = K->d2; per = (size_t)BK_HW * BK_EXP; }
+    else if (b14 && !strcmp(what, "keep")) { src = K->keep; per = 1; }
     else return fail(h, DFD_ERR_ARG, "head_train_tap: unknown tap '%s'", name);
     const size_t count = (size_t)S->last_n * per;
     if (capacity < count) return fail(h, DFD_ERR_ARG, "head_train_tap: '%s' holds %zu floats, capacity %zu", name, count, capacity);
@@ -384,53 +475,56 @@ int headblock_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out
     return DFD_OK;
 }
 
-// Block 15's ten tensors of the inference plan, rewritten in place from the trained parameters (live or EMA) and the
+// A trained block's ten tensors of the inference plan, rewritten in place from the trained parameters (live or EMA) and the
 // running statistics: weights._fold's arithmetic (a = g / sqrt(var + eps); w' = w a; b' = 0 a + (beta - mu a), float64,
-// rounded once) and weights.pack_b0_tensors' layouts (dw.w [ky][kx][c], se.w2 [48][1152]).  Readers of these pointers:
-// b0_forward's block loop - launch_mbconv_front (mbconv_late_kernel / mbconv_k5_kernel: exp.w through its cached split
-// AND the fp32 tensor, exp.b, dw.w, dw.b), the unfused pointwise_t (exp.w / proj.w: the cached split under the split GEMM
-// and under "bf16_activations", the fp32 tensor in launch_pointwise), launch_depthwise (dw.w, dw.b), launch_se (se.*) and
-// the projection's bias (proj.b).  The two cached splits are rebuilt in place, so plan and tile-table pointers stay valid.
-int headblock_commit(dfd_handle* h, HeadTrainState* S, int use_ema) {
-    HeadBlockState* K = S->block;
-    if ((int)h->b0.blocks.size() != BK_INDEX + 1) return fail(h, DFD_ERR_STATE, "head_train_commit: the plan has no block %d", BK_INDEX);
-    const B0Block& b = h->b0.blocks[BK_INDEX];
-    if (b.c_in != BK_IN || b.c_exp != BK_EXP || b.c_se != BK_SE || b.c_out != BK_OUT || b.kernel != 3)
-        return fail(h, DFD_ERR_STATE, "head_train_commit: block %d of the plan is not 192 -> 1152 -> 320, k3", BK_INDEX);
-    std::vector<float> P(BK_COUNT), rm[3], rv[3];
-    DFD_HIP_TRY(h, hipMemcpyAsync(P.data(), use_ema ? K->ema : K->param, (size_t)BK_COUNT * 4, hipMemcpyDeviceToHost, h->stream));
+// rounded once) and weights.pack_b0_tensors' layouts (dw.w [ky][kx][c] with 9 or 25 taps, se.w2 [48][1152]).  Readers of
+// these pointers, for block 15 and block 14 alike (b0_forward's block loop treats both as "late" 7 x 7 blocks):
+// launch_mbconv_front (mbconv_late_kernel for k3, and for k5 the fused front launch mbconv_k5_kernel in its modes 1 and 2:
+// exp.w through its cached split AND the fp32 tensor, exp.b, dw.w, dw.b), the unfused pointwise_t (exp.w / proj.w: the
+// cached split under the split GEMM and, in the bf16-activation instances under "bf16_activations", always; the fp32 tensor
+// in launch_pointwise), launch_depthwise (dw.w, dw.b; fp32 and bf16 instances), launch_se (se.w1, se.b1, se.w2, se.b2) and
+// the projection's bias (proj.b); block 14's projection also adds its input (the skip), which is no weight.  The two cached
+// splits are rebuilt in place, so plan and tile-table pointers stay valid.
+static int commit_one(dfd_handle* h, HeadBlockState* K, int use_ema) {
+    const Layout& L = K->L;
+    if ((int)h->b0.blocks.size() <= L.index) return fail(h, DFD_ERR_STATE, "head_train_commit: the plan has no block %d", L.index);
+    const B0Block& b = h->b0.blocks[L.index];
+    if (b.c_in != BK_IN || b.c_exp != BK_EXP || b.c_se != BK_SE || b.c_out != L.out || b.kernel != L.ks || (b.skip != 0) != L.skip)
+        return fail(h, DFD_ERR_STATE, "head_train_commit: block %d of the plan is not 192 -> 1152 -> %d, k%d", L.index, L.out, L.ks);
+    const int T = L.taps, OUT = L.out;
+    std::vector<float> P(L.count), rm[3], rv[3];
+    DFD_HIP_TRY(h, hipMemcpyAsync(P.data(), use_ema ? K->ema : K->param, (size_t)L.count * 4, hipMemcpyDeviceToHost, h->stream));
     for (int l = 0; l < 3; ++l) {
-        rm[l].resize(kBnC[l]);
-        rv[l].resize(kBnC[l]);
-        DFD_HIP_TRY(h, hipMemcpyAsync(rm[l].data(), K->rm[l], (size_t)kBnC[l] * 4, hipMemcpyDeviceToHost, h->stream));
-        DFD_HIP_TRY(h, hipMemcpyAsync(rv[l].data(), K->rv[l], (size_t)kBnC[l] * 4, hipMemcpyDeviceToHost, h->stream));
+        rm[l].resize(L.bnc[l]);
+        rv[l].resize(L.bnc[l]);
+        DFD_HIP_TRY(h, hipMemcpyAsync(rm[l].data(), K->rm[l], (size_t)L.bnc[l] * 4, hipMemcpyDeviceToHost, h->stream));
+        DFD_HIP_TRY(h, hipMemcpyAsync(rv[l].data(), K->rv[l], (size_t)L.bnc[l] * 4, hipMemcpyDeviceToHost, h->stream));
     }
     DFD_HIP_TRY(h, stream_sync(h));
-    const int og[3] = {BO_G0, BO_G1, BO_G2}, obe[3] = {BO_BE0, BO_BE1, BO_BE2};
-    auto scale = [&](int l, int o) { return (double)P[og[l] + o] / std::sqrt((double)rv[l][o] + K->eps); };
-    auto bias = [&](int l, int o, double a) { return (float)(0.0 * a + ((double)P[obe[l] + o] - (double)rm[l][o] * a)); };
-    std::vector<float> ew((size_t)BK_EXP * BK_IN), eb(BK_EXP), dw((size_t)9 * BK_EXP), db(BK_EXP), w2((size_t)BK_SE * BK_EXP),
-        pw((size_t)BK_OUT * BK_EXP), pb(BK_OUT);
+    auto scale = [&](int l, int o) { return (double)P[L.o_g[l] + o] / std::sqrt((double)rv[l][o] + K->eps); };
+    auto bias = [&](int l, int o, double a) { return (float)(0.0 * a + ((double)P[L.o_be[l] + o] - (double)rm[l][o] * a)); };
+    std::vector<float> ew((size_t)BK_EXP * BK_IN), eb(BK_EXP), dw((size_t)T * BK_EXP), db(BK_EXP), w2((size_t)BK_SE * BK_EXP),
+        pw((size_t)OUT * BK_EXP), pb(OUT);
     for (int o = 0; o < BK_EXP; ++o) {
         const double a0 = scale(0, o), a1 = scale(1, o);
-        for (int k = 0; k < BK_IN; ++k) ew[(size_t)o * BK_IN + k] = (float)((double)P[BO_WE + (size_t)o * BK_IN + k] * a0);
+        for (int k = 0; k < BK_IN; ++k) ew[(size_t)o * BK_IN + k] = (float)((double)P[L.o_we + (size_t)o * BK_IN + k] * a0);
         eb[o] = bias(0, o, a0);
-        for (int t = 0; t < 9; ++t) dw[(size_t)t * BK_EXP + o] = (float)((double)P[BO_WD + o * 9 + t] * a1);
+        for (int t = 0; t < T; ++t) dw[(size_t)t * BK_EXP + o] = (float)((double)P[L.o_wd + o * T + t] * a1);
         db[o] = bias(1, o, a1);
-        for (int j = 0; j < BK_SE; ++j) w2[(size_t)j * BK_EXP + o] = P[BO_W2 + (size_t)o * BK_SE + j];
+        for (int j = 0; j < BK_SE; ++j) w2[(size_t)j * BK_EXP + o] = P[L.o_w2 + (size_t)o * BK_SE + j];
     }
-    for (int o = 0; o < BK_OUT; ++o) {
+    for (int o = 0; o < OUT; ++o) {
         const double a2 = scale(2, o);
-        for (int k = 0; k < BK_EXP; ++k) pw[(size_t)o * BK_EXP + k] = (float)((double)P[BO_WP + (size_t)o * BK_EXP + k] * a2);
+        for (int k = 0; k < BK_EXP; ++k) pw[(size_t)o * BK_EXP + k] = (float)((double)P[L.o_wp + (size_t)o * BK_EXP + k] * a2);
         pb[o] = bias(2, o, a2);
     }
     const struct { const float* dst; const float* src; size_t count; } ups[] = {
         {b.exp_w, ew.data(), ew.size()}, {b.exp_b, eb.data(), eb.size()}, {b.dw_w, dw.data(), dw.size()}, {b.dw_b, db.data(), db.size()},
-        {b.se_w1, P.data() + BO_W1, (size_t)BK_SE * BK_EXP}, {b.se_b1, P.data() + BO_B1, (size_t)BK_SE}, {b.se_w2, w2.data(), w2.size()},
-        {b.se_b2, P.data() + BO_B2, (size_t)BK_EXP}, {b.proj_w, pw.data(), pw.size()}, {b.proj_b, pb.data(), pb.size()}};
+        {b.se_w1, P.data() + L.o_w1, (size_t)BK_SE * BK_EXP}, {b.se_b1, P.data() + L.o_b1, (size_t)BK_SE}, {b.se_w2, w2.data(), w2.size()},
+        {b.se_b2, P.data() + L.o_b2, (size_t)BK_EXP}, {b.proj_w, pw.data(), pw.size()}, {b.proj_b, pb.data(), pb.size()}};
     for (const auto& u : ups)
         DFD_HIP_TRY(h, hipMemcpyAsync(const_cast<float*>(u.dst), u.src, u.count * 4, hipMemcpyHostToDevice, h->stream));
-    const struct { const float* w; int N, Kd; } splits[] = {{b.exp_w, BK_EXP, BK_IN}, {b.proj_w, BK_OUT, BK_EXP}};
+    const struct { const float* w; int N, Kd; } splits[] = {{b.exp_w, BK_EXP, BK_IN}, {b.proj_w, OUT, BK_EXP}};
     for (const auto& sp : splits) {
         auto it = h->wsplit.find(sp.w);
         if (it != h->wsplit.end()) launch_split_weights(sp.w, it->second, sp.N, sp.Kd, h->stream, false);
@@ -440,26 +534,35 @@ int headblock_commit(dfd_handle* h, HeadTrainState* S, int use_ema) {
     return DFD_OK;
 }
 
+int headblock_commit(dfd_handle* h, HeadTrainState* S, int use_ema) {
+    int rc = commit_one(h, S->block, use_ema);
+    if (!rc && S->block14) rc = commit_one(h, S->block14, use_ema);
+    return rc;
+}
+
 }  // namespace dfd
 
 namespace {
 
 struct BField { float* dfd_mbconv_params::*ptr; int off, count; };
-const BField kBlockTrainable[] = {
-    {&dfd_mbconv_params::exp_w, BO_WE, BK_EXP * BK_IN},   {&dfd_mbconv_params::dw_w, BO_WD, BK_EXP * 9},
-    {&dfd_mbconv_params::se_w1, BO_W1, BK_SE * BK_EXP},   {&dfd_mbconv_params::se_b1, BO_B1, BK_SE},
-    {&dfd_mbconv_params::se_w2, BO_W2, BK_EXP * BK_SE},   {&dfd_mbconv_params::se_b2, BO_B2, BK_EXP},
-    {&dfd_mbconv_params::proj_w, BO_WP, BK_OUT * BK_EXP}, {&dfd_mbconv_params::g0, BO_G0, BK_EXP},
-    {&dfd_mbconv_params::be0, BO_BE0, BK_EXP},            {&dfd_mbconv_params::g1, BO_G1, BK_EXP},
-    {&dfd_mbconv_params::be1, BO_BE1, BK_EXP},            {&dfd_mbconv_params::g2, BO_G2, BK_OUT},
-    {&dfd_mbconv_params::be2, BO_BE2, BK_OUT},
-};
+// the 13 trainable tensors of a block with their places in its arena
+std::vector<BField> trainable_fields(const Layout& L) {
+    return {
+        {&dfd_mbconv_params::exp_w, L.o_we, BK_EXP * BK_IN},   {&dfd_mbconv_params::dw_w, L.o_wd, BK_EXP * L.taps},
+        {&dfd_mbconv_params::se_w1, L.o_w1, BK_SE * BK_EXP},   {&dfd_mbconv_params::se_b1, L.o_b1, BK_SE},
+        {&dfd_mbconv_params::se_w2, L.o_w2, BK_EXP * BK_SE},   {&dfd_mbconv_params::se_b2, L.o_b2, BK_EXP},
+        {&dfd_mbconv_params::proj_w, L.o_wp, L.out * BK_EXP},  {&dfd_mbconv_params::g0, L.o_g[0], BK_EXP},
+        {&dfd_mbconv_params::be0, L.o_be[0], BK_EXP},          {&dfd_mbconv_params::g1, L.o_g[1], BK_EXP},
+        {&dfd_mbconv_params::be1, L.o_be[1], BK_EXP},          {&dfd_mbconv_params::g2, L.o_g[2], L.out},
+        {&dfd_mbconv_params::be2, L.o_be[2], L.out},
+    };
+}
 struct BStat { float* dfd_mbconv_params::*rm; float* dfd_mbconv_params::*rv; };
 const BStat kBlockStats[3] = {{&dfd_mbconv_params::rm0, &dfd_mbconv_params::rv0}, {&dfd_mbconv_params::rm1, &dfd_mbconv_params::rv1},
                               {&dfd_mbconv_params::rm2, &dfd_mbconv_params::rv2}};
 
 bool block_complete(const dfd_mbconv_params* p, bool stats) {
-    for (const BField& f : kBlockTrainable)
+    for (const BField& f : trainable_fields(layout_of<G15>()))
         if (!(p->*f.ptr)) return false;
     if (stats)
         for (const BStat& st : kBlockStats)
@@ -477,15 +580,14 @@ HeadTrainState* open_block(dfd_handle* h, const char* who, bool want_stage, int*
 }
 
 BnC bn_consts(const HeadBlockState* K, const float* P, int l, int m, bool backward) {
-    const int og[3] = {BO_G0, BO_G1, BO_G2}, obe[3] = {BO_BE0, BO_BE1, BO_BE2};
-    return BnC{K->mean[l], K->istd[l], backward ? K->sdy[l] : nullptr, backward ? K->sdx[l] : nullptr, P + og[l], P + obe[l], m};
+    return BnC{K->mean[l], K->istd[l], backward ? K->sdy[l] : nullptr, backward ? K->sdx[l] : nullptr, P + K->L.o_g[l], P + K->L.o_be[l], m};
 }
 
 dim3 flat(size_t total) { return dim3((unsigned)((total + HT_THREADS - 1) / HT_THREADS)); }
 
 // mean and istd of BatchNorm l over the m rows of Z: the batch's (train; running statistics updated) or the running ones
 void bn_statistics(HeadBlockState* K, int l, const float* Z, int m, bool train, hipStream_t s) {
-    const int C = kBnC[l];
+    const int C = K->L.bnc[l];
     const dim3 blk(HT_THREADS), chan((C + HT_THREADS - 1) / HT_THREADS);
     if (!train) {
         hipLaunchKernelGGL(bk_eval_consts_kernel, chan, blk, 0, s, K->rm[l], K->rv[l], K->eps, K->mean[l], K->istd[l], C);
@@ -503,75 +605,199 @@ void bn_statistics(HeadBlockState* K, int l, const float* Z, int m, bool train, 
 // sum dy and sum dy xhat of BatchNorm l from its gradient source; adds the gradients of gamma and beta
 template <class G>
 void bn_backward_statistics(HeadBlockState* K, int l, const G& g, int m, hipStream_t s) {
-    const int C = kBnC[l], ch = stat_chunks(m);
-    const int og[3] = {BO_G0, BO_G1, BO_G2}, obe[3] = {BO_BE0, BO_BE1, BO_BE2};
+    const int C = K->L.bnc[l], ch = stat_chunks(m);
     const dim3 blk(HT_THREADS);
     hipLaunchKernelGGL((colstat_kernel<2, G>), dim3(C / 64, ch), blk, 0, s, g, nullptr, nullptr, K->spart, K->spart2, m, C);
     hipLaunchKernelGGL(finalize_kernel<2>, dim3((C + HT_THREADS - 1) / HT_THREADS), blk, 0, s, K->spart, K->spart2, ch, m, C, K->sdy[l],
-                       K->sdx[l], K->grad + og[l], K->grad + obe[l], 0.f, 0.0);
+                       K->sdx[l], K->grad + K->L.o_g[l], K->grad + K->L.o_be[l], 0.f, 0.0);
 }
 
-// X (K->x, n rows of block 14's output) -> x15 in the conv stage's rows, with the block's parameters at P
-int block_forward(dfd_handle* h, HeadTrainState* S, const float* P, int n, bool train) {
-    HeadBlockState* K = S->block;
+// X (K->x, n rows of the block below) -> the block's output in `out` (the next stage's input rows), with the block's
+// parameters at P.  With the skip: out = X + the branch times the crop's drop-connect factor (`masked`: K->keep, else none).
+template <class GEO>
+int block_forward(dfd_handle* h, HeadBlockState* K, const float* P, int n, bool train, float* out, bool masked) {
     hipStream_t s = h->stream;
     const int m = n * BK_HW;
     const dim3 blk(HT_THREADS);
-    const size_t te = (size_t)m * BK_EXP, to = (size_t)m * BK_OUT;
-    hipLaunchKernelGGL((gemm_fwd_kernel<BK_JE, false>), dim3(BK_EXP / (16 * BK_JE), (m + 63) / 64), blk, 0, s, K->x, nullptr, P + BO_WE,
+    const size_t te = (size_t)m * BK_EXP, to = (size_t)m * GEO::OUT;
+    hipLaunchKernelGGL((gemm_fwd_kernel<BK_JE, false>), dim3(BK_EXP / (16 * BK_JE), (m + 63) / 64), blk, 0, s, K->x, nullptr, P + GEO::O_WE,
                        K->ze, m, BK_IN, BK_EXP, BK_HW);
     bn_statistics(K, 0, K->ze, m, train, s);
     hipLaunchKernelGGL(bk_bn_swish_kernel, flat(te), blk, 0, s, K->ze, bn_consts(K, P, 0, m, false), K->ae, te, BK_EXP);
-    hipLaunchKernelGGL(bk_dw_fwd_kernel, flat(te), blk, 0, s, K->ae, P + BO_WD, K->zd, te);
+    hipLaunchKernelGGL(bk_dw_fwd_kernel<GEO::KS>, flat(te), blk, 0, s, K->ae, P + GEO::O_WD, K->zd, te);
     bn_statistics(K, 1, K->zd, m, train, s);
     hipLaunchKernelGGL(bk_bn_swish_pool_kernel, dim3((BK_EXP + HT_THREADS - 1) / HT_THREADS, n), blk, 0, s, K->zd,
                        bn_consts(K, P, 1, m, false), K->ad, K->pooled);
-    hipLaunchKernelGGL(bk_se_fwd_kernel, dim3(n), blk, 0, s, K->pooled, P + BO_W1, P + BO_B1, P + BO_W2, P + BO_B2, K->r, K->q, K->gate);
-    hipLaunchKernelGGL((gemm_fwd_kernel<BK_JP, true>), dim3(BK_OUT / (16 * BK_JP), (m + 63) / 64), blk, 0, s, K->ad, K->gate, P + BO_WP,
-                       K->zp, m, BK_EXP, BK_OUT, BK_HW);
+    hipLaunchKernelGGL(bk_se_fwd_kernel, dim3(n), blk, 0, s, K->pooled, P + GEO::O_W1, P + GEO::O_B1, P + GEO::O_W2, P + GEO::O_B2, K->r, K->q,
+                       K->gate);
+    hipLaunchKernelGGL((gemm_fwd_kernel<GEO::JP, true>), dim3(GEO::OUT / (16 * GEO::JP), (m + 63) / 64), blk, 0, s, K->ad, K->gate,
+                       P + GEO::O_WP, K->zp, m, BK_EXP, GEO::OUT, BK_HW);
     bn_statistics(K, 2, K->zp, m, train, s);
-    hipLaunchKernelGGL(bk_bn_kernel, flat(to), blk, 0, s, K->zp, bn_consts(K, P, 2, m, false), headconv_rows(S), to, BK_OUT);
+    if constexpr (GEO::SKIP)
+        hipLaunchKernelGGL(bk_bn_skip_kernel, flat(to), blk, 0, s, K->zp, bn_consts(K, P, 2, m, false), K->x, masked ? K->keep : nullptr,
+                           masked ? K->keep_prob : 1.0, out, to, GEO::OUT);
+    else
+        hipLaunchKernelGGL(bk_bn_kernel, flat(to), blk, 0, s, K->zp, bn_consts(K, P, 2, m, false), out, to, GEO::OUT);
     DFD_HIP_TRY(h, hipGetLastError());
     return DFD_OK;
 }
 
-// from dX15 (K->dx15) back to the gradients of the block's parameters
-int block_backward(dfd_handle* h, HeadTrainState* S, int n) {
-    HeadBlockState* K = S->block;
+// from the gradient of the block's output (K->dx) back to the gradients of the block's parameters; dx_below (or null):
+// the gradient with respect to the block's input, dZe . We, for a trained block below
+template <class GEO>
+int block_backward(dfd_handle* h, HeadBlockState* K, int n, float* dx_below) {
     hipStream_t s = h->stream;
     const int m = n * BK_HW, wch = wg_chunks(m);
     const dim3 blk(HT_THREADS);
     const float* P = K->param;
     float* G = K->grad;
     const size_t te = (size_t)m * BK_EXP;
+    typedef Grad2<GEO::SKIP> G2;
     // BN2, project
-    Grad2 g2{bn_consts(K, P, 2, m, true), K->zp, K->dx15};
+    G2 g2{bn_consts(K, P, 2, m, true), K->zp, K->dx, GEO::OUT, K->keep, K->keep_prob};
     bn_backward_statistics(K, 2, g2, m, s);
-    hipLaunchKernelGGL((wgrad_kernel<BK_JE, true, Grad2>), dim3(BK_OUT / 16 * (BK_EXP / (16 * BK_JE)) / 4, wch), blk, 0, s, g2, K->ad,
-                       K->gate, K->wpart, m, BK_OUT, BK_EXP, BK_HW);
-    hipLaunchKernelGGL(wreduce_kernel, flat((size_t)BK_OUT * BK_EXP), blk, 0, s, K->wpart, wch, BK_OUT * BK_EXP, G + BO_WP);
-    hipLaunchKernelGGL((gemm_dyw_kernel<BK_JE, Grad2>), dim3(BK_EXP / (16 * BK_JE), (m + 15) / 16), blk, 0, s, g2, P + BO_WP, K->d1, m,
-                       BK_OUT, BK_EXP);
+    hipLaunchKernelGGL((wgrad_kernel<BK_JE, true, G2>), dim3(GEO::OUT / 16 * (BK_EXP / (16 * BK_JE)) / 4, wch), blk, 0, s, g2, K->ad,
+                       K->gate, K->wpart, m, GEO::OUT, BK_EXP, BK_HW);
+    hipLaunchKernelGGL(wreduce_kernel, flat((size_t)GEO::OUT * BK_EXP), blk, 0, s, K->wpart, wch, GEO::OUT * BK_EXP, G + GEO::O_WP);
+    hipLaunchKernelGGL((gemm_dyw_kernel<BK_JE, G2>), dim3(BK_EXP / (16 * BK_JE), (m + 15) / 16), blk, 0, s, g2, P + GEO::O_WP, K->d1, m,
+                       GEO::OUT, BK_EXP);
     // squeeze-excite
-    hipLaunchKernelGGL(bk_se_bwd_kernel, dim3(n), blk, 0, s, K->d1, K->ad, K->gate, K->r, P + BO_W1, P + BO_W2, K->du, K->dr, K->ds);
+    hipLaunchKernelGGL(bk_se_bwd_kernel, dim3(n), blk, 0, s, K->d1, K->ad, K->gate, K->r, P + GEO::O_W1, P + GEO::O_W2, K->du, K->dr, K->ds);
     hipLaunchKernelGGL(bk_se_wgrad_kernel, flat((size_t)2 * BK_EXP * BK_SE + BK_EXP + BK_SE), blk, 0, s, K->du, K->dr, K->q, K->pooled,
-                       G + BO_W1, G + BO_B1, G + BO_W2, G + BO_B2, n);
+                       G + GEO::O_W1, G + GEO::O_B1, G + GEO::O_W2, G + GEO::O_B2, n);
     // BN1, depthwise
     Grad1 g1{bn_consts(K, P, 1, m, true), K->zd, K->d1, K->gate, K->ds};
     bn_backward_statistics(K, 1, g1, m, s);
     hipLaunchKernelGGL(bk_dz_store_kernel, flat(te), blk, 0, s, g1, K->d1, te);
     const int dch = (n + BK_DW_CROPS - 1) / BK_DW_CROPS;
-    hipLaunchKernelGGL(bk_dw_wgrad_kernel, dim3((BK_EXP + HT_THREADS - 1) / HT_THREADS, 9, dch), blk, 0, s, K->d1, K->ae, K->dwpart, n);
-    hipLaunchKernelGGL(bk_dw_wreduce_kernel, flat((size_t)BK_EXP * 9), blk, 0, s, K->dwpart, dch, G + BO_WD);
-    hipLaunchKernelGGL(bk_dw_bwd_kernel, flat(te), blk, 0, s, K->d1, P + BO_WD, K->d2, te);
+    hipLaunchKernelGGL(bk_dw_wgrad_kernel<GEO::KS>, dim3((BK_EXP + HT_THREADS - 1) / HT_THREADS, GEO::TAPS, dch), blk, 0, s, K->d1, K->ae,
+                       K->dwpart, n);
+    hipLaunchKernelGGL(bk_dw_wreduce_kernel, flat((size_t)BK_EXP * GEO::TAPS), blk, 0, s, K->dwpart, dch, G + GEO::O_WD, GEO::TAPS);
+    hipLaunchKernelGGL(bk_dw_bwd_kernel<GEO::KS>, flat(te), blk, 0, s, K->d1, P + GEO::O_WD, K->d2, te);
     // BN0, expand
     Grad0 g0{bn_consts(K, P, 0, m, true), K->ze, K->d2};
     bn_backward_statistics(K, 0, g0, m, s);
     hipLaunchKernelGGL((wgrad_kernel<BK_JE, false, Grad0>), dim3(BK_EXP / 16 * (BK_IN / (16 * BK_JE)) / 4, wch), blk, 0, s, g0, K->x, nullptr,
                        K->wpart, m, BK_EXP, BK_IN, BK_HW);
-    hipLaunchKernelGGL(wreduce_kernel, flat((size_t)BK_EXP * BK_IN), blk, 0, s, K->wpart, wch, BK_EXP * BK_IN, G + BO_WE);
+    hipLaunchKernelGGL(wreduce_kernel, flat((size_t)BK_EXP * BK_IN), blk, 0, s, K->wpart, wch, BK_EXP * BK_IN, G + GEO::O_WE);
+    if (dx_below)                                               // dOut of the block below = dZe . We: 192 columns, reduction over 1152
+        hipLaunchKernelGGL((gemm_dyw_kernel<BK_JE, Grad0>), dim3(BK_IN / (16 * BK_JE), (m + 15) / 16), blk, 0, s, g0, P + GEO::O_WE, dx_below,
+                           m, BK_EXP, BK_IN);
     DFD_HIP_TRY(h, hipGetLastError());
     return DFD_OK;
+}
+
+// block 14's drop-connect factors of accumulate number `counter`: head_training.drop_connect_keep is the specification
+int draw_keep(dfd_handle* h, HeadTrainState* S, HeadBlockState* K, int n) {
+    const uint32_t key = mask_key(S->cfg.seed, S->counter, 3);
+    const float scale = (float)(1.0 / K->keep_prob);
+    for (int i = 0; i < n; ++i) K->keep_host[i] = mask_keep(key, (uint32_t)i, K->drop_thr) ? scale : 0.f;
+    DFD_HIP_TRY(h, hipMemcpyAsync(K->keep, K->keep_host.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    return DFD_OK;
+}
+
+// Allocates a block's stage for max_n crops in ONE hipMalloc and uploads `init`
+int create_stage(dfd_handle* h, HeadTrainState* S, const char* who, const Layout& L, const dfd_mbconv_params* init, float bn_momentum,
+                 float bn_eps, HeadBlockState** slot) {
+    HeadBlockState* K = new (std::nothrow) HeadBlockState();
+    if (!K) return fail(h, DFD_ERR_CAPACITY, "%s: out of host memory", who);
+    K->L = L;
+    K->momentum = bn_momentum;
+    K->eps = bn_eps == 1e-3f ? 1e-3 : (double)bn_eps;          // the backbone's eps (weights._fold's double), not its float neighbour
+    const size_t mn = (size_t)S->max_n, mm = mn * BK_HW, sch = (size_t)stat_chunks((int)mm), wch = (size_t)wg_chunks((int)mm),
+                 dch = (mn + BK_DW_CROPS - 1) / BK_DW_CROPS, cnt = (size_t)L.count, out = (size_t)L.out,
+                 wmax = std::max(out * BK_EXP, (size_t)BK_EXP * BK_IN);
+    struct Slot { void** p; size_t bytes; };
+    std::vector<Slot> slots = {
+        {(void**)&K->param, cnt * 4}, {(void**)&K->grad, cnt * 4}, {(void**)&K->m, cnt * 4},
+        {(void**)&K->v, cnt * 4},     {(void**)&K->ema, cnt * 4},
+        {(void**)&K->x, mm * BK_IN * 4},   {(void**)&K->ze, mm * BK_EXP * 4}, {(void**)&K->ae, mm * BK_EXP * 4},
+        {(void**)&K->zd, mm * BK_EXP * 4}, {(void**)&K->ad, mm * BK_EXP * 4}, {(void**)&K->d1, mm * BK_EXP * 4},
+        {(void**)&K->d2, mm * BK_EXP * 4}, {(void**)&K->zp, mm * out * 4}, {(void**)&K->dx, mm * out * 4},
+        {(void**)&K->pooled, mn * BK_EXP * 4}, {(void**)&K->gate, mn * BK_EXP * 4},
+        {(void**)&K->spart, sch * BK_EXP * 8}, {(void**)&K->spart2, sch * BK_EXP * 8},
+        {(void**)&K->wpart, wch * wmax * 8}, {(void**)&K->dwpart, dch * L.taps * BK_EXP * 8},
+        {(void**)&K->partial, NORM_BLOCKS * 8},
+        {(void**)&K->r, mn * BK_SE * 8}, {(void**)&K->q, mn * BK_SE * 8}, {(void**)&K->du, mn * BK_EXP * 8},
+        {(void**)&K->dr, mn * BK_SE * 8}, {(void**)&K->ds, mn * BK_EXP * 8},
+    };
+    for (int l = 0; l < 3; ++l) {
+        const size_t c = (size_t)L.bnc[l];
+        slots.push_back({(void**)&K->rm[l], c * 4});
+        slots.push_back({(void**)&K->rv[l], c * 4});
+        slots.push_back({(void**)&K->mean[l], c * 8});
+        slots.push_back({(void**)&K->istd[l], c * 8});
+        slots.push_back({(void**)&K->sdy[l], c * 8});
+        slots.push_back({(void**)&K->sdx[l], c * 8});
+    }
+    if (L.skip) {
+        slots.push_back({(void**)&K->keep, mn * 4});
+        slots.push_back({(void**)&K->norm, 4});
+        K->keep_host.assign(mn, 0.f);
+    }
+    size_t total = 0;
+    for (const Slot& sl : slots) total += (sl.bytes + 255) / 256 * 256;
+    if (hipMalloc(&K->pool, total) != hipSuccess) {
+        delete K;
+        return fail(h, DFD_ERR_HIP, "%s: hipMalloc of %zu bytes failed", who, total);
+    }
+    size_t off = 0;
+    for (const Slot& sl : slots) {
+        *sl.p = static_cast<char*>(K->pool) + off;
+        off += (sl.bytes + 255) / 256 * 256;
+    }
+    *slot = K;
+    auto bail = [&](hipError_t e, const char* what) {
+        destroy_one(slot);
+        return fail(h, DFD_ERR_HIP, "%s: %s failed: %s", who, what, hipGetErrorString(e));
+    };
+    hipError_t e;
+    if ((e = hipMemsetAsync(K->pool, 0, total, h->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
+    for (const BField& f : trainable_fields(L))
+        if ((e = hipMemcpyAsync(K->param + f.off, init->*f.ptr, (size_t)f.count * 4, hipMemcpyHostToDevice, h->stream)) != hipSuccess)
+            return bail(e, "parameter upload");
+    for (int l = 0; l < 3; ++l) {
+        if ((e = hipMemcpyAsync(K->rm[l], init->*kBlockStats[l].rm, (size_t)L.bnc[l] * 4, hipMemcpyHostToDevice, h->stream)) != hipSuccess)
+            return bail(e, "statistics upload");
+        if ((e = hipMemcpyAsync(K->rv[l], init->*kBlockStats[l].rv, (size_t)L.bnc[l] * 4, hipMemcpyHostToDevice, h->stream)) != hipSuccess)
+            return bail(e, "statistics upload");
+    }
+    if ((e = hipMemcpyAsync(K->ema, K->param, cnt * 4, hipMemcpyDeviceToDevice, h->stream)) != hipSuccess) return bail(e, "shadow copy");
+    if ((e = stream_sync(h)) != hipSuccess) return bail(e, "stream wait");
+    return DFD_OK;
+}
+
+int export_stage(dfd_handle* h, HeadBlockState* K, int use_ema, dfd_mbconv_params* out) {
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    const float* P = use_ema ? K->ema : K->param;
+    for (const BField& f : trainable_fields(K->L))
+        DFD_HIP_TRY(h, hipMemcpyAsync(out->*f.ptr, P + f.off, (size_t)f.count * 4, hipMemcpyDeviceToHost, h->stream));
+    for (int l = 0; l < 3; ++l) {
+        DFD_HIP_TRY(h, hipMemcpyAsync(out->*kBlockStats[l].rm, K->rm[l], (size_t)K->L.bnc[l] * 4, hipMemcpyDeviceToHost, h->stream));
+        DFD_HIP_TRY(h, hipMemcpyAsync(out->*kBlockStats[l].rv, K->rv[l], (size_t)K->L.bnc[l] * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    DFD_HIP_TRY(h, stream_sync(h));
+    return DFD_OK;
+}
+
+int stage_grads(dfd_handle* h, HeadBlockState* K, dfd_mbconv_params* io, int set) {
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    for (const BField& f : trainable_fields(K->L)) {
+        if (set) DFD_HIP_TRY(h, hipMemcpyAsync(K->grad + f.off, io->*f.ptr, (size_t)f.count * 4, hipMemcpyHostToDevice, h->stream));
+        else DFD_HIP_TRY(h, hipMemcpyAsync(io->*f.ptr, K->grad + f.off, (size_t)f.count * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    DFD_HIP_TRY(h, stream_sync(h));
+    return DFD_OK;
+}
+
+// the stage of `block` (14 or 15) for the _at entries
+HeadBlockState* stage_at(dfd_handle* h, HeadTrainState* S, const char* who, int block, int* rc) {
+    if (block != 14 && block != 15) { *rc = fail(h, DFD_ERR_UNSUPPORTED, "%s: block %d; 14 or 15", who, block); return nullptr; }
+    HeadBlockState* K = stage_of(S, block);
+    if (!K)
+        *rc = fail(h, DFD_ERR_ARG, "%s: block %d is not unfrozen (%s)", who, block,
+                   block == 14 ? "dfd_head_train_unfreeze_block_at" : "dfd_head_train_unfreeze_block");
+    return K;
 }
 
 }  // namespace
@@ -582,73 +808,40 @@ int dfd_head_train_unfreeze_block(dfd_handle* h, int block, const dfd_mbconv_par
     int rc;
     HeadTrainState* S = open_block(h, "head_train_unfreeze_block", false, &rc);
     if (!S) return rc;
-    if (block != BK_INDEX)
-        return fail(h, DFD_ERR_UNSUPPORTED, "head_train_unfreeze_block: block %d; only the last block (%d) can be unfrozen", block, BK_INDEX);
+    if (block != G15::INDEX_)
+        return fail(h, DFD_ERR_UNSUPPORTED, "head_train_unfreeze_block: block %d; only the last block (%d) can be unfrozen", block, G15::INDEX_);
     if (!S->conv) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block: the conv stage comes first (dfd_head_train_unfreeze_conv)");
-    if (S->block) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block: block %d is already unfrozen", BK_INDEX);
+    if (S->block) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block: block %d is already unfrozen", G15::INDEX_);
     if (S->counter) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block: the trainer has accumulated already; unfreeze right after begin");
     if (!init || !block_complete(init, true)) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block: null parameters");
     if (!(bn_momentum >= 0.f && bn_momentum <= 1.f && bn_eps > 0.f))
         return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block: bn_momentum %g or bn_eps %g out of range", (double)bn_momentum, (double)bn_eps);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
-    HeadBlockState* K = new (std::nothrow) HeadBlockState();
-    if (!K) return fail(h, DFD_ERR_CAPACITY, "head_train_unfreeze_block: out of host memory");
-    K->momentum = bn_momentum;
-    K->eps = bn_eps == 1e-3f ? 1e-3 : (double)bn_eps;          // the backbone's eps (weights._fold's double), not its float neighbour
-    const size_t mn = (size_t)S->max_n, mm = mn * BK_HW, sch = (size_t)stat_chunks((int)mm), wch = (size_t)wg_chunks((int)mm),
-                 dch = (mn + BK_DW_CROPS - 1) / BK_DW_CROPS;
-    struct Slot { void** p; size_t bytes; };
-    std::vector<Slot> slots = {
-        {(void**)&K->param, (size_t)BK_COUNT * 4}, {(void**)&K->grad, (size_t)BK_COUNT * 4}, {(void**)&K->m, (size_t)BK_COUNT * 4},
-        {(void**)&K->v, (size_t)BK_COUNT * 4},     {(void**)&K->ema, (size_t)BK_COUNT * 4},
-        {(void**)&K->x, mm * BK_IN * 4},   {(void**)&K->ze, mm * BK_EXP * 4}, {(void**)&K->ae, mm * BK_EXP * 4},
-        {(void**)&K->zd, mm * BK_EXP * 4}, {(void**)&K->ad, mm * BK_EXP * 4}, {(void**)&K->d1, mm * BK_EXP * 4},
-        {(void**)&K->d2, mm * BK_EXP * 4}, {(void**)&K->zp, mm * BK_OUT * 4}, {(void**)&K->dx15, mm * BK_OUT * 4},
-        {(void**)&K->pooled, mn * BK_EXP * 4}, {(void**)&K->gate, mn * BK_EXP * 4},
-        {(void**)&K->spart, sch * BK_EXP * 8}, {(void**)&K->spart2, sch * BK_EXP * 8},
-        {(void**)&K->wpart, wch * (size_t)BK_OUT * BK_EXP * 8}, {(void**)&K->dwpart, dch * 9 * BK_EXP * 8},
-        {(void**)&K->partial, NORM_BLOCKS * 8},
-        {(void**)&K->r, mn * BK_SE * 8}, {(void**)&K->q, mn * BK_SE * 8}, {(void**)&K->du, mn * BK_EXP * 8},
-        {(void**)&K->dr, mn * BK_SE * 8}, {(void**)&K->ds, mn * BK_EXP * 8},
-    };
-    for (int l = 0; l < 3; ++l) {
-        const size_t c = (size_t)kBnC[l];
-        slots.push_back({(void**)&K->rm[l], c * 4});
-        slots.push_back({(void**)&K->rv[l], c * 4});
-        slots.push_back({(void**)&K->mean[l], c * 8});
-        slots.push_back({(void**)&K->istd[l], c * 8});
-        slots.push_back({(void**)&K->sdy[l], c * 8});
-        slots.push_back({(void**)&K->sdx[l], c * 8});
-    }
-    size_t total = 0;
-    for (const Slot& sl : slots) total += (sl.bytes + 255) / 256 * 256;
-    if (hipMalloc(&K->pool, total) != hipSuccess) {
-        delete K;
-        return fail(h, DFD_ERR_HIP, "head_train_unfreeze_block: hipMalloc of %zu bytes failed", total);
-    }
-    size_t off = 0;
-    for (const Slot& sl : slots) {
-        *sl.p = static_cast<char*>(K->pool) + off;
-        off += (sl.bytes + 255) / 256 * 256;
-    }
-    S->block = K;
-    auto bail = [&](hipError_t e, const char* what) {
-        headblock_destroy(S);
-        return fail(h, DFD_ERR_HIP, "head_train_unfreeze_block: %s failed: %s", what, hipGetErrorString(e));
-    };
-    hipError_t e;
-    if ((e = hipMemsetAsync(K->pool, 0, total, h->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
-    for (const BField& f : kBlockTrainable)
-        if ((e = hipMemcpyAsync(K->param + f.off, init->*f.ptr, (size_t)f.count * 4, hipMemcpyHostToDevice, h->stream)) != hipSuccess)
-            return bail(e, "parameter upload");
-    for (int l = 0; l < 3; ++l) {
-        if ((e = hipMemcpyAsync(K->rm[l], init->*kBlockStats[l].rm, (size_t)kBnC[l] * 4, hipMemcpyHostToDevice, h->stream)) != hipSuccess)
-            return bail(e, "statistics upload");
-        if ((e = hipMemcpyAsync(K->rv[l], init->*kBlockStats[l].rv, (size_t)kBnC[l] * 4, hipMemcpyHostToDevice, h->stream)) != hipSuccess)
-            return bail(e, "statistics upload");
-    }
-    if ((e = hipMemcpyAsync(K->ema, K->param, (size_t)BK_COUNT * 4, hipMemcpyDeviceToDevice, h->stream)) != hipSuccess) return bail(e, "shadow copy");
-    if ((e = stream_sync(h)) != hipSuccess) return bail(e, "stream wait");
+    return create_stage(h, S, "head_train_unfreeze_block", layout_of<G15>(), init, bn_momentum, bn_eps, &S->block);
+}
+
+int dfd_head_train_unfreeze_block_at(dfd_handle* h, int block, const dfd_mbconv_params* init, float bn_momentum, float bn_eps,
+                                     float drop_connect) {
+    int rc;
+    HeadTrainState* S = open_block(h, "head_train_unfreeze_block_at", false, &rc);
+    if (!S) return rc;
+    if (block != G14::INDEX_)
+        return fail(h, DFD_ERR_UNSUPPORTED, "head_train_unfreeze_block_at: block %d; only block %d can be unfrozen below block 15", block,
+                    G14::INDEX_);
+    if (!S->block) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: block 15 comes first (dfd_head_train_unfreeze_block)");
+    if (S->block14) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: block %d is already unfrozen", G14::INDEX_);
+    if (S->counter) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: the trainer has accumulated already; unfreeze right after begin");
+    if (!init || !block_complete(init, true)) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: null parameters");
+    if (!(bn_momentum >= 0.f && bn_momentum <= 1.f && bn_eps > 0.f))
+        return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: bn_momentum %g or bn_eps %g out of range", (double)bn_momentum, (double)bn_eps);
+    if (!(drop_connect >= 0.f && drop_connect < 1.f))
+        return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: drop_connect %g outside [0, 1)", (double)drop_connect);
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = create_stage(h, S, "head_train_unfreeze_block_at", layout_of<G14>(), init, bn_momentum, bn_eps, &S->block14))) return rc;
+    HeadBlockState* K = S->block14;
+    K->drop_p = (double)drop_connect;                           // the double of the float32 argument, as the head's dropout rates
+    K->keep_prob = 1.0 - K->drop_p;
+    K->drop_thr = (uint32_t)(unsigned long long)(K->drop_p * 4294967296.0);
     return DFD_OK;
 }
 
@@ -663,12 +856,18 @@ int dfd_head_train_accumulate_block(dfd_handle* h, const float* rows, int n, con
     if (!head_train_mix_ok(lam, loss_scale))
         return fail(h, DFD_ERR_ARG, "head_train_accumulate_block: lam %g outside [0, 1] or loss_scale %g not a number", (double)lam, (double)loss_scale);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
-    HeadBlockState* K = S->block;
+    HeadBlockState *K = S->block, *K14 = S->block14;
     hipStream_t s = h->stream;
-    DFD_HIP_TRY(h, hipMemcpyAsync(K->x, rows, (size_t)n * BK_ROW * 4, hipMemcpyHostToDevice, s));
-    if ((rc = block_forward(h, S, K->param, n, true))) return rc;
-    if ((rc = headconv_step(h, S, n, labels_a, labels_b, lam, loss_scale, K->dx15))) return rc;
-    if ((rc = block_backward(h, S, n))) return rc;
+    // the rows are the input of the deepest unfrozen block
+    DFD_HIP_TRY(h, hipMemcpyAsync(K14 ? K14->x : K->x, rows, (size_t)n * BK_ROW * 4, hipMemcpyHostToDevice, s));
+    if (K14) {
+        if ((rc = draw_keep(h, S, K14, n))) return rc;
+        if ((rc = block_forward<G14>(h, K14, K14->param, n, true, K->x, true))) return rc;
+    }
+    if ((rc = block_forward<G15>(h, K, K->param, n, true, headconv_rows(S), false))) return rc;
+    if ((rc = headconv_step(h, S, n, labels_a, labels_b, lam, loss_scale, K->dx))) return rc;
+    if ((rc = block_backward<G15>(h, K, n, K14 ? K14->dx : nullptr))) return rc;
+    if (K14 && (rc = block_backward<G14>(h, K14, n, nullptr))) return rc;       // block 13 is frozen
     DFD_HIP_TRY(h, hipMemcpyAsync(loss_out, S->scalars, 4, hipMemcpyDeviceToHost, s));
     if (logits_out) DFD_HIP_TRY(h, hipMemcpyAsync(logits_out, S->logits, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     DFD_HIP_TRY(h, stream_sync(h));
@@ -684,9 +883,10 @@ int dfd_head_train_eval_block(dfd_handle* h, const float* rows, int n, int use_e
     if (!rows || !logits_out) return fail(h, DFD_ERR_ARG, "head_train_eval_block: null pointer");
     if (n < 1 || n > S->max_n) return fail(h, DFD_ERR_ARG, "head_train_eval_block: %d rows outside 1..%d", n, S->max_n);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
-    HeadBlockState* K = S->block;
-    DFD_HIP_TRY(h, hipMemcpyAsync(K->x, rows, (size_t)n * BK_ROW * 4, hipMemcpyHostToDevice, h->stream));
-    if ((rc = block_forward(h, S, use_ema ? K->ema : K->param, n, false))) return rc;
+    HeadBlockState *K = S->block, *K14 = S->block14;
+    DFD_HIP_TRY(h, hipMemcpyAsync(K14 ? K14->x : K->x, rows, (size_t)n * BK_ROW * 4, hipMemcpyHostToDevice, h->stream));
+    if (K14 && (rc = block_forward<G14>(h, K14, use_ema ? K14->ema : K14->param, n, false, K->x, false))) return rc;   // no drop-connect
+    if ((rc = block_forward<G15>(h, K, use_ema ? K->ema : K->param, n, false, headconv_rows(S), false))) return rc;
     if ((rc = headconv_eval_step(h, S, use_ema, n))) return rc;
     DFD_HIP_TRY(h, hipMemcpyAsync(logits_out, S->logits, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     DFD_HIP_TRY(h, stream_sync(h));
@@ -698,17 +898,7 @@ int dfd_head_train_export_block(dfd_handle* h, int use_ema, dfd_mbconv_params* o
     HeadTrainState* S = open_block(h, "head_train_export_block", true, &rc);
     if (!S) return rc;
     if (!out || !block_complete(out, true)) return fail(h, DFD_ERR_ARG, "head_train_export_block: null pointer");
-    DFD_HIP_TRY(h, hipSetDevice(h->device));
-    HeadBlockState* K = S->block;
-    const float* P = use_ema ? K->ema : K->param;
-    for (const BField& f : kBlockTrainable)
-        DFD_HIP_TRY(h, hipMemcpyAsync(out->*f.ptr, P + f.off, (size_t)f.count * 4, hipMemcpyDeviceToHost, h->stream));
-    for (int l = 0; l < 3; ++l) {
-        DFD_HIP_TRY(h, hipMemcpyAsync(out->*kBlockStats[l].rm, K->rm[l], (size_t)kBnC[l] * 4, hipMemcpyDeviceToHost, h->stream));
-        DFD_HIP_TRY(h, hipMemcpyAsync(out->*kBlockStats[l].rv, K->rv[l], (size_t)kBnC[l] * 4, hipMemcpyDeviceToHost, h->stream));
-    }
-    DFD_HIP_TRY(h, stream_sync(h));
-    return DFD_OK;
+    return export_stage(h, S->block, use_ema, out);
 }
 
 int dfd_head_train_block_grads(dfd_handle* h, dfd_mbconv_params* io, int set) {
@@ -716,14 +906,27 @@ int dfd_head_train_block_grads(dfd_handle* h, dfd_mbconv_params* io, int set) {
     HeadTrainState* S = open_block(h, "head_train_block_grads", true, &rc);
     if (!S) return rc;
     if (!io || !block_complete(io, false)) return fail(h, DFD_ERR_ARG, "head_train_block_grads: null pointer");
-    DFD_HIP_TRY(h, hipSetDevice(h->device));
-    HeadBlockState* K = S->block;
-    for (const BField& f : kBlockTrainable) {
-        if (set) DFD_HIP_TRY(h, hipMemcpyAsync(K->grad + f.off, io->*f.ptr, (size_t)f.count * 4, hipMemcpyHostToDevice, h->stream));
-        else DFD_HIP_TRY(h, hipMemcpyAsync(io->*f.ptr, K->grad + f.off, (size_t)f.count * 4, hipMemcpyDeviceToHost, h->stream));
-    }
-    DFD_HIP_TRY(h, stream_sync(h));
-    return DFD_OK;
+    return stage_grads(h, S->block, io, set);
+}
+
+int dfd_head_train_export_block_at(dfd_handle* h, int block, int use_ema, dfd_mbconv_params* out) {
+    int rc;
+    HeadTrainState* S = open_block(h, "head_train_export_block_at", false, &rc);
+    if (!S) return rc;
+    HeadBlockState* K = stage_at(h, S, "head_train_export_block_at", block, &rc);
+    if (!K) return rc;
+    if (!out || !block_complete(out, true)) return fail(h, DFD_ERR_ARG, "head_train_export_block_at: null pointer");
+    return export_stage(h, K, use_ema, out);
+}
+
+int dfd_head_train_block_grads_at(dfd_handle* h, int block, dfd_mbconv_params* io, int set) {
+    int rc;
+    HeadTrainState* S = open_block(h, "head_train_block_grads_at", false, &rc);
+    if (!S) return rc;
+    HeadBlockState* K = stage_at(h, S, "head_train_block_grads_at", block, &rc);
+    if (!K) return rc;
+    if (!io || !block_complete(io, false)) return fail(h, DFD_ERR_ARG, "head_train_block_grads_at: null pointer");
+    return stage_grads(h, K, io, set);
 }
 
 }  // extern "C"

@@ -297,7 +297,7 @@ void headconv_adamw(dfd_handle* h, HeadTrainState* S, double lr, double t) {
     HeadConvState* C = S->conv;
     // S->partial comes first in the norm's sum, as in the head's own launch: both launches see the same norm
     head_train_launch_adamw(h->stream, C->param, C->grad, C->m, C->v, C->ema, CV_COUNT, S->partial, C->partial,
-                            S->block ? headblock_partial(S) : nullptr, S->cfg, lr * (double)C->lr_scale, t, S->scalars + 2);
+                            S->block ? headblock_partial(S) : nullptr, headblock_partial(S, 14), S->cfg, lr * (double)C->lr_scale, t, S->scalars + 2);
 }
 
 int headconv_commit(dfd_handle* h, HeadTrainState* S, int use_ema) {

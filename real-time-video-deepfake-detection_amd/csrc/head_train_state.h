@@ -1,7 +1,8 @@
 // What head_train.hip and head_train_conv.hip share: the trainer's state, the layout of the head's parameter arena and
 // the host entry points each file offers the other.  The conv stage (dfd_head_train_unfreeze_conv) hangs off the head
 // trainer's state; everything from the pooled features on runs in head_train.hip's kernels.  Block 15
-// (dfd_head_train_unfreeze_block, head_train_block.hip) hangs off it in turn and feeds the conv stage on the device.
+// (dfd_head_train_unfreeze_block, head_train_block.hip) hangs off it in turn and feeds the conv stage on the device;
+// block 14 (dfd_head_train_unfreeze_block_at, the same file) feeds block 15.
 #pragma once
 #include <cstdint>
 
@@ -18,7 +19,8 @@ static_assert(O_W2 % 4 == 0 && O_W3 % 4 == 0, "weight rows must stay 16-byte ali
 constexpr int NORM_BLOCKS = 256;
 
 struct HeadConvState;   // head_train_conv.hip: _conv_head + _bn1 under training (null until dfd_head_train_unfreeze_conv)
-struct HeadBlockState;  // head_train_block.hip: _blocks.15 under training (null until dfd_head_train_unfreeze_block)
+struct HeadBlockState;  // head_train_block.hip: one MBConv block under training: `block` = _blocks.15 (null until
+                        // dfd_head_train_unfreeze_block), `block14` = _blocks.14 (null until dfd_head_train_unfreeze_block_at)
 
 struct HeadTrainState {
     dfd_head_config cfg{};
@@ -37,7 +39,25 @@ struct HeadTrainState {
     void* pool = nullptr;
     HeadConvState* conv = nullptr;
     HeadBlockState* block = nullptr;
+    HeadBlockState* block14 = nullptr;
 };
+
+// The trainer's counter-based hash: head_training.dropout_keep_mask is the specification of these three.  layer 0..2 are
+// the head's dropouts, layer 3 block 14's drop-connect (one draw per crop).
+__host__ __device__ inline uint32_t fmix32(uint32_t x) {
+    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+    return x;
+}
+inline uint32_t mask_key(unsigned long long seed, unsigned long long counter, int layer) {
+    uint32_t k = fmix32((uint32_t)seed + 0x9E3779B9u);
+    k = fmix32(k ^ (uint32_t)(seed >> 32));
+    k = fmix32(k ^ (uint32_t)counter);
+    k = fmix32(k ^ (uint32_t)(counter >> 32));
+    return fmix32(k ^ (uint32_t)(layer + 1));
+}
+__host__ __device__ inline bool mask_keep(uint32_t key, uint32_t idx, uint32_t thr) {
+    return fmix32(fmix32(idx ^ key) + key) >= thr;
+}
 
 // what every accumulate entry accepts for its two scalars: lam in [0, 1] and a loss_scale that is a number (NaN fails both)
 inline bool head_train_mix_ok(float lam, float loss_scale) { return lam >= 0.f && lam <= 1.f && loss_scale == loss_scale; }
@@ -51,12 +71,12 @@ int head_train_step(dfd_handle* h, HeadTrainState* S, int n, const float* labels
 // eval-mode forward of the n rows in S->feat with the parameters at P -> S->logits
 int head_train_eval_step(dfd_handle* h, HeadTrainState* S, const float* P, int n);
 void head_train_launch_sumsq(hipStream_t s, const float* g, int count, double* partial);
-// clip + AdamW + EMA + zeroing over one arena at the rate `lr`; partial2 / partial3 (or null): a second and a third
-// arena's partial sums of squares, added to `partial` entry by entry, in this order, before the norm is taken.
-// t = 1-based step number.
+// clip + AdamW + EMA + zeroing over one arena at the rate `lr`; partial2 / partial3 / partial4 (or null): a second, a
+// third and a fourth arena's partial sums of squares, added to `partial` entry by entry, in this order, before the norm
+// is taken.  t = 1-based step number.
 void head_train_launch_adamw(hipStream_t s, float* p, float* g, float* m, float* v, float* ema, int count,
-                             const double* partial, const double* partial2, const double* partial3, const dfd_head_config& c,
-                             double lr, double t, float* norm_out);
+                             const double* partial, const double* partial2, const double* partial3, const double* partial4,
+                             const dfd_head_config& c, double lr, double t, float* norm_out);
 
 // ---- head_train_conv.hip, for the head trainer
 void headconv_destroy(HeadTrainState* S);
@@ -75,11 +95,12 @@ int headconv_step(dfd_handle* h, HeadTrainState* S, int n, const float* labels_a
 int headconv_eval_step(dfd_handle* h, HeadTrainState* S, int use_ema, int n);    // -> S->logits
 
 // ---- head_train_block.hip, for the head trainer
-void headblock_destroy(HeadTrainState* S);
-const double* headblock_sumsq(dfd_handle* h, HeadTrainState* S);             // launches; -> the block arena's partials
-const double* headblock_partial(HeadTrainState* S);
-void headblock_adamw(dfd_handle* h, HeadTrainState* S, double lr, double t);  // the block group's step at lr * the conv stage's lr_scale
-int headblock_commit(dfd_handle* h, HeadTrainState* S, int use_ema);
-int headblock_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out, size_t capacity);  // "b15.*"
+// `block` = 15 or 14 throughout; a stage that is not unfrozen has no partials (null) and nothing to step
+void headblock_destroy(HeadTrainState* S);                                   // both stages
+const double* headblock_sumsq(dfd_handle* h, HeadTrainState* S, int block = 15);   // launches; -> the block arena's partials
+const double* headblock_partial(HeadTrainState* S, int block = 15);
+void headblock_adamw(dfd_handle* h, HeadTrainState* S, double lr, double t);  // the block groups' steps at lr * the conv stage's lr_scale
+int headblock_commit(dfd_handle* h, HeadTrainState* S, int use_ema);          // block 15, then block 14 where it is unfrozen
+int headblock_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out, size_t capacity);  // "b15.*", "b14.*"
 
 }  // namespace dfd

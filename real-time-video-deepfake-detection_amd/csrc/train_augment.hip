@@ -737,12 +737,13 @@ int dfd_train_augment_tap(dfd_handle* h, const unsigned char* rgb_host, int n, i
 }
 
 // the chain at 224 on all n images, then the backbone in chunks of max_batch: pooled rows, or (trunk) block 15's output, or
-// (trunk, block = 14) block 14's
+// (trunk, block = 14) block 14's, or (first_block = 13: dfd_train_augment_block_out) block 13's
 static int augment_forward(dfd_handle* h, const char* who, const unsigned char* rgb, int on_device, int n, int H, int W,
                            const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, float* out_host, bool trunk,
-                           int block = 15) {
+                           int block = 15, int first_block = 14) {
     if (!h) return DFD_ERR_ARG;
-    if (block != 14 && block != 15) return fail(h, DFD_ERR_ARG, "%s: block %d; 14 or 15", who, block);
+    if (block < first_block || block > 15)
+        return fail(h, DFD_ERR_ARG, first_block == 13 ? "%s: block %d; 13, 14 or 15" : "%s: block %d; 14 or 15", who, block);
     int rc = aug_check(h, rgb, n, H, W, DFD_CROP, rows, batch);
     if (rc) return rc;
     if (!out_host) return fail(h, DFD_ERR_ARG, "%s: null pointer", who);
@@ -760,7 +761,7 @@ static int augment_forward(dfd_handle* h, const char* who, const unsigned char* 
             in = h->in_nchw;
         }
         if (trunk) {
-            if ((rc = b0_trunk_to_host(h, in, m, out_host + (size_t)first * (block == 14 ? DFD_BLOCK14_ROW : DFD_TRUNK_ROW), block))) return rc;
+            if ((rc = b0_trunk_to_host(h, in, m, out_host + (size_t)first * (block == 15 ? DFD_TRUNK_ROW : DFD_BLOCK14_ROW), block))) return rc;
             continue;
         }
         rc = b0_forward(h, in, m, nullptr, nullptr, nullptr);
@@ -785,6 +786,11 @@ int dfd_train_augment_trunk(dfd_handle* h, const unsigned char* rgb, int on_devi
 int dfd_train_augment_trunk_at(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
                                const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, int block, float* out_host) {
     return augment_forward(h, "train_augment_trunk_at", rgb, on_device, n, H, W, rows, batch, out_host, true, block);
+}
+
+int dfd_train_augment_block_out(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
+                                const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, int block, float* out_host) {
+    return augment_forward(h, "train_augment_block_out", rgb, on_device, n, H, W, rows, batch, out_host, true, block, 13);
 }
 
 }  // extern "C"

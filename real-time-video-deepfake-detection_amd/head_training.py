@@ -11,7 +11,9 @@ rows", and the conv is a second AdamW group at `backbone_lr_scale` x lr as train
 rows (trunk rows with the conv stage) unless `augment=` is given (then the crops are augmented on the device every epoch and Mixup / CutMix act on the
 images, train_augment.py); a last batch of one row is dropped (BatchNorm1d needs two).  `HeadTrainer(train_block15=True)`
 adds the backbone's last block, ``net._blocks.15`` (csrc/head_train_block.hip): the rows are then block 14's output,
-(n, 7, 7, 192), and the block's tensors join the conv's group; blocks 14 down to 9 of train.py's recipe stay frozen.
+(n, 7, 7, 192), and the block's tensors join the conv's group.  `HeadTrainer(train_block14=True)` adds ``net._blocks.14``
+below it (the identity skip with per-crop drop-connect): the rows are then block 13's output, the same shape; blocks 13
+down to 9 of train.py's recipe stay frozen.
 """
 from __future__ import annotations
 
@@ -51,6 +53,13 @@ BLOCK_TRACKED = tuple(k for k, f in BLOCK_KEYS.items() if f.startswith("nbt"))
 # the state dict's shapes of the conv kernels (the struct holds them without the 1 x 1 axes)
 BLOCK_SD_SHAPES = {"exp_w": (1152, 192, 1, 1), "dw_w": (1152, 1, 3, 3), "se_w1": (48, 1152, 1, 1), "se_w2": (1152, 48, 1, 1),
                    "proj_w": (320, 1152, 1, 1)}
+# block 14 (train_block14=True): the same fields in block 14's shapes (`_lib.BLOCK14_SHAPES`)
+BLOCK14_PREFIX = "net._blocks.14."
+BLOCK14_KEYS = {BLOCK14_PREFIX + k[len(BLOCK_PREFIX):]: f for k, f in BLOCK_KEYS.items()}
+BLOCK14_TRACKED = tuple(k for k, f in BLOCK14_KEYS.items() if f.startswith("nbt"))
+BLOCK14_SD_SHAPES = {"exp_w": (1152, 192, 1, 1), "dw_w": (1152, 1, 5, 5), "se_w1": (48, 1152, 1, 1), "se_w2": (1152, 48, 1, 1),
+                     "proj_w": (192, 1152, 1, 1)}
+DROP_CONNECT_BLOCK14 = 0.2 * 14 / 16     # efficientnet-b0's drop_connect_rate times idx / len(blocks)
 BN_MOMENTUM_BACKBONE = 0.01              # efficientnet_pytorch: 1 - batch_norm_momentum (0.99)
 BN_EPS_BACKBONE = 1e-3                   # efficientnet_pytorch's batch_norm_epsilon, the eps weights.pack_b0 folds with
 LAYER_WIDTHS = (1280, 512, 256)          # what dropout layer 0 / 1 / 2 acts on
@@ -115,6 +124,13 @@ def dropout_keep_mask(seed: int, counter: int, layer: int, n: int, width: int, p
     return (u >= np.uint32(int(p * 4294967296.0))).reshape(n, width)
 
 
+def drop_connect_keep(seed: int, counter: int, n: int, p: float) -> np.ndarray:
+    """The specification of block 14's drop-connect: bool (n,), True = the crop's branch is kept (and scaled by
+    1 / (1 - p)).  The trainer's hash with a fourth layer index and one draw per crop; `p` is the double of the float32
+    setting, the rule `dropout_rates` uses; `counter` = accumulate calls since the trainer was opened."""
+    return dropout_keep_mask(seed, counter, 3, n, 1, float(np.float32(p))).reshape(n)
+
+
 # --------------------------------------------------------------------------- loss and metrics on the host
 def focal_loss(logits, targets, gamma: float = 2.0, alpha: float = 0.25, label_smoothing: float = 0.0) -> float:
     """train.py:380-392 in float64 numpy (validation loss; the training loss comes from the device)"""
@@ -166,7 +182,7 @@ def fit_loop(trainer, features, labels, epochs: int, batch_size: int = 32, grad_
     `max_n` and `loss_settings` (HeadTrainer; the tests' float64 oracle).  A trainer may carry `row_width` (floats of one
     row; default 1280) and `extract_method` (the extractor call `augment=` uses; default "train_augment_features"): a
     trainer with the conv stage takes trunk rows of 15680 floats from "train_augment_trunk", one with block 15 rows of 9408
-    floats from "train_augment_block14", and feature-space Mixup then acts on those rows.  Returns a log shaped like
+    floats from "train_augment_block14" (with block 14: "train_augment_block13"), and feature-space Mixup then acts on those rows.  Returns a log shaped like
     weights/training_log.json: one dict per epoch (epoch, train_loss, train_acc, val_loss, val_acc, val_f1, val_auc,
     lr, time_seconds).
 
@@ -310,6 +326,10 @@ class HeadTrainer:
     (n, 9408) - the block's tensors step at `backbone_lr_scale` x lr with the conv's, and `commit` / `export_state_dict`
     cover all three groups.
 
+    `train_block14=True` (implies `train_block15`) also trains ``net._blocks.14`` (`dfd_head_train_unfreeze_block_at`) with
+    per-crop drop-connect at rate `drop_connect`: the rows are then block 13's output - `Handle.extract_block(x, 13)`'s
+    (n, 7, 7, 192) or (n, 9408) - and `commit` / `export_state_dict` cover all four groups.
+
     `model_or_handle`: a `DeepfakeEfficientNet` (its handle and state dict are used) or a `_lib.Handle` with
     `state_dict` (reference key names, at least the ten ``net._fc.*`` tensors and the four running statistics).
     `config`: fields of `dfd_head_config` - max_n, seed, dropout, beta1, beta2, eps, weight_decay, focal_gamma,
@@ -320,7 +340,8 @@ class HeadTrainer:
     (n, 15680) - the conv tensors step at `backbone_lr_scale` x lr, and `commit` / `export_state_dict` cover both."""
 
     def __init__(self, model_or_handle, state_dict: Optional[Mapping[str, np.ndarray]] = None, train_conv_head: bool = False,
-                 backbone_lr_scale: float = 0.1, train_block15: bool = False, **config):
+                 backbone_lr_scale: float = 0.1, train_block15: bool = False, train_block14: bool = False,
+                 drop_connect: float = DROP_CONNECT_BLOCK14, **config):
         if isinstance(model_or_handle, _lib.Handle):
             handle = model_or_handle
             if state_dict is None:
@@ -333,15 +354,20 @@ class HeadTrainer:
         params = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
                   for k, f in KEYS.items()}
         self._tracked = [int(np.asarray(sd[k])) if k in sd else 0 for k in TRACKED]
-        self.train_block15 = bool(train_block15)
+        self.train_block14 = bool(train_block14)
+        self.train_block15 = bool(train_block15) or self.train_block14
         self.train_conv_head = bool(train_conv_head) or self.train_block15
         self.row_width = _lib.BLOCK14_ROW if self.train_block15 else _lib.TRUNK_ROW if self.train_conv_head else 1280
-        self.extract_method = ("train_augment_block14" if self.train_block15 else
+        self.extract_method = ("train_augment_block13" if self.train_block14 else "train_augment_block14" if self.train_block15 else
                                "train_augment_trunk" if self.train_conv_head else "train_augment_features")
         if self.train_block15:
             block = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
                      for k, f in BLOCK_KEYS.items() if not f.startswith("nbt")}
             self._block_tracked = [int(np.asarray(sd[k])) if k in sd else 0 for k in BLOCK_TRACKED]
+        if self.train_block14:
+            block14 = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
+                       for k, f in BLOCK14_KEYS.items() if not f.startswith("nbt")}
+            self._block14_tracked = [int(np.asarray(sd[k])) if k in sd else 0 for k in BLOCK14_TRACKED]
         if self.train_conv_head:
             conv = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
                     for k, f in CONV_KEYS.items()}
@@ -362,6 +388,12 @@ class HeadTrainer:
         if self.train_block15:
             try:
                 handle.head_train_unfreeze_block(block, 15, BN_MOMENTUM_BACKBONE, BN_EPS_BACKBONE)
+            except Exception:
+                self.close()
+                raise
+        if self.train_block14:
+            try:
+                handle.head_train_unfreeze_block_at(block14, 14, BN_MOMENTUM_BACKBONE, BN_EPS_BACKBONE, drop_connect)
             except Exception:
                 self.close()
                 raise
@@ -407,7 +439,7 @@ class HeadTrainer:
         """the head under the reference's names: ten ``net._fc.*`` parameters, four running statistics (always the live
         ones) and the two ``num_batches_tracked`` counters; with the conv stage also ``net._conv_head.weight``
         ((1280, 320, 1, 1)), ``net._bn1.*`` and its counter; with block 15 also the 22 ``net._blocks.15.*`` entries of
-        `BLOCK_KEYS` (conv kernels in the state dict's 4-d shapes)"""
+        `BLOCK_KEYS` (conv kernels in the state dict's 4-d shapes); with block 14 also the 22 of `BLOCK14_KEYS`"""
         out = self._h.head_train_export(use_ema)
         sd = {k: out[f] for k, f in KEYS.items()}
         for k, t in zip(TRACKED, self._tracked):
@@ -421,10 +453,15 @@ class HeadTrainer:
             sd.update({k: blk[f].reshape(BLOCK_SD_SHAPES.get(f, blk[f].shape)) for k, f in BLOCK_KEYS.items() if f in blk})
             for k, t in zip(BLOCK_TRACKED, self._block_tracked):
                 sd[k] = np.array(t + self.accumulates, dtype=np.int64)
+        if self.train_block14:
+            blk = self._h.head_train_export_block_at(14, use_ema)
+            sd.update({k: blk[f].reshape(BLOCK14_SD_SHAPES.get(f, blk[f].shape)) for k, f in BLOCK14_KEYS.items() if f in blk})
+            for k, t in zip(BLOCK14_TRACKED, self._block14_tracked):
+                sd[k] = np.array(t + self.accumulates, dtype=np.int64)
         return sd
 
     def commit(self, use_ema: bool = True):
-        """fold BatchNorm and swap the head (and, with the conv stage, the head conv; with block 15, its ten tensors) the
+        """fold BatchNorm and swap the head (and, with the conv stage, the head conv; with block 15 and block 14, their ten tensors each) the
         handle classifies with (`dfd_head_train_commit`)"""
         self._h.head_train_commit(use_ema)
 
@@ -435,4 +472,5 @@ class HeadTrainer:
                         cutmix_alpha)
 
 
-__all__ = ["HeadTrainer", "fit_loop", "one_cycle_lr", "dropout_keep_mask", "dropout_rates", "focal_loss", "KEYS", "CONV_KEYS", "BLOCK_KEYS"]
+__all__ = ["HeadTrainer", "fit_loop", "one_cycle_lr", "dropout_keep_mask", "dropout_rates", "focal_loss", "KEYS", "CONV_KEYS", "BLOCK_KEYS", "BLOCK14_KEYS",
+           "drop_connect_keep"]
