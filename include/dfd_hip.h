@@ -1016,8 +1016,8 @@ int dfd_frequency_features_tap(dfd_handle* h, const unsigned char* img, int hh, 
  * In dfd_mbconv_params block 14's shapes are those of block 15 except dw_w [1152][5][5], proj_w [192][1152] and g2 / be2 /
  * rm2 / rv2 [192]: 587 952 trainable floats.
  *
- * dfd_head_train_unfreeze_block_at adds block `block` below block 15: `block` must be 14 (any other:
- * DFD_ERR_UNSUPPORTED); legal once, after dfd_head_train_unfreeze_block and before the first accumulate (anything else:
+ * dfd_head_train_unfreeze_block_at adds block `block` below block 15: `block` must be 14, or 13 or 12 under the rules of
+ * the next section (any other: DFD_ERR_UNSUPPORTED); legal once, after dfd_head_train_unfreeze_block and before the first accumulate (anything else:
  * DFD_ERR_ARG); a null field, bn_momentum outside [0, 1], bn_eps <= 0, drop_connect outside [0, 1) or NaN: DFD_ERR_ARG.
  * One hipMalloc holds everything the stage needs for max_n crops; it is freed with the trainer and no later call
  * allocates.  The Python side passes bn_momentum 0.01, bn_eps 1e-3 and drop_connect 0.2 * 14 / 16 (efficientnet-b0's
@@ -1027,7 +1027,7 @@ int dfd_frequency_features_tap(dfd_handle* h, const unsigned char* img, int hh, 
  * of the float32 drop_connect: out = x13 + (y / keep_prob) b_i, b_i = head_training.dropout_keep_mask(seed, counter,
  * layer = 3, n, width = 1, p)[i]; a dropped crop's output is its input row bit for bit, and it still counts in the batch
  * statistics and running updates of the block's BatchNorms, which come before the mask.  Eval applies no drop-connect.
- * Block 15 hands dOut14 = dZe15 . We15 down; BN2's gradient source is dOut14 b_i / keep_prob; block 13 stays frozen, so
+ * Block 15 hands dOut14 = dZe15 . We15 down; BN2's gradient source is dOut14 b_i / keep_prob; while block 13 is frozen
  * no gradient leaves block 14.  dfd_head_train_apply takes ONE gradient norm over the four arenas (partial sums added
  * entry by entry: head, conv, block 15, block 14) and one clip coefficient; block 14 steps at lr * lr_scale with the same
  * betas, eps and weight decay; EMA and zeroing cover it.  dfd_head_train_commit also folds block 14's three BatchNorms
@@ -1039,8 +1039,9 @@ int dfd_frequency_features_tap(dfd_handle* h, const unsigned char* img, int hh, 
  * stage they are DFD_ERR_ARG.  A trainer without the stage launches exactly what it launched before. */
 int dfd_head_train_unfreeze_block_at(dfd_handle* h, int block, const dfd_mbconv_params* init, float bn_momentum, float bn_eps,
                                      float drop_connect);
-/* dfd_head_train_export_block / _block_grads for block 14 or 15 (15: the bits of those two); any other block:
- * DFD_ERR_UNSUPPORTED; a block that is not unfrozen: DFD_ERR_ARG */
+/* dfd_head_train_export_block / _block_grads for block 12 .. 15 (15: the bits of those two); any other block:
+ * DFD_ERR_UNSUPPORTED; block 14 or 15 while it is not unfrozen: DFD_ERR_ARG; block 13 or 12 while it is not unfrozen:
+ * DFD_ERR_UNSUPPORTED */
 int dfd_head_train_export_block_at(dfd_handle* h, int block, int use_ema, dfd_mbconv_params* out);
 int dfd_head_train_block_grads_at(dfd_handle* h, int block, dfd_mbconv_params* io, int set);
 /* dfd_extract_trunk_at / dfd_train_augment_trunk_at for block 13, 14 or 15: 14 and 15 give the bits of those entries, 13
@@ -1048,6 +1049,35 @@ int dfd_head_train_block_grads_at(dfd_handle* h, int block, dfd_mbconv_params* i
 int dfd_extract_block_out(dfd_handle* h, const float* nchw_host, int n, int block, float* out_host);
 int dfd_train_augment_block_out(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
                                 const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, int block, float* out_host);
+
+/* ---- fine-tuning blocks 13 and 12 below block 14 ------------------------------------------------
+ * net._blocks.13 and net._blocks.12 have block 14's geometry exactly (MBConv k5, stride 1, pad 2 / 2, 192 -> 1152 -> 192,
+ * squeeze-excite 48, 7 x 7, identity skip, 587 952 trainable floats, the shapes of block 14 in dfd_mbconv_params) and run
+ * block 14's launches on a state of their own: after them every 7 x 7 block of the reference's unfrozen group trains.
+ *
+ * dfd_head_train_unfreeze_block_at takes the blocks from the top down, before the first accumulate: 13 once 14 is
+ * unfrozen, 12 once 13 is.  13 or 12 while the block above it is frozen: DFD_ERR_UNSUPPORTED; a block that is already
+ * unfrozen, or any block after an accumulate: DFD_ERR_ARG; blocks outside 12..14: DFD_ERR_UNSUPPORTED.  Each stage is
+ * ONE hipMalloc at max_n, freed with the trainer.  The Python side passes drop_connect 0.2 * b / 16: 0.175, 0.1625, 0.15.
+ * The rows of dfd_head_train_accumulate_block / _eval_block are the input rows of the deepest unfrozen block (block 12's
+ * or block 11's output; dfd_extract_block_input below).  Block b writes out = x_(b-1) + (BN2(Zp) / keep_prob_b) b_i
+ * into block b + 1's input; its mask is head_training.dropout_keep_mask(seed, counter, layer = 17 - b, n, 1, p_b): 3 for
+ * block 14, 4 for 13, 5 for 12, so the blocks drop independently.  A trained skip block with a trained block below it
+ * hands down dX_b = dOut_b + dZe_b . We_b, the sum formed in double and rounded once; the deepest trained block hands
+ * nothing down, and a trainer whose deepest block is 14 launches exactly what it launched before.  A dropped crop's
+ * branch still receives a gradient through the batch statistics of the other crops; only when every crop of block b is
+ * dropped are block b's gradients exactly 0 and dX_b == dOut_b element for element.
+ * dfd_head_train_apply takes ONE norm over up to six arenas (partial sums added entry by entry: head, conv, 15, 14, 13,
+ * 12); EMA, zeroing and dfd_head_train_commit (15, 14, 13, 12 in that order; the ten b13.* / b12.* tensors and their two
+ * cached splits rewritten in place) cover every stage.  dfd_head_train_tap knows "b13.*" and "b12.*" with block 14's six
+ * names (out, gate, ad, keep, dout, dae); without the stage they are DFD_ERR_ARG.
+ *
+ * dfd_extract_block_input / dfd_train_augment_block_input: the input rows of block `block` in 12..15, [n][7][7][192],
+ * the "b{block-1}.out" tap of the same forward; for 14 and 15 the bits of dfd_extract_block_out /
+ * dfd_train_augment_block_out at block - 1 (those entries serve the outputs of blocks 13..15).  Any other block: DFD_ERR_ARG.  n and capacity as those entries. */
+int dfd_extract_block_input(dfd_handle* h, const float* nchw_host, int n, int block, float* out_host);
+int dfd_train_augment_block_input(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
+                                  const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, int block, float* out_host);
 
 #ifdef __cplusplus
 }

@@ -207,6 +207,9 @@ SIGNATURES = {
     "dfd_extract_block_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dfd_train_augment_block_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_int, C.c_void_p]),
+    "dfd_extract_block_input": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dfd_train_augment_block_input": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_void_p]),
     "dfd_train_augment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dfd_train_augment_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),
@@ -307,7 +310,7 @@ BLOCK_SHAPES = {"exp_w": (1152, 192), "dw_w": (1152, 3, 3), "se_w1": (48, 1152),
 BLOCK_SHAPES.update({k + str(l): ((1152,) if l < 2 else (320,)) for l in range(3) for k in ("g", "be", "rm", "rv")})
 # block 14 in the same struct (k5, 192 -> 1152 -> 192); blocks 13 and 12 have these shapes too
 BLOCK14_SHAPES = dict(BLOCK_SHAPES, dw_w=(1152, 5, 5), proj_w=(192, 1152), g2=(192,), be2=(192,), rm2=(192,), rv2=(192,))
-BLOCK_SHAPES_AT = {15: BLOCK_SHAPES, 14: BLOCK14_SHAPES}
+BLOCK_SHAPES_AT = {15: BLOCK_SHAPES, 14: BLOCK14_SHAPES, 13: BLOCK14_SHAPES, 12: BLOCK14_SHAPES}
 BLOCK_OUT_SHAPES = {13: BLOCK14_SHAPE, 14: BLOCK14_SHAPE, 15: TRUNK_SHAPE}     # what `Handle.extract_block` returns per crop
 
 
@@ -622,6 +625,14 @@ class Handle:
         self._check(self._lib.dfd_extract_block_out(self._p, _ptr(a), a.shape[0], int(block), _ptr(out)))
         return out
 
+    def extract_block_input(self, x, block: int) -> np.ndarray:
+        """the input rows of block 12, 13, 14 or 15, (n,7,7,192) float32 NHWC (`dfd_extract_block_input`): the output of the
+        block below, the rows a trainer whose deepest unfrozen block is `block` trains on; any other block is refused"""
+        a = self._as_nchw(x)
+        out = np.empty((a.shape[0],) + BLOCK14_SHAPE, dtype=np.float32)
+        self._check(self._lib.dfd_extract_block_input(self._p, _ptr(a), a.shape[0], int(block), _ptr(out)))
+        return out
+
     # -- train-time augmentation (include/dfd_hip.h "train-time image augmentation"; train_augment.draw_batch makes the tables)
     @staticmethod
     def _aug_tables(n, rows, batch):
@@ -730,6 +741,22 @@ class Handle:
         """`train_augment_block(block=13)`: the extractor of a trainer with block 14 unfrozen"""
         return self.train_augment_block(rgb, rows, batch, shape, block=13)
 
+    def train_augment_block_input(self, rgb, rows, batch, block: int = 12, shape=None) -> np.ndarray:
+        """`train_augment_features` with the input rows of block 12, 13, 14 or 15 in place of the pooled rows -> (n,7,7,192)
+        (`dfd_train_augment_block_input`)"""
+        def fn(p, src, on_device, n, hh, ww, r, b, out):
+            return self._lib.dfd_train_augment_block_input(p, src, on_device, n, hh, ww, r, b, int(block), out)
+
+        return self._train_augment_forward(fn, BLOCK14_SHAPE, rgb, rows, batch, shape)
+
+    def train_augment_input13(self, rgb, rows, batch, shape=None) -> np.ndarray:
+        """`train_augment_block_input(block=13)`: the extractor of a trainer with block 13 unfrozen"""
+        return self.train_augment_block_input(rgb, rows, batch, block=13, shape=shape)
+
+    def train_augment_input12(self, rgb, rows, batch, shape=None) -> np.ndarray:
+        """`train_augment_block_input(block=12)`: the extractor of a trainer with block 12 unfrozen"""
+        return self.train_augment_block_input(rgb, rows, batch, block=12, shape=shape)
+
     # -- head training (include/dfd_hip.h "classifier head training"; head_training.HeadTrainer is the front end)
     @staticmethod
     def _as_features(x) -> np.ndarray:
@@ -790,8 +817,10 @@ class Handle:
     def head_train_tap(self, name: str, n: int) -> np.ndarray:
         width = {"mask0": 1280, "mask1": 512, "mask2": 256, "z1": 512, "z2": 256, "a1": 512, "a2": 256}.get(name, 1280)   # unknown names: the library refuses
         wide = {"cz": (49, 1280), "b15.out": (49, 320), "b15.dout": (49, 320), "b15.ad": (49, 1152), "b15.dae": (49, 1152),
-                "b15.gate": (1152,), "b14.out": (49, 192), "b14.dout": (49, 192), "b14.ad": (49, 1152), "b14.dae": (49, 1152),
-                "b14.gate": (1152,), "b14.keep": ()}
+                "b15.gate": (1152,)}
+        for b in (14, 13, 12):                                  # the skip blocks share block 14's six taps
+            wide.update({f"b{b}.out": (49, 192), f"b{b}.dout": (49, 192), f"b{b}.ad": (49, 1152), f"b{b}.dae": (49, 1152),
+                         f"b{b}.gate": (1152,), f"b{b}.keep": ()})
         out = np.empty((int(n),) + wide.get(name, (width,)), np.float32)
         self._check(self._lib.dfd_head_train_tap(self._p, name.encode(), _ptr(out), out.size))
         return out
@@ -904,10 +933,13 @@ class Handle:
         return out
 
     # -- block 14 of the head trainer (include/dfd_hip.h "fine-tuning block 14 with block 15, the head conv and the head");
-    #    once it is unfrozen `head_train_accumulate_block` / `_eval_block` take rows of block 13's output (the same width)
+    #    once it is unfrozen `head_train_accumulate_block` / `_eval_block` take rows of block 13's output (the same width);
+    #    blocks 13 and 12 follow from the top down ("fine-tuning blocks 13 and 12 below block 14"), the rows are then the
+    #    input rows of the deepest unfrozen block (`extract_block_input`)
     def head_train_unfreeze_block_at(self, params, block: int = 14, bn_momentum: float = 0.01, bn_eps: float = 1e-3,
                                      drop_connect: float = 0.2 * 14 / 16):
-        """params: dict of the 19 `BLOCK_FIELDS` arrays in block 14's shapes (`BLOCK14_SHAPES`)"""
+        """params: dict of the 19 `BLOCK_FIELDS` arrays in block 14's shapes (`BLOCK14_SHAPES`); `block` = 14, then 13, then
+        12 (each with its own `drop_connect`; the reference's rates are 0.2 * block / 16)"""
         missing = [k for k in BLOCK_FIELDS if k not in params]
         if missing:
             raise KeyError(f"block parameters missing: {missing}")
@@ -921,7 +953,7 @@ class Handle:
         return out
 
     def head_train_block_grads_at(self, block: int, set_to=None):
-        """`head_train_block_grads` of block 14 or 15"""
+        """`head_train_block_grads` of block 12 .. 15"""
         if set_to is not None:
             bp, _keep = _block_arrays(set_to, BLOCK_STAT_FIELDS, block)
             self._check(self._lib.dfd_head_train_block_grads_at(self._p, int(block), C.byref(bp), 1))

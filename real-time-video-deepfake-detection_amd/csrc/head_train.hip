@@ -400,22 +400,20 @@ __global__ __launch_bounds__(HT_THREADS) void ht_sumsq_kernel(const float* __res
 
 // clip_grad_norm_ + torch.optim.AdamW (single-tensor path, in its order) + EMAModel.update + zero_grad, one element per thread.
 // decay_mul = 1 - lr wd, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t): computed on the host in double.
-// The squared norm is the sum of partial[] (and, entry by entry, partial2[], partial3[] then partial4[] when given).
+// The squared norm is the sum of the arenas' partials, added entry by entry in the table's order (head, conv, block 15, 14,
+// 13, 12; null entries left out): one norm over every group.
 __global__ __launch_bounds__(HT_THREADS) void ht_adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                               float* __restrict__ v, float* __restrict__ ema, int count,
-                                                              const double* __restrict__ partial,
-                                                              const double* __restrict__ partial2,
-                                                              const double* __restrict__ partial3,
-                                                              const double* __restrict__ partial4, float clip_norm,
+                                                              NormParts parts, float clip_norm,
                                                               float decay_mul, float w1, float beta2, float w2, float step_size,
                                                               float bc2_sqrt, float eps, float ema_decay, float ema_w,
                                                               float* __restrict__ norm_out) {
     __shared__ double sh[HT_THREADS];
     static_assert(NORM_BLOCKS == HT_THREADS, "one partial per thread");
-    double mine = partial[threadIdx.x];
-    if (partial2) mine += partial2[threadIdx.x];                // the conv stage's arena: one norm over both groups
-    if (partial3) mine += partial3[threadIdx.x];                // block 15's arena: one norm over all three
-    if (partial4) mine += partial4[threadIdx.x];                // block 14's arena: one norm over all four
+    double mine = parts.p[0][threadIdx.x];
+#pragma unroll
+    for (int a = 1; a < HT_ARENAS; ++a)
+        if (parts.p[a]) mine += parts.p[a][threadIdx.x];
     const float norm = (float)sqrt(block_sum(mine, sh));
     const float coef = fminf(clip_norm / (norm + 1e-6f), 1.f);
     const int i = blockIdx.x * HT_THREADS + threadIdx.x;
@@ -454,12 +452,19 @@ void head_train_launch_sumsq(hipStream_t s, const float* g, int count, double* p
     hipLaunchKernelGGL(ht_sumsq_kernel, dim3(NORM_BLOCKS), dim3(HT_THREADS), 0, s, g, count, partial);
 }
 
-void head_train_launch_adamw(hipStream_t s, float* p, float* g, float* m, float* v, float* ema, int count, const double* partial,
-                             const double* partial2, const double* partial3, const double* partial4, const dfd_head_config& c,
-                             double lr, double t, float* norm_out) {
+NormParts head_train_norm_parts(HeadTrainState* S) {
+    NormParts parts{};
+    parts.p[0] = S->partial;
+    parts.p[1] = S->conv ? headconv_partial(S) : nullptr;
+    for (int k = 0; k < HT_STAGES; ++k) parts.p[2 + k] = headblock_partial(S, k);
+    return parts;
+}
+
+void head_train_launch_adamw(hipStream_t s, float* p, float* g, float* m, float* v, float* ema, int count, const NormParts& parts,
+                             const dfd_head_config& c, double lr, double t, float* norm_out) {
     const double bc1 = 1.0 - std::pow((double)c.beta1, t), bc2 = 1.0 - std::pow((double)c.beta2, t);
     hipLaunchKernelGGL(ht_adamw_kernel, dim3((count + HT_THREADS - 1) / HT_THREADS), dim3(HT_THREADS), 0, s, p, g, m, v, ema, count,
-                       partial, partial2, partial3, partial4, c.clip_norm, (float)(1.0 - lr * (double)c.weight_decay), (float)(1.0 - (double)c.beta1),
+                       parts, c.clip_norm, (float)(1.0 - lr * (double)c.weight_decay), (float)(1.0 - (double)c.beta1),
                        c.beta2, (float)(1.0 - (double)c.beta2), (float)(lr / bc1), (float)std::sqrt(bc2), c.eps, c.ema_decay,
                        (float)(1.0 - (double)c.ema_decay), norm_out);
 }
@@ -682,13 +687,12 @@ int dfd_head_train_apply(dfd_handle* h, float lr, float* grad_norm_out) {
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     const double t = (double)(S->step + 1);
     head_train_launch_sumsq(h->stream, S->grad, HT_COUNT, S->partial);
-    const double* partial2 = S->conv ? headconv_sumsq(h, S) : nullptr;          // one norm over all groups
-    const double* partial3 = S->block ? headblock_sumsq(h, S) : nullptr;
-    const double* partial4 = S->block14 ? headblock_sumsq(h, S, 14) : nullptr;
-    head_train_launch_adamw(h->stream, S->param, S->grad, S->m, S->v, S->ema, HT_COUNT, S->partial, partial2, partial3, partial4,
-                            S->cfg, (double)lr, t, S->scalars + 1);
+    if (S->conv) headconv_sumsq(h, S);                                          // one norm over all groups
+    for (int k = 0; k < HT_STAGES && S->stage[k]; ++k) headblock_sumsq(h, S, k);
+    head_train_launch_adamw(h->stream, S->param, S->grad, S->m, S->v, S->ema, HT_COUNT, head_train_norm_parts(S), S->cfg, (double)lr, t,
+                            S->scalars + 1);
     if (S->conv) headconv_adamw(h, S, (double)lr, t);
-    if (S->block) headblock_adamw(h, S, (double)lr, t);
+    if (S->stage[0]) headblock_adamw(h, S, (double)lr, t);
     DFD_HIP_TRY(h, hipGetLastError());
     ++S->step;
     if (grad_norm_out) {
@@ -752,7 +756,7 @@ int dfd_head_train_tap(dfd_handle* h, const char* name, float* out, size_t capac
     if (!name || !out) return fail(h, DFD_ERR_ARG, "head_train_tap: null pointer");
     if (S->last_n == 0) return fail(h, DFD_ERR_ARG, "head_train_tap: no accumulate has run yet");
     if (!strcmp(name, "cfeat") || !strcmp(name, "dfeat") || !strcmp(name, "cz")) return headconv_tap(h, S, name, out, capacity);
-    if (!strncmp(name, "b15.", 4) || !strncmp(name, "b14.", 4)) return headblock_tap(h, S, name, out, capacity);
+    if (name[0] == 'b' && name[1] == '1' && name[2] >= '2' && name[2] <= '5' && name[3] == '.') return headblock_tap(h, S, name, out, capacity);
     const uint8_t* mask = nullptr;
     const float* act = nullptr;
     int width = 0;
@@ -784,7 +788,7 @@ int dfd_head_train_commit(dfd_handle* h, int use_ema) {
     HeadTrainState* S = open_state(h, "head_train_commit", &rc);
     if (!S) return rc;
     DFD_HIP_TRY(h, hipSetDevice(h->device));
-    if (S->block && (rc = headblock_commit(h, S, use_ema))) return rc;         // the blocks' BatchNorms folded, b15.* / b14.*
+    if (S->stage[0] && (rc = headblock_commit(h, S, use_ema))) return rc;      // the blocks' BatchNorms folded, b15.* .. b12.*
     if (S->conv && (rc = headconv_commit(h, S, use_ema))) return rc;           // _bn1 folded into _conv_head, head.w / head.b
     std::vector<float> P(HT_COUNT), rm1(HT_H1), rv1(HT_H1), rm2(HT_H2), rv2(HT_H2);
     DFD_HIP_TRY(h, hipMemcpyAsync(P.data(), use_ema ? S->ema : S->param, (size_t)HT_COUNT * 4, hipMemcpyDeviceToHost, h->stream));

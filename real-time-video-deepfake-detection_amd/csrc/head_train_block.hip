@@ -19,7 +19,14 @@
 // (Geo: kernel size, output width, skip) the host functions below are instantiated with.  Its last forward launch
 // (bk_bn_skip_kernel) writes out = x13 + (BN2(Zp) / keep_prob) b_i into block 15's input buffer; block 15's backward then
 // ends with dOut14 = dZe15 . We15 (gemm_dyw<6, Grad0>), and block 14's BN2 takes dOut14 b_i / keep_prob as its gradient
-// source (Grad2<true>).  Block 13 is frozen: no gradient leaves block 14.  Blocks 13 and 12 have block 14's geometry.
+// source (Grad2<true>).
+//
+// Blocks 13 and 12 (the same entry, once the block above is unfrozen) have block 14's geometry exactly and run block 14's
+// instantiations on a third and a fourth state; the block's index is a run-time field that only names taps, plan entries
+// and messages.  Block b writes its output into block b + 1's input buffer.  A trained skip block with a trained block
+// below it hands down dX_b = dOut_b + dZe_b . We_b (gemm_dyw<6, Grad0, true>: the skip path added to the branch in double,
+// one rounding) into that block's dx; the deepest trained block hands nothing down.  Block b draws its drop-connect mask
+// from the trainer's hash with layer 17 - b.
 //
 // Arithmetic as head_train_conv.hip: the GEMMs run on the fp64 MFMA with fp32 operands widened at the load
 // (head_train_gemm.h), every other element is computed in double from stored fp32 values and rounded once where it is
@@ -50,11 +57,11 @@ namespace {
 constexpr int BK_IN = 192, BK_EXP = 1152, BK_SE = 48, BK_HW = 49, BK_H = 7, BK_ROW = BK_HW * BK_IN;
 constexpr int BK_JE = 6;                  // column tiles a wave over 1152 = 12 x 96
 constexpr int BK_DW_CROPS = 8;            // crops of one partial depthwise weight gradient
-// A block's geometry: its index, depthwise kernel size (pad KS / 2), output width, whether it has the identity skip, and JP,
-// the column tiles a wave of the projection's forward GEMM.  The block group's arena (floats); every offset a multiple of 4.
-template <int INDEX, int KS_, int OUT_, bool SKIP_, int JP_>
+// A block's geometry: its depthwise kernel size (pad KS / 2), output width, whether it has the identity skip, and JP, the
+// column tiles a wave of the projection's forward GEMM.  The block group's arena (floats); every offset a multiple of 4.
+template <int KS_, int OUT_, bool SKIP_, int JP_>
 struct Geo {
-    static constexpr int INDEX_ = INDEX, KS = KS_, TAPS = KS_ * KS_, PAD = KS_ / 2, OUT = OUT_, JP = JP_;
+    static constexpr int KS = KS_, TAPS = KS_ * KS_, PAD = KS_ / 2, OUT = OUT_, JP = JP_;
     static constexpr bool SKIP = SKIP_;
     static constexpr int O_WE = 0, O_WD = O_WE + BK_EXP * BK_IN, O_W1 = O_WD + BK_EXP * TAPS, O_B1 = O_W1 + BK_SE * BK_EXP;
     static constexpr int O_W2 = O_B1 + BK_SE, O_B2 = O_W2 + BK_EXP * BK_SE, O_WP = O_B2 + BK_EXP, O_G0 = O_WP + OUT * BK_EXP;
@@ -65,12 +72,13 @@ struct Geo {
     static_assert(OUT % 16 == 0, "gemm_dyw splits its channels over four waves");
     static_assert(O_WD % 4 == 0 && O_W1 % 4 == 0 && O_W2 % 4 == 0 && O_WP % 4 == 0, "weight rows must stay 16-byte aligned");
 };
-typedef Geo<15, 3, 320, false, 5> G15;    // 320 = 4 x 80
-typedef Geo<14, 5, 192, true, 6> G14;     // 192 = 2 x 96; blocks 13 and 12 have this geometry too
+typedef Geo<3, 320, false, 5> G15;        // block 15; 320 = 4 x 80
+typedef Geo<5, 192, true, 6> G14;         // blocks 14, 13 and 12; 192 = 2 x 96
+constexpr int BK_LAST = 15, BK_FIRST = BK_LAST - (HT_STAGES - 1);   // the blocks a trainer can hold: stage k = block 15 - k
 static_assert(G15::COUNT == 717232, "trainable floats of block 15");
-static_assert(G14::COUNT == 587952, "trainable floats of block 14");
+static_assert(G14::COUNT == 587952, "trainable floats of each of blocks 14, 13 and 12");
 static_assert(DFD_TRUNK_ROW == BK_HW * G15::OUT, "block 15's output is the conv stage's row");
-static_assert(G14::OUT == BK_IN && BK_IN % (16 * BK_JE) == 0, "block 14's output is block 15's input; dOut14 = dZe15 . We15 in 96-column tiles");
+static_assert(G14::OUT == BK_IN && BK_IN % (16 * BK_JE) == 0, "a skip block's output is the next block's input; dOut = dZe . We in 96-column tiles");
 // the same at run time, for the host code that only moves tensors
 struct Layout {
     int index, ks, taps, out;
@@ -78,8 +86,8 @@ struct Layout {
     int o_we, o_wd, o_w1, o_b1, o_w2, o_b2, o_wp, o_g[3], o_be[3], count, bnc[3];
 };
 template <class G>
-Layout layout_of() {
-    return Layout{G::INDEX_, G::KS, G::TAPS, G::OUT, G::SKIP, G::O_WE, G::O_WD, G::O_W1, G::O_B1, G::O_W2, G::O_B2, G::O_WP,
+Layout layout_of(int index) {
+    return Layout{index, G::KS, G::TAPS, G::OUT, G::SKIP, G::O_WE, G::O_WD, G::O_W1, G::O_B1, G::O_W2, G::O_B2, G::O_WP,
                   {G::O_G0, G::O_G1, G::O_G2}, {G::O_BE0, G::O_BE1, G::O_BE2}, G::COUNT, {BK_EXP, BK_EXP, G::OUT}};
 }
 
@@ -104,7 +112,7 @@ __global__ __launch_bounds__(HT_THREADS) void bk_bn_kernel(const float* __restri
     out[i] = (float)((((double)Z[i] - k.mean) * k.istd) * k.gamma + k.beta);
 }
 
-// Block 14's output: out = x + (BN(Zp) / keep_prob) b_i (efficientnet_pytorch's drop_connect), in double, rounded once.
+// A skip block's output: out = x + (BN(Zp) / keep_prob) b_i (efficientnet_pytorch's drop_connect), in double, rounded once.
 // keep [crop] != 0 where b_i = 1 (null: every crop kept - eval, with keep_prob = 1); a dropped crop's output is its input
 // row bit for bit.  X and out are different buffers.
 __global__ __launch_bounds__(HT_THREADS) void bk_bn_skip_kernel(const float* __restrict__ Z, BnC bn, const float* __restrict__ X,
@@ -403,8 +411,8 @@ struct HeadBlockState {
            *sdx[3] = {nullptr, nullptr, nullptr};
     double *spart = nullptr, *spart2 = nullptr, *wpart = nullptr, *dwpart = nullptr, *partial = nullptr;
     double *r = nullptr, *q = nullptr, *du = nullptr, *dr = nullptr, *ds = nullptr;
-    // the skip's drop-connect (block 14): rate, 1 - rate, floor(rate 2^32); per crop the factor of the last accumulate, 0 or
-    // 1 / keep_prob ("b14.keep"), on the device and as it was uploaded; the norm this arena's AdamW launch writes
+    // the skip's drop-connect (blocks 14, 13, 12): rate, 1 - rate, floor(rate 2^32); per crop the factor of the last accumulate,
+    // 0 or 1 / keep_prob ("b14.keep"), on the device and as it was uploaded; the norm this arena's AdamW launch writes
     double drop_p = 0.0, keep_prob = 1.0;
     uint32_t drop_thr = 0;
     float *keep = nullptr, *norm = nullptr;
@@ -420,52 +428,54 @@ void destroy_one(HeadBlockState** slot) {
     delete K;
     *slot = nullptr;
 }
-HeadBlockState* stage_of(HeadTrainState* S, int block) { return block == 14 ? S->block14 : S->block; }
+// the stage of block 15 .. 12, or null where it is not unfrozen (or the trainer holds no such block)
+HeadBlockState* stage_of(HeadTrainState* S, int block) {
+    return block >= BK_FIRST && block <= BK_LAST ? S->stage[BK_LAST - block] : nullptr;
+}
+const char* unfreeze_entry(int block) { return block == BK_LAST ? "dfd_head_train_unfreeze_block" : "dfd_head_train_unfreeze_block_at"; }
 }  // namespace
 
 void headblock_destroy(HeadTrainState* S) {
-    destroy_one(&S->block14);
-    destroy_one(&S->block);
+    for (int k = HT_STAGES - 1; k >= 0; --k) destroy_one(&S->stage[k]);
 }
 
-const double* headblock_sumsq(dfd_handle* h, HeadTrainState* S, int block) {
-    HeadBlockState* K = stage_of(S, block);
+const double* headblock_sumsq(dfd_handle* h, HeadTrainState* S, int k) {
+    HeadBlockState* K = S->stage[k];
     head_train_launch_sumsq(h->stream, K->grad, K->L.count, K->partial);
     return K->partial;
 }
 
-const double* headblock_partial(HeadTrainState* S, int block) {
-    HeadBlockState* K = stage_of(S, block);
+const double* headblock_partial(HeadTrainState* S, int k) {
+    HeadBlockState* K = S->stage[k];
     return K ? K->partial : nullptr;
 }
 
 void headblock_adamw(dfd_handle* h, HeadTrainState* S, double lr, double t) {
-    HeadBlockState *K = S->block, *K14 = S->block14;
-    // the arenas' partials in the order of the other launches (head, conv, block 15, block 14): all see the same norm
-    const double* p4 = K14 ? K14->partial : nullptr;
-    head_train_launch_adamw(h->stream, K->param, K->grad, K->m, K->v, K->ema, K->L.count, S->partial, headconv_partial(S), K->partial, p4,
-                            S->cfg, lr * (double)headconv_lr_scale(S), t, S->scalars + 3);
-    if (K14)
-        head_train_launch_adamw(h->stream, K14->param, K14->grad, K14->m, K14->v, K14->ema, K14->L.count, S->partial, headconv_partial(S),
-                                K->partial, p4, S->cfg, lr * (double)headconv_lr_scale(S), t, K14->norm);
+    // the arenas' partials in the order of the other launches (head, conv, block 15, 14, 13, 12): all see the same norm
+    const NormParts parts = head_train_norm_parts(S);
+    for (int k = 0; k < HT_STAGES && S->stage[k]; ++k) {
+        HeadBlockState* K = S->stage[k];
+        head_train_launch_adamw(h->stream, K->param, K->grad, K->m, K->v, K->ema, K->L.count, parts, S->cfg,
+                                lr * (double)headconv_lr_scale(S), t, k == 0 ? S->scalars + 3 : K->norm);
+    }
 }
 
 int headblock_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out, size_t capacity) {
-    const bool b14 = !strncmp(name, "b14.", 4);
-    HeadBlockState* K = b14 ? S->block14 : S->block;
+    const int block = 10 + (name[2] - '0'), k = BK_LAST - block;             // "b15." .. "b12.": the caller checked the prefix
+    const bool skip = block != BK_LAST;
+    HeadBlockState* K = stage_of(S, block);
     if (!K)
-        return fail(h, DFD_ERR_ARG, "head_train_tap: '%s' needs block %d's stage (%s)", name, b14 ? 14 : 15,
-                    b14 ? "dfd_head_train_unfreeze_block_at" : "dfd_head_train_unfreeze_block");
+        return fail(h, DFD_ERR_ARG, "head_train_tap: '%s' needs block %d's stage (%s)", name, block, unfreeze_entry(block));
     const float* src = nullptr;
     size_t per = 0;
     const char* what = name + 4;
     // a block's output lives in the next stage's input buffer
-    if (!strcmp(what, "out")) { src = b14 ? S->block->x : headconv_rows(S); per = (size_t)BK_HW * K->L.out; }
+    if (!strcmp(what, "out")) { src = skip ? S->stage[k - 1]->x : headconv_rows(S); per = (size_t)BK_HW * K->L.out; }
     else if (!strcmp(what, "gate")) { src = K->gate; per = BK_EXP; }
     else if (!strcmp(what, "ad")) { src = K->ad; per = (size_t)BK_HW * BK_EXP; }
     else if (!strcmp(what, "dout")) { src = K->dx; per = (size_t)BK_HW * K->L.out; }
     else if (!strcmp(what, "dae")) { src = K->d2; per = (size_t)BK_HW * BK_EXP; }
-    else if (b14 && !strcmp(what, "keep")) { src = K->keep; per = 1; }
+    else if (skip && !strcmp(what, "keep")) { src = K->keep; per = 1; }
     else return fail(h, DFD_ERR_ARG, "head_train_tap: unknown tap '%s'", name);
     const size_t count = (size_t)S->last_n * per;
     if (capacity < count) return fail(h, DFD_ERR_ARG, "head_train_tap: '%s' holds %zu floats, capacity %zu", name, count, capacity);
@@ -478,12 +488,12 @@ int headblock_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out
 // A trained block's ten tensors of the inference plan, rewritten in place from the trained parameters (live or EMA) and the
 // running statistics: weights._fold's arithmetic (a = g / sqrt(var + eps); w' = w a; b' = 0 a + (beta - mu a), float64,
 // rounded once) and weights.pack_b0_tensors' layouts (dw.w [ky][kx][c] with 9 or 25 taps, se.w2 [48][1152]).  Readers of
-// these pointers, for block 15 and block 14 alike (b0_forward's block loop treats both as "late" 7 x 7 blocks):
+// these pointers, for blocks 15, 14, 13 and 12 alike (b0_forward's block loop treats all four as "late" 7 x 7 blocks):
 // launch_mbconv_front (mbconv_late_kernel for k3, and for k5 the fused front launch mbconv_k5_kernel in its modes 1 and 2:
 // exp.w through its cached split AND the fp32 tensor, exp.b, dw.w, dw.b), the unfused pointwise_t (exp.w / proj.w: the
 // cached split under the split GEMM and, in the bf16-activation instances under "bf16_activations", always; the fp32 tensor
 // in launch_pointwise), launch_depthwise (dw.w, dw.b; fp32 and bf16 instances), launch_se (se.w1, se.b1, se.w2, se.b2) and
-// the projection's bias (proj.b); block 14's projection also adds its input (the skip), which is no weight.  The two cached
+// the projection's bias (proj.b); the projections of blocks 14, 13 and 12 also add their input (the skip), which is no weight.  The two cached
 // splits are rebuilt in place, so plan and tile-table pointers stay valid.
 static int commit_one(dfd_handle* h, HeadBlockState* K, int use_ema) {
     const Layout& L = K->L;
@@ -535,8 +545,8 @@ static int commit_one(dfd_handle* h, HeadBlockState* K, int use_ema) {
 }
 
 int headblock_commit(dfd_handle* h, HeadTrainState* S, int use_ema) {
-    int rc = commit_one(h, S->block, use_ema);
-    if (!rc && S->block14) rc = commit_one(h, S->block14, use_ema);
+    int rc = DFD_OK;
+    for (int k = 0; k < HT_STAGES && S->stage[k] && !rc; ++k) rc = commit_one(h, S->stage[k], use_ema);
     return rc;
 }
 
@@ -562,7 +572,7 @@ const BStat kBlockStats[3] = {{&dfd_mbconv_params::rm0, &dfd_mbconv_params::rv0}
                               {&dfd_mbconv_params::rm2, &dfd_mbconv_params::rv2}};
 
 bool block_complete(const dfd_mbconv_params* p, bool stats) {
-    for (const BField& f : trainable_fields(layout_of<G15>()))
+    for (const BField& f : trainable_fields(layout_of<G15>(BK_LAST)))
         if (!(p->*f.ptr)) return false;
     if (stats)
         for (const BStat& st : kBlockStats)
@@ -574,13 +584,20 @@ HeadTrainState* open_block(dfd_handle* h, const char* who, bool want_stage, int*
     if (!h) { *rc = DFD_ERR_ARG; return nullptr; }
     HeadTrainState* S = h->head_train;
     if (!S) { *rc = fail(h, DFD_ERR_ARG, "%s: no trainer is open on this handle (dfd_head_train_begin)", who); return nullptr; }
-    if (want_stage && !S->block) { *rc = fail(h, DFD_ERR_ARG, "%s: block 15 is not unfrozen (dfd_head_train_unfreeze_block)", who); return nullptr; }
+    if (want_stage && !S->stage[0]) { *rc = fail(h, DFD_ERR_ARG, "%s: block 15 is not unfrozen (dfd_head_train_unfreeze_block)", who); return nullptr; }
     *rc = DFD_OK;
     return S;
 }
 
 BnC bn_consts(const HeadBlockState* K, const float* P, int l, int m, bool backward) {
     return BnC{K->mean[l], K->istd[l], backward ? K->sdy[l] : nullptr, backward ? K->sdx[l] : nullptr, P + K->L.o_g[l], P + K->L.o_be[l], m};
+}
+
+// the place of the deepest unfrozen block in S->stage (block 15 is unfrozen)
+int deepest(const HeadTrainState* S) {
+    int k = 0;
+    while (k + 1 < HT_STAGES && S->stage[k + 1]) ++k;
+    return k;
 }
 
 dim3 flat(size_t total) { return dim3((unsigned)((total + HT_THREADS - 1) / HT_THREADS)); }
@@ -643,7 +660,7 @@ int block_forward(dfd_handle* h, HeadBlockState* K, const float* P, int n, bool 
 }
 
 // from the gradient of the block's output (K->dx) back to the gradients of the block's parameters; dx_below (or null):
-// the gradient with respect to the block's input, dZe . We, for a trained block below
+// the gradient with respect to the block's input for a trained block below: dZe . We, and with the skip K->dx + dZe . We
 template <class GEO>
 int block_backward(dfd_handle* h, HeadBlockState* K, int n, float* dx_below) {
     hipStream_t s = h->stream;
@@ -680,16 +697,21 @@ int block_backward(dfd_handle* h, HeadBlockState* K, int n, float* dx_below) {
     hipLaunchKernelGGL((wgrad_kernel<BK_JE, false, Grad0>), dim3(BK_EXP / 16 * (BK_IN / (16 * BK_JE)) / 4, wch), blk, 0, s, g0, K->x, nullptr,
                        K->wpart, m, BK_EXP, BK_IN, BK_HW);
     hipLaunchKernelGGL(wreduce_kernel, flat((size_t)BK_EXP * BK_IN), blk, 0, s, K->wpart, wch, BK_EXP * BK_IN, G + GEO::O_WE);
-    if (dx_below)                                               // dOut of the block below = dZe . We: 192 columns, reduction over 1152
-        hipLaunchKernelGGL((gemm_dyw_kernel<BK_JE, Grad0>), dim3(BK_IN / (16 * BK_JE), (m + 15) / 16), blk, 0, s, g0, P + GEO::O_WE, dx_below,
-                           m, BK_EXP, BK_IN);
+    if (dx_below) {                                             // dOut of the block below: 192 columns, reduction over 1152
+        const dim3 grid(BK_IN / (16 * BK_JE), (m + 15) / 16);
+        if constexpr (GEO::SKIP)                                // the skip path K->dx (another buffer than dx_below) + the branch
+            hipLaunchKernelGGL((gemm_dyw_kernel<BK_JE, Grad0, true>), grid, blk, 0, s, g0, P + GEO::O_WE, dx_below, m, BK_EXP, BK_IN, K->dx);
+        else
+            hipLaunchKernelGGL((gemm_dyw_kernel<BK_JE, Grad0>), grid, blk, 0, s, g0, P + GEO::O_WE, dx_below, m, BK_EXP, BK_IN, nullptr);
+    }
     DFD_HIP_TRY(h, hipGetLastError());
     return DFD_OK;
 }
 
-// block 14's drop-connect factors of accumulate number `counter`: head_training.drop_connect_keep is the specification
+// a skip block's drop-connect factors of accumulate number `counter`, drawn with layer 17 - its index (block 14: 3):
+// head_training.drop_connect_keep is the specification
 int draw_keep(dfd_handle* h, HeadTrainState* S, HeadBlockState* K, int n) {
-    const uint32_t key = mask_key(S->cfg.seed, S->counter, 3);
+    const uint32_t key = mask_key(S->cfg.seed, S->counter, 17 - K->L.index);
     const float scale = (float)(1.0 / K->keep_prob);
     for (int i = 0; i < n; ++i) K->keep_host[i] = mask_keep(key, (uint32_t)i, K->drop_thr) ? scale : 0.f;
     DFD_HIP_TRY(h, hipMemcpyAsync(K->keep, K->keep_host.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
@@ -790,13 +812,15 @@ int stage_grads(dfd_handle* h, HeadBlockState* K, dfd_mbconv_params* io, int set
     return DFD_OK;
 }
 
-// the stage of `block` (14 or 15) for the _at entries
+// the stage of `block` (12 .. 15) for the _at entries
 HeadBlockState* stage_at(dfd_handle* h, HeadTrainState* S, const char* who, int block, int* rc) {
-    if (block != 14 && block != 15) { *rc = fail(h, DFD_ERR_UNSUPPORTED, "%s: block %d; 14 or 15", who, block); return nullptr; }
+    if (block < BK_FIRST || block > BK_LAST) {
+        *rc = fail(h, DFD_ERR_UNSUPPORTED, "%s: block %d; %d .. %d", who, block, BK_FIRST, BK_LAST);
+        return nullptr;
+    }
     HeadBlockState* K = stage_of(S, block);
-    if (!K)
-        *rc = fail(h, DFD_ERR_ARG, "%s: block %d is not unfrozen (%s)", who, block,
-                   block == 14 ? "dfd_head_train_unfreeze_block_at" : "dfd_head_train_unfreeze_block");
+    if (!K)                                                     // 13 and 12 frozen: not served, as before they could be unfrozen
+        *rc = fail(h, block < 14 ? DFD_ERR_UNSUPPORTED : DFD_ERR_ARG, "%s: block %d is not unfrozen (%s)", who, block, unfreeze_entry(block));
     return K;
 }
 
@@ -808,16 +832,16 @@ int dfd_head_train_unfreeze_block(dfd_handle* h, int block, const dfd_mbconv_par
     int rc;
     HeadTrainState* S = open_block(h, "head_train_unfreeze_block", false, &rc);
     if (!S) return rc;
-    if (block != G15::INDEX_)
-        return fail(h, DFD_ERR_UNSUPPORTED, "head_train_unfreeze_block: block %d; only the last block (%d) can be unfrozen", block, G15::INDEX_);
+    if (block != BK_LAST)
+        return fail(h, DFD_ERR_UNSUPPORTED, "head_train_unfreeze_block: block %d; only the last block (%d) can be unfrozen", block, BK_LAST);
     if (!S->conv) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block: the conv stage comes first (dfd_head_train_unfreeze_conv)");
-    if (S->block) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block: block %d is already unfrozen", G15::INDEX_);
+    if (S->stage[0]) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block: block %d is already unfrozen", BK_LAST);
     if (S->counter) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block: the trainer has accumulated already; unfreeze right after begin");
     if (!init || !block_complete(init, true)) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block: null parameters");
     if (!(bn_momentum >= 0.f && bn_momentum <= 1.f && bn_eps > 0.f))
         return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block: bn_momentum %g or bn_eps %g out of range", (double)bn_momentum, (double)bn_eps);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
-    return create_stage(h, S, "head_train_unfreeze_block", layout_of<G15>(), init, bn_momentum, bn_eps, &S->block);
+    return create_stage(h, S, "head_train_unfreeze_block", layout_of<G15>(BK_LAST), init, bn_momentum, bn_eps, &S->stage[0]);
 }
 
 int dfd_head_train_unfreeze_block_at(dfd_handle* h, int block, const dfd_mbconv_params* init, float bn_momentum, float bn_eps,
@@ -825,11 +849,15 @@ int dfd_head_train_unfreeze_block_at(dfd_handle* h, int block, const dfd_mbconv_
     int rc;
     HeadTrainState* S = open_block(h, "head_train_unfreeze_block_at", false, &rc);
     if (!S) return rc;
-    if (block != G14::INDEX_)
-        return fail(h, DFD_ERR_UNSUPPORTED, "head_train_unfreeze_block_at: block %d; only block %d can be unfrozen below block 15", block,
-                    G14::INDEX_);
-    if (!S->block) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: block 15 comes first (dfd_head_train_unfreeze_block)");
-    if (S->block14) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: block %d is already unfrozen", G14::INDEX_);
+    if (block < BK_FIRST || block >= BK_LAST)
+        return fail(h, DFD_ERR_UNSUPPORTED, "head_train_unfreeze_block_at: block %d; only blocks %d .. %d can be unfrozen below block 15", block,
+                    BK_FIRST, BK_LAST - 1);
+    const int k = BK_LAST - block;
+    if (S->stage[k]) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: block %d is already unfrozen", block);
+    if (!S->stage[k - 1])                                       // the blocks come from the top down: 15, 14, 13, 12
+        return k == 1 ? fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: block 15 comes first (dfd_head_train_unfreeze_block)")
+                      : fail(h, DFD_ERR_UNSUPPORTED, "head_train_unfreeze_block_at: block %d cannot be unfrozen while block %d is frozen", block,
+                             block + 1);
     if (S->counter) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: the trainer has accumulated already; unfreeze right after begin");
     if (!init || !block_complete(init, true)) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: null parameters");
     if (!(bn_momentum >= 0.f && bn_momentum <= 1.f && bn_eps > 0.f))
@@ -837,8 +865,8 @@ int dfd_head_train_unfreeze_block_at(dfd_handle* h, int block, const dfd_mbconv_
     if (!(drop_connect >= 0.f && drop_connect < 1.f))
         return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: drop_connect %g outside [0, 1)", (double)drop_connect);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = create_stage(h, S, "head_train_unfreeze_block_at", layout_of<G14>(), init, bn_momentum, bn_eps, &S->block14))) return rc;
-    HeadBlockState* K = S->block14;
+    if ((rc = create_stage(h, S, "head_train_unfreeze_block_at", layout_of<G14>(block), init, bn_momentum, bn_eps, &S->stage[k]))) return rc;
+    HeadBlockState* K = S->stage[k];
     K->drop_p = (double)drop_connect;                           // the double of the float32 argument, as the head's dropout rates
     K->keep_prob = 1.0 - K->drop_p;
     K->drop_thr = (uint32_t)(unsigned long long)(K->drop_p * 4294967296.0);
@@ -856,18 +884,21 @@ int dfd_head_train_accumulate_block(dfd_handle* h, const float* rows, int n, con
     if (!head_train_mix_ok(lam, loss_scale))
         return fail(h, DFD_ERR_ARG, "head_train_accumulate_block: lam %g outside [0, 1] or loss_scale %g not a number", (double)lam, (double)loss_scale);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
-    HeadBlockState *K = S->block, *K14 = S->block14;
+    HeadBlockState** T = S->stage;
+    HeadBlockState* K = T[0];
     hipStream_t s = h->stream;
-    // the rows are the input of the deepest unfrozen block
-    DFD_HIP_TRY(h, hipMemcpyAsync(K14 ? K14->x : K->x, rows, (size_t)n * BK_ROW * 4, hipMemcpyHostToDevice, s));
-    if (K14) {
-        if ((rc = draw_keep(h, S, K14, n))) return rc;
-        if ((rc = block_forward<G14>(h, K14, K14->param, n, true, K->x, true))) return rc;
+    const int deep = deepest(S);
+    // the rows are the input of the deepest unfrozen block; every skip block writes into the input of the block above it
+    DFD_HIP_TRY(h, hipMemcpyAsync(T[deep]->x, rows, (size_t)n * BK_ROW * 4, hipMemcpyHostToDevice, s));
+    for (int k = deep; k >= 1; --k) {
+        if ((rc = draw_keep(h, S, T[k], n))) return rc;
+        if ((rc = block_forward<G14>(h, T[k], T[k]->param, n, true, T[k - 1]->x, true))) return rc;
     }
     if ((rc = block_forward<G15>(h, K, K->param, n, true, headconv_rows(S), false))) return rc;
     if ((rc = headconv_step(h, S, n, labels_a, labels_b, lam, loss_scale, K->dx))) return rc;
-    if ((rc = block_backward<G15>(h, K, n, K14 ? K14->dx : nullptr))) return rc;
-    if (K14 && (rc = block_backward<G14>(h, K14, n, nullptr))) return rc;       // block 13 is frozen
+    if ((rc = block_backward<G15>(h, K, n, deep >= 1 ? T[1]->dx : nullptr))) return rc;
+    for (int k = 1; k <= deep; ++k)                             // the deepest block hands nothing down: the block below it is frozen
+        if ((rc = block_backward<G14>(h, T[k], n, k < deep ? T[k + 1]->dx : nullptr))) return rc;
     DFD_HIP_TRY(h, hipMemcpyAsync(loss_out, S->scalars, 4, hipMemcpyDeviceToHost, s));
     if (logits_out) DFD_HIP_TRY(h, hipMemcpyAsync(logits_out, S->logits, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     DFD_HIP_TRY(h, stream_sync(h));
@@ -883,9 +914,12 @@ int dfd_head_train_eval_block(dfd_handle* h, const float* rows, int n, int use_e
     if (!rows || !logits_out) return fail(h, DFD_ERR_ARG, "head_train_eval_block: null pointer");
     if (n < 1 || n > S->max_n) return fail(h, DFD_ERR_ARG, "head_train_eval_block: %d rows outside 1..%d", n, S->max_n);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
-    HeadBlockState *K = S->block, *K14 = S->block14;
-    DFD_HIP_TRY(h, hipMemcpyAsync(K14 ? K14->x : K->x, rows, (size_t)n * BK_ROW * 4, hipMemcpyHostToDevice, h->stream));
-    if (K14 && (rc = block_forward<G14>(h, K14, use_ema ? K14->ema : K14->param, n, false, K->x, false))) return rc;   // no drop-connect
+    HeadBlockState** T = S->stage;
+    HeadBlockState* K = T[0];
+    const int deep = deepest(S);
+    DFD_HIP_TRY(h, hipMemcpyAsync(T[deep]->x, rows, (size_t)n * BK_ROW * 4, hipMemcpyHostToDevice, h->stream));
+    for (int k = deep; k >= 1; --k)                             // no drop-connect
+        if ((rc = block_forward<G14>(h, T[k], use_ema ? T[k]->ema : T[k]->param, n, false, T[k - 1]->x, false))) return rc;
     if ((rc = block_forward<G15>(h, K, use_ema ? K->ema : K->param, n, false, headconv_rows(S), false))) return rc;
     if ((rc = headconv_eval_step(h, S, use_ema, n))) return rc;
     DFD_HIP_TRY(h, hipMemcpyAsync(logits_out, S->logits, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
@@ -898,7 +932,7 @@ int dfd_head_train_export_block(dfd_handle* h, int use_ema, dfd_mbconv_params* o
     HeadTrainState* S = open_block(h, "head_train_export_block", true, &rc);
     if (!S) return rc;
     if (!out || !block_complete(out, true)) return fail(h, DFD_ERR_ARG, "head_train_export_block: null pointer");
-    return export_stage(h, S->block, use_ema, out);
+    return export_stage(h, S->stage[0], use_ema, out);
 }
 
 int dfd_head_train_block_grads(dfd_handle* h, dfd_mbconv_params* io, int set) {
@@ -906,7 +940,7 @@ int dfd_head_train_block_grads(dfd_handle* h, dfd_mbconv_params* io, int set) {
     HeadTrainState* S = open_block(h, "head_train_block_grads", true, &rc);
     if (!S) return rc;
     if (!io || !block_complete(io, false)) return fail(h, DFD_ERR_ARG, "head_train_block_grads: null pointer");
-    return stage_grads(h, S->block, io, set);
+    return stage_grads(h, S->stage[0], io, set);
 }
 
 int dfd_head_train_export_block_at(dfd_handle* h, int block, int use_ema, dfd_mbconv_params* out) {

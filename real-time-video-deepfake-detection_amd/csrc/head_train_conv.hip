@@ -296,8 +296,8 @@ const double* headconv_sumsq(dfd_handle* h, HeadTrainState* S) {
 void headconv_adamw(dfd_handle* h, HeadTrainState* S, double lr, double t) {
     HeadConvState* C = S->conv;
     // S->partial comes first in the norm's sum, as in the head's own launch: both launches see the same norm
-    head_train_launch_adamw(h->stream, C->param, C->grad, C->m, C->v, C->ema, CV_COUNT, S->partial, C->partial,
-                            S->block ? headblock_partial(S) : nullptr, headblock_partial(S, 14), S->cfg, lr * (double)C->lr_scale, t, S->scalars + 2);
+    head_train_launch_adamw(h->stream, C->param, C->grad, C->m, C->v, C->ema, CV_COUNT, head_train_norm_parts(S), S->cfg,
+                            lr * (double)C->lr_scale, t, S->scalars + 2);
 }
 
 int headconv_commit(dfd_handle* h, HeadTrainState* S, int use_ema) {
@@ -489,7 +489,7 @@ int dfd_head_train_accumulate_trunk(dfd_handle* h, const float* trunk, int n, co
     int rc;
     HeadTrainState* S = open_conv(h, "head_train_accumulate_trunk", true, &rc);
     if (!S) return rc;
-    if (S->block) return fail(h, DFD_ERR_ARG, "head_train_accumulate_trunk: block 15 is unfrozen, rows are block 14's output (dfd_head_train_accumulate_block)");
+    if (S->stage[0]) return fail(h, DFD_ERR_ARG, "head_train_accumulate_trunk: block 15 is unfrozen, rows are block 14's output (dfd_head_train_accumulate_block)");
     if (!trunk || !labels_a || !loss_out) return fail(h, DFD_ERR_ARG, "head_train_accumulate_trunk: null pointer");
     if (n < 2) return fail(h, DFD_ERR_ARG, "head_train_accumulate_trunk: %d rows; batch statistics need at least 2", n);
     if (n > S->max_n) return fail(h, DFD_ERR_ARG, "head_train_accumulate_trunk: %d rows exceed the trainer's max_n %d", n, S->max_n);
@@ -512,7 +512,7 @@ int dfd_head_train_eval_trunk(dfd_handle* h, const float* trunk, int n, int use_
     int rc;
     HeadTrainState* S = open_conv(h, "head_train_eval_trunk", true, &rc);
     if (!S) return rc;
-    if (S->block) return fail(h, DFD_ERR_ARG, "head_train_eval_trunk: block 15 is unfrozen, rows are block 14's output (dfd_head_train_eval_block)");
+    if (S->stage[0]) return fail(h, DFD_ERR_ARG, "head_train_eval_trunk: block 15 is unfrozen, rows are block 14's output (dfd_head_train_eval_block)");
     if (!trunk || !logits_out) return fail(h, DFD_ERR_ARG, "head_train_eval_trunk: null pointer");
     if (n < 1 || n > S->max_n) return fail(h, DFD_ERR_ARG, "head_train_eval_trunk: %d rows outside 1..%d", n, S->max_n);
     DFD_HIP_TRY(h, hipSetDevice(h->device));

@@ -104,9 +104,11 @@ __global__ __launch_bounds__(HT_THREADS) void gemm_fwd_kernel(const float* __res
 // dX [m][NC] = dZ [m][R] . W [R][NC], dZ formed from the gradient source as it loads.  grid (NC / (16 J), ceil(m / 16)); a
 // workgroup owns 16 rows x 16 J columns and each of its 4 waves a quarter of the R channels, walked 4 at a time; the four
 // partial tiles are added in wave order through LDS (6 J KB) and rounded once.  R % 16 == 0.
-template <int J, class G>
+// ADD: dX = add + dZ . W, the gradient an identity skip hands down (add [m][NC]: the gradient of the block's output, a
+// buffer other than dX); the stored value is the double sum (add + the four partial tiles), rounded once.
+template <int J, class G, bool ADD = false>
 __global__ __launch_bounds__(HT_THREADS) void gemm_dyw_kernel(G g, const float* __restrict__ W, float* __restrict__ dX, int m,
-                                                              int R, int NC) {
+                                                              int R, int NC, const float* __restrict__ add = nullptr) {
     __shared__ double red[3][J][4][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r16 = lane & 15, q = lane >> 4;
     const int row0 = blockIdx.y * 16, col0 = blockIdx.x * (16 * J);
@@ -140,8 +142,12 @@ __global__ __launch_bounds__(HT_THREADS) void gemm_dyw_kernel(G g, const float* 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int r = row0 + q + 4 * e;
-            const double s = ((acc[j][e] + red[0][j][e][lane]) + red[1][j][e][lane]) + red[2][j][e][lane];
-            if (r < m) dX[(size_t)r * NC + col0 + j * 16 + r16] = (float)s;
+            double s = ((acc[j][e] + red[0][j][e][lane]) + red[1][j][e][lane]) + red[2][j][e][lane];
+            if (r < m) {
+                const size_t o = (size_t)r * NC + col0 + j * 16 + r16;
+                if constexpr (ADD) s = (double)add[o] + s;
+                dX[o] = (float)s;
+            }
         }
     }
 }

@@ -2,7 +2,7 @@
 // the host entry points each file offers the other.  The conv stage (dfd_head_train_unfreeze_conv) hangs off the head
 // trainer's state; everything from the pooled features on runs in head_train.hip's kernels.  Block 15
 // (dfd_head_train_unfreeze_block, head_train_block.hip) hangs off it in turn and feeds the conv stage on the device;
-// block 14 (dfd_head_train_unfreeze_block_at, the same file) feeds block 15.
+// blocks 14, 13 and 12 (dfd_head_train_unfreeze_block_at, the same file) each feed the block above them.
 #pragma once
 #include <cstdint>
 
@@ -17,10 +17,15 @@ constexpr int O_W2 = O_BE1 + HT_H1, O_B2 = O_W2 + HT_H2 * HT_H1, O_G2 = O_B2 + H
 constexpr int O_W3 = O_BE2 + HT_H2, O_B3 = O_W3 + HT_H2, HT_COUNT = O_B3 + 1;
 static_assert(O_W2 % 4 == 0 && O_W3 % 4 == 0, "weight rows must stay 16-byte aligned");
 constexpr int NORM_BLOCKS = 256;
+constexpr int HT_STAGES = 4;              // block stages a trainer can hold: _blocks.15 down to _blocks.12
+constexpr int HT_ARENAS = 2 + HT_STAGES;  // head, conv, then the block stages
 
 struct HeadConvState;   // head_train_conv.hip: _conv_head + _bn1 under training (null until dfd_head_train_unfreeze_conv)
-struct HeadBlockState;  // head_train_block.hip: one MBConv block under training: `block` = _blocks.15 (null until
-                        // dfd_head_train_unfreeze_block), `block14` = _blocks.14 (null until dfd_head_train_unfreeze_block_at)
+struct HeadBlockState;  // head_train_block.hip: one MBConv block under training
+
+// The partial sums of squares of every arena, in the order head, conv, block 15, 14, 13, 12 (null: no such stage).  Each
+// AdamW launch adds them entry by entry in this order before it takes the norm, so all see the same norm.
+struct NormParts { const double* p[HT_ARENAS]; };
 
 struct HeadTrainState {
     dfd_head_config cfg{};
@@ -38,12 +43,13 @@ struct HeadTrainState {
     uint8_t *mask0 = nullptr, *mask1 = nullptr, *mask2 = nullptr;
     void* pool = nullptr;
     HeadConvState* conv = nullptr;
-    HeadBlockState* block = nullptr;
-    HeadBlockState* block14 = nullptr;
+    // stage[k] = _blocks.(15 - k), deepest last: stage[0] null until dfd_head_train_unfreeze_block, the others until
+    // dfd_head_train_unfreeze_block_at; stage[k] is only ever set when stage[k - 1] is
+    HeadBlockState* stage[HT_STAGES] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 // The trainer's counter-based hash: head_training.dropout_keep_mask is the specification of these three.  layer 0..2 are
-// the head's dropouts, layer 3 block 14's drop-connect (one draw per crop).
+// the head's dropouts, layer 17 - b block b's drop-connect (one draw per crop): 3 for block 14, 4 for 13, 5 for 12.
 __host__ __device__ inline uint32_t fmix32(uint32_t x) {
     x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
     return x;
@@ -71,11 +77,11 @@ int head_train_step(dfd_handle* h, HeadTrainState* S, int n, const float* labels
 // eval-mode forward of the n rows in S->feat with the parameters at P -> S->logits
 int head_train_eval_step(dfd_handle* h, HeadTrainState* S, const float* P, int n);
 void head_train_launch_sumsq(hipStream_t s, const float* g, int count, double* partial);
-// clip + AdamW + EMA + zeroing over one arena at the rate `lr`; partial2 / partial3 / partial4 (or null): a second, a
-// third and a fourth arena's partial sums of squares, added to `partial` entry by entry, in this order, before the norm
-// is taken.  t = 1-based step number.
-void head_train_launch_adamw(hipStream_t s, float* p, float* g, float* m, float* v, float* ema, int count,
-                             const double* partial, const double* partial2, const double* partial3, const double* partial4,
+// every arena's partials of the last sumsq launches (head_train_apply), for the AdamW launches
+NormParts head_train_norm_parts(HeadTrainState* S);
+// clip + AdamW + EMA + zeroing over one arena at the rate `lr`, under the norm over all arenas of `parts`.
+// t = 1-based step number.
+void head_train_launch_adamw(hipStream_t s, float* p, float* g, float* m, float* v, float* ema, int count, const NormParts& parts,
                              const dfd_head_config& c, double lr, double t, float* norm_out);
 
 // ---- head_train_conv.hip, for the head trainer
@@ -95,12 +101,12 @@ int headconv_step(dfd_handle* h, HeadTrainState* S, int n, const float* labels_a
 int headconv_eval_step(dfd_handle* h, HeadTrainState* S, int use_ema, int n);    // -> S->logits
 
 // ---- head_train_block.hip, for the head trainer
-// `block` = 15 or 14 throughout; a stage that is not unfrozen has no partials (null) and nothing to step
-void headblock_destroy(HeadTrainState* S);                                   // both stages
-const double* headblock_sumsq(dfd_handle* h, HeadTrainState* S, int block = 15);   // launches; -> the block arena's partials
-const double* headblock_partial(HeadTrainState* S, int block = 15);
+// `k` = the stage's place in HeadTrainState::stage; a stage that is not unfrozen has no partials (null) and nothing to step
+void headblock_destroy(HeadTrainState* S);                                   // every stage
+const double* headblock_sumsq(dfd_handle* h, HeadTrainState* S, int k);      // launches; -> the stage arena's partials
+const double* headblock_partial(HeadTrainState* S, int k);
 void headblock_adamw(dfd_handle* h, HeadTrainState* S, double lr, double t);  // the block groups' steps at lr * the conv stage's lr_scale
-int headblock_commit(dfd_handle* h, HeadTrainState* S, int use_ema);          // block 15, then block 14 where it is unfrozen
-int headblock_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out, size_t capacity);  // "b15.*", "b14.*"
+int headblock_commit(dfd_handle* h, HeadTrainState* S, int use_ema);          // block 15, then 14, 13, 12 where they are unfrozen
+int headblock_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out, size_t capacity);  // "b15.*" .. "b12.*"
 
 }  // namespace dfd

@@ -737,7 +737,8 @@ int dfd_train_augment_tap(dfd_handle* h, const unsigned char* rgb_host, int n, i
 }
 
 // the chain at 224 on all n images, then the backbone in chunks of max_batch: pooled rows, or (trunk) block 15's output, or
-// (trunk, block = 14) block 14's, or (first_block = 13: dfd_train_augment_block_out) block 13's
+// (trunk, block = 14) block 14's, or (first_block = 13: dfd_train_augment_block_out) block 13's, or (first_block = 11:
+// dfd_train_augment_block_input, which checks its own range) block 11's or 12's
 static int augment_forward(dfd_handle* h, const char* who, const unsigned char* rgb, int on_device, int n, int H, int W,
                            const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, float* out_host, bool trunk,
                            int block = 15, int first_block = 14) {
@@ -791,6 +792,14 @@ int dfd_train_augment_trunk_at(dfd_handle* h, const unsigned char* rgb, int on_d
 int dfd_train_augment_block_out(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
                                 const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, int block, float* out_host) {
     return augment_forward(h, "train_augment_block_out", rgb, on_device, n, H, W, rows, batch, out_host, true, block, 13);
+}
+
+int dfd_train_augment_block_input(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
+                                  const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, int block, float* out_host) {
+    if (!h) return DFD_ERR_ARG;
+    if (block < 12 || block > 15) return fail(h, DFD_ERR_ARG, "train_augment_block_input: block %d; 12, 13, 14 or 15", block);
+    // a block's input is the output of the block below it: [7][7][192] for all four
+    return augment_forward(h, "train_augment_block_input", rgb, on_device, n, H, W, rows, batch, out_host, true, block - 1, 11);
 }
 
 }  // extern "C"

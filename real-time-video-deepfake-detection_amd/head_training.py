@@ -12,8 +12,10 @@ rows (trunk rows with the conv stage) unless `augment=` is given (then the crops
 images, train_augment.py); a last batch of one row is dropped (BatchNorm1d needs two).  `HeadTrainer(train_block15=True)`
 adds the backbone's last block, ``net._blocks.15`` (csrc/head_train_block.hip): the rows are then block 14's output,
 (n, 7, 7, 192), and the block's tensors join the conv's group.  `HeadTrainer(train_block14=True)` adds ``net._blocks.14``
-below it (the identity skip with per-crop drop-connect): the rows are then block 13's output, the same shape; blocks 13
-down to 9 of train.py's recipe stay frozen.
+below it (the identity skip with per-crop drop-connect): the rows are then block 13's output, the same shape.
+`train_block13=True` and `train_block12=True` add ``net._blocks.13`` and ``net._blocks.12`` (block 14's geometry, each with
+its own drop-connect rate and mask): the rows are the input rows of the deepest unfrozen block.  After them every 7 x 7
+block of train.py's unfrozen group trains; its 14 x 14 blocks 11 down to 9 stay frozen.
 """
 from __future__ import annotations
 
@@ -60,6 +62,19 @@ BLOCK14_TRACKED = tuple(k for k, f in BLOCK14_KEYS.items() if f.startswith("nbt"
 BLOCK14_SD_SHAPES = {"exp_w": (1152, 192, 1, 1), "dw_w": (1152, 1, 5, 5), "se_w1": (48, 1152, 1, 1), "se_w2": (1152, 48, 1, 1),
                      "proj_w": (192, 1152, 1, 1)}
 DROP_CONNECT_BLOCK14 = 0.2 * 14 / 16     # efficientnet-b0's drop_connect_rate times idx / len(blocks)
+# blocks 13 and 12 (train_block13=True, train_block12=True): block 14's shapes under their own names
+BLOCK13_PREFIX, BLOCK12_PREFIX = "net._blocks.13.", "net._blocks.12."
+BLOCK13_KEYS = {BLOCK13_PREFIX + k[len(BLOCK_PREFIX):]: f for k, f in BLOCK_KEYS.items()}
+BLOCK12_KEYS = {BLOCK12_PREFIX + k[len(BLOCK_PREFIX):]: f for k, f in BLOCK_KEYS.items()}
+BLOCK13_TRACKED = tuple(k for k, f in BLOCK13_KEYS.items() if f.startswith("nbt"))
+BLOCK12_TRACKED = tuple(k for k, f in BLOCK12_KEYS.items() if f.startswith("nbt"))
+BLOCK13_SD_SHAPES = dict(BLOCK14_SD_SHAPES)
+BLOCK12_SD_SHAPES = dict(BLOCK14_SD_SHAPES)
+DROP_CONNECT_BLOCK13 = 0.2 * 13 / 16
+DROP_CONNECT_BLOCK12 = 0.2 * 12 / 16
+# the skip blocks a trainer can hold, top down: (block, keys, tracked keys, state-dict shapes)
+_SKIP_BLOCKS = ((14, BLOCK14_KEYS, BLOCK14_TRACKED, BLOCK14_SD_SHAPES), (13, BLOCK13_KEYS, BLOCK13_TRACKED, BLOCK13_SD_SHAPES),
+                (12, BLOCK12_KEYS, BLOCK12_TRACKED, BLOCK12_SD_SHAPES))
 BN_MOMENTUM_BACKBONE = 0.01              # efficientnet_pytorch: 1 - batch_norm_momentum (0.99)
 BN_EPS_BACKBONE = 1e-3                   # efficientnet_pytorch's batch_norm_epsilon, the eps weights.pack_b0 folds with
 LAYER_WIDTHS = (1280, 512, 256)          # what dropout layer 0 / 1 / 2 acts on
@@ -124,11 +139,14 @@ def dropout_keep_mask(seed: int, counter: int, layer: int, n: int, width: int, p
     return (u >= np.uint32(int(p * 4294967296.0))).reshape(n, width)
 
 
-def drop_connect_keep(seed: int, counter: int, n: int, p: float) -> np.ndarray:
-    """The specification of block 14's drop-connect: bool (n,), True = the crop's branch is kept (and scaled by
-    1 / (1 - p)).  The trainer's hash with a fourth layer index and one draw per crop; `p` is the double of the float32
-    setting, the rule `dropout_rates` uses; `counter` = accumulate calls since the trainer was opened."""
-    return dropout_keep_mask(seed, counter, 3, n, 1, float(np.float32(p))).reshape(n)
+def drop_connect_keep(seed: int, counter: int, n: int, p: float, block: int = 14) -> np.ndarray:
+    """The specification of block `block`'s drop-connect (14, 13 or 12): bool (n,), True = the crop's branch is kept (and
+    scaled by 1 / (1 - p)).  The trainer's hash with layer index 17 - block (3 for block 14, 4 for 13, 5 for 12: the blocks
+    drop independently) and one draw per crop; `p` is the double of the float32 setting, the rule `dropout_rates` uses;
+    `counter` = accumulate calls since the trainer was opened."""
+    if block not in (12, 13, 14):
+        raise ValueError("block outside 12..14")
+    return dropout_keep_mask(seed, counter, 17 - int(block), n, 1, float(np.float32(p))).reshape(n)
 
 
 # --------------------------------------------------------------------------- loss and metrics on the host
@@ -182,7 +200,8 @@ def fit_loop(trainer, features, labels, epochs: int, batch_size: int = 32, grad_
     `max_n` and `loss_settings` (HeadTrainer; the tests' float64 oracle).  A trainer may carry `row_width` (floats of one
     row; default 1280) and `extract_method` (the extractor call `augment=` uses; default "train_augment_features"): a
     trainer with the conv stage takes trunk rows of 15680 floats from "train_augment_trunk", one with block 15 rows of 9408
-    floats from "train_augment_block14" (with block 14: "train_augment_block13"), and feature-space Mixup then acts on those rows.  Returns a log shaped like
+    floats from "train_augment_block14" (with block 14: "train_augment_block13"; with block 13 or 12: "train_augment_input13" /
+    "train_augment_input12", `Handle.train_augment_block_input` at the deepest block), and feature-space Mixup then acts on those rows.  Returns a log shaped like
     weights/training_log.json: one dict per epoch (epoch, train_loss, train_acc, val_loss, val_acc, val_f1, val_auc,
     lr, time_seconds).
 
@@ -330,6 +349,12 @@ class HeadTrainer:
     per-crop drop-connect at rate `drop_connect`: the rows are then block 13's output - `Handle.extract_block(x, 13)`'s
     (n, 7, 7, 192) or (n, 9408) - and `commit` / `export_state_dict` cover all four groups.
 
+    `train_block13=True` (implies `train_block14`) and `train_block12=True` (implies `train_block13`) also train
+    ``net._blocks.13`` / ``net._blocks.12`` with their own drop-connect rates `drop_connect13` / `drop_connect12` (`drop_connect`
+    keeps meaning block 14) and their own masks (`drop_connect_keep(block=...)`): the rows are then the input rows of the
+    deepest unfrozen block - `Handle.extract_block_input(x, 13 or 12)`'s (n, 7, 7, 192) or (n, 9408) - and `commit` /
+    `export_state_dict` cover all five or six groups.
+
     `model_or_handle`: a `DeepfakeEfficientNet` (its handle and state dict are used) or a `_lib.Handle` with
     `state_dict` (reference key names, at least the ten ``net._fc.*`` tensors and the four running statistics).
     `config`: fields of `dfd_head_config` - max_n, seed, dropout, beta1, beta2, eps, weight_decay, focal_gamma,
@@ -341,7 +366,8 @@ class HeadTrainer:
 
     def __init__(self, model_or_handle, state_dict: Optional[Mapping[str, np.ndarray]] = None, train_conv_head: bool = False,
                  backbone_lr_scale: float = 0.1, train_block15: bool = False, train_block14: bool = False,
-                 drop_connect: float = DROP_CONNECT_BLOCK14, **config):
+                 drop_connect: float = DROP_CONNECT_BLOCK14, train_block13: bool = False, train_block12: bool = False,
+                 drop_connect13: float = DROP_CONNECT_BLOCK13, drop_connect12: float = DROP_CONNECT_BLOCK12, **config):
         if isinstance(model_or_handle, _lib.Handle):
             handle = model_or_handle
             if state_dict is None:
@@ -354,20 +380,30 @@ class HeadTrainer:
         params = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
                   for k, f in KEYS.items()}
         self._tracked = [int(np.asarray(sd[k])) if k in sd else 0 for k in TRACKED]
-        self.train_block14 = bool(train_block14)
+        self.train_block12 = bool(train_block12)
+        self.train_block13 = bool(train_block13) or self.train_block12
+        self.train_block14 = bool(train_block14) or self.train_block13
         self.train_block15 = bool(train_block15) or self.train_block14
         self.train_conv_head = bool(train_conv_head) or self.train_block15
         self.row_width = _lib.BLOCK14_ROW if self.train_block15 else _lib.TRUNK_ROW if self.train_conv_head else 1280
-        self.extract_method = ("train_augment_block13" if self.train_block14 else "train_augment_block14" if self.train_block15 else
+        self.extract_method = ("train_augment_input12" if self.train_block12 else "train_augment_input13" if self.train_block13 else
+                               "train_augment_block13" if self.train_block14 else "train_augment_block14" if self.train_block15 else
                                "train_augment_trunk" if self.train_conv_head else "train_augment_features")
         if self.train_block15:
             block = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
                      for k, f in BLOCK_KEYS.items() if not f.startswith("nbt")}
             self._block_tracked = [int(np.asarray(sd[k])) if k in sd else 0 for k in BLOCK_TRACKED]
+        # the unfrozen skip blocks, top down: (block, keys, tracked keys, state-dict shapes, drop-connect rate)
+        rates = {14: drop_connect, 13: drop_connect13, 12: drop_connect12}
+        on = {14: self.train_block14, 13: self.train_block13, 12: self.train_block12}
+        self._skip_blocks = [sb + (rates[sb[0]],) for sb in _SKIP_BLOCKS if on[sb[0]]]
+        skip_params, self._skip_tracked = {}, {}
+        for b, keys, tracked, _shapes, _rate in self._skip_blocks:
+            skip_params[b] = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
+                              for k, f in keys.items() if not f.startswith("nbt")}
+            self._skip_tracked[b] = [int(np.asarray(sd[k])) if k in sd else 0 for k in tracked]
         if self.train_block14:
-            block14 = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
-                       for k, f in BLOCK14_KEYS.items() if not f.startswith("nbt")}
-            self._block14_tracked = [int(np.asarray(sd[k])) if k in sd else 0 for k in BLOCK14_TRACKED]
+            self._block14_tracked = self._skip_tracked[14]
         if self.train_conv_head:
             conv = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
                     for k, f in CONV_KEYS.items()}
@@ -391,9 +427,9 @@ class HeadTrainer:
             except Exception:
                 self.close()
                 raise
-        if self.train_block14:
+        for b, _keys, _tracked, _shapes, rate in self._skip_blocks:
             try:
-                handle.head_train_unfreeze_block_at(block14, 14, BN_MOMENTUM_BACKBONE, BN_EPS_BACKBONE, drop_connect)
+                handle.head_train_unfreeze_block_at(skip_params[b], b, BN_MOMENTUM_BACKBONE, BN_EPS_BACKBONE, rate)
             except Exception:
                 self.close()
                 raise
@@ -439,7 +475,8 @@ class HeadTrainer:
         """the head under the reference's names: ten ``net._fc.*`` parameters, four running statistics (always the live
         ones) and the two ``num_batches_tracked`` counters; with the conv stage also ``net._conv_head.weight``
         ((1280, 320, 1, 1)), ``net._bn1.*`` and its counter; with block 15 also the 22 ``net._blocks.15.*`` entries of
-        `BLOCK_KEYS` (conv kernels in the state dict's 4-d shapes); with block 14 also the 22 of `BLOCK14_KEYS`"""
+        `BLOCK_KEYS` (conv kernels in the state dict's 4-d shapes); with block 14 also the 22 of `BLOCK14_KEYS`, with block 13
+        those of `BLOCK13_KEYS`, with block 12 those of `BLOCK12_KEYS`"""
         out = self._h.head_train_export(use_ema)
         sd = {k: out[f] for k, f in KEYS.items()}
         for k, t in zip(TRACKED, self._tracked):
@@ -453,15 +490,15 @@ class HeadTrainer:
             sd.update({k: blk[f].reshape(BLOCK_SD_SHAPES.get(f, blk[f].shape)) for k, f in BLOCK_KEYS.items() if f in blk})
             for k, t in zip(BLOCK_TRACKED, self._block_tracked):
                 sd[k] = np.array(t + self.accumulates, dtype=np.int64)
-        if self.train_block14:
-            blk = self._h.head_train_export_block_at(14, use_ema)
-            sd.update({k: blk[f].reshape(BLOCK14_SD_SHAPES.get(f, blk[f].shape)) for k, f in BLOCK14_KEYS.items() if f in blk})
-            for k, t in zip(BLOCK14_TRACKED, self._block14_tracked):
+        for b, keys, tracked, shapes, _rate in self._skip_blocks:
+            blk = self._h.head_train_export_block_at(b, use_ema)
+            sd.update({k: blk[f].reshape(shapes.get(f, blk[f].shape)) for k, f in keys.items() if f in blk})
+            for k, t in zip(tracked, self._skip_tracked[b]):
                 sd[k] = np.array(t + self.accumulates, dtype=np.int64)
         return sd
 
     def commit(self, use_ema: bool = True):
-        """fold BatchNorm and swap the head (and, with the conv stage, the head conv; with block 15 and block 14, their ten tensors each) the
+        """fold BatchNorm and swap the head (and, with the conv stage, the head conv; with blocks 15 down to 12, their ten tensors each) the
         handle classifies with (`dfd_head_train_commit`)"""
         self._h.head_train_commit(use_ema)
 
@@ -473,4 +510,4 @@ class HeadTrainer:
 
 
 __all__ = ["HeadTrainer", "fit_loop", "one_cycle_lr", "dropout_keep_mask", "dropout_rates", "focal_loss", "KEYS", "CONV_KEYS", "BLOCK_KEYS", "BLOCK14_KEYS",
-           "drop_connect_keep"]
+           "BLOCK13_KEYS", "BLOCK12_KEYS", "drop_connect_keep"]

@@ -159,13 +159,20 @@ class DeepfakeEfficientNet:
         the rows `fit_head(train_block14=True)` trains on - and 14, (B,7,7,320) for 15"""
         return self._run(rgb_input, lambda a: self.handle.extract_block(a, block))
 
+    def extract_block_input(self, rgb_input, block: int):
+        """(B,7,7,192) the input rows of block 12, 13, 14 or 15, NHWC, `max_batch` crops at a time
+        (`Handle.extract_block_input`): the rows `fit_head(train_block13=True)` (block 13) / `train_block12=True` (block 12)
+        trains on"""
+        return self._run(rgb_input, lambda a: self.handle.extract_block_input(a, block))
+
     def forward_with_projection(self, rgb_input, freq_input=None):
         """reference model.py:91-98"""
         return self.forward(rgb_input), None
 
     def fit_head(self, images_or_features, labels, *, epochs: int = 20, val=None, commit_ema: bool = True,
                  trainer_config: Optional[Mapping] = None, augment=None, train_conv_head: bool = False,
-                 train_block15: bool = False, train_block14: bool = False, **fit_kw):
+                 train_block15: bool = False, train_block14: bool = False, train_block13: bool = False,
+                 train_block12: bool = False, **fit_kw):
         """Train the 1280 -> 512 -> 256 -> 1 head on this engine's own pooled features and swap it in.
 
         `images_or_features`: (N,3,224,224) normalised RGB (features are extracted here, `max_batch` crops at a time) or
@@ -188,16 +195,25 @@ class DeepfakeEfficientNet:
 
         `train_block14=True` (implies `train_block15`): ``net._blocks.14`` is fine-tuned as well, with the reference's
         drop-connect rate: images go through `extract_block(block=13)`, other arrays are rows of block 13's output
-        ((N,7,7,192) or (N,9408))."""
+        ((N,7,7,192) or (N,9408)).
+
+        `train_block13=True` (implies `train_block14`) / `train_block12=True` (implies `train_block13`): ``net._blocks.13`` /
+        ``net._blocks.12`` are fine-tuned as well, each with the reference's drop-connect rate and its own mask: images go
+        through `extract_block_input` at the deepest block, other arrays are its input rows ((N,7,7,192) or (N,9408))."""
         from .head_training import HeadTrainer
 
+        train_block13 = train_block13 or train_block12
+        train_block14 = train_block14 or train_block13
         train_block15 = train_block15 or train_block14
 
         def feats(x):
             a = x.detach().cpu().numpy() if _is_torch(x) else np.asarray(x)
             if train_conv_head or train_block15:
                 if a.ndim == 4 and a.shape[1:] == (3, A.IMAGE_SIZE, A.IMAGE_SIZE):
-                    a = self.extract_block(a, 13) if train_block14 else self.extract_trunk(a, block=14 if train_block15 else 15)
+                    if train_block13:
+                        a = self.extract_block_input(a, 12 if train_block12 else 13)
+                    else:
+                        a = self.extract_block(a, 13) if train_block14 else self.extract_trunk(a, block=14 if train_block15 else 15)
                 return np.ascontiguousarray(a, np.float32).reshape(a.shape[0], -1)
             return np.ascontiguousarray(a, np.float32) if a.ndim == 2 else np.asarray(self.extract_features(a), np.float32)
 
@@ -215,7 +231,8 @@ class DeepfakeEfficientNet:
             x = feats(images_or_features)
             v = None if val is None else (feats(val[0]), np.asarray(val[1], np.float32))
         y = labels.detach().cpu().numpy() if _is_torch(labels) else np.asarray(labels)
-        with HeadTrainer(self, train_conv_head=train_conv_head, train_block15=train_block15, train_block14=train_block14, **cfg) as tr:
+        with HeadTrainer(self, train_conv_head=train_conv_head, train_block15=train_block15, train_block14=train_block14,
+                         train_block13=train_block13, train_block12=train_block12, **cfg) as tr:
             log_ = tr.fit(x, y, epochs, val=v, **fit_kw)
             tr.commit(use_ema=commit_ema)
             self._state.update(tr.export_state_dict(use_ema=commit_ema))
