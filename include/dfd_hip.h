@@ -1079,6 +1079,34 @@ int dfd_extract_block_input(dfd_handle* h, const float* nchw_host, int n, int bl
 int dfd_train_augment_block_input(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
                                   const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, int block, float* out_host);
 
+/* ---- fine-tuning block 11, the stride-2 block below block 12 ------------------------------------
+ * net._blocks.11 is the MBConv that takes the 14 x 14 maps to 7 x 7: expand 112 -> 672, depthwise 5 x 5 at stride 2 with
+ * TF-"SAME" padding 1 before and 2 after on both axes (output (oy, ox) reads input (2 oy - 1 + ky, 2 ox - 1 + kx)),
+ * squeeze-excite 28, projection 672 -> 192, no skip and therefore no drop-connect; 262 492 trainable floats.  In
+ * dfd_mbconv_params: exp_w [672][112], dw_w [672][5][5], se_w1 [28][672], se_b1 [28], se_w2 [672][28], se_b2 [672],
+ * proj_w [192][672], BatchNorms of 672, 672 and 192 channels.  Blocks 10 and 9 stay frozen.
+ *
+ * dfd_head_train_unfreeze_block_at also takes block 11, once 12 is unfrozen and before the first accumulate, with
+ * drop_connect 0 (anything else: DFD_ERR_ARG).  11 while 12 is frozen: DFD_ERR_UNSUPPORTED; 11 again, or after an
+ * accumulate: DFD_ERR_ARG; blocks outside 11..14: DFD_ERR_UNSUPPORTED.  dfd_head_train_export_block_at / _block_grads_at
+ * serve 11 once it is unfrozen (frozen: DFD_ERR_UNSUPPORTED).  The stage is ONE hipMalloc at max_n.  The rows of
+ * dfd_head_train_accumulate_block / _eval_block are then block 10's output, float32 NHWC [n][14][14][112]:
+ * DFD_BLOCK11_INPUT_ROW floats a crop.  BatchNorm 0 takes its statistics over 196 n rows, BatchNorms 1 and 2 and the
+ * squeeze-excite pool over 49 n.  Block 11 writes BN2(Zp) into block 12's input; block 12 hands down
+ * dX12 = dOut12 + dZe12 . We12 as every trained skip block does, and block 11 forms no input gradient.
+ * dfd_head_train_apply takes ONE norm over up to seven arenas (head, conv, 15, 14, 13, 12, 11); EMA, zeroing and
+ * dfd_head_train_commit (15 .. 11 in that order) cover the stage.  dfd_head_train_tap knows "b11.out" [n][49][192] (block
+ * 12's input), "b11.gate" [n][672], "b11.ad" [n][49][672], "b11.dout" [n][49][192] and "b11.dae" [n][196][672]; there is no
+ * "b11.keep" (DFD_ERR_ARG), and every "b11.*" tap without the stage is DFD_ERR_ARG.
+ *
+ * dfd_extract_block_rows / dfd_train_augment_block_rows: dfd_extract_block_input / dfd_train_augment_block_input (their
+ * bits for `block` in 12..15) with block 11 as well, whose rows are [n][14][14][112], the "b10.out" tap of the same
+ * forward (fp32 and bf16-activation mode).  Any other block: DFD_ERR_ARG.  The two older entries keep refusing 11. */
+#define DFD_BLOCK11_INPUT_ROW 21952   /* 14 * 14 * 112 floats of one crop */
+int dfd_extract_block_rows(dfd_handle* h, const float* nchw_host, int n, int block, float* out_host);
+int dfd_train_augment_block_rows(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
+                                 const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, int block, float* out_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,9 @@ SIGNATURES = {
     "dfd_train_augment_block_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_int, C.c_void_p]),
     "dfd_extract_block_input": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dfd_extract_block_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dfd_train_augment_block_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_int, C.c_void_p]),
     "dfd_train_augment_block_input": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_int, C.c_void_p]),
     "dfd_train_augment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -310,7 +313,14 @@ BLOCK_SHAPES = {"exp_w": (1152, 192), "dw_w": (1152, 3, 3), "se_w1": (48, 1152),
 BLOCK_SHAPES.update({k + str(l): ((1152,) if l < 2 else (320,)) for l in range(3) for k in ("g", "be", "rm", "rv")})
 # block 14 in the same struct (k5, 192 -> 1152 -> 192); blocks 13 and 12 have these shapes too
 BLOCK14_SHAPES = dict(BLOCK_SHAPES, dw_w=(1152, 5, 5), proj_w=(192, 1152), g2=(192,), be2=(192,), rm2=(192,), rv2=(192,))
-BLOCK_SHAPES_AT = {15: BLOCK_SHAPES, 14: BLOCK14_SHAPES, 13: BLOCK14_SHAPES, 12: BLOCK14_SHAPES}
+# block 11 in the same struct (k5 at stride 2, 112 -> 672 -> 192, squeeze-excite 28)
+BLOCK11_SHAPES = {"exp_w": (672, 112), "dw_w": (672, 5, 5), "se_w1": (28, 672), "se_b1": (28,), "se_w2": (672, 28), "se_b2": (672,),
+                  "proj_w": (192, 672)}
+BLOCK11_SHAPES.update({k + str(l): ((672,) if l < 2 else (192,)) for l in range(3) for k in ("g", "be", "rm", "rv")})
+BLOCK_SHAPES_AT = {15: BLOCK_SHAPES, 14: BLOCK14_SHAPES, 13: BLOCK14_SHAPES, 12: BLOCK14_SHAPES, 11: BLOCK11_SHAPES}
+BLOCK11_INPUT_SHAPE = (14, 14, 112)   # block 10's output of one crop, NHWC (DFD_BLOCK11_INPUT_ROW floats): the rows block 11's stage trains on
+BLOCK11_INPUT_ROW = 14 * 14 * 112
+BLOCK_ROWS_SHAPES = {11: BLOCK11_INPUT_SHAPE, 12: BLOCK14_SHAPE, 13: BLOCK14_SHAPE, 14: BLOCK14_SHAPE, 15: BLOCK14_SHAPE}
 BLOCK_OUT_SHAPES = {13: BLOCK14_SHAPE, 14: BLOCK14_SHAPE, 15: TRUNK_SHAPE}     # what `Handle.extract_block` returns per crop
 
 
@@ -633,6 +643,15 @@ class Handle:
         self._check(self._lib.dfd_extract_block_input(self._p, _ptr(a), a.shape[0], int(block), _ptr(out)))
         return out
 
+    def extract_block_rows(self, x, block: int) -> np.ndarray:
+        """`extract_block_input` with block 11 as well (`dfd_extract_block_rows`): (n,7,7,192) for 12..15 - the older entry's
+        bits - and (n,14,14,112), block 10's output, for 11: the rows a trainer whose deepest unfrozen block is `block` trains
+        on; any other block is refused"""
+        a = self._as_nchw(x)
+        out = np.empty((a.shape[0],) + BLOCK_ROWS_SHAPES.get(int(block), BLOCK14_SHAPE), dtype=np.float32)
+        self._check(self._lib.dfd_extract_block_rows(self._p, _ptr(a), a.shape[0], int(block), _ptr(out)))
+        return out
+
     # -- train-time augmentation (include/dfd_hip.h "train-time image augmentation"; train_augment.draw_batch makes the tables)
     @staticmethod
     def _aug_tables(n, rows, batch):
@@ -749,6 +768,18 @@ class Handle:
 
         return self._train_augment_forward(fn, BLOCK14_SHAPE, rgb, rows, batch, shape)
 
+    def train_augment_block_rows(self, rgb, rows, batch, block: int = 11, shape=None) -> np.ndarray:
+        """`train_augment_block_input` with block 11 as well -> (n,14,14,112) for 11, (n,7,7,192) for 12..15
+        (`dfd_train_augment_block_rows`)"""
+        def fn(p, src, on_device, n, hh, ww, r, b, out):
+            return self._lib.dfd_train_augment_block_rows(p, src, on_device, n, hh, ww, r, b, int(block), out)
+
+        return self._train_augment_forward(fn, BLOCK_ROWS_SHAPES.get(int(block), BLOCK14_SHAPE), rgb, rows, batch, shape)
+
+    def train_augment_rows11(self, rgb, rows, batch, shape=None) -> np.ndarray:
+        """`train_augment_block_rows(block=11)`: the extractor of a trainer with block 11 unfrozen"""
+        return self.train_augment_block_rows(rgb, rows, batch, block=11, shape=shape)
+
     def train_augment_input13(self, rgb, rows, batch, shape=None) -> np.ndarray:
         """`train_augment_block_input(block=13)`: the extractor of a trainer with block 13 unfrozen"""
         return self.train_augment_block_input(rgb, rows, batch, block=13, shape=shape)
@@ -772,6 +803,7 @@ class Handle:
             raise KeyError(f"head parameters missing: {missing}")
         hp, _keep = _head_arrays(params)
         self._check(self._lib.dfd_head_train_begin(self._p, C.byref(hp), C.byref(config)))
+        self._block_row = BLOCK14_ROW                           # floats of a row of the `_block` entries; block 11 widens it
 
     def head_train_accumulate(self, feat, labels_a, labels_b=None, lam: float = 1.0, loss_scale: float = 1.0):
         """-> (unscaled loss, logits (n,))"""
@@ -821,6 +853,8 @@ class Handle:
         for b in (14, 13, 12):                                  # the skip blocks share block 14's six taps
             wide.update({f"b{b}.out": (49, 192), f"b{b}.dout": (49, 192), f"b{b}.ad": (49, 1152), f"b{b}.dae": (49, 1152),
                          f"b{b}.gate": (1152,), f"b{b}.keep": ()})
+        wide.update({"b11.out": (49, 192), "b11.dout": (49, 192), "b11.ad": (49, 672), "b11.dae": (196, 672), "b11.gate": (672,),
+                     "b11.keep": ()})                           # block 11 has no skip: the library refuses "b11.keep"
         out = np.empty((int(n),) + wide.get(name, (width,)), np.float32)
         self._check(self._lib.dfd_head_train_tap(self._p, name.encode(), _ptr(out), out.size))
         return out
@@ -884,10 +918,14 @@ class Handle:
 
     # -- block 15 of the head trainer (include/dfd_hip.h "fine-tuning block 15 with the head conv and the head")
     @staticmethod
-    def _as_block14(x) -> np.ndarray:
+    def _as_block14(x, row: int = BLOCK14_ROW) -> np.ndarray:
+        """rows of a block stage: (n,7,7,192) / (n,9408), or with block 11 unfrozen (`row` = 21952) its (n,14,14,112) /
+        (n,21952): the library reads `row` floats a crop, so rows of the other kind are refused here"""
         a = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
-        if a.ndim < 2 or a.shape[1:] not in (BLOCK14_SHAPE, (BLOCK14_ROW,)):
-            raise ValueError(f"expected (n,7,7,192) or (n,{BLOCK14_ROW}) rows of block 14's output, got {a.shape}")
+        ok = (BLOCK11_INPUT_SHAPE, (BLOCK11_INPUT_ROW,)) if row == BLOCK11_INPUT_ROW else (BLOCK14_SHAPE, (BLOCK14_ROW,))
+        if a.ndim < 2 or a.shape[1:] not in ok:
+            raise ValueError(f"expected (n,7,7,192) or (n,{BLOCK14_ROW}) rows of block 14's output (with block 11 unfrozen: "
+                             f"(n,14,14,112) or (n,{BLOCK11_INPUT_ROW})), got {a.shape}")
         return a
 
     def head_train_unfreeze_block(self, params, block: int = 15, bn_momentum: float = 0.01, bn_eps: float = 1e-3):
@@ -900,7 +938,7 @@ class Handle:
 
     def head_train_accumulate_block(self, rows, labels_a, labels_b=None, lam: float = 1.0, loss_scale: float = 1.0):
         """-> (unscaled loss, logits (n,))"""
-        a = self._as_block14(rows)
+        a = self._as_block14(rows, getattr(self, "_block_row", BLOCK14_ROW))
         n = a.shape[0]
         ya = np.ascontiguousarray(np.asarray(labels_a, dtype=np.float32).reshape(-1))
         yb = None if labels_b is None else np.ascontiguousarray(np.asarray(labels_b, dtype=np.float32).reshape(-1))
@@ -913,7 +951,7 @@ class Handle:
         return float(loss.value), logits[:n]
 
     def head_train_eval_block(self, rows, use_ema: bool = False) -> np.ndarray:
-        a = self._as_block14(rows)
+        a = self._as_block14(rows, getattr(self, "_block_row", BLOCK14_ROW))
         out = np.empty(max(a.shape[0], 1), np.float32)
         self._check(self._lib.dfd_head_train_eval_block(self._p, _ptr(a), a.shape[0], int(bool(use_ema)), _ptr(out)))
         return out[: a.shape[0]]
@@ -943,9 +981,14 @@ class Handle:
         missing = [k for k in BLOCK_FIELDS if k not in params]
         if missing:
             raise KeyError(f"block parameters missing: {missing}")
-        bp, _keep = _block_arrays(params, block=14)
+        # block 11 has shapes of its own: the arrays are taken in the shapes their sizes name (block 11's or block 14's),
+        # so that a call the library refuses by `block` or by the trainer's state reaches it and gets its code
+        own = int(np.size(params["exp_w"])) == int(np.prod(BLOCK11_SHAPES["exp_w"]))
+        bp, _keep = _block_arrays(params, block=11 if own else 14)
         self._check(self._lib.dfd_head_train_unfreeze_block_at(self._p, int(block), C.byref(bp), float(bn_momentum), float(bn_eps),
                                                                float(drop_connect)))
+        if int(block) == 11:
+            self._block_row = BLOCK11_INPUT_ROW                 # the rows are block 10's output from here on
 
     def head_train_export_block_at(self, block: int, use_ema: bool = False):
         bp, out = _block_arrays(block=block)
@@ -953,7 +996,7 @@ class Handle:
         return out
 
     def head_train_block_grads_at(self, block: int, set_to=None):
-        """`head_train_block_grads` of block 12 .. 15"""
+        """`head_train_block_grads` of block 11 .. 15"""
         if set_to is not None:
             bp, _keep = _block_arrays(set_to, BLOCK_STAT_FIELDS, block)
             self._check(self._lib.dfd_head_train_block_grads_at(self._p, int(block), C.byref(bp), 1))

@@ -561,6 +561,16 @@ int dfd_extract_block_input(dfd_handle* h, const float* nchw_host, int n, int bl
     return b0_trunk_to_host(h, h->in_nchw, n, out_host, block - 1);        // a block's input is the output of the block below it
 }
 
+int dfd_extract_block_rows(dfd_handle* h, const float* nchw_host, int n, int block, float* out_host) {
+    if (!h) return DFD_ERR_ARG;
+    if (!nchw_host || !out_host) return fail(h, DFD_ERR_ARG, "extract_block_rows: null pointer");
+    if (block < 11 || block > 15) return fail(h, DFD_ERR_ARG, "extract_block_rows: block %d; 11, 12, 13, 14 or 15", block);
+    if (n <= 0 || n > h->max_batch) return fail(h, n <= 0 ? DFD_ERR_ARG : DFD_ERR_CAPACITY, "extract_block_rows: batch %d outside 1..%d", n, h->max_batch);
+    DFD_HIP_TRY(h, hipSetDevice(h->device));
+    DFD_HIP_TRY(h, hipMemcpyAsync(h->in_nchw, nchw_host, (size_t)n * 3 * 224 * 224 * 4, hipMemcpyHostToDevice, h->stream));
+    return b0_trunk_to_host(h, h->in_nchw, n, out_host, block - 1);        // block 11's rows are block 10's output, [14][14][112]
+}
+
 int dfd_b0_tap(dfd_handle* h, const float* nchw_dev, int n, const char* name, float* out_host,
                size_t capacity, size_t* count) {
     if (!h) return DFD_ERR_ARG;

@@ -401,7 +401,7 @@ __global__ __launch_bounds__(HT_THREADS) void ht_sumsq_kernel(const float* __res
 // clip_grad_norm_ + torch.optim.AdamW (single-tensor path, in its order) + EMAModel.update + zero_grad, one element per thread.
 // decay_mul = 1 - lr wd, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t): computed on the host in double.
 // The squared norm is the sum of the arenas' partials, added entry by entry in the table's order (head, conv, block 15, 14,
-// 13, 12; null entries left out): one norm over every group.
+// 13, 12, 11; null entries left out): one norm over every group.
 __global__ __launch_bounds__(HT_THREADS) void ht_adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                               float* __restrict__ v, float* __restrict__ ema, int count,
                                                               NormParts parts, float clip_norm,
@@ -756,7 +756,7 @@ int dfd_head_train_tap(dfd_handle* h, const char* name, float* out, size_t capac
     if (!name || !out) return fail(h, DFD_ERR_ARG, "head_train_tap: null pointer");
     if (S->last_n == 0) return fail(h, DFD_ERR_ARG, "head_train_tap: no accumulate has run yet");
     if (!strcmp(name, "cfeat") || !strcmp(name, "dfeat") || !strcmp(name, "cz")) return headconv_tap(h, S, name, out, capacity);
-    if (name[0] == 'b' && name[1] == '1' && name[2] >= '2' && name[2] <= '5' && name[3] == '.') return headblock_tap(h, S, name, out, capacity);
+    if (name[0] == 'b' && name[1] == '1' && name[2] >= '1' && name[2] <= '5' && name[3] == '.') return headblock_tap(h, S, name, out, capacity);
     const uint8_t* mask = nullptr;
     const float* act = nullptr;
     int width = 0;
@@ -788,7 +788,7 @@ int dfd_head_train_commit(dfd_handle* h, int use_ema) {
     HeadTrainState* S = open_state(h, "head_train_commit", &rc);
     if (!S) return rc;
     DFD_HIP_TRY(h, hipSetDevice(h->device));
-    if (S->stage[0] && (rc = headblock_commit(h, S, use_ema))) return rc;      // the blocks' BatchNorms folded, b15.* .. b12.*
+    if (S->stage[0] && (rc = headblock_commit(h, S, use_ema))) return rc;      // the blocks' BatchNorms folded, b15.* .. b11.*
     if (S->conv && (rc = headconv_commit(h, S, use_ema))) return rc;           // _bn1 folded into _conv_head, head.w / head.b
     std::vector<float> P(HT_COUNT), rm1(HT_H1), rv1(HT_H1), rm2(HT_H2), rv2(HT_H2);
     DFD_HIP_TRY(h, hipMemcpyAsync(P.data(), use_ema ? S->ema : S->param, (size_t)HT_COUNT * 4, hipMemcpyDeviceToHost, h->stream));

@@ -28,6 +28,14 @@
 // one rounding) into that block's dx; the deepest trained block hands nothing down.  Block b draws its drop-connect mask
 // from the trainer's hash with layer 17 - b.
 //
+// Block 11 (the same entry, once block 12 is unfrozen): net._blocks.11 (MBConv k5 at stride 2 with TF-"SAME" padding 1 before
+// and 2 after, 112 -> 672 -> 192, squeeze-excite 28, 14 x 14 -> 7 x 7, no skip and so no drop-connect) runs the same chain on
+// a fifth state through the geometry G11: m0 = 196 n rows in front of the depthwise conv (X, Ze, ae, dae, BN0's statistics),
+// m1 = 49 n after it; the depthwise conv, its input gradient (a gather per input element) and its weight gradient are the
+// bk_dws_* kernels; the channel statistics over 672 channels and the expand's weight gradient (42 waves) run the guarded
+// instances of head_train_gemm.h.  Its last forward launch (bk_bn_kernel) writes BN2(Zp) into block 12's input buffer, block
+// 12 hands dX12 = dOut12 + dZe12 . We12 into its dx, and it forms no input gradient itself: block 10 is frozen.
+//
 // Arithmetic as head_train_conv.hip: the GEMMs run on the fp64 MFMA with fp32 operands widened at the load
 // (head_train_gemm.h), every other element is computed in double from stored fp32 values and rounded once where it is
 // stored.  ye, yd, t = ad * gate and the dZ of the three BatchNorms are never stored; the small squeeze-excite vectors
@@ -53,42 +61,67 @@ using namespace dfd::ht64;
 
 namespace {
 
-// what blocks 12-15 share: 192 -> 1152, squeeze-excite 48, 7 x 7
-constexpr int BK_IN = 192, BK_EXP = 1152, BK_SE = 48, BK_HW = 49, BK_H = 7, BK_ROW = BK_HW * BK_IN;
-constexpr int BK_JE = 6;                  // column tiles a wave over 1152 = 12 x 96
+// What the blocks of one width share: input width, expanded width, squeeze width, the input's edge and the depthwise
+// conv's stride.  HW_IN positions a crop in front of the depthwise conv (the rows of X, Ze, ae, dae), HW after it (Zd, ad,
+// dt, Zp, the output); the two are one number at stride 1.  The kernels that index by these take the shape as a parameter.
+template <int IN_, int EXP_, int SE_, int H_IN_, int STRIDE_>
+struct Shape {
+    static constexpr int IN = IN_, EXP = EXP_, SE = SE_, H_IN = H_IN_, STRIDE = STRIDE_;
+    static constexpr int H = (H_IN_ + STRIDE_ - 1) / STRIDE_, HW_IN = H_IN * H_IN, HW = H * H, ROW = HW_IN * IN;
+    static_assert(SE % 4 == 0, "a wave of the squeeze-excite kernels owns SE / 4 of the squeezed values");
+};
+typedef Shape<192, 1152, 48, 7, 1> S7;    // blocks 12-15: 192 -> 1152, squeeze-excite 48, 7 x 7
+typedef Shape<112, 672, 28, 14, 2> S14;   // block 11: 112 -> 672, squeeze-excite 28, 14 x 14 -> 7 x 7
 constexpr int BK_DW_CROPS = 8;            // crops of one partial depthwise weight gradient
-// A block's geometry: its depthwise kernel size (pad KS / 2), output width, whether it has the identity skip, and JP, the
-// column tiles a wave of the projection's forward GEMM.  The block group's arena (floats); every offset a multiple of 4.
-template <int KS_, int OUT_, bool SKIP_, int JP_>
+// A block's geometry: its shape, its depthwise kernel size and low pad (the high pad follows from TF-"SAME"), output width,
+// whether it has the identity skip, and the column tiles a wave takes: JP in the projection's forward GEMM, JE in the
+// expand's forward GEMM, gemm_dyw and the projection's weight gradient (EXP = 96 x ..), JW over the input width in the
+// expand's weight gradient.  The block group's arena (floats); every offset a multiple of 4.
+template <class S_, int KS_, int PAD_, int OUT_, bool SKIP_, int JP_, int JE_, int JW_>
 struct Geo {
-    static constexpr int KS = KS_, TAPS = KS_ * KS_, PAD = KS_ / 2, OUT = OUT_, JP = JP_;
+    typedef S_ S;
+    static constexpr int IN = S::IN, EXP = S::EXP, SE = S::SE, HW_IN = S::HW_IN, HW = S::HW, STRIDE = S::STRIDE;
+    static constexpr int KS = KS_, TAPS = KS_ * KS_, PAD = PAD_, OUT = OUT_, JP = JP_, JE = JE_, JW = JW_;
     static constexpr bool SKIP = SKIP_;
-    static constexpr int O_WE = 0, O_WD = O_WE + BK_EXP * BK_IN, O_W1 = O_WD + BK_EXP * TAPS, O_B1 = O_W1 + BK_SE * BK_EXP;
-    static constexpr int O_W2 = O_B1 + BK_SE, O_B2 = O_W2 + BK_EXP * BK_SE, O_WP = O_B2 + BK_EXP, O_G0 = O_WP + OUT * BK_EXP;
-    static constexpr int O_BE0 = O_G0 + BK_EXP, O_G1 = O_BE0 + BK_EXP, O_BE1 = O_G1 + BK_EXP, O_G2 = O_BE1 + BK_EXP;
+    static constexpr int O_WE = 0, O_WD = O_WE + EXP * IN, O_W1 = O_WD + EXP * TAPS, O_B1 = O_W1 + SE * EXP;
+    static constexpr int O_W2 = O_B1 + SE, O_B2 = O_W2 + EXP * SE, O_WP = O_B2 + EXP, O_G0 = O_WP + OUT * EXP;
+    static constexpr int O_BE0 = O_G0 + EXP, O_G1 = O_BE0 + EXP, O_BE1 = O_G1 + EXP, O_G2 = O_BE1 + EXP;
     static constexpr int O_BE2 = O_G2 + OUT, COUNT = O_BE2 + OUT;
-    static_assert(BK_EXP % (16 * BK_JE) == 0 && OUT % (16 * JP) == 0 && BK_IN % 16 == 0 && BK_EXP % 64 == 0 && OUT % 64 == 0, "tiles");
-    static_assert((OUT / 16 * (BK_EXP / (16 * BK_JE))) % 4 == 0 && (BK_EXP / 16 * (BK_IN / (16 * BK_JE))) % 4 == 0, "weight-gradient grids");
+    // waves of the two weight-gradient launches; the expand's may be no multiple of 4 (the guarded instance takes it)
+    static constexpr int WP_WAVES = OUT / 16 * (EXP / (16 * JE)), WE_WAVES = EXP / 16 * (IN / (16 * JW));
+    static constexpr bool WE_GUARD = WE_WAVES % 4 != 0;
+    static_assert(EXP % (16 * JE) == 0 && OUT % (16 * JP) == 0 && IN % (16 * JW) == 0 && IN % 16 == 0 && EXP % 16 == 0, "tiles");
+    static_assert(WP_WAVES % 4 == 0, "the projection's weight-gradient grid");
     static_assert(OUT % 16 == 0, "gemm_dyw splits its channels over four waves");
     static_assert(O_WD % 4 == 0 && O_W1 % 4 == 0 && O_W2 % 4 == 0 && O_WP % 4 == 0, "weight rows must stay 16-byte aligned");
+    static_assert(!SKIP || (STRIDE == 1 && OUT == IN), "the identity skip");
+    static_assert(PAD == (S::H * STRIDE + KS - STRIDE - S::H_IN) / 2, "TF-SAME: the smaller half of the padding comes first");
 };
-typedef Geo<3, 320, false, 5> G15;        // block 15; 320 = 4 x 80
-typedef Geo<5, 192, true, 6> G14;         // blocks 14, 13 and 12; 192 = 2 x 96
+typedef Geo<S7, 3, 1, 320, false, 5, 6, 6> G15;     // block 15; 320 = 4 x 80, 1152 = 12 x 96, 192 = 2 x 96
+typedef Geo<S7, 5, 2, 192, true, 6, 6, 6> G14;      // blocks 14, 13 and 12; 192 = 2 x 96
+typedef Geo<S14, 5, 1, 192, false, 6, 6, 7> G11;    // block 11: stride 2, pad 1 / 2; 672 = 7 x 96, 112 = 7 x 16
 constexpr int BK_LAST = 15, BK_FIRST = BK_LAST - (HT_STAGES - 1);   // the blocks a trainer can hold: stage k = block 15 - k
+constexpr int BK_STRIDED = 11;            // the one block of the range with G11's geometry; 12 .. 14 have G14's
+static_assert(BK_FIRST == BK_STRIDED, "the deepest stage is block 11");
 static_assert(G15::COUNT == 717232, "trainable floats of block 15");
 static_assert(G14::COUNT == 587952, "trainable floats of each of blocks 14, 13 and 12");
-static_assert(DFD_TRUNK_ROW == BK_HW * G15::OUT, "block 15's output is the conv stage's row");
-static_assert(G14::OUT == BK_IN && BK_IN % (16 * BK_JE) == 0, "a skip block's output is the next block's input; dOut = dZe . We in 96-column tiles");
+static_assert(G11::COUNT == 262492, "trainable floats of block 11");
+static_assert(!G15::WE_GUARD && !G14::WE_GUARD && G11::WE_GUARD && G11::WE_WAVES == 42, "only block 11's expand needs the guarded weight gradient");
+static_assert(DFD_TRUNK_ROW == S7::HW * G15::OUT, "block 15's output is the conv stage's row");
+static_assert(G14::OUT == S7::IN && S7::IN % (16 * G14::JE) == 0, "a skip block's output is the next block's input; dOut = dZe . We in 96-column tiles");
+static_assert(G11::OUT == S7::IN && G11::HW == S7::HW_IN, "block 11's output is block 12's input");
 // the same at run time, for the host code that only moves tensors
 struct Layout {
     int index, ks, taps, out;
     bool skip;
     int o_we, o_wd, o_w1, o_b1, o_w2, o_b2, o_wp, o_g[3], o_be[3], count, bnc[3];
+    int in, exp, se, hw_in, hw, stride;
 };
 template <class G>
 Layout layout_of(int index) {
     return Layout{index, G::KS, G::TAPS, G::OUT, G::SKIP, G::O_WE, G::O_WD, G::O_W1, G::O_B1, G::O_W2, G::O_B2, G::O_WP,
-                  {G::O_G0, G::O_G1, G::O_G2}, {G::O_BE0, G::O_BE1, G::O_BE2}, G::COUNT, {BK_EXP, BK_EXP, G::OUT}};
+                  {G::O_G0, G::O_G1, G::O_G2}, {G::O_BE0, G::O_BE1, G::O_BE2}, G::COUNT, {G::EXP, G::EXP, G::OUT},
+                  G::IN, G::EXP, G::SE, G::HW_IN, G::HW, G::STRIDE};
 }
 
 // ---------------------------------------------------------------------------------------------- forward
@@ -115,12 +148,13 @@ __global__ __launch_bounds__(HT_THREADS) void bk_bn_kernel(const float* __restri
 // A skip block's output: out = x + (BN(Zp) / keep_prob) b_i (efficientnet_pytorch's drop_connect), in double, rounded once.
 // keep [crop] != 0 where b_i = 1 (null: every crop kept - eval, with keep_prob = 1); a dropped crop's output is its input
 // row bit for bit.  X and out are different buffers.
+template <class S>
 __global__ __launch_bounds__(HT_THREADS) void bk_bn_skip_kernel(const float* __restrict__ Z, BnC bn, const float* __restrict__ X,
                                                                 const float* __restrict__ keep, double keep_prob,
                                                                 float* __restrict__ out, size_t total, int C) {
     const size_t i = (size_t)blockIdx.x * HT_THREADS + threadIdx.x;
     if (i >= total) return;
-    if (keep && keep[i / ((size_t)BK_HW * C)] == 0.f) {
+    if (keep && keep[i / ((size_t)S::HW * C)] == 0.f) {
         out[i] = X[i];
         return;
     }
@@ -139,12 +173,14 @@ __global__ __launch_bounds__(HT_THREADS) void bk_eval_consts_kernel(const float*
     istd[c] = 1.0 / sqrt((double)rv[c] + eps);
 }
 
-// Depthwise KS x KS, pad KS / 2, on [n][7][7][1152]: one thread per output element, channels fastest; the KS KS taps in
+// Depthwise KS x KS at stride 1, pad KS / 2, on [n][7][7][1152]: one thread per output element, channels fastest; the KS KS taps in
 // (ky, kx) order in double, taps outside the 7 x 7 left out (at KS = 5 every position has some, 16 of 25 in the corners).
 // W [c][ky][kx] (torch's layout).
-template <int KS>
+template <class S, int KS>
 __global__ __launch_bounds__(HT_THREADS) void bk_dw_fwd_kernel(const float* __restrict__ A, const float* __restrict__ W,
                                                                float* __restrict__ Z, size_t total) {
+    static_assert(S::STRIDE == 1, "the strided form is bk_dws_fwd_kernel");
+    constexpr int BK_EXP = S::EXP, BK_HW = S::HW, BK_H = S::H;
     const size_t i = (size_t)blockIdx.x * HT_THREADS + threadIdx.x;
     if (i >= total) return;
     const int c = (int)(i % BK_EXP), p = (int)((i / BK_EXP) % BK_HW), y = p / BK_H, x = p % BK_H;
@@ -162,10 +198,36 @@ __global__ __launch_bounds__(HT_THREADS) void bk_dw_fwd_kernel(const float* __re
     Z[i] = (float)s;
 }
 
-// ad = swish(BN(Zd)) and its mean over the 49 positions: grid (ceil(1152 / 256), n), one thread per (crop, channel).  The
-// pooled value is the sum of the stored fp32 ad in position order / 49, rounded once.
+// The same at a stride (block 11: 5 x 5, stride 2, pad 1 before and 2 after, [n][14][14][672] -> [n][7][7][672]): one thread
+// per OUTPUT element; output (oy, ox) reads input (STRIDE oy - PAD + ky, STRIDE ox - PAD + kx), the taps in (ky, kx) order in
+// double, taps outside the input left out (9 live taps of 25 in the corner (6, 6), 16 in (0, 0)).  total = n HW EXP.
+template <class S, int KS, int PAD>
+__global__ __launch_bounds__(HT_THREADS) void bk_dws_fwd_kernel(const float* __restrict__ A, const float* __restrict__ W,
+                                                                float* __restrict__ Z, size_t total) {
+    constexpr int EXP = S::EXP, H = S::H, H_IN = S::H_IN;
+    const size_t i = (size_t)blockIdx.x * HT_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)(i % EXP), p = (int)((i / EXP) % S::HW), oy = p / H, ox = p % H;
+    const size_t base = (i / ((size_t)S::HW * EXP)) * ((size_t)S::HW_IN * EXP) + c;      // input position 0 of this crop, channel c
+    double s = 0.0;
+#pragma unroll
+    for (int ky = 0; ky < KS; ++ky) {
+#pragma unroll
+        for (int kx = 0; kx < KS; ++kx) {
+            const int yy = S::STRIDE * oy - PAD + ky, xx = S::STRIDE * ox - PAD + kx;
+            if (yy < 0 || yy >= H_IN || xx < 0 || xx >= H_IN) continue;
+            s += (double)A[base + (size_t)(yy * H_IN + xx) * EXP] * (double)W[c * (KS * KS) + ky * KS + kx];
+        }
+    }
+    Z[i] = (float)s;
+}
+
+// ad = swish(BN(Zd)) and its mean over the HW output positions (49): grid (ceil(EXP / 256), n), one thread per (crop,
+// channel).  The pooled value is the sum of the stored fp32 ad in position order / 49, rounded once.
+template <class S>
 __global__ __launch_bounds__(HT_THREADS) void bk_bn_swish_pool_kernel(const float* __restrict__ Z, BnC bn, float* __restrict__ AD,
                                                                       float* __restrict__ pooled) {
+    constexpr int BK_EXP = S::EXP, BK_HW = S::HW;
     const int c = blockIdx.x * HT_THREADS + threadIdx.x, i = blockIdx.y;
     if (c >= BK_EXP) return;
     const BnK k = bn.load(c);
@@ -186,12 +248,15 @@ __device__ __forceinline__ double wave_sum(double v) {
     return __shfl(v, 0, 64);
 }
 
-// Squeeze-excite forward, one block per crop: r = W1 s + b1 [48], q = swish(r), u = W2 q + b2 [1152], gate = sigmoid(u).
-// A wave owns 12 of the 48 r: lanes take the 1152 terms 64 apart, then the fixed tree.  r, q stay in double.
+// Squeeze-excite forward, one block per crop: r = W1 s + b1 [SE], q = swish(r), u = W2 q + b2 [EXP], gate = sigmoid(u).
+// A wave owns SE / 4 of the r (12 of 48; 7 of 28): lanes take the EXP terms 64 apart (at 672 the upper half of the lanes
+// one term fewer), then the fixed tree.  r, q stay in double.
+template <class S>
 __global__ __launch_bounds__(HT_THREADS) void bk_se_fwd_kernel(const float* __restrict__ pooled, const float* __restrict__ W1,
                                                                const float* __restrict__ B1, const float* __restrict__ W2,
                                                                const float* __restrict__ B2, double* __restrict__ R,
                                                                double* __restrict__ Q, float* __restrict__ gate) {
+    constexpr int BK_EXP = S::EXP, BK_SE = S::SE;
     __shared__ double qs[BK_SE];
     const int i = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const float* s = pooled + (size_t)i * BK_EXP;
@@ -217,7 +282,7 @@ __global__ __launch_bounds__(HT_THREADS) void bk_se_fwd_kernel(const float* __re
 // ---------------------------------------------------------------------------------------------- gradient sources
 // BN2: dy is the stored gradient of the block's output (dX15); with the skip (SKIP) that gradient times the crop's
 // drop-connect factor, dOut14 b_i / keep_prob: exactly zero on a dropped crop
-template <bool SKIP>
+template <bool SKIP, int BK_HW = S7::HW>
 struct Grad2 {
     typedef BnK K;
     BnC bn;
@@ -234,7 +299,9 @@ struct Grad2 {
     }
 };
 // BN1: dad = dt gate + ds / 49 through swish'(yd)
+template <class S>
 struct Grad1 {
+    static constexpr int BK_EXP = S::EXP, BK_HW = S::HW;
     typedef BnK K;
     BnC bn;
     const float *Zd, *dT, *gate;
@@ -248,7 +315,9 @@ struct Grad1 {
     }
 };
 // BN0: the stored dae through swish'(ye)
+template <class S>
 struct Grad0 {
+    static constexpr int BK_EXP = S::EXP;
     typedef BnK K;
     BnC bn;
     const float *Ze, *dA;
@@ -263,10 +332,12 @@ struct Grad0 {
 // ---------------------------------------------------------------------------------------------- backward
 // Squeeze-excite backward, one block per crop: dgate = sum over 49 of dt ad (position order), du = dgate gate (1 - gate),
 // dq = du . W2, dr = dq swish'(r), ds = dr . W1.  du, dr, ds are kept per crop, in double, for bk_se_wgrad_kernel and Grad1.
+template <class S>
 __global__ __launch_bounds__(HT_THREADS) void bk_se_bwd_kernel(const float* __restrict__ dT, const float* __restrict__ AD,
                                                                const float* __restrict__ gate, const double* __restrict__ R,
                                                                const float* __restrict__ W1, const float* __restrict__ W2,
                                                                double* __restrict__ dU, double* __restrict__ dR, double* __restrict__ dS) {
+    constexpr int BK_EXP = S::EXP, BK_SE = S::SE, BK_HW = S::HW;
     __shared__ double du[BK_EXP];
     __shared__ double dr[BK_SE];
     const int i = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -301,11 +372,12 @@ __global__ __launch_bounds__(HT_THREADS) void bk_se_bwd_kernel(const float* __re
 
 // The squeeze-excite weight gradients, one thread per gradient element, the crops added one by one in double:
 //   dW2 [c][j] += sum_i du[i][c] q[i][j],  dW1 [j][k] += sum_i dr[i][j] s[i][k],  db2 [c] += sum_i du[i][c],  db1 [j] += sum_i dr[i][j]
+template <class S>
 __global__ __launch_bounds__(HT_THREADS) void bk_se_wgrad_kernel(const double* __restrict__ dU, const double* __restrict__ dR,
                                                                  const double* __restrict__ Q, const float* __restrict__ pooled,
                                                                  float* __restrict__ gW1, float* __restrict__ gB1,
                                                                  float* __restrict__ gW2, float* __restrict__ gB2, int n) {
-    constexpr int NW = BK_EXP * BK_SE;
+    constexpr int BK_EXP = S::EXP, BK_SE = S::SE, NW = BK_EXP * BK_SE;
     int e = blockIdx.x * HT_THREADS + threadIdx.x;
     double s = 0.0;
     if (e < NW) {
@@ -326,7 +398,9 @@ __global__ __launch_bounds__(HT_THREADS) void bk_se_wgrad_kernel(const double* _
 }
 
 // dZd of BN1, stored over dt (every thread reads its own element of dt before it writes it)
-__global__ __launch_bounds__(HT_THREADS) void bk_dz_store_kernel(Grad1 g, float* out, size_t total) {
+template <class S>
+__global__ __launch_bounds__(HT_THREADS) void bk_dz_store_kernel(Grad1<S> g, float* out, size_t total) {
+    constexpr int BK_EXP = S::EXP;
     const size_t i = (size_t)blockIdx.x * HT_THREADS + threadIdx.x;
     if (i >= total) return;
     const int c = (int)(i % BK_EXP);
@@ -336,9 +410,11 @@ __global__ __launch_bounds__(HT_THREADS) void bk_dz_store_kernel(Grad1 g, float*
 
 // dae [y][x] = sum over (ky, kx) of dZd [y - ky + KS / 2][x - kx + KS / 2] W [ky][kx]: the correlation with the flipped
 // kernel, pad KS / 2
-template <int KS>
+template <class S, int KS>
 __global__ __launch_bounds__(HT_THREADS) void bk_dw_bwd_kernel(const float* __restrict__ dZ, const float* __restrict__ W,
                                                                float* __restrict__ dA, size_t total) {
+    static_assert(S::STRIDE == 1, "the strided form is bk_dws_bwd_kernel");
+    constexpr int BK_EXP = S::EXP, BK_HW = S::HW, BK_H = S::H;
     const size_t i = (size_t)blockIdx.x * HT_THREADS + threadIdx.x;
     if (i >= total) return;
     const int c = (int)(i % BK_EXP), p = (int)((i / BK_EXP) % BK_HW), y = p / BK_H, x = p % BK_H;
@@ -356,12 +432,41 @@ __global__ __launch_bounds__(HT_THREADS) void bk_dw_bwd_kernel(const float* __re
     dA[i] = (float)s;
 }
 
+// The same at a stride, as a gather (no atomics, no scatter): one thread per INPUT element (iy, ix); it collects the taps
+// with STRIDE oy - PAD + ky = iy, in (ky, kx) order - at stride 2 and pad 1 an even iy takes ky in {1, 3}, an odd one ky in
+// {0, 2, 4}, so an element sums 4, 6 or 9 taps before the border removes those whose output lies outside the 7 x 7.
+// dZ [n][HW][EXP] -> dA [n][HW_IN][EXP]; total = n HW_IN EXP.
+template <class S, int KS, int PAD>
+__global__ __launch_bounds__(HT_THREADS) void bk_dws_bwd_kernel(const float* __restrict__ dZ, const float* __restrict__ W,
+                                                                float* __restrict__ dA, size_t total) {
+    constexpr int EXP = S::EXP, H = S::H, H_IN = S::H_IN, ST = S::STRIDE;
+    const size_t i = (size_t)blockIdx.x * HT_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)(i % EXP), p = (int)((i / EXP) % S::HW_IN), iy = p / H_IN, ix = p % H_IN;
+    const size_t base = (i / ((size_t)S::HW_IN * EXP)) * ((size_t)S::HW * EXP) + c;      // output position 0 of this crop, channel c
+    double s = 0.0;
+#pragma unroll
+    for (int ky = 0; ky < KS; ++ky) {
+        const int ty = iy + PAD - ky;                            // = STRIDE oy
+        if (ty < 0 || ty % ST != 0 || ty / ST >= H) continue;
+#pragma unroll
+        for (int kx = 0; kx < KS; ++kx) {
+            const int tx = ix + PAD - kx;
+            if (tx < 0 || tx % ST != 0 || tx / ST >= H) continue;
+            s += (double)dZ[base + (size_t)((ty / ST) * H + tx / ST) * EXP] * (double)W[c * (KS * KS) + ky * KS + kx];
+        }
+    }
+    dA[i] = (float)s;
+}
+
 // Partial depthwise weight gradient of crops [8 chunk, 8 (chunk + 1)) n [0, n): P [chunk][tap][c] = sum over those crops
 // and the positions (crop, then position order) of dZd [y][x] ae [y + ky - KS / 2][x + kx - KS / 2].
 // grid (ceil(1152 / 256), KS KS, chunks).
-template <int KS>
+template <class S, int KS>
 __global__ __launch_bounds__(HT_THREADS) void bk_dw_wgrad_kernel(const float* __restrict__ dZ, const float* __restrict__ A,
                                                                  double* __restrict__ P, int n) {
+    static_assert(S::STRIDE == 1, "the strided form is bk_dws_wgrad_kernel");
+    constexpr int BK_EXP = S::EXP, BK_HW = S::HW, BK_H = S::H;
     const int c = blockIdx.x * HT_THREADS + threadIdx.x, tap = blockIdx.y, ky = tap / KS, kx = tap % KS;
     if (c >= BK_EXP) return;
     const int i0 = blockIdx.z * BK_DW_CROPS, i1 = min(n, i0 + BK_DW_CROPS);
@@ -381,9 +486,36 @@ __global__ __launch_bounds__(HT_THREADS) void bk_dw_wgrad_kernel(const float* __
     P[((size_t)blockIdx.z * (KS * KS) + tap) * BK_EXP + c] = s;
 }
 
+// The same at a stride: P [chunk][tap][c] = sum over the chunk's crops and the OUTPUT positions (crop, then position order)
+// of dZd [oy][ox] ae [STRIDE oy - PAD + ky][STRIDE ox - PAD + kx], positions whose tap lies outside the input left out.
+template <class S, int KS, int PAD>
+__global__ __launch_bounds__(HT_THREADS) void bk_dws_wgrad_kernel(const float* __restrict__ dZ, const float* __restrict__ A,
+                                                                  double* __restrict__ P, int n) {
+    constexpr int EXP = S::EXP, H = S::H, H_IN = S::H_IN, ST = S::STRIDE;
+    const int c = blockIdx.x * HT_THREADS + threadIdx.x, tap = blockIdx.y, ky = tap / KS, kx = tap % KS;
+    if (c >= EXP) return;
+    const int i0 = blockIdx.z * BK_DW_CROPS, i1 = min(n, i0 + BK_DW_CROPS);
+    double s = 0.0;
+    for (int i = i0; i < i1; ++i) {
+        const size_t zb = (size_t)i * S::HW * EXP + c, ab = (size_t)i * S::HW_IN * EXP + c;
+        for (int oy = 0; oy < H; ++oy) {
+            const int yy = ST * oy - PAD + ky;
+            if (yy < 0 || yy >= H_IN) continue;
+            for (int ox = 0; ox < H; ++ox) {
+                const int xx = ST * ox - PAD + kx;
+                if (xx < 0 || xx >= H_IN) continue;
+                s += (double)dZ[zb + (size_t)(oy * H + ox) * EXP] * (double)A[ab + (size_t)(yy * H_IN + xx) * EXP];
+            }
+        }
+    }
+    P[((size_t)blockIdx.z * (KS * KS) + tap) * EXP + c] = s;
+}
+
 // G [c][tap] += the chunks' partials added in chunk order, rounded once
+template <class S>
 __global__ __launch_bounds__(HT_THREADS) void bk_dw_wreduce_kernel(const double* __restrict__ P, int chunks, float* __restrict__ G,
                                                                    int taps) {
+    constexpr int BK_EXP = S::EXP;
     const int e = blockIdx.x * HT_THREADS + threadIdx.x;
     if (e >= BK_EXP * taps) return;
     const int tap = e / BK_EXP, c = e % BK_EXP;
@@ -428,7 +560,7 @@ void destroy_one(HeadBlockState** slot) {
     delete K;
     *slot = nullptr;
 }
-// the stage of block 15 .. 12, or null where it is not unfrozen (or the trainer holds no such block)
+// the stage of block 15 .. 11, or null where it is not unfrozen (or the trainer holds no such block)
 HeadBlockState* stage_of(HeadTrainState* S, int block) {
     return block >= BK_FIRST && block <= BK_LAST ? S->stage[BK_LAST - block] : nullptr;
 }
@@ -451,7 +583,7 @@ const double* headblock_partial(HeadTrainState* S, int k) {
 }
 
 void headblock_adamw(dfd_handle* h, HeadTrainState* S, double lr, double t) {
-    // the arenas' partials in the order of the other launches (head, conv, block 15, 14, 13, 12): all see the same norm
+    // the arenas' partials in the order of the other launches (head, conv, block 15, 14, 13, 12, 11): all see the same norm
     const NormParts parts = head_train_norm_parts(S);
     for (int k = 0; k < HT_STAGES && S->stage[k]; ++k) {
         HeadBlockState* K = S->stage[k];
@@ -461,8 +593,8 @@ void headblock_adamw(dfd_handle* h, HeadTrainState* S, double lr, double t) {
 }
 
 int headblock_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out, size_t capacity) {
-    const int block = 10 + (name[2] - '0'), k = BK_LAST - block;             // "b15." .. "b12.": the caller checked the prefix
-    const bool skip = block != BK_LAST;
+    const int block = 10 + (name[2] - '0'), k = BK_LAST - block;             // "b15." .. "b11.": the caller checked the prefix
+    const bool below = block != BK_LAST;                        // a block under block 15: its output is the next stage's input
     HeadBlockState* K = stage_of(S, block);
     if (!K)
         return fail(h, DFD_ERR_ARG, "head_train_tap: '%s' needs block %d's stage (%s)", name, block, unfreeze_entry(block));
@@ -470,12 +602,13 @@ int headblock_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out
     size_t per = 0;
     const char* what = name + 4;
     // a block's output lives in the next stage's input buffer
-    if (!strcmp(what, "out")) { src = skip ? S->stage[k - 1]->x : headconv_rows(S); per = (size_t)BK_HW * K->L.out; }
-    else if (!strcmp(what, "gate")) { src = K->gate; per = BK_EXP; }
-    else if (!strcmp(what, "ad")) { src = K->ad; per = (size_t)BK_HW * BK_EXP; }
-    else if (!strcmp(what, "dout")) { src = K->dx; per = (size_t)BK_HW * K->L.out; }
-    else if (!strcmp(what, "dae")) { src = K->d2; per = (size_t)BK_HW * BK_EXP; }
-    else if (skip && !strcmp(what, "keep")) { src = K->keep; per = 1; }
+    const Layout& L = K->L;
+    if (!strcmp(what, "out")) { src = below ? S->stage[k - 1]->x : headconv_rows(S); per = (size_t)L.hw * L.out; }
+    else if (!strcmp(what, "gate")) { src = K->gate; per = L.exp; }
+    else if (!strcmp(what, "ad")) { src = K->ad; per = (size_t)L.hw * L.exp; }
+    else if (!strcmp(what, "dout")) { src = K->dx; per = (size_t)L.hw * L.out; }
+    else if (!strcmp(what, "dae")) { src = K->d2; per = (size_t)L.hw_in * L.exp; }
+    else if (L.skip && !strcmp(what, "keep")) { src = K->keep; per = 1; }      // block 11 has no skip: no "b11.keep"
     else return fail(h, DFD_ERR_ARG, "head_train_tap: unknown tap '%s'", name);
     const size_t count = (size_t)S->last_n * per;
     if (capacity < count) return fail(h, DFD_ERR_ARG, "head_train_tap: '%s' holds %zu floats, capacity %zu", name, count, capacity);
@@ -487,7 +620,7 @@ int headblock_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out
 
 // A trained block's ten tensors of the inference plan, rewritten in place from the trained parameters (live or EMA) and the
 // running statistics: weights._fold's arithmetic (a = g / sqrt(var + eps); w' = w a; b' = 0 a + (beta - mu a), float64,
-// rounded once) and weights.pack_b0_tensors' layouts (dw.w [ky][kx][c] with 9 or 25 taps, se.w2 [48][1152]).  Readers of
+// rounded once) and weights.pack_b0_tensors' layouts (dw.w [ky][kx][c] with 9 or 25 taps, se.w2 [SE][EXP]).  Readers of
 // these pointers, for blocks 15, 14, 13 and 12 alike (b0_forward's block loop treats all four as "late" 7 x 7 blocks):
 // launch_mbconv_front (mbconv_late_kernel for k3, and for k5 the fused front launch mbconv_k5_kernel in its modes 1 and 2:
 // exp.w through its cached split AND the fp32 tensor, exp.b, dw.w, dw.b), the unfused pointwise_t (exp.w / proj.w: the
@@ -495,13 +628,24 @@ int headblock_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out
 // in launch_pointwise), launch_depthwise (dw.w, dw.b; fp32 and bf16 instances), launch_se (se.w1, se.b1, se.w2, se.b2) and
 // the projection's bias (proj.b); the projections of blocks 14, 13 and 12 also add their input (the skip), which is no weight.  The two cached
 // splits are rebuilt in place, so plan and tile-table pointers stay valid.
+// Block 11 (112 -> 672 -> 192, k5 at stride 2, 14 x 14 -> 7 x 7) is no "late" 7 x 7 block.  Readers of its ten tensors in
+// b0_forward's block loop: launch_mbconv_front with mbconv_k5_kernel as the per-image instance of "fuse_k5" (block 11 has no
+// mbconv_late_kernel form, so always mode 2: exp.w through its cached split AND the fp32 tensor, exp.b, dw.w, dw.b) and the
+// other fused front modes (mbconv_kernel under "fuse_expand": the same five pointers); the standalone expand GEMM
+// (pointwise_t on exp.w / exp.b: the cached split under the split GEMM, the fp32 tensor in launch_pointwise); the unfused
+// launch_depthwise (dw.w, dw.b) and launch_se (se.w1, se.b1, se.w2, se.b2); the projection (pointwise_t on proj.w through
+// its cached split, proj.b; no skip input); and the bf16-activation instances of all of these, which always read the
+// cached splits.  Every one of them reads through the plan's pointers or h->wsplit's entry for that pointer at launch time;
+// nothing holds a copy, so the in-place writes below reach all of them.
 static int commit_one(dfd_handle* h, HeadBlockState* K, int use_ema) {
     const Layout& L = K->L;
     if ((int)h->b0.blocks.size() <= L.index) return fail(h, DFD_ERR_STATE, "head_train_commit: the plan has no block %d", L.index);
     const B0Block& b = h->b0.blocks[L.index];
-    if (b.c_in != BK_IN || b.c_exp != BK_EXP || b.c_se != BK_SE || b.c_out != L.out || b.kernel != L.ks || (b.skip != 0) != L.skip)
-        return fail(h, DFD_ERR_STATE, "head_train_commit: block %d of the plan is not 192 -> 1152 -> %d, k%d", L.index, L.out, L.ks);
-    const int T = L.taps, OUT = L.out;
+    if (b.c_in != L.in || b.c_exp != L.exp || b.c_se != L.se || b.c_out != L.out || b.kernel != L.ks || (b.skip != 0) != L.skip ||
+        b.stride != L.stride)
+        return fail(h, DFD_ERR_STATE, "head_train_commit: block %d of the plan is not %d -> %d -> %d, k%d at stride %d", L.index, L.in, L.exp,
+                    L.out, L.ks, L.stride);
+    const int T = L.taps, OUT = L.out, BK_IN = L.in, BK_EXP = L.exp, BK_SE = L.se;
     std::vector<float> P(L.count), rm[3], rv[3];
     DFD_HIP_TRY(h, hipMemcpyAsync(P.data(), use_ema ? K->ema : K->param, (size_t)L.count * 4, hipMemcpyDeviceToHost, h->stream));
     for (int l = 0; l < 3; ++l) {
@@ -557,6 +701,7 @@ namespace {
 struct BField { float* dfd_mbconv_params::*ptr; int off, count; };
 // the 13 trainable tensors of a block with their places in its arena
 std::vector<BField> trainable_fields(const Layout& L) {
+    const int BK_IN = L.in, BK_EXP = L.exp, BK_SE = L.se;
     return {
         {&dfd_mbconv_params::exp_w, L.o_we, BK_EXP * BK_IN},   {&dfd_mbconv_params::dw_w, L.o_wd, BK_EXP * L.taps},
         {&dfd_mbconv_params::se_w1, L.o_w1, BK_SE * BK_EXP},   {&dfd_mbconv_params::se_b1, L.o_b1, BK_SE},
@@ -600,6 +745,10 @@ int deepest(const HeadTrainState* S) {
     return k;
 }
 
+constexpr int K11 = BK_LAST - BK_STRIDED;                       // block 11's place in S->stage
+// floats of one input row of a stage: [7][7][192], or block 11's [14][14][112]
+size_t row_floats(const HeadBlockState* K) { return (size_t)K->L.hw_in * K->L.in; }
+
 dim3 flat(size_t total) { return dim3((unsigned)((total + HT_THREADS - 1) / HT_THREADS)); }
 
 // mean and istd of BatchNorm l over the m rows of Z: the batch's (train; running statistics updated) or the running ones
@@ -611,10 +760,13 @@ void bn_statistics(HeadBlockState* K, int l, const float* Z, int m, bool train, 
         return;
     }
     const int ch = stat_chunks(m);
-    const dim3 sg(C / 64, ch);
-    hipLaunchKernelGGL((colstat_kernel<0, NoGrad>), sg, blk, 0, s, NoGrad{}, Z, nullptr, K->spart, nullptr, m, C);
+    const bool guard = C % 64 != 0;                             // 672 channels: the guarded instance on ceil(C / 64) blocks
+    const dim3 sg((C + 63) / 64, ch);
+    if (guard) hipLaunchKernelGGL((colstat_kernel<0, NoGrad, true>), sg, blk, 0, s, NoGrad{}, Z, nullptr, K->spart, nullptr, m, C);
+    else hipLaunchKernelGGL((colstat_kernel<0, NoGrad>), sg, blk, 0, s, NoGrad{}, Z, nullptr, K->spart, nullptr, m, C);
     hipLaunchKernelGGL(finalize_kernel<0>, chan, blk, 0, s, K->spart, nullptr, ch, m, C, K->mean[l], nullptr, nullptr, nullptr, 0.f, 0.0);
-    hipLaunchKernelGGL((colstat_kernel<1, NoGrad>), sg, blk, 0, s, NoGrad{}, Z, K->mean[l], K->spart, nullptr, m, C);
+    if (guard) hipLaunchKernelGGL((colstat_kernel<1, NoGrad, true>), sg, blk, 0, s, NoGrad{}, Z, K->mean[l], K->spart, nullptr, m, C);
+    else hipLaunchKernelGGL((colstat_kernel<1, NoGrad>), sg, blk, 0, s, NoGrad{}, Z, K->mean[l], K->spart, nullptr, m, C);
     hipLaunchKernelGGL(finalize_kernel<1>, chan, blk, 0, s, K->spart, nullptr, ch, m, C, K->istd[l], K->mean[l], K->rm[l], K->rv[l],
                        K->momentum, K->eps);
 }
@@ -624,37 +776,43 @@ template <class G>
 void bn_backward_statistics(HeadBlockState* K, int l, const G& g, int m, hipStream_t s) {
     const int C = K->L.bnc[l], ch = stat_chunks(m);
     const dim3 blk(HT_THREADS);
-    hipLaunchKernelGGL((colstat_kernel<2, G>), dim3(C / 64, ch), blk, 0, s, g, nullptr, nullptr, K->spart, K->spart2, m, C);
+    if (C % 64 != 0) hipLaunchKernelGGL((colstat_kernel<2, G, true>), dim3((C + 63) / 64, ch), blk, 0, s, g, nullptr, nullptr, K->spart, K->spart2, m, C);
+    else hipLaunchKernelGGL((colstat_kernel<2, G>), dim3(C / 64, ch), blk, 0, s, g, nullptr, nullptr, K->spart, K->spart2, m, C);
     hipLaunchKernelGGL(finalize_kernel<2>, dim3((C + HT_THREADS - 1) / HT_THREADS), blk, 0, s, K->spart, K->spart2, ch, m, C, K->sdy[l],
                        K->sdx[l], K->grad + K->L.o_g[l], K->grad + K->L.o_be[l], 0.f, 0.0);
 }
 
 // X (K->x, n rows of the block below) -> the block's output in `out` (the next stage's input rows), with the block's
 // parameters at P.  With the skip: out = X + the branch times the crop's drop-connect factor (`masked`: K->keep, else none).
+// m0 = HW_IN n rows in front of the depthwise conv, m1 = HW n rows after it (one number at stride 1).
 template <class GEO>
 int block_forward(dfd_handle* h, HeadBlockState* K, const float* P, int n, bool train, float* out, bool masked) {
+    typedef typename GEO::S S;
     hipStream_t s = h->stream;
-    const int m = n * BK_HW;
+    const int m0 = n * GEO::HW_IN, m1 = n * GEO::HW;
     const dim3 blk(HT_THREADS);
-    const size_t te = (size_t)m * BK_EXP, to = (size_t)m * GEO::OUT;
-    hipLaunchKernelGGL((gemm_fwd_kernel<BK_JE, false>), dim3(BK_EXP / (16 * BK_JE), (m + 63) / 64), blk, 0, s, K->x, nullptr, P + GEO::O_WE,
-                       K->ze, m, BK_IN, BK_EXP, BK_HW);
-    bn_statistics(K, 0, K->ze, m, train, s);
-    hipLaunchKernelGGL(bk_bn_swish_kernel, flat(te), blk, 0, s, K->ze, bn_consts(K, P, 0, m, false), K->ae, te, BK_EXP);
-    hipLaunchKernelGGL(bk_dw_fwd_kernel<GEO::KS>, flat(te), blk, 0, s, K->ae, P + GEO::O_WD, K->zd, te);
-    bn_statistics(K, 1, K->zd, m, train, s);
-    hipLaunchKernelGGL(bk_bn_swish_pool_kernel, dim3((BK_EXP + HT_THREADS - 1) / HT_THREADS, n), blk, 0, s, K->zd,
-                       bn_consts(K, P, 1, m, false), K->ad, K->pooled);
-    hipLaunchKernelGGL(bk_se_fwd_kernel, dim3(n), blk, 0, s, K->pooled, P + GEO::O_W1, P + GEO::O_B1, P + GEO::O_W2, P + GEO::O_B2, K->r, K->q,
-                       K->gate);
-    hipLaunchKernelGGL((gemm_fwd_kernel<GEO::JP, true>), dim3(GEO::OUT / (16 * GEO::JP), (m + 63) / 64), blk, 0, s, K->ad, K->gate,
-                       P + GEO::O_WP, K->zp, m, BK_EXP, GEO::OUT, BK_HW);
-    bn_statistics(K, 2, K->zp, m, train, s);
+    const size_t te0 = (size_t)m0 * GEO::EXP, te1 = (size_t)m1 * GEO::EXP, to = (size_t)m1 * GEO::OUT;
+    hipLaunchKernelGGL((gemm_fwd_kernel<GEO::JE, false>), dim3(GEO::EXP / (16 * GEO::JE), (m0 + 63) / 64), blk, 0, s, K->x, nullptr,
+                       P + GEO::O_WE, K->ze, m0, GEO::IN, GEO::EXP, GEO::HW_IN);
+    bn_statistics(K, 0, K->ze, m0, train, s);
+    hipLaunchKernelGGL(bk_bn_swish_kernel, flat(te0), blk, 0, s, K->ze, bn_consts(K, P, 0, m0, false), K->ae, te0, GEO::EXP);
+    if constexpr (GEO::STRIDE == 1)
+        hipLaunchKernelGGL((bk_dw_fwd_kernel<S, GEO::KS>), flat(te1), blk, 0, s, K->ae, P + GEO::O_WD, K->zd, te1);
+    else
+        hipLaunchKernelGGL((bk_dws_fwd_kernel<S, GEO::KS, GEO::PAD>), flat(te1), blk, 0, s, K->ae, P + GEO::O_WD, K->zd, te1);
+    bn_statistics(K, 1, K->zd, m1, train, s);
+    hipLaunchKernelGGL(bk_bn_swish_pool_kernel<S>, dim3((GEO::EXP + HT_THREADS - 1) / HT_THREADS, n), blk, 0, s, K->zd,
+                       bn_consts(K, P, 1, m1, false), K->ad, K->pooled);
+    hipLaunchKernelGGL(bk_se_fwd_kernel<S>, dim3(n), blk, 0, s, K->pooled, P + GEO::O_W1, P + GEO::O_B1, P + GEO::O_W2, P + GEO::O_B2, K->r,
+                       K->q, K->gate);
+    hipLaunchKernelGGL((gemm_fwd_kernel<GEO::JP, true>), dim3(GEO::OUT / (16 * GEO::JP), (m1 + 63) / 64), blk, 0, s, K->ad, K->gate,
+                       P + GEO::O_WP, K->zp, m1, GEO::EXP, GEO::OUT, GEO::HW);
+    bn_statistics(K, 2, K->zp, m1, train, s);
     if constexpr (GEO::SKIP)
-        hipLaunchKernelGGL(bk_bn_skip_kernel, flat(to), blk, 0, s, K->zp, bn_consts(K, P, 2, m, false), K->x, masked ? K->keep : nullptr,
+        hipLaunchKernelGGL(bk_bn_skip_kernel<S>, flat(to), blk, 0, s, K->zp, bn_consts(K, P, 2, m1, false), K->x, masked ? K->keep : nullptr,
                            masked ? K->keep_prob : 1.0, out, to, GEO::OUT);
     else
-        hipLaunchKernelGGL(bk_bn_kernel, flat(to), blk, 0, s, K->zp, bn_consts(K, P, 2, m, false), out, to, GEO::OUT);
+        hipLaunchKernelGGL(bk_bn_kernel, flat(to), blk, 0, s, K->zp, bn_consts(K, P, 2, m1, false), out, to, GEO::OUT);
     DFD_HIP_TRY(h, hipGetLastError());
     return DFD_OK;
 }
@@ -663,46 +821,59 @@ int block_forward(dfd_handle* h, HeadBlockState* K, const float* P, int n, bool 
 // the gradient with respect to the block's input for a trained block below: dZe . We, and with the skip K->dx + dZe . We
 template <class GEO>
 int block_backward(dfd_handle* h, HeadBlockState* K, int n, float* dx_below) {
+    typedef typename GEO::S S;
     hipStream_t s = h->stream;
-    const int m = n * BK_HW, wch = wg_chunks(m);
+    const int m0 = n * GEO::HW_IN, m1 = n * GEO::HW, wch0 = wg_chunks(m0), wch1 = wg_chunks(m1);
     const dim3 blk(HT_THREADS);
     const float* P = K->param;
     float* G = K->grad;
-    const size_t te = (size_t)m * BK_EXP;
+    const size_t te0 = (size_t)m0 * GEO::EXP, te1 = (size_t)m1 * GEO::EXP;
     typedef Grad2<GEO::SKIP> G2;
+    typedef Grad1<S> G1;
+    typedef Grad0<S> G0;
     // BN2, project
-    G2 g2{bn_consts(K, P, 2, m, true), K->zp, K->dx, GEO::OUT, K->keep, K->keep_prob};
-    bn_backward_statistics(K, 2, g2, m, s);
-    hipLaunchKernelGGL((wgrad_kernel<BK_JE, true, G2>), dim3(GEO::OUT / 16 * (BK_EXP / (16 * BK_JE)) / 4, wch), blk, 0, s, g2, K->ad,
-                       K->gate, K->wpart, m, GEO::OUT, BK_EXP, BK_HW);
-    hipLaunchKernelGGL(wreduce_kernel, flat((size_t)GEO::OUT * BK_EXP), blk, 0, s, K->wpart, wch, GEO::OUT * BK_EXP, G + GEO::O_WP);
-    hipLaunchKernelGGL((gemm_dyw_kernel<BK_JE, G2>), dim3(BK_EXP / (16 * BK_JE), (m + 15) / 16), blk, 0, s, g2, P + GEO::O_WP, K->d1, m,
-                       GEO::OUT, BK_EXP);
+    G2 g2{bn_consts(K, P, 2, m1, true), K->zp, K->dx, GEO::OUT, K->keep, K->keep_prob};
+    bn_backward_statistics(K, 2, g2, m1, s);
+    hipLaunchKernelGGL((wgrad_kernel<GEO::JE, true, G2>), dim3(GEO::WP_WAVES / 4, wch1), blk, 0, s, g2, K->ad, K->gate, K->wpart, m1, GEO::OUT,
+                       GEO::EXP, GEO::HW);
+    hipLaunchKernelGGL(wreduce_kernel, flat((size_t)GEO::OUT * GEO::EXP), blk, 0, s, K->wpart, wch1, GEO::OUT * GEO::EXP, G + GEO::O_WP);
+    hipLaunchKernelGGL((gemm_dyw_kernel<GEO::JE, G2>), dim3(GEO::EXP / (16 * GEO::JE), (m1 + 15) / 16), blk, 0, s, g2, P + GEO::O_WP, K->d1, m1,
+                       GEO::OUT, GEO::EXP);
     // squeeze-excite
-    hipLaunchKernelGGL(bk_se_bwd_kernel, dim3(n), blk, 0, s, K->d1, K->ad, K->gate, K->r, P + GEO::O_W1, P + GEO::O_W2, K->du, K->dr, K->ds);
-    hipLaunchKernelGGL(bk_se_wgrad_kernel, flat((size_t)2 * BK_EXP * BK_SE + BK_EXP + BK_SE), blk, 0, s, K->du, K->dr, K->q, K->pooled,
+    hipLaunchKernelGGL(bk_se_bwd_kernel<S>, dim3(n), blk, 0, s, K->d1, K->ad, K->gate, K->r, P + GEO::O_W1, P + GEO::O_W2, K->du, K->dr, K->ds);
+    hipLaunchKernelGGL(bk_se_wgrad_kernel<S>, flat((size_t)2 * GEO::EXP * GEO::SE + GEO::EXP + GEO::SE), blk, 0, s, K->du, K->dr, K->q, K->pooled,
                        G + GEO::O_W1, G + GEO::O_B1, G + GEO::O_W2, G + GEO::O_B2, n);
     // BN1, depthwise
-    Grad1 g1{bn_consts(K, P, 1, m, true), K->zd, K->d1, K->gate, K->ds};
-    bn_backward_statistics(K, 1, g1, m, s);
-    hipLaunchKernelGGL(bk_dz_store_kernel, flat(te), blk, 0, s, g1, K->d1, te);
+    G1 g1{bn_consts(K, P, 1, m1, true), K->zd, K->d1, K->gate, K->ds};
+    bn_backward_statistics(K, 1, g1, m1, s);
+    hipLaunchKernelGGL(bk_dz_store_kernel<S>, flat(te1), blk, 0, s, g1, K->d1, te1);
     const int dch = (n + BK_DW_CROPS - 1) / BK_DW_CROPS;
-    hipLaunchKernelGGL(bk_dw_wgrad_kernel<GEO::KS>, dim3((BK_EXP + HT_THREADS - 1) / HT_THREADS, GEO::TAPS, dch), blk, 0, s, K->d1, K->ae,
-                       K->dwpart, n);
-    hipLaunchKernelGGL(bk_dw_wreduce_kernel, flat((size_t)BK_EXP * GEO::TAPS), blk, 0, s, K->dwpart, dch, G + GEO::O_WD, GEO::TAPS);
-    hipLaunchKernelGGL(bk_dw_bwd_kernel<GEO::KS>, flat(te), blk, 0, s, K->d1, P + GEO::O_WD, K->d2, te);
+    const dim3 dwg((GEO::EXP + HT_THREADS - 1) / HT_THREADS, GEO::TAPS, dch);
+    if constexpr (GEO::STRIDE == 1)
+        hipLaunchKernelGGL((bk_dw_wgrad_kernel<S, GEO::KS>), dwg, blk, 0, s, K->d1, K->ae, K->dwpart, n);
+    else
+        hipLaunchKernelGGL((bk_dws_wgrad_kernel<S, GEO::KS, GEO::PAD>), dwg, blk, 0, s, K->d1, K->ae, K->dwpart, n);
+    hipLaunchKernelGGL(bk_dw_wreduce_kernel<S>, flat((size_t)GEO::EXP * GEO::TAPS), blk, 0, s, K->dwpart, dch, G + GEO::O_WD, GEO::TAPS);
+    if constexpr (GEO::STRIDE == 1)
+        hipLaunchKernelGGL((bk_dw_bwd_kernel<S, GEO::KS>), flat(te0), blk, 0, s, K->d1, P + GEO::O_WD, K->d2, te0);
+    else
+        hipLaunchKernelGGL((bk_dws_bwd_kernel<S, GEO::KS, GEO::PAD>), flat(te0), blk, 0, s, K->d1, P + GEO::O_WD, K->d2, te0);
     // BN0, expand
-    Grad0 g0{bn_consts(K, P, 0, m, true), K->ze, K->d2};
-    bn_backward_statistics(K, 0, g0, m, s);
-    hipLaunchKernelGGL((wgrad_kernel<BK_JE, false, Grad0>), dim3(BK_EXP / 16 * (BK_IN / (16 * BK_JE)) / 4, wch), blk, 0, s, g0, K->x, nullptr,
-                       K->wpart, m, BK_EXP, BK_IN, BK_HW);
-    hipLaunchKernelGGL(wreduce_kernel, flat((size_t)BK_EXP * BK_IN), blk, 0, s, K->wpart, wch, BK_EXP * BK_IN, G + GEO::O_WE);
-    if (dx_below) {                                             // dOut of the block below: 192 columns, reduction over 1152
-        const dim3 grid(BK_IN / (16 * BK_JE), (m + 15) / 16);
-        if constexpr (GEO::SKIP)                                // the skip path K->dx (another buffer than dx_below) + the branch
-            hipLaunchKernelGGL((gemm_dyw_kernel<BK_JE, Grad0, true>), grid, blk, 0, s, g0, P + GEO::O_WE, dx_below, m, BK_EXP, BK_IN, K->dx);
-        else
-            hipLaunchKernelGGL((gemm_dyw_kernel<BK_JE, Grad0>), grid, blk, 0, s, g0, P + GEO::O_WE, dx_below, m, BK_EXP, BK_IN, nullptr);
+    G0 g0{bn_consts(K, P, 0, m0, true), K->ze, K->d2};
+    bn_backward_statistics(K, 0, g0, m0, s);
+    hipLaunchKernelGGL((wgrad_kernel<GEO::JW, false, G0, GEO::WE_GUARD>), dim3((GEO::WE_WAVES + 3) / 4, wch0), blk, 0, s, g0, K->x, nullptr,
+                       K->wpart, m0, GEO::EXP, GEO::IN, GEO::HW_IN);
+    hipLaunchKernelGGL(wreduce_kernel, flat((size_t)GEO::EXP * GEO::IN), blk, 0, s, K->wpart, wch0, GEO::EXP * GEO::IN, G + GEO::O_WE);
+    if constexpr (GEO::STRIDE == 1) {
+        if (dx_below) {                                         // dOut of the block below: IN columns, reduction over EXP
+            const dim3 grid(GEO::IN / (16 * GEO::JE), (m0 + 15) / 16);
+            if constexpr (GEO::SKIP)                            // the skip path K->dx (another buffer than dx_below) + the branch
+                hipLaunchKernelGGL((gemm_dyw_kernel<GEO::JE, G0, true>), grid, blk, 0, s, g0, P + GEO::O_WE, dx_below, m0, GEO::EXP, GEO::IN, K->dx);
+            else
+                hipLaunchKernelGGL((gemm_dyw_kernel<GEO::JE, G0>), grid, blk, 0, s, g0, P + GEO::O_WE, dx_below, m0, GEO::EXP, GEO::IN, nullptr);
+        }
+    } else if (dx_below) {                                      // block 11 forms no dX: block 10 is frozen
+        return fail(h, DFD_ERR_STATE, "block %d hands no gradient down", K->L.index);
     }
     DFD_HIP_TRY(h, hipGetLastError());
     return DFD_OK;
@@ -726,19 +897,21 @@ int create_stage(dfd_handle* h, HeadTrainState* S, const char* who, const Layout
     K->L = L;
     K->momentum = bn_momentum;
     K->eps = bn_eps == 1e-3f ? 1e-3 : (double)bn_eps;          // the backbone's eps (weights._fold's double), not its float neighbour
-    const size_t mn = (size_t)S->max_n, mm = mn * BK_HW, sch = (size_t)stat_chunks((int)mm), wch = (size_t)wg_chunks((int)mm),
+    // mm0 rows in front of the depthwise conv (x, Ze, ae, dae), mm1 after it; the chunked partials are sized by the larger
+    const size_t BK_IN = (size_t)L.in, BK_EXP = (size_t)L.exp, BK_SE = (size_t)L.se;
+    const size_t mn = (size_t)S->max_n, mm0 = mn * L.hw_in, mm1 = mn * L.hw, sch = (size_t)stat_chunks((int)mm0),
                  dch = (mn + BK_DW_CROPS - 1) / BK_DW_CROPS, cnt = (size_t)L.count, out = (size_t)L.out,
-                 wmax = std::max(out * BK_EXP, (size_t)BK_EXP * BK_IN);
+                 wmax = std::max((size_t)wg_chunks((int)mm1) * out * BK_EXP, (size_t)wg_chunks((int)mm0) * BK_EXP * BK_IN);
     struct Slot { void** p; size_t bytes; };
     std::vector<Slot> slots = {
         {(void**)&K->param, cnt * 4}, {(void**)&K->grad, cnt * 4}, {(void**)&K->m, cnt * 4},
         {(void**)&K->v, cnt * 4},     {(void**)&K->ema, cnt * 4},
-        {(void**)&K->x, mm * BK_IN * 4},   {(void**)&K->ze, mm * BK_EXP * 4}, {(void**)&K->ae, mm * BK_EXP * 4},
-        {(void**)&K->zd, mm * BK_EXP * 4}, {(void**)&K->ad, mm * BK_EXP * 4}, {(void**)&K->d1, mm * BK_EXP * 4},
-        {(void**)&K->d2, mm * BK_EXP * 4}, {(void**)&K->zp, mm * out * 4}, {(void**)&K->dx, mm * out * 4},
+        {(void**)&K->x, mm0 * BK_IN * 4},   {(void**)&K->ze, mm0 * BK_EXP * 4}, {(void**)&K->ae, mm0 * BK_EXP * 4},
+        {(void**)&K->zd, mm1 * BK_EXP * 4}, {(void**)&K->ad, mm1 * BK_EXP * 4}, {(void**)&K->d1, mm1 * BK_EXP * 4},
+        {(void**)&K->d2, mm0 * BK_EXP * 4}, {(void**)&K->zp, mm1 * out * 4}, {(void**)&K->dx, mm1 * out * 4},
         {(void**)&K->pooled, mn * BK_EXP * 4}, {(void**)&K->gate, mn * BK_EXP * 4},
         {(void**)&K->spart, sch * BK_EXP * 8}, {(void**)&K->spart2, sch * BK_EXP * 8},
-        {(void**)&K->wpart, wch * wmax * 8}, {(void**)&K->dwpart, dch * L.taps * BK_EXP * 8},
+        {(void**)&K->wpart, wmax * 8}, {(void**)&K->dwpart, dch * L.taps * BK_EXP * 8},
         {(void**)&K->partial, NORM_BLOCKS * 8},
         {(void**)&K->r, mn * BK_SE * 8}, {(void**)&K->q, mn * BK_SE * 8}, {(void**)&K->du, mn * BK_EXP * 8},
         {(void**)&K->dr, mn * BK_SE * 8}, {(void**)&K->ds, mn * BK_EXP * 8},
@@ -754,9 +927,9 @@ int create_stage(dfd_handle* h, HeadTrainState* S, const char* who, const Layout
     }
     if (L.skip) {
         slots.push_back({(void**)&K->keep, mn * 4});
-        slots.push_back({(void**)&K->norm, 4});
         K->keep_host.assign(mn, 0.f);
     }
+    if (L.index != BK_LAST) slots.push_back({(void**)&K->norm, 4});          // block 15's launch writes the trainer's own scalar
     size_t total = 0;
     for (const Slot& sl : slots) total += (sl.bytes + 255) / 256 * 256;
     if (hipMalloc(&K->pool, total) != hipSuccess) {
@@ -812,14 +985,14 @@ int stage_grads(dfd_handle* h, HeadBlockState* K, dfd_mbconv_params* io, int set
     return DFD_OK;
 }
 
-// the stage of `block` (12 .. 15) for the _at entries
+// the stage of `block` (11 .. 15) for the _at entries
 HeadBlockState* stage_at(dfd_handle* h, HeadTrainState* S, const char* who, int block, int* rc) {
     if (block < BK_FIRST || block > BK_LAST) {
         *rc = fail(h, DFD_ERR_UNSUPPORTED, "%s: block %d; %d .. %d", who, block, BK_FIRST, BK_LAST);
         return nullptr;
     }
     HeadBlockState* K = stage_of(S, block);
-    if (!K)                                                     // 13 and 12 frozen: not served, as before they could be unfrozen
+    if (!K)                                                     // 13, 12 and 11 frozen: not served, as before they could be unfrozen
         *rc = fail(h, block < 14 ? DFD_ERR_UNSUPPORTED : DFD_ERR_ARG, "%s: block %d is not unfrozen (%s)", who, block, unfreeze_entry(block));
     return K;
 }
@@ -854,7 +1027,7 @@ int dfd_head_train_unfreeze_block_at(dfd_handle* h, int block, const dfd_mbconv_
                     BK_FIRST, BK_LAST - 1);
     const int k = BK_LAST - block;
     if (S->stage[k]) return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: block %d is already unfrozen", block);
-    if (!S->stage[k - 1])                                       // the blocks come from the top down: 15, 14, 13, 12
+    if (!S->stage[k - 1])                                       // the blocks come from the top down: 15, 14, 13, 12, 11
         return k == 1 ? fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: block 15 comes first (dfd_head_train_unfreeze_block)")
                       : fail(h, DFD_ERR_UNSUPPORTED, "head_train_unfreeze_block_at: block %d cannot be unfrozen while block %d is frozen", block,
                              block + 1);
@@ -864,8 +1037,11 @@ int dfd_head_train_unfreeze_block_at(dfd_handle* h, int block, const dfd_mbconv_
         return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: bn_momentum %g or bn_eps %g out of range", (double)bn_momentum, (double)bn_eps);
     if (!(drop_connect >= 0.f && drop_connect < 1.f))
         return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: drop_connect %g outside [0, 1)", (double)drop_connect);
+    if (block == BK_STRIDED && drop_connect != 0.f)
+        return fail(h, DFD_ERR_ARG, "head_train_unfreeze_block_at: drop_connect %g for block %d, which has no skip; 0", (double)drop_connect, block);
     DFD_HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = create_stage(h, S, "head_train_unfreeze_block_at", layout_of<G14>(block), init, bn_momentum, bn_eps, &S->stage[k]))) return rc;
+    const Layout L = block == BK_STRIDED ? layout_of<G11>(block) : layout_of<G14>(block);
+    if ((rc = create_stage(h, S, "head_train_unfreeze_block_at", L, init, bn_momentum, bn_eps, &S->stage[k]))) return rc;
     HeadBlockState* K = S->stage[k];
     K->drop_p = (double)drop_connect;                           // the double of the float32 argument, as the head's dropout rates
     K->keep_prob = 1.0 - K->drop_p;
@@ -887,18 +1063,20 @@ int dfd_head_train_accumulate_block(dfd_handle* h, const float* rows, int n, con
     HeadBlockState** T = S->stage;
     HeadBlockState* K = T[0];
     hipStream_t s = h->stream;
-    const int deep = deepest(S);
-    // the rows are the input of the deepest unfrozen block; every skip block writes into the input of the block above it
-    DFD_HIP_TRY(h, hipMemcpyAsync(T[deep]->x, rows, (size_t)n * BK_ROW * 4, hipMemcpyHostToDevice, s));
-    for (int k = deep; k >= 1; --k) {
+    const int deep = deepest(S), skips = std::min(deep, K11 - 1);            // stages 1 .. skips are the skip blocks 14 .. 12
+    // the rows are the input of the deepest unfrozen block; every block below block 15 writes into the input of the block above it
+    DFD_HIP_TRY(h, hipMemcpyAsync(T[deep]->x, rows, (size_t)n * row_floats(T[deep]) * 4, hipMemcpyHostToDevice, s));
+    if (deep == K11 && (rc = block_forward<G11>(h, T[K11], T[K11]->param, n, true, T[K11 - 1]->x, false))) return rc;
+    for (int k = skips; k >= 1; --k) {
         if ((rc = draw_keep(h, S, T[k], n))) return rc;
         if ((rc = block_forward<G14>(h, T[k], T[k]->param, n, true, T[k - 1]->x, true))) return rc;
     }
     if ((rc = block_forward<G15>(h, K, K->param, n, true, headconv_rows(S), false))) return rc;
     if ((rc = headconv_step(h, S, n, labels_a, labels_b, lam, loss_scale, K->dx))) return rc;
     if ((rc = block_backward<G15>(h, K, n, deep >= 1 ? T[1]->dx : nullptr))) return rc;
-    for (int k = 1; k <= deep; ++k)                             // the deepest block hands nothing down: the block below it is frozen
+    for (int k = 1; k <= skips; ++k)                            // the deepest block hands nothing down: the block below it is frozen
         if ((rc = block_backward<G14>(h, T[k], n, k < deep ? T[k + 1]->dx : nullptr))) return rc;
+    if (deep == K11 && (rc = block_backward<G11>(h, T[K11], n, nullptr))) return rc;
     DFD_HIP_TRY(h, hipMemcpyAsync(loss_out, S->scalars, 4, hipMemcpyDeviceToHost, s));
     if (logits_out) DFD_HIP_TRY(h, hipMemcpyAsync(logits_out, S->logits, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     DFD_HIP_TRY(h, stream_sync(h));
@@ -916,9 +1094,10 @@ int dfd_head_train_eval_block(dfd_handle* h, const float* rows, int n, int use_e
     DFD_HIP_TRY(h, hipSetDevice(h->device));
     HeadBlockState** T = S->stage;
     HeadBlockState* K = T[0];
-    const int deep = deepest(S);
-    DFD_HIP_TRY(h, hipMemcpyAsync(T[deep]->x, rows, (size_t)n * BK_ROW * 4, hipMemcpyHostToDevice, h->stream));
-    for (int k = deep; k >= 1; --k)                             // no drop-connect
+    const int deep = deepest(S), skips = std::min(deep, K11 - 1);
+    DFD_HIP_TRY(h, hipMemcpyAsync(T[deep]->x, rows, (size_t)n * row_floats(T[deep]) * 4, hipMemcpyHostToDevice, h->stream));
+    if (deep == K11 && (rc = block_forward<G11>(h, T[K11], use_ema ? T[K11]->ema : T[K11]->param, n, false, T[K11 - 1]->x, false))) return rc;
+    for (int k = skips; k >= 1; --k)                            // no drop-connect
         if ((rc = block_forward<G14>(h, T[k], use_ema ? T[k]->ema : T[k]->param, n, false, T[k - 1]->x, false))) return rc;
     if ((rc = block_forward<G15>(h, K, use_ema ? K->ema : K->param, n, false, headconv_rows(S), false))) return rc;
     if ((rc = headconv_eval_step(h, S, use_ema, n))) return rc;

@@ -155,11 +155,17 @@ __global__ __launch_bounds__(HT_THREADS) void gemm_dyw_kernel(G g, const float* 
 // ---------------------------------------------------------------------------------------------- weight gradient
 // P [chunk][NO][NI] = dZ^T . B over rows [512 chunk, 512 (chunk + 1)) n [0, m), in double; B = X or (GATED) X * gate.
 // grid (NO / 16 * NI / (16 J) / 4, chunks): wave w owns channels 16 (w / (NI / 16 J)) .. + 16 and inputs 16 J (w % ..) .. + 16 J.
-template <int J, bool GATED, class G>
+// GUARD: the instance for a wave count that is no multiple of 4 (672 x 112 at J = 7: 42 waves), grid ceil(waves / 4); a
+// wave whose tile lies past channel NO returns before any load or store (wave-uniform; the kernel has no barrier).  The
+// instances without it keep their instruction stream.
+template <int J, bool GATED, class G, bool GUARD = false>
 __global__ __launch_bounds__(HT_THREADS) void wgrad_kernel(G g, const float* __restrict__ X, const float* __restrict__ gate,
                                                            double* __restrict__ P, int m, int NO, int NI, int hw) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r16 = lane & 15, q = lane >> 4;
     const int groups = NI / (16 * J), gw = blockIdx.x * 4 + wv, o0 = (gw / groups) * 16, i0 = (gw % groups) * (16 * J);
+    if constexpr (GUARD) {
+        if (o0 >= NO) return;
+    }
     const int r0 = blockIdx.y * WG_ROWS, r1 = min(m, r0 + WG_ROWS);
     const int c = o0 + r16;
     const typename G::K k = g.load(c);
@@ -203,21 +209,29 @@ static __global__ __launch_bounds__(HT_THREADS) void wreduce_kernel(const double
 // Partial sums over rows [256 chunk, 256 (chunk + 1)) n [0, m): grid (C / 64, chunks).  Thread (col, g) adds rows g, g + 4, ..
 // of its column in double, then the 4 row groups are added in order.
 //   MODE 0: sum z      MODE 1: sum (z - mean)^2      MODE 2: sum dy -> part, sum dy xhat -> part2 (gradient source G)
+// GUARD: the instance for a C that is no multiple of 64 (672 = 10.5 x 64), grid (ceil(C / 64), chunks): a thread whose
+// column lies past C loads and stores nothing but still meets the barrier (a wave is 64 columns of one row group, so the
+// last block's waves are half past the end: the guard is per lane).  The instances without it keep their instruction stream.
 struct NoGrad {
     typedef BnK K;
     __device__ __forceinline__ K load(int) const { return K{}; }
     __device__ __forceinline__ void dy_xh(const K&, size_t, int, double* dy, double* xh) const { *dy = 0.0; *xh = 0.0; }
 };
-template <int MODE, class G>
+template <int MODE, class G, bool GUARD = false>
 __global__ __launch_bounds__(HT_THREADS) void colstat_kernel(G g, const float* __restrict__ Z, const double* __restrict__ mean,
                                                              double* __restrict__ part, double* __restrict__ part2, int m, int C) {
     __shared__ double red[2][4][64];
     const int cl = threadIdx.x & 63, gr = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
-    const int r0 = blockIdx.y * STAT_ROWS, r1 = min(m, r0 + STAT_ROWS);
+    const bool live = !GUARD || c < C;
+    const int r0 = blockIdx.y * STAT_ROWS, r1 = live ? min(m, r0 + STAT_ROWS) : r0;
     double mu = 0.0;
-    if constexpr (MODE == 1) mu = mean[c];
+    if constexpr (MODE == 1) {
+        if (live) mu = mean[c];
+    }
     typename G::K k{};
-    if constexpr (MODE == 2) k = g.load(c);
+    if constexpr (MODE == 2) {
+        if (live) k = g.load(c);
+    }
     double s0 = 0.0, s1 = 0.0;
     for (int r = r0 + gr; r < r1; r += 4) {
         if constexpr (MODE == 0) s0 += (double)Z[(size_t)r * C + c];
@@ -232,7 +246,7 @@ __global__ __launch_bounds__(HT_THREADS) void colstat_kernel(G g, const float* _
     red[0][gr][cl] = s0;
     red[1][gr][cl] = s1;
     __syncthreads();
-    if (gr == 0) {
+    if (gr == 0 && live) {
         part[(size_t)blockIdx.y * C + c] = ((red[0][0][cl] + red[0][1][cl]) + red[0][2][cl]) + red[0][3][cl];
         if constexpr (MODE == 2) part2[(size_t)blockIdx.y * C + c] = ((red[1][0][cl] + red[1][1][cl]) + red[1][2][cl]) + red[1][3][cl];
     }

@@ -2,7 +2,7 @@
 // the host entry points each file offers the other.  The conv stage (dfd_head_train_unfreeze_conv) hangs off the head
 // trainer's state; everything from the pooled features on runs in head_train.hip's kernels.  Block 15
 // (dfd_head_train_unfreeze_block, head_train_block.hip) hangs off it in turn and feeds the conv stage on the device;
-// blocks 14, 13 and 12 (dfd_head_train_unfreeze_block_at, the same file) each feed the block above them.
+// blocks 14, 13, 12 and 11 (dfd_head_train_unfreeze_block_at, the same file) each feed the block above them.
 #pragma once
 #include <cstdint>
 
@@ -17,13 +17,13 @@ constexpr int O_W2 = O_BE1 + HT_H1, O_B2 = O_W2 + HT_H2 * HT_H1, O_G2 = O_B2 + H
 constexpr int O_W3 = O_BE2 + HT_H2, O_B3 = O_W3 + HT_H2, HT_COUNT = O_B3 + 1;
 static_assert(O_W2 % 4 == 0 && O_W3 % 4 == 0, "weight rows must stay 16-byte aligned");
 constexpr int NORM_BLOCKS = 256;
-constexpr int HT_STAGES = 4;              // block stages a trainer can hold: _blocks.15 down to _blocks.12
+constexpr int HT_STAGES = 5;              // block stages a trainer can hold: _blocks.15 down to _blocks.11
 constexpr int HT_ARENAS = 2 + HT_STAGES;  // head, conv, then the block stages
 
 struct HeadConvState;   // head_train_conv.hip: _conv_head + _bn1 under training (null until dfd_head_train_unfreeze_conv)
 struct HeadBlockState;  // head_train_block.hip: one MBConv block under training
 
-// The partial sums of squares of every arena, in the order head, conv, block 15, 14, 13, 12 (null: no such stage).  Each
+// The partial sums of squares of every arena, in the order head, conv, block 15, 14, 13, 12, 11 (null: no such stage).  Each
 // AdamW launch adds them entry by entry in this order before it takes the norm, so all see the same norm.
 struct NormParts { const double* p[HT_ARENAS]; };
 
@@ -45,7 +45,7 @@ struct HeadTrainState {
     HeadConvState* conv = nullptr;
     // stage[k] = _blocks.(15 - k), deepest last: stage[0] null until dfd_head_train_unfreeze_block, the others until
     // dfd_head_train_unfreeze_block_at; stage[k] is only ever set when stage[k - 1] is
-    HeadBlockState* stage[HT_STAGES] = {nullptr, nullptr, nullptr, nullptr};
+    HeadBlockState* stage[HT_STAGES] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
 // The trainer's counter-based hash: head_training.dropout_keep_mask is the specification of these three.  layer 0..2 are
@@ -106,7 +106,7 @@ void headblock_destroy(HeadTrainState* S);                                   // 
 const double* headblock_sumsq(dfd_handle* h, HeadTrainState* S, int k);      // launches; -> the stage arena's partials
 const double* headblock_partial(HeadTrainState* S, int k);
 void headblock_adamw(dfd_handle* h, HeadTrainState* S, double lr, double t);  // the block groups' steps at lr * the conv stage's lr_scale
-int headblock_commit(dfd_handle* h, HeadTrainState* S, int use_ema);          // block 15, then 14, 13, 12 where they are unfrozen
-int headblock_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out, size_t capacity);  // "b15.*" .. "b12.*"
+int headblock_commit(dfd_handle* h, HeadTrainState* S, int use_ema);          // block 15, then 14, 13, 12, 11 where they are unfrozen
+int headblock_tap(dfd_handle* h, HeadTrainState* S, const char* name, float* out, size_t capacity);  // "b15.*" .. "b11.*"
 
 }  // namespace dfd

@@ -738,7 +738,8 @@ int dfd_train_augment_tap(dfd_handle* h, const unsigned char* rgb_host, int n, i
 
 // the chain at 224 on all n images, then the backbone in chunks of max_batch: pooled rows, or (trunk) block 15's output, or
 // (trunk, block = 14) block 14's, or (first_block = 13: dfd_train_augment_block_out) block 13's, or (first_block = 11:
-// dfd_train_augment_block_input, which checks its own range) block 11's or 12's
+// dfd_train_augment_block_input, which checks its own range) block 11's or 12's, or (first_block = 10:
+// dfd_train_augment_block_rows, likewise) block 10's, [14][14][112] a crop
 static int augment_forward(dfd_handle* h, const char* who, const unsigned char* rgb, int on_device, int n, int H, int W,
                            const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, float* out_host, bool trunk,
                            int block = 15, int first_block = 14) {
@@ -762,7 +763,8 @@ static int augment_forward(dfd_handle* h, const char* who, const unsigned char* 
             in = h->in_nchw;
         }
         if (trunk) {
-            if ((rc = b0_trunk_to_host(h, in, m, out_host + (size_t)first * (block == 15 ? DFD_TRUNK_ROW : DFD_BLOCK14_ROW), block))) return rc;
+            const size_t row = block == 15 ? DFD_TRUNK_ROW : block == 10 ? DFD_BLOCK11_INPUT_ROW : DFD_BLOCK14_ROW;
+            if ((rc = b0_trunk_to_host(h, in, m, out_host + (size_t)first * row, block))) return rc;
             continue;
         }
         rc = b0_forward(h, in, m, nullptr, nullptr, nullptr);
@@ -800,6 +802,14 @@ int dfd_train_augment_block_input(dfd_handle* h, const unsigned char* rgb, int o
     if (block < 12 || block > 15) return fail(h, DFD_ERR_ARG, "train_augment_block_input: block %d; 12, 13, 14 or 15", block);
     // a block's input is the output of the block below it: [7][7][192] for all four
     return augment_forward(h, "train_augment_block_input", rgb, on_device, n, H, W, rows, batch, out_host, true, block - 1, 11);
+}
+
+int dfd_train_augment_block_rows(dfd_handle* h, const unsigned char* rgb, int on_device, int n, int H, int W,
+                                 const dfd_train_aug_image* rows, const dfd_train_aug_batch* batch, int block, float* out_host) {
+    if (!h) return DFD_ERR_ARG;
+    if (block < 11 || block > 15) return fail(h, DFD_ERR_ARG, "train_augment_block_rows: block %d; 11, 12, 13, 14 or 15", block);
+    // dfd_train_augment_block_input with block 11 as well: its rows are block 10's output, [14][14][112]
+    return augment_forward(h, "train_augment_block_rows", rgb, on_device, n, H, W, rows, batch, out_host, true, block - 1, 10);
 }
 
 }  // extern "C"

@@ -15,7 +15,9 @@ adds the backbone's last block, ``net._blocks.15`` (csrc/head_train_block.hip): 
 below it (the identity skip with per-crop drop-connect): the rows are then block 13's output, the same shape.
 `train_block13=True` and `train_block12=True` add ``net._blocks.13`` and ``net._blocks.12`` (block 14's geometry, each with
 its own drop-connect rate and mask): the rows are the input rows of the deepest unfrozen block.  After them every 7 x 7
-block of train.py's unfrozen group trains; its 14 x 14 blocks 11 down to 9 stay frozen.
+block of train.py's unfrozen group trains.  `train_block11=True` adds ``net._blocks.11``, the stride-2 block that takes the
+14 x 14 maps to 7 x 7 (112 -> 672 -> 192, no skip, no drop-connect): the rows are then block 10's output, (n, 14, 14, 112).
+The 14 x 14 skip blocks 10 and 9 stay frozen.
 """
 from __future__ import annotations
 
@@ -72,6 +74,12 @@ BLOCK13_SD_SHAPES = dict(BLOCK14_SD_SHAPES)
 BLOCK12_SD_SHAPES = dict(BLOCK14_SD_SHAPES)
 DROP_CONNECT_BLOCK13 = 0.2 * 13 / 16
 DROP_CONNECT_BLOCK12 = 0.2 * 12 / 16
+# block 11 (train_block11=True): the same fields in block 11's shapes (`_lib.BLOCK11_SHAPES`); no skip, no drop-connect
+BLOCK11_PREFIX = "net._blocks.11."
+BLOCK11_KEYS = {BLOCK11_PREFIX + k[len(BLOCK_PREFIX):]: f for k, f in BLOCK_KEYS.items()}
+BLOCK11_TRACKED = tuple(k for k, f in BLOCK11_KEYS.items() if f.startswith("nbt"))
+BLOCK11_SD_SHAPES = {"exp_w": (672, 112, 1, 1), "dw_w": (672, 1, 5, 5), "se_w1": (28, 672, 1, 1), "se_w2": (672, 28, 1, 1),
+                     "proj_w": (192, 672, 1, 1)}
 # the skip blocks a trainer can hold, top down: (block, keys, tracked keys, state-dict shapes)
 _SKIP_BLOCKS = ((14, BLOCK14_KEYS, BLOCK14_TRACKED, BLOCK14_SD_SHAPES), (13, BLOCK13_KEYS, BLOCK13_TRACKED, BLOCK13_SD_SHAPES),
                 (12, BLOCK12_KEYS, BLOCK12_TRACKED, BLOCK12_SD_SHAPES))
@@ -201,7 +209,8 @@ def fit_loop(trainer, features, labels, epochs: int, batch_size: int = 32, grad_
     row; default 1280) and `extract_method` (the extractor call `augment=` uses; default "train_augment_features"): a
     trainer with the conv stage takes trunk rows of 15680 floats from "train_augment_trunk", one with block 15 rows of 9408
     floats from "train_augment_block14" (with block 14: "train_augment_block13"; with block 13 or 12: "train_augment_input13" /
-    "train_augment_input12", `Handle.train_augment_block_input` at the deepest block), and feature-space Mixup then acts on those rows.  Returns a log shaped like
+    "train_augment_input12", `Handle.train_augment_block_input` at the deepest block; with block 11 rows of 21952 floats from
+    "train_augment_rows11", `Handle.train_augment_block_rows(block=11)`), and feature-space Mixup then acts on those rows.  Returns a log shaped like
     weights/training_log.json: one dict per epoch (epoch, train_loss, train_acc, val_loss, val_acc, val_f1, val_auc,
     lr, time_seconds).
 
@@ -252,7 +261,7 @@ def fit_loop(trainer, features, labels, epochs: int, batch_size: int = 32, grad_
         x = np.ascontiguousarray(np.asarray(features, np.float32))
         if width != 1280 and x.ndim > 2:
             x = x.reshape(x.shape[0], -1)                          # (N, 7, 7, 320) trunk rows
-        if x.ndim != 2 or (width != 1280 and x.shape[1] != width):
+        if x.ndim != 2 or (width != 1280 and x.shape[1] != width):   # (N, 14, 14, 112) rows of block 10 were flattened above
             raise ValueError(f"features (N, {width}) and one label per row")
     y = np.asarray(labels, np.float32).reshape(-1)
     if x.shape[0] != y.size:
@@ -355,6 +364,10 @@ class HeadTrainer:
     deepest unfrozen block - `Handle.extract_block_input(x, 13 or 12)`'s (n, 7, 7, 192) or (n, 9408) - and `commit` /
     `export_state_dict` cover all five or six groups.
 
+    `train_block11=True` (implies `train_block12`) also trains ``net._blocks.11`` (MBConv k5 at stride 2, 112 -> 672 -> 192,
+    no skip and so no drop-connect): the rows are then block 10's output - `Handle.extract_block_rows(x, 11)`'s
+    (n, 14, 14, 112) or (n, 21952) - and `commit` / `export_state_dict` cover all seven groups.
+
     `model_or_handle`: a `DeepfakeEfficientNet` (its handle and state dict are used) or a `_lib.Handle` with
     `state_dict` (reference key names, at least the ten ``net._fc.*`` tensors and the four running statistics).
     `config`: fields of `dfd_head_config` - max_n, seed, dropout, beta1, beta2, eps, weight_decay, focal_gamma,
@@ -367,7 +380,8 @@ class HeadTrainer:
     def __init__(self, model_or_handle, state_dict: Optional[Mapping[str, np.ndarray]] = None, train_conv_head: bool = False,
                  backbone_lr_scale: float = 0.1, train_block15: bool = False, train_block14: bool = False,
                  drop_connect: float = DROP_CONNECT_BLOCK14, train_block13: bool = False, train_block12: bool = False,
-                 drop_connect13: float = DROP_CONNECT_BLOCK13, drop_connect12: float = DROP_CONNECT_BLOCK12, **config):
+                 drop_connect13: float = DROP_CONNECT_BLOCK13, drop_connect12: float = DROP_CONNECT_BLOCK12,
+                 train_block11: bool = False, **config):
         if isinstance(model_or_handle, _lib.Handle):
             handle = model_or_handle
             if state_dict is None:
@@ -380,13 +394,15 @@ class HeadTrainer:
         params = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
                   for k, f in KEYS.items()}
         self._tracked = [int(np.asarray(sd[k])) if k in sd else 0 for k in TRACKED]
-        self.train_block12 = bool(train_block12)
+        self.train_block11 = bool(train_block11)
+        self.train_block12 = bool(train_block12) or self.train_block11
         self.train_block13 = bool(train_block13) or self.train_block12
         self.train_block14 = bool(train_block14) or self.train_block13
         self.train_block15 = bool(train_block15) or self.train_block14
         self.train_conv_head = bool(train_conv_head) or self.train_block15
-        self.row_width = _lib.BLOCK14_ROW if self.train_block15 else _lib.TRUNK_ROW if self.train_conv_head else 1280
-        self.extract_method = ("train_augment_input12" if self.train_block12 else "train_augment_input13" if self.train_block13 else
+        self.row_width = (_lib.BLOCK11_INPUT_ROW if self.train_block11 else _lib.BLOCK14_ROW if self.train_block15 else
+                          _lib.TRUNK_ROW if self.train_conv_head else 1280)
+        self.extract_method = ("train_augment_rows11" if self.train_block11 else "train_augment_input12" if self.train_block12 else "train_augment_input13" if self.train_block13 else
                                "train_augment_block13" if self.train_block14 else "train_augment_block14" if self.train_block15 else
                                "train_augment_trunk" if self.train_conv_head else "train_augment_features")
         if self.train_block15:
@@ -404,6 +420,10 @@ class HeadTrainer:
             self._skip_tracked[b] = [int(np.asarray(sd[k])) if k in sd else 0 for k in tracked]
         if self.train_block14:
             self._block14_tracked = self._skip_tracked[14]
+        if self.train_block11:
+            block11 = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
+                       for k, f in BLOCK11_KEYS.items() if not f.startswith("nbt")}
+            self._block11_tracked = [int(np.asarray(sd[k])) if k in sd else 0 for k in BLOCK11_TRACKED]
         if self.train_conv_head:
             conv = {f: np.asarray(sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else sd[k], np.float32)
                     for k, f in CONV_KEYS.items()}
@@ -430,6 +450,12 @@ class HeadTrainer:
         for b, _keys, _tracked, _shapes, rate in self._skip_blocks:
             try:
                 handle.head_train_unfreeze_block_at(skip_params[b], b, BN_MOMENTUM_BACKBONE, BN_EPS_BACKBONE, rate)
+            except Exception:
+                self.close()
+                raise
+        if self.train_block11:
+            try:
+                handle.head_train_unfreeze_block_at(block11, 11, BN_MOMENTUM_BACKBONE, BN_EPS_BACKBONE, 0.0)
             except Exception:
                 self.close()
                 raise
@@ -476,7 +502,7 @@ class HeadTrainer:
         ones) and the two ``num_batches_tracked`` counters; with the conv stage also ``net._conv_head.weight``
         ((1280, 320, 1, 1)), ``net._bn1.*`` and its counter; with block 15 also the 22 ``net._blocks.15.*`` entries of
         `BLOCK_KEYS` (conv kernels in the state dict's 4-d shapes); with block 14 also the 22 of `BLOCK14_KEYS`, with block 13
-        those of `BLOCK13_KEYS`, with block 12 those of `BLOCK12_KEYS`"""
+        those of `BLOCK13_KEYS`, with block 12 those of `BLOCK12_KEYS`, with block 11 those of `BLOCK11_KEYS`"""
         out = self._h.head_train_export(use_ema)
         sd = {k: out[f] for k, f in KEYS.items()}
         for k, t in zip(TRACKED, self._tracked):
@@ -495,10 +521,15 @@ class HeadTrainer:
             sd.update({k: blk[f].reshape(shapes.get(f, blk[f].shape)) for k, f in keys.items() if f in blk})
             for k, t in zip(tracked, self._skip_tracked[b]):
                 sd[k] = np.array(t + self.accumulates, dtype=np.int64)
+        if self.train_block11:
+            blk = self._h.head_train_export_block_at(11, use_ema)
+            sd.update({k: blk[f].reshape(BLOCK11_SD_SHAPES.get(f, blk[f].shape)) for k, f in BLOCK11_KEYS.items() if f in blk})
+            for k, t in zip(BLOCK11_TRACKED, self._block11_tracked):
+                sd[k] = np.array(t + self.accumulates, dtype=np.int64)
         return sd
 
     def commit(self, use_ema: bool = True):
-        """fold BatchNorm and swap the head (and, with the conv stage, the head conv; with blocks 15 down to 12, their ten tensors each) the
+        """fold BatchNorm and swap the head (and, with the conv stage, the head conv; with blocks 15 down to 11, their ten tensors each) the
         handle classifies with (`dfd_head_train_commit`)"""
         self._h.head_train_commit(use_ema)
 
@@ -510,4 +541,4 @@ class HeadTrainer:
 
 
 __all__ = ["HeadTrainer", "fit_loop", "one_cycle_lr", "dropout_keep_mask", "dropout_rates", "focal_loss", "KEYS", "CONV_KEYS", "BLOCK_KEYS", "BLOCK14_KEYS",
-           "BLOCK13_KEYS", "BLOCK12_KEYS", "drop_connect_keep"]
+           "BLOCK13_KEYS", "BLOCK12_KEYS", "BLOCK11_KEYS", "drop_connect_keep"]

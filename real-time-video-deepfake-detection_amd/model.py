@@ -165,6 +165,11 @@ class DeepfakeEfficientNet:
         trains on"""
         return self._run(rgb_input, lambda a: self.handle.extract_block_input(a, block))
 
+    def extract_block_rows(self, rgb_input, block: int):
+        """`extract_block_input` with block 11 as well, `max_batch` crops at a time (`Handle.extract_block_rows`): (B,14,14,112),
+        block 10's output, for 11 - the rows `fit_head(train_block11=True)` trains on - and (B,7,7,192) for 12..15"""
+        return self._run(rgb_input, lambda a: self.handle.extract_block_rows(a, block))
+
     def forward_with_projection(self, rgb_input, freq_input=None):
         """reference model.py:91-98"""
         return self.forward(rgb_input), None
@@ -172,7 +177,7 @@ class DeepfakeEfficientNet:
     def fit_head(self, images_or_features, labels, *, epochs: int = 20, val=None, commit_ema: bool = True,
                  trainer_config: Optional[Mapping] = None, augment=None, train_conv_head: bool = False,
                  train_block15: bool = False, train_block14: bool = False, train_block13: bool = False,
-                 train_block12: bool = False, **fit_kw):
+                 train_block12: bool = False, train_block11: bool = False, **fit_kw):
         """Train the 1280 -> 512 -> 256 -> 1 head on this engine's own pooled features and swap it in.
 
         `images_or_features`: (N,3,224,224) normalised RGB (features are extracted here, `max_batch` crops at a time) or
@@ -199,9 +204,14 @@ class DeepfakeEfficientNet:
 
         `train_block13=True` (implies `train_block14`) / `train_block12=True` (implies `train_block13`): ``net._blocks.13`` /
         ``net._blocks.12`` are fine-tuned as well, each with the reference's drop-connect rate and its own mask: images go
-        through `extract_block_input` at the deepest block, other arrays are its input rows ((N,7,7,192) or (N,9408))."""
+        through `extract_block_input` at the deepest block, other arrays are its input rows ((N,7,7,192) or (N,9408)).
+
+        `train_block11=True` (implies `train_block12`): ``net._blocks.11``, the stride-2 block below block 12, is fine-tuned as
+        well (no skip, no drop-connect): images go through `extract_block_rows(block=11)`, other arrays are rows of block
+        10's output ((N,14,14,112) or (N,21952)).  Blocks 10 and 9 stay frozen."""
         from .head_training import HeadTrainer
 
+        train_block12 = train_block12 or train_block11
         train_block13 = train_block13 or train_block12
         train_block14 = train_block14 or train_block13
         train_block15 = train_block15 or train_block14
@@ -210,7 +220,9 @@ class DeepfakeEfficientNet:
             a = x.detach().cpu().numpy() if _is_torch(x) else np.asarray(x)
             if train_conv_head or train_block15:
                 if a.ndim == 4 and a.shape[1:] == (3, A.IMAGE_SIZE, A.IMAGE_SIZE):
-                    if train_block13:
+                    if train_block11:
+                        a = self.extract_block_rows(a, 11)
+                    elif train_block13:
                         a = self.extract_block_input(a, 12 if train_block12 else 13)
                     else:
                         a = self.extract_block(a, 13) if train_block14 else self.extract_trunk(a, block=14 if train_block15 else 15)
@@ -232,7 +244,7 @@ class DeepfakeEfficientNet:
             v = None if val is None else (feats(val[0]), np.asarray(val[1], np.float32))
         y = labels.detach().cpu().numpy() if _is_torch(labels) else np.asarray(labels)
         with HeadTrainer(self, train_conv_head=train_conv_head, train_block15=train_block15, train_block14=train_block14,
-                         train_block13=train_block13, train_block12=train_block12, **cfg) as tr:
+                         train_block13=train_block13, train_block12=train_block12, train_block11=train_block11, **cfg) as tr:
             log_ = tr.fit(x, y, epochs, val=v, **fit_kw)
             tr.commit(use_ema=commit_ema)
             self._state.update(tr.export_state_dict(use_ema=commit_ema))
